@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py — images/sec + ms/denoise-step, FLUX.1-dev 1024x1024 50-step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     ... bench.py --gpus N --sequence-parallel [--split-k]      (opt-in: ONE image on all N ranks, strong scaling)
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last timed step
+(--dump-outputs DIR: DIR/image.npy, the u8 image(s) as float32, and DIR/latents.npy, the denoised f32 latents), one JSON line.
+Everything else described below — the profiled pass (roofline, phases, VAE timing), the live PMC traffic passes, the energy
+counters, the image CRC-32s, the secondary legs and the CPU baseline — runs only with --full (the --no-* flags then switch parts off).
 
 A "step" is ONE IMAGE: the full hot path over one batch of synthetic input — 50 denoise
 steps (Flux::forward + Euler update), unpack, VAE decode, u8 post-process — with inputs
@@ -13,12 +18,12 @@ rank generates its own image (weak scaling, no data-path collective); weights ar
 rank 0 and broadcast over RCCL/xGMI, the decoded u8 images are gathered to rank 0 after the
 timed region.
 
-With N = 1 the same run appends short legs under "secondary" (2 images each, own roofline): BASELINE config C3
+With N = 1 a --full run appends short legs under "secondary" (2 images each, own roofline): BASELINE config C3
 (nf4 weights: only the packed codes resident), the headline workload in fp8 mode, the C5 shape (fp8 e4m3 block linears,
 1280x720, batch 2), plus the per-rank compute of single-image sequence parallelism at 8 ranks (loopback exchange, 10 denoise
 steps) — `--no-secondary` skips them.  `python bench.py --gpus N` with N > 1 and no launcher starts its N ranks itself.
 
-One JSON line is printed by rank 0 (contract in the task statement) with two extra objects:
+One JSON line is printed by rank 0; with --full it holds two extra objects:
   roofline     — the dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs / device time from
                  hipEvents on the launch stream, measured in a profiled pass of the same step
                  right after the timed region (the per-phase event pairs serialise phases, so
@@ -165,6 +170,31 @@ def measure_traffic_live(quant_args, denoise_steps=4, timeout=300):
     return int((2 * kib["FETCH_SIZE"] + kib["WRITE_SIZE"]) * 1024), note
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes each array as dirname/<name>.npy in float32 (float64 stays float64).  Above `limit` bytes in all, every array takes a share of
+    it in proportion to its size, as a fixed sample (seed 0, sorted flat indices, saved flat): two builds given the same arguments
+    write the same elements, so their files compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):  # a torch tensor (bf16 has no numpy type: widen on the way)
+            a = a.detach().cpu()
+            a = (a if a.is_floating_point() and a.element_size() == 8 else a.float()).numpy()
+        a = np.asarray(a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > limit:
+            keep = max(1, int(a.size * limit / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -183,6 +213,10 @@ def main():
     ap.add_argument("--sequence-parallel", action="store_true",
                     help="N > 1: all ranks denoise ONE image together (token shards, two all-to-alls per block; strong scaling) instead of one image each")
     ap.add_argument("--split-k", action="store_true", help="with --sequence-parallel: the opt-in latency mode (fmi_flux_set_split_k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: profiled pass, live PMC traffic, energy, image CRCs, secondary legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; at most 64 MB, a seeded sample beyond)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the nf4 (C3) and fp8 (C5 shape) legs appended to the N = 1 line")
     ap.add_argument("--no-profile-pass", action="store_true")
@@ -198,6 +232,10 @@ def main():
                     "the images of an N-GPU run must equal the single-GPU images of the same global samples)")
     ap.add_argument("--as-world", type=int, default=None)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_secondary = args.no_profile_pass = args.no_live_traffic = True
     maybe_self_launch(args, sys.argv[1:])
 
     import numpy as np
@@ -325,11 +363,13 @@ def main():
                 img, img_ids = d.pack_latents(lat)
                 img = spg.gather(model.denoise(spg.shard(img), spg.shard(img_ids), spg.shard(self.txt), spg.shard(self.txt_ids), self.y, self.guidance,
                                                self.timesteps))
+                self.last_latents = img
                 z = d.unpack_latents(img, 16, self.h, self.w, vae.scale_factor(), vae.shift_factor())
                 return d.postprocess_u8(vae.decode(z))
             lat = d.randn_latents(self.B, 16, self.h, self.w, seed=1234, first_sample=(srank + sworld * i) * self.B, device=dev)
             img, img_ids = d.pack_latents(lat)
             img = model.denoise(img, img_ids, self.txt, self.txt_ids, self.y, self.guidance, self.timesteps)
+            self.last_latents = img  # (a reference: what --dump-outputs writes besides the image)
             z = d.unpack_latents(img, 16, self.h, self.w, vae.scale_factor(), vae.shift_factor())
             return d.postprocess_u8(vae.decode(z))
 
@@ -389,14 +429,14 @@ def main():
     for i in range(args.warmup):
         u8 = one_image(i)
     barrier()
-    e_start = energy_uj() if rank == 0 else None
+    e_start = energy_uj() if rank == 0 and args.full else None
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
         u8 = one_image(args.warmup + i)
     barrier()
     elapsed = time.perf_counter() - t0
-    e_end = energy_uj() if rank == 0 else None
+    e_end = energy_uj() if rank == 0 and args.full else None
     per_rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -416,10 +456,12 @@ def main():
         gather_ms = (time.perf_counter() - tg) * 1e3
         if rank == 0:
             assert gathered.shape[0] == world * B
+    if rank == 0 and args.dump_outputs:  # what the last timed step computed: the image(s) rank 0 holds, and its denoised latents
+        dump_outputs(args.dump_outputs, {"image": gathered if world > 1 and spg is None else u8, "latents": wl.last_latents})
     # CRC-32 of the last image of every rank (rank order; after the gather for N > 1): lets a test check that an image does not depend
     # on how many GPUs the job ran on (tests/test_gpu_multi_device.py)
     image_crc = None
-    if rank == 0 and spg is None:
+    if rank == 0 and spg is None and args.full:
         import zlib
         imgs = gathered if world > 1 else u8
         image_crc = [zlib.crc32(imgs[j].contiguous().cpu().numpy().tobytes()) for j in range(imgs.shape[0])]
@@ -617,16 +659,11 @@ def main():
         if secondary is not None:
             out["secondary"] = secondary
         out.update(extra)
-        # The GPU figures are complete here.  They go to stderr (and to gpurun_out/bench_gpu_line.json when that directory exists) BEFORE the CPU
-        # baseline starts — minutes of host work that can be OOM-killed — and to stdout as THE one JSON line once the baseline has been added.
-        sys.stderr.write("[bench] GPU line (cpu_baseline pending): " + json.dumps(out) + "\n")
-        sys.stderr.flush()
-        try:
-            if os.path.isdir(os.path.join(ROOT, "gpurun_out")):
-                with open(os.path.join(ROOT, "gpurun_out", "bench_gpu_line.json"), "w") as f:
-                    json.dump(out, f)
-        except OSError:
-            pass
+        if world == 1 and not args.no_cpu_baseline:
+            # The GPU figures are complete here.  They go to stderr BEFORE the CPU baseline starts — minutes of host work that can be
+            # OOM-killed — and to stdout as THE one JSON line once the baseline has been added.
+            sys.stderr.write("[bench] GPU line (cpu_baseline pending): " + json.dumps(out) + "\n")
+            sys.stderr.flush()
 
     # ---------------- CPU baseline (rank 0, N=1 only): oracle = port of the reference CPU semantics
     cpu = None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generate tests/golden/c2_trajectory.npz — the HEADLINE config pinned at full size and full length (VERDICT r5 "next" 2).
+"""Generate tests/golden/c2_trajectory.npz (committed as the pieces .npz.00, .01, ...: tests/util.py save_split_npz) — the HEADLINE config pinned at full size and full length (VERDICT r5 "next" 2).
 
 BASELINE configs[1]: FLUX.1-dev, D = 3072, 19 + 38 blocks, 1024 x 1024 (S = 4096 image tokens) + T = 512 text tokens, guidance 3.5,
 the real 50-step dynamic-shift schedule: `Sampler::sample` (pipelines/sampling.rs:25-48) around the step closure
@@ -31,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import diffusion_rs_amd as d  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
+from tests.util import save_split_npz  # noqa: E402
 
 S_ = d.synth
 MARKS = (10, 25, 50)
@@ -147,9 +148,9 @@ def main():
     meta = dict(config=desc, tag=TAG, latent_hw=[H_LAT, W_LAT], marks=list(MARKS), crcs=crcs,
                 image_crc32=zlib.crc32(u8.tobytes()), oracle_threads=a.threads, total_oracle_s=float(np.sum(step_s)), exact_salt=S_.EXACT_SALT,
                 generator="tests/golden/gen_c2_trajectory_fixture.py")
-    np.savez_compressed(a.out, ts=ts, u8=u8, step_s=np.array(step_s, np.float32), meta=np.frombuffer(json.dumps(meta).encode(), np.uint8),
-                        **{f"lat_{n}": marks[n].astype(np.float32) for n in MARKS})
-    print(f"[gen] wrote {a.out} ({os.path.getsize(a.out) / 2**20:.1f} MiB); oracle time {np.sum(step_s) / 3600:.2f} h", flush=True)
+    size = save_split_npz(a.out, ts=ts, u8=u8, step_s=np.array(step_s, np.float32), meta=np.frombuffer(json.dumps(meta).encode(), np.uint8),
+                          **{f"lat_{n}": marks[n].astype(np.float32) for n in MARKS})
+    print(f"[gen] wrote {a.out}.00, .01, ... ({size / 2**20:.1f} MiB); oracle time {np.sum(step_s) / 3600:.2f} h", flush=True)
 
 
 if __name__ == "__main__":

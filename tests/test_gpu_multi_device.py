@@ -127,7 +127,7 @@ def _bench(extra, env_extra=None, timeout=1500):
         env.pop(k, None)
     env.update(env_extra or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--height", "256", "--width", "256", "--denoise-steps", "3",
-           "--txt-tokens", "64", "--no-cpu-baseline", "--no-secondary", "--no-profile-pass"] + extra
+           "--txt-tokens", "64", "--full", "--no-cpu-baseline", "--no-secondary", "--no-profile-pass"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,6 +2,7 @@
 the C-ABI library loads and exports every declared symbol, and the product fails loudly
 without a GPU (no CPU fallback)."""
 import ctypes as C
+import json
 import math
 import os
 import re
@@ -248,6 +249,48 @@ def test_bench_as_rank_hook_is_validated():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=300,
                            env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
         assert r.returncode != 0 and "--as-rank" in r.stderr, r.stderr[-500:]
+
+
+def test_bench_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one DIR/<name>.npy per array, float32 (float64 kept), whole when the arrays fit the limit;
+    above it a seeded sample of each array in proportion to its size — the same elements on every call, so two builds compare element for element."""
+    import torch
+    import bench
+    img = torch.arange(2 * 3 * 8 * 8, dtype=torch.uint8).reshape(2, 3, 8, 8)
+    lat = torch.linspace(-1, 1, 4 * 64, dtype=torch.bfloat16).reshape(1, 4, 64)
+    f64 = np.linspace(0, 1, 10)
+    bench.dump_outputs(str(tmp_path / "all"), {"image": img, "latents": lat, "x": f64})
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("image", "latents", "x")}
+    assert got["image"].dtype == np.float32 and got["latents"].dtype == np.float32 and got["x"].dtype == np.float64
+    np.testing.assert_array_equal(got["image"], img.numpy().astype(np.float32))
+    np.testing.assert_array_equal(got["latents"], lat.float().numpy())
+    np.testing.assert_array_equal(got["x"], f64)
+    big = np.arange(100_000, dtype=np.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"big": big, "small": big[:1000]}, limit=40_000)
+    a, b = (np.load(tmp_path / r / "big.npy") for r in ("a", "b"))
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert a.nbytes + small.nbytes <= 40_000 and a.size > 0 and small.size > 0
+    np.testing.assert_array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(big.tolist())  # sorted distinct elements of the array
+    assert bench.DUMP_LIMIT_BYTES == 64 * 2**20
+
+
+def test_golden_files_are_small_and_the_split_fixtures_load():
+    """Every committed fixture stays under 1 MiB; the full-size trajectory fixtures are byte pieces (<tag>_trajectory.npz.00, .01, ...) that
+    tests/util.load_split_npz joins into the .npz that tests/test_gpu_c2_fixture.py reads."""
+    from tests.util import load_split_npz
+    golden = os.path.join(ROOT, "tests", "golden")
+    for name in os.listdir(golden):
+        path = os.path.join(golden, name)
+        assert not os.path.isfile(path) or os.path.getsize(path) < 2**20, name
+    for tag, n_img in (("c2", 4096), ("c5", 3600), ("o2", 4096)):
+        z = load_split_npz(os.path.join(golden, f"{tag}_trajectory.npz"))
+        assert z is not None, tag
+        assert sorted(z.files) == ["lat_10", "lat_25", "lat_50", "meta", "step_s", "ts", "u8"]
+        assert z["lat_50"].shape == (1, n_img, 64) and z["ts"].shape == (51,)
+        meta = json.loads(bytes(z["meta"]).decode())
+        assert meta["marks"] == [10, 25, 50] and zlib.crc32(z["u8"].tobytes()) == meta["image_crc32"]
 
 
 def test_committed_attention_streams_are_what_their_generators_emit(tmp_path):

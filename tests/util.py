@@ -1,5 +1,12 @@
 """Shared helpers for the parity tests (oracle = checker, HIP library = thing under test)."""
+import glob
+import io
+import os
+
 import numpy as np
+
+# a committed file stays under 1 MiB: larger .npz fixtures are stored as byte pieces <path>.00, <path>.01, ... of at most this size
+SPLIT_PART_BYTES = 1_000_000
 
 SMALL_FLUX = dict(in_channels=64, pooled_projection_dim=64, joint_attention_dim=128, num_attention_heads=2, num_layers=2,
                   num_single_layers=2, guidance_embeds=True, axes_dim=[16, 56, 56], theta=10000)
@@ -43,6 +50,29 @@ def flux_inputs(cfg, B, S_hw, T, seed=1234):
     ids[:, :, 2] = np.tile(np.arange(w2), h2)[None]
     txt_ids = np.zeros((B, T, 3), np.float32)
     return img, ids, txt, txt_ids, y
+
+
+def save_split_npz(path, **arrays):
+    """np.savez_compressed(path, **arrays), written as the pieces path.00, path.01, ... (each at most SPLIT_PART_BYTES); returns the total size."""
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    data = buf.getvalue()
+    for old in glob.glob(glob.escape(path) + ".[0-9][0-9]"):
+        os.remove(old)
+    for i in range(0, len(data), SPLIT_PART_BYTES):
+        with open(f"{path}.{i // SPLIT_PART_BYTES:02d}", "wb") as f:
+            f.write(data[i:i + SPLIT_PART_BYTES])
+    return len(data)
+
+
+def load_split_npz(path):
+    """The .npz that save_split_npz wrote (its pieces joined in order), or None when no piece exists.  A missing or damaged piece fails
+    in np.load: the zip directory sits at the end and every member carries a CRC-32."""
+    parts = sorted(glob.glob(glob.escape(path) + ".[0-9][0-9]"))
+    if not parts:
+        return None
+    data = b"".join(open(p, "rb").read() for p in parts)
+    return np.load(io.BytesIO(data))
 
 
 def pow2_attention_scale(n):

@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -2 "$OUT/smoke.log"
 timeout 900 python -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1; echo "tests rc=$?"; tail -3 "$OUT/gpu_tests.log"
-timeout 600 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+timeout 600 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
