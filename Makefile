@@ -27,7 +27,7 @@ alt: $(ALT_LIB)
 oracle:
 	$(MAKE) -C oracle -s
 
-HDRS := $(CSRC)/common.h $(CSRC)/gemm_w4q.h $(CSRC)/attention_w4.h $(CSRC)/attention_w4_loop.inc $(CSRC)/attention_w16.h $(CSRC)/attention_w16_loop.inc $(CSRC)/attention_w16f8_loop.inc $(CSRC)/attention_w32.h $(CSRC)/attention_w32_loop.inc $(CSRC)/attention_w16l.h $(CSRC)/attention_w16l_loop.inc $(CSRC)/attention_w16lf8_loop.inc $(CSRC)/attention_w16lf8pv_loop.inc include/flux_mi355x.h
+HDRS := $(wildcard $(CSRC)/*.h $(CSRC)/*.inc) include/flux_mi355x.h
 build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -Ibuild -c $< -o $@

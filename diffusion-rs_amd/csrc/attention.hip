@@ -43,6 +43,10 @@ constexpr int ATT_PF = 4;  // operand reads in flight in the ping-pong kernel's 
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+}  // namespace fmi
+#include "attention_frame.h"
+namespace fmi {
+
 #if FMI_ALT_KERNELS  // the single-barrier 8-wave kernel (round 1): superseded by the ping-pong form below, kept in the test build as its bit-identical twin
 template <int THR_X16>  // rescale threshold in 1/16 units of log2 (0 = always rescale)
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(const bf16_t* __restrict Q, const bf16_t* __restrict K,
@@ -52,14 +56,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(const bf16_t*
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // 1-D grid, XCD-aware: block b runs on XCD b % 8, so give each XCD a contiguous range of
-  // (head, q-block) ids — all q-blocks of a head then share that head's K / Vt in ONE L2 instead
-  // of pulling it into all eight.
-  const int nqb = (Lq + ATT_QBLK - 1) / ATT_QBLK;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = lid / nqb;
-  const int b = bh / H, h = bh % H;
-  const int q0 = (lid % nqb) * ATT_QBLK + wave * 32;
+  const AttnBlock blk = attn_block(xcd_remap(blockIdx.x, gridDim.x), H, Lq, wave, 32);
+  const int bh = blk.bh, q0 = blk.q0;
   const int hl = lane >> 5;   // half of the wave
   const int l31 = lane & 31;  // query row within the wave / operand row
 
@@ -144,51 +142,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(const bf16_t*
     if (t + 2 < ntiles) stage_k(t + 2, t & 1);
     if (t + 1 < ntiles) stage_v(t + 1, (t + 1) & 1);
     if (t + 1 < ntiles) qk(sn, (t + 1) & 1);
-    // ---- mask the ragged tail (kv >= Lk); kv_local = 32u + (r&3) + 8(r>>2) + 4hl
-    if ((t + 1) * ATT_KV > Lk) {
-      const int kvb = t * ATT_KV + 4 * hl;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kvb + 32 * u + (r & 3) + 8 * (r >> 2) >= Lk) sc[u][r] = -1e30f;
-    }
-    // ---- online softmax (exp2 domain), lane-local row
-    float pmax = sc[0][0];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pmax = fmaxf(pmax, sc[u][r]);
-    pmax = fmaxf(pmax, __shfl_xor(pmax, 32, 64));
-    const float ps = pmax * scale_log2e;
-    if (__any(ps - m_run > (float)THR_X16 * 0.0625f)) {
-      const float mn = fmaxf(m_run, ps);
-      const float alpha = fast_exp2(m_run - mn);
-      m_run = mn;
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[i][r] *= alpha;
-    }
-    float lsum = 0.f;
     bf16x8_t pf[4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      uint32_t pk[8];
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = fast_exp2(sc[u][r] * scale_log2e - m_run);
-        const float p1 = fast_exp2(sc[u][r + 1] * scale_log2e - m_run);
-        lsum += p0 + p1;
-        pk[r >> 1] = pack_bf16x2(p0, p1);
-      }
-      uint4 lo = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-      uint4 hi = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-      __builtin_memcpy(&pf[2 * u], &lo, 16);
-      __builtin_memcpy(&pf[2 * u + 1], &hi, 16);
-    }
-    l_run += lsum;
+    attn_softmax_tile<THR_X16>(sc, ot, pf, m_run, l_run, t, Lk, hl, scale_log2e);
     // ---- Oᵀ += Vᵀ Pᵀ : k-slot (hl,e) of step (u,w) <-> Vt position 32u + 16w + 8hl + e
     const char* vl = smem + 32768 + (t & 1) * 16384;
 #pragma unroll
@@ -221,9 +176,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_kernel(const bf16_t*
     if (out.head_major)
       op = out.p1 + ((int64_t)bh * Lq + q) * HD;
     else if (q < out.rows0)
-      op = out.p0 + (int64_t)b * out.bstride0 + (int64_t)q * out.ld0 + h * HD;
+      op = out.p0 + (int64_t)blk.b * out.bstride0 + (int64_t)q * out.ld0 + blk.h * HD;
     else
-      op = out.p1 + (int64_t)b * out.bstride1 + (int64_t)(q - out.rows0) * out.ld1 + h * HD;
+      op = out.p1 + (int64_t)blk.b * out.bstride1 + (int64_t)(q - out.rows0) * out.ld1 + blk.h * HD;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -274,11 +229,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2;
-  const int nqb = (Lq + ATT_QBLK - 1) / ATT_QBLK;
-  const int lid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = lid / nqb;
-  const int b = bh / H, h = bh % H;
-  const int q0 = (lid % nqb) * ATT_QBLK + wave * 32;
+  const AttnBlock blk = attn_block(xcd_remap(blockIdx.x, gridDim.x), H, Lq, wave, 32);
+  const int bh = blk.bh, q0 = blk.q0;
   const int hl = lane >> 5;
   const int l31 = lane & 31;
 
@@ -319,15 +271,15 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
 
   auto stage_k = [&](int tile) {
     char* kd = smem + (tile & 3) * 16384;
-    const int kv0 = tile * ATT_KV;
     if constexpr (QK8) {  // 64 rows x 128 B = 8 pieces of 8 rows: one per wave
       const int row = wave * 8 + (lane >> 3);
-      int kr = kv0 + row;
+      int kr = tile * ATT_KV + row;
       kr = kr > Lk - 1 ? Lk - 1 : kr;
       const uint8_t* src = reinterpret_cast<const uint8_t*>(K) + ((int64_t)bh * Lk + kr) * HD + (((lane & 7) ^ (row & 7)) << 4);
       __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(kd + wave * 1024), 16, 0, 0);
       return;
     }
+    const int kv0 = tile * ATT_KV;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int chunk = wave * 2 + i;
@@ -395,48 +347,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
     if (t + 3 < ntiles) stage_k(t + 3);
     if (t + 2 < ntiles) stage_v(t + 2);
     __builtin_amdgcn_sched_barrier(0);
-    if ((t + 1) * ATT_KV > Lk) {
-      const int kvb = t * ATT_KV + 4 * hl;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kvb + 32 * u + (r & 3) + 8 * (r >> 2) >= Lk) sc[u][r] = -1e30f;
-    }
-    float pmax = sc[0][0];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) pmax = fmaxf(pmax, sc[u][r]);
-    pmax = fmaxf(pmax, __shfl_xor(pmax, 32, 64));
-    const float ps = pmax * scale_log2e;
-    if (__any(ps - m_run > (float)THR_X16 * 0.0625f)) {
-      const float mn = fmaxf(m_run, ps);
-      const float alpha = fast_exp2(m_run - mn);
-      m_run = mn;
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[i][r] *= alpha;
-    }
-    float lsum = 0.f;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      uint32_t pk[8];
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = fast_exp2(sc[u][r] * scale_log2e - m_run);
-        const float p1 = fast_exp2(sc[u][r + 1] * scale_log2e - m_run);
-        lsum += p0 + p1;
-        pk[r >> 1] = pack_bf16x2(p0, p1);
-      }
-      uint4 lo = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-      uint4 hi = make_uint4(pk[4], pk[5], pk[6], pk[7]);
-      __builtin_memcpy(&pf[2 * u], &lo, 16);
-      __builtin_memcpy(&pf[2 * u + 1], &hi, 16);
-    }
-    l_run += lsum;
+    attn_softmax_tile<THR_X16>(sc, ot, pf, m_run, l_run, t, Lk, hl, scale_log2e);
     slot_barrier();
     // ================= M(t): PV(t) (steps 0..15), then QK^T(t+1) (steps 16..31) into sc
     {
@@ -533,9 +444,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
     if (out.head_major)
       op = out.p1 + ((int64_t)bh * Lq + q) * HD;
     else if (q < out.rows0)
-      op = out.p0 + (int64_t)b * out.bstride0 + (int64_t)q * out.ld0 + h * HD;
+      op = out.p0 + (int64_t)blk.b * out.bstride0 + (int64_t)q * out.ld0 + blk.h * HD;
     else
-      op = out.p1 + (int64_t)b * out.bstride1 + (int64_t)(q - out.rows0) * out.ld1 + h * HD;
+      op = out.p1 + (int64_t)blk.b * out.bstride1 + (int64_t)(q - out.rows0) * out.ld1 + blk.h * HD;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -558,76 +469,76 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
 namespace fmi {
 
 bool alt_kernels_built() { return FMI_ALT_KERNELS != 0; }
-static std::atomic<bool> g_att_pingpong{true};  // process-wide test hooks, like the GEMM switches (gemm_bf16.hip)
-void set_attention_pingpong(bool on) { g_att_pingpong = on; }
-// bf16 operands: the one-wave-per-SIMD kernel (attention_w4.h); FMI_ATT_W4=0 / set_attention_w4(false) -> the 8-wave ping-pong kernel
-static std::atomic<bool> g_att_w4{[] {
-  const char* e = getenv("FMI_ATT_W4");
-  return e ? atoi(e) != 0 : true;
-}()};
-void set_attention_w4(bool on) { g_att_w4 = on; }
-// bf16 operands, round 3: the 16x16x32-MFMA one-wave kernel (attention_w16.h) in front of all of them; FMI_ATT_W16=0 /
-// set_attention_w16(false) falls back to the selection above.  Not bit-identical to the others (Q pre-scaled, row sums of the rounded P).
-static std::atomic<bool> g_att_w16{[] {
-  const char* e = getenv("FMI_ATT_W16");
-  return e ? atoi(e) != 0 : true;
-}()};
-void set_attention_w16(bool on) { g_att_w16 = on; }
-// the same design on the 32x32x16 MFMA (attention_w32.h), bit-identical to attention_w16: off by default (in the denoise loop the
-// 16x16x32 form measured 13.17 vs 13.32 ms of attention per step, profiles/r03_attention_ab.txt); FMI_ATT_W32=1 / set_attention_w32(true)
-static std::atomic<bool> g_att_w32{[] {
-  const char* e = getenv("FMI_ATT_W32");
-  return e ? atoi(e) != 0 : false;
-}()};
-void set_attention_w32(bool on) { g_att_w32 = on; }
-// bf16 operands, round 4: the lock-step schedule of the 16x16x32 kernel (attention_w16l.h) in front of all of them — the default;
-// FMI_ATT_W16L=0 / set_attention_w16l(false) falls back to the selection above.  Bit-identical to attention_w16 / _w32 at rescale
-// threshold 0, equal to rounding at the default threshold.
-static std::atomic<bool> g_att_w16l{[] {
-  const char* e = getenv("FMI_ATT_W16L");
-  return e ? atoi(e) != 0 : true;
-}()};
-void set_attention_w16l(bool on) { g_att_w16l = on; }
+
+// The process-wide kernel choice (test / ablation hook, like the GEMM switches of gemm_bf16.hip): an AttnKind, W16L by default.  Its initial value is
+// read once from the environment, FMI_ATT_W16L / _W32 / _W16 / _W4 = 0 | 1 (defaults 1, 0, 1, 1), folded in that order of precedence.
+static int attention_kind_from_env() {
+  auto on = [](const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) != 0 : dflt;
+  };
+  if (on("FMI_ATT_W16L", true)) return W16L;
+  if (on("FMI_ATT_W32", false)) return W32;
+  if (on("FMI_ATT_W16", true)) return W16;
+  if (on("FMI_ATT_W4", true)) return W4;
+  return PINGPONG;
+}
+static std::atomic<int> g_att_kind{attention_kind_from_env()};
+void set_attention_kind(int kind) { g_att_kind = kind; }
 
 static std::atomic<unsigned long long> g_fp8_fallbacks{0};  // fp8-QK^T launches that did not get the one-wave stream
 unsigned long long attention_fp8_fallbacks() { return g_fp8_fallbacks.load(std::memory_order_relaxed); }
 
+// ---- which kernel serves a launch: the whole table, as a pure function
+enum AttnKernel { AK_SINGLE_BARRIER, AK_PP, AK_PP_QK8, AK_W4, AK_W4_LSE, AK_W16, AK_W16_QK8, AK_W32, AK_W16L, AK_W16L_QK8, AK_W16L_PV8 };
+struct AttnChoice {
+  AttnKernel kernel;
+  fmi_status err;      // != FMI_OK: no kernel serves this launch, msg says why
+  const char* msg;
+  bool fp8_fallback;   // counted (fmi_device_info: fp8_attention_fallbacks): an fp8-QK^T launch that WOULD take a one-wave stream — that kernel family is
+                       // selected and there is more than one KV tile — but whose factor is not a power of two.  A handle or user that picked kernel 0..2
+                       // chose the 8-wave kernel; a single-tile problem has no stream to fall back from.
+};
+// kind: AttnKind.  qk_fp8: 0 = bf16 operands, 1 = e4m3 Q and K, 2 = e4m3 P and V^T as well.  key_split: the launch writes the log-sum-exp.
+// pow2: the fp8 score factor is a power of two (the one-wave streams carry it as an E8M0 block scale).  alt: the test build (all six kinds).
+AttnChoice select_attention_kernel(int kind, int qk_fp8, bool key_split, int Lk, bool pow2, bool alt) {
+  // the product build carries the lock-step kernel (5) and the 8-wave ping-pong kernel (1: single-tile problems, fp8 factors that are no power of two)
+  if (!alt && kind != W16L && kind != PINGPONG)
+    return {AK_PP, FMI_ERR_UNSUPPORTED, "attention: this build carries kernels 5 and 1 only (the others live in the test build, libflux_mi355x_alt.so: make alt)", false};
+  if (key_split) return {AK_W4_LSE, FMI_OK, nullptr, false};  // only the round-2 one-wave kernel writes the log-sum-exp
+  const bool stream = Lk > ATT_KV;  // (a single KV tile has no steady state to pipeline: the 8-wave kernel serves it)
+  if (qk_fp8 == 2) {  // round 5: the lock-step stream's third form, and the only kernel that reads this V^T
+    if (kind != W16L || !stream || !pow2)
+      return {AK_PP, FMI_ERR_UNSUPPORTED, "attention: e4m3 P / V needs the lock-step kernel (kind 5), more than one KV tile and a power-of-two score factor", false};
+    return {AK_W16L_PV8, FMI_OK, nullptr, false};
+  }
+  if (qk_fp8) {  // rounds 3, 4: the one-wave kernels' fp8-QK^T streams serve power-of-two factors; anything else runs on the 8-wave kernel
+    if (kind >= W16 && stream && pow2) return {kind == W16L ? AK_W16L_QK8 : AK_W16_QK8, FMI_OK, nullptr, false};
+    return {AK_PP_QK8, FMI_OK, nullptr, kind >= W16 && stream};
+  }
+  if (stream && kind >= W4) return {kind == W16L ? AK_W16L : kind == W32 ? AK_W32 : kind == W16 ? AK_W16 : AK_W4, FMI_OK, nullptr, false};
+  return {kind >= PINGPONG ? AK_PP : AK_SINGLE_BARRIER, FMI_OK, nullptr, false};
+}
+
+// the rescale threshold as a compile-time tag: launch(std::integral_constant<int, 0 or 96>{})
+template <class F>
+static int with_rescale_thr(int thr_x16, F&& launch) {
+  return thr_x16 == 0 ? launch(std::integral_constant<int, 0>{}) : launch(std::integral_constant<int, 96>{});
+}
+
 int launch_attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const AttnOut& out, int B, int H, int Lq, int Lk,
-                        int Lkpad, float scale, int rescale_thr_x16, hipStream_t stream, int qk_fp8, float* lse, int k_hstride, int score_exp2,
-                        int kind, float v_inv) {  // (k_hstride: see the lse branch)
-  // which kernel: the caller's choice (a model handle's fmi_flux_set_attention_kernel, kind 0..5) or, kind < 0, the process-wide switches
-  const bool g_att_w16l = kind >= 0 ? kind == 5 : (bool)fmi::g_att_w16l, g_att_w32 = kind >= 0 ? kind == 4 : (bool)fmi::g_att_w32,
-             g_att_w16 = kind >= 0 ? kind >= 3 : (bool)fmi::g_att_w16, g_att_w4 = kind >= 0 ? kind >= 2 : (bool)fmi::g_att_w4,
-             g_att_pingpong = kind >= 0 ? kind >= 1 : (bool)fmi::g_att_pingpong;
+                        int Lkpad, float scale, int rescale_thr_x16, hipStream_t stream, int qk_fp8, float* lse, int nsplit, int score_exp2,
+                        int kind, float v_inv) {  // (nsplit: number of key ranges of a key-split launch)
   if (Lq <= 0 || Lk <= 0) return fail(FMI_ERR_INVALID, "attention: empty sequence");
   if (Lkpad % ATT_KV != 0 || Lkpad < Lk) return fail(FMI_ERR_INVALID, "attention: Lkpad must be a multiple of 64 and >= Lk");
-#if !FMI_ALT_KERNELS
-  // the product build carries the lock-step kernel (5) and the 8-wave ping-pong kernel (1: single-tile problems, fp8 factors that are no power of two)
-  if (!g_att_pingpong || g_att_w32 || (g_att_w16 != g_att_w16l) || (g_att_w4 != g_att_w16l))
-    return fail(FMI_ERR_UNSUPPORTED, "attention: this build carries kernels 5 and 1 only (the others live in the test build, libflux_mi355x_alt.so: make alt)");
-#endif
-  dim3 grid(cdiv(Lq, ATT_QBLK) * B * H);
   const float sl = scale * 1.4426950408889634f;
-  if (lse) {  // key-split launch (k_hstride = number of key ranges): only the one-wave kernel writes the log-sum-exp
-    const int nsplit = k_hstride;
-    if (qk_fp8 || B != 1 || out.head_major || out.rows0 != 0 || nsplit < 2 || cdiv(Lk, ATT_KV) < 2 * nsplit)
-      return fail(FMI_ERR_UNSUPPORTED, "attention: a key-split launch needs bf16 operands, B = 1, one token-major output and >= 2 KV tiles per part");
-    const dim3 gs(grid.x * nsplit);
-    if (rescale_thr_x16 == 0)
-      FMI_LAUNCH_LDS((attention_w4_kernel<0, true>), 8 * 16384, gs, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, Lk, lse, nsplit);
-    else
-      FMI_LAUNCH_LDS((attention_w4_kernel<96, true>), 8 * 16384, gs, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, Lk, lse, nsplit);
-    FMI_LAUNCH_CHECK();
-    return FMI_OK;
-  }
+  // fp8 QK^T: the one-wave streams carry scale * log2(e) / (sq * sk) as an E8M0 block scale of the score MFMA, so they serve the calls whose
+  // factor is a power of two 2^-n, n = 0 .. 126 — the model's fp8 mode picks its q scale that way (flux_model.hip: fp8_q_scale_pow2).
+  // The exponent comes from the caller as an integer when it has one (score_exp2: the model, fmi_sdpa_fp8qk_ws).  A bare float
+  // (fmi_sdpa_fp8qk) qualifies if scale * log2(e), rounded to f32 here, is a power of two or ONE ulp beside one: a caller who builds
+  // scale = 2^n / log2(e) in f32 lands there by construction — anything further off was not constructed as one.
+  int n2 = 1;
   if (qk_fp8) {
-    // round 3: the one-wave kernel's fp8-QK^T stream (attention_w16.h, QK8) carries scale * log2(e) / (sq * sk) as an E8M0 block
-    // scale of the score MFMA, so it serves the calls whose factor is a power of two 2^-n, n = 0 .. 126 — the model's fp8 mode
-    // picks its q scale that way (flux_model.hip: fp8_q_scale_pow2); anything else runs on the 8-wave kernel below
-    // The exponent comes from the caller as an integer when it has one (score_exp2: the model, fmi_sdpa_fp8qk_ws).  A bare float
-    // (fmi_sdpa_fp8qk) qualifies if scale * log2(e), rounded to f32 here, is a power of two or ONE ulp beside one: a caller who builds
-    // scale = 2^n / log2(e) in f32 lands there by construction — anything further off was not constructed as one.
-    int n2 = 1;
     if (score_exp2 != ATT_NO_EXP2) n2 = score_exp2;
     else if (sl > 0.f) {
       int e;
@@ -635,82 +546,38 @@ int launch_attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* vt, cons
       if (mant == 0.5f || mant == nextafterf(0.5f, 1.0f)) n2 = e - 1;
       else if (mant == nextafterf(1.0f, 0.0f)) n2 = e;
     }
-    const bool pow2 = n2 <= 0 && n2 >= -126;
-    // counted (fmi_device_info: fp8_attention_fallbacks): launches that WOULD take a one-wave stream — that kernel family is selected and
-    // there is more than one KV tile — but whose factor is not a power of two.  A handle or user that picked kernel 0..2 chose the 8-wave
-    // kernel; a single-tile problem has no stream to fall back from.
-    if (qk_fp8 == 2) {  // round 5: e4m3 P and V^T as well — the lock-step stream's third form, and the only kernel that reads this V^T
-      if (!(g_att_w16l && g_att_w16) || Lk <= ATT_KV || !pow2)
-        return fail(FMI_ERR_UNSUPPORTED, "attention: e4m3 P / V needs the lock-step kernel (kind 5), more than one KV tile and a power-of-two score factor");
-      const float sl2 = ldexpf(1.0f, n2);
-      if (rescale_thr_x16 == 0)
-        FMI_LAUNCH_LDS((attention_w16l_kernel<0, true, true>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2, v_inv);
-      else
-        FMI_LAUNCH_LDS((attention_w16l_kernel<96, true, true>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2, v_inv);
-      FMI_LAUNCH_CHECK();
-      return FMI_OK;
-    }
-    if (g_att_w16 && Lk > ATT_KV && !pow2) g_fp8_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    if (g_att_w16l && g_att_w16 && Lk > ATT_KV && pow2) {  // round 4: the lock-step schedule's fp8-QK^T stream
-      const float sl2 = ldexpf(1.0f, n2);
-      if (rescale_thr_x16 == 0)
-        FMI_LAUNCH_LDS((attention_w16l_kernel<0, true>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2);
-      else
-        FMI_LAUNCH_LDS((attention_w16l_kernel<96, true>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2);
-      FMI_LAUNCH_CHECK();
-      return FMI_OK;
-    }
-#if FMI_ALT_KERNELS
-    if (g_att_w16 && Lk > ATT_KV && pow2) {
-      const float sl2 = ldexpf(1.0f, n2);
-      if (rescale_thr_x16 == 0)
-        FMI_LAUNCH_LDS((attention_w16_kernel<0, true>), 8 * 16384, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2);
-      else
-        FMI_LAUNCH_LDS((attention_w16_kernel<96, true>), 8 * 16384, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2);
-      FMI_LAUNCH_CHECK();
-      return FMI_OK;
-    }
-#endif
-    if (rescale_thr_x16 == 0)
-      hipLaunchKernelGGL((attention_pp_kernel<0, true>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-    else
-      hipLaunchKernelGGL((attention_pp_kernel<96, true>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-  } else if (g_att_w16l && Lk > ATT_KV) {  // (a single KV tile has no steady state to pipeline: the 8-wave kernel serves it)
-    if (rescale_thr_x16 == 0)
-      FMI_LAUNCH_LDS((attention_w16l_kernel<0>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-    else
-      FMI_LAUNCH_LDS((attention_w16l_kernel<96>), 8 * 16384, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-#if FMI_ALT_KERNELS
-  } else if (g_att_w32 && Lk > ATT_KV) {
-    if (rescale_thr_x16 == 0)
-      FMI_LAUNCH_LDS((attention_w32_kernel<0>), 8 * 16384, grid, dim3(AW32_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-    else
-      FMI_LAUNCH_LDS((attention_w32_kernel<96>), 8 * 16384, grid, dim3(AW32_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-  } else if (g_att_w16 && Lk > ATT_KV) {
-    if (rescale_thr_x16 == 0)
-      FMI_LAUNCH_LDS((attention_w16_kernel<0>), 8 * 16384, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-    else
-      FMI_LAUNCH_LDS((attention_w16_kernel<96>), 8 * 16384, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-  } else if (g_att_w4 && Lk > ATT_KV) {
-    if (rescale_thr_x16 == 0)
-      FMI_LAUNCH_LDS((attention_w4_kernel<0>), 8 * 16384, grid, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, 0, nullptr, 1);
-    else
-      FMI_LAUNCH_LDS((attention_w4_kernel<96>), 8 * 16384, grid, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, 0, nullptr, 1);
-#endif
-  } else if (g_att_pingpong) {
-    if (rescale_thr_x16 == 0)
-      hipLaunchKernelGGL((attention_pp_kernel<0, false>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-    else
-      hipLaunchKernelGGL((attention_pp_kernel<96, false>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
   }
+  const bool pow2 = n2 <= 0 && n2 >= -126;
+  // which kernel: the caller's choice (a model handle's fmi_flux_set_attention_kernel, kind 0..5) or, kind < 0, the process-wide one
+  const AttnChoice c = select_attention_kernel(kind >= 0 ? kind : (int)g_att_kind, qk_fp8, lse != nullptr, Lk, pow2, alt_kernels_built());
+  if (c.err != FMI_OK) return fail(c.err, c.msg);
+  if (c.kernel == AK_W4_LSE && (qk_fp8 || B != 1 || out.head_major || out.rows0 != 0 || nsplit < 2 || cdiv(Lk, ATT_KV) < 2 * nsplit))
+    return fail(FMI_ERR_UNSUPPORTED, "attention: a key-split launch needs bf16 operands, B = 1, one token-major output and >= 2 KV tiles per part");
+  if (c.fp8_fallback) g_fp8_fallbacks.fetch_add(1, std::memory_order_relaxed);
+  const dim3 grid(cdiv(Lq, ATT_QBLK) * B * H), gs(grid.x * (lse ? nsplit : 1));
+  const float sl2 = ldexpf(1.0f, n2);  // the streams' fp8 score factor
+  constexpr int LDS = 8 * 16384;
+  return with_rescale_thr(rescale_thr_x16, [&](auto thr) -> int {
+    constexpr int THR = decltype(thr)::value;
+    switch (c.kernel) {
+      case AK_W16L: FMI_LAUNCH_LDS((attention_w16l_kernel<THR>), LDS, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
+      case AK_W16L_QK8: FMI_LAUNCH_LDS((attention_w16l_kernel<THR, true>), LDS, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2); break;
+      case AK_W16L_PV8: FMI_LAUNCH_LDS((attention_w16l_kernel<THR, true, true>), LDS, grid, dim3(AW16L_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2, v_inv); break;
+      case AK_W4_LSE: FMI_LAUNCH_LDS((attention_w4_kernel<THR, true>), LDS, gs, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, Lk, lse, nsplit); break;
+      case AK_PP: hipLaunchKernelGGL((attention_pp_kernel<THR, false>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
+      case AK_PP_QK8: hipLaunchKernelGGL((attention_pp_kernel<THR, true>), grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
 #if FMI_ALT_KERNELS
-  else if (rescale_thr_x16 == 0)
-    hipLaunchKernelGGL(attention_kernel<0>, grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
-  else
-    hipLaunchKernelGGL(attention_kernel<96>, grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl);
+      case AK_W16: FMI_LAUNCH_LDS((attention_w16_kernel<THR>), LDS, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
+      case AK_W16_QK8: FMI_LAUNCH_LDS((attention_w16_kernel<THR, true>), LDS, grid, dim3(AW16_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl2); break;
+      case AK_W32: FMI_LAUNCH_LDS((attention_w32_kernel<THR>), LDS, grid, dim3(AW32_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
+      case AK_W4: FMI_LAUNCH_LDS((attention_w4_kernel<THR>), LDS, grid, dim3(AW4_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl, 0, nullptr, 1); break;
+      case AK_SINGLE_BARRIER: hipLaunchKernelGGL(attention_kernel<THR>, grid, dim3(ATT_THREADS), 0, stream, q, k, vt, out, H, Lq, Lk, Lkpad, sl); break;
 #endif
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
+      default: return fail(FMI_ERR_UNSUPPORTED, "attention: the selected kernel is not part of this build");
+    }
+    FMI_LAUNCH_CHECK();
+    return FMI_OK;
+  });
 }
 
 int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16_t* o, int B, int H, int Lq, int Lk, int Lkpad,

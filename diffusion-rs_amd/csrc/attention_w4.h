@@ -56,13 +56,12 @@ __global__ __launch_bounds__(AW4_THREADS, 1) void attention_w4_kernel(const bf16
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nqb = (Lq + ATT_QBLK - 1) / ATT_QBLK;
   int lid = xcd_remap(blockIdx.x, gridDim.x);
   if (LSE) {
     // key-split launch: the grid is nsplit x (heads x query blocks); part `sp` walks the KV tiles [nt * sp / nsplit, nt * (sp + 1) / nsplit)
     // of the full sequence (Lk = its length on entry, k_hstride = rows per head of K), writes its normalised output to slice sp of
     // out.p1 (slices of Lq * out.ld1 elements) and its log-sum-exp to slice sp of lse
-    const int per = gridDim.x / nsplit, sp = lid / per, nt = (Lk + ATT_KV - 1) / ATT_KV;
+    const int per = gridDim.x / nsplit, sp = lid / per, nt = (Lk + ATT_KV - 1) / ATT_KV, nqb = (Lq + ATT_QBLK - 1) / ATT_QBLK;
     lid -= sp * per;
     const int t0 = (int)((int64_t)nt * sp / nsplit), t1 = (int)((int64_t)nt * (sp + 1) / nsplit);
     const int k0 = t0 * ATT_KV, k1 = min(Lk, t1 * ATT_KV);
@@ -70,9 +69,8 @@ __global__ __launch_bounds__(AW4_THREADS, 1) void attention_w4_kernel(const bf16
     out.p1 += (int64_t)sp * Lq * out.ld1;
     lse += (int64_t)sp * (per / nqb) * Lq;
   }
-  const int bh = lid / nqb;
-  const int b_ = bh / H, h = bh % H;
-  const int q0 = (lid % nqb) * ATT_QBLK + wave * 64;
+  const AttnBlock blk = attn_block(lid, H, Lq, wave, 64);
+  const int bh = blk.bh, q0 = blk.q0;
   const int hl = lane >> 5, l31 = lane & 31;
   const bf16_t* Kb = K + (int64_t)bh * (LSE ? k_hstride : Lk) * HD;
   const bf16_t* Vb = Vt + (int64_t)bh * HD * Lkpad;
@@ -406,9 +404,6 @@ __global__ __launch_bounds__(AW4_THREADS, 1) void attention_w4_kernel(const bf16
   // pinned operands, so the statement is entered and left with nothing in flight (A(0) above; the statement fetches the
   // first fragments of B itself and ends with a drain) and runs on every path (zero iterations when ntiles == 2).
   {
-    typedef float f32x32 __attribute__((ext_vector_type(32)));
-    typedef int i32x32 __attribute__((ext_vector_type(32)));
-    typedef int i32x16 __attribute__((ext_vector_type(16)));
     typedef int i32x8 __attribute__((ext_vector_type(8)));
     f32x32 O[4], S[2];
     i32x32 F, QA[2];
@@ -438,14 +433,12 @@ __global__ __launch_bounds__(AW4_THREADS, 1) void attention_w4_kernel(const bf16
       misc[8 + r] = kr >= k_last_rows ? (int)((k_last_rows - 1) * 256 + (((lane & 15) ^ (kr & 15)) << 4)) : (int)k_voff[r];
     }
     misc[12] = __float_as_int(m_run[0]), misc[13] = __float_as_int(m_run[1]), misc[14] = __float_as_int(l_run[0]), misc[15] = __float_as_int(l_run[1]);
-    const uint64_t kb64 = (uint64_t)(uintptr_t)Kb, vb64 = (uint64_t)(uintptr_t)Vb;
-    const uint32_t kb_lo = __builtin_amdgcn_readfirstlane((uint32_t)kb64), kb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(kb64 >> 32));
-    const uint32_t vb_lo = __builtin_amdgcn_readfirstlane((uint32_t)vb64), vb_hi = __builtin_amdgcn_readfirstlane((uint32_t)(vb64 >> 32));
+    const AttnBase kb = attn_split_base(Kb), vb = attn_split_base(Vb);
     const float thr = (float)THR_X16 * 0.0625f;
     asm volatile(FMI_AW4_LOOP_ASM
                  : "+{a[0:31]}"(O[0]), "+{a[32:63]}"(O[1]), "+{a[64:95]}"(O[2]), "+{a[96:127]}"(O[3]), "+{v[0:31]}"(S[0]), "+{v[32:63]}"(S[1]),
                    "+{v[64:79]}"(P[0]), "+{v[80:95]}"(P[1]), "+{v[96:127]}"(F), "+{v[128:135]}"(KA), "+{v[136:139]}"(VA), "+{v[140:155]}"(misc)
-                 : "{a[128:159]}"(QA[0]), "{a[160:191]}"(QA[1]), [kb_lo] "s"(kb_lo), [kb_hi] "s"(kb_hi), [vb_lo] "s"(vb_lo), [vb_hi] "s"(vb_hi),
+                 : "{a[128:159]}"(QA[0]), "{a[160:191]}"(QA[1]), [kb_lo] "s"(kb.lo), [kb_hi] "s"(kb.hi), [vb_lo] "s"(vb.lo), [vb_hi] "s"(vb.hi),
                    [nt] "s"(ntiles), [ntm1] "s"(ntiles - 1), [sl] "s"(scale_log2e), [thr] "s"(thr), [woff] "s"(wave * 4096)
                  : "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167", "v168", "v169", "v170", "v171", "s80",
                    "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "vcc", "scc", "memory");
@@ -496,26 +489,9 @@ __global__ __launch_bounds__(AW4_THREADS, 1) void attention_w4_kernel(const bf16
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d = dt * 32 + g * 8 + 4 * hl;
-        const uint2 v = make_uint2(pack_bf16x2(ot[b][dt][4 * g] * inv, ot[b][dt][4 * g + 1] * inv), pack_bf16x2(ot[b][dt][4 * g + 2] * inv, ot[b][dt][4 * g + 3] * inv));
-        *reinterpret_cast<uint2*>(stg + r * 256 + ((((d * 2) >> 4) ^ (r & 15)) << 4) + ((d * 2) & 15)) = v;
-      }
+      for (int g = 0; g < 4; ++g) attn_stage_put(stg, r, dt * 32 + g * 8 + 4 * hl, ot[b][dt][4 * g], ot[b][dt][4 * g + 1], ot[b][dt][4 * g + 2], ot[b][dt][4 * g + 3], inv);
   }
-  __syncthreads();  // (each wave reads back only its own region; the barrier also orders the LDS writes before the reads)
-#pragma unroll
-  for (int it = 0; it < 16; ++it) {
-    const int r = it * 4 + (lane >> 4), c = lane & 15;
-    const int q = q0 + r;
-    const uint4 v = *reinterpret_cast<const uint4*>(stg + r * 256 + ((c ^ (r & 15)) << 4));
-    if (q < Lq) {
-      bf16_t* op;
-      if (out.head_major) op = out.p1 + ((int64_t)bh * Lq + q) * HD;
-      else if (q < out.rows0) op = out.p0 + (int64_t)b_ * out.bstride0 + (int64_t)q * out.ld0 + h * HD;
-      else op = out.p1 + (int64_t)b_ * out.bstride1 + (int64_t)(q - out.rows0) * out.ld1 + h * HD;
-      *reinterpret_cast<uint4*>(op + c * 8) = v;
-    }
-  }
+  attn_store_staged(stg, out, blk, Lq, lane);
 }
 
 }  // namespace fmi

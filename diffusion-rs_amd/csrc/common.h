@@ -284,7 +284,7 @@ int launch_attention_ex(const bf16_t* q, const bf16_t* k, const bf16_t* vt, cons
 // qk_fp8 == 2 (round 5): vt is e4m3 as well — (B, H, 128, Lkpad) BYTES, keys in plain order, value * v_scale, zero beyond Lk — and P is rounded to e4m3:
 // both products on the fp8 MFMA (attention_w16l_kernel<.., true, true>); v_inv = 1 / v_scale.  Only the lock-step stream has this form: the call
 // needs a power-of-two score factor and more than one KV tile, anything else is an error (there is no kernel to fall back to).
-// kind: 0..5 = this kernel (fmi_set_attention_kernel's numbering: a model handle's own choice, fmi_flux_set_attention_kernel), -1 = the process-wide switches
+// kind: 0..5 = this kernel (fmi_set_attention_kernel's numbering: a model handle's own choice, fmi_flux_set_attention_kernel), -1 = the process-wide one (set_attention_kind)
 // score_exp2 (fp8 QK^T only): the caller KNOWS that scale * log2(e) == 2^score_exp2 exactly and says so as an integer (the model's fp8
 // mode constructs its q scale that way) -> the one-wave stream, which carries the factor in the MFMA's E8M0 block scale.  ATT_NO_EXP2 =
 // unknown: the launcher recognises an exact power of two itself, anything else runs on the 8-wave kernel and is COUNTED
@@ -305,11 +305,18 @@ struct OpScratch {
   bool locked_ = false;
 };
 bool alt_kernels_built();  // attention.hip: was THIS library linked from the test build's objects (the flag differs per object: only attention.o / gemm_bf16.o)
-void set_attention_pingpong(bool on);  // 8-wave kernels: ping-pong (default) or the single-barrier one
-void set_attention_w4(bool on);        // bf16 operands: one-wave-per-SIMD kernel (default) or the 8-wave ones
-void set_attention_w16(bool on);       // bf16 operands: the 16x16x32-MFMA one-wave kernel in front of the others (default on)
-void set_attention_w16l(bool on);      // bf16 operands: the lock-step schedule of the 16x16x32 kernel, in front of all (default on)
-void set_attention_w32(bool on);       // bf16 operands: the same design on the 32x32x16 MFMA, in front of all (default off)
+// The attention kernels, in fmi_set_attention_kernel's numbering.  {SINGLE_BARRIER, PINGPONG, W4} are bit-identical among themselves, so are {W16, W32};
+// W16L equals those two bit for bit at rescale threshold 0 and to rounding at the default one.  The kernels share their frame (workgroup decode, output
+// addressing, LDS-DMA set-up, Q fragments, epilogues) through attention_frame.h.  The product build carries W16L and PINGPONG, the test build all six.
+enum AttnKind {
+  SINGLE_BARRIER = 0,  // 8 waves, one barrier per KV tile (attention.hip: attention_kernel)
+  PINGPONG = 1,        // 8 waves in two alternating groups (attention_pp_kernel): single-tile problems, fp8 factors that are no power of two
+  W4 = 2,              // one wave per SIMD on the 32x32x16 MFMA (attention_w4.h); its key-split form serves every key-split launch
+  W16 = 3,             // one wave per SIMD on the 16x16x32 MFMA, the whole KV stream generated (attention_w16.h)
+  W32 = 4,             // the same design on the 32x32x16 MFMA (attention_w32.h)
+  W16L = 5,            // the lock-step schedule of W16 (attention_w16l.h): the default
+};
+void set_attention_kind(int kind);  // the process-wide choice (an AttnKind; launch_attention_ex's kind = -1 follows it)
 // flash attention, d = 128.  q,k: (BH, L, 128) bf16; vt: (BH, 128, Lpad) bf16 with the kv axis
 // permuted inside each group of 16 (see attention.hip); out token-major (B, L, H*128) or (BH,L,128)
 int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* vt, bf16_t* out, int B, int H,

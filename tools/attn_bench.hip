@@ -75,8 +75,7 @@ static void fp8_section(int iters) {
     }
     double us[3];
     for (int w = 0; w < 3; ++w) {  // 8-wave fp8 kernel, round 3's one-wave stream, round 4's lock-step stream
-      set_attention_w16(w >= 1);
-      set_attention_w16l(w == 2);
+      set_attention_kind(w == 0 ? PINGPONG : w == 1 ? W16 : W16L);
       out.p1 = w == 0 ? oa : w == 1 ? ob : oc;
       for (int i = 0; i < 3; ++i) launch_attention_ex((const bf16_t*)q, (const bf16_t*)k, vt, out, s.B, s.H, s.L, s.L, Lpad, scale, 96, nullptr, 1);
       hipDeviceSynchronize();
@@ -106,8 +105,7 @@ static void fp8_section(int iters) {
            std::sqrt(num / std::max(den, 1e-30)), mx, nan, us[2], mis_l, nan_l, us_pv, hipGetLastError() == hipSuccess ? "" : "  (HIP ERROR)");
     hipFree(q); hipFree(k); hipFree(vt); hipFree(oa); hipFree(ob); hipFree(oc); hipFree(vt8); hipFree(od);
   }
-  set_attention_w16(true);
-  set_attention_w16l(true);
+  set_attention_kind(W16L);
 }
 
 int main(int argc, char** argv) {
@@ -144,11 +142,7 @@ int main(int argc, char** argv) {
     hipMemset(o6, 0xff, n * 2);
     double tf[6];
     for (int pp = 0; pp < 6; ++pp) {  // single-barrier kernel, the ping-pong kernel, the one-wave-per-SIMD kernel, the 16x16x32 one-wave kernel, its 32x32x16 twin, the lock-step schedule
-      set_attention_pingpong(pp != 0);
-      set_attention_w4(pp == 2);
-      set_attention_w16(pp == 3);
-      set_attention_w32(pp == 4);
-      set_attention_w16l(pp == 5);
+      set_attention_kind(pp);
       bf16_t* dst = pp == 0 ? o : pp == 1 ? o2 : pp == 2 ? o3 : pp == 3 ? o4 : pp == 4 ? o5 : o6;
       for (int i = 0; i < 3; ++i) launch_attention(q, k, vt, dst, s.B, s.H, s.L, s.L, Lpad, scale, 1, nullptr);
       hipDeviceSynchronize();
@@ -206,10 +200,10 @@ int main(int argc, char** argv) {
       }
       AttnOut ao{};
       ao.p1 = o4, ao.ld1 = s.H * 128, ao.bstride1 = (int64_t)s.L * s.H * 128;
-      set_attention_w16l(false), set_attention_w32(false), set_attention_w16(true);
+      set_attention_kind(W16);
       launch_attention_ex(q, k, vt, ao, s.B, s.H, s.L, s.L, Lpad, scale, 0, nullptr);
       ao.p1 = o6;
-      set_attention_w16l(true);
+      set_attention_kind(W16L);
       launch_attention_ex(q, k, vt, ao, s.B, s.H, s.L, s.L, Lpad, scale, 0, nullptr);
       hipDeviceSynchronize();
       std::vector<uint16_t> h0(n), h1(n);

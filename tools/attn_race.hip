@@ -130,8 +130,7 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < n; ++i) kk[i] = kk[i % 128];
       hipMemcpy(k, kk.data(), n * 2, hipMemcpyHostToDevice);
     }
-    set_attention_pingpong(kind != 0);
-    set_attention_w4(kind == 2);
+    set_attention_kind(kind);  // 0 .. 2
     launch_attention(q, k, vt, o0, B, H, L, L, Lpad, 0.08838834764f, 1, nullptr);
     hipDeviceSynchronize();
     if (getenv("WAIT")) {  // the reference launch ran alone; now let the co-runner start
