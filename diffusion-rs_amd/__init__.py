@@ -6,3 +6,5 @@ from .flux import (AutoEncoderKl, FLUX_DEV, FLUX_SCHNELL, FluxModel, SchedulerCo
 from .pipeline import DiffusionGenerationParams, ModelDType, ModelSource, Offloading, Pipeline, encode_png  # noqa: F401
 from .text import CLIP_L, T5_XXL, ClipTextTransformer, T5EncoderModel, load_bpe_tokenizer, tokenize_and_pad  # noqa: F401
 from . import synth  # noqa: F401
+from . import lora  # noqa: F401
+from .lora import read_lora  # noqa: F401

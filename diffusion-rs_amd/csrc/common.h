@@ -380,6 +380,12 @@ int launch_gemv(const float* x, const bf16_t* W, const bf16_t* bias, float* y, i
                 int silu_in, int accumulate, hipStream_t stream);
 // bf16 out = w_i8 * SCB[row] / 127 (dequant.cu:205-214) on `stream`
 int launch_dequant_int8_scb_bf16(const int8_t* w, const float* scb, bf16_t* out, int col, int64_t n, hipStream_t stream);
+// LoRA merge (lora.hip): w rows = bf16_rne(w0 rows + sum_j Bt[j, n] * A[j, k]), f64 FMAs in ascending j, one rounding.  w0 / w: (rows, K) bf16, leading
+// dimension K; A (Rpad, K) f32; Bt (Rpad, rows_pad) f64 = the up-projections transposed, weight * scale folded in; Rpad % LORA_RANK_CHUNK == 0 and
+// rows_pad % LORA_TILE_ROWS == 0, zero beyond the real rank / rows.  launch_lora_pack writes one adapter's rank rows [off, off + r) of both: Acat = A, Bt[off + j, n] = coef * B[n, j] (0 for n >= rows).
+constexpr int LORA_TILE_ROWS = 64, LORA_RANK_CHUNK = 16;
+int launch_lora_pack(const float* A, const float* B, int rows, int K, int r, double coef, float* Acat, double* Bt, int rows_pad, int off, hipStream_t stream);
+int launch_lora_merge(const bf16_t* w0, bf16_t* w, int rows, int K, const float* A, const double* Bt, int rows_pad, int Rpad, hipStream_t stream);
 int launch_timestep_embedding(const float* t, int B, int dim, float* out, hipStream_t stream);
 int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hipStream_t stream);

@@ -49,6 +49,10 @@ def _tensor_arg(t):
     return C.c_void_p(t.data_ptr()), _TORCH_DT[t.dtype], tuple(t.shape), t
 
 
+def _as_f32(t):
+    return np.asarray(t, np.float32) if isinstance(t, np.ndarray) else t.to(torch.float32)
+
+
 @dataclass
 class SchedulerConfig:
     """pipelines/scheduler.rs:4-20 (public FLUX.1 values as defaults)."""
@@ -108,6 +112,50 @@ class FluxModel:
         for k, v in tensors.items():
             self.set_tensor(k, v)
         self.assert_complete()
+
+    def get_tensor(self, name: str, dtype=torch.bfloat16):
+        """The current value of a tensor set_tensor accepts (with adapters loaded: the merged weight), as a torch tensor on this model's device.
+        dtype bfloat16 (the resident bits) or float32 (the same values)."""
+        shapes = self._shapes()
+        if name not in shapes:
+            raise L.FmiError(f"get_tensor: unknown tensor name '{name}'", code=L.ERR_INVALID)
+        shape = shapes[name]
+        out = torch.empty(shape, dtype=dtype, device=self.device)
+        sh = (C.c_int64 * len(shape))(*shape)
+        L.check(self.lib.fmi_flux_get_tensor(self.h, name.encode(), _ptr(out), _TORCH_DT[dtype], sh, len(shape)), self.lib)
+        return out
+
+    def _shapes(self):
+        if getattr(self, "_shape_cache", None) is None:
+            from . import synth
+            self._shape_cache = synth.flux_tensor_shapes(self.cfg)
+        return self._shape_cache
+
+    # ---- LoRA adapters, merged into the resident weights (include/flux_mi355x.h: fmi_flux_lora_*)
+    def lora_add(self, adapter: str, prefix: str, A, B, scale: float = 1.0):
+        """One (A (r, in), B (out, r)) pair of `adapter` for the Linear `prefix`; torch tensors (any device) or numpy arrays, F32 / F16 / BF16.
+        Takes effect before it returns; a pair the adapter already holds for that Linear is replaced."""
+        pa, dta, sa, keep_a = _tensor_arg(A)
+        pb, dtb, sb, keep_b = _tensor_arg(B)
+        if dta != dtb:
+            pa, dta, sa, keep_a = _tensor_arg(_as_f32(A))
+            pb, dtb, sb, keep_b = _tensor_arg(_as_f32(B))
+        if len(sa) != 2 or len(sb) != 2 or sa[0] != sb[1]:
+            raise L.FmiError(f"lora_add: {prefix}: A {tuple(sa)} and B {tuple(sb)} are not (r, in) and (out, r)", code=L.ERR_INVALID)
+        want = self._shapes().get(prefix + ".weight")
+        if want is not None and len(want) == 2 and sa[0] >= 1 and (sb[0], sa[1]) != tuple(want):
+            raise L.FmiError(f"lora_add: {prefix}: B A is {(sb[0], sa[1])}, the Linear is {tuple(want)}", code=L.ERR_INVALID)
+        L.check(self.lib.fmi_flux_lora_add(self.h, adapter.encode(), prefix.encode(), pa, pb, dta, int(sa[0]), float(scale)), self.lib)
+
+    def lora_set_weight(self, adapter: str, weight: float):
+        L.check(self.lib.fmi_flux_lora_set_weight(self.h, adapter.encode(), float(weight)), self.lib)
+
+    def lora_remove(self, adapter: Optional[str] = None):
+        """Drop one adapter (None: every adapter); a Linear left without one holds its loaded weights again, bit for bit."""
+        L.check(self.lib.fmi_flux_lora_remove(self.h, adapter.encode() if adapter is not None else None), self.lib)
+
+    def loras(self) -> List[str]:
+        return [self.lib.fmi_flux_lora_name(self.h, i).decode() for i in range(self.lib.fmi_flux_lora_count(self.h))]
 
     def set_linear_bnb4(self, prefix: str, packed, absmax, blocksize: int, quant_type: str, out_features: int, in_features: int):
         q = {"fp4": 1, "nf4": 2}[quant_type]

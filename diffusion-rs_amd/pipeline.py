@@ -344,6 +344,54 @@ class Pipeline:
         self.flux.quantize_int8()
         self._int8_pending = False
 
+    # ---- LoRA adapters (lora.py reads the file, FluxModel.lora_* merge it into the resident weights).  Load-time calls under the pipeline lock; with
+    # ModelDType.I8 they work until the first request has quantised the model, afterwards the library answers with its state error.  Under
+    # torch.distributed every rank makes the same call on its own copy of the weights: there is no collective.
+    def load_lora(self, path_or_dict, name: Optional[str] = None, weight: float = 1.0, skip_unsupported: bool = False) -> str:
+        """Merge the adapter of a .safetensors file (diffusers / PEFT or kohya / BFL keys) or of a {key: tensor} dict into the DiT; returns its name
+        (default: the file's base name).  Several adapters stack; the result does not depend on the order they were loaded in."""
+        from . import lora
+        pairs = lora.read_lora(path_or_dict, skip_unsupported=skip_unsupported, hidden_size=self.flux.hidden)
+        if name is None:
+            name = os.path.splitext(os.path.basename(os.fspath(path_or_dict)))[0] if isinstance(path_or_dict, (str, os.PathLike)) else "lora"
+        if not pairs:
+            raise ValueError(f"LoRA '{name}': no supported keys")
+        shapes = self.flux._shapes()
+        for prefix, (A, B, _) in pairs.items():
+            want = shapes.get(prefix + ".weight")
+            if want is None or len(want) != 2:
+                raise ValueError(f"LoRA '{name}': {prefix} is not a Linear of this model")
+            if (int(B.shape[0]), int(A.shape[1])) != tuple(want):
+                raise ValueError(f"LoRA '{name}': {prefix}: B A is {(int(B.shape[0]), int(A.shape[1]))}, the Linear is {tuple(want)}")
+        with self._lock:
+            if name in self.flux.loras():
+                raise ValueError(f"a LoRA named '{name}' is loaded already: unload_lora('{name}') first, or pass another name")
+            try:
+                first = True
+                for prefix, (A, B, scale) in pairs.items():
+                    self.flux.lora_add(name, prefix, A, B, scale)
+                    if first and weight != 1.0:  # before the other pairs arrive: each Linear is then merged once, at its final weight
+                        self.flux.lora_set_weight(name, weight)
+                    first = False
+            except Exception:
+                if name in self.flux.loras():
+                    self.flux.lora_remove(name)
+                raise
+        return name
+
+    def set_lora_weight(self, name: str, weight: float):
+        with self._lock:
+            self.flux.lora_set_weight(name, weight)
+
+    def unload_lora(self, name: Optional[str] = None):
+        """Drop one adapter (None: all of them): the Linears it touched are recomputed from the loaded weights and the adapters that remain."""
+        with self._lock:
+            self.flux.lora_remove(name)
+
+    def loras(self) -> List[str]:
+        with self._lock:
+            return self.flux.loras()
+
     def enable_sequence_parallel(self, group=None):
         """Single-image latency mode: the ranks of `group` (default: all of torch.distributed) denoise every
         image TOGETHER, each on 1/N of its tokens (dist.SequenceParallel; two all-to-alls per transformer block), instead of

@@ -42,7 +42,7 @@ extern "C" {
  * 6 (round 6): + fmi_release_scratch; + the small f32 seams fmi_timestep_embedding, fmi_rope_table, fmi_rmsnorm_rope; + fmi_flux_calibrate_int8
  *   (per-channel smoothing of the int8 mode from a calibration; fmi_flux_quantize_int8 without one is unchanged).  The op-level entries that use
  *   the library's per-stream scratch (fmi_sdpa_*, fmi_linear_fp8 / _i8, fmi_groupnorm_nhwc) now enqueue their kernels under one lock: host threads
- *   may share a stream.
+ *   may share a stream.  Later additions under the same number: fmi_flux_get_tensor and the LoRA adapter calls fmi_flux_lora_*.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -156,6 +156,40 @@ int fmi_flux_set_linear_int8(fmi_flux*, const char* prefix, const int8_t* weight
  *    3 as 0, but a matrix that 0 would expand per call is expanded once into its dense slot (small launches stay on the codes).
  * All of them produce the same bits. */
 int fmi_flux_set_quant_dense_cache(fmi_flux*, int mode);
+
+/* Read back the CURRENT value of any tensor fmi_flux_set_tensor accepts (same names, same shapes; `shape` / `rank` are checked): the row range of
+ * the fused matrix it lives in, bf16 converted exactly to `dtype` F32 or BF16.  `out` may be a host or device pointer.  Synchronises the device.
+ * FMI_ERR_STATE for a tensor that was never set; FMI_ERR_UNSUPPORTED for a Linear that is resident only as packed nf4 / fp4 / LLM.int8 codes.
+ * With LoRA adapters loaded it returns the merged weight. */
+int fmi_flux_get_tensor(fmi_flux*, const char* name, void* out, fmi_dtype dtype, const int64_t* shape, int rank);
+
+/* LoRA adapters, MERGED into the resident bf16 weights (no runtime low-rank path: the denoise loop runs the same GEMMs at the same speed).
+ * For a Linear with loaded weight W0 (out, in) and adapters a = 1..n, each holding A_a (r_a, in), B_a (out, r_a), scale_a (= alpha / r) and a
+ * user weight_a (default 1), the resident weight is
+ *     W = bf16_rne( W0 + sum_a weight_a * scale_a * (B_a A_a) )
+ * with the sum taken over the adapters in lexicographic order of their names.  The factors are kept as f32, converted exactly from F32 / F16 / BF16,
+ * and never rounded to bf16; products and sums run in f64 (products of f32 values are exact there) and there is ONE rounding at the end, so every
+ * element of W is the correctly rounded value of the expression — also where W0 and the update cancel, which f32 sums cannot guarantee.  W is always recomputed from a pristine copy of W0 that
+ * the library keeps while a Linear has an active adapter (weight != 0) — never patched incrementally — so stacking, reweighting and switching do
+ * not depend on the history of calls, and removing the adapters restores the loaded weights bit for bit.  Biases are never touched.
+ *   fmi_flux_lora_add        one (A, B) pair of adapter `adapter` for the Linear `prefix` (as in fmi_flux_set_linear_bnb4, e.g.
+ *                            "transformer_blocks.0.attn.to_k"); host or device pointers; a pair the adapter already holds for that Linear is replaced.
+ *   fmi_flux_lora_set_weight the user weight of an adapter; 0 switches it off (its factors stay loaded).
+ *   fmi_flux_lora_remove     drop an adapter (NULL: every adapter).
+ *   fmi_flux_lora_count / fmi_flux_lora_name(i): the loaded adapters in lexicographic order (the pointer is valid until that adapter is removed).
+ * The three mutating calls are load-time operations: each synchronises the device on entry (which orders it against evaluations on any stream),
+ * re-merges the affected Linears and completes before it returns.  They validate first and leave every weight and adapter untouched on error:
+ * FMI_ERR_STATE once the model is in an 8-bit mode (adapters go in BEFORE fmi_flux_quantize_fp8 / _int8, which then quantise the merged weights) or
+ * while tensors are missing; FMI_ERR_UNSUPPORTED for a Linear resident as nf4 / fp4 / LLM.int8 codes (merging into packed codes is out of scope);
+ * FMI_ERR_INVALID for an unknown Linear or adapter, rank < 1, a null pointer, a non-finite scale or weight.  While a weight has adapters,
+ * fmi_flux_set_tensor, fmi_flux_set_linear_bnb4 and fmi_flux_set_linear_int8 on it return FMI_ERR_STATE (remove the adapters first).  Quantising to
+ * 8 bits freezes the adapters and releases their factors and the pristine copies; the names stay listed.  The pristine copies are private allocations, not part of
+ * fmi_flux_state_*: the flat state carries the effective (merged) weights. */
+int fmi_flux_lora_add(fmi_flux*, const char* adapter, const char* prefix, const void* A, const void* B, fmi_dtype dtype, int rank, float scale);
+int fmi_flux_lora_set_weight(fmi_flux*, const char* adapter, float weight);
+int fmi_flux_lora_remove(fmi_flux*, const char* adapter);
+int fmi_flux_lora_count(const fmi_flux*);
+const char* fmi_flux_lora_name(const fmi_flux*, int i);
 /* Single-image sequence parallelism.  The reference runs one image on one device
  * (pipelines/mod.rs:214-217 "This will need to be updated!"); here the tokens of ONE image are sharded over the
  * world_size ranks of a group: rank r passes ONLY its token shard to fmi_flux_forward / fmi_flux_denoise
