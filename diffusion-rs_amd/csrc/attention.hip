@@ -31,10 +31,6 @@
 
 namespace fmi {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
-
 constexpr int ATT_THREADS = 512;
 constexpr int ATT_QBLK = 256;  // query rows per workgroup
 constexpr int ATT_KV = 64;     // kv rows per tile
@@ -300,12 +296,6 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_pp_kernel(const bf16
       const bf16_t* src = Vb + (int64_t)row * Lkpad + kv0 + (((lane & 7) ^ ((row >> 1) & 7)) << 3);
       __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(vd + chunk * 1024), 16, 0, 0);
     }
-  };
-  auto slot_barrier = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
   };
 
   const int ntiles = (Lk + ATT_KV - 1) / ATT_KV;

@@ -157,6 +157,10 @@ __device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcp
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 bf16 = 4 VGPRs (MFMA A/B operand)
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;  // 32x32 MFMA accumulator
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;  // the bf16 MFMA builtins' operand type
+// the two pointer types of __builtin_amdgcn_global_load_lds (LDS-DMA: HBM -> LDS without a VGPR round trip)
+typedef __attribute__((address_space(3))) void lds_void;
+typedef const __attribute__((address_space(1))) void glb_void;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -176,6 +180,14 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ void dma_barrier() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+}
+// Barrier between the slots of the ping-pong kernels (gemm_pp_kernel, attention_pp_kernel): raw s_barrier + lgkmcnt(0) — a __syncthreads()
+// would make hipcc drain vmcnt as well and collapse the DMA pipeline — fenced so that no MFMA is moved across a slot boundary.
+__device__ __forceinline__ void slot_barrier() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my LDS reads are done: the slots I read may be refilled
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 constexpr int NUM_XCD = 8;
@@ -258,7 +270,8 @@ struct GemmProblem {
   const float* w_sum;
 };
 int launch_gemm(const GemmProblem* probs, int nprob, hipStream_t stream);
-// Process-wide kernel-selection hooks (tests, ablations; the alternatives are bit-identical):
+// Process-wide kernel-selection hooks (tests, ablations; the alternatives are bit-identical).  launch_gemm reduces a group to GemmTraits, snapshots
+// these switches and asks one pure function, select_gemm_kernel (gemm_bf16.hip), which kernel runs; the kernels share their frame through gemm_frame.h.
 void set_gemm_w4(bool on);             // residual-update launches (N > 128, no fused relayout) on the 4-wave 128x128-per-wave kernel (default off)
 void set_gemm_pingpong(bool on);       // dense N > 128 launches: the ping-pong kernel (default) or the double-buffered one
 void set_gemm_w4q_min_rows(int rows);  // 4-bit weights: M from which the one-wave-per-SIMD fused dequant-GEMM runs (default 256)

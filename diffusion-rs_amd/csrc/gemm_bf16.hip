@@ -54,20 +54,9 @@ struct GemmBatch {
   int nprob;
 };
 
-// Logical tile t of a problem -> (tm, tn).  Tiles are numbered band by band (gh tile-rows each), column by column inside a band, so
-// the ~32 consecutive tiles an XCD runs at any time form a compact gh x (32 / gh) patch: gh + 32 / gh distinct A / W panels per K
-// step instead of 33 (L2 hits).  Bijective for any gh >= 1.
-__device__ __forceinline__ void tile_coords(int t, int tiles_m, int tiles_n, int gh, int& tm, int& tn) {
-  const int band = t / (gh * tiles_n);
-  const int band_h = min(gh, tiles_m - band * gh);
-  const int tin = t - band * gh * tiles_n;
-  tn = tin / band_h;
-  tm = band * gh + tin % band_h;
-}
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void glb_void;
+}  // namespace fmi
+#include "gemm_frame.h"
+namespace fmi {
 
 __device__ __constant__ float kNF4[16] = {-1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
                                           -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
@@ -79,24 +68,6 @@ __device__ __forceinline__ float dq_fp4(unsigned v, float am) {
   const float tab[8] = {0.0f, 5.208333333e-03f, 0.66666667f, 1.0f, 0.33333333f, 0.5f, 0.16666667f, 0.25f};
   float sign = (v & 8) ? -1.0f : 1.0f;
   return tab[v & 7] * am * sign;
-}
-
-// Stage ROWS x 64 bf16 (rows r0.., cols k0..k0+63 of a row-major matrix with `ld`) into LDS.
-// Rows past `rmax` are clamped (duplicates of the last row; their results are never stored).
-template <int ROWS>
-__device__ __forceinline__ void stage_tile_dma(const bf16_t* __restrict g, int ld, int r0, int rmax, int k0, char* lds_tile, int wave, int lane) {
-  const int r8 = lane >> 3, cs = lane & 7;
-  constexpr int CPW = ROWS / 64;  // 1-KiB chunks (8 rows) per wave
-#pragma unroll
-  for (int i = 0; i < CPW; ++i) {
-    const int chunk = wave * CPW + i;
-    const int row = chunk * 8 + r8;  // tile-local row
-    const int src_slot = cs ^ ((row >> 1) & 7);
-    int grow = r0 + row;
-    grow = grow > rmax ? rmax : grow;
-    const bf16_t* src = g + (int64_t)grow * ld + k0 + src_slot * 8;
-    __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(lds_tile + chunk * 1024), 16, 0, 0);
-  }
 }
 
 // x / 127 for the LLM.int8 expansion, correctly rounded without the IEEE division sequence: q = x * RN(1/127), one Newton
@@ -641,41 +612,22 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(const GemmBa
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  // ---- which problem / tile
-  const int total = batch.tile_start[batch.nprob];
-  const int lid = xcd_remap(blockIdx.x, total);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_PROBLEMS; ++i)
-    if (i < batch.nprob && lid >= batch.tile_start[i]) pi = i;
-  const GemmProblem& P = batch.p[pi];
-  const int t = lid - batch.tile_start[pi];
-  const int tiles_m = (P.M + BM - 1) / BM;
-  const int tiles_n = (P.N + BN - 1) / BN;
-  int tm, tn;
-  tile_coords(t, tiles_m, tiles_n, batch.band[pi], tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = P.K / BK;
+  const GemmTile tile = gemm_tile<BN>(batch, 2);  // which problem / tile
+  const GemmProblem& P = tile.P;
+  const int m0 = tile.m0, n0 = tile.n0, nk = tile.nk;
 
   auto bufA = [&](int b) -> char* { return smem + b * BUF_BYTES; };
   auto bufW = [&](int b) -> char* { return smem + b * BUF_BYTES + A_TILE_BYTES; };
 
   // v_mfma_f32_16x16x32_bf16 (see gemm_pp_kernel): the wave's 128 x 32 NJ is 8 x 2 NJ accumulators of 16 x 16
   f32x4 acc[8][2 * NJ];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 2 * NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+  zero(acc);
 
   // per-lane swizzled column-slot byte offsets for the 2 k-steps (32 wide) of a tile: slot 4 s + (lane >> 4) of row lane & 15
-  const int sw = ((lane & 15) >> 1) & 7;
-  int koff[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) koff[s] = ((s * 4 + (lane >> 4)) ^ sw) << 4;
-  const int a_row_off = (wm * 128 + (lane & 15)) * 128;
-  const int w_row_off = (wn * 32 * NJ + (lane & 15)) * 128;
+  const FragSlots<16> frag = frag_slots<16>(lane);
+  const int (&koff)[2] = frag.koff;
+  const int a_row_off = frag.row_off(wm * 128);
+  const int w_row_off = frag.row_off(wn * 32 * NJ);
 
   // CONV: this lane stages rows chunk*8 + (lane>>3), chunk = wave*4 + i; precompute their pixels.
   // cv_up > 0: nearest-2x upsample folded in; cv_up < 0: the VAE encoder's Downsample (stride 2,
@@ -861,20 +813,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_pp_kernel(const GemmBatc
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wn = wave & 3;  // group = row half (wm)
 
-  const int total = batch.tile_start[batch.nprob];
-  const int lid = xcd_remap(blockIdx.x, total);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_PROBLEMS; ++i)
-    if (i < batch.nprob && lid >= batch.tile_start[i]) pi = i;
-  const GemmProblem& P = batch.p[pi];
-  const int t_in = lid - batch.tile_start[pi];
-  const int tiles_m = (P.M + BM - 1) / BM;
-  const int tiles_n = (P.N + BN - 1) / BN;
-  int tm, tn;  // same band / patch order as gemm_bf16_kernel
-  tile_coords(t_in, tiles_m, tiles_n, batch.band[pi], tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = P.K * ES / (BK * 2);  // 128-byte K tiles
+  const GemmTile tile = gemm_tile<BN>(batch, ES);  // which problem / tile
+  const GemmProblem& P = tile.P;
+  const int m0 = tile.m0, n0 = tile.n0, nk = tile.nk;
 
   // fp8: v_mfma_f32_32x32x64_f8f6f4, accumulators acc[4][NJ] of 32 x 32 (Acc32).  bf16: v_mfma_f32_16x16x32_bf16, accumulators
   // acc16[8][2 NJ] of 16 x 16 (Acc16) — on this power-capped part the 16 x 16 x 32 form sustains 14 % more than 32 x 32 x 16
@@ -884,21 +825,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_pp_kernel(const GemmBatc
   f32x16 acc[FP8 ? 4 : 1][NJ];
   i32x16_t acci[I8 ? 4 : 1][NJ];
   f32x4 acc16[FP8 ? 1 : 8][2 * NJ];
-  if constexpr (I8) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acci[i][j][r] = 0;
-  } else if constexpr (FP8) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  } else {
+  if constexpr (I8) zero(acci);
+  else if constexpr (FP8) zero(acc);
+  else {  // (written out: behind zero() hipcc assigned the accumulators of <0, 1..3> other registers and their K loop lost two v_mov_b64, gemm_frame.h)
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -907,25 +836,21 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_pp_kernel(const GemmBatc
         for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
   }
 
-  const int rl = FP8 ? (lane & 31) : (lane & 15);  // fragment row inside its 32- / 16-row block
-  const int sw = (rl >> 1) & 7;
-  int koff[4];  // fp8: 16-byte k slots 2 s + (lane >> 5), s = 0..3; bf16: slots 4 s + (lane >> 4), s = 0..1
-#pragma unroll
-  for (int s = 0; s < 4; ++s) koff[s] = FP8 ? ((s * 2 + (lane >> 5)) ^ sw) << 4 : (((s & 1) * 4 + (lane >> 4)) ^ sw) << 4;
-  const int a_row_off = (g * 128 + rl) * 128;
-  const int w_row_off = (wn * 64 + rl) * 128;
+  // fragment blocks of 32 rows (8-bit: 16-byte k slots 2 s + (lane >> 5), s = 0..3) or 16 (bf16: slots 4 s + (lane >> 4), s = 0..1)
+  const auto frag = frag_slots<FP8 ? 32 : 16>(lane);
+  const auto& koff = frag.koff;
+  const int a_row_off = frag.row_off(g * 128);
+  const int w_row_off = frag.row_off(wn * 64);
 
   // chunks (8 rows, 1 KiB) this wave stages: A chunks of the other group's rows, W chunks wave*4+i
   const int a_chunk0 = (wave ^ 4) * 4, w_chunk0 = wave * 4;
-  // per-lane BYTE offsets (32-bit: the operands are < 4 GiB) from the uniform tile base, so the DMA
-  // uses the saddr + voffset form: 8 VGPRs instead of 16 for pointers (the kernel sits at the
-  // 256-register limit and a spilled pointer costs a vmcnt(0) reload — a full pipeline drain)
+  // per-lane BYTE offsets (32-bit) from the uniform tile base, so the DMA uses the saddr + voffset form: 8 VGPRs instead of 16 for
+  // pointers (the kernel sits at the 256-register limit and a spilled pointer costs a vmcnt(0) reload — a full pipeline drain).
+  // The text of TileDma (gemm_frame.h), kept here: behind the struct this kernel's bf16 form came out with another scratch size.
   uint32_t a_off[4], w_off[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int ra = (a_chunk0 + i) * 8 + (lane >> 3), rw = (w_chunk0 + i) * 8 + (lane >> 3);
-    // relative to the tile's first row (the uniform base below carries m0 / n0 in 64 bits): an operand may exceed 4 GiB — the fused
-    // modulation matrix of FLUX.1 is 6.5 GB — but a tile's 256 rows never do
     a_off[i] = (uint32_t)((int64_t)(min(m0 + ra, P.M - 1) - m0) * P.lda * ES + (((lane & 7) ^ ((ra >> 1) & 7)) << 4));
     w_off[i] = (uint32_t)((int64_t)(min(n0 + rw, P.N - 1) - n0) * P.ldw * ES + (((lane & 7) ^ ((rw >> 1) & 7)) << 4));
   }
@@ -938,12 +863,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_pp_kernel(const GemmBatc
   auto dma_w = [&](int kt, int slot, int i) {
     const char* base = w_base + (int64_t)kt * (BK * 2);
     __builtin_amdgcn_global_load_lds((glb_void*)(base + w_off[i]), (lds_void*)(smem + W_RING + slot * TILE + (w_chunk0 + i) * 1024), 16, 0, 0);
-  };
-  auto slot_barrier = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my LDS reads are done: the slots I read may be refilled
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
   };
 
   // ---- prologue: what the steady-state rule would have issued before LOAD(0): A(0) (both
@@ -1139,22 +1058,31 @@ constexpr int W4_THREADS = 256;
 // The lane id is laundered: everything the epilogue derives from it is then computed after the K loop instead of being
 // hoisted above it, kept live across 256 arch VGPRs of loop state, spilled, and reloaded (each reload = vmcnt(0) = the
 // wave's stores serialised: measured 30 us per tile instead of 12).
-template <int ACT>
-__device__ __forceinline__ void w4_epilogue(const GemmProblem& P, f32x16 (&acc)[4][4], char* smem, int m0, int n0, int wave, int wm, int wn, int lane) {
+// One template over the accumulator array: f32x16 [4][4] (32 x 32 blocks, gemm_w4q_kernel: the half r = column blocks 2 r, 2 r + 1, view Acc32<2>)
+// or f32x4 [8][8] (16 x 16 blocks, gemm_w4_kernel: the half r = column blocks 4 r .. 4 r + 3, view Acc16<2>).
+template <int ACT, class V, int I, int J>
+__device__ __forceinline__ void w4_epilogue(const GemmProblem& P, V (&acc)[I][J], char* smem, int m0, int n0, int wave, int wm, int wn, int lane) {
+  using View = std::conditional_t<std::is_same<V, f32x16>::value, Acc32<2>, Acc16<2>>;
+  constexpr int H = J / 2;
+  // (the copies of a half are written out: behind a lambda or a function hipcc lays the blocks of the test build's gemm_w4_kernel out in another order)
   int lane_e = lane;
   asm volatile("" : "+v"(lane_e));
   if (P.qk_qh != nullptr && n0 < 3 * P.qk_D) {
     // fused q|k|v relayout: both halves staged into the one LDS image, then this wave emits row groups 2*wave, 2*wave + 1
     __syncthreads();
     {
-      f32x16 hacc[4][2];
+      V hacc[I][H];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) hacc[i][0] = acc[i][0], hacc[i][1] = acc[i][1];
+      for (int i = 0; i < I; ++i)
+#pragma unroll
+        for (int j = 0; j < H; ++j) hacc[i][j] = acc[i][j];
 #pragma clang loop unroll(disable)
       for (int r = 0; r < 2; ++r) {
-        qkv_relayout_stage(P, Acc32<2>{hacc, lane_e}, smem, n0, wm * 4 + wn * 2 + r, lane_e);
+        qkv_relayout_stage(P, View{hacc, lane_e}, smem, n0, wm * 4 + wn * 2 + r, lane_e);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) hacc[i][0] = acc[i][2], hacc[i][1] = acc[i][3];
+        for (int i = 0; i < I; ++i)
+#pragma unroll
+          for (int j = 0; j < H; ++j) hacc[i][j] = acc[i][H + j];
         asm volatile("" : "+v"(lane_e));
       }
     }
@@ -1166,125 +1094,63 @@ __device__ __forceinline__ void w4_epilogue(const GemmProblem& P, f32x16 (&acc)[
     }
     return;
   }
-  f32x16 hacc[4][2];
+  V hacc[I][H];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) hacc[i][0] = acc[i][0], hacc[i][1] = acc[i][1];
+  for (int i = 0; i < I; ++i)
+#pragma unroll
+    for (int j = 0; j < H; ++j) hacc[i][j] = acc[i][j];
 #pragma clang loop unroll(disable)
   for (int r = 0; r < 2; ++r) {
-    gemm_epilogue_impl<2, 4, ACT>(P, Acc32<2>{hacc, lane_e}, smem, m0, n0, wm * 4 + wn * 2 + r, lane_e);
+    gemm_epilogue_impl<2, 4, ACT>(P, View{hacc, lane_e}, smem, m0, n0, wm * 4 + wn * 2 + r, lane_e);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) hacc[i][0] = acc[i][2], hacc[i][1] = acc[i][3];
+    for (int i = 0; i < I; ++i)
+#pragma unroll
+      for (int j = 0; j < H; ++j) hacc[i][j] = acc[i][H + j];
     asm volatile("" : "+v"(lane_e));  // keep the second round's address math out of the first
   }
 }
 
 #if FMI_ALT_KERNELS  // the dense 4-wave kernel (FMI_GEMM_W4=1: off by default since round 2) lives in the test build; its epilogue tail above serves gemm_w4q_kernel
-// The same tail for 16 x 16 accumulators (gemm_w4_kernel): acc[tm][tn], the half r = column tiles 4 r .. 4 r + 3.
 template <int ACT>
-__device__ __forceinline__ void w4_epilogue16(const GemmProblem& P, f32x4 (&acc)[8][8], char* smem, int m0, int n0, int wave, int wm, int wn, int lane) {
-  int lane_e = lane;
-  asm volatile("" : "+v"(lane_e));
-  f32x4 hacc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) hacc[i][j] = acc[i][j];
-  if (P.qk_qh != nullptr && n0 < 3 * P.qk_D) {
-    __syncthreads();
-#pragma clang loop unroll(disable)
-    for (int r = 0; r < 2; ++r) {
-      qkv_relayout_stage(P, Acc16<2>{hacc, lane_e}, smem, n0, wm * 4 + wn * 2 + r, lane_e);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hacc[i][j] = acc[i][4 + j];
-      asm volatile("" : "+v"(lane_e));
-    }
-    __syncthreads();
-#pragma clang loop unroll(disable)
-    for (int r = 0; r < 2; ++r) {
-      qkv_relayout_emit(P, smem, m0, n0, wave * 2 + r, lane_e);
-      asm volatile("" : "+v"(lane_e));
-    }
-    return;
-  }
-#pragma clang loop unroll(disable)
-  for (int r = 0; r < 2; ++r) {
-    gemm_epilogue_impl<2, 4, ACT>(P, Acc16<2>{hacc, lane_e}, smem, m0, n0, wm * 4 + wn * 2 + r, lane_e);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) hacc[i][j] = acc[i][4 + j];
-    asm volatile("" : "+v"(lane_e));  // keep the second round's address math out of the first
-  }
-}
-
-template <bool FP8, int ACT>
 __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4_kernel(const GemmBatch batch) {
   constexpr int NJ = 4, BN = 256;
   constexpr int A_RING = 0, W_RING = 2 * A_TILE_BYTES, TILE = A_TILE_BYTES;
-  constexpr int ES = FP8 ? 1 : 2;
+  constexpr int ES = 2;  // bf16 operands
   __shared__ __attribute__((aligned(16))) char smem[5 * TILE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  const int total = batch.tile_start[batch.nprob];
-  const int lid = xcd_remap(blockIdx.x, total);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_PROBLEMS; ++i)
-    if (i < batch.nprob && lid >= batch.tile_start[i]) pi = i;
-  const GemmProblem& P = batch.p[pi];
-  const int t_in = lid - batch.tile_start[pi];
-  const int tiles_m = (P.M + BM - 1) / BM;
-  const int tiles_n = (P.N + BN - 1) / BN;
-  int tm, tn;
-  tile_coords(t_in, tiles_m, tiles_n, batch.band[pi], tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = P.K * ES / (BK * 2);
+  const GemmTile tile = gemm_tile<BN>(batch, ES);  // which problem / tile
+  const GemmProblem& P = tile.P;
+  const int m0 = tile.m0, n0 = tile.n0, nk = tile.nk;
 
   // v_mfma_f32_16x16x32_bf16: the wave's 128 x 128 is 8 x 8 accumulators of 16 x 16 (the 16 x 16 x 32 form sustains 14 % more than
   // 32 x 32 x 16 on this power-capped part, tools/mfma_peak; same results bit for bit, same LDS image)
   f32x4 acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+  zero(acc);
 
-  const int sw = ((lane & 15) >> 1) & 7;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void*)smem;
-  uint32_t koff[2];  // k-step s of 32: 16-byte slot 4 s + (lane >> 4) of the row
-#pragma unroll
-  for (int s = 0; s < 2; ++s) koff[s] = ((s * 4 + (lane >> 4)) ^ sw) << 4;
-  const uint32_t a_row = lds0 + A_RING + (wm * 128 + (lane & 15)) * 128;
-  const uint32_t w_row = lds0 + W_RING + (wn * 128 + (lane & 15)) * 128;
+  const FragSlots<16> frag = frag_slots<16>(lane);  // k-step s of 32: 16-byte slot 4 s + (lane >> 4) of the row
+  const int (&koff)[2] = frag.koff;
+  const uint32_t a_row = lds0 + A_RING + frag.row_off(wm * 128);
+  const uint32_t w_row = lds0 + W_RING + frag.row_off(wn * 128);
 
   // DMA pieces of this wave: 1-KiB chunks wave*8 + i of the A tile and of the W tile
-  uint32_t a_off[8], w_off[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int r = (wave * 8 + i) * 8 + (lane >> 3);
-    a_off[i] = (uint32_t)((int64_t)(min(m0 + r, P.M - 1) - m0) * P.lda * ES + (((lane & 7) ^ ((r >> 1) & 7)) << 4));  // tile-relative, see gemm_pp_kernel
-    w_off[i] = (uint32_t)((int64_t)(min(n0 + r, P.N - 1) - n0) * P.ldw * ES + (((lane & 7) ^ ((r >> 1) & 7)) << 4));
-  }
-  const char* const a_base = reinterpret_cast<const char*>(P.A) + (int64_t)m0 * P.lda * ES;
-  const char* const w_base = reinterpret_cast<const char*>(P.W) + (int64_t)n0 * P.ldw * ES;
+  const TileDma<8> dma(P, m0, n0, ES, wave * 8, wave * 8, lane);
   // LDS-DMA in the scalar-base form (SGPR pair + 32-bit lane offset), written as asm: from the builtin hipcc forms a 64-bit
   // per-lane address with a v_lshl_add_u64 in front of every piece inside this loop (+1-2 % on the K loop, tools/gemm_bench).
   // m0 = LDS destination of the 1-KiB piece; one wait state between the m0 write and the load.
   auto dma_a = [&](int kt, int i) {
-    const char* base = a_base + (int64_t)kt * (BK * 2);
+    const char* base = dma.a_base + (int64_t)kt * (BK * 2);
     const uint32_t l = lds0 + A_RING + (kt & 1) * TILE + (wave * 8 + i) * 1024;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(a_off[i]), "s"(base), "s"(l) : "memory");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(dma.a_off[i]), "s"(base), "s"(l) : "memory");
   };
   auto dma_w = [&](int kt, int slot, int i) {
-    const char* base = w_base + (int64_t)kt * (BK * 2);
+    const char* base = dma.w_base + (int64_t)kt * (BK * 2);
     const uint32_t l = lds0 + W_RING + slot * TILE + (wave * 8 + i) * 1024;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(w_off[i]), "s"(base), "s"(l) : "memory");
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(dma.w_off[i]), "s"(base), "s"(l) : "memory");
   };
   auto sync_all = [&]() {
     __builtin_amdgcn_sched_barrier(0);
@@ -1396,7 +1262,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4_kernel(const GemmBatch 
     for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(acc[i][j]));
 #undef FMI_W4_RD
 #undef FMI_W4_WAIT
-  w4_epilogue16<ACT>(P, acc, smem, m0, n0, wave, wm, wn, lane);
+  w4_epilogue<ACT>(P, acc, smem, m0, n0, wave, wm, wn, lane);
 }
 
 #endif  // FMI_ALT_KERNELS
@@ -1412,14 +1278,14 @@ static std::atomic<bool> g_pingpong{true};
 // Default OFF since both kernels moved to v_mfma_f32_16x16x32_bf16 (round 2): with twice the MFMA instructions per K tile the
 // one-wave-per-SIMD stream no longer beats two waves per SIMD (tools/gemm_bench, f32 residual epilogue: 4608x3072x15360 1280 vs
 // 1385 TF, 4096x3072x12288 1259 vs 1353 TF; it was +5-8 % with 32x32x16).  Bit-identical to the ping-pong kernel;
-// FMI_GEMM_W4=1 in the environment (or set_gemm_w4(true)) sends the launches `w4_pays` selects below (the residual-update
+// FMI_GEMM_W4=1 in the environment (or set_gemm_w4(true)) sends the launches gemm_w4_pays selects below (the residual-update
 // GEMMs: proj, mlp2, linear2) to it.
 static std::atomic<bool> g_w4{[] {
   const char* e = getenv("FMI_GEMM_W4");
   return e ? atoi(e) != 0 : false;
 }()};
 static std::atomic<int> g_w4q_min_rows{256};
-// never for dense weights (measured: slower, see launch_gemm); the packed 4-bit kernel always fuses.  FMI_GEMM_W4_QKV_MIN_N = the bound for experiments
+// never for dense weights (measured: slower, see gemm_w4_pays); the packed 4-bit kernel always fuses.  FMI_GEMM_W4_QKV_MIN_N = the bound for experiments
 static std::atomic<int> g_w4_qkv_min_n{[]() { const char* e = getenv("FMI_GEMM_W4_QKV_MIN_N"); return e && atoi(e) > 0 ? atoi(e) : 1 << 30; }()};
 void set_gemm_w4_qkv_min_n(int n) { g_w4_qkv_min_n = n; }
 void set_gemm_w4q_min_rows(int rows) { g_w4q_min_rows = rows; }
@@ -1450,25 +1316,51 @@ static int pick_tile_band(int tiles_m) {
   return best;
 }
 
-int launch_gemm(const GemmProblem* probs, int nprob, hipStream_t stream) {
-  if (nprob <= 0) return FMI_OK;
-  if (nprob > MAX_PROBLEMS) return fail(FMI_ERR_INVALID, "launch_gemm: too many grouped problems");
-  GemmBatch b;
-  b.nprob = nprob;
-  int total = 0;
-  const bool quant = probs[0].q_type != 0;
-  const bool conv = probs[0].cv_ks != 0;
-  const bool fp8 = probs[0].fp8 != 0;
+// ---- what a group of problems reduces to for the kernel choice
+// Tile width: 256, or 128 when no problem is wider.
+static int gemm_tile_width(const GemmProblem* probs, int nprob) {
   int max_n = 0;
   for (int i = 0; i < nprob; ++i) max_n = std::max(max_n, probs[i].N);
   int bn = max_n <= 128 ? 128 : 256;
-  if (conv && bn == 256) {
+  if (probs[0].cv_ks != 0 && bn == 256) {
     // a convolution whose 256 x 256 tiles leave a quarter of the CUs or more without one (the decoder's 512 -> 512 layers on 128 x 128
     // pixels: 128 tiles) runs on 256 x 128 tiles instead
     int64_t tiles = 0;
     for (int i = 0; i < nprob; ++i) tiles += (int64_t)cdiv(probs[i].M, BM) * cdiv(probs[i].N, 256);
     if (tiles <= 192) bn = 128;
   }
+  return bn;
+}
+// 4-wave kernel: its K loop is 7-10 % faster, its two-round epilogue slower — measured break-even (tools/gemm_bench,
+// FMI_EPI=store|gelu|resid on the FLUX shapes): the f32 residual read-modify-write launches at every K (proj -5 %,
+// mlp2 -10 %, linear2 -7 %), everything else from K = 8192 on (mlp1 + GELU at K = 3072 is a wash).
+// The launches with the fused q|k|v relayout epilogue stay on the 8-wave kernel: the 4-wave kernels have the epilogue
+// too (w4_epilogue; the packed 4-bit kernel needs it), but with one workgroup per CU nothing overlaps its two LDS round
+// trips, and it costs more than the K loop gains (tools/gemm_bench FMI_EPI=qkv, 4608 x 21504 x 3072: 8-wave 588 us,
+// 4-wave 637 us; 4096 x 9216 x 3072: 258 vs 305 us).  set_gemm_w4_qkv_min_n lowers the bound (qkv_min_n) for experiments.
+static bool gemm_w4_pays(const GemmProblem* probs, int nprob, int qkv_min_n) {
+  if (probs[0].fp8 != 0 || probs[0].cv_ks != 0 || probs[0].q_type != 0) return false;
+  for (int i = 0; i < nprob; ++i) {
+    const GemmProblem& p = probs[i];
+    if (p.epi != EPI_RESID_GATE_F32 && p.K < 8192 && !(p.qk_qh && p.N >= qkv_min_n)) return false;
+  }
+  return true;
+}
+// 4-bit weights: the one-wave-per-SIMD fused kernel from min_rows rows on (below it the GEMM is bound by the packed
+// weight stream and the two-workgroups-per-CU kernel with the VGPR expand hides latency better)
+static bool gemm_w4q_ok(const GemmProblem* probs, int nprob, int min_rows) {
+  if (probs[0].q_type == 0) return false;
+  for (int i = 0; i < nprob; ++i) {
+    const GemmProblem& p = probs[i];
+    const int kb = p.q_blocksize / BK;  // K tiles per absmax block
+    if (p.q_type == 3 || p.M < min_rows || p.K % p.q_blocksize || (kb & (kb - 1)) || (int64_t)p.N * p.K / 2 >= (1ll << 32)) return false;
+  }
+  return true;
+}
+
+// The checks of a group, in the order their messages are reported.  bn: gemm_tile_width (the fp8 and q|k|v checks need 256); launch_gemm evaluates epilogue_kind again, to dispatch.
+static int validate_gemm_problems(const GemmProblem* probs, int nprob, int bn) {
+  const bool quant = probs[0].q_type != 0, conv = probs[0].cv_ks != 0, fp8 = probs[0].fp8 != 0;
   for (int i = 0; i < nprob; ++i) {
     const GemmProblem& p = probs[i];
     if (p.M <= 0 || p.N <= 0) return fail(FMI_ERR_INVALID, "launch_gemm: empty problem");
@@ -1488,83 +1380,108 @@ int launch_gemm(const GemmProblem* probs, int nprob, hipStream_t stream) {
           p.qk_Lpad % 64 || !p.qk_kh || !p.qk_vt || !p.qk_wq || !p.qk_wk || !p.qk_pe || (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 7)))
         return fail(FMI_ERR_INVALID, "launch_gemm: bad fused qkv relayout descriptor (needs 256-wide tiles, D % 256 == 0, rows/row_off/M % 16 == 0)");
     }
-    b.p[i] = p;
+  }
+  if (epilogue_kind(probs, nprob) < 0) return fail(FMI_ERR_INVALID, "launch_gemm: the problems of a grouped launch must share the activation kind");
+  return FMI_OK;
+}
+
+// ---- which kernel serves a group: the whole table, as a pure function
+enum GemmKernel {
+  GK_DB128,    // gemm_bf16_kernel<0, 1>: N <= 128, the 256 x 128 double-buffered kernel
+  GK_DB256,    // gemm_bf16_kernel<0, 2>: the double-buffered 256 x 256 kernel, gemm_pp_kernel's bit-identical predecessor (test build)
+  GK_Q4_DB,    // gemm_bf16_kernel<1, .>: 4-bit / LLM.int8 weights expanded by the VALU
+  GK_CONV,     // gemm_bf16_kernel<2, .>: implicit-GEMM convolution
+  GK_PP,       // gemm_pp_kernel<0, act>: every dense bf16 launch wider than 128
+  GK_PP_E4M3,  // gemm_pp_kernel<1, act>
+  GK_PP_I8,    // gemm_pp_kernel<2, act>
+  GK_W4,       // gemm_w4_kernel<act>: dense, one wave per SIMD (test build)
+  GK_W4Q,      // gemm_w4q_kernel<act>: fused dequant-GEMM, one wave per SIMD (gemm_w4q.h)
+};
+enum GemmOperands { GO_DENSE, GO_Q4, GO_CONV };
+struct GemmTraits {
+  GemmOperands operands;  // dense / quantised weights (4-bit, LLM.int8) / convolution
+  int q8;                 // 8-bit operands on both sides: 0 = none (bf16), 1 = e4m3, 2 = int8 (GemmProblem::fp8)
+  int bn;                 // tile width (gemm_tile_width)
+  bool w4_pays, w4q_ok;   // gemm_w4_pays, gemm_w4q_ok
+};
+struct GemmSwitches {  // a snapshot of the process-wide switches above
+  bool pingpong, w4;               // what select_gemm_kernel reads
+  int w4q_min_rows, w4_qkv_min_n;  // bounds of the reductions gemm_w4q_ok / gemm_w4_pays, which launch_gemm fills GemmTraits with
+};
+struct GemmChoice {
+  GemmKernel kernel;
+  fmi_status err;  // != FMI_OK: no kernel serves this group in this build, msg says why
+  const char* msg;
+};
+// alt: the test build (it carries GK_W4 and GK_DB256)
+GemmChoice select_gemm_kernel(const GemmTraits& t, const GemmSwitches& sw, bool alt) {
+  if (t.q8 == 2) return {GK_PP_I8, FMI_OK, nullptr};
+  if (t.q8) return {GK_PP_E4M3, FMI_OK, nullptr};
+  if (t.operands == GO_CONV) return {GK_CONV, FMI_OK, nullptr};
+  if (t.operands == GO_Q4) return {t.bn == 256 && t.w4q_ok ? GK_W4Q : GK_Q4_DB, FMI_OK, nullptr};
+  if (t.bn != 256) return {GK_DB128, FMI_OK, nullptr};
+  const bool w4 = sw.w4 && t.w4_pays;
+  if (!alt && (w4 || !sw.pingpong))
+    return {GK_PP, FMI_ERR_UNSUPPORTED, "launch_gemm: the dense 4-wave / double-buffered 256-wide kernels live in the test build (libflux_mi355x_alt.so: make alt)"};
+  return {w4 ? GK_W4 : !sw.pingpong ? GK_DB256 : GK_PP, FMI_OK, nullptr};
+}
+
+// the activation kind (epilogue_kind) as a compile-time tag: launch(std::integral_constant<int, 0..3>{})
+template <class F>
+static int with_act(int act, F&& launch) {
+  switch (act) {
+    case 0: return launch(std::integral_constant<int, 0>{});
+    case 1: return launch(std::integral_constant<int, 1>{});
+    case 2: return launch(std::integral_constant<int, 2>{});
+    default: return launch(std::integral_constant<int, 3>{});
+  }
+}
+
+int launch_gemm(const GemmProblem* probs, int nprob, hipStream_t stream) {
+  if (nprob <= 0) return FMI_OK;
+  if (nprob > MAX_PROBLEMS) return fail(FMI_ERR_INVALID, "launch_gemm: too many grouped problems");
+  const int bn = gemm_tile_width(probs, nprob);
+  FMI_TRY(validate_gemm_problems(probs, nprob, bn));
+  const GemmSwitches sw{g_pingpong, g_w4, g_w4q_min_rows, g_w4_qkv_min_n};
+  const GemmTraits t{probs[0].cv_ks != 0 ? GO_CONV : probs[0].q_type != 0 ? GO_Q4 : GO_DENSE, probs[0].fp8, bn,
+                     gemm_w4_pays(probs, nprob, sw.w4_qkv_min_n), gemm_w4q_ok(probs, nprob, sw.w4q_min_rows)};
+  const GemmChoice c = select_gemm_kernel(t, sw, FMI_ALT_KERNELS != 0);
+  if (c.err != FMI_OK) return fail(c.err, c.msg);
+  GemmBatch b;
+  b.nprob = nprob;
+  int total = 0;
+  for (int i = 0; i < nprob; ++i) {
+    b.p[i] = probs[i];
     b.tile_start[i] = total;
-    b.band[i] = pick_tile_band(cdiv(p.M, BM));
-    total += cdiv(p.M, BM) * cdiv(p.N, bn);
+    b.band[i] = pick_tile_band(cdiv(probs[i].M, BM));
+    total += cdiv(probs[i].M, BM) * cdiv(probs[i].N, bn);
   }
   for (int i = nprob; i <= MAX_PROBLEMS; ++i) b.tile_start[i] = total;
   for (int i = nprob; i < MAX_PROBLEMS; ++i) b.band[i] = TILE_BAND;
-  const dim3 grid(total), blk(GEMM_THREADS);
-#define FMI_GEMM_LAUNCH(MODE)                                                               \
-  do {                                                                                      \
-    if (bn == 128)                                                                          \
-      hipLaunchKernelGGL((gemm_bf16_kernel<MODE, 1>), grid, blk, 0, stream, b);             \
-    else                                                                                    \
-      hipLaunchKernelGGL((gemm_bf16_kernel<MODE, 2>), grid, blk, 0, stream, b);             \
-  } while (0)
-  const int act = epilogue_kind(probs, nprob);
-  if (act < 0) return fail(FMI_ERR_INVALID, "launch_gemm: the problems of a grouped launch must share the activation kind");
-  // 4-wave kernel: its K loop is 7-10 % faster, its two-round epilogue slower — measured break-even (tools/gemm_bench,
-  // FMI_EPI=store|gelu|resid on the FLUX shapes): the f32 residual read-modify-write launches at every K (proj -5 %,
-  // mlp2 -10 %, linear2 -7 %), everything else from K = 8192 on (mlp1 + GELU at K = 3072 is a wash).
-  // The launches with the fused q|k|v relayout epilogue stay on the 8-wave kernel: the 4-wave kernels have the epilogue
-  // too (w4_epilogue; the packed 4-bit kernel needs it), but with one workgroup per CU nothing overlaps its two LDS round
-  // trips, and it costs more than the K loop gains (tools/gemm_bench FMI_EPI=qkv, 4608 x 21504 x 3072: 8-wave 588 us,
-  // 4-wave 637 us; 4096 x 9216 x 3072: 258 vs 305 us).  set_gemm_w4_qkv_min_n lowers the bound for experiments.
-  bool w4_pays = !fp8 && !conv && !quant;
-  // 4-bit weights: the one-wave-per-SIMD fused kernel from g_w4q_min_rows rows on (below it the GEMM is bound by the packed
-  // weight stream and the two-workgroups-per-CU kernel with the VGPR expand hides latency better)
-  bool w4q_ok = quant;
-  for (int i = 0; quant && i < nprob; ++i) {
-    const GemmProblem& p = probs[i];
-    const int kb = p.q_blocksize / BK;  // K tiles per absmax block
-    if (p.q_type == 3 || p.M < g_w4q_min_rows || p.K % p.q_blocksize || (kb & (kb - 1)) || (int64_t)p.N * p.K / 2 >= (1ll << 32)) w4q_ok = false;
-  }
-  for (int i = 0; i < nprob; ++i) {
-    const GemmProblem& p = probs[i];
-    if (p.epi != EPI_RESID_GATE_F32 && p.K < 8192 && !(p.qk_qh && p.N >= g_w4_qkv_min_n)) w4_pays = false;
-  }
-#define FMI_ACT_LAUNCH(KERNEL, FP8FLAG, THREADS)                                                    \
-  do {                                                                                              \
-    if (act == 0) hipLaunchKernelGGL((KERNEL<FP8FLAG, 0>), grid, dim3(THREADS), 0, stream, b);      \
-    else if (act == 1) hipLaunchKernelGGL((KERNEL<FP8FLAG, 1>), grid, dim3(THREADS), 0, stream, b); \
-    else if (act == 2) hipLaunchKernelGGL((KERNEL<FP8FLAG, 2>), grid, dim3(THREADS), 0, stream, b); \
-    else hipLaunchKernelGGL((KERNEL<FP8FLAG, 3>), grid, dim3(THREADS), 0, stream, b);               \
-  } while (0)
-  if (fp8 && probs[0].fp8 == 2)
-    FMI_ACT_LAUNCH(gemm_pp_kernel, 2, GEMM_THREADS);
-  else if (fp8)
-    FMI_ACT_LAUNCH(gemm_pp_kernel, 1, GEMM_THREADS);
-  else if (conv)
-    FMI_GEMM_LAUNCH(2);
-  else if (quant && bn == 256 && w4q_ok) {
-    // fused dequant-GEMM, one wave per SIMD (gemm_w4q.h)
-    const dim3 g4(total), b4(W4_THREADS);
-    FMI_LDS_GUARD((gemm_w4q_kernel<0>), W4Q_LUT_BYTES + 4 * A_TILE_BYTES);  // (the four instantiations share the LDS layout)
-    if (act == 0) hipLaunchKernelGGL((gemm_w4q_kernel<0>), g4, b4, 0, stream, b);
-    else if (act == 1) hipLaunchKernelGGL((gemm_w4q_kernel<1>), g4, b4, 0, stream, b);
-    else if (act == 2) hipLaunchKernelGGL((gemm_w4q_kernel<2>), g4, b4, 0, stream, b);
-    else hipLaunchKernelGGL((gemm_w4q_kernel<3>), g4, b4, 0, stream, b);
-  } else if (quant)
-    FMI_GEMM_LAUNCH(1);
+  const bool wide = bn == 256;
+  return with_act(epilogue_kind(probs, nprob), [&](auto act) -> int {
+    constexpr int ACT = decltype(act)::value;
+    auto launch = [&](auto kernel, int threads) { hipLaunchKernelGGL(kernel, dim3(total), dim3(threads), 0, stream, b); };
+    switch (c.kernel) {
+      case GK_DB128: launch(gemm_bf16_kernel<0, 1>, GEMM_THREADS); break;
+      case GK_Q4_DB: wide ? launch(gemm_bf16_kernel<1, 2>, GEMM_THREADS) : launch(gemm_bf16_kernel<1, 1>, GEMM_THREADS); break;
+      case GK_CONV: wide ? launch(gemm_bf16_kernel<2, 2>, GEMM_THREADS) : launch(gemm_bf16_kernel<2, 1>, GEMM_THREADS); break;
+      case GK_PP: launch(gemm_pp_kernel<0, ACT>, GEMM_THREADS); break;
+      case GK_PP_E4M3: launch(gemm_pp_kernel<1, ACT>, GEMM_THREADS); break;
+      case GK_PP_I8: launch(gemm_pp_kernel<2, ACT>, GEMM_THREADS); break;
+      case GK_W4Q:
+        FMI_LDS_GUARD((gemm_w4q_kernel<ACT>), W4Q_LUT_BYTES + 4 * A_TILE_BYTES);  // (once per instantiation; the four share the LDS layout)
+        launch(gemm_w4q_kernel<ACT>, W4_THREADS);
+        break;
 #if FMI_ALT_KERNELS
-  else if (bn == 256 && g_w4 && w4_pays)
-    FMI_ACT_LAUNCH(gemm_w4_kernel, false, W4_THREADS);
-  else if (bn == 256 && !g_pingpong)
-    FMI_GEMM_LAUNCH(0);  // (the double-buffered 256 x 256 kernel: gemm_pp_kernel's bit-identical predecessor)
-#else
-  else if (bn == 256 && ((g_w4 && w4_pays) || !g_pingpong))
-    return fail(FMI_ERR_UNSUPPORTED, "launch_gemm: the dense 4-wave / double-buffered 256-wide kernels live in the test build (libflux_mi355x_alt.so: make alt)");
+      case GK_DB256: launch(gemm_bf16_kernel<0, 2>, GEMM_THREADS); break;
+      case GK_W4: launch(gemm_w4_kernel<ACT>, W4_THREADS); break;
 #endif
-  else if (bn == 256)
-    FMI_ACT_LAUNCH(gemm_pp_kernel, 0, GEMM_THREADS);
-  else
-    hipLaunchKernelGGL((gemm_bf16_kernel<0, 1>), grid, blk, 0, stream, b);  // N <= 128: the 256 x 128 double-buffered kernel
-#undef FMI_GEMM_LAUNCH
-#undef FMI_ACT_LAUNCH
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
+      default: return fail(FMI_ERR_UNSUPPORTED, "launch_gemm: the selected kernel is not part of this build");  // (not reached: select_gemm_kernel refuses GK_DB256 / GK_W4 when !alt)
+    }
+    FMI_LAUNCH_CHECK();
+    return FMI_OK;
+  });
 }
 
 }  // namespace fmi

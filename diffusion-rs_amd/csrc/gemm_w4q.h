@@ -45,29 +45,13 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4q_kernel(const GemmBatch
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  const int total = batch.tile_start[batch.nprob];
-  const int lid = xcd_remap(blockIdx.x, total);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_PROBLEMS; ++i)
-    if (i < batch.nprob && lid >= batch.tile_start[i]) pi = i;
-  const GemmProblem& P = batch.p[pi];
-  const int t_in = lid - batch.tile_start[pi];
-  const int tiles_m = (P.M + BM - 1) / BM;
-  const int tiles_n = (P.N + 255) / 256;
-  int tm, tn;
-  tile_coords(t_in, tiles_m, tiles_n, batch.band[pi], tm, tn);
-  const int m0 = tm * BM, n0 = tn * 256;
-  const int nk = P.K / BK;
+  const GemmTile tile = gemm_tile<256>(batch, 2);  // which problem / tile
+  const GemmProblem& P = tile.P;
+  const int m0 = tile.m0, n0 = tile.n0, nk = tile.nk;
   const int klast = nk - 1;
 
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero(acc);
 
   // (smem sits at LDS byte 0 — the table lookups rely on it: it is the kernel's only __shared__ object, which the host checks before the first launch, FMI_LDS_GUARD)
   {  // packed byte -> the two code values, weight order (high nibble first); fp4: value * sign of the tree in dequant.cu:12-37
@@ -76,7 +60,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4q_kernel(const GemmBatch
     reinterpret_cast<float2*>(smem)[tid] = make_float2(val(tid >> 4), val(tid & 15));  // 256 threads, 256 entries
   }
 
-  // ---- A operand: LDS-DMA pieces of this wave (1-KiB chunks wave*8 + i), as gemm_w4_kernel
+  // ---- A operand: LDS-DMA pieces of this wave (1-KiB chunks wave*8 + i), as gemm_w4_kernel (the text of TileDma: behind the struct hipcc moved loads and stores of the K loop, gemm_frame.h)
   uint32_t a_off[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -194,12 +178,10 @@ __global__ __launch_bounds__(W4_THREADS, 1) void gemm_w4q_kernel(const GemmBatch
   // ---- fragment reads: one VGPR address per (operand, k-step), rebased once per tile; the row block is the immediate
   typedef __attribute__((ext_vector_type(4))) int frag_t;
   frag_t xf[2][4], wf[2][4];
-  const int sw = ((lane & 31) >> 1) & 7;
-  uint32_t koff[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) koff[s] = ((s * 2 + (lane >> 5)) ^ sw) << 4;
-  const uint32_t a_row = A_RING + (wm * 128 + (lane & 31)) * 128;
-  const uint32_t w_row = W_RING + (wn * 128 + (lane & 31)) * 128;
+  const FragSlots<32> frag = frag_slots<32>(lane);  // 32x32x16: k-step s of 16 = 16-byte slot 2 s + (lane >> 5) of the row
+  const int (&koff)[4] = frag.koff;
+  const uint32_t a_row = A_RING + frag.row_off(wm * 128);
+  const uint32_t w_row = W_RING + frag.row_off(wn * 128);
   uint32_t a_ad[4], w_ad[4];
   auto rebase = [&](int slot) {
 #pragma unroll

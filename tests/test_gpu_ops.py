@@ -423,3 +423,48 @@ np.savez(sys.argv[1], **out)
         res[v] = np.load(path)
     for k in res["0"].files:
         np.testing.assert_array_equal(res["0"][k], res["1"][k], err_msg=k)
+
+
+_W4_PRODUCT_PROBE = r'''
+import ctypes as C, sys, numpy as np, torch
+sys.path.insert(0, ".")
+from diffusion_rs_amd import _lib as L
+from tests.util import bf16_round, dev
+lib = L.load()
+p = lambda t: C.c_void_p(t.data_ptr())
+out = {}
+for K in (8192, 64):
+    rng = np.random.default_rng(K)
+    x = dev(bf16_round(rng.standard_normal((64, K)).astype(np.float32)), torch.bfloat16)
+    w = dev(bf16_round((rng.standard_normal((256, K)) / np.sqrt(K)).astype(np.float32)), torch.bfloat16)
+    b = dev(bf16_round(rng.standard_normal(256).astype(np.float32)), torch.bfloat16)
+    y = torch.zeros(64, 256, device="cuda", dtype=torch.bfloat16)
+    out[f"rc{K}"] = lib.fmi_linear_bf16(p(x), p(w), p(b), p(y), 64, 256, K, 0, None)  # epilogue 0 = FMI_EPI_NONE (capi.hip: epi_of -> plain bf16 store)
+    out[f"msg{K}"] = lib.fmi_last_error().decode(errors="replace") if out[f"rc{K}"] else ""
+    torch.cuda.synchronize()
+    out[f"y{K}"] = y.view(torch.int16).cpu().numpy()
+np.savez(sys.argv[1], **out)
+'''
+
+
+def test_gemm_4wave_request_in_the_product_build(tmp_path):
+    """FMI_GEMM_W4=1 with the PRODUCT library: a launch the 4-wave kernel would take (dense, N > 128, K >= 8192) is refused with
+    FMI_ERR_UNSUPPORTED and an error that names the test build — never served by another kernel behind the caller's back — while a
+    launch it would not take (K = 64, plain store) runs on the ping-pong kernel as always: the same bits as without the variable."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for v in ("1", None):
+        path = str(tmp_path / f"w4_product_{v}.npz")
+        env = {k: val for k, val in os.environ.items() if k not in ("FMI_GEMM_W4", "FMI_LIB")}
+        if v:
+            env["FMI_GEMM_W4"] = v
+        subprocess.run([sys.executable, "-c", _W4_PRODUCT_PROBE, path], check=True, cwd=root, env=env, timeout=300)
+        res[v] = np.load(path)
+    assert int(res["1"]["rc8192"]) == -4, res["1"]["rc8192"]  # FMI_ERR_UNSUPPORTED
+    assert "test build" in str(res["1"]["msg8192"]), res["1"]["msg8192"]
+    assert int(res[None]["rc8192"]) == 0 and int(res["1"]["rc64"]) == 0 and int(res[None]["rc64"]) == 0
+    assert res[None]["y64"].any()
+    np.testing.assert_array_equal(res["1"]["y64"], res[None]["y64"])
