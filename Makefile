@@ -53,21 +53,21 @@ $(ALT_LIB): $(ALT_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(ALT_OBJS) -Wl,-soname,libflux_mi355x_alt.so -Wl,-Bsymbolic
 
 # the KV loop of attention_w4_kernel is generated assembly (committed; regenerate after editing the generator)
-$(CSRC)/attention_w4_loop.inc: tools/gen_attention_w4_loop.py
-	python3 tools/gen_attention_w4_loop.py > /dev/null
+$(CSRC)/attention_w4_loop.inc: tools/gen_attention_w4_loop.py tools/attn_stream.py
+	python3 tools/gen_attention_w4_loop.py
 
 # attention_w16_kernel / attention_w32_kernel: the whole KV stream is generated (committed; regenerate after editing a generator)
-$(CSRC)/attention_w16_loop.inc: tools/gen_attention_w16.py
+$(CSRC)/attention_w16_loop.inc: tools/gen_attention_w16.py tools/attn_stream.py
 	python3 tools/gen_attention_w16.py
-$(CSRC)/attention_w16f8_loop.inc: tools/gen_attention_w16.py
+$(CSRC)/attention_w16f8_loop.inc: tools/gen_attention_w16.py tools/attn_stream.py
 	AW16_MODE=fp8qk python3 tools/gen_attention_w16.py
-$(CSRC)/attention_w32_loop.inc: tools/gen_attention_w32.py
+$(CSRC)/attention_w32_loop.inc: tools/gen_attention_w32.py tools/attn_stream.py
 	python3 tools/gen_attention_w32.py
-$(CSRC)/attention_w16l_loop.inc: tools/gen_attention_w16l.py
+$(CSRC)/attention_w16l_loop.inc: tools/gen_attention_w16l.py tools/attn_stream.py
 	python3 tools/gen_attention_w16l.py
-$(CSRC)/attention_w16lf8_loop.inc: tools/gen_attention_w16l.py
+$(CSRC)/attention_w16lf8_loop.inc: tools/gen_attention_w16l.py tools/attn_stream.py
 	AW16L_MODE=fp8qk python3 tools/gen_attention_w16l.py
-$(CSRC)/attention_w16lf8pv_loop.inc: tools/gen_attention_w16l.py
+$(CSRC)/attention_w16lf8pv_loop.inc: tools/gen_attention_w16l.py tools/attn_stream.py
 	AW16L_MODE=fp8pv python3 tools/gen_attention_w16l.py
 
 clean:

@@ -307,6 +307,7 @@ def test_committed_attention_streams_are_what_their_generators_emit(tmp_path):
             ("gen_attention_w16.py", {"AW16_MODE": "fp8qk"}, "attention_w16f8_loop.inc"), ("gen_attention_w32.py", {}, "attention_w32_loop.inc"),
             ("gen_attention_w16l.py", {}, "attention_w16l_loop.inc"), ("gen_attention_w16l.py", {"AW16L_MODE": "fp8qk"}, "attention_w16lf8_loop.inc"),
             ("gen_attention_w16l.py", {"AW16L_MODE": "fp8pv"}, "attention_w16lf8pv_loop.inc")]
+    shutil.copy(os.path.join(ROOT, "tools", "attn_stream.py"), tmp_path / "tools" / "attn_stream.py")  # what the generators import
     for gen, env, out in jobs:
         shutil.copy(os.path.join(ROOT, "tools", gen), tmp_path / "tools" / gen)
         clean = {k: v for k, v in os.environ.items() if not k.startswith(("AW16", "AW32", "AW4"))}

@@ -40,7 +40,7 @@ Stream (n = number of KV tiles >= 2):
       A(t+1)  PV(1,t) + QK(1,t+1) | softmax(0,t+1) | barrier | DMA V^T(t+3)      ; K, V^T address registers -> next slot
     post  PV(1,n-1)
 The fragment stream (each fragment read LOOKAHEAD MFMA slots ahead of its first use, into the buffer of a fragment whose last
-MFMA has left the front of the matrix pipe — rule 3 of DESIGN 4.4, asserted below) is continuous from pre to the loop's end;
+MFMA has left the front of the matrix pipe — rule 3 of DESIGN 4.4, asserted by attn_stream.check_rule3) is continuous from pre to the loop's end;
 post drains and fetches its own first fragments.
 
 fp8 mode (AW16_MODE=fp8qk -> attention_w16f8_loop.inc; BASELINE configs[4]): Q and K arrive as OCP e4m3 bytes with
@@ -63,7 +63,9 @@ Register map (pinned by the operand constraints in attention_w16.h):
   v[184:213]  temporaries (clobbers)   s[80:95] loop state (clobbers)
 """
 import os
-import sys
+
+from attn_stream import (Ablation, Phase, check_rule3, early_reads, emit_phase, lane_group_max, max_chain, rag_flag, scale_accumulators, spread,
+                         write_inc)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = 16384
@@ -73,7 +75,8 @@ LOOKAHEAD = int(os.environ.get("AW16_LOOKAHEAD", "12"))    # a fragment is read 
 MODE = os.environ.get("AW16_MODE", "bf16")  # "bf16" | "fp8qk": Q and K as OCP e4m3 (see the fp8 notes below), P and V^T stay bf16
 FP8 = MODE == "fp8qk"
 TILE_K = 8192 if FP8 else TILE  # bytes of a K tile in LDS (64 keys x 128 d)
-X = os.environ.get("AW16_X", "")  # timing experiments only (wrong results): novalu | noexp | nodma | nobarrier | halfreads | nomfma | nowait
+X = os.environ.get("AW16_X", "")  # timing experiments only (wrong results): novalu | noexp | nodma | nobarrier | halfreads | nomfma | nowait | halfpv | nopv
+ABL = Ablation([X], X[5:].split("+") if X.startswith("drop_") else (), ".Law16")  # | drop_<prefix>+<prefix>: gap instructions with these mnemonic prefixes left out
 
 PMAX, TA, TB, T0, T1, AL, DL = (f"v{n}" for n in range(184, 191))
 XT = [f"v{n}" for n in range(191, 197)]
@@ -126,6 +129,7 @@ def Pr(b, kk, c, d):
 
 
 NBUFK = 4  # fp8 mode: 32-byte K fragments live in their own pool of four 8-register buffers in the accumulator half, a[208:239]
+NBUFS = {"V": NBUF, "K8": NBUFK}
 
 
 def FR(n, pool="V", half=None):
@@ -205,60 +209,70 @@ def qk_frag(f):  # fragment f = 0..15 of a QK^T product: d-step s = f >> 2, key 
     return [(KAD(f >> 2), (a >> 1) * 8192 + (a & 1) * 2048)]
 
 
-class Phase:
-    """One phase: its MFMA slots (the MFMA text with a {fr} hole, and the index of its fragment in the phase's fragment list)
-    and the fragments (address register, immediate) in order of first use."""
-
-    def __init__(self, name, pv_b, qk_b, sm_b, dma, barrier, advance, forced_rescale=False):
-        self.name, self.pv_b, self.qk_b, self.sm_b = name, pv_b, qk_b, sm_b
-        self.dma, self.barrier, self.advance, self.forced_rescale = dma, barrier, advance, forced_rescale
-        self.mfma, self.frags = [], []
-        if pv_b is not None and qk_b is not None:
-            pv, qk = pv_seq(pv_b), qk_seq(qk_b)
-            # alternate PV / QK^T (consecutive MFMAs never share an accumulator); the phase's fragments are numbered in order of first use
-            seq = []
-            if FP8:  # 36 PV MFMAs and 8 score MFMAs: spread the latter evenly
-                npv, nqk, ip, iq = len(pv), len(qk), 0, 0
-                while ip < npv or iq < nqk:
-                    if iq >= nqk or (ip < npv and (ip + 1) * nqk <= (iq + 1) * npv):
-                        t, f = pv[ip]
-                        ip += 1
-                        seq.append((t, None if f is None else ("V", f)))
-                    else:
-                        t, f = qk[iq]
-                        iq += 1
-                        seq.append((t, ("K", f)))
-                pv, qk = [], []
-            while pv or qk:
-                if pv:
-                    t, f = pv.pop(0)
+def phase(name, uid, pv_b, qk_b, sm_b=None, dma=None, barrier=False, advance="", forced_rescale=False):
+    """One phase (attn_stream.Phase): its MFMA slots (the MFMA text with a {fr} hole, and the index of its fragment in the phase's fragment
+    list), the fragments (address register, immediate) in order of first use, and where its softmax, DMA pieces, barrier and ring-slot
+    advance go."""
+    mfma, frags = [], []
+    if pv_b is not None and qk_b is not None:
+        pv, qk = pv_seq(pv_b), qk_seq(qk_b)
+        # alternate PV / QK^T (consecutive MFMAs never share an accumulator); the phase's fragments are numbered in order of first use
+        seq = []
+        if FP8:  # 36 PV MFMAs and 8 score MFMAs: spread the latter evenly
+            npv, nqk, ip, iq = len(pv), len(qk), 0, 0
+            while ip < npv or iq < nqk:
+                if iq >= nqk or (ip < npv and (ip + 1) * nqk <= (iq + 1) * npv):
+                    t, f = pv[ip]
+                    ip += 1
                     seq.append((t, None if f is None else ("V", f)))
-                if qk:
-                    t, f = qk.pop(0)
+                else:
+                    t, f = qk[iq]
+                    iq += 1
                     seq.append((t, ("K", f)))
-            index = {}
-            for t, key in seq:
-                if key is not None and key not in index:
-                    index[key] = len(self.frags)
-                    self.frags.append(pv_frag(key[1]) if key[0] == "V" else qk_frag(key[1]))
-                self.mfma.append((t, None if key is None else index[key]))
-        else:
-            self.mfma = pv_seq(pv_b) if pv_b is not None else qk_seq(qk_b)
-            nfr = 1 + max(f for _, f in self.mfma if f is not None)
-            self.frags = [pv_frag(f) if pv_b is not None else qk_frag(f) for f in range(nfr)]
-        self.n = len(self.mfma)
-        self.fu = [min(i for i, (_, ff) in enumerate(self.mfma) if ff == f) for f in range(len(self.frags))]
-        self.lu = [max(i for i, (_, ff) in enumerate(self.mfma) if ff == f) for f in range(len(self.frags))]
-        assert self.fu == sorted(self.fu), self.fu
-        # fragment buffers: per pool, numbered in order of first use; a phase's span in each pool is padded to a multiple of the
-        # pool size, so every phase starts at buffer 0 of both pools
-        self.pool = ["K8" if len(fr) == 2 else "V" for fr in self.frags]
-        self.bpos, cnt = [], {"V": 0, "K8": 0}
-        for pl in self.pool:
-            self.bpos.append(cnt[pl])
-            cnt[pl] += 1
-        self.span = {"V": -(-cnt["V"] // NBUF) * NBUF, "K8": -(-cnt["K8"] // NBUFK) * NBUFK}
-        self.buf0 = 0
+            pv, qk = [], []
+        while pv or qk:
+            if pv:
+                t, f = pv.pop(0)
+                seq.append((t, None if f is None else ("V", f)))
+            if qk:
+                t, f = qk.pop(0)
+                seq.append((t, ("K", f)))
+        index = {}
+        for t, key in seq:
+            if key is not None and key not in index:
+                index[key] = len(frags)
+                frags.append(pv_frag(key[1]) if key[0] == "V" else qk_frag(key[1]))
+            mfma.append((t, None if key is None else index[key]))
+    else:
+        mfma = pv_seq(pv_b) if pv_b is not None else qk_seq(qk_b)
+        nfr = 1 + max(f for _, f in mfma if f is not None)
+        frags = [pv_frag(f) if pv_b is not None else qk_frag(f) for f in range(nfr)]
+    # fragment buffers: per pool, numbered in order of first use; every phase's fragment count is a multiple of the pool size (16 / 32 bf16
+    # fragments, 4 fp8 K fragments), so every phase starts at buffer 0 of both pools
+    ph = Phase(name, mfma, frags, ["K8" if len(fr) == 2 else "V" for fr in frags], 4, LOOKAHEAD)
+    assert all(c % NBUFS[pl] == 0 for pl, c in ph.count.items()), name
+    n = ph.n
+    if X == "halfpv":  # every second PV MFMA pair dropped: what would fp8 P V buy?
+        ph.mfma = [("s_nop 0", f) if f is not None and ph.pool[f] == "V" and (i // 2) % 2 else (t, f) for i, (t, f) in enumerate(mfma)]
+    if X == "nopv":
+        ph.mfma = [("s_nop 0", f) if f is None or ph.pool[f] == "V" else (t, f) for t, f in mfma]
+    if sm_b is not None:
+        ph.valu = softmax_plan(n, sm_b, forced_rescale, uid)
+    ph.advance = ([(KAD(s_), S_MKK) for s_ in range(2 if FP8 else 4)] if "K" in advance else []) + ([(VAD(k_), S_MKV) for k_ in range(2)] if "V" in advance else [])
+    # ---- DMA pieces (4 per phase): B stages K(tile) once per quarter, A stages V^T(tile) in the second half (behind the barrier)
+    q = n // 4
+    for i in range(n):
+        if dma == "K" and i % q == q // 2 - 1 and i // q < (2 if FP8 else 4):
+            piece = i // q
+            ph.dma[i] = ([f"s_add_i32 m0, {S_M0K}, {piece * 1024}", f"v_cndmask_b32 {DMAT}, v{134 + piece}, v{142 + piece}, {S_MASK}"],
+                         f"global_load_lds_dwordx4 {DMAT}, {S_KP}")
+        if dma == "V" and i >= n // 2 and (i - n // 2) % (n // 8) == n // 8 - 1:
+            piece = (i - n // 2) // (n // 8)
+            ph.dma[i] = ([f"s_add_i32 m0, {S_M0V}, {piece * 1024}"], f"global_load_lds_dwordx4 v{138 + piece}, {S_VP}")
+    if barrier:
+        # everything but this wave's newest pieces — V^T(t+2) [4] and K(t+3) [4; 2 in fp8 mode] — has landed: K(t+2), V^T(t+1)
+        ph.barrier = ("after", n // 2, [f"s_waitcnt vmcnt({4 + (2 if FP8 else 4)})", "s_barrier"])
+    return ph
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -274,17 +288,6 @@ def mask_block(b):
             out.append(f"v_cmp_le_i32 vcc, {S_TMP2}, {LKEY}")
             for c in range(2):
                 out.append(f"v_cndmask_b32 {Sr(b, a, c, i)}, {Sr(b, a, c, i)}, {T1}, vcc")
-    return out
-
-
-def max_chain(dst, regs):
-    out = [f"v_max3_f32 {dst}, {regs[0]}, {regs[1]}, {regs[2]}"]
-    k = 3
-    while k + 1 < len(regs):
-        out.append(f"v_max3_f32 {dst}, {dst}, {regs[k]}, {regs[k + 1]}")
-        k += 2
-    if k < len(regs):
-        out.append(f"v_max_f32 {dst}, {dst}, {regs[k]}")
     return out
 
 
@@ -312,21 +315,7 @@ def rescale_block(b):
     out = []
     for c, pm in ((0, PM0), (1, PM1)):
         out += max_chain(pm, [Sr(b, a, c, i) for a in range(4) for i in range(4)])
-    # reduce over the four lane groups (lanes n, n + 16, n + 32, n + 48 hold the same query): after the first swap the lower half
-    # of the wave works on query 0 and the upper half on query 1; the last swap hands every lane both results
-    out += ["s_nop 1",
-            f"v_permlane32_swap_b32 {PM0}, {PM1}",       # PM0 = [q0.r0, q0.r1, q1.r0, q1.r1]  PM1 = [q0.r2, q0.r3, q1.r2, q1.r3]
-            "s_nop 1",
-            f"v_max_f32 {TA}, {PM0}, {PM1}",
-            f"v_mov_b32 {TB}, {TA}",
-            "s_nop 1",
-            f"v_permlane16_swap_b32 {TA}, {TB}",         # TA = [r0, r0, r2, r2]  TB = [r1, r1, r3, r3]
-            "s_nop 1",
-            f"v_max_f32 {TA}, {TA}, {TB}",
-            f"v_mov_b32 {TB}, {TA}",
-            "s_nop 1",
-            f"v_permlane32_swap_b32 {TA}, {TB}",         # TA = query 0's maximum in every lane, TB = query 1's
-            "s_nop 1"]
+    out += lane_group_max(PM0, PM1, TA, TB)       # TA = query 0's maximum in every lane, TB = query 1's
     for c, ps in ((0, TA), (1, TB)):
         out += [f"v_sub_f32 {T0}, {ps}, {NMr(b, c, 0)}",            # the maximum in the unshifted domain: ps' - NM
                 f"v_max_f32 {T0}, {M(b, c)}, {T0}",                  # m'
@@ -339,13 +328,7 @@ def rescale_block(b):
         out += [f"v_sub_f32 {Sr(b, a, c, i)}, {Sr(b, a, c, i)}, {DL}" for a in range(4) for i in range(4)]
         lo = 192 + (2 * b + c) * 4
         out += [f"v_accvgpr_read_b32 {T1}, a{lo}", f"s_nop 0", f"v_mul_f32 {T1}, {T1}, {AL}", f"s_nop 0", f"v_accvgpr_write_b32 a{lo}, {T1}"]
-        n = len(XT)
-        out.append(f"v_accvgpr_read_b32 {XT[0]}, {Or(b, c, 0)}")
-        for r in range(32):  # software pipeline over the 32 accumulator registers of (b, c)
-            if r + 1 < 32:
-                out.append(f"v_accvgpr_read_b32 {XT[(r + 1) % n]}, {Or(b, c, r + 1)}")
-            out.append(f"v_mul_f32 {XT[r % n]}, {XT[r % n]}, {AL}")
-            out.append(f"v_accvgpr_write_b32 {Or(b, c, r)}, {XT[r % n]}")
+        out += scale_accumulators([Or(b, c, r) for r in range(32)], AL, XT)
     return out
 
 
@@ -375,18 +358,10 @@ def exp_stream(b):
     return out
 
 
-def spread(plan, stream, first, last):
-    """stream instructions over gaps first..last (inclusive), as evenly as integer division allows, in order"""
-    n = last - first + 1
-    for k, ins in enumerate(stream):
-        plan[first + k * n // len(stream)].append(ins)
-
-
-def softmax_plan(ph, uid):
-    """instruction lists per gap for the softmax of ph.sm_b: mask branch, running max, decision + rescale branch, exp stream.
+def softmax_plan(n, b, forced_rescale, uid):
+    """instruction lists per gap for the softmax of block b in a phase of n slots: mask branch, running max, decision + rescale branch, exp stream.
     S^T(b) was finished by the previous phase's last QK^T MFMAs (key block 3 by its very last two): nothing reads it before
     gap 4 (>= 4 MFMAs = 64+ clocks behind; an MFMA result needs ~40)."""
-    b, n = ph.sm_b, ph.n
     plan = [[] for _ in range(n)]
     g_mask = 4 if n >= 16 else 0   # (fp8 mode's first phases are 8 MFMAs long and entered drained: S^T is complete at slot 0)
     skipm = f".Law16_nomask_{uid}_%="
@@ -396,11 +371,11 @@ def softmax_plan(ph, uid):
     g_dec = g_mask + span + 1
     skip, do = f".Law16_skip_{uid}_%=", f".Law16_resc_{uid}_%="
     dec = [f"v_cmp_lt_f32 vcc, %[thr], {PMAX}"]
-    if ph.forced_rescale == "always":      # softmax(0,0): this block's first tile
+    if forced_rescale == "always":      # softmax(0,0): this block's first tile
         dec += []
-    elif ph.forced_rescale == "t0":        # softmax(1,t): first tile when t == 0
+    elif forced_rescale == "t0":        # softmax(1,t): first tile when t == 0
         dec += [f"s_cbranch_vccnz {do}", f"s_cmp_eq_u32 {S_T}, 0", f"s_cbranch_scc0 {skip}", f"{do}:"]
-    elif ph.forced_rescale == "tm1":       # softmax(0,t+1) inside the loop is never a first tile
+    elif forced_rescale == "tm1":       # softmax(0,t+1) inside the loop is never a first tile
         dec += [f"s_cbranch_vccz {skip}"]
     plan[g_dec] += dec + rescale_block(b) + [f"{skip}:"]
     spread(plan, exp_stream(b), g_dec + 1, n - 1)
@@ -408,158 +383,28 @@ def softmax_plan(ph, uid):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
-def emit_phase(ph, nxt, uid, own_prefetch=False, drain=False):
-    """asm lines of one phase.  `nxt` = the phase whose first fragments are fetched behind this phase's last MFMAs (None: none).
-    Fragment f of a phase is read in the gap behind MFMA slot fu[f] - LOOKAHEAD (a negative slot: in the previous phase's tail, or
-    in front of the phase when own_prefetch)."""
-    o = [f"; ==== phase {ph.name}"]
-    n = ph.n
-    nf = len(ph.frags)
-    plan = softmax_plan(ph, uid) if ph.sm_b is not None else [[] for _ in range(n)]
-    # ---- the read instructions of every gap, in stream order: (key, register range, reg, imm); key = (0, f) own fragment f, (1, f) the next phase's
-    def rd_regs(p_, f, k):
-        return FR(p_.bpos[f], p_.pool[f], k if p_.pool[f] == "K8" else None)
-
-    reads = [[] for _ in range(n)]
-    early = []                               # read before slot 0 (previous phase's tail or own prefetch), in order
-    for f, fr in enumerate(ph.frags):
-        i = ph.fu[f] - LOOKAHEAD
-        for k, (reg, imm) in enumerate(fr):
-            (reads[i] if i >= 0 else early).append(((0, f), rd_regs(ph, f, k), reg, imm))
-    own_last_read = max([g for g in range(n) if reads[g]], default=-1)
-    if nxt is not None:
-        for f, fr in enumerate(nxt.frags):
-            i = n + nxt.fu[f] - LOOKAHEAD
-            if i < n:
-                assert i > own_last_read, (ph.name, "next phase's reads must follow the own ones")
-                for k, (reg, imm) in enumerate(fr):
-                    reads[i].append(((1, f), rd_regs(nxt, f, k), reg, imm))
-    if own_prefetch:
-        for (_, b_, reg, imm) in early:
-            o.append(f"ds_read_b128 {b_}, {reg} offset:{imm}")
-    # position of every read in issue order (early ones first); last[f] = position of fragment f's last read
-    order = [key for (key, _, _, _) in early]
-    issued_before_slot = [len(order)]
-    for g in range(n):
-        order += [key for (key, _, _, _) in reads[g]]
-        issued_before_slot.append(len(order))   # issued before MFMA slot g + 1
-    last = {}
-    for k, key in enumerate(order):
-        last[key] = k
-    # ---- ring-slot advance of the address registers: each register right behind the last own read that uses it (the next
-    # phase's reads of that register come later by construction: asserted)
-    adv_at = [[] for _ in range(n)]
-    if ph.advance:
-        regs = ([(KAD(s_), S_MKK) for s_ in range(2 if FP8 else 4)] if "K" in ph.advance else []) + ([(VAD(k_), S_MKV) for k_ in range(2)] if "V" in ph.advance else [])
-        for reg, mask in regs:
-            own = [g for g in range(n) for (key, _, r_, _) in reads[g] if key[0] == 0 and r_ == reg]
-            g_last = max(own, default=0)
-            nxt_use = [g for g in range(n) for (key, _, r_, _) in reads[g] if key[0] == 1 and r_ == reg]
-            assert all(g > g_last for g in nxt_use), (ph.name, reg, g_last, nxt_use)
-            adv_at[g_last].append(f"v_xor_b32 {reg}, {mask}, {reg}")
-    q = n // 4
-    for i in range(n):
-        text, f = ph.mfma[i]
-        pre, post = [], []
-        # ---- DMA pieces (4 per phase): B stages K(tile) once per quarter, A stages V^T(tile) in the second half (behind the barrier)
-        dma = None
-        if ph.dma == "K" and i % q == q // 2 - 1 and i // q < (2 if FP8 else 4) and X != "nodma":
-            piece = i // q
-            pre.append(f"s_add_i32 m0, {S_M0K}, {piece * 1024}")
-            pre.append(f"v_cndmask_b32 {DMAT}, v{134 + piece}, v{142 + piece}, {S_MASK}")
-            dma = f"global_load_lds_dwordx4 {DMAT}, {S_KP}"
-        if ph.dma == "V" and i >= n // 2 and (i - n // 2) % (n // 8) == n // 8 - 1 and X != "nodma":
-            piece = (i - n // 2) // (n // 8)
-            pre.append(f"s_add_i32 m0, {S_M0V}, {piece * 1024}")
-            dma = f"global_load_lds_dwordx4 v{138 + piece}, {S_VP}"
-        # ---- counted wait (LDS reads retire in order) every fourth slot, for every fragment first used in slots i .. i + 3
-        if i % 4 == 0:
-            need = [f2 for f2 in range(nf) if i <= ph.fu[f2] < i + 4]
-            if need:
-                younger = issued_before_slot[i] - last[(0, max(need))] - 1
-                assert 0 <= younger <= 15, (ph.name, i, younger)
-                pre.append(f"s_waitcnt lgkmcnt({younger})")
-        mf = text.format(fr=FR(ph.bpos[f], ph.pool[f])) if f is not None else text
-        rd = [f"ds_read_b128 {b_}, {reg} offset:{imm}" for (_, b_, reg, imm) in reads[i]]
-        post += adv_at[i]
-        post += plan[i]
-        if X == "halfreads":
-            rd = [r_ if k % 2 == 0 else "s_nop 0" for k, r_ in enumerate(rd)] if i % 4 < 2 else ["s_nop 0" for _ in rd]
-        if X == "nomfma":
-            mf = "s_nop 0"
-        if X == "halfpv" and f is not None and ph.pool[f] == "V" and (i // 2) % 2:  # every second PV MFMA pair dropped: what would fp8 P V buy?
-            mf = "s_nop 0"
-        if X == "nopv" and (f is None or ph.pool[f] == "V"):
-            mf = "s_nop 0"
-        if X == "nowait":
-            pre = [p_ for p_ in pre if not p_.startswith("s_waitcnt lgkmcnt")]
-        if X.startswith("drop_"):  # drop every instruction whose mnemonic starts with one of the '+'-separated prefixes
-            pref = tuple(X[5:].split("+"))
-            post = [p_ for p_ in post if not p_.startswith(pref)]
-        if X == "novalu":
-            post = [p_ for p_ in post if p_.startswith(("s_", ".Law16", "v_xor", "v_cmp"))]
-        if X == "noexp":
-            post = [p_.replace("v_exp_f32", "v_mov_b32") for p_ in post]
-        o.append(f"; slot {i}")
-        o += pre + [mf] + rd
-        if dma:
-            o.append(dma)
-        o += post
-        if ph.barrier and i == n // 2 and X != "nobarrier":
-            # everything but this wave's newest pieces — V^T(t+2) [4] and K(t+3) [4; 2 in fp8 mode] — has landed: K(t+2), V^T(t+1)
-            o += [f"s_waitcnt vmcnt({4 + (2 if FP8 else 4)})", "s_barrier"]
-    if drain:
-        o += ["s_waitcnt lgkmcnt(0)", "s_nop 15", "s_nop 15", "s_nop 15"]
-    return o
-
-
-def early_reads(ph):
-    """the reads of ph's fragments that precede its slot 0 (what the previous phase's tail, or an own prefetch, issues), in order"""
-    out = []
-    for f, fr in enumerate(ph.frags):
-        if ph.fu[f] - LOOKAHEAD < 0:
-            for k, (reg, imm) in enumerate(fr):
-                out.append(f"ds_read_b128 {FR(ph.bpos[f], ph.pool[f], k if ph.pool[f] == 'K8' else None)}, {reg} offset:{imm}")
-    return out
-
-
-def check_rule3(seq):
-    """Linearise a sequence of phases and assert that every read refills a buffer whose previous fragment's LAST MFMA sits
-    strictly before the MFMA slot the read is issued behind (so a later MFMA has issued and the old operand has left the front
-    of the matrix pipe), and that reads are issued in stream order."""
-    base, last_user, prev_rd = 0, {}, None
-    for ph in seq:
-        for f, fr in enumerate(ph.frags):
-            rd = base + ph.fu[f] - LOOKAHEAD
-            assert prev_rd is None or rd >= prev_rd, ("stream order", ph.name, f)
-            prev_rd = rd
-            pb = (ph.pool[f], ph.bpos[f] % (NBUFK if ph.pool[f] == "K8" else NBUF))
-            assert last_user.get(pb, -10**9) < rd, ("rule 3", ph.name, f, pb, last_user.get(pb), rd)
-            last_user[pb] = base + ph.lu[f]
-        base += ph.n
-
-
 def build():
-    pre = Phase("pre: QK(0,0)", None, 0, None, None, False, "")
-    a0 = Phase("A0: QK(1,0) | softmax(0,0)", None, 1, 0, "V", True, "K", forced_rescale="always")
-    bt = Phase("B(t): PV(0,t) + QK(0,t+1) | softmax(1,t)", 0, 0, 1, "K", False, "", forced_rescale="t0")
-    at = Phase("A(t+1): PV(1,t) + QK(1,t+1) | softmax(0,t+1)", 1, 1, 0, "V", True, "KV", forced_rescale="tm1")
-    post = Phase("post: PV(1,n-1)", 1, None, None, None, False, "")
+    pre = phase("pre: QK(0,0)", "pre", None, 0)
+    a0 = phase("A0: QK(1,0) | softmax(0,0)", "a0", None, 1, 0, "V", True, "K", forced_rescale="always")
+    bt = phase("B(t): PV(0,t) + QK(0,t+1) | softmax(1,t)", "b", 0, 0, 1, "K", False, "", forced_rescale="t0")
+    at = phase("A(t+1): PV(1,t) + QK(1,t+1) | softmax(0,t+1)", "a", 1, 1, 0, "V", True, "KV", forced_rescale="tm1")
+    post = phase("post: PV(1,n-1)", "post", 1, None)
     return pre, a0, bt, at, post
 
 
 def loop():
     pre, a0, bt, at, post = build()
-    # every phase's fragment count is a multiple of the pool size (16 / 32 bf16 fragments, 4 fp8 K fragments): all start at buffer 0
-    for ph in (pre, a0, bt, at, post):
-        assert ph.span["V"] == sum(1 for p_ in ph.pool if p_ == "V") and ph.span["K8"] == sum(1 for p_ in ph.pool if p_ == "K8"), ph.name
+
+    def emit(ph, nxt, **kw):
+        return emit_phase(ph, nxt, FR, ABL, **kw)
+
     if FP8:  # pre and A0 are only 8 MFMAs long there: each fetches its own first fragments and ends drained (see below)
-        check_rule3([pre])
-        check_rule3([a0])
-        check_rule3([bt, at, bt, at, bt])
+        check_rule3([pre], NBUFS)
+        check_rule3([a0], NBUFS)
+        check_rule3([bt, at, bt, at, bt], NBUFS)
     else:
-        check_rule3([pre, a0, bt, at, bt, at, bt])
-    check_rule3([post])
+        check_rule3([pre, a0, bt, at, bt, at, bt], NBUFS)
+    check_rule3([post], NBUFS)
 
     def dma_setup():
         """scalar state of one loop iteration: the tile both DMA streams fetch, min(t + 3, n - 1), and its ring slot"""
@@ -580,13 +425,6 @@ def loop():
                 f"s_cmp_eq_u32 {S_TILE}, %[ntm1]",
                 f"s_cselect_b64 {S_MASK}, -1, 0"]
 
-    def rag_flag(tile_reg):
-        """S_FLAG = 1 when the softmax of this phase works on the last tile and that tile is ragged"""
-        return [f"s_cmp_eq_u32 {tile_reg}, %[ntm1]",
-                f"s_cselect_b32 {S_FLAG}, 1, 0",
-                f"s_cmp_lt_u32 {S_RAG}, 64",
-                f"s_cselect_b32 {S_FLAG}, {S_FLAG}, 0"]
-
     o = []
     # ---- pre, A0 (= "A(t+1)" with t = -1: it stages V^T(2) and moves the K address registers from slot 0 to slot 1)
     o += [f"s_mov_b32 {S_T}, -1"] + dma_setup()
@@ -597,12 +435,12 @@ def loop():
         # the first two phases are 8 MFMAs each — shorter than the fragment lookahead and with all eight buffers holding their own
         # four 32-byte K fragments — so each fetches its own first fragments and ends drained, and B(0)'s first fragments are
         # fetched here, in front of the loop label, exactly as A(t+1)'s tail fetches them for B(t+1)
-        o += emit_phase(pre, None, "pre", own_prefetch=True, drain=True)
-        o += emit_phase(a0, None, "a0", own_prefetch=True, drain=True)
-        o += early_reads(bt)
+        o += emit(pre, None, own_prefetch=True, drain=True)
+        o += emit(a0, None, own_prefetch=True, drain=True)
+        o += early_reads(bt, FR)
     else:
-        o += emit_phase(pre, a0, "pre", own_prefetch=True)
-        o += emit_phase(a0, bt, "a0")
+        o += emit(pre, a0, own_prefetch=True)
+        o += emit(a0, bt)
     o += [f"s_mov_b32 {S_T}, 0",
           ".Law16_loop_%=:"]
     o += dma_setup()
@@ -613,43 +451,29 @@ def loop():
           f"s_xor_b32 {S_TMP}, {S_TMP}, 1",                    # K leaves slot t + 1
           f"s_lshl_b32 {S_TMP}, {S_TMP}, {(13 if FP8 else 14) + 1}",
           f"s_or_b32 {S_MKK}, {S_TMP}, {TILE_K}"]
-    o += rag_flag(S_T)                                   # B(t): softmax(1, t)
-    o += emit_phase(bt, at, "b")
+    o += rag_flag(S_T, S_FLAG, S_RAG)                                   # B(t): softmax(1, t)
+    o += emit(bt, at)
     o += [f"s_cmp_eq_u32 {S_T}, %[ntm1]",
           "s_cbranch_scc1 .Law16_done_%=",
           f"s_add_i32 {S_TMP}, {S_T}, 1"]
-    o += rag_flag(S_TMP)                                 # A(t+1): softmax(0, t+1)
-    o += emit_phase(at, bt, "a")
+    o += rag_flag(S_TMP, S_FLAG, S_RAG)                                 # A(t+1): softmax(0, t+1)
+    o += emit(at, bt)
     o += [f"s_add_i32 {S_T}, {S_T}, 1",
           "s_branch .Law16_loop_%=",
           ".Law16_done_%=:",
           # B's tail fetched fragments of an A phase that does not follow: let them land, and let B's last MFMAs leave the front of
           # the matrix pipe before post's own fragments refill their buffers (rule 3)
           "s_waitcnt lgkmcnt(0)", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15"]
-    o += emit_phase(post, None, "post", own_prefetch=True, drain=True)
+    o += emit(post, None, own_prefetch=True, drain=True)
     return o
 
 
 def main():
-    lines = loop()
     stem = "attention_w16f8_loop" if FP8 else "attention_w16_loop"
-    path = os.path.join(ROOT, "diffusion-rs_amd", "csrc", stem + ".inc")
-    if X:
-        os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-        path = os.path.join(ROOT, "build", f"{stem}_{X}.inc")
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_attention_w16.py — do not edit.  The whole KV stream of attention_w16_kernel as one asm\n")
-        f.write("// statement (pre, A0, loop { B(t); A(t+1) }, post); register map and schedule: see the generator.\n")
-        f.write(f"#define FMI_AW16{'F8' if FP8 else ''}_LOOP_ASM \\\n")
-        body = ['  "' + ln + '\\n\\t"' for ln in lines if not ln.startswith(";")]
-        f.write(" \\\n".join(body))
-        f.write("\n")
-    if os.environ.get("AW16_DUMP"):
-        with open(os.environ["AW16_DUMP"], "w") as f:
-            f.write("\n".join(lines) + "\n")
-    n_mfma = sum(1 for ln in lines if ln.startswith("v_mfma"))
-    n_other = sum(1 for ln in lines if not ln.startswith(";") and not ln.startswith("v_mfma") and not ln.endswith(":"))
-    print(f"{path}: {len(lines)} lines, {n_mfma} MFMAs, {n_other} other instructions", file=sys.stderr)
+    path = os.path.join(ROOT, "build", f"{stem}_{X}.inc") if X else os.path.join(ROOT, "diffusion-rs_amd", "csrc", stem + ".inc")
+    write_inc(path, ["GENERATED by tools/gen_attention_w16.py — do not edit.  The whole KV stream of attention_w16_kernel as one asm",
+                     "statement (pre, A0, loop { B(t); A(t+1) }, post); register map and schedule: see the generator."],
+              f"FMI_AW16{'F8' if FP8 else ''}_LOOP_ASM", loop(), os.environ.get("AW16_DUMP"))
 
 
 if __name__ == "__main__":

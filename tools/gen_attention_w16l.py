@@ -43,13 +43,16 @@ Register map (pinned by the operand constraints in attention_w16l.h):
   v[208:255]  temporaries (clobbers)   s[80:97] loop state (clobbers)
 """
 import os
-import sys
+
+from attn_stream import (Ablation, Phase, check_rule3, early_reads, emit_phase, lane_group_max, max_chain, rag_flag, scale_accumulators, spread,
+                         write_inc)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = 16384
 VT_RING = 4 * TILE
 NBUF = 8
 NBUFK = 4         # fp8 mode: the 32-byte K fragments have their own pool of four 8-register buffers, a[160:191]
+NBUFS = {"V": NBUF, "K8": NBUFK, "V8": NBUFK}
 MODE = os.environ.get("AW16L_MODE", "bf16")  # "bf16" | "fp8qk": Q and K as OCP e4m3 (the model's fp8 mode), P and V^T stay bf16 -> attention_w16lf8_loop.inc
 #                                              | "fp8pv" (round 5): P and V^T as e4m3 too, second product on v_mfma_f32_32x32x64_f8f6f4 -> attention_w16lf8pv_loop.inc
 PV8 = MODE == "fp8pv"
@@ -57,8 +60,9 @@ FP8 = MODE in ("fp8qk", "fp8pv")
 TILE_K = 8192 if FP8 else TILE  # bytes of a K tile (64 keys x 128 d) in HBM and in LDS
 LOOKAHEAD = int(os.environ.get("AW16L_LOOKAHEAD", "16"))  # a fragment is read this many MFMA slots ahead of its first use (4 fragments in flight)
 X = os.environ.get("AW16L_X", "")  # timing experiments only (wrong results): novalu | noexp | nodma | nobarrier | nomfma | nowait
-XS = set(x for x in X.split("/") if not x.startswith("drop:"))  # (several experiments at once: separated by "/")
-XDROP = next((x[5:] for x in X.split("/") if x.startswith("drop:")), None)
+XDROP = next((x[5:] for x in X.split("/") if x.startswith("drop:")), None)  # drop:<prefix>+<prefix>: gap instructions that start with one of the prefixes are left out ("~" = a space)
+ABL = Ablation([x for x in X.split("/") if not x.startswith("drop:")],  # (several experiments at once: separated by "/"; also nolds | nosetup | halftree)
+               XDROP.replace("~", " ").split("+") if XDROP else (), ".Law16l")
 TAG = os.environ.get("AW16L_TAG", X)  # a tag (or an experiment) writes build/attention_w16l_loop_<tag>.inc instead of the committed file
 EY = int(os.environ.get("AW16L_EY", "8"))  # how many of a tile's 16 exponential units (4 scores each, key-block major) run in the Y phase; the rest in X
 F8_EX = int(os.environ.get("AW16L_F8_EX", "6" if PV8 else "4"))  # fp8 mode: how many of the 16 exponential units (from the last) run in the X phase instead of Y
@@ -194,59 +198,50 @@ ONESF = "v[200:203]"
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
-class Phase:
-    """One phase: its MFMA slots (text with a {fr} hole + the index of the slot's fragment) and its fragments (address register,
-    immediate) in order of first use.  kind "X": S^T(buf) = K Q^T; kind "Y": O^T += V^T P^T and the ones row."""
-
-    def __init__(self, name, kind, buf=None):
-        self.name, self.kind, self.buf = name, kind, buf
-        self.mfma, self.frags = [], []
-        if kind == "X" and FP8:
-            # one v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 score tile: the whole head dimension in one instruction, whose E8M0 block
-            # scales carry the score factor 2^-n; fragment a = the key block's 32 bytes per lane (two reads: KAD[0], KAD[1] = KAD[0] ^ 16)
-            for a in range(4):
-                # the key whose score sits in row m of block a: 32 (a >> 1) + 8 (a & 1) + (m & 7) + 16 (m >> 3); fp8pv: 8 a + (m & 7) + 32 (m >> 3), so that a
-                # lane's 32 operand bytes of the second product are 32 consecutive keys (plan_x_pv8)
-                imm = a * 1024 if PV8 else (a >> 1) * 4096 + (a & 1) * 1024
-                self.frags.append([(KAD(0), imm), (KAD(1), imm)])
+def phase(name, kind, buf=None):
+    """One phase (attn_stream.Phase): its MFMA slots (text with a {fr} hole + the index of the slot's fragment) and its fragments (address register,
+    immediate) in order of first use.  kind "X": S^T(buf) = K Q^T; kind "Y": O^T += V^T P^T and the ones row.  build() adds what fills the gaps."""
+    mfma, frags = [], []
+    if kind == "X" and FP8:
+        # one v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 score tile: the whole head dimension in one instruction, whose E8M0 block
+        # scales carry the score factor 2^-n; fragment a = the key block's 32 bytes per lane (two reads: KAD[0], KAD[1] = KAD[0] ^ 16)
+        for a in range(4):
+            # the key whose score sits in row m of block a: 32 (a >> 1) + 8 (a & 1) + (m & 7) + 16 (m >> 3); fp8pv: 8 a + (m & 7) + 32 (m >> 3), so that a
+            # lane's 32 operand bytes of the second product are 32 consecutive keys (plan_x_pv8)
+            imm = a * 1024 if PV8 else (a >> 1) * 4096 + (a & 1) * 1024
+            frags.append([(KAD(0), imm), (KAD(1), imm)])
+            for q in range(4):
+                mfma.append((f"v_mfma_scale_f32_16x16x128_f8f6f4 {S(buf, a, q)}, {{fr}}, {QF8(q)}, {NM(q)}, {SCA}, {SCB}", a))
+    elif kind == "X":
+        for s in range(4):          # d-step (32 of the 128 head dimensions)
+            for a in range(4):      # key block (16 keys)
+                frags.append([(KAD(s), (a >> 1) * 8192 + (a & 1) * 2048)])
                 for q in range(4):
-                    self.mfma.append((f"v_mfma_scale_f32_16x16x128_f8f6f4 {S(buf, a, q)}, {{fr}}, {QF8(q)}, {NM(q)}, {SCA}, {SCB}", a))
-        elif kind == "X":
-            for s in range(4):          # d-step (32 of the 128 head dimensions)
-                for a in range(4):      # key block (16 keys)
-                    self.frags.append([(KAD(s), (a >> 1) * 8192 + (a & 1) * 2048)])
-                    for q in range(4):
-                        acc = NM(q) if s == 0 else S(buf, a, q)  # first d-step: start from -m of the lane's query (the fold)
-                        self.mfma.append((f"v_mfma_f32_16x16x32_bf16 {S(buf, a, q)}, {{fr}}, {QF(q, s)}, {acc}", 4 * s + a))
-        elif PV8:
-            # O^T[32 d x 32 queries] += V^T[32 d x 64 keys] P^T[64 keys x 32 queries]: one v_mfma_f32_32x32x64_f8f6f4 per (d block, query pair), the
-            # whole tile's keys in one instruction; fragment db = 32 bytes per lane (row 32 db + (lane & 31), keys 32 (lane >> 5) ..): two reads
-            for db in range(4):
-                self.frags.append([(VAD(0), db * 2048), (VAD(1), db * 2048)])
-                for pair in range(2):
-                    self.mfma.append((f"v_mfma_f32_32x32x64_f8f6f4 {O8(pair, db)}, {{fr}}, {P8(pair)}, {O8(pair, db)}", db))
-            for pair in range(2):       # V^T extended by a row of ones: the row sums of the e4m3-rounded P
-                self.mfma.append((f"v_mfma_f32_32x32x64_f8f6f4 {OL8(pair)}, {ONES8}, {P8(pair)}, {OL8(pair)}", None))
-        else:
-            for kk in range(2):         # k-step (32 keys)
-                for dt in range(8):     # d block (16 head dimensions)
-                    self.frags.append([(VAD(kk), dt * 2048)])
-                    for q in range(4):
-                        self.mfma.append((f"v_mfma_f32_16x16x32_bf16 {O(q, dt)}, {{fr}}, {P(kk, q)}, {O(q, dt)}", 8 * kk + dt))
-                for q in range(4):      # V^T extended by a row of ones: the row sums of the bf16-rounded P
-                    self.mfma.append((f"v_mfma_f32_16x16x32_bf16 {OL(q)}, {ONESF}, {P(kk, q)}, {OL(q)}", None))
-        self.n = len(self.mfma)
-        nf = len(self.frags)
-        self.fu = [min(i for i, (_, ff) in enumerate(self.mfma) if ff == f) for f in range(nf)]
-        self.lu = [max(i for i, (_, ff) in enumerate(self.mfma) if ff == f) for f in range(nf)]
-        self.pool = "K8" if (kind == "X" and FP8) else "V8" if PV8 else "V"
-        assert self.fu == sorted(self.fu) and nf % (NBUFK if self.pool != "V" else NBUF) == 0
-        # where a fragment is read, in MFMA slots relative to the phase's slot 0 (negative: in the previous phase, counted from its end).
-        # fp8pv: the slots are not of one length (32 clocks in X, 64 in Y) — a table with >= ~200 clocks of lead; otherwise LOOKAHEAD slots
-        self.rd = ([-4, -2, 2, 6] if kind == "X" else [-7, -3, 0, 2]) if PV8 else [self.fu[f] - LOOKAHEAD for f in range(nf)]
-        self.wg = 2 if (PV8 and kind == "Y") else 4  # counted waits every wg slots
-        # set by build(): valu (list of instruction lists per gap), dma ("K" | "V" | None), barrier, advance ((regs, xor mask) applied behind the last own read)
-        self.valu, self.dma, self.barrier, self.advance = [[] for _ in range(self.n)], None, False, None
+                    acc = NM(q) if s == 0 else S(buf, a, q)  # first d-step: start from -m of the lane's query (the fold)
+                    mfma.append((f"v_mfma_f32_16x16x32_bf16 {S(buf, a, q)}, {{fr}}, {QF(q, s)}, {acc}", 4 * s + a))
+    elif PV8:
+        # O^T[32 d x 32 queries] += V^T[32 d x 64 keys] P^T[64 keys x 32 queries]: one v_mfma_f32_32x32x64_f8f6f4 per (d block, query pair), the
+        # whole tile's keys in one instruction; fragment db = 32 bytes per lane (row 32 db + (lane & 31), keys 32 (lane >> 5) ..): two reads
+        for db in range(4):
+            frags.append([(VAD(0), db * 2048), (VAD(1), db * 2048)])
+            for pair in range(2):
+                mfma.append((f"v_mfma_f32_32x32x64_f8f6f4 {O8(pair, db)}, {{fr}}, {P8(pair)}, {O8(pair, db)}", db))
+        for pair in range(2):       # V^T extended by a row of ones: the row sums of the e4m3-rounded P
+            mfma.append((f"v_mfma_f32_32x32x64_f8f6f4 {OL8(pair)}, {ONES8}, {P8(pair)}, {OL8(pair)}", None))
+    else:
+        for kk in range(2):         # k-step (32 keys)
+            for dt in range(8):     # d block (16 head dimensions)
+                frags.append([(VAD(kk), dt * 2048)])
+                for q in range(4):
+                    mfma.append((f"v_mfma_f32_16x16x32_bf16 {O(q, dt)}, {{fr}}, {P(kk, q)}, {O(q, dt)}", 8 * kk + dt))
+            for q in range(4):      # V^T extended by a row of ones: the row sums of the bf16-rounded P
+                mfma.append((f"v_mfma_f32_16x16x32_bf16 {OL(q)}, {ONESF}, {P(kk, q)}, {OL(q)}", None))
+    pool = "K8" if (kind == "X" and FP8) else "V8" if PV8 else "V"
+    assert len(frags) % NBUFS[pool] == 0
+    # where a fragment is read, in MFMA slots relative to the phase's slot 0 (negative: in the previous phase, counted from its end).
+    # fp8pv: the slots are not of one length (32 clocks in X, 64 in Y) — a table with >= ~200 clocks of lead; otherwise LOOKAHEAD slots
+    rd = ([-4, -2, 2, 6] if kind == "X" else [-7, -3, 0, 2]) if PV8 else None
+    return Phase(name, mfma, frags, pool, 2 if (PV8 and kind == "Y") else 4, LOOKAHEAD, rd)  # (counted waits every 4 slots; fp8pv's Y: every 2)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -278,17 +273,6 @@ def mask_block(buf):
             out.append(f"v_cmp_le_i32 vcc, {S_TMP2}, {LKEY}")
             for q in range(4):
                 out.append(f"v_cndmask_b32 {Sr(buf, a, q, i)}, {Sr(buf, a, q, i)}, {T1}, vcc")
-    return out
-
-
-def max_chain(dst, regs):
-    out = [f"v_max3_f32 {dst}, {regs[0]}, {regs[1]}, {regs[2]}"]
-    k = 3
-    while k + 1 < len(regs):
-        out.append(f"v_max3_f32 {dst}, {dst}, {regs[k]}, {regs[k + 1]}")
-        k += 2
-    if k < len(regs):
-        out.append(f"v_max_f32 {dst}, {dst}, {regs[k]}")
     return out
 
 
@@ -331,21 +315,7 @@ def rescale_s(buf, set_flag):
     for b in range(2):
         for c, pm in ((0, PM0), (1, PM1)):
             out += max_chain(pm, [Sr(buf, a, 2 * b + c, i) for a in range(4) for i in range(4)])
-        # reduce over the four lane groups (lanes n, n + 16, n + 32, n + 48 hold the same query): after the first swap the lower half
-        # of the wave works on query block 2b and the upper half on 2b + 1; the last swap hands every lane both results
-        out += ["s_nop 1",
-                f"v_permlane32_swap_b32 {PM0}, {PM1}",
-                "s_nop 1",
-                f"v_max_f32 {TA}, {PM0}, {PM1}",
-                f"v_mov_b32 {TB}, {TA}",
-                "s_nop 1",
-                f"v_permlane16_swap_b32 {TA}, {TB}",
-                "s_nop 1",
-                f"v_max_f32 {TA}, {TA}, {TB}",
-                f"v_mov_b32 {TB}, {TA}",
-                "s_nop 1",
-                f"v_permlane32_swap_b32 {TA}, {TB}",         # TA = block 2b's maximum in every lane, TB = block 2b + 1's
-                "s_nop 1"]
+        out += lane_group_max(PM0, PM1, TA, TB)       # TA = block 2b's maximum in every lane, TB = block 2b + 1's
         for c, ps in ((0, TA), (1, TB)):
             q = 2 * b + c
             out += [f"v_sub_f32 {T0}, {ps}, {NMr(q, 0)}",            # the maximum in the unshifted domain: ps' - NM
@@ -369,13 +339,7 @@ def rescale_o():
     for q in range(4):
         lo = 192 + q * 4
         out += [f"v_accvgpr_read_b32 {T1}, a{lo}", "s_nop 0", f"v_mul_f32 {T1}, {T1}, {ALPHA(q)}", "s_nop 0", f"v_accvgpr_write_b32 a{lo}, {T1}"]
-        n = len(XT)
-        out.append(f"v_accvgpr_read_b32 {XT[0]}, {Or(q, 0)}")
-        for r in range(32):  # software pipeline over the 32 accumulator registers of block q
-            if r + 1 < 32:
-                out.append(f"v_accvgpr_read_b32 {XT[(r + 1) % n]}, {Or(q, r + 1)}")
-            out.append(f"v_mul_f32 {XT[r % n]}, {XT[r % n]}, {ALPHA(q)}")
-            out.append(f"v_accvgpr_write_b32 {Or(q, r)}, {XT[r % n]}")
+        out += scale_accumulators([Or(q, r) for r in range(32)], ALPHA(q), XT)
     out.append(f"s_mov_b32 {S_RESC}, 0")
     return out
 
@@ -405,19 +369,12 @@ def exp_pack_stream(buf, units, SKEW=2):
     return out
 
 
-def spread(plan, stream, first, last):
-    """stream instructions over gaps first..last (inclusive), as evenly as integer division allows, in order"""
-    n = last - first + 1
-    for k, ins in enumerate(stream):
-        plan[first + k * n // len(stream)].append(ins)
-
-
 def plan_y(ph, buf, uid):
     """Y(t)'s gaps: mask (ragged last tile), max tree, decision (+ rare rescale of S / M / NM), first half of the exponentials — of tile
     t + 1 in S^T buffer `buf`, which the X phase in front of this one completed (its last MFMAs are >= 4 slots behind gap 4)."""
     n, plan = ph.n, ph.valu
     plan[4] += rare("nomask", uid, "s_cbranch_scc1", "s_cbranch_scc0", mask_block(buf), [f"s_cmp_eq_u32 {S_FLAG}, 0"])
-    if not ("halftree" in XS and uid == "yo"):  # (timing experiment: the maximum taken on every other tile only)
+    if not ("halftree" in ABL and uid == "yo"):  # (timing experiment: the maximum taken on every other tile only)
         spread(plan, max_tree(buf), 5, TREE_END)
         plan[TREE_END + 2] += rare("skip", uid, "s_cbranch_vccz", "s_cbranch_vccnz", rescale_s(buf, True), [f"v_cmp_lt_f32 vcc, %[thr], {PMAX}"])
     spread(plan, [i for (a, q) in UNITS[:EY] for i in exps(buf, a, q)], TREE_END + 3, n - 1)
@@ -479,7 +436,7 @@ def plan_p1_f8(ph, uid):
 # So: four scores -> one dword of e4m3 (two v_cvt_pk_fp8_f32), the dwords of the pair's two query blocks in neighbouring registers, and one
 # v_permlane16_swap_b32 per (pair, a) hands the odd groups' block-0 dword to the even groups and the even groups' block-1 dword to the odd
 # ones.  Afterwards register 2 a (+1) of lane (g, n) = key rows 8 (g >> 1) + 0..3 (4..7) of block a, i.e. with the key of (a, row m) chosen as
-# 8 a + (m & 7) + 32 (m >> 3) (Phase: the K fragment immediates) byte j of the lane's operand is key 32 (g >> 1) + j: V^T is read in plain order.
+# 8 a + (m & 7) + 32 (m >> 3) (phase(): the K fragment immediates) byte j of the lane's operand is key 32 (g >> 1) + j: V^T is read in plain order.
 def cvts8(buf, a, q):
     d = P8r(q >> 1, a, q & 1)
     return [f"v_cvt_pk_fp8_f32 {d}, {Sr(buf, a, q, 0)}, {Sr(buf, a, q, 1)}",
@@ -513,17 +470,11 @@ def rescale_o_pv8():
     """fp8pv form of rescale_o: the 32 x 32 accumulators of a pair hold query block 2 pair in the even 16-lane groups and 2 pair + 1 in the
     odd ones — alpha is selected per lane (S_GODD)."""
     out = []
-    n = len(XT)
     for pair in range(2):
         lo = 240 if pair else 192
         out += [f"v_cndmask_b32 {AL}, {ALPHA(2 * pair)}, {ALPHA(2 * pair + 1)}, {S_GODD}",
                 f"v_accvgpr_read_b32 {T1}, a{lo}", "s_nop 0", f"v_mul_f32 {T1}, {T1}, {AL}", "s_nop 0", f"v_accvgpr_write_b32 a{lo}, {T1}"]
-        out.append(f"v_accvgpr_read_b32 {XT[0]}, {O8r(pair, 0)}")
-        for r in range(64):
-            if r + 1 < 64:
-                out.append(f"v_accvgpr_read_b32 {XT[(r + 1) % n]}, {O8r(pair, r + 1)}")
-            out.append(f"v_mul_f32 {XT[r % n]}, {XT[r % n]}, {AL}")
-            out.append(f"v_accvgpr_write_b32 {O8r(pair, r)}, {XT[r % n]}")
+        out += scale_accumulators([O8r(pair, r) for r in range(64)], AL, XT)
     out.append(f"s_mov_b32 {S_RESC}, 0")
     return out
 
@@ -576,128 +527,29 @@ def plan_p1(ph, uid):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
-def emit_phase(ph, nxt, own_prefetch=False, drain=False):
-    """asm lines of one phase.  `nxt` = the phase whose first fragments are fetched behind this phase's last MFMAs (None: none).
-    Fragment f of a phase is read in the gap behind MFMA slot fu[f] - LOOKAHEAD (a negative slot: in the previous phase's tail, or in
-    front of the phase when own_prefetch)."""
-    o = [f"; ==== phase {ph.name}"]
-    n, nf = ph.n, len(ph.frags)
-    reads = [[] for _ in range(n)]
-    early = []
-    def dest(p_, f, k):
-        return FR(f, p_.pool, k if p_.pool != "V" else None)
-
-    for f, fr in enumerate(ph.frags):
-        i = ph.rd[f]
-        for k, (reg, imm) in enumerate(fr):
-            (reads[i] if i >= 0 else early).append(((0, f), dest(ph, f, k), reg, imm))
-    own_last_read = max([g for g in range(n) if reads[g]], default=-1)
-    if nxt is not None:
-        for f, fr in enumerate(nxt.frags):
-            i = n + nxt.rd[f]
-            if i < n:
-                assert i > own_last_read, (ph.name, "next phase's reads must follow the own ones")
-                for k, (reg, imm) in enumerate(fr):
-                    reads[i].append(((1, f), dest(nxt, f, k), reg, imm))
-    if own_prefetch:
-        for (_, b_, reg, imm) in early:
-            o.append(f"ds_read_b128 {b_}, {reg} offset:{imm}")
-    order = [key for (key, _, _, _) in early]
-    issued_before_slot = [len(order)]
-    for g in range(n):
-        order += [key for (key, _, _, _) in reads[g]]
-        issued_before_slot.append(len(order))
-    last = {}
-    for k, key in enumerate(order):
-        last[key] = k
-    # ring-slot advance of the address registers: each right behind the last own read that uses it
-    adv_at = [[] for _ in range(n)]
-    if ph.advance:
-        regs, mask = ph.advance
-        for reg in regs:
-            own = [g for g in range(n) for (key, _, r_, _) in reads[g] if key[0] == 0 and r_ == reg]
-            g_last = max(own, default=0)
-            nxt_use = [g for g in range(n) for (key, _, r_, _) in reads[g] if key[0] == 1 and r_ == reg]
-            assert all(g > g_last for g in nxt_use), (ph.name, reg, g_last, nxt_use)
-            adv_at[g_last].append(f"v_xor_b32 {reg}, 0x{mask:x}, {reg}")
+def dma_pieces(n, what):
+    """{slot: (lines in front of the MFMA, DMA instruction)} of a phase of n slots.  "K": 4 pieces (fp8: 2), one per quarter; "V": 4 pieces in
+    the second half, behind the barrier (fp8pv: a V^T tile is 8 KiB, 2 pieces)"""
+    out = {}
     for i in range(n):
-        text, f = ph.mfma[i]
-        pre, post = [], []
-        dma = None
-        if ph.dma == "K" and i % (n // 4) == n // 8 - 1 and i // (n // 4) < (2 if FP8 else 4) and "nodma" not in XS:  # 4 pieces (fp8: 2), one per quarter
+        if what == "K" and i % (n // 4) == n // 8 - 1 and i // (n // 4) < (2 if FP8 else 4):
             piece = i // (n // 4)
-            pre.append(f"s_add_i32 m0, {S_M0K}, {piece * 1024}")
-            pre.append(f"v_cndmask_b32 {DMAT}, v{166 + piece}, v{174 + piece}, {S_MASKK}")
-            dma = f"global_load_lds_dwordx4 {DMAT}, {S_KP}"
-        if ph.dma == "V" and i >= n // 2 and (i - n // 2) % (n // 8) == n // 8 - 1 and "nodma" not in XS and (
-                not PV8 or (i - n // 2) // (n // 8) < 2):   # 4 pieces in the second half, behind the barrier (fp8pv: a V^T tile is 8 KiB, 2 pieces)
+            out[i] = ([f"s_add_i32 m0, {S_M0K}, {piece * 1024}", f"v_cndmask_b32 {DMAT}, v{166 + piece}, v{174 + piece}, {S_MASKK}"],
+                      f"global_load_lds_dwordx4 {DMAT}, {S_KP}")
+        if what == "V" and i >= n // 2 and (i - n // 2) % (n // 8) == n // 8 - 1 and (not PV8 or (i - n // 2) // (n // 8) < 2):
             piece = (i - n // 2) // (n // 8)
-            pre.append(f"s_add_i32 m0, {S_M0V}, {piece * 1024}")
-            dma = f"global_load_lds_dwordx4 v{170 + piece}, {S_VP}"
-        if i % ph.wg == 0:  # counted wait (LDS reads retire in order) for every fragment first used in slots i .. i + 3
-            need = [f2 for f2 in range(nf) if i <= ph.fu[f2] < i + ph.wg]
-            if need:
-                younger = issued_before_slot[i] - last[(0, max(need))] - 1
-                assert 0 <= younger <= 15, (ph.name, i, younger)
-                pre.append(f"s_waitcnt lgkmcnt({younger})")
-        mf = text.format(fr=FR(f, ph.pool)) if f is not None else text
-        rd = [f"ds_read_b128 {b_}, {reg} offset:{imm}" for (_, b_, reg, imm) in reads[i]]
-        post += adv_at[i]
-        post += ph.valu[i]
-        if "nomfma" in XS:
-            mf = "s_nop 0"
-        if "nowait" in XS:
-            pre = [p_ for p_ in pre if not p_.startswith("s_waitcnt lgkmcnt")]
-        if "novalu" in XS:
-            post = [p_ for p_ in post if p_.startswith(("s_", ".Law16l", "v_xor", "v_cmp"))]
-        if "noexp" in XS:
-            post = [p_.replace("v_exp_f32", "v_mov_b32") for p_ in post]
-        if XDROP:  # drop:<prefix>+<prefix>: the gap instructions that start with one of the prefixes are left out ("~" = a space)
-            post = [p_ for p_ in post if not p_.startswith(tuple(XDROP.replace("~", " ").split("+")))]
-        if "nolds" in XS:
-            rd = []
-        o.append(f"; slot {i}")
-        if ph.barrier and FP8 and i == 0 and "nobarrier" not in XS:
-            # fp8 mode: an X phase is 16 slots long and the NEXT Y phase's first V^T fragments are read from its slot 0 on (look-ahead 16) —
-            # the barrier that publishes V^T(t+1) must stand in front of them (in the bf16 stream those reads start at slot 48, behind
-            # the mid-phase barrier).  Same accounting: the newest V^T(t+2) [4] + K(t+4) [2] pieces may fly.
-            o += [f"s_waitcnt vmcnt({4 if PV8 else 6})", "s_barrier"]
-        o += pre + [mf] + rd
-        if dma:
-            o.append(dma)
-        o += post
-        if ph.barrier and not FP8 and i == n // 2 and "nobarrier" not in XS:
-            # everything but this wave's newest pieces — V^T(t+2) [4] and K(t+4) [4; 2 in fp8 mode] — has landed: K(t+3), V^T(t+1)
-            o += ["s_waitcnt vmcnt(8)", "s_barrier"]
-    if drain:
-        o += ["s_waitcnt lgkmcnt(0)", "s_nop 15", "s_nop 15", "s_nop 15"]
-    return o
-
-
-def early_reads(ph):
-    """the reads of ph's fragments that precede its slot 0 (what the previous phase's tail, or an own prefetch, issues), in order"""
-    out = []
-    for f, fr in enumerate(ph.frags):
-        if ph.rd[f] < 0:
-            for k, (reg, imm) in enumerate(fr):
-                out.append(f"ds_read_b128 {FR(f, ph.pool, k if ph.pool != 'V' else None)}, {reg} offset:{imm}")
+            out[i] = ([f"s_add_i32 m0, {S_M0V}, {piece * 1024}"], f"global_load_lds_dwordx4 v{170 + piece}, {S_VP}")
     return out
 
 
-def check_rule3(seq):
-    """Linearise a sequence of phases and assert that every read refills a buffer whose previous fragment's LAST MFMA sits strictly
-    before the MFMA slot the read is issued behind (so a later MFMA has issued and the old operand has left the front of the matrix
-    pipe — DESIGN 4.4 rule 3), and that reads are issued in stream order."""
-    base, last_user, prev_rd = 0, {}, None
-    for ph in seq:
-        for f in range(len(ph.frags)):
-            rd = base + ph.rd[f]
-            assert prev_rd is None or rd >= prev_rd or PV8, ("stream order", ph.name, f)  # (fp8pv: two pools, each in its own order)
-            prev_rd = rd
-            pb = (ph.pool, f % (NBUFK if ph.pool != "V" else NBUF))
-            assert last_user.get(pb, -10**9) < rd, ("rule 3", ph.name, f, pb, last_user.get(pb), rd)
-            last_user[pb] = base + ph.lu[f]
-        base += ph.n
+def barrier(n):
+    """the one barrier per tile, in an X phase of n slots.  bf16: mid-phase; everything but this wave's newest pieces — V^T(t+2) [4] and K(t+4) [4] —
+    has landed: K(t+3), V^T(t+1).  fp8 mode: an X phase is 16 slots long and the NEXT Y phase's first V^T fragments are read from its slot 0 on
+    (look-ahead 16) — the barrier that publishes V^T(t+1) must stand in front of them (in the bf16 stream those reads start at slot 48, behind
+    the mid-phase barrier).  Same accounting: the newest V^T(t+2) [4; fp8pv 2] + K(t+4) [2] pieces may fly."""
+    if FP8:
+        return ("before", 0, [f"s_waitcnt vmcnt({4 if PV8 else 6})", "s_barrier"])
+    return ("after", n // 2, ["s_waitcnt vmcnt(8)", "s_barrier"])
 
 
 def build():
@@ -705,34 +557,43 @@ def build():
     EVEN, ODD = TILE, 3 * TILE  # ring slot s -> s + 1: xor one slot size out of an even slot, three out of an odd one
     KEVEN, KODD = TILE_K, 3 * TILE_K
     py, px, pp1 = (plan_y_pv8, plan_x_pv8, plan_p1_pv8) if PV8 else (plan_y_f8, plan_x_f8, plan_p1_f8) if FP8 else (plan_y, plan_x, plan_p1)
-    pre = Phase("pre: X(0) -> S0", "X", 0)
-    pre.advance = (K_REGS, KEVEN)                    # K leaves slot 0
-    p1 = Phase("P1: X(1) -> S1 | softmax(0)", "X", 1)
-    p1.advance, p1.barrier = (K_REGS, KODD), True    # K leaves slot 1
+
+    def make(name, kind, buf, regs, mask, dma=None, bar=False):
+        ph = phase(name, kind, buf)
+        ph.advance = [(reg, f"0x{mask:x}") for reg in regs]   # applied behind the last own read through each register
+        ph.dma = dma_pieces(ph.n, dma)
+        ph.barrier = barrier(ph.n) if bar else None
+        return ph
+
+    pre = make("pre: X(0) -> S0", "X", 0, K_REGS, KEVEN)                                      # K leaves slot 0
+    p1 = make("P1: X(1) -> S1 | softmax(0)", "X", 1, K_REGS, KODD, bar=True)                  # K leaves slot 1
     pp1(p1, "p1")
-    ye = Phase("Y(t), t even | softmax 1st half of tile t+1 (S1)", "Y")
-    ye.advance, ye.dma = (V_REGS, EVEN), "K"
+    ye = make("Y(t), t even | softmax 1st half of tile t+1 (S1)", "Y", None, V_REGS, EVEN, "K")
     py(ye, 1, "ye")
-    xe = Phase("X(t+2) -> S0, t even | softmax 2nd half of tile t+1 (S1)", "X", 0)
-    xe.advance, xe.dma, xe.barrier = (K_REGS, KEVEN), "V", True   # t + 2 even
+    xe = make("X(t+2) -> S0, t even | softmax 2nd half of tile t+1 (S1)", "X", 0, K_REGS, KEVEN, "V", True)   # t + 2 even
     px(xe, 1, "xe")
-    yo = Phase("Y(t), t odd | softmax 1st half of tile t+1 (S0)", "Y")
-    yo.advance, yo.dma = (V_REGS, ODD), "K"
+    yo = make("Y(t), t odd | softmax 1st half of tile t+1 (S0)", "Y", None, V_REGS, ODD, "K")
     py(yo, 0, "yo")
-    xo = Phase("X(t+2) -> S1, t odd | softmax 2nd half of tile t+1 (S0)", "X", 1)
-    xo.advance, xo.dma, xo.barrier = (K_REGS, KODD), "V", True
+    xo = make("X(t+2) -> S1, t odd | softmax 2nd half of tile t+1 (S0)", "X", 1, K_REGS, KODD, "V", True)
     px(xo, 0, "xo")
     return pre, p1, ye, xe, yo, xo
 
 
 def stream():
     pre, p1, ye, xe, yo, xo = build()
+
+    def emit(ph, nxt, **kw):
+        return emit_phase(ph, nxt, FR, ABL, **kw)
+
+    def rule3(seq):
+        check_rule3(seq, NBUFS, ordered=not PV8)   # (fp8pv: two pools, each in its own order)
+
     if FP8:  # pre and P1 are 16 MFMAs each, as long as the look-ahead and back to back on the same four K buffers: each fetches its own
-        check_rule3([pre])  # fragments and ends drained, and Y(0)'s first fragments are fetched in front of the loop label
-        check_rule3([p1])
-        check_rule3([ye, xe, yo, xo, ye, xe, yo, xo, ye])
+        rule3([pre])  # fragments and ends drained, and Y(0)'s first fragments are fetched in front of the loop label
+        rule3([p1])
+        rule3([ye, xe, yo, xo, ye, xe, yo, xo, ye])
     else:
-        check_rule3([pre, p1, ye, xe, yo, xo, ye, xe, yo, xo, ye])
+        rule3([pre, p1, ye, xe, yo, xo, ye, xe, yo, xo, ye])
 
     def dma_setup():
         """scalar state of one tile: K(min(t + 4, n - 1)) and V^T(min(t + 3, n - 1)): HBM base and ring slot of either"""
@@ -755,32 +616,24 @@ def stream():
                 f"s_lshl_b32 {S_TMP}, {S_TMP}, 14",
                 f"s_add_i32 {S_M0V}, {S_TMP}, %[woffv]"]
 
-    def rag_flag():
-        """S_FLAG = 1 when the softmax of this Y phase (tile t + 1) works on the last tile and that tile is ragged"""
-        return [f"s_add_i32 {S_TMP}, {S_T}, 1",
-                f"s_cmp_eq_u32 {S_TMP}, %[ntm1]",
-                f"s_cselect_b32 {S_FLAG}, 1, 0",
-                f"s_cmp_lt_u32 {S_RAG}, 64",
-                f"s_cselect_b32 {S_FLAG}, {S_FLAG}, 0"]
-
     o = [f"s_mov_b32 {S_RAG}, %[rag]", f"s_mov_b32 {S_FLAG}, 0", f"s_mov_b32 {S_RESC}, 0", f"s_mov_b32 {S_T}, 0"]
     if PV8:  # the lane-group mask of the 32 x 32 accumulators and the 8-register ones fragment (row 0 of the A operand = e4m3 1.0, handed over in v200)
         o += ["s_mov_b32 s96, 0xffff0000", "s_mov_b32 s97, 0xffff0000"] + [f"v_mov_b32 v{144 + r}, v200" for r in range(8)]
-    o += emit_phase(pre, None if FP8 else p1, own_prefetch=True, drain=FP8)
+    o += emit(pre, None if FP8 else p1, own_prefetch=True, drain=FP8)
     # the one un-hidden softmax piece of a workgroup: tile 0's maxima.  X(0)'s last MFMAs must have written S0 (an MFMA result needs
     # ~40 clocks); tile 0 is never the ragged last tile (n >= 2); O^T = l = 0: no rescale_o, no flag
     o += ["s_nop 15", "s_nop 15", "s_nop 15", "s_nop 15"] + rescale_s(0, False)
     if FP8:
-        o += emit_phase(p1, None, own_prefetch=True, drain=True) + early_reads(ye)
+        o += emit(p1, None, own_prefetch=True, drain=True) + early_reads(ye, FR)
     else:
-        o += emit_phase(p1, ye)
+        o += emit(p1, ye)
     o += [".Law16l_loop_%=:"]
     for y, x in ((ye, xe), (yo, xo)):
-        o += [] if "nosetup" in XS else dma_setup() + rag_flag()
-        o += emit_phase(y, x)
+        o += [] if "nosetup" in ABL else dma_setup() + [f"s_add_i32 {S_TMP}, {S_T}, 1"] + rag_flag(S_TMP, S_FLAG, S_RAG)   # (the softmax of this Y phase: tile t + 1)
+        o += emit(y, x)
         o += [f"s_cmp_eq_u32 {S_T}, %[ntm1]",
               "s_cbranch_scc1 .Law16l_done_%="]
-        o += emit_phase(x, yo if y is ye else ye)
+        o += emit(x, yo if y is ye else ye)
         o += [f"s_add_i32 {S_T}, {S_T}, 1"]
     o += ["s_branch .Law16l_loop_%=",
           ".Law16l_done_%=:",
@@ -794,23 +647,10 @@ def stream():
 def main():
     lines = [x for ln in stream() for x in ln.split(" ;; ")]
     stem = "attention_w16lf8pv_loop" if PV8 else "attention_w16lf8_loop" if FP8 else "attention_w16l_loop"
-    path = os.path.join(ROOT, "diffusion-rs_amd", "csrc", stem + ".inc")
-    if TAG:
-        os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-        path = os.path.join(ROOT, "build", f"{stem}_{TAG}.inc")
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_attention_w16l.py — do not edit.  The whole KV stream of attention_w16l_kernel as one asm\n")
-        f.write("// statement (pre, P1, loop { Y(t); X(t+2) } unrolled over two tiles); register map and schedule: see the generator.\n")
-        f.write(f"#define FMI_AW16L{'F8PV' if PV8 else 'F8' if FP8 else ''}_LOOP_ASM \\\n")
-        body = ['  "' + ln + '\\n\\t"' for ln in lines if not ln.startswith(";")]
-        f.write(" \\\n".join(body))
-        f.write("\n")
-    if os.environ.get("AW16L_DUMP"):
-        with open(os.environ["AW16L_DUMP"], "w") as f:
-            f.write("\n".join(lines) + "\n")
-    n_mfma = sum(1 for ln in lines if ln.startswith("v_mfma"))
-    n_other = sum(1 for ln in lines if not ln.startswith(";") and not ln.startswith("v_mfma") and not ln.endswith(":"))
-    print(f"{path}: {len(lines)} lines, {n_mfma} MFMAs, {n_other} other instructions", file=sys.stderr)
+    path = os.path.join(ROOT, "build", f"{stem}_{TAG}.inc") if TAG else os.path.join(ROOT, "diffusion-rs_amd", "csrc", stem + ".inc")
+    write_inc(path, ["GENERATED by tools/gen_attention_w16l.py — do not edit.  The whole KV stream of attention_w16l_kernel as one asm",
+                     "statement (pre, P1, loop { Y(t); X(t+2) } unrolled over two tiles); register map and schedule: see the generator."],
+              f"FMI_AW16L{'F8PV' if PV8 else 'F8' if FP8 else ''}_LOOP_ASM", lines, os.environ.get("AW16L_DUMP"))
 
 
 if __name__ == "__main__":

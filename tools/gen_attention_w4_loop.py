@@ -27,6 +27,8 @@ Register map (per lane; pinned by the operand constraints in attention_w4.h):
 """
 import os
 
+from attn_stream import write_inc
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = 16384
 PF = 8
@@ -338,22 +340,10 @@ def loop():
 
 
 def main():
-    lines = loop()
-    path = os.path.join(ROOT, "diffusion-rs_amd", "csrc", "attention_w4_loop.inc")
-    with open(path, "w") as f:
-        f.write("// GENERATED by tools/gen_attention_w4_loop.py — do not edit.  The steady-state KV loop of attention_w4_kernel\n")
-        f.write("// (phases B(t), A(t+1) for t = 0 .. ntiles-3) as one asm statement; register map and schedule: see the generator.\n")
-        f.write("#define FMI_AW4_LOOP_ASM \\\n")
-        body = []
-        for ln in lines:
-            if ln.startswith(";"):
-                continue
-            body.append('  "' + ln + '\\n\\t"')
-        f.write(" \\\n".join(body))
-        f.write("\n")
-    n_mfma = sum(1 for ln in lines if ln.startswith("v_mfma"))
-    n_other = sum(1 for ln in lines if not ln.startswith(";") and not ln.startswith("v_mfma") and not ln.endswith(":"))
-    print(f"{path}: {len(lines)} lines, {n_mfma} MFMAs, {n_other} other instructions (incl. 2 x 199 of the rarely taken rescale blocks)")
+    write_inc(os.path.join(ROOT, "diffusion-rs_amd", "csrc", "attention_w4_loop.inc"),
+              ["GENERATED by tools/gen_attention_w4_loop.py — do not edit.  The steady-state KV loop of attention_w4_kernel",
+               "(phases B(t), A(t+1) for t = 0 .. ntiles-3) as one asm statement; register map and schedule: see the generator."],
+              "FMI_AW4_LOOP_ASM", loop())   # (the other-instruction count includes 2 x 199 of the rarely taken rescale blocks)
 
 
 if __name__ == "__main__":
