@@ -1514,8 +1514,10 @@ extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* p
   return forward_core(m, in, m->ws.img_f32, in->timesteps, pred_out, s);
 }
 
-extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
-                                void* stream) {
+// The denoise loop of both entries.  x0 / noise / mask all null: fmi_flux_denoise, the plain Euler update.  All three set: fmi_flux_denoise_inpaint, the same
+// launches with the per-step update replaced by the masked one (launch_euler_blend); nothing before or inside the model evaluation knows the difference.
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, const float* x0, const float* noise,
+                        const float* mask, void* stream) {
   FMI_TRY(check_inputs(m, in));
   if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
   hipStream_t s = (hipStream_t)stream;
@@ -1583,9 +1585,23 @@ extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* i
     FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
-    FMI_TRY(launch_euler_update(img_inout, m->ws.pred_tmp, dt, n, s));
+    if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
+      FMI_TRY(launch_euler_blend(img_inout, m->ws.pred_tmp, x0, noise, mask, dt, (float)timesteps_host[i + 1], n, s));
+    else
+      FMI_TRY(launch_euler_update(img_inout, m->ws.pred_tmp, dt, n, s));
   }
   return FMI_OK;
+}
+
+extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
+                                void* stream) {
+  return denoise_loop(m, in, img_inout, timesteps_host, n_steps, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
+                                        const float* x0, const float* noise, const float* mask, void* stream) {
+  if (!x0 || !noise || !mask) return fail(FMI_ERR_INVALID, "flux_denoise_inpaint: x0, noise and mask are all required");
+  return denoise_loop(m, in, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
 }
 
 extern "C" int fmi_flux_set_profiling(fmi_flux* m, int enable) {

@@ -3,7 +3,9 @@
 //                     streaming, one wave per output row, 16-B loads  (model.rs:178-183,244-299,695-698)
 //   timestep_embedding (model.rs:104-122), Euler update (pipelines/sampling.rs:43),
 //   pack/unpack latents (pipelines/flux/sampling.rs:26-48,61-68), u8 post-process (flux/mod.rs:332),
-//   Philox N(0,1) latents (seedable replacement of get_noise, flux/sampling.rs:5-14), dtype casts.
+//   Philox N(0,1) latents (seedable replacement of get_noise, flux/sampling.rs:5-14), dtype casts,
+//   image-to-image / inpainting glue (no counterpart in the reference; the flow-matching forms of diffusers' FluxImg2ImgPipeline /
+//   FluxInpaintPipeline): scale_noise, the masked Euler step, u8 -> f32, latent mask, encode_latents.
 #include "common.h"
 
 namespace fmi {
@@ -150,6 +152,71 @@ int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipS
   return FMI_OK;
 }
 
+namespace {
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// a * x + t * y with a = 1 - t computed ONCE by the caller: t = 1 gives y and t = 0 gives x bit for bit (finite inputs), contracted or not
+__device__ __forceinline__ float lerp_at(float a, float x, float t, float y) { return a * x + t * y; }
+__device__ __forceinline__ float4 lerp_at(float a, float4 x, float t, float4 y) {
+  return make_float4(lerp_at(a, x.x, t, y.x), lerp_at(a, x.y, t, y.y), lerp_at(a, x.z, t, y.z), lerp_at(a, x.w, t, y.w));
+}
+// e = img + pred * dt (launch_euler_update's expression), k = a * x0 + s * noise, m * e + (1 - m) * k: m = 1 gives e and m = 0 gives k bit for bit
+__device__ __forceinline__ float euler_blend1(float img, float pred, float x0, float noise, float m, float dt, float a, float s) {
+  const float e = img + pred * dt;
+  const float k = lerp_at(a, x0, s, noise);
+  const float keep = 1.0f - m;
+  return m * e + keep * k;
+}
+__device__ __forceinline__ float4 euler_blend1(float4 img, float4 pred, float4 x0, float4 noise, float4 m, float dt, float a, float s) {
+  return make_float4(euler_blend1(img.x, pred.x, x0.x, noise.x, m.x, dt, a, s), euler_blend1(img.y, pred.y, x0.y, noise.y, m.y, dt, a, s),
+                     euler_blend1(img.z, pred.z, x0.z, noise.z, m.z, dt, a, s), euler_blend1(img.w, pred.w, x0.w, noise.w, m.w, dt, a, s));
+}
+// V = float4 (16-B accesses) or float (any alignment, any n); grid-stride like map_kernel.  img is read and written at the same index only.
+template <typename V>
+__global__ __launch_bounds__(256) void euler_blend_kernel(V* img, const V* __restrict__ pred, const V* __restrict__ x0, const V* __restrict__ noise,
+                                                          const V* __restrict__ mask, float dt, float a, float s, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    img[i] = euler_blend1(img[i], pred[i], x0[i], noise[i], mask[i], dt, a, s);
+}
+template <typename V>
+__global__ __launch_bounds__(256) void scale_noise_kernel(const V* __restrict__ x0, const V* __restrict__ noise, float a, float t, V* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = lerp_at(a, x0[i], t, noise[i]);
+}
+template <bool V4>
+__device__ __forceinline__ void store4(float* p, float a, float b, float c, float d) {
+  if constexpr (V4)
+    *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
+  else
+    p[0] = a, p[1] = b, p[2] = c, p[3] = d;
+}
+}  // namespace
+
+// The masked step of the inpainting loop in one pass (five f32 reads, one write per element):
+//   e = img + pred * dt;  k = (1 - s) * x0 + s * noise;  img = mask * e + (1 - mask) * k        (s = the step's target time, rounded to f32)
+int launch_euler_blend(float* img, const float* pred, const float* x0, const float* noise, const float* mask, float dt, float s, int64_t n,
+                       hipStream_t stream) {
+  if (n <= 0) return FMI_OK;
+  const float a = 1.0f - s;
+  if (n % 4 == 0 && aligned16(img) && aligned16(pred) && aligned16(x0) && aligned16(noise) && aligned16(mask))
+    hipLaunchKernelGGL(euler_blend_kernel<float4>, map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), reinterpret_cast<const float4*>(pred),
+                       reinterpret_cast<const float4*>(x0), reinterpret_cast<const float4*>(noise), reinterpret_cast<const float4*>(mask), dt, a, s, n / 4);
+  else
+    hipLaunchKernelGGL(euler_blend_kernel<float>, map_grid(n), dim3(256), 0, stream, img, pred, x0, noise, mask, dt, a, s, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+// out = (1 - t) * x0 + t * noise  (FlowMatchEulerDiscreteScheduler.scale_noise)
+int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, float* out, hipStream_t stream) {
+  if (n <= 0) return FMI_OK;
+  const float a = 1.0f - t;
+  if (n % 4 == 0 && aligned16(x0) && aligned16(noise) && aligned16(out))
+    hipLaunchKernelGGL(scale_noise_kernel<float4>, map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<const float4*>(x0), reinterpret_cast<const float4*>(noise), a, t,
+                       reinterpret_cast<float4*>(out), n / 4);
+  else
+    hipLaunchKernelGGL(scale_noise_kernel<float>, map_grid(n), dim3(256), 0, stream, x0, noise, a, t, out, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
 // y[r][n] = (y[r][n] + g[r % B][n]) + v[r % B][n]: the step-invariant terms of `vec` added in the order the accumulating GEMVs added them
 int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int N, hipStream_t stream) {
   const int64_t n = (int64_t)R * N;
@@ -259,6 +326,124 @@ extern "C" int fmi_postprocess_u8(const float* image, int B, int C, int H, int W
   });
   FMI_LAUNCH_CHECK();
   return FMI_OK;
+}
+
+// ---- image-to-image / inpainting glue
+namespace {
+// one item = four pixels of a row, all C channels: u8 NCHW (uchar4 per channel) or NHWC (4 * C consecutive bytes) -> C stores of four f32
+template <bool V4>
+__global__ __launch_bounds__(256) void preprocess_u8_kernel(const uint8_t* __restrict__ in, int C, int64_t HW, int interleaved, float* __restrict__ out, int64_t items) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = (i % (HW / 4)) * 4, b = i / (HW / 4);  // pixel index inside the image (a row is a multiple of 4 wide)
+    for (int c = 0; c < C; ++c) {
+      float f[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint8_t u = interleaved ? in[(b * HW + p + j) * C + c] : in[(b * C + c) * HW + p + j];
+        // the centre of the bin that postprocess_u8 truncates into u: three f32 roundings, as the numpy expression
+        f[j] = __fsub_rn(__fdiv_rn(__fadd_rn((float)u, 0.5f), 127.5f), 1.0f);
+      }
+      store4<V4>(out + (b * C + c) * HW + p, f[0], f[1], f[2], f[3]);
+    }
+  }
+}
+// one thread per token: the four 8x8 block means of its 16x16 pixels, then the C copies of them in pack_latents' order (c, ph, pw)
+template <bool V4>
+__global__ __launch_bounds__(64) void latent_mask_kernel(const float* __restrict__ mask, int C, int H, int W, float* __restrict__ out, int64_t tokens) {
+  const int h2 = H / 16, w2 = W / 16;
+  for (int64_t tok = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tok < tokens; tok += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(tok % w2), ii = (int)((tok / w2) % h2);
+    const int64_t b = tok / ((int64_t)w2 * h2);
+    const float* src = mask + (b * H + 16 * ii) * W + 16 * j;
+    float m[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+    for (int y = 0; y < 16; ++y) {
+      float l = 0.f, r = 0.f;
+      if constexpr (V4) {
+        const float4* row = reinterpret_cast<const float4*>(src + (int64_t)y * W);
+        const float4 q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
+        l = ((q0.x + q0.y) + (q0.z + q0.w)) + ((q1.x + q1.y) + (q1.z + q1.w));
+        r = ((q2.x + q2.y) + (q2.z + q2.w)) + ((q3.x + q3.y) + (q3.z + q3.w));
+      } else {
+        for (int x = 0; x < 8; ++x) l += src[(int64_t)y * W + x], r += src[(int64_t)y * W + 8 + x];
+      }
+      m[y >> 3][0] += l, m[y >> 3][1] += r;
+    }
+    const float s = 1.0f / 64.0f;
+    for (int c = 0; c < C; ++c) store4<V4>(out + (tok * C + c) * 4, m[0][0] * s, m[0][1] * s, m[1][0] * s, m[1][1] * s);
+  }
+}
+// one thread per (token, channel): the 2x2 patch of z as one 16-B store; (z - shift) * scale in two roundings, the inverse of fmi_unpack_latents' two
+template <bool V4>
+__global__ __launch_bounds__(256) void encode_latents_kernel(const float* __restrict__ z, int C, int h, int w, float sc, float sh, float* __restrict__ x0,
+                                                             float* __restrict__ ids, int64_t n) {
+  const int h2 = h / 2, w2 = w / 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const int64_t tok = i / C;
+    const int j = (int)(tok % w2), ii = (int)((tok / w2) % h2);
+    const int64_t b = tok / ((int64_t)w2 * h2);
+    const float* p = z + ((b * C + c) * h + 2 * ii) * w + 2 * j;
+    store4<V4>(x0 + i * 4, __fmul_rn(__fsub_rn(p[0], sh), sc), __fmul_rn(__fsub_rn(p[1], sh), sc), __fmul_rn(__fsub_rn(p[w], sh), sc),
+               __fmul_rn(__fsub_rn(p[w + 1], sh), sc));
+    if (ids && c == 0) ids[tok * 3] = 0.f, ids[tok * 3 + 1] = (float)ii, ids[tok * 3 + 2] = (float)j;
+  }
+}
+}  // namespace
+
+extern "C" int fmi_preprocess_u8(const uint8_t* in, int B, int C, int H, int W, int interleaved, float* out, void* stream) {
+  if (!in || !out || B < 0 || C <= 0 || H <= 0 || W <= 0) return fail(FMI_ERR_INVALID, "preprocess_u8: bad arguments");
+  const int64_t HW = (int64_t)H * W;
+  if (B == 0) return FMI_OK;
+  if (HW % 4 == 0) {
+    const int64_t items = (int64_t)B * (HW / 4);
+    if (aligned16(out))
+      hipLaunchKernelGGL(preprocess_u8_kernel<true>, map_grid(items), dim3(256), 0, (hipStream_t)stream, in, C, HW, interleaved, out, items);
+    else
+      hipLaunchKernelGGL(preprocess_u8_kernel<false>, map_grid(items), dim3(256), 0, (hipStream_t)stream, in, C, HW, interleaved, out, items);
+  } else {  // an image whose pixel count is no multiple of 4: one element per thread
+    const int64_t n = (int64_t)B * C * HW;
+    hipLaunchKernelGGL(map_kernel, map_grid(n), dim3(256), 0, (hipStream_t)stream, n, [=] __device__(int64_t i) {
+      const int64_t p = i % HW, c = (i / HW) % C, b = i / (HW * C);
+      const uint8_t u = interleaved ? in[(b * HW + p) * C + c] : in[i];
+      out[i] = __fsub_rn(__fdiv_rn(__fadd_rn((float)u, 0.5f), 127.5f), 1.0f);
+    });
+  }
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+extern "C" int fmi_latent_mask(const float* mask, int B, int C, int H, int W, float* out, void* stream) {
+  if (!mask || !out || B < 0 || C <= 0) return fail(FMI_ERR_INVALID, "latent_mask: bad arguments");
+  if (H <= 0 || W <= 0 || H % 16 || W % 16) return fail(FMI_ERR_INVALID, "latent_mask: H and W must be positive multiples of 16");
+  const int64_t tokens = (int64_t)B * (H / 16) * (W / 16);
+  if (tokens == 0) return FMI_OK;
+  const dim3 grid((unsigned)std::min<int64_t>(cdiv64(tokens, 64), 256 * 8));
+  if (aligned16(mask) && aligned16(out))  // W % 16 == 0: every 16-pixel row segment is then 16-B aligned too
+    hipLaunchKernelGGL(latent_mask_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, mask, C, H, W, out, tokens);
+  else
+    hipLaunchKernelGGL(latent_mask_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, mask, C, H, W, out, tokens);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+extern "C" int fmi_encode_latents(const float* z, int B, int C, int h, int w, double scale_factor, double shift_factor, float* x0_out, float* img_ids_out,
+                                  void* stream) {
+  if (!z || !x0_out || B < 0 || C <= 0 || h <= 0 || w <= 0) return fail(FMI_ERR_INVALID, "encode_latents: bad arguments");
+  if (h % 2 || w % 2) return fail(FMI_ERR_INVALID, "encode_latents: h and w must be even");
+  const int64_t n = (int64_t)B * (h / 2) * (w / 2) * C;
+  if (n == 0) return FMI_OK;
+  const float sc = (float)scale_factor, sh = (float)shift_factor;  // the scalars rounded to f32 like candle's affine
+  if (aligned16(x0_out))
+    hipLaunchKernelGGL(encode_latents_kernel<true>, map_grid(n), dim3(256), 0, (hipStream_t)stream, z, C, h, w, sc, sh, x0_out, img_ids_out, n);
+  else
+    hipLaunchKernelGGL(encode_latents_kernel<false>, map_grid(n), dim3(256), 0, (hipStream_t)stream, z, C, h, w, sc, sh, x0_out, img_ids_out, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+extern "C" int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, float* out, void* stream) {
+  if (!x0 || !noise || !out || n < 0) return fail(FMI_ERR_INVALID, "scale_noise: bad arguments");
+  return launch_scale_noise(x0, noise, (float)t, n, out, (hipStream_t)stream);
 }
 
 // Philox4x32-10 + Box-Muller.  counter = (i/4, sample, 0, 0), key = seed; 4 normals per counter.

@@ -306,12 +306,26 @@ class FluxModel:
         L.check(self.lib.fmi_flux_forward(self.h, C.byref(inp), _ptr(pred), _stream()), self.lib)
         return pred
 
-    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float]):
-        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned."""
+    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None):
+        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
+        x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
+        latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h)."""
         img = img.to(torch.float32).clone().contiguous()
         inp, keep = self._inputs(None, img_ids, txt, txt_ids, None, y, guidance)
         ts = (C.c_double * len(timesteps))(*timesteps)
-        L.check(self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _stream()), self.lib)
+        if x0 is None and noise is None and mask is None:
+            L.check(self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _stream()), self.lib)
+            return img
+        extra = []
+        for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask")):
+            if t is not None:
+                if tuple(t.shape) != tuple(img.shape):
+                    raise ValueError(f"denoise: {nm} is {tuple(t.shape)}, img is {tuple(img.shape)}")
+                t = t.to(device=img.device, dtype=torch.float32).contiguous()
+            extra.append(t)
+        # a missing one reaches the library as NULL: it answers FMI_ERR_INVALID
+        L.check(self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
+                                                  _stream()), self.lib)
         return img
 
     def set_profiling(self, on: bool):
@@ -432,6 +446,52 @@ def postprocess_u8(image, interleave=False):
     B, Cc, H, W = image.shape
     out = torch.empty((B, H, W, Cc) if interleave else (B, Cc, H, W), dtype=torch.uint8, device=image.device)
     L.check(L.load().fmi_postprocess_u8(_ptr(image), B, Cc, H, W, int(interleave), _ptr(out), _stream()))
+    return out
+
+
+# ---- image-to-image / inpainting glue
+def preprocess_u8(image, interleaved=False):
+    """u8 (B,C,H,W), or (B,H,W,C) with interleaved=True (what output="rgb" returns) -> f32 (B,C,H,W) in [-1,1]: x = (u + 0.5) / 127.5 - 1, the centre of the
+    bin postprocess_u8 truncates into u, so postprocess_u8(preprocess_u8(u)) == u."""
+    if image.dtype != torch.uint8 or image.dim() != 4:
+        raise TypeError("preprocess_u8: a uint8 tensor of 4 dimensions is required")
+    image = image.contiguous()
+    B, Cc, H, W = (image.shape[0], image.shape[3], image.shape[1], image.shape[2]) if interleaved else image.shape
+    out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=image.device)
+    L.check(L.load().fmi_preprocess_u8(_ptr(image), B, Cc, H, W, int(interleaved), _ptr(out), _stream()))
+    return out
+
+
+def latent_mask(mask, Cc=16):
+    """Pixel mask (B,H,W) f32 in [0,1] (1 = repaint, 0 = keep), H and W multiples of 16 -> (B,(H/16)(W/16),4*Cc) f32: 8x8 block means, broadcast over the
+    Cc latent channels, in pack_latents' layout."""
+    mask = mask.to(torch.float32).contiguous()
+    B, H, W = mask.shape
+    if H % 16 or W % 16:
+        raise ValueError(f"latent_mask: H and W must be multiples of 16, got {H} x {W}")
+    out = torch.empty((B, (H // 16) * (W // 16), Cc * 4), dtype=torch.float32, device=mask.device)
+    L.check(L.load().fmi_latent_mask(_ptr(mask), B, Cc, H, W, _ptr(out), _stream()))
+    return out
+
+
+def encode_latents(z, scale_factor, shift_factor):
+    """The mirror of unpack_latents: z (B,C,h,w) f32 (AutoEncoderKl.encode) -> x0 (B,hw/4,4C) = pack((z - shift_factor) * scale_factor), img_ids (B,hw/4,3)."""
+    z = z.to(torch.float32).contiguous()
+    B, Cc, h, w = z.shape
+    x0 = torch.empty((B, (h // 2) * (w // 2), Cc * 4), dtype=torch.float32, device=z.device)
+    ids = torch.empty((B, (h // 2) * (w // 2), 3), dtype=torch.float32, device=z.device)
+    L.check(L.load().fmi_encode_latents(_ptr(z), B, Cc, h, w, scale_factor, shift_factor, _ptr(x0), _ptr(ids), _stream()))
+    return x0, ids
+
+
+def scale_noise(x0, noise, t):
+    """(1 - t) * x0 + t * noise in f32 (any shape; the tensors are used as they lie in memory): noise bit for bit at t = 1, x0 at t = 0."""
+    if x0.dtype != torch.float32 or noise.dtype != torch.float32 or x0.shape != noise.shape:
+        raise TypeError("scale_noise: two float32 tensors of one shape are required")
+    if not (x0.is_contiguous() and noise.is_contiguous()):
+        x0, noise = x0.contiguous(), noise.contiguous()
+    out = torch.empty_like(x0)
+    L.check(L.load().fmi_scale_noise(_ptr(x0), _ptr(noise), float(t), x0.numel(), _ptr(out), _stream()))
     return out
 
 

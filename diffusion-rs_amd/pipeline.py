@@ -13,7 +13,8 @@ the `tokenizers` package; without them pass `token_ids=(t5_ids, clip_ids)` or pr
 `embeddings=(t5_emb, clip_emb)` — a loaded checkpoint never falls back to made-up embeddings.  Only the
 Synthetic source built without text encoders (the benchmark) derives deterministic placeholder
 embeddings from the prompt text: only shapes matter there.  Extensions over the reference, all keyword-only:
-`latents=` / `seed=` (the reference cannot be seeded), `embeddings=`, `token_ids=`, `output=`.
+`latents=` / `seed=` (the reference cannot be seeded), `embeddings=`, `token_ids=`, `output=`, and image-to-image / inpainting:
+`image=` / `strength=` / `mask=` / `return_latents=` (the reference has neither).
 
 Multi-GPU: when torch.distributed is initialised (one process per GPU), the constructor loads the
 DiT on rank 0 only and broadcasts its weight arenas over RCCL (dist.broadcast_state), and `forward` shards the
@@ -123,6 +124,18 @@ def placeholder_embeddings(prompts: Sequence[str], T: int, joint_dim: int, poole
         t5.append(torch.randn((T, joint_dim), generator=g))
         clip.append(torch.randn((pooled_dim,), generator=g))
     return torch.stack(t5).to(device=device, dtype=torch.bfloat16), torch.stack(clip).to(device=device, dtype=torch.float32)
+
+
+def img2img_timesteps(timesteps: Sequence[float], strength: float) -> list:
+    """The part of a schedule an image-to-image run walks: with N = len(timesteps) - 1 steps, the last n_run = min(int(N * strength), N) of them
+    (diffusers' expression, float truncation included: int(100 * 0.29) == 28), i.e. timesteps[N - n_run:].  The source is noised to the first value."""
+    n = len(timesteps) - 1
+    if not (0.0 < strength <= 1.0):
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    n_run = min(int(n * strength), n)
+    if n_run < 1:
+        raise ValueError(f"strength {strength} leaves no step of {n} to run: raise strength or num_steps")
+    return list(timesteps[n - n_run:])
 
 
 class Pipeline:
@@ -265,23 +278,85 @@ class Pipeline:
 
     MAX_BATCH = 8  # samples per denoise call (the C-ABI's per-device batch limit); longer prompt lists run in chunks
 
+    def _source_image(self, image, mask, strength, B, params):
+        """Check the image-to-image arguments and bring them to their device form: image f32 (B,3,H,W) in [-1,1], mask f32 (B,H,W) or None."""
+        if image is None:
+            if mask is not None:
+                raise ValueError("mask= needs image=: inpainting repaints part of a source image")
+            if strength != 1.0:
+                raise ValueError("strength= needs image=: text to image always runs the whole schedule")
+            return None, None
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("image= is not wired through sequence parallelism: disable_sequence_parallel() first")
+        H, W = params.height, params.width
+        if H % 16 or W % 16:
+            raise ValueError(f"image= needs height and width that are multiples of 16, got {H} x {W}")
+        img2img_timesteps([0.0] * (params.num_steps + 1), strength)  # the strength range, before any work
+
+        def batched(t, what):
+            if t.shape[0] == B:
+                return t
+            if t.shape[0] == 1:
+                return t.expand(B, *t.shape[1:])
+            raise ValueError(f"{what} holds {t.shape[0]} samples for {B} prompts (one is broadcast)")
+
+        if isinstance(image, (list, tuple)):  # the list of (H,W,3) arrays output="rgb" returns
+            image = np.stack([np.asarray(i) for i in image])
+        t = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("image must be a numpy array or a torch tensor")
+        if t.dtype == torch.uint8:  # (B,H,W,3) or (H,W,3): what output="rgb" returns
+            t = t.unsqueeze(0) if t.dim() == 3 else t
+            if t.dim() != 4 or tuple(t.shape[1:]) != (H, W, 3):
+                raise ValueError(f"a uint8 image must be (B,{H},{W},3) or ({H},{W},3) as params say, got {tuple(t.shape)}")
+            t = F.preprocess_u8(t.to(self.device), interleaved=True)
+        elif t.is_floating_point():  # (B,3,H,W) in [-1,1]
+            if t.dim() != 4 or tuple(t.shape[1:]) != (3, H, W):
+                raise ValueError(f"a float image must be (B,3,{H},{W}) as params say, got {tuple(t.shape)}")
+            t = t.to(device=self.device, dtype=torch.float32)
+        else:
+            raise ValueError(f"image must be uint8 or float, got {t.dtype}")
+        image = batched(t, "image")
+        if mask is not None:
+            m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
+            if not isinstance(m, torch.Tensor) or not (m.dtype == torch.bool or m.is_floating_point()):
+                raise ValueError("mask must be a bool or float numpy array or torch tensor")
+            m = m.unsqueeze(0) if m.dim() == 2 else m
+            if m.dim() != 3 or tuple(m.shape[1:]) != (H, W):
+                raise ValueError(f"mask must be (B,{H},{W}) or ({H},{W}) as params say, got {tuple(m.shape)}")
+            mask = batched(m.to(device=self.device, dtype=torch.float32), "mask")
+        return image, mask
+
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
-                        seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None) -> torch.Tensor:
+                        seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
+                        image=None, strength: float = 1.0, mask=None, return_latents: bool = False):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
-        the samples, so that a sample draws the same noise whichever rank / chunk it runs in."""
+        the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
+
+        Image to image (`image=`; not in the reference): the source — u8 (B,H,W,3) / (H,W,3) as output="rgb" returns it, or f32 (B,3,H,W)
+        in [-1,1]; numpy or torch; one image is broadcast over the prompts — is encoded by the VAE, noised to the schedule's value at `strength`
+        (diffusers' FluxImg2ImgPipeline: the last min(int(num_steps * strength), num_steps) steps run; strength 1 is text to image bit for bit) with the
+        noise text to image would have started from (same seed / sample ids, or `latents=`).  UNLIKE diffusers, which samples the VAE posterior, the
+        source latents are the posterior MEAN: deterministic, no second noise stream.  `mask=` ((B,H,W) / (H,W), float in [0,1] or bool; 1 = repaint,
+        0 = keep) makes it inpainting (FluxInpaintPipeline's step): every step blends the re-noised source back in where the 8x8-mean latent mask keeps
+        it, and kept latents end as the source's exactly.  `return_latents=True` returns (u8, final packed latents (B,S,64) f32)."""
         B = len(prompts)
         ids = list(sample_ids) if sample_ids is not None else [first_sample + b for b in range(B)]
         if len(ids) != B:
             raise ValueError("sample_ids must name one stream per prompt")
         if B == 0:
-            return torch.empty((0, 3, params.height, params.width), dtype=torch.uint8, device=self.device)
+            u8 = torch.empty((0, 3, params.height, params.width), dtype=torch.uint8, device=self.device)
+            S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
+            return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
+        image, mask = self._source_image(image, mask, strength, B, params)
         sp = getattr(self, "_sp", None)
         if sp is not None and B > 1:  # sequence parallel: the ranks of the group work on ONE image at a time
-            return torch.cat([self.generate_tensor(
+            outs = [self.generate_tensor(
                 prompts[b:b + 1], params, embeddings=None if embeddings is None else (embeddings[0][b:b + 1], embeddings[1][b:b + 1]),
-                latents=None if latents is None else latents[b:b + 1], seed=seed,
-                token_ids=None if token_ids is None else (token_ids[0][b:b + 1], token_ids[1][b:b + 1]), sample_ids=ids[b:b + 1]) for b in range(B)], 0)
+                latents=None if latents is None else latents[b:b + 1], seed=seed, return_latents=return_latents,
+                token_ids=None if token_ids is None else (token_ids[0][b:b + 1], token_ids[1][b:b + 1]), sample_ids=ids[b:b + 1]) for b in range(B)]
+            return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
         if B > self.MAX_BATCH:  # the reference accepts any batch (pipelines/mod.rs:241-270)
             outs = []
             for a in range(0, B, self.MAX_BATCH):
@@ -289,8 +364,9 @@ class Pipeline:
                 outs.append(self.generate_tensor(
                     prompts[sl], params, embeddings=None if embeddings is None else (embeddings[0][sl], embeddings[1][sl]),
                     latents=None if latents is None else latents[sl], seed=seed,
-                    token_ids=None if token_ids is None else (token_ids[0][sl], token_ids[1][sl]), sample_ids=ids[sl]))
-            return torch.cat(outs, 0)
+                    token_ids=None if token_ids is None else (token_ids[0][sl], token_ids[1][sl]), sample_ids=ids[sl],
+                    image=None if image is None else image[sl], strength=strength, mask=None if mask is None else mask[sl], return_latents=return_latents))
+            return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
         cfg = self.flux.cfg
         dev = self.device
         with self._lock:  # the whole forward, text encoders included, like the reference's mutex (pipelines/mod.rs:247)
@@ -319,15 +395,23 @@ class Pipeline:
             mu = self.scheduler.calculate_shift(img.shape[1])
             timesteps = self.scheduler.get_timesteps(params.num_steps, mu)
             guidance = torch.full((B,), float(params.guidance_scale), dtype=torch.float32, device=dev) if self.flux.is_guidance() else None
+            inpaint = {}
+            if image is not None:  # start from the source noised to the cut schedule's first value (at strength 1 that is the noise itself, bit for bit)
+                x0, _ = F.encode_latents(self.vae.encode(image), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
+                timesteps = img2img_timesteps(timesteps, strength)
+                noise = img
+                img = F.scale_noise(x0, noise, timesteps[0])
+                if mask is not None:
+                    inpaint = dict(x0=x0, noise=noise, mask=F.latent_mask(mask, x0.shape[2] // 4))
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps)
             if sp is not None:  # every rank holds the same inputs; each denoises its token shard, then all get the latents
                 img = sp.gather(self.flux.denoise(sp.shard(img), sp.shard(img_ids), sp.shard(t5_emb), sp.shard(txt_ids), clip_emb, guidance, timesteps))
             else:
-                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps)
+                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint)
             z = F.unpack_latents(img, 16, h, w, self.vae.scale_factor(), self.vae.shift_factor())
-            image = self.vae.decode(z)
-            return F.postprocess_u8(image)
+            u8 = F.postprocess_u8(self.vae.decode(z))
+            return (u8, img) if return_latents else u8
 
     INT8_CALIBRATION_POINTS = 4
 
@@ -406,18 +490,28 @@ class Pipeline:
             self._sp.detach(self.flux)
             self._sp = None
 
-    def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", **kw):
+    def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
+                return_latents: bool = False, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
-        the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None."""
+        the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
+        image= / strength= / mask=: image to image and inpainting, see generate_tensor; return_latents=True returns (images, final packed latents)."""
         from . import dist as D
         rank, world = D.world()
+        kw = dict(kw, image=image, strength=strength, mask=mask, return_latents=return_latents)
+        final = None  # return_latents=True: the final packed latents, returned next to the images
         if getattr(self, "_sp", None) is not None:  # all ranks produce every image together; rank 0 returns them
             u8 = self.generate_tensor(prompts, params, **kw)
+            if return_latents:
+                u8, final = u8
             if rank != 0:
                 return None
         elif world > 1:
             n = len(prompts)
+            if return_latents:
+                raise ValueError("return_latents= is not gathered across ranks: call generate_tensor on the rank that holds the sample")
+            if n > 0:  # batched device tensors, so that a rank picks its rows of them exactly as it picks its rows of `latents`
+                kw["image"], kw["mask"] = self._source_image(image, mask, strength, n, params)
             if getattr(self, "_int8_pending", False) and n > 0:
                 # every rank calibrates on the SAME sample — global sample 0 of this request — so that all ranks hold the same int8 weights and an image does
                 # not depend on the rank that produced it (one extra image per rank, once per model)
@@ -425,8 +519,9 @@ class Pipeline:
                 for key in ("embeddings", "token_ids"):
                     if sub.get(key) is not None:
                         sub[key] = tuple(t[:1] for t in sub[key])
-                if sub.get("latents") is not None:
-                    sub["latents"] = sub["latents"][:1]
+                for key in ("latents", "image", "mask"):
+                    if sub.get(key) is not None:
+                        sub[key] = sub[key][:1]
                 first = sub.pop("first_sample", 0)
                 self.generate_tensor(prompts[:1], params, sample_ids=[first], **sub)
 
@@ -438,8 +533,9 @@ class Pipeline:
                 for key in ("embeddings", "token_ids"):
                     if sub.get(key) is not None:
                         sub[key] = tuple(pick(t, ids) for t in sub[key])
-                if sub.get("latents") is not None:
-                    sub["latents"] = pick(sub["latents"], ids)
+                for key in ("latents", "image", "mask"):
+                    if sub.get(key) is not None:
+                        sub[key] = pick(sub[key], ids)
                 first = sub.pop("first_sample", 0)
                 return self.generate_tensor(my_prompts, params, sample_ids=[first + i for i in ids], **sub)
 
@@ -450,9 +546,11 @@ class Pipeline:
             assert u8.shape[0] == n
         else:
             u8 = self.generate_tensor(prompts, params, **kw)
+            if return_latents:
+                u8, final = u8
         if output == "tensor":
-            return u8
-        hwc = u8.permute(0, 2, 3, 1).contiguous().cpu().numpy()
-        if output == "rgb":
-            return [hwc[i] for i in range(hwc.shape[0])]
-        return [encode_png(hwc[i]) for i in range(hwc.shape[0])]
+            out = u8
+        else:
+            hwc = u8.permute(0, 2, 3, 1).contiguous().cpu().numpy()
+            out = [hwc[i] for i in range(hwc.shape[0])] if output == "rgb" else [encode_png(hwc[i]) for i in range(hwc.shape[0])]
+        return (out, final) if return_latents else out

@@ -43,6 +43,7 @@ extern "C" {
  *   (per-channel smoothing of the int8 mode from a calibration; fmi_flux_quantize_int8 without one is unchanged).  The op-level entries that use
  *   the library's per-stream scratch (fmi_sdpa_*, fmi_linear_fp8 / _i8, fmi_groupnorm_nhwc) now enqueue their kernels under one lock: host threads
  *   may share a stream.  Later additions under the same number: fmi_flux_get_tensor and the LoRA adapter calls fmi_flux_lora_*.
+ *   Then, still 6: image to image and inpainting — fmi_preprocess_u8, fmi_latent_mask, fmi_encode_latents, fmi_scale_noise, fmi_flux_denoise_inpaint.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -362,6 +363,20 @@ int fmi_flux_forward(fmi_flux*, const fmi_flux_inputs* in, float* pred_out, void
  * The latent stays f32 between steps. */
 int fmi_flux_denoise(fmi_flux*, const fmi_flux_inputs* in, float* img_inout,
                      const double* timesteps_host, int n_steps, void* stream);
+/* The same loop with the inpainting step (no counterpart in the reference; the flow-matching form of diffusers'
+ * FluxInpaintPipeline).  After the model evaluation of step i, with s = f32(timesteps[i+1]):
+ *   e = img + pred * dt                     (fmi_flux_denoise's update, same rounding)
+ *   k = (1 - s) * x0 + s * noise            (the source re-noised to the step's target time, fmi_scale_noise's form)
+ *   img = mask * e + (1 - mask) * k
+ * mask = 1 gives e and mask = 0 gives k bit for bit; the schedule ends at s = 0, where k = x0 bit for bit, so kept
+ * elements end as the source's exactly.  x0, noise, mask: (B,S,in_channels) f32 device buffers laid out like img_inout
+ * (fmi_encode_latents, the packed noise the image would have started from, fmi_latent_mask); under sequence parallelism
+ * this rank's rows, like img_inout.  All three are required (FMI_ERR_INVALID).  Everything else — arguments, errors,
+ * asynchrony, allocations, every launch up to the per-step update — is fmi_flux_denoise's.
+ * Plain image-to-image (no mask) needs no loop of its own: it is fmi_scale_noise at the first timestep of the cut
+ * schedule followed by fmi_flux_denoise on that schedule. */
+int fmi_flux_denoise_inpaint(fmi_flux*, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
+                             const float* x0, const float* noise, const float* mask, void* stream);
 
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
@@ -505,6 +520,24 @@ int fmi_unpack_latents(const float* img, int B, int C, int h, int w, double scal
  * to RgbImage::from_raw, pipelines/mod.rs:253-266). */
 int fmi_postprocess_u8(const float* image, int B, int C, int H, int W, int interleave,
                        uint8_t* out, void* stream);
+/* ---- image-to-image / inpainting glue (the reference has neither) ----
+ * u8 image -> f32 NCHW in [-1, 1], the mirror of fmi_postprocess_u8: in (B,C,H,W) u8 (interleaved=0) or (B,H,W,C) u8
+ * (interleaved=1, what Pipeline::forward returns), x = (u + 0.5) / 127.5 - 1 in f32 — the centre of the bin that the
+ * truncating post-process maps to u, so fmi_postprocess_u8(fmi_preprocess_u8(u)) == u for all 256 values (u / 127.5 - 1
+ * comes back one too low on 63 of them). */
+int fmi_preprocess_u8(const uint8_t* in, int B, int C, int H, int W, int interleaved, float* out, void* stream);
+/* Pixel mask (B,H,W) f32 in [0,1] (1 = repaint, 0 = keep) -> latent mask (B,(H/16)(W/16),C*4) f32: the mean of every
+ * 8x8 block, broadcast over the C latent channels and laid out as fmi_pack_latents lays the latents out. */
+int fmi_latent_mask(const float* mask, int B, int C, int H, int W, float* out, void* stream);   /* H, W multiples of 16 */
+/* The mirror of fmi_unpack_latents: z (B,C,h,w) f32 (fmi_vae_encode's output) -> x0 (B,(h/2)(w/2),C*4) f32 =
+ * pack((z - shift_factor) * scale_factor), two roundings with the scalars rounded to f32, and img_ids (B,(h/2)(w/2),3)
+ * as fmi_pack_latents writes them (img_ids_out may be NULL). */
+int fmi_encode_latents(const float* z, int B, int C, int h, int w, double scale_factor, double shift_factor,
+                       float* x0_out, float* img_ids_out, void* stream);
+/* FlowMatchEulerDiscreteScheduler.scale_noise: out = (1 - t) * x0 + t * noise over n f32 elements, t rounded to f32 and
+ * 1 - t computed once: t = 1 gives noise and t = 0 gives x0 bit for bit.  The start state of image-to-image at
+ * t = timesteps[num_steps - n_run]. */
+int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, float* out, void* stream);
 /* Deterministic N(0,1) latents from a counter-based Philox4x32-10 generator
  * (the reference's RNG is unseedable; this is the explicit-seed extension).
  * Elements 4q..4q+3 of sample b come from the four words of philox(counter = (q lo, q hi, s lo, s hi),
