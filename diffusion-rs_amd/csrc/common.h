@@ -358,8 +358,9 @@ int launch_qk_norm_rope(const bf16_t* q, const bf16_t* k, int ld, int64_t in_bst
                         int B, int H, int rows, int row_off, int Ltot, hipStream_t stream);
 int launch_qk_norm_rope_f32(const bf16_t* q, const bf16_t* k, int ld, int64_t in_bstride, const bf16_t* wq, const bf16_t* wk, const float* pe,
                             int64_t pe_bstride, float* qo, float* ko, int B, int H, int rows, int row_off, int Ltot, hipStream_t stream);
+// rows [0, T) from txt_ids, [T, T + S) from img_ids, [T + S, T + S + R) from ctx_ids (the reference-image tokens of a context evaluation; R = 0: none)
 int launch_rope_table(const float* txt_ids, const float* img_ids, int B, int T, int S, const int* axes,
-                      int theta, float* pe, hipStream_t stream);
+                      int theta, float* pe, hipStream_t stream, const float* ctx_ids = nullptr, int R = 0);
 // LayerNorm(no affine) * (1+scale) + shift; x f32 (rows, D) -> bf16. scale/shift per batch
 // (vector + batch*mod_bstride), batch = row / rows_per_batch.
 // two row sets in one launch (the image and text streams of a double block); rows2 = 0: one set
@@ -402,6 +403,8 @@ int launch_lora_merge(const bf16_t* w0, bf16_t* w, int rows, int K, const float*
 int launch_timestep_embedding(const float* t, int B, int dim, float* out, hipStream_t stream);
 int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hipStream_t stream);
+// per-sample strided cast: n contiguous elements of sample b at src + b * src_bs (F32 | BF16) -> bf16 at dst + b * dst_bs, one launch (small_ops.hip)
+int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream);
 int launch_silu_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream);
 // the masked (inpainting) step: img = mask * (img + pred * dt) + (1 - mask) * ((1 - s) * x0 + s * noise), one pass (small_ops.hip)

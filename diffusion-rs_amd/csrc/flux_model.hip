@@ -847,14 +847,27 @@ int check_ready(fmi_flux* m) {
 int use_device(const fmi_flux* m) { return use_device_ordinal(m->device); }
 
 // Everything of Flux::forward that does not depend on the timestep: input casts + RoPE table.
-int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, hipStream_t s) {
+// R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
+int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s) {
   auto& w = m->ws;
-  const int B = in->B, S = in->S, T = in->T;
+  const int B = in->B, S = in->S, T = in->T, C = m->cfg.in_channels;
   PhaseTimer pt(m, s, PH_EMBED);
   FMI_TRY(launch_cast_to_bf16(in->txt, in->txt_dtype, w.txt_bf, (int64_t)B * T * m->cfg.joint_attention_dim, s));
   FMI_TRY(launch_cast_to_f32(in->y, in->y_dtype, w.yf, (int64_t)B * m->cfg.pooled_projection_dim, s));
   // pe = EmbedNd(cat([txt_ids, img_ids], 1)) (model.rs:807-810); one table per batch element
-  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, in->ids_per_sample ? B : 1, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s));
+  if (!R) return launch_rope_table(in->txt_ids, in->img_ids, in->ids_per_sample ? B : 1, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s);
+  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, in->ids_per_sample ? B : 1, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s, ctx->ctx_ids, R));
+  return launch_cast_rows_bf16(ctx->ctx, ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s);
+}
+// The context of an evaluation, validated: R rows per sample (0: none, the text-to-image launches)
+int context_rows(const fmi_flux* m, const fmi_flux_context* ctx, int* R) {
+  *R = 0;
+  if (!ctx || ctx->R == 0) return FMI_OK;
+  if (ctx->R < 0) return fail(FMI_ERR_INVALID, "flux: context R must not be negative");
+  if (!ctx->ctx || !ctx->ctx_ids) return fail(FMI_ERR_INVALID, "flux: a context of R > 0 rows needs ctx and ctx_ids");
+  if (ctx->ctx_dtype != FMI_F32 && ctx->ctx_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux: ctx_dtype must be F32 or BF16");
+  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux: a context is not supported under sequence parallelism");
+  *R = ctx->R;
   return FMI_OK;
 }
 
@@ -902,13 +915,15 @@ int compute_vec_steps(fmi_flux* m, const fmi_flux_inputs* in, const float* tv_de
 }
 
 // One model evaluation given prepared static inputs; img_f32 (B,S,C) -> pred (B,S,C) f32.
+// R: context rows per sample.  The image stream then has in->S + R rows per sample — rows [in->S, in->S + R) of w.img_bf and of the RoPE table were
+// written by prepare_static — and everything between the input assembly and the final layer sees only that longer stream; img_f32 and pred stay (B, in->S, C).
 // mod_pre: this step's (B, n_mod) modulation vectors if the caller precomputed them (fmi_flux_denoise), else null.
 // txt_pre: txt_in(txt) if the caller computed it once for all steps (fmi_flux_denoise: it does not depend on the latent or on t), else null.
 int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, const float* timesteps_dev, float* pred, hipStream_t s,
-                 const float* mod_pre = nullptr, const float* txt_pre = nullptr) {
+                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
-  const int B = in->B, S = in->S, T = in->T, L = S + T;
+  const int B = in->B, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
   const int D = m->D, Mh = m->M, H = m->H, C = c.in_channels;
   const int nmod = (int)m->n_mod;
   const int64_t pe_bs = in->ids_per_sample ? (int64_t)L * 128 : 0;
@@ -930,7 +945,8 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
 
   {
     PhaseTimer pt(m, s, PH_EMBED);
-    FMI_TRY(launch_cast_to_bf16(img_f32, FMI_F32, w.img_bf, (int64_t)B * S * C, s));
+    if (R) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s));  // the state rows into their places
+    else FMI_TRY(launch_cast_to_bf16(img_f32, FMI_F32, w.img_bf, (int64_t)B * S * C, s));
     if (!mod_pre) FMI_TRY(compute_vec(m, in, timesteps_dev, w.vec, s));
     // img = img_in(img), txt = txt_in(txt)   (model.rs:811-812) -> f32 residual streams
     GemmProblem p[2];
@@ -1162,14 +1178,14 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
     }
   }
 
-  // ---------------- img = img[:, T:] ; LastLayer (model.rs:694-705): chunks = (scale, shift)
+  // ---------------- img = img[:, T:] ; LastLayer (model.rs:694-705): chunks = (scale, shift) — on the state's rows only: a context's rows end here
   {
     PhaseTimer pt(m, s, PH_FINAL);
     const float* mf = mod + m->mod_final_off;
     for (int b = 0; b < B; ++b)
       FMI_TRY(launch_layernorm_mod(w.x + ((size_t)b * L + T) * D, mf + (size_t)b * nmod, mf + (size_t)b * nmod + D, 0, 0,
-                                   w.xm + (size_t)b * S * D, S, D, 1e-6f, s));
-    GemmProblem p = make_problem(m->final_proj, w.xm, D, B * S, pred, C, EPI_STORE_F32);
+                                   w.xm + (size_t)b * Ss * D, Ss, D, 1e-6f, s));
+    GemmProblem p = make_problem(m->final_proj, w.xm, D, B * Ss, pred, C, EPI_STORE_F32);
     FMI_TRY(gemm1(m, p, m->final_proj, s));
   }
   return FMI_OK;
@@ -1504,26 +1520,35 @@ extern "C" int fmi_flux_state_buffer(fmi_flux* m, int index, void** ptr, size_t*
   return FMI_OK;
 }
 
-extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* pred_out, void* stream) {
+// One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
+extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
   FMI_TRY(check_inputs(m, in));
   if (!in->img || !in->timesteps || !pred_out) return fail(FMI_ERR_INVALID, "flux_forward: null img/timesteps/pred_out");
+  int R = 0;
+  FMI_TRY(context_rows(m, ctx, &R));
   hipStream_t s = (hipStream_t)stream;
-  FMI_TRY(ensure_workspace(m, in->B, in->S, in->T));
-  FMI_TRY(prepare_static(m, in, s));
+  FMI_TRY(ensure_workspace(m, in->B, in->S + R, in->T));
+  FMI_TRY(prepare_static(m, in, ctx, R, s));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, m->ws.img_f32, (int64_t)in->B * in->S * m->cfg.in_channels, s));
-  return forward_core(m, in, m->ws.img_f32, in->timesteps, pred_out, s);
+  return forward_core(m, in, m->ws.img_f32, in->timesteps, pred_out, s, nullptr, nullptr, R);
+}
+extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* pred_out, void* stream) {
+  return fmi_flux_forward_context(m, in, nullptr, pred_out, stream);
 }
 
 // The denoise loop of both entries.  x0 / noise / mask all null: fmi_flux_denoise, the plain Euler update.  All three set: fmi_flux_denoise_inpaint, the same
 // launches with the per-step update replaced by the masked one (launch_euler_blend); nothing before or inside the model evaluation knows the difference.
-static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, const float* x0, const float* noise,
-                        const float* mask, void* stream) {
+// ctx: the reference-image rows every evaluation appends to the state's (fmi_flux_denoise_context); the state, the update and the blend stay (B,S,C).
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
+                        const float* x0, const float* noise, const float* mask, void* stream) {
   FMI_TRY(check_inputs(m, in));
   if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
+  int Rc = 0;  // context rows per sample
+  FMI_TRY(context_rows(m, ctx, &Rc));
   hipStream_t s = (hipStream_t)stream;
   const int B = in->B;
-  FMI_TRY(ensure_workspace(m, B, in->S, in->T));
-  FMI_TRY(prepare_static(m, in, s));  // txt cast, y cast and the RoPE table are loop invariant
+  FMI_TRY(ensure_workspace(m, B, in->S + Rc, in->T));
+  FMI_TRY(prepare_static(m, in, ctx, Rc, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
   const int64_t n = (int64_t)B * in->S * m->cfg.in_channels;
   // t_vec = full(1f32, B) * t_curr  (sampling.rs:35,42): all steps' vectors uploaded once
   if ((int64_t)n_steps * B > 4096) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: n_steps * B > 4096");
@@ -1582,7 +1607,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout
     txt_pre = m->ws.x_txt0;
   }
   for (int i = 0; i < n_steps; ++i) {
-    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre));
+    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
     if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
@@ -1595,13 +1620,19 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout
 
 extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
                                 void* stream) {
-  return denoise_loop(m, in, img_inout, timesteps_host, n_steps, nullptr, nullptr, nullptr, stream);
+  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
                                         const float* x0, const float* noise, const float* mask, void* stream) {
   if (!x0 || !noise || !mask) return fail(FMI_ERR_INVALID, "flux_denoise_inpaint: x0, noise and mask are all required");
-  return denoise_loop(m, in, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
+  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
+}
+
+extern "C" int fmi_flux_denoise_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
+                                        int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
+  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_context: x0, noise and mask go together (all three or none)");
+  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
 }
 
 extern "C" int fmi_flux_set_profiling(fmi_flux* m, int enable) {

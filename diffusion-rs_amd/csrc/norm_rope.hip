@@ -204,11 +204,11 @@ int launch_qk_norm_rope_f32(const bf16_t* q, const bf16_t* k, int ld, int64_t in
   return FMI_OK;
 }
 
-// pe[b][l][i] = {cos(pos*inv_freq_i), sin(...)} for l in [0,T) from txt_ids and [T,T+S) from img_ids.
+// pe[b][l][i] = {cos(pos*inv_freq_i), sin(...)} for l in [0,T) from txt_ids, [T,T+S) from img_ids and [T+S,T+S+R) from ctx_ids (R = 0: no such rows).
 // inv_freq exactly as model.rs:71-74: 1f32 / (theta^(2j/dim) computed in f64) as f32.
-__global__ void rope_table_kernel(const float* __restrict txt_ids, const float* __restrict img_ids, int T, int S, int a0, int a1, int a2,
-                                  int theta, float* __restrict pe) {
-  const int L = T + S;
+__global__ void rope_table_kernel(const float* __restrict txt_ids, const float* __restrict img_ids, const float* __restrict ctx_ids, int T, int S, int R, int a0,
+                                  int a1, int a2, int theta, float* __restrict pe) {
+  const int L = T + S + R;
   const int half = (a0 + a1 + a2) / 2;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
@@ -222,7 +222,7 @@ __global__ void rope_table_kernel(const float* __restrict txt_ids, const float* 
   } else {
     axis = 2, j = i - (a0 + a1) / 2, dim = a2;
   }
-  const float* ids = l < T ? txt_ids + ((int64_t)b * T + l) * 3 : img_ids + ((int64_t)b * S + (l - T)) * 3;
+  const float* ids = l < T ? txt_ids + ((int64_t)b * T + l) * 3 : l < T + S ? img_ids + ((int64_t)b * S + (l - T)) * 3 : ctx_ids + ((int64_t)b * R + (l - T - S)) * 3;
   const float pos = ids[axis];
   const float inv_freq = 1.0f / (float)pow((double)theta, (double)(2 * j) / (double)dim);
   const float f = pos * inv_freq;
@@ -233,10 +233,10 @@ __global__ void rope_table_kernel(const float* __restrict txt_ids, const float* 
 }
 
 int launch_rope_table(const float* txt_ids, const float* img_ids, int B, int T, int S, const int* axes, int theta, float* pe,
-                      hipStream_t stream) {
+                      hipStream_t stream, const float* ctx_ids, int R) {
   const int half = (axes[0] + axes[1] + axes[2]) / 2;
-  const int64_t n = (int64_t)(T + S) * half;
-  hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)cdiv64(n, 256), B), dim3(256), 0, stream, txt_ids, img_ids, T, S, axes[0], axes[1],
+  const int64_t n = (int64_t)(T + S + R) * half;
+  hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)cdiv64(n, 256), B), dim3(256), 0, stream, txt_ids, img_ids, ctx_ids, T, S, R, axes[0], axes[1],
                      axes[2], theta, pe);
   FMI_LAUNCH_CHECK();
   return FMI_OK;

@@ -217,6 +217,54 @@ int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, 
   return FMI_OK;
 }
 
+namespace {
+__device__ __forceinline__ float row_elem_f32(float v) { return v; }
+__device__ __forceinline__ float row_elem_f32(bf16_t v) { return bf16_to_f32(v); }
+// n contiguous elements of each of B samples, sample b at src + b * src_bs -> bf16 at dst + b * dst_bs (f32_to_bf16, launch_cast_to_bf16's rounding; a bf16
+// source comes through unchanged).  V8: one item = 8 elements, read as 16-B words and written as one; else one element per item, any alignment, any n.
+template <typename T, bool V8>
+__global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const T* __restrict__ src, int64_t src_bs, bf16_t* __restrict__ dst, int64_t dst_bs, int64_t n, int64_t items) {
+  const int64_t per = V8 ? n / 8 : n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / per, e = (i % per) * (V8 ? 8 : 1);
+    const T* s = src + b * src_bs + e;
+    bf16_t* d = dst + b * dst_bs + e;
+    if constexpr (!V8) {
+      d[0] = f32_to_bf16(row_elem_f32(s[0]));
+    } else if constexpr (sizeof(T) == 4) {
+      const float4 lo = *reinterpret_cast<const float4*>(s), hi = *reinterpret_cast<const float4*>(s + 4);
+      uint4 o;
+      o.x = (uint32_t)f32_to_bf16(lo.x) | ((uint32_t)f32_to_bf16(lo.y) << 16), o.y = (uint32_t)f32_to_bf16(lo.z) | ((uint32_t)f32_to_bf16(lo.w) << 16);
+      o.z = (uint32_t)f32_to_bf16(hi.x) | ((uint32_t)f32_to_bf16(hi.y) << 16), o.w = (uint32_t)f32_to_bf16(hi.z) | ((uint32_t)f32_to_bf16(hi.w) << 16);
+      *reinterpret_cast<uint4*>(d) = o;
+    } else {
+      *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
+    }
+  }
+}
+template <typename T>
+int launch_cast_rows_bf16_t(const T* src, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream) {
+  const int64_t src_v = 16 / (int64_t)sizeof(T);  // elements of a 16-B word of the source
+  if (n % 8 == 0 && src_bs % src_v == 0 && dst_bs % 8 == 0 && aligned16(src) && aligned16(dst)) {
+    const int64_t items = (int64_t)B * (n / 8);
+    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, true>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items);
+  } else {
+    const int64_t items = (int64_t)B * n;
+    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, false>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items);
+  }
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+}  // namespace
+// The image-stream operand of a context evaluation is (B, S + R, C) bf16: the S state rows of every sample are cast into their places each
+// step and the R context rows once per call — both are this per-sample strided copy, one launch for all B samples.  src F32 or BF16.
+int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream) {
+  if (B <= 0 || n <= 0) return FMI_OK;
+  if (dt == FMI_F32) return launch_cast_rows_bf16_t((const float*)src, src_bs, dst, dst_bs, B, n, stream);
+  if (dt == FMI_BF16) return launch_cast_rows_bf16_t((const bf16_t*)src, src_bs, dst, dst_bs, B, n, stream);
+  return fail(FMI_ERR_INVALID, "cast_rows_bf16: the source must be F32 or BF16");
+}
+
 // y[r][n] = (y[r][n] + g[r % B][n]) + v[r % B][n]: the step-invariant terms of `vec` added in the order the accumulating GEMVs added them
 int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int N, hipStream_t stream) {
   const int64_t n = (int64_t)R * N;
@@ -437,6 +485,21 @@ extern "C" int fmi_encode_latents(const float* z, int B, int C, int h, int w, do
     hipLaunchKernelGGL(encode_latents_kernel<true>, map_grid(n), dim3(256), 0, (hipStream_t)stream, z, C, h, w, sc, sh, x0_out, img_ids_out, n);
   else
     hipLaunchKernelGGL(encode_latents_kernel<false>, map_grid(n), dim3(256), 0, (hipStream_t)stream, z, C, h, w, sc, sh, x0_out, img_ids_out, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+// the position ids of an (h2, w2) token grid: (id0, row0 + r, col0 + c) per token, one f32 addition each — fmi_pack_latents' ids at the defaults (0, 0, 0);
+// a reference image's tokens carry id0 = 1
+extern "C" int fmi_latent_ids(int B, int h2, int w2, float id0, float row0, float col0, float* ids_out, void* stream) {
+  if (!ids_out || B < 0 || h2 < 0 || w2 < 0) return fail(FMI_ERR_INVALID, "latent_ids: bad arguments");
+  const int64_t n = (int64_t)B * h2 * w2;
+  if (n == 0) return FMI_OK;
+  hipLaunchKernelGGL(map_kernel, map_grid(n), dim3(256), 0, (hipStream_t)stream, n, [=] __device__(int64_t tok) {
+    const int c = (int)(tok % w2), r = (int)((tok / w2) % h2);
+    float* o = ids_out + tok * 3;
+    o[0] = id0, o[1] = __fadd_rn(row0, (float)r), o[2] = __fadd_rn(col0, (float)c);
+  });
   FMI_LAUNCH_CHECK();
   return FMI_OK;
 }

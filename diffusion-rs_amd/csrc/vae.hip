@@ -228,17 +228,18 @@ __global__ void round_bf16_kernel(const float* __restrict x, bf16_t* __restrict 
   }
 }
 
-// row softmax, bf16 in place, f32 math (softmax_last_dim, nn/ops.rs:419-448)
-__global__ __launch_bounds__(256) void softmax_rows_bf16_kernel(bf16_t* __restrict x, int cols) {
+// row softmax, bf16 in place, f32 math (softmax_last_dim, nn/ops.rs:419-448).  A row holds `cols` values in `ld` elements (ld % 8 == 0, ld >= cols): the pad
+// elements [cols, ld) are never read as values (they count as -inf) and are written as 0, so the row can be the K operand of a GEMM over ld
+__global__ __launch_bounds__(256) void softmax_rows_bf16_kernel(bf16_t* __restrict x, int cols, int ld) {
   __shared__ float red[4];
-  bf16_t* r = x + (int64_t)blockIdx.x * cols;
-  const int nv = cols >> 3;
+  bf16_t* r = x + (int64_t)blockIdx.x * ld;
+  const int nv = ld >> 3;
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < nv; i += 256) {
     const uint4 raw = reinterpret_cast<const uint4*>(r)[i];
     const bf16_t* e = reinterpret_cast<const bf16_t*>(&raw);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) mx = fmaxf(mx, bf16_to_f32(e[k]));
+    for (int k = 0; k < 8; ++k) mx = fmaxf(mx, i * 8 + k < cols ? bf16_to_f32(e[k]) : -INFINITY);
   }
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bf16_kernel(bf16_t* __restri
     const uint4 raw = reinterpret_cast<const uint4*>(r)[i];
     const bf16_t* e = reinterpret_cast<const bf16_t*>(&raw);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) sum += __expf(bf16_to_f32(e[k]) - mx);
+    for (int k = 0; k < 8; ++k) sum += i * 8 + k < cols ? __expf(bf16_to_f32(e[k]) - mx) : 0.f;
   }
   sum = wave_sum(sum);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(256) void softmax_rows_bf16_kernel(bf16_t* __restri
     const bf16_t* e = reinterpret_cast<const bf16_t*>(&raw);
     float v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = __expf(bf16_to_f32(e[k]) - mx) * inv;
+    for (int k = 0; k < 8; ++k) v[k] = i * 8 + k < cols ? __expf(bf16_to_f32(e[k]) - mx) * inv : 0.f;
     reinterpret_cast<uint4*>(r)[i] = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
   }
 }
@@ -412,9 +413,10 @@ int vae_workspace(fmi_vae* v, int B, int h, int w) {
       max_act = std::max(max_act, (size_t)B * H * W * ch);
     }
   }
+  const size_t hw = (size_t)h * w, hwp = (hw + 63) / 64 * 64;  // run_attn pads the key dimension to the GEMM's K tile
+  if (c.mid_block_add_attention) max_act = std::max(max_act, (2 * hw + hwp) * (size_t)c.block_out_channels[c.n_blocks - 1]);  // q, k and V^T of one sample
   const size_t act_bytes = (max_act * 2 + 255) / 256 * 256;
-  const size_t hw = (size_t)h * w;
-  const size_t score_bytes = c.mid_block_add_attention ? (hw * hw * 2 + 255) / 256 * 256 : 256;
+  const size_t score_bytes = c.mid_block_add_attention ? (hw * hwp * 2 + 255) / 256 * 256 : 256;
   const int G = c.norm_num_groups;
   const size_t part_bytes = ((size_t)B * gn_max_chunks((int)((size_t)H * W)) * G * sizeof(float2) + 255) / 256 * 256;
   const size_t stat_bytes = ((size_t)B * G * sizeof(float2) + 255) / 256 * 256;
@@ -486,15 +488,16 @@ struct AttnW {
   const Conv &q, &k, &v, &o;
 };
 int run_attn(fmi_vae* v, const AttnW& a, int B, int H, int W, hipStream_t s) {
-  const int C = a.q.cout, HW = H * W;
-  if (HW % 64) return fail(FMI_ERR_UNSUPPORTED, "vae attention: latent h*w must be a multiple of 64");
+  // HWp: the key dimension padded to the GEMM's K tile (a 96 x 64 image has 12 x 8 = 96 latent positions).  The scores and V^T then have rows of HWp elements:
+  // the softmax writes zeros into the pad of the probabilities, V^T's pad is zeroed once per call, and P V runs over HWp.  HW % 64 == 0: nothing changes.
+  const int C = a.q.cout, HW = H * W, HWp = (HW + 63) / 64 * 64;
   FMI_TRY(run_gn_trunk(v, a.gn, v->fx, v->bt1, nullptr, B, HW, 0, s));
   const float scale = (float)(1.0 / sqrt((double)C));
   for (int b = 0; b < B; ++b) {
     const bf16_t* xn = v->bt1 + (size_t)b * HW * C;
     bf16_t* q = v->bt2;                       // (HW, C)
     bf16_t* k = v->bt2 + (size_t)HW * C;      // (HW, C)
-    bf16_t* vt = v->bt2 + (size_t)2 * HW * C; // (C, HW)
+    bf16_t* vt = v->bt2 + (size_t)2 * HW * C; // (C, HWp)
     bf16_t* o = v->bsc;                       // (HW, C)
     GemmProblem p[2];
     p[0] = conv_problem(xn, a.q.w, a.q.b, nullptr, q, 1, H, W, C, C, 1, 0, v->zero);
@@ -502,17 +505,18 @@ int run_attn(fmi_vae* v, const AttnW& a, int B, int H, int W, hipStream_t s) {
     FMI_TRY(launch_gemm(p, 2, s));
     // V^T (C, HW) = Wv (C,C) · xn(HW,C)^T ; the v bias is added after P·V (softmax rows sum to 1)
     GemmProblem pv{};
-    pv.A = a.v.w, pv.W = xn, pv.out = vt, pv.M = C, pv.N = HW, pv.K = C, pv.lda = C, pv.ldw = C, pv.ldo = HW, pv.epi = EPI_STORE_BF16, pv.alpha = 1.f;
+    if (HWp != HW) FMI_HIP_TRY(hipMemsetAsync(vt, 0, (size_t)C * HWp * 2, s));
+    pv.A = a.v.w, pv.W = xn, pv.out = vt, pv.M = C, pv.N = HW, pv.K = C, pv.lda = C, pv.ldw = C, pv.ldo = HWp, pv.epi = EPI_STORE_BF16, pv.alpha = 1.f;
     FMI_TRY(launch_gemm(&pv, 1, s));
-    // scores = (q k^T) * scale  -> bf16 (HW, HW)
+    // scores = (q k^T) * scale  -> bf16 (HW, HWp)
     GemmProblem ps{};
-    ps.A = q, ps.W = k, ps.out = v->scores, ps.M = HW, ps.N = HW, ps.K = C, ps.lda = C, ps.ldw = C, ps.ldo = HW, ps.epi = EPI_SCALE_BF16, ps.alpha = scale;
+    ps.A = q, ps.W = k, ps.out = v->scores, ps.M = HW, ps.N = HW, ps.K = C, ps.lda = C, ps.ldw = C, ps.ldo = HWp, ps.epi = EPI_SCALE_BF16, ps.alpha = scale;
     FMI_TRY(launch_gemm(&ps, 1, s));
-    hipLaunchKernelGGL(softmax_rows_bf16_kernel, dim3(HW), dim3(256), 0, s, v->scores, HW);
+    hipLaunchKernelGGL(softmax_rows_bf16_kernel, dim3(HW), dim3(256), 0, s, v->scores, HW, HWp);
     FMI_LAUNCH_CHECK();
     // o = P · V + b_v
     GemmProblem po{};
-    po.A = v->scores, po.W = vt, po.bias = a.v.b, po.out = o, po.M = HW, po.N = C, po.K = HW, po.lda = HW, po.ldw = HW, po.ldo = C, po.epi = EPI_STORE_BF16,
+    po.A = v->scores, po.W = vt, po.bias = a.v.b, po.out = o, po.M = HW, po.N = C, po.K = HWp, po.lda = HWp, po.ldw = HWp, po.ldo = C, po.epi = EPI_STORE_BF16,
     po.alpha = 1.f;
     FMI_TRY(launch_gemm(&po, 1, s));
     // x[b] += to_out(o)   (in place on the f32 trunk)

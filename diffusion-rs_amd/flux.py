@@ -299,21 +299,49 @@ class FluxModel:
                            _ptr(timesteps), _ptr(y), _TORCH_DT[y.dtype], _ptr(guidance), B, S, T, 0)
         return inp, keep
 
-    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None):
-        """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32."""
+    def _context(self, img_ids, context, context_ids):
+        """fmi_flux_context of a reference image's packed latents (B,R,C) f32 | bf16 and their ids (B,R,3) f32, with the tensors it points into."""
+        if context is None or context_ids is None:
+            raise ValueError("context= and context_ids= go together")
+        if context.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("context must be float32 or bfloat16")
+        if context_ids.dtype != torch.float32:
+            raise TypeError("context_ids must be float32")
+        if context.dim() != 3:
+            raise ValueError(f"context must be (B,R,C), got {tuple(context.shape)}")
+        B, R = int(context.shape[0]), int(context.shape[1])
+        if B != int(img_ids.shape[0]) or tuple(context_ids.shape) != (B, R, 3):
+            raise ValueError(f"context is {tuple(context.shape)} and context_ids {tuple(context_ids.shape)} for a batch of {int(img_ids.shape[0])}")
+        if int(context.shape[2]) != self.cfg["in_channels"]:
+            raise ValueError(f"context has {int(context.shape[2])} channels, the model's in_channels is {self.cfg['in_channels']}")
+        if context.device != img_ids.device or context_ids.device != img_ids.device:
+            raise ValueError(f"context is on {context.device} and context_ids on {context_ids.device}, img_ids on {img_ids.device}")
+        # (a tensor that is contiguous already is passed as it lies, whatever its address: the library picks the access width)
+        keep = [context.contiguous(), context_ids.contiguous()]
+        return L.FluxContext(_ptr(keep[0]), _TORCH_DT[context.dtype], _ptr(keep[1]), R), keep
+
+    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None):
+        """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.
+        context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's."""
         inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
         pred = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        L.check(self.lib.fmi_flux_forward(self.h, C.byref(inp), _ptr(pred), _stream()), self.lib)
+        if context is None and context_ids is None:
+            L.check(self.lib.fmi_flux_forward(self.h, C.byref(inp), _ptr(pred), _stream()), self.lib)
+            return pred
+        ctx, keep_ctx = self._context(img_ids, context, context_ids)  # (keep_ctx, like keep, holds the tensors until the call has returned)
+        L.check(self.lib.fmi_flux_forward_context(self.h, C.byref(inp), C.byref(ctx), _ptr(pred), _stream()), self.lib)
         return pred
 
-    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None):
+    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
-        latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h)."""
+        latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
+        context= / context_ids=: reference-image tokens every evaluation appends to the state's (fmi_flux_denoise_context); the state stays (B,S,C)."""
         img = img.to(torch.float32).clone().contiguous()
         inp, keep = self._inputs(None, img_ids, txt, txt_ids, None, y, guidance)
         ts = (C.c_double * len(timesteps))(*timesteps)
-        if x0 is None and noise is None and mask is None:
+        has_ctx = context is not None or context_ids is not None
+        if not has_ctx and x0 is None and noise is None and mask is None:
             L.check(self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _stream()), self.lib)
             return img
         extra = []
@@ -323,9 +351,14 @@ class FluxModel:
                     raise ValueError(f"denoise: {nm} is {tuple(t.shape)}, img is {tuple(img.shape)}")
                 t = t.to(device=img.device, dtype=torch.float32).contiguous()
             extra.append(t)
-        # a missing one reaches the library as NULL: it answers FMI_ERR_INVALID
-        L.check(self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
-                                                  _stream()), self.lib)
+        # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
+        if not has_ctx:
+            L.check(self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
+                                                      _stream()), self.lib)
+        else:
+            ctx, keep_ctx = self._context(img_ids, context, context_ids)  # (held until the call has returned)
+            L.check(self.lib.fmi_flux_denoise_context(self.h, C.byref(inp), C.byref(ctx), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]),
+                                                      _ptr(extra[2]), _stream()), self.lib)
         return img
 
     def set_profiling(self, on: bool):
@@ -482,6 +515,14 @@ def encode_latents(z, scale_factor, shift_factor):
     ids = torch.empty((B, (h // 2) * (w // 2), 3), dtype=torch.float32, device=z.device)
     L.check(L.load().fmi_encode_latents(_ptr(z), B, Cc, h, w, scale_factor, shift_factor, _ptr(x0), _ptr(ids), _stream()))
     return x0, ids
+
+
+def latent_ids(B, h2, w2, id0=0.0, row0=0.0, col0=0.0, device="cuda"):
+    """Position ids of an (h2, w2) token grid, (B,h2*w2,3) f32 = (id0, row0 + r, col0 + c): pack_latents' ids at the defaults; a reference image's tokens
+    take id0 = 1."""
+    ids = torch.empty((B, h2 * w2, 3), dtype=torch.float32, device=device)
+    L.check(L.load().fmi_latent_ids(B, h2, w2, float(id0), float(row0), float(col0), _ptr(ids), _stream()))
+    return ids
 
 
 def scale_noise(x0, noise, t):

@@ -29,6 +29,16 @@ _ST_DTYPES = {"F32": (torch.float32, 4), "F16": (torch.float16, 2), "BF16": (tor
               "I32": (torch.int32, 4), "I64": (torch.int64, 8), "F64": (torch.float64, 8)}
 
 
+SUPPORTED_PIPELINES = ("FluxPipeline", "FluxKontextPipeline")  # Kontext: the same components, FLUX.1-dev's transformer
+
+
+def check_pipeline_class(class_name) -> str:
+    """model_index.json's `_class_name` (pipelines/mod.rs:146-149): a pipeline this package loads, or ValueError."""
+    if class_name not in SUPPORTED_PIPELINES:
+        raise ValueError("Only FluxPipeline is supported")
+    return class_name
+
+
 def _safetensors_from_buffer(buf) -> Iterator[Tuple[str, torch.Tensor]]:
     """Zero-copy views of every tensor in a safetensors image held in `buf` (mmap / memoryview)."""
     n = struct.unpack("<Q", bytes(buf[:8]))[0]

@@ -138,6 +138,29 @@ def img2img_timesteps(timesteps: Sequence[float], strength: float) -> list:
     return list(timesteps[n - n_run:])
 
 
+def check_reference(t: torch.Tensor, B: int) -> torch.Tensor:
+    """The shape rules of `reference=`, on any device: uint8 (Hr,Wr,3) / (n,Hr,Wr,3) or float (n,3,Hr,Wr), Hr and Wr multiples of 16 (whatever
+    params.height / width are), n = 1 (broadcast) or B.  Returns the tensor with its batch dimension; ValueError otherwise."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("reference must be a numpy array or a torch tensor")
+    if t.dtype == torch.uint8:
+        t = t.unsqueeze(0) if t.dim() == 3 else t
+        if t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError(f"a uint8 reference must be (B,Hr,Wr,3) or (Hr,Wr,3), got {tuple(t.shape)}")
+        Hr, Wr = int(t.shape[1]), int(t.shape[2])
+    elif t.is_floating_point():
+        if t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError(f"a float reference must be (B,3,Hr,Wr), got {tuple(t.shape)}")
+        Hr, Wr = int(t.shape[2]), int(t.shape[3])
+    else:
+        raise ValueError(f"reference must be uint8 or float, got {t.dtype}")
+    if Hr <= 0 or Wr <= 0 or Hr % 16 or Wr % 16:
+        raise ValueError(f"reference needs a height and width that are positive multiples of 16, got {Hr} x {Wr}")
+    if t.shape[0] not in (1, B):
+        raise ValueError(f"reference holds {t.shape[0]} samples for {B} prompts (one is broadcast)")
+    return t
+
+
 class Pipeline:
     """== diffusion_rs_core::Pipeline (pipelines/mod.rs:110-270) for FluxPipeline."""
 
@@ -212,8 +235,7 @@ class Pipeline:
     def _load_checkpoint(self, path: str, transformer_path: Optional[str], load_dit: bool = True):
         from . import loader
         fl = loader.FileLoader(path)
-        if fl.read_json("model_index.json").get("_class_name") != "FluxPipeline":  # pipelines/mod.rs:146-149
-            raise ValueError("Only FluxPipeline is supported")
+        loader.check_pipeline_class(fl.read_json("model_index.json").get("_class_name"))  # pipelines/mod.rs:146-149; FluxKontextPipeline has the same components
         sc = fl.read_json("scheduler/scheduler_config.json")
         self.scheduler = F.SchedulerConfig(sc["base_image_seq_len"], sc["base_shift"], sc["max_image_seq_len"], sc["max_shift"], sc["shift"],
                                            sc["use_dynamic_shifting"])
@@ -327,9 +349,23 @@ class Pipeline:
             mask = batched(m.to(device=self.device, dtype=torch.float32), "mask")
         return image, mask
 
+    def _reference_image(self, reference, B):
+        """Check `reference=` and bring it to its device form, f32 (B,3,Hr,Wr) in [-1,1] (None stays None)."""
+        if reference is None:
+            return None
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("reference= is not wired through sequence parallelism: disable_sequence_parallel() first")
+        t = torch.from_numpy(np.ascontiguousarray(reference)) if isinstance(reference, np.ndarray) else reference
+        t = check_reference(t, B)
+        if t.dtype == torch.uint8:
+            t = F.preprocess_u8(t.to(self.device), interleaved=True)
+        else:
+            t = t.to(device=self.device, dtype=torch.float32)
+        return t if t.shape[0] == B else t.expand(B, *t.shape[1:])
+
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
-                        image=None, strength: float = 1.0, mask=None, return_latents: bool = False):
+                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -340,7 +376,12 @@ class Pipeline:
         noise text to image would have started from (same seed / sample ids, or `latents=`).  UNLIKE diffusers, which samples the VAE posterior, the
         source latents are the posterior MEAN: deterministic, no second noise stream.  `mask=` ((B,H,W) / (H,W), float in [0,1] or bool; 1 = repaint,
         0 = keep) makes it inpainting (FluxInpaintPipeline's step): every step blends the re-noised source back in where the 8x8-mean latent mask keeps
-        it, and kept latents end as the source's exactly.  `return_latents=True` returns (u8, final packed latents (B,S,64) f32)."""
+        it, and kept latents end as the source's exactly.  `return_latents=True` returns (u8, final packed latents (B,S,64) f32).
+
+        Reference-image conditioning (`reference=`, FLUX.1 Kontext): u8 (Hr,Wr,3) / (B,Hr,Wr,3) or f32 (B,3,Hr,Wr) in [-1,1], numpy or torch, one
+        image broadcast over the prompts; Hr and Wr are multiples of 16 and need not be params.height / width.  It is encoded like `image=` (posterior mean;
+        diffusers' Kontext pipeline takes the mode too) and its tokens, with 1 in axis 0 of their ids, join the image tokens of every model evaluation; the
+        schedule's mu comes from the output's token count alone.  Combines with image= / strength= / mask=.  Not resized to Kontext's preferred resolutions."""
         B = len(prompts)
         ids = list(sample_ids) if sample_ids is not None else [first_sample + b for b in range(B)]
         if len(ids) != B:
@@ -350,6 +391,7 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         image, mask = self._source_image(image, mask, strength, B, params)
+        reference = self._reference_image(reference, B)
         sp = getattr(self, "_sp", None)
         if sp is not None and B > 1:  # sequence parallel: the ranks of the group work on ONE image at a time
             outs = [self.generate_tensor(
@@ -365,7 +407,8 @@ class Pipeline:
                     prompts[sl], params, embeddings=None if embeddings is None else (embeddings[0][sl], embeddings[1][sl]),
                     latents=None if latents is None else latents[sl], seed=seed,
                     token_ids=None if token_ids is None else (token_ids[0][sl], token_ids[1][sl]), sample_ids=ids[sl],
-                    image=None if image is None else image[sl], strength=strength, mask=None if mask is None else mask[sl], return_latents=return_latents))
+                    image=None if image is None else image[sl], strength=strength, mask=None if mask is None else mask[sl],
+                    reference=None if reference is None else reference[sl], return_latents=return_latents))
             return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
         cfg = self.flux.cfg
         dev = self.device
@@ -403,19 +446,24 @@ class Pipeline:
                 img = F.scale_noise(x0, noise, timesteps[0])
                 if mask is not None:
                     inpaint = dict(x0=x0, noise=noise, mask=F.latent_mask(mask, x0.shape[2] // 4))
+            context = {}
+            if reference is not None:  # its packed latents are rows of every evaluation, never of the state; mu and the schedule above know S only
+                ctx, _ = F.encode_latents(self.vae.encode(reference), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
+                context = dict(context=ctx, context_ids=F.latent_ids(B, reference.shape[2] // 16, reference.shape[3] // 16, id0=1.0, device=dev))
             if getattr(self, "_int8_pending", False):
-                self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps)
+                self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
+                                                  {k: v[:1] for k, v in context.items()})
             if sp is not None:  # every rank holds the same inputs; each denoises its token shard, then all get the latents
                 img = sp.gather(self.flux.denoise(sp.shard(img), sp.shard(img_ids), sp.shard(t5_emb), sp.shard(txt_ids), clip_emb, guidance, timesteps))
             else:
-                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint)
+                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context)
             z = F.unpack_latents(img, 16, h, w, self.vae.scale_factor(), self.vae.shift_factor())
             u8 = F.postprocess_u8(self.vae.decode(z))
             return (u8, img) if return_latents else u8
 
     INT8_CALIBRATION_POINTS = 4
 
-    def _int8_calibrate_and_quantize(self, img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps):
+    def _int8_calibrate_and_quantize(self, img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, context=None):
         """ModelDType.I8, first request: INT8_CALIBRATION_POINTS evaluations of the bf16 model on ONE sample at timesteps spread over the request's schedule
         record the per-channel absmax of every block linear's input (the outlier channels of a DiT are the same at every step and for every prompt: they
         come from the AdaLN weights), then the block linears are quantised with the smoothing factors folded in.  ~0.25 s once per model at 1024 x 1024."""
@@ -424,7 +472,7 @@ class Pipeline:
         self.flux.calibrate_int8(True)
         for i in pts:
             t = torch.full((1,), float(timesteps[i]), dtype=torch.float32, device=self.device)
-            self.flux.forward(img, img_ids, t5_emb, txt_ids, t, clip_emb, guidance)
+            self.flux.forward(img, img_ids, t5_emb, txt_ids, t, clip_emb, guidance, **(context or {}))
         self.flux.quantize_int8()
         self._int8_pending = False
 
@@ -491,14 +539,15 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                return_latents: bool = False, **kw):
+                reference=None, return_latents: bool = False, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
-        image= / strength= / mask=: image to image and inpainting, see generate_tensor; return_latents=True returns (images, final packed latents)."""
+        image= / strength= / mask=: image to image and inpainting, reference=: reference-image conditioning, see generate_tensor; return_latents=True
+        returns (images, final packed latents)."""
         from . import dist as D
         rank, world = D.world()
-        kw = dict(kw, image=image, strength=strength, mask=mask, return_latents=return_latents)
+        kw = dict(kw, image=image, strength=strength, mask=mask, reference=reference, return_latents=return_latents)
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if getattr(self, "_sp", None) is not None:  # all ranks produce every image together; rank 0 returns them
             u8 = self.generate_tensor(prompts, params, **kw)
@@ -512,6 +561,7 @@ class Pipeline:
                 raise ValueError("return_latents= is not gathered across ranks: call generate_tensor on the rank that holds the sample")
             if n > 0:  # batched device tensors, so that a rank picks its rows of them exactly as it picks its rows of `latents`
                 kw["image"], kw["mask"] = self._source_image(image, mask, strength, n, params)
+                kw["reference"] = self._reference_image(reference, n)
             if getattr(self, "_int8_pending", False) and n > 0:
                 # every rank calibrates on the SAME sample — global sample 0 of this request — so that all ranks hold the same int8 weights and an image does
                 # not depend on the rank that produced it (one extra image per rank, once per model)
@@ -519,7 +569,7 @@ class Pipeline:
                 for key in ("embeddings", "token_ids"):
                     if sub.get(key) is not None:
                         sub[key] = tuple(t[:1] for t in sub[key])
-                for key in ("latents", "image", "mask"):
+                for key in ("latents", "image", "mask", "reference"):
                     if sub.get(key) is not None:
                         sub[key] = sub[key][:1]
                 first = sub.pop("first_sample", 0)
@@ -533,7 +583,7 @@ class Pipeline:
                 for key in ("embeddings", "token_ids"):
                     if sub.get(key) is not None:
                         sub[key] = tuple(pick(t, ids) for t in sub[key])
-                for key in ("latents", "image", "mask"):
+                for key in ("latents", "image", "mask", "reference"):
                     if sub.get(key) is not None:
                         sub[key] = pick(sub[key], ids)
                 first = sub.pop("first_sample", 0)

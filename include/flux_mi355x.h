@@ -44,6 +44,7 @@ extern "C" {
  *   the library's per-stream scratch (fmi_sdpa_*, fmi_linear_fp8 / _i8, fmi_groupnorm_nhwc) now enqueue their kernels under one lock: host threads
  *   may share a stream.  Later additions under the same number: fmi_flux_get_tensor and the LoRA adapter calls fmi_flux_lora_*.
  *   Then, still 6: image to image and inpainting — fmi_preprocess_u8, fmi_latent_mask, fmi_encode_latents, fmi_scale_noise, fmi_flux_denoise_inpaint.
+ *   Then, still 6: reference-image (FLUX.1 Kontext) conditioning — fmi_flux_context, fmi_flux_forward_context, fmi_flux_denoise_context, fmi_latent_ids.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -378,6 +379,27 @@ int fmi_flux_denoise(fmi_flux*, const fmi_flux_inputs* in, float* img_inout,
 int fmi_flux_denoise_inpaint(fmi_flux*, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
                              const float* x0, const float* noise, const float* mask, void* stream);
 
+/* Reference-image ("in-context") conditioning as in FLUX.1 Kontext (the reference has no counterpart).  The reference image is encoded and
+ * packed like the latents (fmi_vae_encode, fmi_encode_latents) and its R tokens are appended to the image tokens with a 1 in axis 0 of their position ids
+ * (fmi_latent_ids with id0 = 1).  A model evaluation is Flux::forward over img' = cat([img, ctx], 1) and img_ids' = cat([img_ids, ctx_ids], 1) — S + R
+ * image-stream rows per sample in every block — and the prediction is rows [0, S) of each sample: the final layer runs on those rows only.
+ *   fmi_flux_forward_context  one such evaluation; `in` as for fmi_flux_forward, pred_out (B,S,in_channels) f32.  Bit for bit rows [0, S) of fmi_flux_forward on
+ *                             the concatenated inputs.
+ *   fmi_flux_denoise_context  the loop.  The state is img_inout alone, (B,S,in_channels) f32; the Euler update — and with x0 / noise / mask (all three or none)
+ *                             fmi_flux_denoise_inpaint's blend — touch those rows only, with the same expressions and roundings.  The context's rows of the
+ *                             model input and of the RoPE table are written once per call; each step casts only the S state rows.
+ * With R = 0 or a NULL context both are fmi_flux_forward / fmi_flux_denoise / fmi_flux_denoise_inpaint: the same launches.
+ * FMI_ERR_INVALID: R < 0; R > 0 with a NULL ctx or ctx_ids; a ctx_dtype other than F32 / BF16; x0 / noise / mask given only in part.
+ * FMI_ERR_UNSUPPORTED: a context (R > 0) under fmi_flux_set_sequence_parallel. */
+typedef struct fmi_flux_context {
+  const void* ctx;      fmi_dtype ctx_dtype; /* (B,R,in_channels) F32|BF16: packed reference latents, fmi_encode_latents' output */
+  const float* ctx_ids;                      /* (B,R,3) f32; in->ids_per_sample applies to them as to img_ids */
+  int R;                                     /* context tokens per sample; 0 (or a NULL struct) = no context */
+} fmi_flux_context;
+int fmi_flux_forward_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream);
+int fmi_flux_denoise_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
+                             const float* x0, const float* noise, const float* mask, void* stream);
+
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
  * With FMI_ROCTX=1 in the environment every phase is also a roctx range (roctxRangePushA / Pop from
@@ -439,7 +461,7 @@ int fmi_vae_decode(fmi_vae*, const float* z, int B, int h, int w, float* image_o
  * tensors, encode only `encoder.*` (+ `quant_conv.*`). */
 int fmi_vae_encode(fmi_vae*, const float* image, int B, int H, int W, const float* noise, float* z_out, float* moments_out, void* stream);
 /* AttnBlock::forward (vaes/vae.rs:95-111) of the decoder's mid block as one op: x and out (B,H,W,C) bf16 NHWC device
- * buffers, C = block_out_channels.last, H*W a multiple of 64; out = x + to_out(sdpa(q,k,v)(group_norm(x))).  Needs the
+ * buffers, C = block_out_channels.last; out = x + to_out(sdpa(q,k,v)(group_norm(x))).  Needs the
  * `decoder.*` tensors.  Used by the parity tests to check the block alone at production size. */
 int fmi_vae_mid_attention(fmi_vae*, const void* x_bf16_nhwc, int B, int H, int W, void* out_bf16_nhwc, void* stream);
 
@@ -534,6 +556,9 @@ int fmi_latent_mask(const float* mask, int B, int C, int H, int W, float* out, v
  * as fmi_pack_latents writes them (img_ids_out may be NULL). */
 int fmi_encode_latents(const float* z, int B, int C, int h, int w, double scale_factor, double shift_factor,
                        float* x0_out, float* img_ids_out, void* stream);
+/* Position ids as fmi_pack_latents writes them, with a caller-chosen axis 0 and origin: ids_out (B,h2*w2,3) f32 = (id0, row0 + r, col0 + c) for the token at
+ * row r, column c of the (h2, w2) grid (one f32 addition each).  (0, 0, 0) gives fmi_pack_latents' ids; a reference image's tokens take id0 = 1. */
+int fmi_latent_ids(int B, int h2, int w2, float id0, float row0, float col0, float* ids_out, void* stream);
 /* FlowMatchEulerDiscreteScheduler.scale_noise: out = (1 - t) * x0 + t * noise over n f32 elements, t rounded to f32 and
  * 1 - t computed once: t = 1 gives noise and t = 0 gives x0 bit for bit.  The start state of image-to-image at
  * t = timesteps[num_steps - n_run]. */
