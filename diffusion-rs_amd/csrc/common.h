@@ -11,7 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <set>
 #include <string>
+#include <vector>
 
 #include "../../include/flux_mi355x.h"
 
@@ -72,8 +74,84 @@ inline int use_device_ordinal(int dev) {
   return FMI_OK;
 }
 
-// ---------------------------------------------------------------- bf16 helpers (device)
+// ---------------------------------------------------------------- device memory (host)
+// The owner of one hipMalloc block and its size.  It lives as a member of a heap-allocated handle or as a local variable, NEVER in static or thread-local
+// storage: its destructor would call into a HIP runtime that may already be unloaded at process exit (capi.hip's ScratchCache has no freeing destructor
+// for that reason).  It never synchronises: a caller that regrows a block the device may still read waits first, at the place it always did.
+struct DeviceBuffer {
+  void* ptr = nullptr;
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr), bytes_(o.bytes_) { o.ptr = nullptr, o.bytes_ = 0; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {  // frees what it held: the caller decides that this is the moment
+    if (this != &o) {
+      reset();
+      ptr = o.ptr, bytes_ = o.bytes_;
+      o.ptr = nullptr, o.bytes_ = 0;
+    }
+    return *this;
+  }
+  ~DeviceBuffer() { reset(); }
+  // releases what it holds, then allocates exactly `bytes`; on failure it is empty and the error is the caller's to report
+  hipError_t alloc(size_t bytes) {
+    reset();
+    const hipError_t e = hipMalloc(&ptr, bytes);
+    if (e == hipSuccess) bytes_ = bytes;
+    else ptr = nullptr;
+    return e;
+  }
+  void reset() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr, bytes_ = 0;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(ptr); }
+  size_t bytes() const { return bytes_; }
+  explicit operator bool() const { return ptr != nullptr; }
+
+ private:
+  size_t bytes_ = 0;
+};
+static_assert(!std::is_copy_constructible_v<DeviceBuffer>);
+
 typedef uint16_t bf16_t;  // raw bits
+// Weight staging (small_ops.hip).  n elements of a host or device array of F32 / F16 / BF16 arrive in `dst` (device) as bf16 / f32: a plain copy when the
+// dtype already matches, else staged in a local DeviceBuffer, cast on the null stream, and the device is synchronised before the staging block goes.
+int upload_as_bf16(const void* src, fmi_dtype dtype, int64_t n, bf16_t* dst);
+int upload_as_f32(const void* src, fmi_dtype dtype, int64_t n, float* dst);
+// Two arrays (quantised codes + their scales) staged on the device for run(dev_a, dev_b) -> int, which expands them on the null stream; synchronises, frees.
+template <class F>
+int with_staged_pair(const void* a, size_t abytes, const void* b, size_t bbytes, F&& run) {
+  DeviceBuffer da, db;
+  FMI_HIP_TRY(da.alloc(abytes));
+  FMI_HIP_TRY(db.alloc(bbytes));
+  hipError_t e = hipMemcpy(da.ptr, a, abytes, hipMemcpyDefault);
+  if (e == hipSuccess) e = hipMemcpy(db.ptr, b, bbytes, hipMemcpyDefault);
+  int rc = e == hipSuccess ? run(da.ptr, db.ptr) : fail(FMI_ERR_HIP, hipGetErrorString(e));
+  e = hipDeviceSynchronize();
+  if (rc == FMI_OK && e != hipSuccess) rc = fail(FMI_ERR_HIP, hipGetErrorString(e));
+  return rc;
+}
+// The named tensors a model handle still waits for (fmi_*_missing_count / _missing_name, and the "N tensors not set" refusal of an evaluation).
+struct MissingSet {
+  std::set<std::string> names;
+  void insert(const std::string& n) { names.insert(n); }
+  void erase(const std::string& n) { names.erase(n); }
+  int count() const { return (int)names.size(); }
+  const char* name(int i) const {  // materialised for the C accessor: valid until the next call
+    if (i < 0 || i >= count()) return nullptr;
+    list_.assign(names.begin(), names.end());
+    return list_[i].c_str();
+  }
+  int ready(const std::string& who) const {
+    if (names.empty()) return FMI_OK;
+    return fail(FMI_ERR_STATE, who + ": " + std::to_string(names.size()) + " tensors not set, first: " + *names.begin());
+  }
+
+ private:
+  mutable std::vector<std::string> list_;
+};
+
+// ---------------------------------------------------------------- bf16 helpers (device)
 
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // round-to-nearest-even (same rule as half::bf16::from_f32) on the hardware converter:

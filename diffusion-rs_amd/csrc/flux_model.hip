@@ -31,8 +31,8 @@ namespace {
 
 enum ArenaId { AR_BASE = 0, AR_MOD, AR_BLOCKS, AR_Q4, AR_COUNT };
 struct Arena {
-  char* base = nullptr;
-  size_t bytes = 0;  // layout size
+  DeviceBuffer base;
+  size_t bytes = 0;  // layout size (known before the arena is allocated)
 };
 enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_DENSE = 100 };
 
@@ -43,9 +43,9 @@ struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N)
   int ar = AR_BASE;
   size_t w_off = 0, q_off = 0, am_off = 0;  // byte offsets in `ar` / in Q4 (packed codes, absmax sized for blocksize 64)
   // quantised form, used instead of w when q_type != 0 (set by finalize(): every part holds the same kind)
-  uint8_t* wq = nullptr;   // Q4 arena (4-bit) or its own allocation (int8)
+  uint8_t* wq = nullptr;   // Q4 arena (4-bit) or own_wq (int8): what the kernels read
   float* absmax = nullptr;
-  bool q_own = false;
+  DeviceBuffer own_wq, own_absmax;  // int8 matrices own their storage (1 B per weight: they do not fit the 4-bit arena's slots)
   int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N))
   // optional fp8 form (fmi_flux_quantize_fp8): e4m3 (N,K) + per-output-channel f32 scale, used instead of w
   uint8_t* w8 = nullptr;
@@ -112,13 +112,11 @@ struct fmi_flux {
   std::vector<SingleW> sgl;
   int64_t mod_final_off = 0, n_mod = 0;
   std::map<std::string, Dest> names;
-  std::set<std::string> missing;
-  std::vector<std::string> missing_list;  // materialised for the C accessor
+  MissingSet missing;
   // workspace
   struct WS {
     int B = 0, S = 0, T = 0;
-    char* base = nullptr;
-    size_t bytes = 0;
+    DeviceBuffer base;
     float *x_img, *x_txt, *x_txt0, *x, *vec, *mod, *temb, *h1, *yf, *pe, *img_f32, *pred_tmp, *tv;  // x_txt0: txt_in(txt), the same at every step of an image
     bf16_t *img_bf, *txt_bf, *xm, *qkv_img, *qkv_txt, *big, *Qh, *Kh, *Vt, *attn_img, *attn_txt, *hid, *vec_bf;
     uint8_t* a8 = nullptr;  // fp8 mode: the current GEMM input, rows [txt | img], (B*L, <= D+M) e4m3
@@ -139,8 +137,8 @@ struct fmi_flux {
   int attn_kind = -1;  // fmi_flux_set_attention_kernel: 0..5 = this handle's attention kernel, -1 = follow the process-wide switch
   // 4-bit weights, large-M regime: per-layer streaming dequant into a reusable bf16 scratch
   // all denoise steps' modulation vectors (n_steps*B, n_mod) and vec (n_steps*B, D), see fmi_flux_denoise
-  float *mod_steps = nullptr, *vec_steps = nullptr, *temb_steps = nullptr, *h1_steps = nullptr;
-  bf16_t* vec_steps_bf = nullptr;  // silu(vec_steps) in bf16: A operand of the modulation GEMM
+  DeviceBuffer mod_steps, vec_steps, temb_steps, h1_steps;  // f32
+  DeviceBuffer vec_steps_bf;                                // silu(vec_steps) in bf16: A operand of the modulation GEMM
   size_t mod_steps_rows = 0;
   int mod_gemm = 1;  // fmi_flux_denoise: 1 = all steps' modulation vectors in one MFMA GEMM when there are more than 4 rows (else GEMV passes of 4 rows), 0 = always GEMV, 2 = always the GEMM
   bool fuse_qkv_relayout = true;  // QkNorm + RoPE + head/transposed relayout in the QKV GEMM's epilogue
@@ -156,14 +154,12 @@ struct fmi_flux {
   int quant_mode = -1;
   bool quant_auto = true;  // quant_mode was (or will be) chosen from the free memory: an arena that then cannot be had demotes it to 0 instead of failing every forward
   std::set<const void*> dense_ready;
-  bf16_t* wscratch[2] = {nullptr, nullptr};  // per-call expansion of quantised matrices at large M (densify)
-  size_t wscratch_elems = 0;
+  DeviceBuffer wscratch[2];  // per-call expansion of quantised matrices at large M (densify): bf16, both of one size
   // single-image sequence parallelism (fmi_flux_set_sequence_parallel; seq_parallel.hip)
   int sp_rank = 0, sp_world = 1;
   fmi_all_to_all_fn sp_a2a = nullptr;
   void* sp_user = nullptr;
-  char* sp_base = nullptr;  // [send | recv | Qf | Kf | Vtf | O (+ SP_SPLITS partial outputs) | lse]
-  size_t sp_bytes = 0;
+  DeviceBuffer sp_base;  // [send | recv | Qf | Kf | Vtf | O (+ SP_SPLITS partial outputs) | lse]
   int sp_Tl = 0, sp_Sl = 0, sp_Nw = 0;  // the (txt, img, world) shard shape the exchange buffers were laid out for
   void *sp_send = nullptr, *sp_recv = nullptr;
   bf16_t *sp_Qf = nullptr, *sp_Kf = nullptr, *sp_Vtf = nullptr, *sp_O = nullptr;
@@ -171,20 +167,18 @@ struct fmi_flux {
   static constexpr int SP_SPLITS = 4;  // key ranges of the latency mode's attention (attention_sp)
   // latency mode for small launches (fmi_flux_set_split_k): see gemm_split_k
   bool split_k = false;
-  float* splitk_scratch = nullptr;
-  size_t splitk_floats = 0;
+  DeviceBuffer splitk_scratch;  // f32 partial products (grow-only)
   // 8-bit modes (fmi_flux_quantize_fp8 / fmi_flux_quantize_int8): fp8 = some block linears hold an 8-bit form (Dense::w8) and the workspace
   // has the code buffers; q8_kind says which (1 OCP e4m3, 2 int8 — GemmProblem::fp8), q8_mask which linears (FMI_Q8_* bits of the header)
   bool fp8 = false;
   int q8_kind = 0;
   unsigned q8_mask = 0;
-  char* fp8_arena = nullptr;
-  size_t fp8_bytes = 0;
+  DeviceBuffer fp8_arena;
   // calibration of the smoothed int8 recipe: while `calib` is set every bf16 evaluation folds the column absmax of each block linear's input into
   // Dense::sm_amax (one arena: amax | s | 1/s per block linear + a scratch row for the weights' column absmax)
   bool calib = false;
   int calib_evals = 0;
-  float* calib_arena = nullptr;
+  DeviceBuffer calib_arena;
   float* calib_wmax = nullptr;
   // fp8 attention operands (QK^T on the fp8 MFMA): static scales per block, 448 / (sqrt(128) * max|norm weight|) — a
   // QkNorm'ed, rotated head vector has norm sqrt(128) * |w|, so no element can exceed the e4m3 range
@@ -196,8 +190,8 @@ struct fmi_flux {
   // copy of its rows in lora_backup, and its effective rows are ALWAYS recomputed from that copy and every active adapter in name order (lora_remerge) —
   // never patched incrementally — so the result does not depend on the order of the calls and removing the adapters restores the loaded bits.
   struct LoraPair {
-    float* A = nullptr;  // (r, in) f32, device
-    float* B = nullptr;  // (out, r) f32, device
+    DeviceBuffer A;  // (r, in) f32
+    DeviceBuffer B;  // (out, r) f32
     int r = 0;
     float scale = 1.f;  // alpha / r
   };
@@ -206,10 +200,9 @@ struct fmi_flux {
     std::map<std::string, LoraPair> pairs;  // by weight name ("<prefix>.weight")
   };
   std::map<std::string, LoraAdapter> loras;       // by adapter name: iteration order == lexicographic order == summation order
-  std::map<std::string, bf16_t*> lora_backup;     // by weight name: private allocations, not part of the flat state (fmi_flux_state_*)
-  char* lora_scratch = nullptr;                   // the concatenated factors of the merge in flight (grow-only; released with the last adapter)
-  size_t lora_scratch_bytes = 0;
-  std::vector<void*> lora_dead;                   // allocations a LoRA call has retired: freed behind its one final synchronisation (lora_leave)
+  std::map<std::string, DeviceBuffer> lora_backup;  // by weight name: private allocations, not part of the flat state (fmi_flux_state_*)
+  DeviceBuffer lora_scratch;                        // the concatenated factors of the merge in flight (grow-only; released with the last adapter)
+  std::vector<DeviceBuffer> lora_dead;              // blocks a LoRA call has retired (MOVED here, not freed): freed behind its one final synchronisation (lora_leave)
 };
 
 static int compute_attention_scales(fmi_flux* m);  // (defined with the 8-bit modes below)
@@ -228,15 +221,15 @@ size_t arena_take(fmi_flux* m, int ar, size_t bytes) {
 int ensure_arena(fmi_flux* m, int ar) {
   Arena& a = m->arena[ar];
   if (a.base || a.bytes == 0) return FMI_OK;
-  hipError_t e = hipMalloc((void**)&a.base, a.bytes);
+  hipError_t e = a.base.alloc(a.bytes);
   if (e != hipSuccess) return fail(FMI_ERR_NOMEM, "flux: hipMalloc of " + std::to_string(a.bytes) + " bytes (weight arena " + std::to_string(ar) + ") failed: " + hipGetErrorString(e));
-  FMI_HIP_TRY(hipMemset(a.base, 0, a.bytes));
+  FMI_HIP_TRY(hipMemset(a.base.ptr, 0, a.bytes));
   FMI_HIP_TRY(hipDeviceSynchronize());  // (an arena can appear in the middle of a forward — the expand-once policy — on a stream the null stream does not order)
   for (Dense* d : m->fused) {
-    if (ar == d->ar) d->w = reinterpret_cast<bf16_t*>(a.base + d->w_off);
-    if (ar == AR_Q4 && !d->q_own) {
-      d->wq = reinterpret_cast<uint8_t*>(a.base + d->q_off);
-      d->absmax = reinterpret_cast<float*>(a.base + d->am_off);
+    if (ar == d->ar) d->w = reinterpret_cast<bf16_t*>(a.base.as<char>() + d->w_off);
+    if (ar == AR_Q4 && !d->own_wq) {
+      d->wq = reinterpret_cast<uint8_t*>(a.base.as<char>() + d->q_off);
+      d->absmax = reinterpret_cast<float*>(a.base.as<char>() + d->am_off);
     }
   }
   return FMI_OK;
@@ -327,7 +320,7 @@ void build_layout(fmi_flux* m) {
 void resolve_base_and_names(fmi_flux* m) {
   const fmi_flux_config& c = m->cfg;
   const int D = m->D, M = m->M;
-  char* base = m->arena[AR_BASE].base;
+  char* base = m->arena[AR_BASE].base.as<char>();
   auto fix = [&](bf16_t*& p) {
     if (p) p = reinterpret_cast<bf16_t*>(base + (reinterpret_cast<uintptr_t>(p) - 1));
   };
@@ -487,21 +480,16 @@ int ensure_workspace(fmi_flux* m, int B, int S, int T) {
     add((void**)&w.a8o, (size_t)B * L * 4);
   }
   const size_t total = align_up(off, 256);
-  if (w.base) {
-    FMI_HIP_TRY(hipDeviceSynchronize());
-    FMI_HIP_TRY(hipFree(w.base));
-    w.base = nullptr;
-  }
-  FMI_HIP_TRY(hipMalloc((void**)&w.base, total));
-  FMI_HIP_TRY(hipMemset(w.base, 0, total));  // also zeroes the Vt pad columns once
-  for (auto& it : items) *it.p = w.base + it.o;
+  if (w.base) FMI_HIP_TRY(hipDeviceSynchronize());
+  FMI_HIP_TRY(w.base.alloc(total));
+  FMI_HIP_TRY(hipMemset(w.base.ptr, 0, total));  // also zeroes the Vt pad columns once
+  for (auto& it : items) *it.p = w.base.as<char>() + it.o;
   if (B == 1) {
     // one sample: the two streams of the double blocks ARE the halves of the joint stream the single blocks read — cat([txt, img], 1) (model.rs:827)
     // is then no copy at all (with B > 1 the streams are (B*T, D) / (B*S, D) row blocks for the grouped GEMMs and the concat interleaves them per sample)
     w.x_txt = w.x;
     w.x_img = w.x + (size_t)T * D;
   }
-  w.bytes = total;
   w.B = B, w.S = S, w.T = T, w.Lpad = Lpad;
   return FMI_OK;
 }
@@ -643,19 +631,16 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
       }
       p[i].W = d->w;
     } else {
-      if (elems > m->wscratch_elems || !m->wscratch[0]) {
+      if (elems * sizeof(bf16_t) > m->wscratch[1].bytes()) {  // ([1] is allocated last: it has the size only when both have it)
         const size_t want = std::max(elems, (size_t)(3 * m->D + m->M) * (size_t)m->D);  // largest fused weight of the model
         FMI_HIP_TRY(hipDeviceSynchronize());
-        for (int k = 0; k < 2; ++k) {
-          if (m->wscratch[k]) FMI_HIP_TRY(hipFree(m->wscratch[k]));
-          FMI_HIP_TRY(hipMalloc((void**)&m->wscratch[k], want * sizeof(bf16_t)));
-        }
-        m->wscratch_elems = want;
+        for (int k = 0; k < 2; ++k) FMI_HIP_TRY(m->wscratch[k].alloc(want * sizeof(bf16_t)));
       }
-      if (p[i].q_type == 3) FMI_TRY(launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(p[i].Wq), p[i].absmax, m->wscratch[i], p[i].K, (int64_t)elems, s));
-      else if (p[i].q_type == 2) dequantize_blockwise_bf16_nf4(nullptr, p[i].Wq, p[i].absmax, m->wscratch[i], p[i].q_blocksize, (int)elems, s);
-      else dequantize_blockwise_bf16_fp4(nullptr, p[i].Wq, p[i].absmax, m->wscratch[i], p[i].q_blocksize, (int)elems, s);
-      p[i].W = m->wscratch[i];
+      bf16_t* ws_i = m->wscratch[i].as<bf16_t>();
+      if (p[i].q_type == 3) FMI_TRY(launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(p[i].Wq), p[i].absmax, ws_i, p[i].K, (int64_t)elems, s));
+      else if (p[i].q_type == 2) dequantize_blockwise_bf16_nf4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
+      else dequantize_blockwise_bf16_fp4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
+      p[i].W = ws_i;
     }
     p[i].ldw = p[i].K;
     p[i].Wq = nullptr, p[i].absmax = nullptr, p[i].q_type = 0, p[i].q_blocksize = 0;
@@ -689,16 +674,13 @@ int gemm_split_k(fmi_flux* m, const GemmProblem* p, int n, hipStream_t s, bool* 
   };
   while (S > 1 && !fits(S)) S >>= 1;
   if (S == 1) return FMI_OK;
-  if (floats * S > m->splitk_floats) {
+  if (floats * S * sizeof(float) > m->splitk_scratch.bytes()) {
     FMI_HIP_TRY(hipStreamSynchronize(s));
-    if (m->splitk_scratch) FMI_HIP_TRY(hipFree(m->splitk_scratch));
-    m->splitk_scratch = nullptr, m->splitk_floats = 0;
-    FMI_HIP_TRY(hipMalloc((void**)&m->splitk_scratch, floats * S * sizeof(float)));
-    m->splitk_floats = floats * S;
+    FMI_HIP_TRY(m->splitk_scratch.alloc(floats * S * sizeof(float)));
   }
   GemmProblem parts[8];
   const float* base[2];
-  float* cur = m->splitk_scratch;
+  float* cur = m->splitk_scratch.as<float>();
   int np = 0;
   for (int i = 0; i < n; ++i) {
     base[i] = cur;
@@ -746,10 +728,8 @@ int ensure_sp_buffers(fmi_flux* m, int Tl, int Sl) {
   const size_t lb = align_up((size_t)fmi_flux::SP_SPLITS * Hr * L * sizeof(float), 256);
   const size_t total = 2 * xb + 2 * qb + vb + (1 + fmi_flux::SP_SPLITS) * qb + lb;
   FMI_HIP_TRY(hipDeviceSynchronize());
-  if (m->sp_base) FMI_HIP_TRY(hipFree(m->sp_base));
-  m->sp_base = nullptr;
-  FMI_HIP_TRY(hipMalloc((void**)&m->sp_base, total));
-  char* c = m->sp_base;
+  FMI_HIP_TRY(m->sp_base.alloc(total));
+  char* c = m->sp_base.as<char>();
   m->sp_send = c, c += xb;
   m->sp_recv = c, c += xb;
   m->sp_Qf = reinterpret_cast<bf16_t*>(c), c += qb;
@@ -757,7 +737,7 @@ int ensure_sp_buffers(fmi_flux* m, int Tl, int Sl) {
   m->sp_Vtf = reinterpret_cast<bf16_t*>(c), c += vb;
   m->sp_O = reinterpret_cast<bf16_t*>(c), c += (1 + fmi_flux::SP_SPLITS) * qb;
   m->sp_lse = reinterpret_cast<float*>(c);
-  m->sp_bytes = total, m->sp_Tl = Tl, m->sp_Sl = Sl, m->sp_Nw = m->sp_world;
+  m->sp_Tl = Tl, m->sp_Sl = Sl, m->sp_Nw = m->sp_world;
   return FMI_OK;
 }
 int attention_sp(fmi_flux* m, const AttnOut& out, int Tl, int Sl, float scale, hipStream_t s) {
@@ -839,8 +819,7 @@ struct PhaseTimer {
 };
 
 int check_ready(fmi_flux* m) {
-  if (!m->missing.empty())
-    return fail(FMI_ERR_STATE, "flux: " + std::to_string(m->missing.size()) + " tensors not set, first: " + *m->missing.begin());
+  FMI_TRY(m->missing.ready("flux"));
   return finalize(m);
 }
 // the handle's device becomes the calling thread's current device (hipSetDevice is per thread)
@@ -1251,35 +1230,12 @@ extern "C" void fmi_flux_destroy(fmi_flux* m) {
   if (!m) return;
   use_device(m);
   hipDeviceSynchronize();
-  if (m->ws.base) hipFree(m->ws.base);
-  for (int a = 0; a < AR_COUNT; ++a)
-    if (m->arena[a].base) hipFree(m->arena[a].base);
-  for (int k = 0; k < 2; ++k)
-    if (m->wscratch[k]) hipFree(m->wscratch[k]);
-  if (m->sp_base) hipFree(m->sp_base);
-  if (m->splitk_scratch) hipFree(m->splitk_scratch);
-  if (m->mod_steps) hipFree(m->mod_steps);
-  if (m->vec_steps) hipFree(m->vec_steps);
-  if (m->vec_steps_bf) hipFree(m->vec_steps_bf);
-  if (m->temb_steps) hipFree(m->temb_steps);
-  if (m->h1_steps) hipFree(m->h1_steps);
-  if (m->fp8_arena) hipFree(m->fp8_arena);
-  if (m->calib_arena) hipFree(m->calib_arena);
-  for (auto& ad : m->loras)
-    for (auto& pr : ad.second.pairs) hipFree(pr.second.A), hipFree(pr.second.B);
-  for (auto& bk : m->lora_backup) hipFree(bk.second);
-  if (m->lora_scratch) hipFree(m->lora_scratch);
-  for (Dense* d : m->fused)
-    if (d->q_own) {
-      if (d->wq) hipFree(d->wq);
-      if (d->absmax) hipFree(d->absmax);
-    }
   if (m->ev0) hipEventDestroy(m->ev0);
   if (m->ev1) hipEventDestroy(m->ev1);
   if (m->ev_fork) hipEventDestroy(m->ev_fork);
   if (m->ev_join) hipEventDestroy(m->ev_join);
   if (m->side) hipStreamDestroy(m->side);
-  delete m;
+  delete m;  // (every device block is a DeviceBuffer member)
 }
 
 extern "C" int fmi_flux_set_tensor(fmi_flux* m, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
@@ -1310,18 +1266,7 @@ extern "C" int fmi_flux_set_tensor(fmi_flux* m, const char* name, const void* da
     FMI_TRY(ensure_arena(m, d.d->ar));
     dst = d.d->w + (size_t)d.d->parts[d.part].r0 * d.d->K;
   }
-  const size_t esz = dtype == FMI_F32 ? 4 : 2;
-  if (dtype == FMI_BF16) {
-    FMI_HIP_TRY(hipMemcpy(dst, data, numel * 2, hipMemcpyDefault));
-  } else {
-    void* tmp = nullptr;
-    FMI_HIP_TRY(hipMalloc(&tmp, numel * esz));
-    hipError_t e = hipMemcpy(tmp, data, numel * esz, hipMemcpyDefault);
-    int rc = e == hipSuccess ? launch_cast_to_bf16(tmp, dtype, (bf16_t*)dst, numel, nullptr) : fail(FMI_ERR_HIP, hipGetErrorString(e));
-    hipDeviceSynchronize();
-    hipFree(tmp);
-    if (rc) return rc;
-  }
+  FMI_TRY(upload_as_bf16(data, dtype, numel, (bf16_t*)dst));
   if (d.d && !d.bias) {
     d.d->parts[d.part].state = PS_DENSE, d.d->parts[d.part].blocksize = 0;
     m->dense_ready.erase(d.d);
@@ -1334,17 +1279,9 @@ extern "C" int fmi_flux_set_tensor(fmi_flux* m, const char* name, const void* da
 namespace {
 // a quantised Linear that is not a fused GEMM matrix (embedders, final projection): expanded once into the BASE arena
 template <typename F>
-int expand_small(fmi_flux* m, const Dest& dst, const void* q, size_t qbytes, const float* sc, size_t scbytes, F&& run) {
-  void *dq = nullptr, *ds = nullptr;
-  FMI_HIP_TRY(hipMalloc(&dq, qbytes));
-  FMI_HIP_TRY(hipMalloc(&ds, scbytes));
-  hipError_t e = hipMemcpy(dq, q, qbytes, hipMemcpyDefault);
-  if (e == hipSuccess) e = hipMemcpy(ds, sc, scbytes, hipMemcpyDefault);
-  int rc = e == hipSuccess ? run(dq, (const float*)ds, dst.d->w + (size_t)dst.d->parts[dst.part].r0 * dst.d->K) : fail(FMI_ERR_HIP, hipGetErrorString(e));
-  hipDeviceSynchronize();
-  hipFree(dq);
-  hipFree(ds);
-  return rc;
+int expand_small(const Dest& dst, const void* q, size_t qbytes, const float* sc, size_t scbytes, F&& run) {
+  bf16_t* out = dst.d->w + (size_t)dst.d->parts[dst.part].r0 * dst.d->K;
+  return with_staged_pair(q, qbytes, sc, scbytes, [&](void* dq, void* ds) { return run(dq, (const float*)ds, out); });
 }
 }  // namespace
 
@@ -1369,7 +1306,7 @@ extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const u
   const size_t n = (size_t)out_features * in_features;
   if (d->ar == AR_BASE) {
     if (n >= (1ull << 31)) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: linear too large");
-    FMI_TRY(expand_small(m, dst, packed, n / 2, absmax, n / blocksize * 4, [&](void* dq, const float* da, bf16_t* out) {
+    FMI_TRY(expand_small(dst, packed, n / 2, absmax, n / blocksize * 4, [&](void* dq, const float* da, bf16_t* out) {
       if (quant_type == 2) dequantize_blockwise_bf16_nf4(nullptr, (const uint8_t*)dq, da, out, blocksize, (int)n, nullptr);
       else dequantize_blockwise_bf16_fp4(nullptr, (const uint8_t*)dq, da, out, blocksize, (int)n, nullptr);
       return (int)FMI_OK;
@@ -1377,7 +1314,7 @@ extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const u
     m->missing.erase(wname);
     return FMI_OK;
   }
-  if (d->q_own) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: this fused projection already holds int8 parts");
+  if (d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: this fused projection already holds int8 parts");
   FMI_TRY(ensure_arena(m, AR_Q4));
   Dense::Part& pt = d->parts[dst.part];
   FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K / 2, packed, n / 2, hipMemcpyDefault));
@@ -1406,7 +1343,7 @@ extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const i
   if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_int8: shape mismatch for " + wname);
   const int64_t n = (int64_t)out_features * in_features;
   if (d->ar == AR_BASE) {
-    FMI_TRY(expand_small(m, dst, weight, (size_t)n, scb, (size_t)out_features * 4, [&](void* dq, const float* ds, bf16_t* out) {
+    FMI_TRY(expand_small(dst, weight, (size_t)n, scb, (size_t)out_features * 4, [&](void* dq, const float* ds, bf16_t* out) {
       return launch_dequant_int8_scb_bf16((const int8_t*)dq, ds, out, in_features, n, nullptr);
     }));
     m->missing.erase(wname);
@@ -1414,14 +1351,14 @@ extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const i
   }
   for (auto& pt : d->parts)
     if (pt.state == PS_FP4 || pt.state == PS_NF4) return fail(FMI_ERR_UNSUPPORTED, "set_linear_int8: this fused projection already holds 4-bit parts");
-  if (!d->q_own) {  // int8 matrices own their storage (1 B per weight: they do not fit the 4-bit arena's slots)
-    uint8_t* wq = nullptr;
-    float* sc = nullptr;
-    FMI_HIP_TRY(hipMalloc((void**)&wq, (size_t)d->N * d->K));
-    FMI_HIP_TRY(hipMalloc((void**)&sc, (size_t)d->N * 4));
-    FMI_HIP_TRY(hipMemset(wq, 0, (size_t)d->N * d->K));
-    FMI_HIP_TRY(hipMemset(sc, 0, (size_t)d->N * 4));
-    d->wq = wq, d->absmax = sc, d->q_own = true;
+  if (!d->own_wq) {  // the matrix changes only once both blocks exist and are zeroed
+    DeviceBuffer wq, sc;
+    FMI_HIP_TRY(wq.alloc((size_t)d->N * d->K));
+    FMI_HIP_TRY(sc.alloc((size_t)d->N * 4));
+    FMI_HIP_TRY(hipMemset(wq.ptr, 0, wq.bytes()));
+    FMI_HIP_TRY(hipMemset(sc.ptr, 0, sc.bytes()));
+    d->own_wq = std::move(wq), d->own_absmax = std::move(sc);
+    d->wq = d->own_wq.as<uint8_t>(), d->absmax = d->own_absmax.as<float>();
   }
   Dense::Part& pt = d->parts[dst.part];
   FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K, weight, n, hipMemcpyDefault));
@@ -1433,27 +1370,22 @@ extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const i
   return FMI_OK;
 }
 
-extern "C" int fmi_flux_missing_count(const fmi_flux* m) { return m ? (int)m->missing.size() : 0; }
-extern "C" const char* fmi_flux_missing_name(const fmi_flux* m, int i) {
-  if (!m || i < 0 || i >= (int)m->missing.size()) return nullptr;
-  auto* mm = const_cast<fmi_flux*>(m);
-  mm->missing_list.assign(m->missing.begin(), m->missing.end());
-  return mm->missing_list[i].c_str();
-}
+extern "C" int fmi_flux_missing_count(const fmi_flux* m) { return m ? m->missing.count() : 0; }
+extern "C" const char* fmi_flux_missing_name(const fmi_flux* m, int i) { return m ? m->missing.name(i) : nullptr; }
 extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
   if (!m) return 0;
-  size_t b = m->ws.bytes + m->fp8_bytes + 2 * m->wscratch_elems * 2 + m->mod_steps_rows * ((size_t)m->n_mod * 4 + (size_t)m->D * 6);
+  size_t b = m->ws.base.bytes() + m->fp8_arena.bytes() + m->wscratch[0].bytes() + m->wscratch[1].bytes() + m->mod_steps_rows * ((size_t)m->n_mod * 4 + (size_t)m->D * 6);
   for (int a = 0; a < AR_COUNT; ++a)
     if (m->arena[a].base) b += m->arena[a].bytes;
   for (const Dense* d : m->fused)
-    if (d->q_own) b += (size_t)d->N * d->K + (size_t)d->N * 4;
+    if (d->own_wq) b += (size_t)d->N * d->K + (size_t)d->N * 4;
   for (const auto& ad : m->loras)
     for (const auto& pr : ad.second.pairs) {
       const Dest& dst = m->names.at(pr.first);
       if (pr.second.A) b += (size_t)pr.second.r * (dst.rows + dst.cols) * 4;
     }
   for (const auto& bk : m->lora_backup) b += (size_t)m->names.at(bk.first).numel * 2;
-  return b + m->lora_scratch_bytes;
+  return b + m->lora_scratch.bytes();
 }
 
 // ---- weight state as a handful of flat device buffers: the unit of the multi-GPU weight broadcast.
@@ -1478,7 +1410,7 @@ extern "C" int fmi_flux_state_export(fmi_flux* m, uint8_t* blob_host, size_t cap
   o += 8;
   for (int a = 0; a < AR_COUNT; ++a) *o++ = m->arena[a].base ? 1 : 0;
   for (const Dense* d : m->fused) {
-    if (d->q_own) return fail(FMI_ERR_UNSUPPORTED, "state_export: LLM.int8 matrices are not part of the flat weight state");
+    if (d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_export: LLM.int8 matrices are not part of the flat weight state");
     *o++ = (uint8_t)d->q_type;
     const uint32_t bs = (uint32_t)d->q_blocksize;
     memcpy(o, &bs, 4);
@@ -1502,12 +1434,12 @@ extern "C" int fmi_flux_state_adopt(fmi_flux* m, const uint8_t* blob_host, size_
     uint32_t bs = 0;
     memcpy(&bs, o, 4);
     o += 4;
-    if (qt == 3 || d->q_own) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
+    if (qt == 3 || d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
     d->q_type = qt, d->q_blocksize = (int)bs;
     for (auto& pt : d->parts) pt.state = qt ? (uint8_t)qt : (uint8_t)PS_DENSE, pt.blocksize = (int)bs;
     if (qt ? !m->arena[AR_Q4].base : !m->arena[d->ar].base) return fail(FMI_ERR_INVALID, "state_adopt: blob is inconsistent (matrix stored in an arena that is not present)");
   }
-  m->missing.clear();
+  m->missing.names.clear();
   m->dense_ready.clear();
   m->attn_scales_valid = false;  // the weights arrive after this call (broadcast into the arenas)
   m->finalized = true;
@@ -1515,7 +1447,7 @@ extern "C" int fmi_flux_state_adopt(fmi_flux* m, const uint8_t* blob_host, size_
 }
 extern "C" int fmi_flux_state_buffer(fmi_flux* m, int index, void** ptr, size_t* bytes) {
   if (!m || !ptr || !bytes || index < 0 || index >= AR_COUNT) return fail(FMI_ERR_INVALID, "state_buffer: bad argument");
-  *ptr = m->arena[index].base;
+  *ptr = m->arena[index].base.ptr;
   *bytes = m->arena[index].base ? m->arena[index].bytes : 0;
   return FMI_OK;
 }
@@ -1565,22 +1497,17 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_c
   if (n_steps > 1 && R * nmod * 4 <= (2ull << 30)) {
     if (m->mod_steps_rows < R) {
       FMI_HIP_TRY(hipStreamSynchronize(s));
-      if (m->mod_steps) FMI_HIP_TRY(hipFree(m->mod_steps));
-      if (m->vec_steps) FMI_HIP_TRY(hipFree(m->vec_steps));
-      if (m->vec_steps_bf) FMI_HIP_TRY(hipFree(m->vec_steps_bf));
-      if (m->temb_steps) FMI_HIP_TRY(hipFree(m->temb_steps));
-      if (m->h1_steps) FMI_HIP_TRY(hipFree(m->h1_steps));
-      m->mod_steps = m->vec_steps = nullptr, m->vec_steps_bf = nullptr, m->temb_steps = m->h1_steps = nullptr, m->mod_steps_rows = 0;
-      FMI_HIP_TRY(hipMalloc((void**)&m->mod_steps, R * nmod * 4));
-      FMI_HIP_TRY(hipMalloc((void**)&m->vec_steps, R * (size_t)m->D * 4));
-      FMI_HIP_TRY(hipMalloc((void**)&m->vec_steps_bf, R * (size_t)m->D * 2));
-      FMI_HIP_TRY(hipMalloc((void**)&m->temb_steps, R * (size_t)256 * 4));
-      FMI_HIP_TRY(hipMalloc((void**)&m->h1_steps, std::max<size_t>(R, 2 * (size_t)B) * (size_t)m->D * 4));
+      m->mod_steps.reset(), m->vec_steps.reset(), m->vec_steps_bf.reset(), m->temb_steps.reset(), m->h1_steps.reset(), m->mod_steps_rows = 0;
+      FMI_HIP_TRY(m->mod_steps.alloc(R * nmod * 4));
+      FMI_HIP_TRY(m->vec_steps.alloc(R * (size_t)m->D * 4));
+      FMI_HIP_TRY(m->vec_steps_bf.alloc(R * (size_t)m->D * 2));
+      FMI_HIP_TRY(m->temb_steps.alloc(R * (size_t)256 * 4));
+      FMI_HIP_TRY(m->h1_steps.alloc(std::max<size_t>(R, 2 * (size_t)B) * (size_t)m->D * 4));
       m->mod_steps_rows = R;
     }
     {
       PhaseTimer pt(m, s, PH_EMBED);
-      FMI_TRY(compute_vec_steps(m, in, m->ws.tv, n_steps, m->vec_steps, m->temb_steps, m->h1_steps, s));
+      FMI_TRY(compute_vec_steps(m, in, m->ws.tv, n_steps, m->vec_steps.as<float>(), m->temb_steps.as<float>(), m->h1_steps.as<float>(), s));
     }
     {
       PhaseTimer pt(m, s, PH_MOD);
@@ -1588,16 +1515,16 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_c
       if (m->mod_all.q_type || (m->mod_gemm && (R > GEMV_MAXROWS || m->mod_gemm == 2) && m->D % 64 == 0 && nmod % 8 == 0 && R * nmod < (1ull << 31))) {
         // all rows in ONE pass over the matrix on the MFMA GEMM (silu(vec) rounded to bf16 like every other
         // GEMM input): the matrix is read once per image instead of once per 4 steps
-        FMI_TRY(launch_silu_to_bf16(m->vec_steps, m->vec_steps_bf, (int64_t)R * m->D, s));
-        GemmProblem p = make_problem(m->mod_all, m->vec_steps_bf, m->D, (int)R, m->mod_steps, (int)nmod, EPI_STORE_F32);
+        FMI_TRY(launch_silu_to_bf16(m->vec_steps.as<float>(), m->vec_steps_bf.as<bf16_t>(), (int64_t)R * m->D, s));
+        GemmProblem p = make_problem(m->mod_all, m->vec_steps_bf.as<bf16_t>(), m->D, (int)R, m->mod_steps.as<float>(), (int)nmod, EPI_STORE_F32);
         FMI_TRY(gemm1(m, p, m->mod_all, s));
       } else {
         for (size_t r0 = 0; r0 < R; r0 += GEMV_MAXROWS)
-          FMI_TRY(launch_gemv(m->vec_steps + r0 * m->D, m->mod_all.w, m->mod_all.b, m->mod_steps + r0 * nmod, (int)std::min<size_t>(GEMV_MAXROWS, R - r0),
+          FMI_TRY(launch_gemv(m->vec_steps.as<float>() + r0 * m->D, m->mod_all.w, m->mod_all.b, m->mod_steps.as<float>() + r0 * nmod, (int)std::min<size_t>(GEMV_MAXROWS, R - r0),
                               (int)nmod, m->D, 1, 0, s));
       }
     }
-    mod_steps = m->mod_steps;
+    mod_steps = m->mod_steps.as<float>();
   }
   const float* txt_pre = nullptr;
   if (n_steps > 1) {  // txt = txt_in(txt) (model.rs:812) depends on the prompt only: once per image
@@ -1786,14 +1713,14 @@ static int quantize_8bit(fmi_flux* m, int kind, unsigned mask, void* stream) {
   const bool smooth = kind == 2 && m->calib && m->calib_evals > 0;
   if (kind == 2 && m->calib && !smooth) return fail(FMI_ERR_STATE, "quantize_int8: calibration is on but no evaluation has run (fmi_flux_forward / fmi_flux_denoise first, or fmi_flux_calibrate_int8(m, 0))");
   m->calib = false;
-  FMI_HIP_TRY(hipMalloc((void**)&m->fp8_arena, bytes));
-  m->fp8_bytes = bytes;
+  FMI_HIP_TRY(m->fp8_arena.alloc(bytes));  // (a retry after a failed launch below starts from a fresh block: the earlier one is released here)
+  char* const arena8 = m->fp8_arena.as<char>();
   hipStream_t s = (hipStream_t)stream;
   size_t off = 0;
   for (Dense* d : lin) {
-    d->w8 = reinterpret_cast<uint8_t*>(m->fp8_arena + off);
+    d->w8 = reinterpret_cast<uint8_t*>(arena8 + off);
     off += align_up((size_t)d->N * d->K, 256);
-    d->w8_scale = reinterpret_cast<float*>(m->fp8_arena + off);
+    d->w8_scale = reinterpret_cast<float*>(arena8 + off);
     off += align_up((size_t)d->N * 4, 256);
     const float* wvec = nullptr;
     if (smooth && d->sm_amax) {
@@ -1818,18 +1745,14 @@ static int quantize_8bit(fmi_flux* m, int kind, unsigned mask, void* stream) {
     }
     FMI_TRY(launch_quantize_rows_fp8(d->w, d->K, d->N, d->K, d->w8, d->w8_scale, s, kind, wvec));
     if (d->w8_d0 >= 0) {
-      d->w8_sum = reinterpret_cast<float*>(m->fp8_arena + off);
+      d->w8_sum = reinterpret_cast<float*>(arena8 + off);
       off += align_up((size_t)d->N * 4, 256);
       FMI_TRY(launch_rowsum_i8(reinterpret_cast<const int8_t*>(d->w8), d->w8_scale, d->N, d->K, d->w8_d0, d->w8_sum, s));
     }
   }
   FMI_HIP_TRY(hipStreamSynchronize(s));
   FMI_TRY(compute_attention_scales(m));
-  if (m->ws.base) {  // the fp8 workspace has two more buffers: rebuild on the next call
-    FMI_HIP_TRY(hipFree(m->ws.base));
-    m->ws.base = nullptr;
-    m->ws.bytes = 0;
-  }
+  m->ws.base.reset();  // the fp8 workspace has two more buffers: rebuild on the next call
   m->fp8 = true;
   m->q8_kind = kind;
   m->q8_mask = mask;
@@ -1856,8 +1779,8 @@ extern "C" int fmi_flux_calibrate_int8(fmi_flux* m, int enable) {
   for (auto& b : m->sgl) lin.push_back(&b.w1), lin.push_back(&b.w2);
   if (!enable) {
     FMI_HIP_TRY(hipDeviceSynchronize());
-    if (m->calib_arena) FMI_HIP_TRY(hipFree(m->calib_arena));
-    m->calib_arena = nullptr, m->calib_wmax = nullptr, m->calib = false, m->calib_evals = 0;
+    m->calib_arena.reset();
+    m->calib_wmax = nullptr, m->calib = false, m->calib_evals = 0;
     for (Dense* d : lin) d->sm_amax = d->sm_s = d->sm_inv = d->sm_inv_store = nullptr;
     return FMI_OK;
   }
@@ -1870,9 +1793,9 @@ extern "C" int fmi_flux_calibrate_int8(fmi_flux* m, int enable) {
     floats += 3 * (size_t)d->K;
     kmax = std::max(kmax, d->K);
   }
-  if (!m->calib_arena) FMI_HIP_TRY(hipMalloc((void**)&m->calib_arena, (floats + (size_t)kmax) * sizeof(float)));
-  FMI_HIP_TRY(hipMemset(m->calib_arena, 0, (floats + (size_t)kmax) * sizeof(float)));
-  float* p = m->calib_arena;
+  if (!m->calib_arena) FMI_HIP_TRY(m->calib_arena.alloc((floats + (size_t)kmax) * sizeof(float)));
+  FMI_HIP_TRY(hipMemset(m->calib_arena.ptr, 0, (floats + (size_t)kmax) * sizeof(float)));
+  float* p = m->calib_arena.as<float>();
   for (Dense* d : lin) {
     d->sm_amax = p, d->sm_s = p + d->K, d->sm_inv_store = p + 2 * (size_t)d->K, d->sm_inv = nullptr;
     p += 3 * (size_t)d->K;
@@ -1892,7 +1815,7 @@ extern "C" int fmi_flux_set_fp8_attention(fmi_flux* m, int enable) {
   m->fp8_attn = enable;
   // 2 in bf16 mode: the static scales come from the QkNorm weights — taken here when the weights are complete (not inside the next evaluation: they
   // are small synchronous copies), else at the first evaluation after the last tensor arrived
-  if (enable == 2 && !m->attn_scales_valid && m->missing.empty()) {
+  if (enable == 2 && !m->attn_scales_valid && m->missing.names.empty()) {
     FMI_TRY(use_device(m));
     FMI_TRY(compute_attention_scales(m));
   }
@@ -1915,12 +1838,6 @@ extern "C" int fmi_flux_set_attention_rescale_threshold(fmi_flux* m, int thr_x16
 // ---------------------------------------------------------------------------------------- LoRA adapters (merged; the kernel is lora.hip)
 namespace {
 
-void lora_free_pair(fmi_flux::LoraPair& p) {
-  if (p.A) hipFree(p.A);
-  if (p.B) hipFree(p.B);
-  p.A = p.B = nullptr;
-}
-
 // Everything a later re-merge of the Linear `wname` can need, taken BEFORE any adapter state changes (so that a failed allocation leaves the model as it
 // was): the factor scratch for the total rank of every pair on it plus `extra_r`, and the pristine copy of its rows (while there is none, the rows ARE
 // the loaded weights).  A copy made for a Linear that then has no active adapter is released again by lora_remerge.
@@ -1936,24 +1853,21 @@ int lora_reserve(fmi_flux* m, const std::string& wname, int extra_r) {
   const int Rpad = (R + LORA_RANK_CHUNK - 1) / LORA_RANK_CHUNK * LORA_RANK_CHUNK;
   const int rows_pad = (rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * LORA_TILE_ROWS;
   const size_t need = align_up((size_t)Rpad * K * 4, 256) + (size_t)Rpad * rows_pad * 8;
-  if (m->lora_scratch_bytes < need) {  // grow-only
-    char* grown = nullptr;
-    hipError_t e = hipMalloc((void**)&grown, need);
+  if (m->lora_scratch.bytes() < need) {  // grow-only
+    DeviceBuffer grown;
+    hipError_t e = grown.alloc(need);
     if (e != hipSuccess) return fail(FMI_ERR_NOMEM, std::string("lora: hipMalloc of the factor scratch failed: ") + hipGetErrorString(e));
-    if (m->lora_scratch) m->lora_dead.push_back(m->lora_scratch);  // (an earlier merge of this call may still read it: freed after the call's synchronisation)
-    m->lora_scratch = grown, m->lora_scratch_bytes = need;
+    if (m->lora_scratch) m->lora_dead.push_back(std::move(m->lora_scratch));  // (an earlier merge of this call may still read it: freed after the call's synchronisation)
+    m->lora_scratch = std::move(grown);
   }
   if (!m->lora_backup.count(wname)) {
     const size_t bytes = (size_t)rows * K * 2;
-    bf16_t* fresh = nullptr;
-    hipError_t e = hipMalloc((void**)&fresh, bytes);
+    DeviceBuffer fresh;
+    hipError_t e = fresh.alloc(bytes);
     if (e != hipSuccess) return fail(FMI_ERR_NOMEM, std::string("lora: hipMalloc of the pristine copy failed: ") + hipGetErrorString(e));
-    e = hipMemcpyAsync(fresh, dst.d->w + (size_t)dst.d->parts[dst.part].r0 * K, bytes, hipMemcpyDeviceToDevice, nullptr);
-    if (e != hipSuccess) {
-      hipFree(fresh);
-      return fail(FMI_ERR_HIP, std::string("lora: ") + hipGetErrorString(e));
-    }
-    m->lora_backup.emplace(wname, fresh);
+    e = hipMemcpyAsync(fresh.ptr, dst.d->w + (size_t)dst.d->parts[dst.part].r0 * K, bytes, hipMemcpyDeviceToDevice, nullptr);
+    if (e != hipSuccess) return fail(FMI_ERR_HIP, std::string("lora: ") + hipGetErrorString(e));
+    m->lora_backup.emplace(wname, std::move(fresh));
   }
   return FMI_OK;
 }
@@ -1984,8 +1898,8 @@ int lora_remerge(fmi_flux* m, const std::string& wname) {
   auto bk = m->lora_backup.find(wname);
   if (terms.empty()) {
     if (bk != m->lora_backup.end()) {
-      FMI_HIP_TRY(hipMemcpyAsync(w, bk->second, bytes, hipMemcpyDeviceToDevice, nullptr));
-      m->lora_dead.push_back(bk->second);  // freed after the call's one synchronisation
+      FMI_HIP_TRY(hipMemcpyAsync(w, bk->second.ptr, bytes, hipMemcpyDeviceToDevice, nullptr));
+      m->lora_dead.push_back(std::move(bk->second));  // freed after the call's one synchronisation
       m->lora_backup.erase(bk);
     }
     return FMI_OK;
@@ -1993,65 +1907,43 @@ int lora_remerge(fmi_flux* m, const std::string& wname) {
   const int Rpad = (R + LORA_RANK_CHUNK - 1) / LORA_RANK_CHUNK * LORA_RANK_CHUNK;
   const int rows_pad = (rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * LORA_TILE_ROWS;
   const size_t a_bytes = align_up((size_t)Rpad * K * 4, 256), b_bytes = (size_t)Rpad * rows_pad * 8;
-  if (bk == m->lora_backup.end() || m->lora_scratch_bytes < a_bytes + b_bytes) return fail(FMI_ERR_STATE, "lora: re-merge without its reserved storage");
-  float* Acat = reinterpret_cast<float*>(m->lora_scratch);
-  double* Bt = reinterpret_cast<double*>(m->lora_scratch + a_bytes);
+  if (bk == m->lora_backup.end() || m->lora_scratch.bytes() < a_bytes + b_bytes) return fail(FMI_ERR_STATE, "lora: re-merge without its reserved storage");
+  float* Acat = m->lora_scratch.as<float>();
+  double* Bt = reinterpret_cast<double*>(m->lora_scratch.as<char>() + a_bytes);
   if (Rpad > R) {  // the rank rows that pad the last chunk (the pack launches write every other byte the kernel reads)
     FMI_HIP_TRY(hipMemsetAsync(Acat + (size_t)R * K, 0, (size_t)(Rpad - R) * K * 4, nullptr));
     FMI_HIP_TRY(hipMemsetAsync(Bt + (size_t)R * rows_pad, 0, (size_t)(Rpad - R) * rows_pad * 8, nullptr));
   }
   int off = 0;
   for (const Term& t : terms) {
-    FMI_TRY(launch_lora_pack(t.p->A, t.p->B, rows, K, t.p->r, t.coef, Acat, Bt, rows_pad, off, nullptr));
+    FMI_TRY(launch_lora_pack(t.p->A.as<float>(), t.p->B.as<float>(), rows, K, t.p->r, t.coef, Acat, Bt, rows_pad, off, nullptr));
     off += t.p->r;
   }
-  return launch_lora_merge(bk->second, w, rows, K, Acat, Bt, rows_pad, Rpad, nullptr);
+  return launch_lora_merge(bk->second.as<bf16_t>(), w, rows, K, Acat, Bt, rows_pad, Rpad, nullptr);
 }
 
 // the end of every mutating LoRA call: nothing is in flight when it returns; what the call retired is freed behind that one synchronisation
 int lora_leave(fmi_flux* m, int rc) {
   hipError_t e = hipDeviceSynchronize();
   if (rc == FMI_OK && e != hipSuccess) rc = fail(FMI_ERR_HIP, std::string("lora: ") + hipGetErrorString(e));
-  for (void* p : m->lora_dead) hipFree(p);
   m->lora_dead.clear();
-  if (m->loras.empty() && m->lora_scratch) {
-    hipFree(m->lora_scratch);
-    m->lora_scratch = nullptr, m->lora_scratch_bytes = 0;
-  }
+  if (m->loras.empty()) m->lora_scratch.reset();
   return rc;
 }
 
 // what every mutating LoRA call checks first: a complete bf16-mode model; then the device is drained (load-time calls: this orders them against evaluations on any stream)
 int lora_enter(fmi_flux* m, const char* what) {
   if (m->fp8) return fail(FMI_ERR_STATE, std::string(what) + ": the model was quantised to 8 bits; adapters go in before fmi_flux_quantize_fp8 / fmi_flux_quantize_int8");
-  if (!m->missing.empty()) return fail(FMI_ERR_STATE, std::string(what) + ": " + std::to_string(m->missing.size()) + " tensors not set, first: " + *m->missing.begin());
+  FMI_TRY(m->missing.ready(what));
   FMI_TRY(use_device(m));
   FMI_HIP_TRY(hipDeviceSynchronize());
   return finalize(m);
 }
 
 // device f32 copy of a host / device array of F32 / F16 / BF16 (exact conversions)
-int lora_upload_f32(const void* src, fmi_dtype dtype, int64_t n, float** out) {
-  float* dstp = nullptr;
-  FMI_HIP_TRY(hipMalloc((void**)&dstp, n * 4));
-  int rc = FMI_OK;
-  if (dtype == FMI_F32) {
-    hipError_t e = hipMemcpy(dstp, src, n * 4, hipMemcpyDefault);
-    if (e != hipSuccess) rc = fail(FMI_ERR_HIP, hipGetErrorString(e));
-  } else {
-    void* tmp = nullptr;
-    hipError_t e = hipMalloc(&tmp, n * 2);
-    if (e == hipSuccess) e = hipMemcpy(tmp, src, n * 2, hipMemcpyDefault);
-    rc = e == hipSuccess ? launch_cast_to_f32(tmp, dtype, dstp, n, nullptr) : fail(FMI_ERR_HIP, hipGetErrorString(e));
-    hipDeviceSynchronize();
-    if (tmp) hipFree(tmp);
-  }
-  if (rc != FMI_OK) {
-    hipFree(dstp);
-    return rc;
-  }
-  *out = dstp;
-  return FMI_OK;
+int lora_upload_f32(const void* src, fmi_dtype dtype, int64_t n, DeviceBuffer& out) {
+  FMI_HIP_TRY(out.alloc(n * 4));
+  return upload_as_f32(src, dtype, n, out.as<float>());
 }
 
 }  // namespace
@@ -2075,19 +1967,12 @@ extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* p
   if (dst.cols % 8) return fail(FMI_ERR_UNSUPPORTED, "lora_add: in_features must be a multiple of 8");
   fmi_flux::LoraPair np;
   np.r = rank, np.scale = scale;
-  FMI_TRY(lora_upload_f32(A, dtype, (int64_t)rank * dst.cols, &np.A));
-  if (int rc = lora_upload_f32(B, dtype, (int64_t)dst.rows * rank, &np.B)) {
-    lora_free_pair(np);
-    return rc;
-  }
+  FMI_TRY(lora_upload_f32(A, dtype, (int64_t)rank * dst.cols, np.A));
+  FMI_TRY(lora_upload_f32(B, dtype, (int64_t)dst.rows * rank, np.B));
   // storage first, state second: until here nothing of the model has changed, and a re-merge allocates nothing
-  if (int rc = lora_reserve(m, wname, rank)) {
-    lora_free_pair(np);
-    return lora_leave(m, rc);
-  }
-  fmi_flux::LoraPair& slot = m->loras[adapter].pairs[wname];  // (a new adapter starts at weight 1)
-  lora_free_pair(slot);  // re-adding a pair replaces it (the device is idle: lora_enter)
-  slot = np;
+  if (int rc = lora_reserve(m, wname, rank)) return lora_leave(m, rc);
+  // re-adding a pair replaces it: the move-assignment frees the slot's earlier factors HERE (the device is idle: lora_enter), after lora_reserve
+  m->loras[adapter].pairs[wname] = std::move(np);  // (a new adapter starts at weight 1)
   return lora_leave(m, lora_remerge(m, wname));
 }
 
@@ -2125,8 +2010,7 @@ extern "C" int fmi_flux_lora_remove(fmi_flux* m, const char* adapter) {
       ++ad;
       continue;
     }
-    for (auto& pr : ad->second.pairs) lora_free_pair(pr.second);
-    ad = m->loras.erase(ad);
+    ad = m->loras.erase(ad);  // (frees its factors: the device is idle, lora_enter)
   }
   for (const std::string& wname : touched)
     if ((rc = lora_remerge(m, wname)) != FMI_OK) break;
@@ -2137,11 +2021,9 @@ extern "C" int fmi_flux_lora_remove(fmi_flux* m, const char* adapter) {
 static void lora_release_storage(fmi_flux* m) {
   hipDeviceSynchronize();
   for (auto& ad : m->loras)
-    for (auto& pr : ad.second.pairs) lora_free_pair(pr.second);
-  for (auto& bk : m->lora_backup) hipFree(bk.second);
+    for (auto& pr : ad.second.pairs) pr.second.A.reset(), pr.second.B.reset();
   m->lora_backup.clear();
-  if (m->lora_scratch) hipFree(m->lora_scratch);
-  m->lora_scratch = nullptr, m->lora_scratch_bytes = 0;
+  m->lora_scratch.reset();
 }
 
 extern "C" int fmi_flux_lora_count(const fmi_flux* m) { return m ? (int)m->loras.size() : 0; }
@@ -2160,10 +2042,10 @@ extern "C" int fmi_flux_get_tensor(fmi_flux* m, const char* name, void* out, fmi
   const bool ok = d.cols ? (rank == 2 && shape[0] == d.rows && shape[1] == d.cols) : (rank == 1 && shape[0] == d.rows);
   if (!ok) return fail(FMI_ERR_INVALID, std::string("flux_get_tensor: shape mismatch for ") + name + ": expected (" + std::to_string(d.rows) + (d.cols ? "," + std::to_string(d.cols) : "") + ")");
   if (dtype != FMI_F32 && dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux_get_tensor: dtype must be F32 or BF16 (the exact read-backs of a bf16 value)");
-  if (m->missing.count(name)) return fail(FMI_ERR_STATE, std::string("flux_get_tensor: ") + name + " was never set");
+  if (m->missing.names.count(name)) return fail(FMI_ERR_STATE, std::string("flux_get_tensor: ") + name + " was never set");
   FMI_TRY(use_device(m));
   FMI_HIP_TRY(hipDeviceSynchronize());
-  if (m->missing.empty()) FMI_TRY(finalize(m));  // (a quantised part of a mixed fused matrix becomes dense rows here, as at the first evaluation)
+  if (m->missing.names.empty()) FMI_TRY(finalize(m));  // (a quantised part of a mixed fused matrix becomes dense rows here, as at the first evaluation)
   const void* src = d.ptr;
   if (d.d && !d.bias) {
     if (d.d->ar != AR_BASE && (d.d->q_type != 0 || d.d->parts[d.part].state != PS_DENSE || !d.d->w))
@@ -2174,12 +2056,11 @@ extern "C" int fmi_flux_get_tensor(fmi_flux* m, const char* name, void* out, fmi
     FMI_HIP_TRY(hipMemcpy(out, src, (size_t)d.numel * 2, hipMemcpyDefault));
     return FMI_OK;
   }
-  float* tmp = nullptr;
-  FMI_HIP_TRY(hipMalloc((void**)&tmp, (size_t)d.numel * 4));
-  int rc = launch_cast_to_f32(src, FMI_BF16, tmp, d.numel, nullptr);
+  DeviceBuffer tmp;  // (the cast runs on the device, the copy out follows: the staging of upload_as_f32 the other way round)
+  FMI_HIP_TRY(tmp.alloc((size_t)d.numel * 4));
+  int rc = launch_cast_to_f32(src, FMI_BF16, tmp.as<float>(), d.numel, nullptr);
   hipError_t e = hipDeviceSynchronize();
-  if (rc == FMI_OK && e == hipSuccess) e = hipMemcpy(out, tmp, (size_t)d.numel * 4, hipMemcpyDefault);
-  hipFree(tmp);
+  if (rc == FMI_OK && e == hipSuccess) e = hipMemcpy(out, tmp.ptr, (size_t)d.numel * 4, hipMemcpyDefault);
   if (rc == FMI_OK && e != hipSuccess) rc = fail(FMI_ERR_HIP, std::string("flux_get_tensor: ") + hipGetErrorString(e));
   return rc;
 }

@@ -144,6 +144,23 @@ int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hip
   FMI_LAUNCH_CHECK();
   return FMI_OK;
 }
+// The weight upload of every set_tensor (common.h): host or device array -> resident bf16 / f32 (exact or RNE, the cast kernels above)
+template <class T, class Cast>
+static int upload_as(const void* src, fmi_dtype dtype, fmi_dtype same, int64_t n, T* dst, Cast cast) {
+  if (dtype == same) {
+    FMI_HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDefault));
+    return FMI_OK;
+  }
+  const size_t esz = dtype == FMI_F32 ? 4 : 2;
+  DeviceBuffer tmp;
+  FMI_HIP_TRY(tmp.alloc(n * esz));
+  const hipError_t e = hipMemcpy(tmp.ptr, src, n * esz, hipMemcpyDefault);
+  const int rc = e == hipSuccess ? cast(tmp.ptr, dtype, dst, n, nullptr) : fail(FMI_ERR_HIP, hipGetErrorString(e));
+  (void)hipDeviceSynchronize();  // the cast reads the staging block, which goes out of scope here
+  return rc;
+}
+int upload_as_bf16(const void* src, fmi_dtype dtype, int64_t n, bf16_t* dst) { return upload_as(src, dtype, FMI_BF16, n, dst, launch_cast_to_bf16); }
+int upload_as_f32(const void* src, fmi_dtype dtype, int64_t n, float* dst) { return upload_as(src, dtype, FMI_F32, n, dst, launch_cast_to_f32); }
 
 // img = img + pred * dt   (pipelines/sampling.rs:43; latent kept in f32)
 int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream) {

@@ -187,15 +187,14 @@ struct Dest {
   int rows, cols;  // cols == 0 -> 1-D
 };
 struct Registry {
-  char* arena = nullptr;
-  size_t bytes = 0, used = 0;
+  DeviceBuffer arena;
+  size_t bytes = 0, used = 0;  // bytes: the layout size (known before the arena exists)
   std::map<std::string, Dest> names;
-  std::set<std::string> missing;
-  std::vector<std::string> missing_list;
+  MissingSet missing;
   bf16_t* take(size_t count) {
     const size_t off = align_up(used, 256);
     used = off + count * sizeof(bf16_t);
-    return arena ? reinterpret_cast<bf16_t*>(arena + off) : nullptr;
+    return arena ? reinterpret_cast<bf16_t*>(arena.as<char>() + off) : nullptr;
   }
   void reg(const std::string& name, bf16_t* p, int rows, int cols) {
     names[name] = Dest{p, rows, cols};
@@ -210,37 +209,18 @@ struct Registry {
     if (!ok) return fail(FMI_ERR_INVALID, std::string(who) + ": shape mismatch for " + name + " (expected (" + std::to_string(d.rows) + (d.cols ? "," + std::to_string(d.cols) : "") + "))");
     if (dtype != FMI_F32 && dtype != FMI_F16 && dtype != FMI_BF16) return fail(FMI_ERR_INVALID, std::string(who) + ": dtype must be F32/F16/BF16");
     const int64_t numel = (int64_t)d.rows * (d.cols ? d.cols : 1);
-    if (dtype == FMI_BF16) {
-      FMI_HIP_TRY(hipMemcpy(d.ptr, data, numel * 2, hipMemcpyDefault));
-    } else {
-      const size_t esz = dtype == FMI_F32 ? 4 : 2;
-      void* tmp = nullptr;
-      FMI_HIP_TRY(hipMalloc(&tmp, numel * esz));
-      hipError_t e = hipMemcpy(tmp, data, numel * esz, hipMemcpyDefault);
-      int rc = e == hipSuccess ? launch_cast_to_bf16(tmp, dtype, d.ptr, numel, nullptr) : fail(FMI_ERR_HIP, hipGetErrorString(e));
-      (void)hipDeviceSynchronize();
-      (void)hipFree(tmp);
-      if (rc) return rc;
-    }
+    FMI_TRY(upload_as_bf16(data, dtype, numel, d.ptr));
     missing.erase(name);
     return FMI_OK;
-  }
-  int ready(const char* who) {
-    if (missing.empty()) return FMI_OK;
-    return fail(FMI_ERR_STATE, std::string(who) + ": " + std::to_string(missing.size()) + " tensors not set, first: " + *missing.begin());
   }
 };
 
 struct Workspace {
-  char* base = nullptr;
-  size_t bytes = 0;
+  DeviceBuffer base;
   int B = 0, T = 0;
-  int reserve(size_t need) {
-    if (need <= bytes) return FMI_OK;
-    if (base) FMI_HIP_TRY(hipFree(base));
-    base = nullptr, bytes = 0;
-    FMI_HIP_TRY(hipMalloc((void**)&base, need));
-    bytes = need;
+  int reserve(size_t need) {  // grow-only
+    if (need <= base.bytes()) return FMI_OK;
+    FMI_HIP_TRY(base.alloc(need));
     return FMI_OK;
   }
 };
@@ -316,7 +296,7 @@ static void t5_layout(fmi_t5* m) {
   Registry& r = m->r;
   r.used = 0;
   r.names.clear();
-  r.missing.clear();
+  r.missing.names.clear();
   m->shared = r.take((size_t)c.vocab_size * D);
   r.reg("shared.weight", m->shared, c.vocab_size, D);
   m->rel = r.take((size_t)c.relative_attention_num_buckets * c.num_heads);
@@ -368,7 +348,7 @@ extern "C" int fmi_t5_create(const fmi_t5_config* cfg, fmi_t5** out) {
   m->cfg = *cfg;
   t5_layout(m);  // pass 0: size
   m->r.bytes = align_up(m->r.used, 256);
-  hipError_t e = hipMalloc((void**)&m->r.arena, m->r.bytes);
+  hipError_t e = m->r.arena.alloc(m->r.bytes);
   if (e != hipSuccess) {
     delete m;
     return fail(FMI_ERR_HIP, std::string("t5_create: hipMalloc of the weight arena: ") + hipGetErrorString(e));
@@ -378,10 +358,7 @@ extern "C" int fmi_t5_create(const fmi_t5_config* cfg, fmi_t5** out) {
   return FMI_OK;
 }
 extern "C" void fmi_t5_destroy(fmi_t5* m) {
-  if (!m) return;
-  if (m->r.arena) (void)hipFree(m->r.arena);
-  if (m->ws.base) (void)hipFree(m->ws.base);
-  delete m;
+  delete m;  // (the weight arena and the workspace are DeviceBuffers)
 }
 extern "C" int fmi_t5_set_tensor(fmi_t5* m, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
@@ -416,20 +393,13 @@ extern "C" int fmi_t5_set_linear_bnb4(fmi_t5* m, const char* prefix, const uint8
   Dest d;
   std::string wname;
   FMI_TRY(t5_linear_dest(m, "t5_set_linear_bnb4", prefix, out_features, in_features, &d, &wname));
-  uint8_t* dq = nullptr;
-  float* da = nullptr;
-  FMI_HIP_TRY(hipMalloc((void**)&dq, (size_t)n / 2));
-  hipError_t e = hipMalloc((void**)&da, (size_t)(n / blocksize) * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dq, packed, (size_t)n / 2, hipMemcpyDefault);
-  if (e == hipSuccess) e = hipMemcpy(da, absmax, (size_t)(n / blocksize) * sizeof(float), hipMemcpyDefault);
-  if (e == hipSuccess) {
-    if (quant_type == 2) dequantize_blockwise_bf16_nf4(nullptr, dq, da, d.ptr, blocksize, (int)n, nullptr);
-    else dequantize_blockwise_bf16_fp4(nullptr, dq, da, d.ptr, blocksize, (int)n, nullptr);
-    e = hipDeviceSynchronize();
-  }
-  (void)hipFree(dq);
-  if (da) (void)hipFree(da);
-  if (e != hipSuccess) return fail(FMI_ERR_HIP, std::string("t5_set_linear_bnb4: ") + hipGetErrorString(e));
+  const int rc = with_staged_pair(packed, (size_t)n / 2, absmax, (size_t)(n / blocksize) * sizeof(float), [&](void* dq, void* da) {
+    if (quant_type == 2) dequantize_blockwise_bf16_nf4(nullptr, (const uint8_t*)dq, (const float*)da, d.ptr, blocksize, (int)n, nullptr);
+    else dequantize_blockwise_bf16_fp4(nullptr, (const uint8_t*)dq, (const float*)da, d.ptr, blocksize, (int)n, nullptr);
+    return (int)FMI_OK;
+  });
+  if (rc == FMI_ERR_HIP) return fail(FMI_ERR_HIP, std::string("t5_set_linear_bnb4: ") + fmi_last_error());
+  if (rc) return rc;
   m->r.missing.erase(wname);
   return FMI_OK;
 }
@@ -440,37 +410,23 @@ extern "C" int fmi_t5_set_linear_int8(fmi_t5* m, const char* prefix, const int8_
   Dest d;
   std::string wname;
   FMI_TRY(t5_linear_dest(m, "t5_set_linear_int8", prefix, out_features, in_features, &d, &wname));
-  int8_t* dw = nullptr;
-  float* ds = nullptr;
-  FMI_HIP_TRY(hipMalloc((void**)&dw, (size_t)n));
-  hipError_t e = hipMalloc((void**)&ds, (size_t)out_features * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(dw, weight, (size_t)n, hipMemcpyDefault);
-  if (e == hipSuccess) e = hipMemcpy(ds, scb, (size_t)out_features * sizeof(float), hipMemcpyDefault);
-  int rc = FMI_OK;
-  if (e == hipSuccess) {
-    rc = launch_dequant_int8_scb_bf16(dw, ds, d.ptr, in_features, n, nullptr);
-    e = hipDeviceSynchronize();
-  }
-  (void)hipFree(dw);
-  if (ds) (void)hipFree(ds);
-  if (e != hipSuccess) return fail(FMI_ERR_HIP, std::string("t5_set_linear_int8: ") + hipGetErrorString(e));
+  const int rc = with_staged_pair(weight, (size_t)n, scb, (size_t)out_features * sizeof(float), [&](void* dw, void* ds) {
+    return launch_dequant_int8_scb_bf16((const int8_t*)dw, (const float*)ds, d.ptr, in_features, n, nullptr);
+  });
+  if (rc == FMI_ERR_HIP) return fail(FMI_ERR_HIP, std::string("t5_set_linear_int8: ") + fmi_last_error());
   if (rc) return rc;
   m->r.missing.erase(wname);
   return FMI_OK;
 }
-extern "C" int fmi_t5_missing_count(const fmi_t5* m) { return m ? (int)m->r.missing.size() : 0; }
-extern "C" const char* fmi_t5_missing_name(fmi_t5* m, int i) {
-  if (!m) return nullptr;
-  m->r.missing_list.assign(m->r.missing.begin(), m->r.missing.end());
-  return (i >= 0 && i < (int)m->r.missing_list.size()) ? m->r.missing_list[i].c_str() : nullptr;
-}
-extern "C" size_t fmi_t5_size_in_bytes(const fmi_t5* m) { return m ? m->r.bytes + m->ws.bytes : 0; }
+extern "C" int fmi_t5_missing_count(const fmi_t5* m) { return m ? m->r.missing.count() : 0; }
+extern "C" const char* fmi_t5_missing_name(fmi_t5* m, int i) { return m ? m->r.missing.name(i) : nullptr; }
+extern "C" size_t fmi_t5_size_in_bytes(const fmi_t5* m) { return m ? m->r.bytes + m->ws.base.bytes() : 0; }
 
 extern "C" int fmi_t5_forward(fmi_t5* m, const int32_t* input_ids, int B, int T, void* out, fmi_dtype out_dtype, void* stream) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
   if (!m || !input_ids || !out) return fail(FMI_ERR_INVALID, "t5_forward: null argument");
   if (B <= 0 || T <= 0) return fail(FMI_ERR_INVALID, "t5_forward: empty batch");
-  FMI_TRY(m->r.ready("t5_forward"));
+  FMI_TRY(m->r.missing.ready("t5_forward"));
   hipStream_t s = (hipStream_t)stream;
   const fmi_t5_config& c = m->cfg;
   const int D = c.d_model, H = c.num_heads, I = H * 64, F = c.d_ff, rows = B * T;
@@ -487,7 +443,7 @@ extern "C" int fmi_t5_forward(fmi_t5* m, const int32_t* input_ids, int B, int T,
   const size_t o_h = carve((size_t)rows * FW * 2), o_g = carve((size_t)rows * F * 2), o_bias = carve((size_t)H * T * T * 4), o_ones = carve((size_t)D * 4);
   const size_t o_ids = carve((size_t)rows * 4), o_bkt = carve((size_t)(2 * T - 1) * 4), o_err = carve(4), o_of = carve((size_t)rows * D * 4);
   FMI_TRY(m->ws.reserve(off));
-  char* w = m->ws.base;
+  char* w = m->ws.base.as<char>();
   float* x = (float*)(w + o_x);
   bf16_t* n = (bf16_t*)(w + o_n);
   bf16_t* qkv = (bf16_t*)(w + o_qkv);
@@ -560,7 +516,7 @@ static void clip_layout(fmi_clip* m) {
   Registry& r = m->r;
   r.used = 0;
   r.names.clear();
-  r.missing.clear();
+  r.missing.names.clear();
   const std::string tm = "text_model.";
   m->tok = r.take((size_t)c.vocab_size * D);
   r.reg(tm + "embeddings.token_embedding.weight", m->tok, c.vocab_size, D);
@@ -606,7 +562,7 @@ extern "C" int fmi_clip_create(const fmi_clip_config* cfg, fmi_clip** out) {
   m->cfg = *cfg;
   clip_layout(m);
   m->r.bytes = align_up(m->r.used, 256);
-  hipError_t e = hipMalloc((void**)&m->r.arena, m->r.bytes);
+  hipError_t e = m->r.arena.alloc(m->r.bytes);
   if (e != hipSuccess) {
     delete m;
     return fail(FMI_ERR_HIP, std::string("clip_create: hipMalloc of the weight arena: ") + hipGetErrorString(e));
@@ -616,23 +572,16 @@ extern "C" int fmi_clip_create(const fmi_clip_config* cfg, fmi_clip** out) {
   return FMI_OK;
 }
 extern "C" void fmi_clip_destroy(fmi_clip* m) {
-  if (!m) return;
-  if (m->r.arena) (void)hipFree(m->r.arena);
-  if (m->ws.base) (void)hipFree(m->ws.base);
-  delete m;
+  delete m;  // (the weight arena and the workspace are DeviceBuffers)
 }
 extern "C" int fmi_clip_set_tensor(fmi_clip* m, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
   if (!m) return fail(FMI_ERR_INVALID, "clip_set_tensor: null model");
   return m->r.set("clip_set_tensor", name, data, dtype, shape, rank);
 }
-extern "C" int fmi_clip_missing_count(const fmi_clip* m) { return m ? (int)m->r.missing.size() : 0; }
-extern "C" const char* fmi_clip_missing_name(fmi_clip* m, int i) {
-  if (!m) return nullptr;
-  m->r.missing_list.assign(m->r.missing.begin(), m->r.missing.end());
-  return (i >= 0 && i < (int)m->r.missing_list.size()) ? m->r.missing_list[i].c_str() : nullptr;
-}
-extern "C" size_t fmi_clip_size_in_bytes(const fmi_clip* m) { return m ? m->r.bytes + m->ws.bytes : 0; }
+extern "C" int fmi_clip_missing_count(const fmi_clip* m) { return m ? m->r.missing.count() : 0; }
+extern "C" const char* fmi_clip_missing_name(fmi_clip* m, int i) { return m ? m->r.missing.name(i) : nullptr; }
+extern "C" size_t fmi_clip_size_in_bytes(const fmi_clip* m) { return m ? m->r.bytes + m->ws.base.bytes() : 0; }
 
 extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, int T, void* pooled_out, fmi_dtype pooled_dtype, float* hidden_out, void* stream) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
@@ -640,7 +589,7 @@ extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, in
   if (B <= 0 || T <= 0) return fail(FMI_ERR_INVALID, "clip_forward: empty batch");
   const fmi_clip_config& c = m->cfg;
   if (T > c.max_position_embeddings) return fail(FMI_ERR_INVALID, "clip_forward: sequence longer than max_position_embeddings");
-  FMI_TRY(m->r.ready("clip_forward"));
+  FMI_TRY(m->r.missing.ready("clip_forward"));
   hipStream_t s = (hipStream_t)stream;
   const int D = c.projection_dim, H = c.num_attention_heads, F = c.intermediate_size, rows = B * T;
   size_t off = 0;
@@ -653,7 +602,7 @@ extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, in
   const size_t o_h = carve((size_t)rows * F * 2), o_g = carve((size_t)rows * F * 2), o_ones = carve((size_t)D * 4), o_ids = carve((size_t)rows * 4), o_err = carve(4);
   const size_t o_hf = carve((size_t)rows * D * 4), o_pf = carve((size_t)B * D * 4), o_pb = carve((size_t)B * D * 2);
   FMI_TRY(m->ws.reserve(off));
-  char* w = m->ws.base;
+  char* w = m->ws.base.as<char>();
   float* x = (float*)(w + o_x);
   bf16_t* n = (bf16_t*)(w + o_n);
   bf16_t* qkv = (bf16_t*)(w + o_qkv);

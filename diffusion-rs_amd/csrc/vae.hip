@@ -323,7 +323,7 @@ struct Dest {
 struct fmi_vae {
   fmi_vae_config cfg;
   int device = current_device();
-  std::vector<void*> allocs;
+  std::vector<DeviceBuffer> allocs;  // every weight tensor: one block each (valloc)
   Conv conv_in, conv_out;
   Resnet mid1, mid2;
   GN attn_gn, norm_out;
@@ -339,12 +339,10 @@ struct fmi_vae {
   std::vector<Conv> downconv;  // per level (cout == 0 if none)
   bf16_t* zero = nullptr;
   std::map<std::string, Dest> names;
-  std::set<std::string> missing;
-  std::vector<std::string> missing_list;
+  MissingSet missing;
   // workspace
   int wB = 0, wh = 0, ww = 0;
-  char* ws = nullptr;
-  size_t ws_bytes = 0;
+  DeviceBuffer ws;
   // fx / fx2: the TRUNK (what ResnetBlocks, the AttnBlock and the samplers add to) in f32 since round 5 — its bf16 rounding after every block was what
   // cost the decoder its u8 agreement (tools/vae_rounding_study.py: all activations bf16 99.54 % within 2; trunk f32, everything else bf16: 100 %);
   // bt1 / bt2 / bsc: bf16 activations inside a block (every MFMA operand); ones: the gate of the f32 read-modify-write epilogue
@@ -356,11 +354,11 @@ struct fmi_vae {
 namespace {
 template <typename T>
 T* valloc(fmi_vae* v, size_t count) {
-  void* p = nullptr;
-  if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 256)) != hipSuccess) return nullptr;
-  hipMemset(p, 0, std::max<size_t>(count * sizeof(T), 256));
-  v->allocs.push_back(p);
-  return (T*)p;
+  DeviceBuffer b;
+  if (b.alloc(std::max<size_t>(count * sizeof(T), 256)) != hipSuccess) return nullptr;
+  hipMemset(b.ptr, 0, b.bytes());
+  v->allocs.push_back(std::move(b));
+  return v->allocs.back().as<T>();
 }
 bool make_conv(fmi_vae* v, Conv& c, const std::string& p, int cin, int cout, int ks, bool linear = false) {
   c.cin = cin, c.cin_pad = pad64(cin), c.cout = cout, c.ks = ks;
@@ -422,13 +420,9 @@ int vae_workspace(fmi_vae* v, int B, int h, int w) {
   const size_t stat_bytes = ((size_t)B * G * sizeof(float2) + 255) / 256 * 256;
   const size_t ones_bytes = 4096 * sizeof(float);
   const size_t total = 7 * act_bytes + score_bytes + part_bytes + stat_bytes + ones_bytes;
-  if (v->ws) {
-    FMI_HIP_TRY(hipDeviceSynchronize());
-    FMI_HIP_TRY(hipFree(v->ws));
-    v->ws = nullptr;
-  }
-  FMI_HIP_TRY(hipMalloc((void**)&v->ws, total));
-  char* p = v->ws;
+  if (v->ws) FMI_HIP_TRY(hipDeviceSynchronize());
+  FMI_HIP_TRY(v->ws.alloc(total));
+  char* p = v->ws.as<char>();
   v->fx = (float*)p, p += 2 * act_bytes;
   v->fx2 = (float*)p, p += 2 * act_bytes;
   v->bt1 = (bf16_t*)p, p += act_bytes;
@@ -442,7 +436,6 @@ int vae_workspace(fmi_vae* v, int B, int h, int w) {
     std::vector<float> one(4096, 1.0f);
     FMI_HIP_TRY(hipMemcpy(v->ones, one.data(), ones_bytes, hipMemcpyHostToDevice));
   }
-  v->ws_bytes = total;
   v->wB = B, v->wh = h, v->ww = w;
   return FMI_OK;
 }
@@ -615,8 +608,6 @@ extern "C" int fmi_vae_create(const fmi_vae_config* cfg, fmi_model_dtype dtype, 
 extern "C" void fmi_vae_destroy(fmi_vae* v) {
   if (!v) return;
   hipDeviceSynchronize();
-  for (void* p : v->allocs) hipFree(p);
-  if (v->ws) hipFree(v->ws);
   delete v;
 }
 
@@ -632,43 +623,29 @@ extern "C" int fmi_vae_set_tensor(fmi_vae* v, const char* name, const void* data
   if (!ok && d.kind == 3 && rank == 4 && shape[0] == d.shape[0] && shape[1] == d.shape[1] && shape[2] == 1 && shape[3] == 1) ok = true;
   if (!ok) return fail(FMI_ERR_INVALID, std::string("vae_set_tensor: shape mismatch for ") + name);
   if (dtype != FMI_F32 && dtype != FMI_F16 && dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "vae_set_tensor: dtype must be F32/F16/BF16");
-  const size_t esz = dtype == FMI_F32 ? 4 : 2;
-  void* tmp = nullptr;
-  FMI_HIP_TRY(hipMalloc(&tmp, d.numel * esz));
   int rc = FMI_OK;
-  if (hipMemcpy(tmp, data, d.numel * esz, hipMemcpyDefault) != hipSuccess) rc = fail(FMI_ERR_HIP, "vae_set_tensor: copy failed");
-  if (rc == FMI_OK) {
-    if (d.kind == 2) {
-      rc = launch_cast_to_f32(tmp, dtype, (float*)d.ptr, d.numel, nullptr);
-    } else if (d.kind == 1) {
-      rc = launch_cast_to_bf16(tmp, dtype, (bf16_t*)d.ptr, d.numel, nullptr);
-    } else {
-      bf16_t* wb = nullptr;
-      if (hipMalloc((void**)&wb, d.numel * 2) != hipSuccess) rc = fail(FMI_ERR_NOMEM, "vae_set_tensor: alloc failed");
-      if (rc == FMI_OK) rc = launch_cast_to_bf16(tmp, dtype, wb, d.numel, nullptr);
-      if (rc == FMI_OK) {
-        const Conv& c = *d.conv;
-        const int64_t n = (int64_t)c.cout * c.ks * c.ks * c.cin_pad;
-        hipLaunchKernelGGL(conv_weight_relayout_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(n, 256), 4096)), dim3(256), 0, nullptr, wb, c.w, c.cin,
-                           c.cin_pad, c.ks * c.ks, n);
-      }
-      hipDeviceSynchronize();
-      if (wb) hipFree(wb);
+  if (d.kind == 2) {
+    rc = upload_as_f32(data, dtype, d.numel, (float*)d.ptr);
+  } else if (d.kind == 1) {
+    rc = upload_as_bf16(data, dtype, d.numel, (bf16_t*)d.ptr);
+  } else {  // a conv / linear weight: bf16 in the checkpoint's layout first, then the relayout into the implicit GEMM's (cout, tap, cin_pad)
+    DeviceBuffer wb;
+    if (wb.alloc(d.numel * 2) != hipSuccess) rc = fail(FMI_ERR_NOMEM, "vae_set_tensor: alloc failed");
+    if (rc == FMI_OK) rc = upload_as_bf16(data, dtype, d.numel, wb.as<bf16_t>());
+    if (rc == FMI_OK) {
+      const Conv& c = *d.conv;
+      const int64_t n = (int64_t)c.cout * c.ks * c.ks * c.cin_pad;
+      hipLaunchKernelGGL(conv_weight_relayout_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(n, 256), 4096)), dim3(256), 0, nullptr, wb.as<bf16_t>(), c.w,
+                         c.cin, c.cin_pad, c.ks * c.ks, n);
     }
+    hipDeviceSynchronize();
   }
-  hipDeviceSynchronize();
-  hipFree(tmp);
   if (rc == FMI_OK) v->missing.erase(name);
   return rc;
 }
 
-extern "C" int fmi_vae_missing_count(const fmi_vae* v) { return v ? (int)v->missing.size() : 0; }
-extern "C" const char* fmi_vae_missing_name(const fmi_vae* v, int i) {
-  if (!v || i < 0 || i >= (int)v->missing.size()) return nullptr;
-  auto* vv = const_cast<fmi_vae*>(v);
-  vv->missing_list.assign(v->missing.begin(), v->missing.end());
-  return vv->missing_list[i].c_str();
-}
+extern "C" int fmi_vae_missing_count(const fmi_vae* v) { return v ? v->missing.count() : 0; }
+extern "C" const char* fmi_vae_missing_name(const fmi_vae* v, int i) { return v ? v->missing.name(i) : nullptr; }
 extern "C" double fmi_vae_scale_factor(const fmi_vae* v) { return v ? v->cfg.scaling_factor : 0.0; }
 extern "C" double fmi_vae_shift_factor(const fmi_vae* v) { return v ? v->cfg.shift_factor : 0.0; }
 
@@ -678,7 +655,7 @@ bool is_encoder_name(const std::string& n) { return n.rfind("encoder.", 0) == 0 
 int check_part(fmi_vae* v, bool decoder) {
   int n = 0;
   const std::string* first = nullptr;
-  for (const auto& m : v->missing)
+  for (const auto& m : v->missing.names)
     if (is_encoder_name(m) != decoder) {
       if (!first) first = &m;
       ++n;
