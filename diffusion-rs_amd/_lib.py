@@ -72,6 +72,17 @@ class ClipConfig(C.Structure):
                 ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int)]
 
 
+class GemmDesc(C.Structure):
+    """fmi_gemm_desc: one problem of fmi_gemm_group, the test seam into the GEMM launcher (include/flux_mi355x.h)."""
+    _fields_ = [("a", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("gate", C.c_void_p), ("resid", C.c_void_p),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldw", C.c_int), ("ldo", C.c_int), ("epi", C.c_int),
+                ("gelu_from", C.c_int), ("alpha", C.c_float), ("rows_per_batch", C.c_int), ("gate_bstride", C.c_int), ("q8", C.c_int),
+                ("a_scale", C.c_void_p), ("w_scale", C.c_void_p), ("a_off", C.c_void_p), ("w_sum", C.c_void_p)]
+
+
+# fmi_gemm_epi
+GEMM_STORE_BF16, GEMM_GELU_BF16, GEMM_RESID_GATE_F32, GEMM_GELU_FROM_COL, GEMM_STORE_F32, GEMM_SCALE_BF16, GEMM_RESID_ADD_BF16, GEMM_SILU_BF16 = range(8)
+
 F32, F16, BF16, U8, I8 = 0, 1, 2, 3, 4
 MODEL_AUTO, MODEL_BF16, MODEL_F16, MODEL_F32 = 0, 1, 2, 3
 
@@ -208,6 +219,9 @@ def _declare(lib):
     lib.fmi_postprocess_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.fmi_linear_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_quantize_rows_fp8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fmi_gemm_group.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
+    lib.fmi_splitk_resid_gate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.fmi_set_gemm_kernel.argtypes = [C.c_int, C.c_int]
     lib.fmi_linear_fp8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_quantize_rows_i8.argtypes = lib.fmi_quantize_rows_fp8.argtypes
     lib.fmi_linear_i8.argtypes = lib.fmi_linear_fp8.argtypes
@@ -293,7 +307,7 @@ EXPORTED = [
     "fmi_t5_size_in_bytes", "fmi_t5_forward", "fmi_clip_default_config", "fmi_clip_create", "fmi_clip_destroy", "fmi_clip_set_tensor",
     "fmi_clip_missing_count", "fmi_clip_missing_name", "fmi_clip_size_in_bytes", "fmi_clip_forward", "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
     "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids",
-    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
+    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
     "fmi_release_scratch", "fmi_timestep_embedding", "fmi_rope_table", "fmi_rmsnorm_rope",
     "fmi_groupnorm_nhwc", "fmi_conv2d_nhwc",
     "fmi_comm_probe", "fmi_comm_unique_id", "fmi_comm_create", "fmi_comm_destroy", "fmi_comm_rank", "fmi_comm_world_size", "fmi_comm_stats", "fmi_comm_all_to_all",

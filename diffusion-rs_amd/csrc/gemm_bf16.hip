@@ -1375,6 +1375,16 @@ static int validate_gemm_problems(const GemmProblem* probs, int nprob, int bn) {
     if ((!conv && p.lda % 8) || (!quant && p.ldw % 8)) return fail(FMI_ERR_INVALID, "launch_gemm: lda/ldw must be multiples of 8 elements (16-byte rows)");
     if (conv && (p.cv_cin % 64 || p.K != p.cv_ks * p.cv_ks * p.cv_cin || !p.cv_zero)) return fail(FMI_ERR_INVALID, "launch_gemm: bad conv descriptor (Cin % 64, K = k*k*Cin)");
     if (quant && p.q_type != 3 && (p.q_blocksize % 64 != 0 || p.q_blocksize <= 0)) return fail(FMI_ERR_INVALID, "launch_gemm: 4-bit blocksize must be a multiple of 64");
+    // what the epilogues read without a look: the staged f32 path fetches the gate as float4 (base and batch stride must keep 16-byte alignment), the
+    // bf16 residual add reads `resid` at every element, and the GELU boundary is decided per group of 4 columns where a tile straddles it
+    if (p.epi == EPI_RESID_GATE_F32) {
+      if (!p.gate) return fail(FMI_ERR_INVALID, "launch_gemm: the gated residual epilogue needs a gate vector");
+      if ((reinterpret_cast<uintptr_t>(p.gate) & 15) || p.gate_bstride % 4)
+        return fail(FMI_ERR_INVALID, "launch_gemm: gate must be 16-byte aligned and gate_bstride a multiple of 4 elements (read as float4)");
+    }
+    if (p.epi == EPI_RESID_ADD_BF16 && !p.resid) return fail(FMI_ERR_INVALID, "launch_gemm: the bf16 residual-add epilogue needs resid");
+    if (p.epi == EPI_GELU_FROM_COL && p.gelu_from % 4) return fail(FMI_ERR_INVALID, "launch_gemm: gelu_from must be a multiple of 4 (decided per 4-column group), got " + std::to_string(p.gelu_from));
+    if (p.rows_per_batch < 0) return fail(FMI_ERR_INVALID, "launch_gemm: rows_per_batch must be >= 0");
     if (p.qk_qh) {
       if (conv || bn != 256 || p.qk_D % 256 || p.qk_H * 128 != p.qk_D || 3 * p.qk_D > p.N || p.qk_rows <= 0 || p.qk_rows % 16 || p.qk_row_off % 16 || p.M % 16 ||
           p.qk_Lpad % 64 || !p.qk_kh || !p.qk_vt || !p.qk_wq || !p.qk_wk || !p.qk_pe || (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 7)))

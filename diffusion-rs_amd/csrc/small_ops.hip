@@ -328,6 +328,7 @@ __global__ void splitk_resid_gate_kernel(const float4* __restrict__ parts, int S
 int launch_splitk_resid_gate(const float* parts, int S, const bf16_t* bias, const float* gate, int rows_per_batch, int gate_bstride, float* out, int ldo,
                              int M, int N, hipStream_t stream) {
   if (N % 4 || ldo % 4) return fail(FMI_ERR_INVALID, "splitk reduce: N and ldo must be multiples of 4");
+  if (!gate) return fail(FMI_ERR_INVALID, "splitk reduce: needs a gate vector");
   const int64_t total = (int64_t)M * (N / 4);
   splitk_resid_gate_kernel<<<(int)std::min<int64_t>((total + 255) / 256, 2048), 256, 0, stream>>>(reinterpret_cast<const float4*>(parts), S, bias, gate, rows_per_batch,
                                                                                                  gate_bstride, out, ldo, M, N / 4);

@@ -45,6 +45,7 @@ extern "C" {
  *   may share a stream.  Later additions under the same number: fmi_flux_get_tensor and the LoRA adapter calls fmi_flux_lora_*.
  *   Then, still 6: image to image and inpainting — fmi_preprocess_u8, fmi_latent_mask, fmi_encode_latents, fmi_scale_noise, fmi_flux_denoise_inpaint.
  *   Then, still 6: reference-image (FLUX.1 Kontext) conditioning — fmi_flux_context, fmi_flux_forward_context, fmi_flux_denoise_context, fmi_latent_ids.
+ *   Then, still 6: the GEMM launcher's test seams — fmi_gemm_desc, fmi_gemm_group, fmi_splitk_resid_gate, fmi_set_gemm_kernel.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -661,6 +662,58 @@ int fmi_quantize_rows_i8_scaled(const void* x, int rows, int K, int d0, const fl
 int fmi_col_absmax(const void* x, int rows, int K, int ld, float* amax_inout, void* stream);
 int fmi_gemm_i8_asym(const void* xq, const float* x_scale, const float* x_offset, const void* wq, const float* w_scale, const float* w_sum,
                      const void* bias, void* y, int M, int N, int K, fmi_epilogue epi, void* stream);
+/* TEST SEAMS into the GEMM launcher (ABI 6; tests/test_gpu_gemm_epilogues.py) — not part of the product surface.  The entries above reach three
+ * of the launcher's eight epilogues, one problem per launch, dense leading dimensions; the rest (gated f32 residual update with per-batch gate
+ * rows, GELU from a column on, f32 store / scaled store, the int8 offset term, strided operands, grouped launches, the split-K reduce) otherwise
+ * runs only inside the models.  fmi_gemm_group hands 1 .. 8 descriptors to the launcher as ONE grouped launch:
+ *   pre[m, n] = alpha * sum_k a[m, k] w[n, k]   (q8 != 0: the 8-bit sum * a_scale[m] * w_scale[n] + a_off[m] * w_sum[n], then * alpha)  + bias[n]
+ *   FMI_GEMM_STORE_BF16 / _GELU_BF16 / _SILU_BF16: out bf16 = act(pre)           (alpha: STORE_F32 and SCALE_BF16 only, exactly 1 elsewhere)
+ *   FMI_GEMM_RESID_GATE_F32: out f32 (read-modify-write) += gate_b[n] * pre,  gate_b = gate + (rows_per_batch > 0 ? m / rows_per_batch : 0) * gate_bstride
+ *   FMI_GEMM_GELU_FROM_COL:  out bf16 = n >= gelu_from ? gelu(pre) : pre      (gelu_from % 4 == 0)
+ *   FMI_GEMM_STORE_F32 / _SCALE_BF16: out f32 / bf16 = pre                    FMI_GEMM_RESID_ADD_BF16: out bf16 = resid[m * ldo + n] + pre
+ * a (M, K) and w (N, K) bf16 (q8 = 1: OCP e4m3 bytes, 2: int8; then N > 128, K % 128 == 0, lda / ldw % 16 == 0, both scale vectors; a_off / w_sum
+ * int8 only, both or neither), 16-byte aligned, leading dimensions in elements (>= K, multiples of 8); K % 64 == 0; bias (N) bf16 or NULL;
+ * gate f32, 16-byte aligned, gate_bstride % 4 == 0; ldo >= N.  All problems of a group share q8 and the activation kind (none / GELU /
+ * GELU from a column / the rest).  Everything is checked on the host before anything is launched: FMI_ERR_INVALID, nothing written.
+ * fmi_splitk_resid_gate is the second kernel of the split-K latency mode (fmi_flux_set_split_k): out[m, n] += gate_b[n] * (parts_0 + ... + parts_{S-1}
+ * + bias[n]), parts (S, M, N) f32 contiguous added in index order; N, ldo % 4 == 0, out and parts 16-byte aligned.
+ * fmi_set_gemm_kernel picks, PROCESS-WIDE, the kernel of the dense bf16 launches wider than 128 columns: pingpong = 1 (default) the ping-pong kernel,
+ * 0 its double-buffered predecessor; w4 = 1 sends the residual-update launches to the 4-wave kernel.  The three are bit-identical; the two
+ * alternatives live in the test build — in the product library a launch that would need one fails with FMI_ERR_UNSUPPORTED. */
+typedef enum fmi_gemm_epi {
+  FMI_GEMM_STORE_BF16 = 0,
+  FMI_GEMM_GELU_BF16 = 1,
+  FMI_GEMM_RESID_GATE_F32 = 2,
+  FMI_GEMM_GELU_FROM_COL = 3,
+  FMI_GEMM_STORE_F32 = 4,
+  FMI_GEMM_SCALE_BF16 = 5,
+  FMI_GEMM_RESID_ADD_BF16 = 6,
+  FMI_GEMM_SILU_BF16 = 7
+} fmi_gemm_epi;
+typedef struct fmi_gemm_desc {
+  const void* a;
+  const void* w;
+  const void* bias;
+  void* out;
+  const float* gate;
+  const void* resid;
+  int M, N, K;
+  int lda, ldw, ldo;
+  int epi; /* fmi_gemm_epi */
+  int gelu_from;
+  float alpha;
+  int rows_per_batch;
+  int gate_bstride;
+  int q8; /* 0 bf16, 1 e4m3, 2 int8 */
+  const float* a_scale;
+  const float* w_scale;
+  const float* a_off;
+  const float* w_sum;
+} fmi_gemm_desc;
+int fmi_gemm_group(const fmi_gemm_desc* probs, int nprob, void* stream);
+int fmi_splitk_resid_gate(const float* parts, int S, const void* bias, const float* gate, int rows_per_batch, int gate_bstride, float* out, int ldo,
+                          int M, int N, void* stream);
+int fmi_set_gemm_kernel(int pingpong, int w4);
 /* softmax(q k^T * scale) v, q,k,v,o (B,H,L,d) bf16, d == 128, non-causal; o is written
  * token-major (B,L,H*d) when `out_token_major`, else (B,H,L,d).
  * == backend::ops::sdpa fallback (ops.rs:247-262) without materialising the scores. */
