@@ -494,5 +494,12 @@ int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int
 int launch_splitk_resid_gate(const float* parts, int S, const bf16_t* bias, const float* gate, int rows_per_batch, int gate_bstride, float* out, int ldo,
                              int M, int N, hipStream_t stream);
 int launch_split_rows_f32(const float* src, float* dst, int B, int rows_src_per_b, int row_off, int rows, int D, hipStream_t stream);
+// First-block step cache (step_cache.hip); n = S' * D elements per sample, x0 / r / r_ref / delta / x1copy are (B, n) contiguous f32.
+// residual: r = x1 - x0 and x0 <- x1 (sample stride of x1: x1_bs); with r_ref also sums[2 b] = sum |r - r_ref|, sums[2 b + 1] = sum |r_ref| of sample b in double, through
+// `part` (B * step_cache_groups(n) * 2 f32) — fixed decomposition, no atomics: the same bits for any B.  delta = xf - x1copy; apply: xf = x1 + delta (xf may be x1).
+int step_cache_groups(int64_t n);
+int launch_step_cache_residual(const float* x1, int64_t x1_bs, float* x0, const float* r_ref, float* r, float* part, double* sums, int B, int64_t n, hipStream_t stream);
+int launch_step_cache_delta(const float* xf, int64_t xf_bs, const float* x1copy, float* delta, int B, int64_t n, hipStream_t stream);
+int launch_step_cache_apply(const float* x1, int64_t x1_bs, const float* delta, float* xf, int64_t xf_bs, int B, int64_t n, hipStream_t stream);
 
 }  // namespace fmi

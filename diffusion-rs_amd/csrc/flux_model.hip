@@ -141,6 +141,12 @@ struct fmi_flux {
   DeviceBuffer vec_steps_bf;                                // silu(vec_steps) in bf16: A operand of the modulation GEMM
   size_t mod_steps_rows = 0;
   int mod_gemm = 1;  // fmi_flux_denoise: 1 = all steps' modulation vectors in one MFMA GEMM when there are more than 4 rows (else GEMV passes of 4 rows), 0 = always GEMV, 2 = always the GEMM
+  // first-block step cache (fmi_flux_denoise_cached): four (B, S', D) f32 buffers — X0, overwritten by the copy of X1 once the residual is
+  // taken; the residual r and the reference residual r_ref, swapped by index on computed steps; the output delta — plus the reduction's partials and sums.
+  // Allocated by the first cached call, regrown like mod_steps, never touched by the plain entries.
+  DeviceBuffer sc_x0, sc_r[2], sc_delta, sc_part, sc_sums;
+  size_t sc_elems = 0, sc_part_floats = 0;
+  double* sc_host = nullptr;  // pinned: (num, den) per sample, read by the host after the per-step synchronisation
   bool fuse_qkv_relayout = true;  // QkNorm + RoPE + head/transposed relayout in the QKV GEMM's epilogue
   // Quantised block linears (nf4 / fp4 / LLM.int8): only the packed codes are resident; small launches multiply from them
   // (fused dequant-GEMM), large ones expand per call into a scratch and run the dense kernel (densify()).
@@ -893,13 +899,54 @@ int compute_vec_steps(fmi_flux* m, const fmi_flux_inputs* in, const float* tv_de
   return launch_add2_rows(vec_steps, gterm, vterm, R, B, D, s);
 }
 
+// The first-block step cache of one fmi_flux_denoise_cached call: the caller's settings and the state the steps hand on.
+struct StepCacheRun {
+  float threshold = 0.f;
+  const int8_t* force = nullptr;
+  int32_t* decisions_out = nullptr;
+  float* distances_out = nullptr;
+  int step = 0;        // index of the evaluation under way
+  bool valid = false;  // a computed step has left r_ref and the delta behind
+  int ref = 0;         // m->sc_r[ref] is r_ref, m->sc_r[ref ^ 1] receives this step's residual
+};
+
+// After double block 0 of a cached evaluation: r = X1 - X0 (X0's buffer takes the copy of X1), the per-sample distances to r_ref through one small device-to-host
+// copy and ONE hipStreamSynchronize, the decision on the host, and on reuse XF = X1 + delta written where the final layer reads the image rows.
+int step_cache_decide(fmi_flux* m, StepCacheRun* sc, int B, int S, int T, hipStream_t s, bool* reuse) {
+  auto& w = m->ws;
+  const int64_t n = (int64_t)S * m->D, L = S + T;
+  PhaseTimer pt(m, s, PH_EMBED);
+  const int i = sc->step;
+  float* const r_ref = m->sc_r[sc->ref].as<float>();
+  FMI_TRY(launch_step_cache_residual(w.x_img, n, m->sc_x0.as<float>(), sc->valid ? r_ref : nullptr, m->sc_r[sc->ref ^ 1].as<float>(), m->sc_part.as<float>(),
+                                     m->sc_sums.as<double>(), B, n, s));
+  bool below = true;  // every sample's distance is under the threshold (a NaN distance is not)
+  if (sc->valid) {
+    FMI_HIP_TRY(hipMemcpyAsync(m->sc_host, m->sc_sums.ptr, (size_t)2 * B * sizeof(double), hipMemcpyDeviceToHost, s));
+    FMI_HIP_TRY(hipStreamSynchronize(s));
+  }
+  for (int b = 0; b < B; ++b) {
+    // d_b = num_b / den_b in double, +inf for den_b == 0, -1 while nothing has been computed yet; reported — and compared — as f32
+    float d = -1.f;
+    if (sc->valid) d = m->sc_host[2 * b + 1] == 0.0 ? INFINITY : (float)(m->sc_host[2 * b] / m->sc_host[2 * b + 1]);
+    if (sc->distances_out) sc->distances_out[(size_t)i * B + b] = d;
+    below = below && d < sc->threshold;
+  }
+  const int f = sc->force ? sc->force[i] : -1;
+  *reuse = sc->valid && (f == 1 || (f < 0 && sc->threshold > 0.f && below));
+  if (sc->decisions_out) sc->decisions_out[i] = *reuse ? 1 : 0;
+  if (*reuse) FMI_TRY(launch_step_cache_apply(w.x_img, n, m->sc_delta.as<float>(), w.x + (size_t)T * m->D, L * m->D, B, n, s));
+  return FMI_OK;
+}
+
 // One model evaluation given prepared static inputs; img_f32 (B,S,C) -> pred (B,S,C) f32.
 // R: context rows per sample.  The image stream then has in->S + R rows per sample — rows [in->S, in->S + R) of w.img_bf and of the RoPE table were
 // written by prepare_static — and everything between the input assembly and the final layer sees only that longer stream; img_f32 and pred stay (B, in->S, C).
 // mod_pre: this step's (B, n_mod) modulation vectors if the caller precomputed them (fmi_flux_denoise), else null.
 // txt_pre: txt_in(txt) if the caller computed it once for all steps (fmi_flux_denoise: it does not depend on the latent or on t), else null.
+// sc: the step cache of a fmi_flux_denoise_cached call, else null — and with null every launch below is the one it always was.
 int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, const float* timesteps_dev, float* pred, hipStream_t s,
-                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0) {
+                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0, StepCacheRun* sc = nullptr) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
   const int B = in->B, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
@@ -938,6 +985,8 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
     } else {
       FMI_TRY(gemm2(m, p, dn, 2, s));
     }
+    // step cache: X0 leaves before block 0's epilogues update the stream in place
+    if (sc) FMI_HIP_TRY(hipMemcpyAsync(m->sc_x0.ptr, w.x_img, (size_t)B * S * D * 4, hipMemcpyDeviceToDevice, s));
   }
   if (!mod_pre) {
     // every Modulation1/2 + LastLayer.ada_ln of the model in one GEMV: lin(silu(vec)) (model.rs:244-299,695-698)
@@ -953,7 +1002,12 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
   const float* const mod = mod_pre ? mod_pre : w.mod;
 
   // ---------------- double-stream blocks (model.rs:523-565)
+  bool reuse = false;  // step cache: this evaluation takes the cached output residual of every block after double block 0
   for (int i = 0; i < c.num_layers; ++i) {
+    if (sc && i == 1) {  // (both chains of block 0 have joined the caller's stream)
+      FMI_TRY(step_cache_decide(m, sc, B, S, T, s, &reuse));
+      if (reuse) break;
+    }
     auto& bw = m->dbl[i];
     const float* mi = mod + bw.mod_off[0];  // shift1, scale1, gate1, shift2, scale2, gate2
     const float* mt = mod + bw.mod_off[1];
@@ -1101,12 +1155,14 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
   }
 
   // ---------------- cat([txt, img], 1) (model.rs:827) then single-stream blocks (model.rs:638-662)
-  for (int b = 0; b < B && w.x_txt != w.x; ++b) {  // (B == 1: the streams alias the joint buffer, ensure_workspace)
+  if (sc && c.num_layers == 1) FMI_TRY(step_cache_decide(m, sc, B, S, T, s, &reuse));
+  // (a reused step has its image rows of the joint stream already and runs neither the concat nor a single block)
+  for (int b = 0; b < B && w.x_txt != w.x && !reuse; ++b) {  // (B == 1: the streams alias the joint buffer, ensure_workspace)
     FMI_HIP_TRY(hipMemcpyAsync(w.x + (size_t)b * L * D, w.x_txt + (size_t)b * T * D, (size_t)T * D * 4, hipMemcpyDeviceToDevice, s));
     FMI_HIP_TRY(hipMemcpyAsync(w.x + ((size_t)b * L + T) * D, w.x_img + (size_t)b * S * D, (size_t)S * D * 4, hipMemcpyDeviceToDevice, s));
   }
   const int ldbig = 3 * D + Mh;
-  for (int i = 0; i < c.num_single_layers; ++i) {
+  for (int i = 0; i < (reuse ? 0 : c.num_single_layers); ++i) {
     auto& bw = m->sgl[i];
     const float* mo = mod + bw.mod_off;  // shift, scale, gate
     bool fused = false;
@@ -1155,6 +1211,14 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
       with_gate(p, mo + 2 * D, L, nmod);
       FMI_TRY(gemm1(m, p, bw.w2, s));
     }
+  }
+  if (sc) {
+    if (!reuse) {  // a computed step: delta = XF - X1 (the copy taken with the residual), this step's residual becomes the reference
+      PhaseTimer pt(m, s, PH_EMBED);
+      FMI_TRY(launch_step_cache_delta(w.x + (size_t)T * D, (int64_t)L * D, m->sc_x0.as<float>(), m->sc_delta.as<float>(), B, (int64_t)S * D, s));
+      sc->ref ^= 1, sc->valid = true;
+    }
+    ++sc->step;
   }
 
   // ---------------- img = img[:, T:] ; LastLayer (model.rs:694-705): chunks = (scale, shift) — on the state's rows only: a context's rows end here
@@ -1235,6 +1299,7 @@ extern "C" void fmi_flux_destroy(fmi_flux* m) {
   if (m->ev_fork) hipEventDestroy(m->ev_fork);
   if (m->ev_join) hipEventDestroy(m->ev_join);
   if (m->side) hipStreamDestroy(m->side);
+  if (m->sc_host) (void)hipHostFree(m->sc_host);
   delete m;  // (every device block is a DeviceBuffer member)
 }
 
@@ -1471,14 +1536,38 @@ extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* p
 // The denoise loop of both entries.  x0 / noise / mask all null: fmi_flux_denoise, the plain Euler update.  All three set: fmi_flux_denoise_inpaint, the same
 // launches with the per-step update replaced by the masked one (launch_euler_blend); nothing before or inside the model evaluation knows the difference.
 // ctx: the reference-image rows every evaluation appends to the state's (fmi_flux_denoise_context); the state, the update and the blend stay (B,S,C).
+// cache: fmi_flux_denoise_cached's first-block step cache, null for every other entry — which then issue exactly the launches they always did.
 static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
-                        const float* x0, const float* noise, const float* mask, void* stream) {
+                        const float* x0, const float* noise, const float* mask, void* stream, const fmi_flux_step_cache* cache = nullptr) {
   FMI_TRY(check_inputs(m, in));
   if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
   int Rc = 0;  // context rows per sample
   FMI_TRY(context_rows(m, ctx, &Rc));
   hipStream_t s = (hipStream_t)stream;
   const int B = in->B;
+  StepCacheRun sc_run, *sc = nullptr;
+  if (cache) {  // every refusal comes before the first launch
+    if (!(cache->threshold >= 0.f)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: threshold must be >= 0 (and not NaN)");
+    for (int i = 0; cache->force && i < n_steps; ++i)
+      if (cache->force[i] < -1 || cache->force[i] > 1 || (i == 0 && cache->force[i] == 1))
+        return fail(FMI_ERR_INVALID, "flux_denoise_cached: force entries are -1, 0 or 1, and step 0 cannot be reused (force[0] != 1)");
+    if (m->cfg.num_layers < 1) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cached: the step cache needs at least one double block");
+    if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cached: the step cache is not supported under sequence parallelism");
+    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise_cached: not while int8 calibration is recording");
+    const size_t per = (size_t)(in->S + Rc) * m->D, elems = (size_t)B * per, part = (size_t)B * step_cache_groups((int64_t)per) * 2;
+    if (m->sc_elems < elems || m->sc_part_floats < part) {
+      FMI_HIP_TRY(hipStreamSynchronize(s));
+      m->sc_x0.reset(), m->sc_r[0].reset(), m->sc_r[1].reset(), m->sc_delta.reset(), m->sc_part.reset(), m->sc_elems = 0, m->sc_part_floats = 0;
+      for (DeviceBuffer* b : {&m->sc_x0, &m->sc_r[0], &m->sc_r[1], &m->sc_delta})
+        if (b->alloc(elems * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise_cached: hipMalloc of a step-cache buffer (" + std::to_string(elems * 4) + " bytes) failed");
+      if (m->sc_part.alloc(part * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise_cached: hipMalloc of the step cache's partial sums failed");
+      m->sc_elems = elems, m->sc_part_floats = part;
+    }
+    if (!m->sc_sums) FMI_HIP_TRY(m->sc_sums.alloc(2 * 8 * sizeof(double)));  // (B <= 8, check_inputs)
+    if (!m->sc_host) FMI_HIP_TRY(hipHostMalloc((void**)&m->sc_host, 2 * 8 * sizeof(double), hipHostMallocDefault));
+    sc_run.threshold = cache->threshold, sc_run.force = cache->force, sc_run.decisions_out = cache->decisions_out, sc_run.distances_out = cache->distances_out;
+    sc = &sc_run;
+  }
   FMI_TRY(ensure_workspace(m, B, in->S + Rc, in->T));
   FMI_TRY(prepare_static(m, in, ctx, Rc, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
   const int64_t n = (int64_t)B * in->S * m->cfg.in_channels;
@@ -1534,7 +1623,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_c
     txt_pre = m->ws.x_txt0;
   }
   for (int i = 0; i < n_steps; ++i) {
-    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc));
+    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc, sc));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
     if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
@@ -1560,6 +1649,18 @@ extern "C" int fmi_flux_denoise_context(fmi_flux* m, const fmi_flux_inputs* in, 
                                         int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
   if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_context: x0, noise and mask go together (all three or none)");
   return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
+}
+
+// The loop of fmi_flux_denoise_context with the first-block step cache; a null cache IS fmi_flux_denoise_context.
+extern "C" int fmi_flux_denoise_cached(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
+                                       int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream) {
+  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: x0, noise and mask go together (all three or none)");
+  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, cache);
+}
+// device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
+extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {
+  if (!m) return 0;
+  return m->sc_x0.bytes() + m->sc_r[0].bytes() + m->sc_r[1].bytes() + m->sc_delta.bytes() + m->sc_part.bytes() + m->sc_sums.bytes();
 }
 
 extern "C" int fmi_flux_set_profiling(fmi_flux* m, int enable) {

@@ -76,6 +76,30 @@ class SchedulerConfig:
         return L.load().fmi_calculate_shift(image_seq_len, self.base_image_seq_len, self.max_image_seq_len, self.base_shift, self.max_shift)
 
 
+def check_step_cache_args(n_steps: int, threshold=None, force=None, sequence_parallel: bool = False):
+    """The arguments of the first-block step cache (FluxModel.denoise / fmi_flux_denoise_cached), checked without the library.
+    Returns (threshold as float, force as an int8 array of n_steps entries or None); (None, None) when neither is given: no cache, the plain loop.
+    ValueError: a negative or NaN threshold; `force` not n_steps entries of -1 (decide by threshold) / 0 (compute) / 1 (reuse); force[0] == 1 (step 0 has
+    nothing to reuse); either of them under sequence parallelism (the distance would need an all-reduce over the ranks)."""
+    if threshold is None and force is None:
+        return None, None
+    if sequence_parallel:
+        raise ValueError("the step cache (cache_threshold= / cache_force=) is not supported under sequence parallelism")
+    thr = 0.0 if threshold is None else float(threshold)
+    if not thr >= 0.0:
+        raise ValueError(f"cache_threshold must be >= 0, got {threshold!r}")
+    if force is None:
+        return thr, None
+    f = np.asarray(force)
+    if f.ndim != 1 or f.shape[0] != n_steps:
+        raise ValueError(f"cache_force must have one entry per step ({n_steps}), got shape {f.shape}")
+    if not np.isin(f, (-1, 0, 1)).all():
+        raise ValueError("cache_force entries are -1 (decide by threshold), 0 (compute) or 1 (reuse)")
+    if n_steps and f[0] == 1:
+        raise ValueError("cache_force[0] == 1: step 0 is always computed (there is nothing to reuse yet)")
+    return thr, np.ascontiguousarray(f, dtype=np.int8)
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
@@ -250,6 +274,7 @@ class FluxModel:
 
         self._sp_cb = L.ALL_TO_ALL_FN(_cb) if world_size > 1 else L.ALL_TO_ALL_FN()  # keep the thunk alive with the model
         L.check(self.lib.fmi_flux_set_sequence_parallel(self.h, int(rank), int(world_size), self._sp_cb, None), self.lib)
+        self._sp_world = int(world_size)
 
     def set_sequence_parallel_native(self, rank: int, world_size: int, comm):
         """The same with the exchange done by the library's own RCCL communicator (dist.RcclComm / fmi_comm): the callback is the C
@@ -258,6 +283,7 @@ class FluxModel:
         fn = C.cast(self.lib.fmi_comm_all_to_all, L.ALL_TO_ALL_FN)
         self._sp_cb, self._sp_comm = fn, comm  # keep both alive with the model
         L.check(self.lib.fmi_flux_set_sequence_parallel(self.h, int(rank), int(world_size), fn, comm.h), self.lib)
+        self._sp_world = int(world_size)
 
     # ---- the weights as flat device buffers (multi-GPU broadcast, dist.broadcast_state)
     def state_export(self) -> bytes:
@@ -332,15 +358,43 @@ class FluxModel:
         L.check(self.lib.fmi_flux_forward_context(self.h, C.byref(inp), C.byref(ctx), _ptr(pred), _stream()), self.lib)
         return pred
 
-    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None):
+    def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
+                cache_threshold=None, cache_force=None, return_cache_stats=False):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
-        context= / context_ids=: reference-image tokens every evaluation appends to the state's (fmi_flux_denoise_context); the state stays (B,S,C)."""
+        context= / context_ids=: reference-image tokens every evaluation appends to the state's (fmi_flux_denoise_context); the state stays (B,S,C).
+        cache_threshold= / cache_force=: the first-block step cache (fmi_flux_denoise_cached), off unless one of them is given.  Every step runs
+        double block 0; a step whose block-0 residual lies within `cache_threshold` (relative L1) of the last computed step's skips every other block and adds
+        their cached output residual.  The decision is per CALL: a batch reuses a step only when every sample is under the threshold, so a batched call may differ
+        from its single-sample runs.  cache_force: one entry per step, -1 decide by threshold, 0 compute, 1 reuse (step 0 is always computed).  The cached loop
+        synchronises the stream once per step.  No threshold is recommended: ParaAttention suggests 0.08 for FLUX.1-dev, which this project has no real weights
+        to verify.  return_cache_stats=True: returns (img, {"decisions": int array (n,), "distances": float array (n, B), -1 where not measured})."""
+        n_steps = len(timesteps) - 1
+        thr, force = check_step_cache_args(n_steps, cache_threshold, cache_force, getattr(self, "_sp_world", 1) > 1)
+        if return_cache_stats and thr is None:
+            raise ValueError("return_cache_stats needs cache_threshold= or cache_force=")
         img = img.to(torch.float32).clone().contiguous()
         inp, keep = self._inputs(None, img_ids, txt, txt_ids, None, y, guidance)
         ts = (C.c_double * len(timesteps))(*timesteps)
         has_ctx = context is not None or context_ids is not None
+        if thr is not None:
+            extra = []
+            for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask")):
+                if t is not None:
+                    if tuple(t.shape) != tuple(img.shape):
+                        raise ValueError(f"denoise: {nm} is {tuple(t.shape)}, img is {tuple(img.shape)}")
+                    t = t.to(device=img.device, dtype=torch.float32).contiguous()
+                extra.append(t)
+            ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
+            B = int(img_ids.shape[0])
+            decisions = np.zeros(max(n_steps, 0), np.int32)
+            distances = np.full((max(n_steps, 0), B), -1.0, np.float32)
+            sc = L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
+                                 decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float)))
+            L.check(self.lib.fmi_flux_denoise_cached(self.h, C.byref(inp), C.byref(ctx) if ctx is not None else None, _ptr(img), ts, n_steps, _ptr(extra[0]),
+                                                     _ptr(extra[1]), _ptr(extra[2]), C.byref(sc), _stream()), self.lib)
+            return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
         if not has_ctx and x0 is None and noise is None and mask is None:
             L.check(self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _stream()), self.lib)
             return img
@@ -360,6 +414,10 @@ class FluxModel:
             L.check(self.lib.fmi_flux_denoise_context(self.h, C.byref(inp), C.byref(ctx), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]),
                                                       _ptr(extra[2]), _stream()), self.lib)
         return img
+
+    def step_cache_bytes(self) -> int:
+        """Device bytes the step cache holds: 0 until the first denoise with cache_threshold= / cache_force= (the plain loops never allocate it)."""
+        return int(self.lib.fmi_flux_step_cache_bytes(self.h))
 
     def set_profiling(self, on: bool):
         L.check(self.lib.fmi_flux_set_profiling(self.h, int(on)), self.lib)

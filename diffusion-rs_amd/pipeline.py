@@ -173,6 +173,7 @@ class Pipeline:
         self.device_index = device
         self.device = torch.device("cuda", device)
         self._lock = threading.Lock()  # Arc<Mutex<dyn ModelPipeline>>, pipelines/mod.rs:110-113
+        self.last_cache_stats = []  # the step-cache stats of the last request (generate_tensor's cache_threshold=), one entry per denoise call
         self.scheduler = F.SchedulerConfig()
         self.t5 = self.clip = self.t5_tokenizer = self.clip_tokenizer = None
         self.source_kind = source.kind
@@ -365,7 +366,8 @@ class Pipeline:
 
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
-                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False):
+                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
+                        _cache_stats: Optional[list] = None):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -381,8 +383,17 @@ class Pipeline:
         Reference-image conditioning (`reference=`, FLUX.1 Kontext): u8 (Hr,Wr,3) / (B,Hr,Wr,3) or f32 (B,3,Hr,Wr) in [-1,1], numpy or torch, one
         image broadcast over the prompts; Hr and Wr are multiples of 16 and need not be params.height / width.  It is encoded like `image=` (posterior mean;
         diffusers' Kontext pipeline takes the mode too) and its tokens, with 1 in axis 0 of their ids, join the image tokens of every model evaluation; the
-        schedule's mu comes from the output's token count alone.  Combines with image= / strength= / mask=.  Not resized to Kontext's preferred resolutions."""
+        schedule's mu comes from the output's token count alone.  Combines with image= / strength= / mask=.  Not resized to Kontext's preferred resolutions.
+
+        First-block step cache (`cache_threshold=`; None: off, today's launches): FluxModel.denoise's cache_threshold — a step whose
+        block-0 residual moved less than the threshold since the last computed step skips the other blocks.  The decision is per denoise CALL (a chunk of up to
+        MAX_BATCH prompts reuses a step only when all its samples are under the threshold), and every call's {"decisions", "distances"} is appended to
+        `pipeline.last_cache_stats` (one entry per denoise call of the request).  No value is recommended: ParaAttention suggests 0.08 for FLUX.1-dev, which
+        this project has no real weights to verify.  Raises under sequence parallelism, like image=."""
         B = len(prompts)
+        if cache_threshold is not None:
+            F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
+        stats = [] if _cache_stats is None else _cache_stats  # one list per request, shared with the chunks it is cut into
         ids = list(sample_ids) if sample_ids is not None else [first_sample + b for b in range(B)]
         if len(ids) != B:
             raise ValueError("sample_ids must name one stream per prompt")
@@ -408,7 +419,8 @@ class Pipeline:
                     latents=None if latents is None else latents[sl], seed=seed,
                     token_ids=None if token_ids is None else (token_ids[0][sl], token_ids[1][sl]), sample_ids=ids[sl],
                     image=None if image is None else image[sl], strength=strength, mask=None if mask is None else mask[sl],
-                    reference=None if reference is None else reference[sl], return_latents=return_latents))
+                    reference=None if reference is None else reference[sl], return_latents=return_latents, cache_threshold=cache_threshold,
+                    _cache_stats=stats))
             return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
         cfg = self.flux.cfg
         dev = self.device
@@ -455,8 +467,13 @@ class Pipeline:
                                                   {k: v[:1] for k, v in context.items()})
             if sp is not None:  # every rank holds the same inputs; each denoises its token shard, then all get the latents
                 img = sp.gather(self.flux.denoise(sp.shard(img), sp.shard(img_ids), sp.shard(t5_emb), sp.shard(txt_ids), clip_emb, guidance, timesteps))
+            elif cache_threshold is not None:
+                img, st = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, cache_threshold=cache_threshold,
+                                            return_cache_stats=True)
+                stats.append(st)
             else:
                 img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context)
+            self.last_cache_stats = stats  # (under the lock) one entry per denoise call of this request so far; empty without cache_threshold=
             z = F.unpack_latents(img, 16, h, w, self.vae.scale_factor(), self.vae.shift_factor())
             u8 = F.postprocess_u8(self.vae.decode(z))
             return (u8, img) if return_latents else u8
@@ -539,15 +556,16 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                reference=None, return_latents: bool = False, **kw):
+                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
         image= / strength= / mask=: image to image and inpainting, reference=: reference-image conditioning, see generate_tensor; return_latents=True
-        returns (images, final packed latents)."""
+        returns (images, final packed latents).  cache_threshold=: the first-block step cache, see generate_tensor (None: off); each rank of a sharded batch
+        decides for its own prompts and keeps its own `last_cache_stats`."""
         from . import dist as D
         rank, world = D.world()
-        kw = dict(kw, image=image, strength=strength, mask=mask, reference=reference, return_latents=return_latents)
+        kw = dict(kw, image=image, strength=strength, mask=mask, reference=reference, return_latents=return_latents, cache_threshold=cache_threshold)
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if getattr(self, "_sp", None) is not None:  # all ranks produce every image together; rank 0 returns them
             u8 = self.generate_tensor(prompts, params, **kw)

@@ -46,6 +46,7 @@ extern "C" {
  *   Then, still 6: image to image and inpainting — fmi_preprocess_u8, fmi_latent_mask, fmi_encode_latents, fmi_scale_noise, fmi_flux_denoise_inpaint.
  *   Then, still 6: reference-image (FLUX.1 Kontext) conditioning — fmi_flux_context, fmi_flux_forward_context, fmi_flux_denoise_context, fmi_latent_ids.
  *   Then, still 6: the GEMM launcher's test seams — fmi_gemm_desc, fmi_gemm_group, fmi_splitk_resid_gate, fmi_set_gemm_kernel.
+ *   Then, still 6: the first-block step cache of the denoise loop — fmi_flux_step_cache, fmi_flux_denoise_cached, fmi_flux_step_cache_bytes.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -400,6 +401,35 @@ typedef struct fmi_flux_context {
 int fmi_flux_forward_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream);
 int fmi_flux_denoise_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
                              const float* x0, const float* noise, const float* mask, void* stream);
+
+/* First-block step cache for the denoise loop (the method of ParaAttention's FBCache / diffusers' FirstBlockCacheConfig; the reference has no
+ * counterpart).  fmi_flux_denoise_cached is fmi_flux_denoise_context — same arguments, same update and blend — with one addition.  Every step runs the input
+ * embedding and double block 0, takes the block's residual r = X1 - X0 of the f32 image stream (S' = S + R rows per sample), and measures per sample
+ *   d_b = sum |r - r_ref| / sum |r_ref|         (r_ref: the residual of the last COMPUTED step; divided on the host in double, +inf for a zero denominator)
+ * A step is reused when a computed step precedes it and force[i] == 1, or force[i] < 0 (or force NULL), threshold > 0 and EVERY sample's d_b < threshold — the
+ * decision is per call, not per sample, so a batched call under a threshold may differ from its single-sample runs (under a forced mask it does not).  A reused
+ * step adds the cached output residual of all other blocks (XF = X1 + delta) and goes straight to the final layer: it costs img_in, one double block and the final
+ * layer.  A computed step runs every block as always and refreshes delta = XF - X1 and r_ref.  Step 0 is always computed; nothing forces the last step.
+ * The distances are compared as the f32 values distances_out reports.  The sums use no atomics and a decomposition fixed by S' * D: the same bits from run to run
+ * and for any B.
+ * No threshold is recommended here: ParaAttention suggests 0.08 for FLUX.1-dev, which nothing in this project could verify (it has no real weights).
+ * cache == NULL: fmi_flux_denoise_context, launch for launch.  With a cache, every step after the first computed one makes ONE small device-to-host copy and ONE
+ * hipStreamSynchronize on `stream` (the decision is taken on the host): unlike the other loops this entry is not legal under stream capture; decisions_out and
+ * distances_out are complete when it returns (the last step's launches may still be queued, as with the other loops).  The first cached call allocates four (B,S',D) f32
+ * device buffers (regrown when a larger shape comes; fmi_flux_step_cache_bytes reports them); the other entries never allocate them.
+ * Works in the bf16, int8 and e4m3 modes, with nf4 weights and with LoRA adapters: it touches the f32 residual stream only.
+ * FMI_ERR_INVALID: threshold negative or NaN; a force entry outside -1 / 0 / 1; force[0] == 1.  FMI_ERR_UNSUPPORTED: a model without double blocks
+ * (num_layers < 1); sequence parallelism set (the distance would need an all-reduce).  FMI_ERR_STATE: while int8 calibration is recording.  All before any launch. */
+typedef struct fmi_flux_step_cache {
+  float threshold;          /* 0: never reuse by distance; > 0: reuse when every sample's distance < threshold */
+  const int8_t* force;      /* NULL or n_steps entries: -1 decide by threshold, 0 compute, 1 reuse */
+  int32_t* decisions_out;   /* NULL or n_steps: 0 computed, 1 reused (host) */
+  float* distances_out;     /* NULL or n_steps * B, step-major: d_b, -1 where not measured (host) */
+} fmi_flux_step_cache;
+int fmi_flux_denoise_cached(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx /* NULL ok */, float* img_inout, const double* timesteps_host,
+                            int n_steps, const float* x0, const float* noise, const float* mask /* all three or none */,
+                            const fmi_flux_step_cache* cache /* NULL: == fmi_flux_denoise_context */, void* stream);
+size_t fmi_flux_step_cache_bytes(fmi_flux*);
 
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
