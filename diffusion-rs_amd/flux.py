@@ -53,6 +53,13 @@ def _as_f32(t):
     return np.asarray(t, np.float32) if isinstance(t, np.ndarray) else t.to(torch.float32)
 
 
+def _like_img(t, name: str, img):
+    """One of denoise's x0 / noise / mask: shaped like img, or ValueError; contiguous f32 on img's device.  None stays None."""
+    if t is not None and tuple(t.shape) != tuple(img.shape):
+        raise ValueError(f"denoise: {name} is {tuple(t.shape)}, img is {tuple(img.shape)}")
+    return None if t is None else t.to(device=img.device, dtype=torch.float32).contiguous()
+
+
 @dataclass
 class SchedulerConfig:
     """pipelines/scheduler.rs:4-20 (public FLUX.1 values as defaults)."""
@@ -377,43 +384,25 @@ class FluxModel:
         img = img.to(torch.float32).clone().contiguous()
         inp, keep = self._inputs(None, img_ids, txt, txt_ids, None, y, guidance)
         ts = (C.c_double * len(timesteps))(*timesteps)
+        # (keep_blend and keep_ctx, like keep, hold the tensors behind the pointers until the call has returned)
+        keep_blend = [_like_img(t, nm, img) for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask"))]
         has_ctx = context is not None or context_ids is not None
+        ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
+        blend = [_ptr(t) for t in keep_blend]  # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
         if thr is not None:
-            extra = []
-            for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask")):
-                if t is not None:
-                    if tuple(t.shape) != tuple(img.shape):
-                        raise ValueError(f"denoise: {nm} is {tuple(t.shape)}, img is {tuple(img.shape)}")
-                    t = t.to(device=img.device, dtype=torch.float32).contiguous()
-                extra.append(t)
-            ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
-            B = int(img_ids.shape[0])
             decisions = np.zeros(max(n_steps, 0), np.int32)
-            distances = np.full((max(n_steps, 0), B), -1.0, np.float32)
+            distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             sc = L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
                                  decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float)))
-            L.check(self.lib.fmi_flux_denoise_cached(self.h, C.byref(inp), C.byref(ctx) if ctx is not None else None, _ptr(img), ts, n_steps, _ptr(extra[0]),
-                                                     _ptr(extra[1]), _ptr(extra[2]), C.byref(sc), _stream()), self.lib)
-            return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
-        if not has_ctx and x0 is None and noise is None and mask is None:
-            L.check(self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _stream()), self.lib)
-            return img
-        extra = []
-        for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask")):
-            if t is not None:
-                if tuple(t.shape) != tuple(img.shape):
-                    raise ValueError(f"denoise: {nm} is {tuple(t.shape)}, img is {tuple(img.shape)}")
-                t = t.to(device=img.device, dtype=torch.float32).contiguous()
-            extra.append(t)
-        # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
-        if not has_ctx:
-            L.check(self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
-                                                      _stream()), self.lib)
+            st = self.lib.fmi_flux_denoise_cached(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, _ptr(img), ts, n_steps, *blend, C.byref(sc), _stream())
+        elif has_ctx:
+            st = self.lib.fmi_flux_denoise_context(self.h, C.byref(inp), C.byref(ctx), _ptr(img), ts, n_steps, *blend, _stream())
+        elif any(t is not None for t in (x0, noise, mask)):
+            st = self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, n_steps, *blend, _stream())
         else:
-            ctx, keep_ctx = self._context(img_ids, context, context_ids)  # (held until the call has returned)
-            L.check(self.lib.fmi_flux_denoise_context(self.h, C.byref(inp), C.byref(ctx), _ptr(img), ts, len(timesteps) - 1, _ptr(extra[0]), _ptr(extra[1]),
-                                                      _ptr(extra[2]), _stream()), self.lib)
-        return img
+            st = self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, n_steps, _stream())
+        L.check(st, self.lib)
+        return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
 
     def step_cache_bytes(self) -> int:
         """Device bytes the step cache holds: 0 until the first denoise with cache_threshold= / cache_force= (the plain loops never allocate it)."""

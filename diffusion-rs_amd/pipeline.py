@@ -27,7 +27,7 @@ import os
 import struct
 import threading
 import zlib
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -159,6 +159,45 @@ def check_reference(t: torch.Tensor, B: int) -> torch.Tensor:
     if t.shape[0] not in (1, B):
         raise ValueError(f"reference holds {t.shape[0]} samples for {B} prompts (one is broadcast)")
     return t
+
+
+def _rows(x, idx):
+    """Rows `idx` (a slice or a list of ints) of one per-sample input: a tensor, a numpy array, a list, or a pair (tuple) of those; None stays None."""
+    if x is None:
+        return None
+    if isinstance(x, tuple):
+        return tuple(_rows(m, idx) for m in x)
+    if isinstance(idx, slice) or isinstance(x, np.ndarray):
+        return x[idx]
+    return x[torch.as_tensor(idx, dtype=torch.long)] if isinstance(x, torch.Tensor) else [x[i] for i in idx]
+
+
+@dataclass
+class _Samples:
+    """The inputs of a request that hold one row per prompt — everything else of it (params, seed, strength, return_latents, cache_threshold) is shared by
+    its prompts.  Chunking, the sequence-parallel split, rank sharding and the int8 calibration sample all select rows through take(), which walks
+    these fields: a new per-sample input is one field here and one use in Pipeline._generate_chunk."""
+    prompts: list
+    sample_ids: list  # the Philox stream of each sample
+    embeddings: Optional[tuple] = None  # (t5_emb, clip_emb)
+    token_ids: Optional[tuple] = None  # (t5_ids, clip_ids)
+    latents: Optional[torch.Tensor] = None
+    image: Optional[torch.Tensor] = None  # in device form (Pipeline._source_image), like mask and reference
+    mask: Optional[torch.Tensor] = None
+    reference: Optional[torch.Tensor] = None
+
+    def take(self, idx) -> "_Samples":
+        return _Samples(**{f.name: _rows(getattr(self, f.name), idx) for f in fields(self)})
+
+    def kwargs(self) -> dict:
+        """generate_tensor's keyword arguments (the prompts are its first positional one)."""
+        return {f.name: getattr(self, f.name) for f in fields(self) if f.name != "prompts"}
+
+
+def _index_sets(B: int, max_batch: int, one_by_one: bool) -> list:
+    """The row sets a request of any B runs in (pipelines/mod.rs:241-270): chunks of max_batch, or single samples (sequence parallel: ONE image at a time)."""
+    n = 1 if one_by_one else max_batch
+    return [slice(a, a + n) for a in range(0, B, n)]
 
 
 class Pipeline:
@@ -366,8 +405,7 @@ class Pipeline:
 
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
-                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        _cache_stats: Optional[list] = None):
+                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -390,50 +428,49 @@ class Pipeline:
         MAX_BATCH prompts reuses a step only when all its samples are under the threshold), and every call's {"decisions", "distances"} is appended to
         `pipeline.last_cache_stats` (one entry per denoise call of the request).  No value is recommended: ParaAttention suggests 0.08 for FLUX.1-dev, which
         this project has no real weights to verify.  Raises under sequence parallelism, like image=."""
-        B = len(prompts)
         if cache_threshold is not None:
             F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
-        stats = [] if _cache_stats is None else _cache_stats  # one list per request, shared with the chunks it is cut into
-        ids = list(sample_ids) if sample_ids is not None else [first_sample + b for b in range(B)]
-        if len(ids) != B:
-            raise ValueError("sample_ids must name one stream per prompt")
-        if B == 0:
+        s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
+                          mask=mask, reference=reference)
+        if not s.prompts:
             u8 = torch.empty((0, 3, params.height, params.width), dtype=torch.uint8, device=self.device)
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
-        image, mask = self._source_image(image, mask, strength, B, params)
-        reference = self._reference_image(reference, B)
-        sp = getattr(self, "_sp", None)
-        if sp is not None and B > 1:  # sequence parallel: the ranks of the group work on ONE image at a time
-            outs = [self.generate_tensor(
-                prompts[b:b + 1], params, embeddings=None if embeddings is None else (embeddings[0][b:b + 1], embeddings[1][b:b + 1]),
-                latents=None if latents is None else latents[b:b + 1], seed=seed, return_latents=return_latents,
-                token_ids=None if token_ids is None else (token_ids[0][b:b + 1], token_ids[1][b:b + 1]), sample_ids=ids[b:b + 1]) for b in range(B)]
-            return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
-        if B > self.MAX_BATCH:  # the reference accepts any batch (pipelines/mod.rs:241-270)
-            outs = []
-            for a in range(0, B, self.MAX_BATCH):
-                sl = slice(a, a + self.MAX_BATCH)
-                outs.append(self.generate_tensor(
-                    prompts[sl], params, embeddings=None if embeddings is None else (embeddings[0][sl], embeddings[1][sl]),
-                    latents=None if latents is None else latents[sl], seed=seed,
-                    token_ids=None if token_ids is None else (token_ids[0][sl], token_ids[1][sl]), sample_ids=ids[sl],
-                    image=None if image is None else image[sl], strength=strength, mask=None if mask is None else mask[sl],
-                    reference=None if reference is None else reference[sl], return_latents=return_latents, cache_threshold=cache_threshold,
-                    _cache_stats=stats))
-            return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
+        stats = []  # one list per request, shared by the chunks it is cut into
+        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats)
+                for idx in _index_sets(len(s.prompts), self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
+        if len(outs) == 1:
+            return outs[0]
+        return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
+
+    def _samples(self, prompts, params, strength, first_sample=0, sample_ids=None, **given) -> _Samples:
+        """A request's per-sample inputs (`given`: the other fields of _Samples as the caller passed them), checked and normalised once: the pairs as tuples,
+        image / mask / reference in device form with a single one broadcast over the prompts."""
+        B = len(prompts)
+        s = _Samples(list(prompts), list(sample_ids) if sample_ids is not None else [first_sample + b for b in range(B)], **given)
+        if len(s.sample_ids) != B:
+            raise ValueError("sample_ids must name one stream per prompt")
+        s.embeddings, s.token_ids = (None if pair is None else tuple(pair) for pair in (s.embeddings, s.token_ids))
+        if B > 0:  # (an empty request returns before any image check)
+            s.image, s.mask = self._source_image(s.image, s.mask, strength, B, params)
+            s.reference = self._reference_image(s.reference, B)
+        return s
+
+    def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats):
+        """One denoise call: at most MAX_BATCH samples (one under sequence parallelism) of a normalised request.  Returns what generate_tensor does."""
         cfg = self.flux.cfg
         dev = self.device
+        sp = getattr(self, "_sp", None)
+        B, ids, latents = len(s.prompts), s.sample_ids, s.latents
         with self._lock:  # the whole forward, text encoders included, like the reference's mutex (pipelines/mod.rs:247)
-            if embeddings is not None:
-                t5_emb, clip_emb = embeddings
-                t5_emb, clip_emb = t5_emb.to(dev), clip_emb.to(dev)
+            if s.embeddings is not None:
+                t5_emb, clip_emb = (e.to(dev) for e in s.embeddings)
             elif self.t5 is not None and self.clip is not None:
-                t5_emb, clip_emb = self.encode_prompts(prompts, token_ids)
+                t5_emb, clip_emb = self.encode_prompts(s.prompts, s.token_ids)
             elif self.source_kind == "synthetic":
                 # schnell pads T5 ids to 256 (flux/mod.rs:243-253); dev uses the prompt length — 512 here
                 T = 256 if not self.flux.is_guidance() else 512
-                t5_emb, clip_emb = placeholder_embeddings(prompts, T, cfg["joint_attention_dim"], cfg["pooled_projection_dim"], dev)
+                t5_emb, clip_emb = placeholder_embeddings(s.prompts, T, cfg["joint_attention_dim"], cfg["pooled_projection_dim"], dev)
             else:
                 raise F.L.FmiError("this checkpoint was loaded without text encoders: pass embeddings=(t5_emb, clip_emb)")
             h = (params.height + 15) // 16 * 2  # get_noise, flux/sampling.rs:12-13
@@ -451,28 +488,28 @@ class Pipeline:
             timesteps = self.scheduler.get_timesteps(params.num_steps, mu)
             guidance = torch.full((B,), float(params.guidance_scale), dtype=torch.float32, device=dev) if self.flux.is_guidance() else None
             inpaint = {}
-            if image is not None:  # start from the source noised to the cut schedule's first value (at strength 1 that is the noise itself, bit for bit)
-                x0, _ = F.encode_latents(self.vae.encode(image), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
+            if s.image is not None:  # start from the source noised to the cut schedule's first value (at strength 1 that is the noise itself, bit for bit)
+                x0, _ = F.encode_latents(self.vae.encode(s.image), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
                 timesteps = img2img_timesteps(timesteps, strength)
                 noise = img
                 img = F.scale_noise(x0, noise, timesteps[0])
-                if mask is not None:
-                    inpaint = dict(x0=x0, noise=noise, mask=F.latent_mask(mask, x0.shape[2] // 4))
+                if s.mask is not None:
+                    inpaint = dict(x0=x0, noise=noise, mask=F.latent_mask(s.mask, x0.shape[2] // 4))
             context = {}
-            if reference is not None:  # its packed latents are rows of every evaluation, never of the state; mu and the schedule above know S only
-                ctx, _ = F.encode_latents(self.vae.encode(reference), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
-                context = dict(context=ctx, context_ids=F.latent_ids(B, reference.shape[2] // 16, reference.shape[3] // 16, id0=1.0, device=dev))
+            if s.reference is not None:  # its packed latents are rows of every evaluation, never of the state; mu and the schedule above know S only
+                ctx, _ = F.encode_latents(self.vae.encode(s.reference), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
+                context = dict(context=ctx, context_ids=F.latent_ids(B, s.reference.shape[2] // 16, s.reference.shape[3] // 16, id0=1.0, device=dev))
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
             if sp is not None:  # every rank holds the same inputs; each denoises its token shard, then all get the latents
                 img = sp.gather(self.flux.denoise(sp.shard(img), sp.shard(img_ids), sp.shard(t5_emb), sp.shard(txt_ids), clip_emb, guidance, timesteps))
-            elif cache_threshold is not None:
-                img, st = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, cache_threshold=cache_threshold,
-                                            return_cache_stats=True)
-                stats.append(st)
             else:
-                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context)
+                cache = {} if cache_threshold is None else dict(cache_threshold=cache_threshold, return_cache_stats=True)
+                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, **cache)
+                if cache:
+                    img, st = img
+                    stats.append(st)
             self.last_cache_stats = stats  # (under the lock) one entry per denoise call of this request so far; empty without cache_threshold=
             z = F.unpack_latents(img, 16, h, w, self.vae.scale_factor(), self.vae.shift_factor())
             u8 = F.postprocess_u8(self.vae.decode(z))
@@ -565,57 +602,31 @@ class Pipeline:
         decides for its own prompts and keeps its own `last_cache_stats`."""
         from . import dist as D
         rank, world = D.world()
-        kw = dict(kw, image=image, strength=strength, mask=mask, reference=reference, return_latents=return_latents, cache_threshold=cache_threshold)
+        shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
+        per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
-        if getattr(self, "_sp", None) is not None:  # all ranks produce every image together; rank 0 returns them
-            u8 = self.generate_tensor(prompts, params, **kw)
-            if return_latents:
-                u8, final = u8
-            if rank != 0:
-                return None
-        elif world > 1:
-            n = len(prompts)
+        if world > 1 and getattr(self, "_sp", None) is None:
             if return_latents:
                 raise ValueError("return_latents= is not gathered across ranks: call generate_tensor on the rank that holds the sample")
-            if n > 0:  # batched device tensors, so that a rank picks its rows of them exactly as it picks its rows of `latents`
-                kw["image"], kw["mask"] = self._source_image(image, mask, strength, n, params)
-                kw["reference"] = self._reference_image(reference, n)
-            if getattr(self, "_int8_pending", False) and n > 0:
-                # every rank calibrates on the SAME sample — global sample 0 of this request — so that all ranks hold the same int8 weights and an image does
-                # not depend on the rank that produced it (one extra image per rank, once per model)
-                sub = dict(kw)
-                for key in ("embeddings", "token_ids"):
-                    if sub.get(key) is not None:
-                        sub[key] = tuple(t[:1] for t in sub[key])
-                for key in ("latents", "image", "mask", "reference"):
-                    if sub.get(key) is not None:
-                        sub[key] = sub[key][:1]
-                first = sub.pop("first_sample", 0)
-                self.generate_tensor(prompts[:1], params, sample_ids=[first], **sub)
-
-            def pick(x, ids):
-                return None if x is None else x[torch.as_tensor(ids, dtype=torch.long)] if isinstance(x, torch.Tensor) else [x[i] for i in ids]
+            # normalised once (batched device tensors), so that a rank takes its rows of an image exactly as it takes its rows of `latents`
+            s = self._samples(prompts, params, strength, **per_sample)
 
             def run_local(my_prompts, ids):
-                sub = dict(kw)
-                for key in ("embeddings", "token_ids"):
-                    if sub.get(key) is not None:
-                        sub[key] = tuple(pick(t, ids) for t in sub[key])
-                for key in ("latents", "image", "mask", "reference"):
-                    if sub.get(key) is not None:
-                        sub[key] = pick(sub[key], ids)
-                first = sub.pop("first_sample", 0)
-                return self.generate_tensor(my_prompts, params, sample_ids=[first + i for i in ids], **sub)
+                return self.generate_tensor(my_prompts, params, **s.take(ids).kwargs(), **shared)
 
+            if getattr(self, "_int8_pending", False) and s.prompts:
+                # every rank calibrates on the SAME sample — global sample 0 of this request — so that all ranks hold the same int8 weights and an image does
+                # not depend on the rank that produced it (one extra image per rank, once per model)
+                run_local(s.prompts[:1], [0])
             u8 = D.generate_sharded(prompts, run_local,
                                     empty=lambda: torch.empty((0, 3, params.height, params.width), dtype=torch.uint8, device=self.device))
-            if rank != 0:
-                return None
-            assert u8.shape[0] == n
-        else:
-            u8 = self.generate_tensor(prompts, params, **kw)
+            assert rank != 0 or u8.shape[0] == len(prompts)
+        else:  # one process, or sequence parallel: all ranks produce every image together
+            u8 = self.generate_tensor(prompts, params, **per_sample, **shared)
             if return_latents:
                 u8, final = u8
+        if rank != 0:  # rank 0 returns the images
+            return None
         if output == "tensor":
             out = u8
         else:

@@ -80,9 +80,14 @@ def _worker(rank, world, port, n_prompts, q):
         def __init__(self):  # no GPU: only forward()'s sharding / gather logic is under test
             self.device = torch.device("cpu")
             self.calls = []
+            self.rows_checked = 0
 
         def generate_tensor(self, my_prompts, params, *, embeddings=None, latents=None, seed=None, sample_ids=None, **kw):
             self.calls.append((list(my_prompts), list(sample_ids)))
+            for x in (latents, *(kw.get("token_ids") or ()), kw.get("image"), kw.get("mask"), kw.get("reference")):
+                if x is not None:  # every per-sample input followed the shard: row j holds the global index of this rank's sample j, all over
+                    assert [[float(v) for v in torch.as_tensor(r).unique()] for r in x] == [[float(i - 100)] for i in sample_ids]
+                    self.rows_checked += 1
             assert embeddings is None or embeddings[0].shape[0] == len(my_prompts)
             e = torch.zeros(len(my_prompts)) if embeddings is None else embeddings[0][:, 0]
             return torch.stack([torch.full((3, params.height, params.width), (7 * i + len(p) + int(e[j])) % 256, dtype=torch.uint8)
@@ -95,6 +100,14 @@ def _worker(rank, world, port, n_prompts, q):
     assert (fwd is None) == (rank != 0)
     assert sp.calls == ([([prompts[i] for i in fd.shard_indices(n_prompts, rank, world)], [100 + i for i in fd.shard_indices(n_prompts, rank, world)])]
                         if fd.shard_indices(n_prompts, rank, world) else [])
+    # ... and with them the rows of every other per-sample input (row i holds the value i); a single image would be broadcast first
+    my_ids = fd.shard_indices(n_prompts, rank, world)
+    ramp = lambda *trailing: torch.arange(n_prompts, dtype=torch.float32).reshape(n_prompts, *[1] * len(trailing)).expand(n_prompts, *trailing).clone()
+    fwd16 = sp.forward(prompts, pl.DiffusionGenerationParams(16, 16, 2, 3.5), output="tensor", first_sample=100, latents=ramp(16, 2, 2),
+                       token_ids=(ramp(7).to(torch.int32).numpy(), ramp(3).to(torch.int32).tolist()), image=ramp(3, 16, 16), mask=ramp(16, 16),
+                       reference=ramp(3, 32, 16))
+    assert (fwd16 is None) == (rank != 0) and (rank != 0 or fwd16.shape == (n_prompts, 3, 16, 16))
+    assert sp.calls[1:] == ([([prompts[i] for i in my_ids], [100 + i for i in my_ids])] if my_ids else []) and sp.rows_checked == (6 if my_ids else 0)
 
     # 5. Ulysses head redistribution: scatter tokens->heads, "attention" as a per-head reduction over all tokens, gather back
     H, d, n_tok = 4, 8, 11  # 11 tokens over 2 ranks: ragged (6 + 5)
