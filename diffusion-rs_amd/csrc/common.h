@@ -482,11 +482,14 @@ int launch_timestep_embedding(const float* t, int B, int dim, float* out, hipStr
 int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hipStream_t stream);
 // per-sample strided cast: n contiguous elements of sample b at src + b * src_bs (F32 | BF16) -> bf16 at dst + b * dst_bs, one launch (small_ops.hip)
-int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream);
+int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream, int B_src = 0);
 int launch_silu_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream);
 // the masked (inpainting) step: img = mask * (img + pred * dt) + (1 - mask) * ((1 - s) * x0 + s * noise), one pass (small_ops.hip)
 int launch_euler_blend(float* img, const float* pred, const float* x0, const float* noise, const float* mask, float dt, float s, int64_t n, hipStream_t stream);
+// the true-CFG step: g = neg + scale * (pos - neg), img = img + g * dt — or, with x0 / noise / mask (all three or none), launch_euler_blend's blend of that — one pass
+int launch_euler_cfg(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0 = nullptr,
+                     const float* noise = nullptr, const float* mask = nullptr, float s = 0.f);
 int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, float* out, hipStream_t stream);  // out = (1 - t) * x0 + t * noise
 int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int N, hipStream_t stream);  // y[r] = (y[r] + g[r % B]) + v[r % B] (g may be null)
 // split-K reduce: out[m][n] += gate_b[n] * (part_0 + part_1 + ... + part_{S-1} + bias[n]), the parts added in index order

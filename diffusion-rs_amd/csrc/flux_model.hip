@@ -145,6 +145,7 @@ struct fmi_flux {
   // taken; the residual r and the reference residual r_ref, swapped by index on computed steps; the output delta — plus the reduction's partials and sums.
   // Allocated by the first cached call, regrown like mod_steps, never touched by the plain entries.
   DeviceBuffer sc_x0, sc_r[2], sc_delta, sc_part, sc_sums;
+  DeviceBuffer cfg_gd;  // true CFG: the guidance vector once for each half of the 2B batch, 8 floats, allocated by the first fmi_flux_denoise_cfg call
   size_t sc_elems = 0, sc_part_floats = 0;
   double* sc_host = nullptr;  // pinned: (num, den) per sample, read by the host after the per-step synchronisation
   bool fuse_qkv_relayout = true;  // QkNorm + RoPE + head/transposed relayout in the QKV GEMM's epilogue
@@ -433,6 +434,7 @@ int finalize(fmi_flux* m) {
   return FMI_OK;
 }
 
+constexpr int PE_ROW_FLOATS = 128;  // one position of the RoPE table: 64 (cos, sin) pairs — the head dim fmi_flux_create checks axes_dim against
 int ensure_workspace(fmi_flux* m, int B, int S, int T) {
   auto& w = m->ws;
   if (w.base && w.B == B && w.S == S && w.T == T) return FMI_OK;
@@ -463,7 +465,7 @@ int ensure_workspace(fmi_flux* m, int B, int S, int T) {
   add((void**)&w.temb, (size_t)B * 256 * 4);
   add((void**)&w.h1, (size_t)B * D * 4);
   add((void**)&w.yf, (size_t)B * P * 4);
-  add((void**)&w.pe, (size_t)B * L * 64 * 2 * 4);
+  add((void**)&w.pe, (size_t)B * L * PE_ROW_FLOATS * 4);
   add((void**)&w.img_f32, (size_t)B * S * C * 4);
   add((void**)&w.pred_tmp, (size_t)B * S * C * 4);
   add((void**)&w.tv, 4096 * 4);
@@ -833,16 +835,28 @@ int use_device(const fmi_flux* m) { return use_device_ordinal(m->device); }
 
 // Everything of Flux::forward that does not depend on the timestep: input casts + RoPE table.
 // R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
-int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s) {
+// cfg (true CFG): `in` is the loop's internal batch of 2 * Bs samples whose txt / y / ids / context pointers are the caller's Bs samples'; the
+// negative's txt and y fill the second halves, and samples Bs .. 2 Bs - 1 take the table and the context rows of samples 0 .. Bs - 1.  Null: nothing changes.
+int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s, const fmi_flux_true_cfg* cfg = nullptr) {
   auto& w = m->ws;
-  const int B = in->B, S = in->S, T = in->T, C = m->cfg.in_channels;
+  const int B = in->B, Bs = cfg ? B / 2 : B, S = in->S, T = in->T, C = m->cfg.in_channels;
+  const int64_t n_txt = (int64_t)Bs * T * m->cfg.joint_attention_dim, n_y = (int64_t)Bs * m->cfg.pooled_projection_dim;
   PhaseTimer pt(m, s, PH_EMBED);
-  FMI_TRY(launch_cast_to_bf16(in->txt, in->txt_dtype, w.txt_bf, (int64_t)B * T * m->cfg.joint_attention_dim, s));
-  FMI_TRY(launch_cast_to_f32(in->y, in->y_dtype, w.yf, (int64_t)B * m->cfg.pooled_projection_dim, s));
+  FMI_TRY(launch_cast_to_bf16(in->txt, in->txt_dtype, w.txt_bf, n_txt, s));
+  FMI_TRY(launch_cast_to_f32(in->y, in->y_dtype, w.yf, n_y, s));
+  if (cfg) {
+    FMI_TRY(launch_cast_to_bf16(cfg->neg_txt, cfg->neg_txt_dtype, w.txt_bf + n_txt, n_txt, s));
+    FMI_TRY(launch_cast_to_f32(cfg->neg_y, cfg->neg_y_dtype, w.yf + n_y, n_y, s));
+  }
   // pe = EmbedNd(cat([txt_ids, img_ids], 1)) (model.rs:807-810); one table per batch element
-  if (!R) return launch_rope_table(in->txt_ids, in->img_ids, in->ids_per_sample ? B : 1, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s);
-  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, in->ids_per_sample ? B : 1, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s, ctx->ctx_ids, R));
-  return launch_cast_rows_bf16(ctx->ctx, ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s);
+  const int tables = in->ids_per_sample ? Bs : 1;
+  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, tables, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s, R ? ctx->ctx_ids : nullptr, R));
+  if (cfg && in->ids_per_sample) {
+    const size_t half = (size_t)Bs * (T + S + R) * PE_ROW_FLOATS;
+    FMI_HIP_TRY(hipMemcpyAsync(w.pe + half, w.pe, half * 4, hipMemcpyDeviceToDevice, s));
+  }
+  if (!R) return FMI_OK;
+  return launch_cast_rows_bf16(ctx->ctx, ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s, Bs);
 }
 // The context of an evaluation, validated: R rows per sample (0: none, the text-to-image launches)
 int context_rows(const fmi_flux* m, const fmi_flux_context* ctx, int* R) {
@@ -945,14 +959,16 @@ int step_cache_decide(fmi_flux* m, StepCacheRun* sc, int B, int S, int T, hipStr
 // mod_pre: this step's (B, n_mod) modulation vectors if the caller precomputed them (fmi_flux_denoise), else null.
 // txt_pre: txt_in(txt) if the caller computed it once for all steps (fmi_flux_denoise: it does not depend on the latent or on t), else null.
 // sc: the step cache of a fmi_flux_denoise_cached call, else null — and with null every launch below is the one it always was.
+// Bs: samples of img_f32 when they are fewer than in->B (true CFG, DESIGN.md 4.12: sample b of the operand is the state's sample b % Bs), else 0 — the
+// input assembly is all that knows.
 int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, const float* timesteps_dev, float* pred, hipStream_t s,
-                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0, StepCacheRun* sc = nullptr) {
+                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0, StepCacheRun* sc = nullptr, int Bs = 0) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
   const int B = in->B, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
   const int D = m->D, Mh = m->M, H = m->H, C = c.in_channels;
   const int nmod = (int)m->n_mod;
-  const int64_t pe_bs = in->ids_per_sample ? (int64_t)L * 128 : 0;
+  const int64_t pe_bs = in->ids_per_sample ? (int64_t)L * PE_ROW_FLOATS : 0;
   const float att_scale = 1.0f / sqrtf(128.0f);
   const bool fp8 = m->fp8;
   const int qk = m->q8_kind;  // 1 e4m3, 2 int8
@@ -971,7 +987,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
 
   {
     PhaseTimer pt(m, s, PH_EMBED);
-    if (R) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s));  // the state rows into their places
+    if (R || Bs) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s, Bs));  // the state rows into their places
     else FMI_TRY(launch_cast_to_bf16(img_f32, FMI_F32, w.img_bf, (int64_t)B * S * C, s));
     if (!mod_pre) FMI_TRY(compute_vec(m, in, timesteps_dev, w.vec, s));
     // img = img_in(img), txt = txt_in(txt)   (model.rs:811-812) -> f32 residual streams
@@ -1537,14 +1553,35 @@ extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* p
 // launches with the per-step update replaced by the masked one (launch_euler_blend); nothing before or inside the model evaluation knows the difference.
 // ctx: the reference-image rows every evaluation appends to the state's (fmi_flux_denoise_context); the state, the update and the blend stay (B,S,C).
 // cache: fmi_flux_denoise_cached's first-block step cache, null for every other entry — which then issue exactly the launches they always did.
-static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
-                        const float* x0, const float* noise, const float* mask, void* stream, const fmi_flux_step_cache* cache = nullptr) {
-  FMI_TRY(check_inputs(m, in));
+// cfg: fmi_flux_denoise_cfg's negative prompt, null for every other entry, likewise.  With it `in` below is the loop's own batch of 2 * Bs samples
+// — the prompt's rows, then the negative's — and only the input assembly (prepare_static, forward_core's state cast) and the update (launch_euler_cfg) know.
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
+                        const float* x0, const float* noise, const float* mask, void* stream, const fmi_flux_step_cache* cache = nullptr,
+                        const fmi_flux_true_cfg* cfg = nullptr) {
+  FMI_TRY(check_inputs(m, in_caller));
   if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
   int Rc = 0;  // context rows per sample
   FMI_TRY(context_rows(m, ctx, &Rc));
   hipStream_t s = (hipStream_t)stream;
+  const int Bs = in_caller->B;  // the state's samples
+  fmi_flux_inputs in_cfg;
+  const fmi_flux_inputs* in = in_caller;
+  if (cfg) {  // every refusal comes before the first launch
+    if (cache) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: true CFG is not combined with the step cache");
+    if (!cfg->neg_txt || !cfg->neg_y) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: neg_txt and neg_y are required");
+    if ((cfg->neg_txt_dtype != FMI_F32 && cfg->neg_txt_dtype != FMI_BF16) || (cfg->neg_y_dtype != FMI_F32 && cfg->neg_y_dtype != FMI_BF16))
+      return fail(FMI_ERR_INVALID, "flux_denoise_cfg: neg_txt_dtype and neg_y_dtype must be F32 or BF16");
+    if (!(cfg->scale >= 0.f) || std::isinf(cfg->scale)) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: scale must be finite and >= 0");
+    if (Bs > 4) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: B > 4 not supported (the loop evaluates 2 B samples; the per-device limit is 8)");
+    if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: true CFG is not supported under sequence parallelism (it runs B = 1)");
+    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise_cfg: not while int8 calibration is recording");
+    if (m->cfg.guidance_embeds && !in_caller->guidance) return fail(FMI_ERR_INVALID, "flux: guidance_embeds model needs a guidance vector");
+    in_cfg = *in_caller;
+    in_cfg.B = 2 * Bs;
+    in = &in_cfg;
+  }
   const int B = in->B;
+  if ((int64_t)n_steps * B > 4096) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: n_steps * B > 4096 (ws.tv holds 4096 rows; true CFG counts 2 B)");  // before any launch
   StepCacheRun sc_run, *sc = nullptr;
   if (cache) {  // every refusal comes before the first launch
     if (!(cache->threshold >= 0.f)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: threshold must be >= 0 (and not NaN)");
@@ -1569,10 +1606,15 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_c
     sc = &sc_run;
   }
   FMI_TRY(ensure_workspace(m, B, in->S + Rc, in->T));
-  FMI_TRY(prepare_static(m, in, ctx, Rc, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
-  const int64_t n = (int64_t)B * in->S * m->cfg.in_channels;
+  if (cfg && in->guidance) {  // the same guidance in both halves
+    if (!m->cfg_gd) FMI_HIP_TRY(m->cfg_gd.alloc(8 * sizeof(float)));  // (2 Bs <= 8; the other entries never allocate it)
+    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>(), in_caller->guidance, (size_t)Bs * 4, hipMemcpyDeviceToDevice, s));
+    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>() + Bs, in_caller->guidance, (size_t)Bs * 4, hipMemcpyDeviceToDevice, s));
+    in_cfg.guidance = m->cfg_gd.as<float>();
+  }
+  FMI_TRY(prepare_static(m, in, ctx, Rc, s, cfg));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
+  const int64_t n = (int64_t)Bs * in->S * m->cfg.in_channels;
   // t_vec = full(1f32, B) * t_curr  (sampling.rs:35,42): all steps' vectors uploaded once
-  if ((int64_t)n_steps * B > 4096) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: n_steps * B > 4096");
   std::vector<float> tv((size_t)(n_steps > 0 ? n_steps : 1) * B);
   for (int i = 0; i < n_steps; ++i)
     for (int b = 0; b < B; ++b) tv[(size_t)i * B + b] = 1.0f * (float)timesteps_host[i];
@@ -1623,10 +1665,13 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_c
     txt_pre = m->ws.x_txt0;
   }
   for (int i = 0; i < n_steps; ++i) {
-    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc, sc));
+    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc, sc,
+                         cfg ? Bs : 0));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
-    if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
+    if (cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
+      FMI_TRY(launch_euler_cfg(img_inout, m->ws.pred_tmp, m->ws.pred_tmp + n, cfg->scale, dt, n, s, x0, noise, mask, (float)timesteps_host[i + 1]));
+    else if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
       FMI_TRY(launch_euler_blend(img_inout, m->ws.pred_tmp, x0, noise, mask, dt, (float)timesteps_host[i + 1], n, s));
     else
       FMI_TRY(launch_euler_update(img_inout, m->ws.pred_tmp, dt, n, s));
@@ -1656,6 +1701,12 @@ extern "C" int fmi_flux_denoise_cached(fmi_flux* m, const fmi_flux_inputs* in, c
                                        int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream) {
   if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: x0, noise and mask go together (all three or none)");
   return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, cache);
+}
+// The loop of fmi_flux_denoise_context with a negative prompt (true CFG); a null cfg IS fmi_flux_denoise_context.
+extern "C" int fmi_flux_denoise_cfg(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_true_cfg* cfg, float* img_inout,
+                                    const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
+  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: x0, noise and mask go together (all three or none)");
+  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, nullptr, cfg);
 }
 // device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
 extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {

@@ -194,6 +194,31 @@ __global__ __launch_bounds__(256) void euler_blend_kernel(V* img, const V* __res
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     img[i] = euler_blend1(img[i], pred[i], x0[i], noise[i], mask[i], dt, a, s);
 }
+// The true-CFG step: g = neg + scale * (pos - neg) — the difference first, diffusers' expression: pos == neg or scale == 0 gives neg bit
+// for bit, contracted or not — then launch_euler_update's e = img + g * dt, or with BLEND euler_blend1 on g: both forms unchanged.
+template <bool BLEND>
+__device__ __forceinline__ float euler_cfg1(float img, float pos, float neg, float x0, float noise, float m, float scale, float dt, float a, float s) {
+  const float d = pos - neg;
+  const float g = neg + scale * d;
+  if constexpr (BLEND) return euler_blend1(img, g, x0, noise, m, dt, a, s);
+  return img + g * dt;
+}
+template <bool BLEND>
+__device__ __forceinline__ float4 euler_cfg1(float4 img, float4 pos, float4 neg, float4 x0, float4 noise, float4 m, float scale, float dt, float a, float s) {
+  return make_float4(euler_cfg1<BLEND>(img.x, pos.x, neg.x, x0.x, noise.x, m.x, scale, dt, a, s), euler_cfg1<BLEND>(img.y, pos.y, neg.y, x0.y, noise.y, m.y, scale, dt, a, s),
+                     euler_cfg1<BLEND>(img.z, pos.z, neg.z, x0.z, noise.z, m.z, scale, dt, a, s), euler_cfg1<BLEND>(img.w, pos.w, neg.w, x0.w, noise.w, m.w, scale, dt, a, s));
+}
+// V as in euler_blend_kernel; BLEND = false never touches x0 / noise / mask (null then).  img is read and written at the same index only.
+template <typename V, bool BLEND>
+__global__ __launch_bounds__(256) void euler_cfg_kernel(V* img, const V* __restrict__ pos, const V* __restrict__ neg, const V* __restrict__ x0,
+                                                        const V* __restrict__ noise, const V* __restrict__ mask, float scale, float dt, float a, float s, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (BLEND)
+      img[i] = euler_cfg1<true>(img[i], pos[i], neg[i], x0[i], noise[i], mask[i], scale, dt, a, s);
+    else
+      img[i] = euler_cfg1<false>(img[i], pos[i], neg[i], V{}, V{}, V{}, scale, dt, a, s);
+  }
+}
 template <typename V>
 __global__ __launch_bounds__(256) void scale_noise_kernel(const V* __restrict__ x0, const V* __restrict__ noise, float a, float t, V* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = lerp_at(a, x0[i], t, noise[i]);
@@ -221,6 +246,28 @@ int launch_euler_blend(float* img, const float* pred, const float* x0, const flo
   FMI_LAUNCH_CHECK();
   return FMI_OK;
 }
+// The true-CFG step in one pass (three f32 reads and one write per element, six reads with the blend):
+//   g = neg + scale * (pos - neg);  e = img + g * dt;  img = e, or with x0 / noise / mask (all three or none) launch_euler_blend's mask * e + (1 - mask) * k
+int launch_euler_cfg(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0, const float* noise,
+                     const float* mask, float s) {
+  if (n <= 0) return FMI_OK;
+  const bool blend = x0 && noise && mask;
+  if (!blend && (x0 || noise || mask)) return fail(FMI_ERR_INVALID, "euler_cfg: x0, noise and mask go together (all three or none)");
+  const float a = 1.0f - s;
+  const bool v4 = n % 4 == 0 && aligned16(img) && aligned16(pos) && aligned16(neg) && (!blend || (aligned16(x0) && aligned16(noise) && aligned16(mask)));
+  const float4 *p4 = reinterpret_cast<const float4*>(pos), *n4 = reinterpret_cast<const float4*>(neg), *x4 = reinterpret_cast<const float4*>(x0),
+               *z4 = reinterpret_cast<const float4*>(noise), *m4 = reinterpret_cast<const float4*>(mask);
+  if (v4 && blend)
+    hipLaunchKernelGGL((euler_cfg_kernel<float4, true>), map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), p4, n4, x4, z4, m4, scale, dt, a, s, n / 4);
+  else if (v4)
+    hipLaunchKernelGGL((euler_cfg_kernel<float4, false>), map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), p4, n4, x4, z4, m4, scale, dt, a, s, n / 4);
+  else if (blend)
+    hipLaunchKernelGGL((euler_cfg_kernel<float, true>), map_grid(n), dim3(256), 0, stream, img, pos, neg, x0, noise, mask, scale, dt, a, s, n);
+  else
+    hipLaunchKernelGGL((euler_cfg_kernel<float, false>), map_grid(n), dim3(256), 0, stream, img, pos, neg, x0, noise, mask, scale, dt, a, s, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
 // out = (1 - t) * x0 + t * noise  (FlowMatchEulerDiscreteScheduler.scale_noise)
 int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, float* out, hipStream_t stream) {
   if (n <= 0) return FMI_OK;
@@ -239,12 +286,14 @@ __device__ __forceinline__ float row_elem_f32(float v) { return v; }
 __device__ __forceinline__ float row_elem_f32(bf16_t v) { return bf16_to_f32(v); }
 // n contiguous elements of each of B samples, sample b at src + b * src_bs -> bf16 at dst + b * dst_bs (f32_to_bf16, launch_cast_to_bf16's rounding; a bf16
 // source comes through unchanged).  V8: one item = 8 elements, read as 16-B words and written as one; else one element per item, any alignment, any n.
-template <typename T, bool V8>
-__global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const T* __restrict__ src, int64_t src_bs, bf16_t* __restrict__ dst, int64_t dst_bs, int64_t n, int64_t items) {
+// WRAP: destination sample b reads source sample b % B_src (the state of a true-CFG evaluation, once for each half of its batch).
+template <typename T, bool V8, bool WRAP>
+__global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const T* __restrict__ src, int64_t src_bs, bf16_t* __restrict__ dst, int64_t dst_bs, int64_t n, int64_t items,
+                                                             int B_src) {
   const int64_t per = V8 ? n / 8 : n;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = i / per, e = (i % per) * (V8 ? 8 : 1);
-    const T* s = src + b * src_bs + e;
+    const T* s = src + (WRAP ? b % B_src : b) * src_bs + e;
     bf16_t* d = dst + b * dst_bs + e;
     if constexpr (!V8) {
       d[0] = f32_to_bf16(row_elem_f32(s[0]));
@@ -259,15 +308,15 @@ __global__ __launch_bounds__(256) void cast_rows_bf16_kernel(const T* __restrict
     }
   }
 }
-template <typename T>
-int launch_cast_rows_bf16_t(const T* src, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream) {
+template <typename T, bool WRAP>
+int launch_cast_rows_bf16_t(const T* src, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream, int B_src) {
   const int64_t src_v = 16 / (int64_t)sizeof(T);  // elements of a 16-B word of the source
   if (n % 8 == 0 && src_bs % src_v == 0 && dst_bs % 8 == 0 && aligned16(src) && aligned16(dst)) {
     const int64_t items = (int64_t)B * (n / 8);
-    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, true>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items);
+    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, true, WRAP>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items, B_src);
   } else {
     const int64_t items = (int64_t)B * n;
-    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, false>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items);
+    hipLaunchKernelGGL((cast_rows_bf16_kernel<T, false, WRAP>), map_grid(items), dim3(256), 0, stream, src, src_bs, dst, dst_bs, n, items, B_src);
   }
   FMI_LAUNCH_CHECK();
   return FMI_OK;
@@ -275,10 +324,16 @@ int launch_cast_rows_bf16_t(const T* src, int64_t src_bs, bf16_t* dst, int64_t d
 }  // namespace
 // The image-stream operand of a context evaluation is (B, S + R, C) bf16: the S state rows of every sample are cast into their places each
 // step and the R context rows once per call — both are this per-sample strided copy, one launch for all B samples.  src F32 or BF16.
-int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream) {
+// B_src (0: B, every sample its own source): the source holds B_src < B samples and destination sample b takes source sample b % B_src, still in one launch.
+int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream, int B_src) {
   if (B <= 0 || n <= 0) return FMI_OK;
-  if (dt == FMI_F32) return launch_cast_rows_bf16_t((const float*)src, src_bs, dst, dst_bs, B, n, stream);
-  if (dt == FMI_BF16) return launch_cast_rows_bf16_t((const bf16_t*)src, src_bs, dst, dst_bs, B, n, stream);
+  if (B_src < 0 || B_src > B) return fail(FMI_ERR_INVALID, "cast_rows_bf16: B_src must be 0 (= B) .. B");
+  if (B_src && B_src != B) {
+    if (dt == FMI_F32) return launch_cast_rows_bf16_t<float, true>((const float*)src, src_bs, dst, dst_bs, B, n, stream, B_src);
+    if (dt == FMI_BF16) return launch_cast_rows_bf16_t<bf16_t, true>((const bf16_t*)src, src_bs, dst, dst_bs, B, n, stream, B_src);
+  }
+  if (dt == FMI_F32) return launch_cast_rows_bf16_t<float, false>((const float*)src, src_bs, dst, dst_bs, B, n, stream, B);
+  if (dt == FMI_BF16) return launch_cast_rows_bf16_t<bf16_t, false>((const bf16_t*)src, src_bs, dst, dst_bs, B, n, stream, B);
   return fail(FMI_ERR_INVALID, "cast_rows_bf16: the source must be F32 or BF16");
 }
 
@@ -522,6 +577,13 @@ extern "C" int fmi_latent_ids(int B, int h2, int w2, float id0, float row0, floa
   return FMI_OK;
 }
 
+extern "C" int fmi_cfg_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, const float* x0, const float* noise,
+                                  const float* mask, float s, void* stream) {
+  if (!img || !pos || !neg || n < 0) return fail(FMI_ERR_INVALID, "cfg_euler_step: bad arguments");
+  if (!(scale >= 0.f) || std::isinf(scale)) return fail(FMI_ERR_INVALID, "cfg_euler_step: scale must be finite and >= 0");
+  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "cfg_euler_step: x0, noise and mask go together (all three or none)");
+  return launch_euler_cfg(img, pos, neg, scale, dt, n, (hipStream_t)stream, x0, noise, mask, s);
+}
 extern "C" int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, float* out, void* stream) {
   if (!x0 || !noise || !out || n < 0) return fail(FMI_ERR_INVALID, "scale_noise: bad arguments");
   return launch_scale_noise(x0, noise, (float)t, n, out, (hipStream_t)stream);

@@ -107,6 +107,35 @@ def check_step_cache_args(n_steps: int, threshold=None, force=None, sequence_par
     return thr, np.ascontiguousarray(f, dtype=np.int8)
 
 
+def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_shape=None, true_cfg_scale=None, cache_args: bool = False,
+                        sequence_parallel: bool = False):
+    """The arguments of true classifier-free guidance (FluxModel.denoise / fmi_flux_denoise_cfg), checked without the library: the shapes
+    of the prompt's txt (B,T,J) and y (B,P), of the negative's, and the scale.  Returns the scale as a float (1.0 when none is given), or None when no
+    negative is given: the plain loop.
+    ValueError: one negative without the other; a scale without a negative; shapes — and with them T — that differ from the prompt's; B > 4 (the loop
+    evaluates 2 B samples and the per-device limit is 8); a scale that is negative, NaN or infinite; the step cache's arguments; sequence parallelism."""
+    if negative_txt_shape is None and negative_y_shape is None:
+        if true_cfg_scale is not None:
+            raise ValueError("true_cfg_scale= needs negative_txt= and negative_y=")
+        return None
+    if negative_txt_shape is None or negative_y_shape is None:
+        raise ValueError("negative_txt= and negative_y= go together")
+    if tuple(negative_txt_shape) != tuple(txt_shape):
+        raise ValueError(f"negative_txt is {tuple(negative_txt_shape)}, txt is {tuple(txt_shape)}: the negative takes the prompt's shape (B,T,J), T included")
+    if tuple(negative_y_shape) != tuple(y_shape):
+        raise ValueError(f"negative_y is {tuple(negative_y_shape)}, y is {tuple(y_shape)}")
+    if int(txt_shape[0]) > 4:
+        raise ValueError(f"true CFG evaluates 2 B samples per step and the per-device limit is 8: B = {int(txt_shape[0])} > 4")
+    scale = 1.0 if true_cfg_scale is None else float(true_cfg_scale)
+    if not (scale >= 0.0 and scale != float("inf")):
+        raise ValueError(f"true_cfg_scale must be finite and >= 0, got {true_cfg_scale!r}")
+    if cache_args:
+        raise ValueError("true CFG (negative_txt= / negative_y=) is not combined with the step cache (cache_threshold= / cache_force=)")
+    if sequence_parallel:
+        raise ValueError("true CFG (negative_txt= / negative_y=) is not supported under sequence parallelism")
+    return scale
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
@@ -366,7 +395,7 @@ class FluxModel:
         return pred
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
-                cache_threshold=None, cache_force=None, return_cache_stats=False):
+                cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
@@ -376,8 +405,15 @@ class FluxModel:
         their cached output residual.  The decision is per CALL: a batch reuses a step only when every sample is under the threshold, so a batched call may differ
         from its single-sample runs.  cache_force: one entry per step, -1 decide by threshold, 0 compute, 1 reuse (step 0 is always computed).  The cached loop
         synchronises the stream once per step.  No threshold is recommended: ParaAttention suggests 0.08 for FLUX.1-dev, which this project has no real weights
-        to verify.  return_cache_stats=True: returns (img, {"decisions": int array (n,), "distances": float array (n, B), -1 where not measured})."""
+        to verify.  return_cache_stats=True: returns (img, {"decisions": int array (n,), "distances": float array (n, B), -1 where not measured}).
+        negative_txt= / negative_y= / true_cfg_scale=: true classifier-free guidance (fmi_flux_denoise_cfg).  The negative prompt's embeddings,
+        shaped like txt and y (f32 | bf16); every step evaluates the prompt and the negative in ONE batch of 2 B samples on the same state, ids, guidance and
+        context, and steps along neg + true_cfg_scale * (pos - neg) (default scale 1.0; any finite scale >= 0).  B <= 4; not with the step cache, not under
+        sequence parallelism; works with x0 / noise / mask and with context=."""
         n_steps = len(timesteps) - 1
+        cfg_scale = check_true_cfg_args(tuple(txt.shape), tuple(y.shape), None if negative_txt is None else tuple(negative_txt.shape),
+                                        None if negative_y is None else tuple(negative_y.shape), true_cfg_scale,
+                                        cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
         thr, force = check_step_cache_args(n_steps, cache_threshold, cache_force, getattr(self, "_sp_world", 1) > 1)
         if return_cache_stats and thr is None:
             raise ValueError("return_cache_stats needs cache_threshold= or cache_force=")
@@ -389,7 +425,16 @@ class FluxModel:
         has_ctx = context is not None or context_ids is not None
         ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
         blend = [_ptr(t) for t in keep_blend]  # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
-        if thr is not None:
+        if cfg_scale is not None:
+            for t, nm in ((negative_txt, "negative_txt"), (negative_y, "negative_y")):
+                if t.dtype not in (torch.float32, torch.bfloat16):
+                    raise TypeError(f"{nm} must be float32 or bfloat16")
+                if t.device != img.device:
+                    raise ValueError(f"{nm} is on {t.device}, img on {img.device}")
+            keep_neg = [negative_txt.contiguous(), negative_y.contiguous()]
+            tc = L.FluxTrueCfg(_ptr(keep_neg[0]), _TORCH_DT[negative_txt.dtype], _ptr(keep_neg[1]), _TORCH_DT[negative_y.dtype], cfg_scale)
+            st = self.lib.fmi_flux_denoise_cfg(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
+        elif thr is not None:
             decisions = np.zeros(max(n_steps, 0), np.int32)
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             sc = L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
@@ -581,6 +626,20 @@ def scale_noise(x0, noise, t):
     out = torch.empty_like(x0)
     L.check(L.load().fmi_scale_noise(_ptr(x0), _ptr(noise), float(t), x0.numel(), _ptr(out), _stream()))
     return out
+
+
+def cfg_euler_step(img, pos, neg, scale, dt, x0=None, noise=None, mask=None, s=0.0):
+    """The true-CFG step on its own (fmi_cfg_euler_step), in place on img and returning it: g = neg + scale * (pos - neg), img = img + g * dt —
+    or with x0 / noise / mask (all three or none) mask * (img + g * dt) + (1 - mask) * ((1 - s) * x0 + s * noise).  float32 tensors of one shape, used as
+    they lie in memory (contiguous); pos == neg or scale == 0 steps along neg bit for bit."""
+    blend = [t for t in (x0, noise, mask) if t is not None]
+    if len(blend) not in (0, 3):
+        raise ValueError("cfg_euler_step: x0, noise and mask go together (all three or none)")
+    for t in [img, pos, neg] + blend:
+        if t.dtype != torch.float32 or t.shape != img.shape or not t.is_contiguous() or t.device != img.device:
+            raise TypeError("cfg_euler_step: contiguous float32 tensors of one shape on one device are required")
+    L.check(L.load().fmi_cfg_euler_step(_ptr(img), _ptr(pos), _ptr(neg), float(scale), float(dt), img.numel(), _ptr(x0), _ptr(noise), _ptr(mask), float(s), _stream()))
+    return img
 
 
 def randn_latents(B, Cc, h, w, seed, first_sample=0, device="cuda"):

@@ -194,6 +194,16 @@ class _Samples:
         return {f.name: getattr(self, f.name) for f in fields(self) if f.name != "prompts"}
 
 
+@dataclass(frozen=True)
+class _Negative:
+    """The negative prompt of a true-CFG request: ONE per request, shared by its prompts like strength — not a per-sample input, so no field
+    of _Samples.  Exactly one of prompt / embeddings / token_ids is set; every chunk of the request receives this same object."""
+    scale: float
+    prompt: Optional[str] = None
+    embeddings: Optional[tuple] = None  # (t5 (1,T,J), clip (1,P))
+    token_ids: Optional[tuple] = None  # (t5 (1,T'), clip (1,.))
+
+
 def _index_sets(B: int, max_batch: int, one_by_one: bool) -> list:
     """The row sets a request of any B runs in (pipelines/mod.rs:241-270): chunks of max_batch, or single samples (sequence parallel: ONE image at a time)."""
     n = 1 if one_by_one else max_batch
@@ -405,7 +415,8 @@ class Pipeline:
 
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
-                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None):
+                        image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
+                        negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -427,9 +438,18 @@ class Pipeline:
         block-0 residual moved less than the threshold since the last computed step skips the other blocks.  The decision is per denoise CALL (a chunk of up to
         MAX_BATCH prompts reuses a step only when all its samples are under the threshold), and every call's {"decisions", "distances"} is appended to
         `pipeline.last_cache_stats` (one entry per denoise call of the request).  No value is recommended: ParaAttention suggests 0.08 for FLUX.1-dev, which
-        this project has no real weights to verify.  Raises under sequence parallelism, like image=."""
+        this project has no real weights to verify.  Raises under sequence parallelism, like image=.
+
+        True classifier-free guidance (`negative_prompt=` / `negative_embeddings=` (t5 (1,T,J), clip (1,P)) / `negative_token_ids=` (t5 (1,T'), clip (1,.)) with
+        `true_cfg_scale` > 1; diffusers' `do_true_cfg`): ONE negative per request, shared by its prompts.  Every step evaluates the prompt and
+        the negative in one batch on the same state and steps along neg + true_cfg_scale * (pos - neg), so a denoise call holds MAX_BATCH // 2 prompts.  The
+        negative takes the prompt's T: with tokenizers it is tokenised and encoded together with the chunk's prompts; negative_embeddings= / negative_token_ids=
+        must have the T of embeddings= / token_ids=.  A negative with true_cfg_scale <= 1 is ignored, as in diffusers (today's launches); true_cfg_scale > 1
+        without a negative raises (diffusers only warns).  Combines with image= / strength= / mask= / reference=; raises with cache_threshold= and under
+        sequence parallelism.  No scale is recommended: there are no real weights here to judge one."""
         if cache_threshold is not None:
             F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
+        neg = self._negative(negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids)
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
         if not s.prompts:
@@ -437,11 +457,49 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats)
-                for idx in _index_sets(len(s.prompts), self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
+        # (the negative is a keyword of true-CFG requests only: any other request makes exactly the call it always made)
+        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **({} if neg is None else dict(negative=neg)))
+                for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
             return outs[0]
         return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
+
+    def _negative(self, negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids) -> Optional[_Negative]:
+        """The negative of a request, checked once: None when true CFG is off (no negative, or a scale <= 1: diffusers' do_true_cfg), else the object its chunks share."""
+        scale = float(true_cfg_scale)
+        given = [x is not None for x in (negative_prompt, negative_embeddings, negative_token_ids)]
+        if not scale >= 0.0 or scale == float("inf"):
+            raise ValueError(f"true_cfg_scale must be finite and >= 0, got {true_cfg_scale!r}")
+        if sum(given) > 1:
+            raise ValueError("negative_prompt=, negative_embeddings= and negative_token_ids= exclude one another: a request has one negative")
+        if not any(given):
+            if scale > 1.0:
+                raise ValueError("true_cfg_scale > 1 needs a negative: negative_prompt=, negative_embeddings= or negative_token_ids=")
+            return None
+        if scale <= 1.0:
+            return None
+        if cache_threshold is not None:
+            raise ValueError("true CFG (a negative with true_cfg_scale > 1) is not combined with the step cache (cache_threshold=)")
+        if getattr(self, "_sp", None) is not None:
+            raise ValueError("true CFG is not wired through sequence parallelism: disable_sequence_parallel() first")
+        if embeddings is not None and negative_embeddings is None:
+            raise ValueError("with embeddings= the negative comes as negative_embeddings= (t5 (1,T,J), clip (1,P))")
+        if embeddings is None and token_ids is not None and negative_prompt is not None:
+            raise ValueError("with token_ids= the negative comes as negative_token_ids= (or negative_embeddings=)")
+        if negative_token_ids is not None and (token_ids is None or embeddings is not None):
+            raise ValueError("negative_token_ids= goes with token_ids=: without them the negative comes as negative_prompt= (or negative_embeddings=)")
+        pair = None
+        for mine, theirs, what in ((negative_embeddings, embeddings, "embeddings"), (negative_token_ids, token_ids, "token_ids")):
+            if mine is None:
+                continue
+            pair = tuple(mine)
+            if len(pair) != 2 or any(np.shape(x)[0] != 1 for x in pair):
+                raise ValueError(f"negative_{what}= is a pair (t5, clip) of ONE row each: the negative is shared by the request's prompts")
+            # T of the t5 member; of token ids also the clip member's length (the rows are concatenated), of embeddings the clip vector's width
+            for n, t in zip(pair, tuple(theirs) if theirs is not None else ()):
+                if np.shape(n)[1] != np.shape(t)[1]:
+                    raise ValueError(f"negative_{what}= has T = {np.shape(n)[1]}, {what}= has T = {np.shape(t)[1]}: the negative takes the prompt's T")
+        return _Negative(scale, negative_prompt, pair if negative_embeddings is not None else None, pair if negative_token_ids is not None else None)
 
     def _samples(self, prompts, params, strength, first_sample=0, sample_ids=None, **given) -> _Samples:
         """A request's per-sample inputs (`given`: the other fields of _Samples as the caller passed them), checked and normalised once: the pairs as tuples,
@@ -456,23 +514,47 @@ class Pipeline:
             s.reference = self._reference_image(s.reference, B)
         return s
 
-    def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats):
-        """One denoise call: at most MAX_BATCH samples (one under sequence parallelism) of a normalised request.  Returns what generate_tensor does."""
+    def _chunk_embeddings(self, s: _Samples, negative: Optional[_Negative]):
+        """(t5_emb (B,T,J), clip_emb (B,P), the negative's two expanded to B rows or None) of a chunk.  The negative reaches the prompts' T here: tokenised and
+        encoded in ONE pass with the chunk's prompts (row B), or checked against them."""
+        cfg, dev, B = self.flux.cfg, self.device, len(s.prompts)
+        neg_text = negative is not None and negative.embeddings is None  # the negative goes through the same source as the prompts, as row B
+        if s.embeddings is not None:
+            t5_emb, clip_emb = (e.to(dev) for e in s.embeddings)  # (the negative is negative_embeddings= then: Pipeline._negative)
+        elif self.t5 is not None and self.clip is not None:
+            prompts, token_ids = s.prompts, s.token_ids
+            if neg_text and token_ids is not None:  # (Pipeline._negative has checked that the negative came as token ids of the same T)
+                token_ids = tuple(torch.cat([torch.as_tensor(t, dtype=torch.int32), torch.as_tensor(n, dtype=torch.int32)], 0) for t, n in zip(token_ids, negative.token_ids))
+            elif neg_text:
+                prompts = list(prompts) + [negative.prompt]  # one tokenize_and_pad, one pass of B + 1 rows through the encoders
+            t5_emb, clip_emb = self.encode_prompts(prompts, token_ids)
+        elif self.source_kind == "synthetic":
+            # schnell pads T5 ids to 256 (flux/mod.rs:243-253); dev uses the prompt length — 512 here
+            T = 256 if not self.flux.is_guidance() else 512
+            t5_emb, clip_emb = placeholder_embeddings(list(s.prompts) + ([negative.prompt] if neg_text else []), T, cfg["joint_attention_dim"],
+                                                      cfg["pooled_projection_dim"], dev)
+        else:
+            raise F.L.FmiError("this checkpoint was loaded without text encoders: pass embeddings=(t5_emb, clip_emb)")
+        if negative is None:
+            return t5_emb, clip_emb, None
+        if neg_text:
+            neg, t5_emb, clip_emb = (t5_emb[B:], clip_emb[B:]), t5_emb[:B], clip_emb[:B]
+        else:
+            neg = tuple(e.to(dev) for e in negative.embeddings)
+            if int(neg[0].shape[1]) != int(t5_emb.shape[1]):
+                raise ValueError(f"negative_embeddings= has T = {int(neg[0].shape[1])}, the prompts' embeddings have T = {int(t5_emb.shape[1])}")
+        neg = (neg[0].to(t5_emb.dtype).expand(B, -1, -1).contiguous(), neg[1].to(clip_emb.dtype).expand(B, -1).contiguous())
+        return t5_emb, clip_emb, neg
+
+    def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None):
+        """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
+        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only."""
         cfg = self.flux.cfg
         dev = self.device
         sp = getattr(self, "_sp", None)
         B, ids, latents = len(s.prompts), s.sample_ids, s.latents
         with self._lock:  # the whole forward, text encoders included, like the reference's mutex (pipelines/mod.rs:247)
-            if s.embeddings is not None:
-                t5_emb, clip_emb = (e.to(dev) for e in s.embeddings)
-            elif self.t5 is not None and self.clip is not None:
-                t5_emb, clip_emb = self.encode_prompts(s.prompts, s.token_ids)
-            elif self.source_kind == "synthetic":
-                # schnell pads T5 ids to 256 (flux/mod.rs:243-253); dev uses the prompt length — 512 here
-                T = 256 if not self.flux.is_guidance() else 512
-                t5_emb, clip_emb = placeholder_embeddings(s.prompts, T, cfg["joint_attention_dim"], cfg["pooled_projection_dim"], dev)
-            else:
-                raise F.L.FmiError("this checkpoint was loaded without text encoders: pass embeddings=(t5_emb, clip_emb)")
+            t5_emb, clip_emb, neg = self._chunk_embeddings(s, negative)
             h = (params.height + 15) // 16 * 2  # get_noise, flux/sampling.rs:12-13
             w = (params.width + 15) // 16 * 2
             if latents is None:
@@ -506,7 +588,8 @@ class Pipeline:
                 img = sp.gather(self.flux.denoise(sp.shard(img), sp.shard(img_ids), sp.shard(t5_emb), sp.shard(txt_ids), clip_emb, guidance, timesteps))
             else:
                 cache = {} if cache_threshold is None else dict(cache_threshold=cache_threshold, return_cache_stats=True)
-                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, **cache)
+                true_cfg = {} if neg is None else dict(negative_txt=neg[0], negative_y=neg[1], true_cfg_scale=negative.scale)
+                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, **cache, **true_cfg)
                 if cache:
                     img, st = img
                     stats.append(st)
@@ -593,16 +676,21 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, **kw):
+                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
+                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
         image= / strength= / mask=: image to image and inpainting, reference=: reference-image conditioning, see generate_tensor; return_latents=True
         returns (images, final packed latents).  cache_threshold=: the first-block step cache, see generate_tensor (None: off); each rank of a sharded batch
-        decides for its own prompts and keeps its own `last_cache_stats`."""
+        decides for its own prompts and keeps its own `last_cache_stats`.  negative_prompt= / negative_embeddings= / negative_token_ids= / true_cfg_scale=: true
+        classifier-free guidance, see generate_tensor — one negative per request, handed to every rank of a sharded batch unchanged."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
+        if negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None or true_cfg_scale != 1.0:
+            # (only when one of them is given: any other request makes exactly the generate_tensor call it always made)
+            shared.update(negative_prompt=negative_prompt, negative_embeddings=negative_embeddings, negative_token_ids=negative_token_ids, true_cfg_scale=true_cfg_scale)
         per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if world > 1 and getattr(self, "_sp", None) is None:

@@ -47,6 +47,7 @@ extern "C" {
  *   Then, still 6: reference-image (FLUX.1 Kontext) conditioning — fmi_flux_context, fmi_flux_forward_context, fmi_flux_denoise_context, fmi_latent_ids.
  *   Then, still 6: the GEMM launcher's test seams — fmi_gemm_desc, fmi_gemm_group, fmi_splitk_resid_gate, fmi_set_gemm_kernel.
  *   Then, still 6: the first-block step cache of the denoise loop — fmi_flux_step_cache, fmi_flux_denoise_cached, fmi_flux_step_cache_bytes.
+ *   Then, still 6: true classifier-free guidance (negative prompts) in the denoise loop — fmi_flux_true_cfg, fmi_flux_denoise_cfg, fmi_cfg_euler_step.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -431,6 +432,32 @@ int fmi_flux_denoise_cached(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux
                             const fmi_flux_step_cache* cache /* NULL: == fmi_flux_denoise_context */, void* stream);
 size_t fmi_flux_step_cache_bytes(fmi_flux*);
 
+/* True classifier-free guidance in the denoise loop (diffusers' FluxPipeline with negative_prompt= and true_cfg_scale > 1, `do_true_cfg`; the
+ * reference has no counterpart).  fmi_flux_denoise_cfg is fmi_flux_denoise_context — same arguments, same state (B,S,in_channels) f32 — whose every step evaluates
+ * the model ONCE on an internal batch of 2B samples: rows [0,B) the prompt's (in->txt, in->y), rows [B,2B) the negative's (neg_txt, neg_y); the state, the ids, the
+ * guidance vector and the context rows are the same in both halves.  With dt = f32(ts[i+1] - ts[i]) and s = f32(ts[i+1]) the update is one pass,
+ *   g = neg + scale * (pos - neg)             (diffusers' expression, the difference first: pos == neg or scale == 0 gives neg bit for bit;
+ *                                              scale == 1 is NOT special-cased and is not pos bit for bit)
+ *   e = img + g * dt                          (fmi_flux_denoise's update)
+ *   img = e,  or with x0 / noise / mask       img = mask * e + (1 - mask) * ((1 - s) * x0 + s * noise)       (fmi_flux_denoise_inpaint's blend, unchanged)
+ * The once-per-image modulation GEMM, txt_in, the context rows and the RoPE table are hoisted for the 2B rows exactly as for a batch of 2B prompts, and each
+ * sample of the call equals its own B = 1 call bit for bit.  The workspace is that of a batch of 2B.
+ * cfg == NULL: fmi_flux_denoise_context, launch for launch.  Works in the bf16, int8 and e4m3 modes, on models without a guidance vector (in->guidance NULL)
+ * and with a context.  The step cache (fmi_flux_denoise_cached) is not combined with it.
+ * FMI_ERR_INVALID: neg_txt or neg_y NULL; a dtype that is not F32 or BF16; scale negative, NaN or infinite; x0 / noise / mask given in part.
+ * FMI_ERR_UNSUPPORTED: in->B > 4 (2B would exceed the per-device limit of 8); sequence parallelism set (it runs B = 1); n_steps * 2B > 4096 (the
+ * loops' limit of n_steps * B rows, counted on the internal batch).
+ * FMI_ERR_STATE: while int8 calibration is recording.  All before any launch. */
+typedef struct fmi_flux_true_cfg {
+  const void* neg_txt; fmi_dtype neg_txt_dtype;   /* (B,T,joint_attention_dim) F32|BF16, same T as in->txt */
+  const void* neg_y;   fmi_dtype neg_y_dtype;     /* (B,pooled_projection_dim) F32|BF16 */
+  float scale;                                    /* finite, >= 0 */
+} fmi_flux_true_cfg;
+int fmi_flux_denoise_cfg(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx /* NULL ok */,
+                         const fmi_flux_true_cfg* cfg /* NULL: == fmi_flux_denoise_context */,
+                         float* img_inout, const double* timesteps_host, int n_steps,
+                         const float* x0, const float* noise, const float* mask /* all three or none */, void* stream);
+
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
  * With FMI_ROCTX=1 in the environment every phase is also a roctx range (roctxRangePushA / Pop from
@@ -594,6 +621,12 @@ int fmi_latent_ids(int B, int h2, int w2, float id0, float row0, float col0, flo
  * 1 - t computed once: t = 1 gives noise and t = 0 gives x0 bit for bit.  The start state of image-to-image at
  * t = timesteps[num_steps - n_run]. */
 int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, float* out, void* stream);
+/* The update of fmi_flux_denoise_cfg on its own (op-level glue; device pointers, no allocation): over n f32 elements
+ *   g = neg + scale * (pos - neg);  e = img + g * dt;  img = e, or with x0 / noise / mask (all three or none) mask * e + (1 - mask) * ((1 - s) * x0 + s * noise).
+ * img is read and written in place.  16-byte accesses when n % 4 == 0 and every pointer is 16-byte aligned, else scalar ones: the same bits either way.
+ * FMI_ERR_INVALID: a null img / pos / neg, n < 0, a scale that is negative, NaN or infinite, x0 / noise / mask given in part. */
+int fmi_cfg_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n,
+                       const float* x0, const float* noise, const float* mask, float s, void* stream);
 /* Deterministic N(0,1) latents from a counter-based Philox4x32-10 generator
  * (the reference's RNG is unseedable; this is the explicit-seed extension).
  * Elements 4q..4q+3 of sample b come from the four words of philox(counter = (q lo, q hi, s lo, s hi),
