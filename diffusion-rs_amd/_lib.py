@@ -57,6 +57,11 @@ class FluxTrueCfg(C.Structure):
     _fields_ = [("neg_txt", C.c_void_p), ("neg_txt_dtype", C.c_int), ("neg_y", C.c_void_p), ("neg_y_dtype", C.c_int), ("scale", C.c_float)]
 
 
+class FluxControl(C.Structure):
+    """fmi_flux_control: the conditioning channels of fmi_flux_forward_control / fmi_flux_denoise_control."""
+    _fields_ = [("cond", C.c_void_p), ("cond_dtype", C.c_int)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4), ("n_blocks", C.c_int),
                 ("layers_per_block", C.c_int), ("latent_channels", C.c_int), ("norm_num_groups", C.c_int),
@@ -221,6 +226,14 @@ def _declare(lib):
     lib.fmi_flux_denoise_cfg.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxContext), C.POINTER(FluxTrueCfg), C.c_void_p, C.POINTER(C.c_double), C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fmi_cfg_euler_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    lib.fmi_flux_create_cond.argtypes = [C.POINTER(FluxConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.fmi_flux_cond_channels.argtypes = [C.c_void_p]
+    lib.fmi_flux_forward_control.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxControl), C.c_void_p, C.c_void_p]
+    lib.fmi_flux_denoise_control.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxControl), C.POINTER(FluxTrueCfg), C.c_void_p, C.POINTER(C.c_double), C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fmi_cast_cols_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.fmi_mask_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.fmi_fill_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.fmi_flux_step_cache_bytes.argtypes = [C.c_void_p]
     lib.fmi_flux_step_cache_bytes.restype = C.c_size_t
     lib.fmi_latent_ids.argtypes =[C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
@@ -316,13 +329,13 @@ def check(rc, lib=None):
 EXPORTED = [
     "fmi_last_error", "fmi_abi_version", "fmi_init", "fmi_device_info", "fmi_build_id", "fmi_has_alt_kernels", "fmi_flux_default_config", "fmi_flux_create", "fmi_flux_destroy",
     "fmi_flux_set_tensor", "fmi_flux_set_linear_bnb4", "fmi_flux_set_linear_int8", "fmi_flux_get_tensor", "fmi_flux_lora_add", "fmi_flux_lora_set_weight", "fmi_flux_lora_remove", "fmi_flux_lora_count", "fmi_flux_lora_name", "fmi_flux_set_quant_dense_cache", "fmi_flux_set_sequence_parallel", "fmi_flux_set_split_k", "fmi_set_bnb4_onewave_min_rows", "fmi_flux_set_attention_rescale_threshold", "fmi_flux_set_attention_kernel", "fmi_flux_state_buffer_count", "fmi_flux_state_export", "fmi_flux_state_adopt", "fmi_flux_state_buffer", "fmi_flux_set_modulation_gemm", "fmi_flux_quantize_fp8", "fmi_flux_quantize_int8", "fmi_flux_calibrate_int8", "fmi_flux_set_fp8_attention", "fmi_flux_missing_count", "fmi_flux_missing_name", "fmi_flux_size_in_bytes",
-    "fmi_flux_forward", "fmi_flux_denoise", "fmi_flux_denoise_inpaint", "fmi_flux_forward_context", "fmi_flux_denoise_context", "fmi_flux_denoise_cached", "fmi_flux_step_cache_bytes", "fmi_flux_denoise_cfg", "fmi_flux_set_profiling", "fmi_flux_set_fused_qkv_relayout", "fmi_flux_phase_count", "fmi_flux_phase_name", "fmi_flux_phase_ms",
+    "fmi_flux_forward", "fmi_flux_denoise", "fmi_flux_denoise_inpaint", "fmi_flux_forward_context", "fmi_flux_denoise_context", "fmi_flux_denoise_cached", "fmi_flux_step_cache_bytes", "fmi_flux_denoise_cfg", "fmi_flux_create_cond", "fmi_flux_cond_channels", "fmi_flux_forward_control", "fmi_flux_denoise_control", "fmi_flux_set_profiling", "fmi_flux_set_fused_qkv_relayout", "fmi_flux_phase_count", "fmi_flux_phase_name", "fmi_flux_phase_ms",
     "fmi_vae_default_config", "fmi_vae_create", "fmi_vae_destroy", "fmi_vae_set_tensor", "fmi_vae_missing_count", "fmi_vae_missing_name",
     "fmi_vae_scale_factor", "fmi_vae_shift_factor", "fmi_vae_decode", "fmi_vae_encode", "fmi_vae_mid_attention",
     "fmi_t5_default_config", "fmi_t5_create", "fmi_t5_destroy", "fmi_t5_set_tensor", "fmi_t5_set_linear_bnb4", "fmi_t5_set_linear_int8", "fmi_t5_missing_count", "fmi_t5_missing_name",
     "fmi_t5_size_in_bytes", "fmi_t5_forward", "fmi_clip_default_config", "fmi_clip_create", "fmi_clip_destroy", "fmi_clip_set_tensor",
     "fmi_clip_missing_count", "fmi_clip_missing_name", "fmi_clip_size_in_bytes", "fmi_clip_forward", "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
-    "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids", "fmi_cfg_euler_step",
+    "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids", "fmi_cfg_euler_step", "fmi_cast_cols_bf16", "fmi_mask_image", "fmi_fill_condition",
     "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
     "fmi_release_scratch", "fmi_timestep_embedding", "fmi_rope_table", "fmi_rmsnorm_rope",
     "fmi_groupnorm_nhwc", "fmi_conv2d_nhwc",

@@ -483,6 +483,8 @@ int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, h
 int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hipStream_t stream);
 // per-sample strided cast: n contiguous elements of sample b at src + b * src_bs (F32 | BF16) -> bf16 at dst + b * dst_bs, one launch (small_ops.hip)
 int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream, int B_src = 0);
+// column-window cast: row r of src (rows_src, cols) F32 | BF16, read at r % rows_src, -> bf16 at dst[r * dst_ld + col0 .. + cols); the other columns stay (small_ops.hip)
+int launch_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t rows_src, int cols, bf16_t* dst, int dst_ld, int col0, hipStream_t stream);
 int launch_silu_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream);
 // the masked (inpainting) step: img = mask * (img + pred * dt) + (1 - mask) * ((1 - s) * x0 + s * noise), one pass (small_ops.hip)

@@ -87,6 +87,7 @@ const char* kPhaseNames[PH_COUNT] = {"embed", "modulation", "layernorm_mod", "ge
 
 struct fmi_flux {
   fmi_flux_config cfg;
+  int cond = 0;  // fmi_flux_create_cond: conditioning channels concatenated to the state's for x_embedder; cfg.in_channels stays the state's width
   int D, M, H;
   int device = 0;
   Arena arena[AR_COUNT];
@@ -276,7 +277,7 @@ void reg_lin(fmi_flux* m, const std::string& prefix, Dense& d, int r0, int rows)
 void build_layout(fmi_flux* m) {
   const fmi_flux_config& c = m->cfg;
   const int D = m->D, M = m->M;
-  layout_dense(m, m->img_in, D, c.in_channels, AR_BASE);
+  layout_dense(m, m->img_in, D, c.in_channels + m->cond, AR_BASE);  // (the one matrix that sees the conditioning channels)
   layout_dense(m, m->txt_in, D, c.joint_attention_dim, AR_BASE);
   layout_dense(m, m->time1, D, 256, AR_BASE);
   layout_dense(m, m->time2, D, D, AR_BASE);
@@ -469,7 +470,7 @@ int ensure_workspace(fmi_flux* m, int B, int S, int T) {
   add((void**)&w.img_f32, (size_t)B * S * C * 4);
   add((void**)&w.pred_tmp, (size_t)B * S * C * 4);
   add((void**)&w.tv, 4096 * 4);
-  add((void**)&w.img_bf, (size_t)B * S * C * 2);
+  add((void**)&w.img_bf, (size_t)B * S * (C + m->cond) * 2);  // the x_embedder operand: [state | conditioning] columns
   add((void**)&w.txt_bf, (size_t)B * T * J * 2);
   add((void**)&w.xm, (size_t)B * L * D * 2);
   add((void**)&w.qkv_img, (size_t)B * S * 3 * D * 2);
@@ -837,7 +838,9 @@ int use_device(const fmi_flux* m) { return use_device_ordinal(m->device); }
 // R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
 // cfg (true CFG): `in` is the loop's internal batch of 2 * Bs samples whose txt / y / ids / context pointers are the caller's Bs samples'; the
 // negative's txt and y fill the second halves, and samples Bs .. 2 Bs - 1 take the table and the context rows of samples 0 .. Bs - 1.  Null: nothing changes.
-int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s, const fmi_flux_true_cfg* cfg = nullptr) {
+// ctl (a channel-conditioned model): the conditioning (Bs, S, cond) goes into columns [C, C + cond) of every row of the img_in operand, once.
+int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s, const fmi_flux_true_cfg* cfg = nullptr,
+                   const fmi_flux_control* ctl = nullptr) {
   auto& w = m->ws;
   const int B = in->B, Bs = cfg ? B / 2 : B, S = in->S, T = in->T, C = m->cfg.in_channels;
   const int64_t n_txt = (int64_t)Bs * T * m->cfg.joint_attention_dim, n_y = (int64_t)Bs * m->cfg.pooled_projection_dim;
@@ -855,6 +858,7 @@ int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_contex
     const size_t half = (size_t)Bs * (T + S + R) * PE_ROW_FLOATS;
     FMI_HIP_TRY(hipMemcpyAsync(w.pe + half, w.pe, half * 4, hipMemcpyDeviceToDevice, s));
   }
+  if (ctl) return launch_cast_cols_bf16(ctl->cond, ctl->cond_dtype, (int64_t)B * S, (int64_t)Bs * S, m->cond, w.img_bf, C + m->cond, C, s);
   if (!R) return FMI_OK;
   return launch_cast_rows_bf16(ctx->ctx, ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s, Bs);
 }
@@ -867,6 +871,18 @@ int context_rows(const fmi_flux* m, const fmi_flux_context* ctx, int* R) {
   if (ctx->ctx_dtype != FMI_F32 && ctx->ctx_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux: ctx_dtype must be F32 or BF16");
   if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux: a context is not supported under sequence parallelism");
   *R = ctx->R;
+  return FMI_OK;
+}
+
+// The control of an evaluation, validated: a channel-conditioned model needs one at every evaluation — so every entry without one refuses
+// such a model — and a plain model takes none.  R: the context rows context_rows() returned.
+int control_check(const fmi_flux* m, const fmi_flux_control* ctl, int R) {
+  if (!m->cond) return ctl ? fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)") : FMI_OK;
+  if (!ctl || !ctl->cond)
+    return fail(FMI_ERR_INVALID, "flux: this model has " + std::to_string(m->cond) + " conditioning channels: it is evaluated by fmi_flux_forward_control / fmi_flux_denoise_control with a control");
+  if (ctl->cond_dtype != FMI_F32 && ctl->cond_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux: cond_dtype must be F32 or BF16");
+  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux: a control is not supported under sequence parallelism");
+  if (R) return fail(FMI_ERR_UNSUPPORTED, "flux: a context and a control are not combined");
   return FMI_OK;
 }
 
@@ -987,12 +1003,14 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
 
   {
     PhaseTimer pt(m, s, PH_EMBED);
-    if (R || Bs) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s, Bs));  // the state rows into their places
+    if (m->cond)  // the state into columns [0, C) of the [state | conditioning] operand, both halves of a true-CFG batch in the one launch (no context: R == 0)
+      FMI_TRY(launch_cast_cols_bf16(img_f32, FMI_F32, (int64_t)B * S, (int64_t)(Bs ? Bs : B) * S, C, w.img_bf, m->img_in.K, 0, s));
+    else if (R || Bs) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s, Bs));  // the state rows into their places
     else FMI_TRY(launch_cast_to_bf16(img_f32, FMI_F32, w.img_bf, (int64_t)B * S * C, s));
     if (!mod_pre) FMI_TRY(compute_vec(m, in, timesteps_dev, w.vec, s));
     // img = img_in(img), txt = txt_in(txt)   (model.rs:811-812) -> f32 residual streams
     GemmProblem p[2];
-    p[0] = make_problem(m->img_in, w.img_bf, C, B * S, w.x_img, D, EPI_STORE_F32);
+    p[0] = make_problem(m->img_in, w.img_bf, m->img_in.K, B * S, w.x_img, D, EPI_STORE_F32);  // K = C + the conditioning channels
     p[1] = make_problem(m->txt_in, w.txt_bf, c.joint_attention_dim, B * T, w.x_txt, D, EPI_STORE_F32);
     Dense* dn[2] = {&m->img_in, &m->txt_in};
     if (txt_pre) {  // the text stream starts every step from the same values: a 6 MB copy instead of a 13-GFLOP GEMM per step (same bits)
@@ -1274,8 +1292,14 @@ extern "C" void fmi_flux_default_config(fmi_flux_config* cfg, int guidance_embed
   cfg->theta = 10000;
 }
 
-extern "C" int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out) {
+extern "C" int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out) { return fmi_flux_create_cond(cfg, 0, dtype, out); }
+extern "C" int fmi_flux_cond_channels(const fmi_flux* m) { return m ? m->cond : 0; }
+
+// x_embedder of a channel-conditioned checkpoint (FLUX.1 Fill / Canny / Depth) is (D, in_channels + cond_channels); everything else keeps in_channels.
+extern "C" int fmi_flux_create_cond(const fmi_flux_config* cfg, int cond_channels, fmi_model_dtype dtype, fmi_flux** out) {
   if (!cfg || !out) return fail(FMI_ERR_INVALID, "flux_create: null argument");
+  if (cond_channels < 0 || cond_channels % 64 || (int64_t)cfg->in_channels + cond_channels > 512)
+    return fail(FMI_ERR_INVALID, "flux_create_cond: cond_channels must be >= 0, a multiple of 64, and in_channels + cond_channels at most 512");
   if (dtype == FMI_MODEL_F16 || dtype == FMI_MODEL_F32)
     return fail(FMI_ERR_UNSUPPORTED, "flux_create: this build computes in bf16 on MFMA; F16/F32 model dtypes are not implemented");
   if (cfg->axes_dim[0] + cfg->axes_dim[1] + cfg->axes_dim[2] != 128 || (cfg->axes_dim[0] | cfg->axes_dim[1] | cfg->axes_dim[2]) & 1)
@@ -1285,6 +1309,7 @@ extern "C" int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype
     return fail(FMI_ERR_INVALID, "flux_create: in_channels and joint_attention_dim must be multiples of 64, pooled dim of 8");
   fmi_flux* m = new fmi_flux();
   m->cfg = *cfg;
+  m->cond = cond_channels;
   hipGetDevice(&m->device);
   m->H = cfg->num_attention_heads;
   m->D = m->H * 128;  // HIDDEN_SIZE (model.rs:17) generalised as heads * pe_dim
@@ -1533,17 +1558,26 @@ extern "C" int fmi_flux_state_buffer(fmi_flux* m, int index, void** ptr, size_t*
   return FMI_OK;
 }
 
-// One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
-extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
+// One evaluation of every forward entry: over cat([img, ctx], 1) with a context, over cat([img, cond], 2) with a control.
+static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, float* pred_out, void* stream) {
   FMI_TRY(check_inputs(m, in));
   if (!in->img || !in->timesteps || !pred_out) return fail(FMI_ERR_INVALID, "flux_forward: null img/timesteps/pred_out");
   int R = 0;
   FMI_TRY(context_rows(m, ctx, &R));
+  FMI_TRY(control_check(m, ctl, R));
   hipStream_t s = (hipStream_t)stream;
   FMI_TRY(ensure_workspace(m, in->B, in->S + R, in->T));
-  FMI_TRY(prepare_static(m, in, ctx, R, s));
+  FMI_TRY(prepare_static(m, in, ctx, R, s, nullptr, ctl));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, m->ws.img_f32, (int64_t)in->B * in->S * m->cfg.in_channels, s));
   return forward_core(m, in, m->ws.img_f32, in->timesteps, pred_out, s, nullptr, nullptr, R);
+}
+// One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
+extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
+  return forward_eval(m, in, ctx, nullptr, pred_out, stream);
+}
+// One evaluation over cat([img, cond], 2) of a channel-conditioned model; pred_out is (B,S,in_channels).  A plain model with ctl NULL: fmi_flux_forward.
+extern "C" int fmi_flux_forward_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream) {
+  return forward_eval(m, in, nullptr, ctl, pred_out, stream);
 }
 extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* pred_out, void* stream) {
   return fmi_flux_forward_context(m, in, nullptr, pred_out, stream);
@@ -1555,13 +1589,16 @@ extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* p
 // cache: fmi_flux_denoise_cached's first-block step cache, null for every other entry — which then issue exactly the launches they always did.
 // cfg: fmi_flux_denoise_cfg's negative prompt, null for every other entry, likewise.  With it `in` below is the loop's own batch of 2 * Bs samples
 // — the prompt's rows, then the negative's — and only the input assembly (prepare_static, forward_core's state cast) and the update (launch_euler_cfg) know.
+// ctl: fmi_flux_denoise_control's conditioning channels, required by a channel-conditioned model and refused by every other: the input assembly
+// alone knows (prepare_static writes the operand's conditioning columns once, forward_core the state's every step); the state, the update and the blend stay (B,S,C).
 static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
                         const float* x0, const float* noise, const float* mask, void* stream, const fmi_flux_step_cache* cache = nullptr,
-                        const fmi_flux_true_cfg* cfg = nullptr) {
+                        const fmi_flux_true_cfg* cfg = nullptr, const fmi_flux_control* ctl = nullptr) {
   FMI_TRY(check_inputs(m, in_caller));
   if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
   int Rc = 0;  // context rows per sample
   FMI_TRY(context_rows(m, ctx, &Rc));
+  FMI_TRY(control_check(m, ctl, Rc));
   hipStream_t s = (hipStream_t)stream;
   const int Bs = in_caller->B;  // the state's samples
   fmi_flux_inputs in_cfg;
@@ -1612,7 +1649,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
     FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>() + Bs, in_caller->guidance, (size_t)Bs * 4, hipMemcpyDeviceToDevice, s));
     in_cfg.guidance = m->cfg_gd.as<float>();
   }
-  FMI_TRY(prepare_static(m, in, ctx, Rc, s, cfg));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
+  FMI_TRY(prepare_static(m, in, ctx, Rc, s, cfg, ctl));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
   const int64_t n = (int64_t)Bs * in->S * m->cfg.in_channels;
   // t_vec = full(1f32, B) * t_curr  (sampling.rs:35,42): all steps' vectors uploaded once
   std::vector<float> tv((size_t)(n_steps > 0 ? n_steps : 1) * B);
@@ -1707,6 +1744,12 @@ extern "C" int fmi_flux_denoise_cfg(fmi_flux* m, const fmi_flux_inputs* in, cons
                                     const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
   if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: x0, noise and mask go together (all three or none)");
   return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, nullptr, cfg);
+}
+// The loop of fmi_flux_denoise_cfg without a context and with a control; on a plain model a null ctl IS fmi_flux_denoise_cfg without a context.
+extern "C" int fmi_flux_denoise_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg, float* img_inout,
+                                        const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
+  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_control: x0, noise and mask go together (all three or none)");
+  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, nullptr, cfg, ctl);
 }
 // device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
 extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {

@@ -337,6 +337,58 @@ int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t*
   return fail(FMI_ERR_INVALID, "cast_rows_bf16: the source must be F32 or BF16");
 }
 
+namespace {
+// A column window of a wider bf16 matrix: row r of src (rows_src, cols), read at r % rows_src, -> dst[r * dst_ld + col0 .. + cols) (f32_to_bf16, a bf16 source
+// comes through unchanged); the columns outside the window are never written.  V8: one item = 8 elements, read as 16-B words and written as one (cols, dst_ld,
+// col0 multiples of 8 make every row's window 16-B aligned when the bases are); else one element per item, any alignment.
+template <typename T, bool V8>
+__global__ __launch_bounds__(256) void cast_cols_bf16_kernel(const T* __restrict__ src, int64_t rows_src, int cols, bf16_t* __restrict__ dst, int64_t dst_ld, int col0,
+                                                             int64_t items) {
+  const int per = V8 ? cols / 8 : cols;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / per;
+    const int c = (int)(i % per) * (V8 ? 8 : 1);
+    const T* s = src + (r % rows_src) * cols + c;
+    bf16_t* d = dst + r * dst_ld + col0 + c;
+    if constexpr (!V8) {
+      d[0] = f32_to_bf16(row_elem_f32(s[0]));
+    } else if constexpr (sizeof(T) == 4) {
+      const float4 lo = *reinterpret_cast<const float4*>(s), hi = *reinterpret_cast<const float4*>(s + 4);
+      uint4 o;
+      o.x = (uint32_t)f32_to_bf16(lo.x) | ((uint32_t)f32_to_bf16(lo.y) << 16), o.y = (uint32_t)f32_to_bf16(lo.z) | ((uint32_t)f32_to_bf16(lo.w) << 16);
+      o.z = (uint32_t)f32_to_bf16(hi.x) | ((uint32_t)f32_to_bf16(hi.y) << 16), o.w = (uint32_t)f32_to_bf16(hi.z) | ((uint32_t)f32_to_bf16(hi.w) << 16);
+      *reinterpret_cast<uint4*>(d) = o;
+    } else {
+      *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
+    }
+  }
+}
+template <typename T>
+int launch_cast_cols_bf16_t(const T* src, int64_t rows, int64_t rows_src, int cols, bf16_t* dst, int dst_ld, int col0, hipStream_t stream) {
+  if (aligned16(src) && aligned16(dst)) {
+    const int64_t items = rows * (cols / 8);
+    hipLaunchKernelGGL((cast_cols_bf16_kernel<T, true>), map_grid(items), dim3(256), 0, stream, src, rows_src, cols, dst, (int64_t)dst_ld, col0, items);
+  } else {
+    const int64_t items = rows * cols;
+    hipLaunchKernelGGL((cast_cols_bf16_kernel<T, false>), map_grid(items), dim3(256), 0, stream, src, rows_src, cols, dst, (int64_t)dst_ld, col0, items);
+  }
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+}  // namespace
+// The x_embedder operand of a channel-conditioned model is (B*S, 64 + Cc) bf16: the f32 state goes into columns [0, 64) every step — under true
+// CFG into both halves of the batch, rows_src = Bs * S — and the conditioning into [64, 64 + Cc) once per call, each in one launch of this cast.
+int launch_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t rows_src, int cols, bf16_t* dst, int dst_ld, int col0, hipStream_t stream) {
+  if (!src || !dst || rows < 0 || rows_src <= 0 || cols <= 0 || dst_ld <= 0 || col0 < 0) return fail(FMI_ERR_INVALID, "cast_cols_bf16: bad arguments");
+  if (cols % 8 || dst_ld % 8 || col0 % 8) return fail(FMI_ERR_INVALID, "cast_cols_bf16: cols, dst_ld and col0 must be multiples of 8");
+  if ((int64_t)col0 + cols > dst_ld) return fail(FMI_ERR_INVALID, "cast_cols_bf16: the window [col0, col0 + cols) must lie inside a row of dst_ld");
+  if (rows % rows_src) return fail(FMI_ERR_INVALID, "cast_cols_bf16: rows_src must divide rows");
+  if (rows == 0) return FMI_OK;
+  if (dt == FMI_F32) return launch_cast_cols_bf16_t((const float*)src, rows, rows_src, cols, dst, dst_ld, col0, stream);
+  if (dt == FMI_BF16) return launch_cast_cols_bf16_t((const bf16_t*)src, rows, rows_src, cols, dst, dst_ld, col0, stream);
+  return fail(FMI_ERR_INVALID, "cast_cols_bf16: the source must be F32 or BF16");
+}
+
 // y[r][n] = (y[r][n] + g[r % B][n]) + v[r % B][n]: the step-invariant terms of `vec` added in the order the accumulating GEMVs added them
 int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int N, hipStream_t stream) {
   const int64_t n = (int64_t)R * N;
@@ -573,6 +625,94 @@ extern "C" int fmi_latent_ids(int B, int h2, int w2, float id0, float row0, floa
     float* o = ids_out + tok * 3;
     o[0] = id0, o[1] = __fadd_rn(row0, (float)r), o[2] = __fadd_rn(col0, (float)c);
   });
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+// ---- channel-concatenated conditioning glue (FLUX.1 Fill / Canny / Depth)
+namespace {
+__device__ __forceinline__ float mask_bit(float m) { return m >= 0.5f ? 1.0f : 0.0f; }  // diffusers' mask processor binarises at 0.5 (a NaN counts as 0)
+// out = image * (1 - b): V = float4 (W % 4 == 0: a word never straddles two rows or images) or float
+template <typename V>
+__global__ __launch_bounds__(256) void mask_image_kernel(const V* __restrict__ image, const V* __restrict__ mask, int64_t HWv, int C, V* __restrict__ out, int64_t items) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = i % HWv, b = i / (HWv * C);
+    const V x = image[i], m = mask[b * HWv + p];
+    if constexpr (sizeof(V) == 16)
+      out[i] = make_float4(x.x * (1.0f - mask_bit(m.x)), x.y * (1.0f - mask_bit(m.y)), x.z * (1.0f - mask_bit(m.z)), x.w * (1.0f - mask_bit(m.w)));
+    else
+      out[i] = x * (1.0f - mask_bit(m));
+  }
+}
+// Twelve items per token.  Items 0..3: 16 of the token's 64 latent values, copied.  Items 4..11: py = item - 4 — the 16 mask pixels of rows 16i + py and
+// 16i + 8 + py (dy = 0, 1) of the token's 16x16 square, binarised, become the 32 columns 64 + (py * 8 + px) * 4 + dy * 2 + dx with px = 0..7, dx = 0, 1 the
+// pixel 8 dx + px of those rows: four 16-B loads per row, eight 16-B stores.
+template <bool V4>
+__global__ __launch_bounds__(256) void fill_condition_kernel(const float* __restrict__ lat, const float* __restrict__ mask, int H, int W, float* __restrict__ out,
+                                                             int64_t items) {
+  const int h2 = H / 16, w2 = W / 16;
+  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const int q = (int)(it % 12);
+    const int64_t tok = it / 12;
+    float* o = out + tok * 320;
+    if (q < 4) {
+      const float* s = lat + tok * 64 + q * 16;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if constexpr (V4)
+          *reinterpret_cast<float4*>(o + q * 16 + 4 * k) = *reinterpret_cast<const float4*>(s + 4 * k);
+        else
+          store4<false>(o + q * 16 + 4 * k, s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+      }
+      continue;
+    }
+    const int py = q - 4;
+    const int j = (int)(tok % w2), ii = (int)((tok / w2) % h2);
+    const int64_t b = tok / ((int64_t)w2 * h2);
+    const float* r0 = mask + (b * H + 16 * ii + py) * W + 16 * j;  // dy = 0
+    const float* r1 = r0 + (int64_t)8 * W;                          // dy = 1
+    __attribute__((aligned(16))) float a[16], c[16];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if constexpr (V4) {
+        *reinterpret_cast<float4*>(a + 4 * k) = *reinterpret_cast<const float4*>(r0 + 4 * k);
+        *reinterpret_cast<float4*>(c + 4 * k) = *reinterpret_cast<const float4*>(r1 + 4 * k);
+      } else {
+        for (int e = 0; e < 4; ++e) a[4 * k + e] = r0[4 * k + e], c[4 * k + e] = r1[4 * k + e];
+      }
+    }
+#pragma unroll
+    for (int px = 0; px < 8; ++px) store4<V4>(o + 64 + (py * 8 + px) * 4, mask_bit(a[px]), mask_bit(a[8 + px]), mask_bit(c[px]), mask_bit(c[8 + px]));
+  }
+}
+}  // namespace
+
+extern "C" int fmi_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t rows_src, int cols, void* dst_bf16, int dst_ld, int col0, void* stream) {
+  return launch_cast_cols_bf16(src, dt, rows, rows_src, cols, (bf16_t*)dst_bf16, dst_ld, col0, (hipStream_t)stream);
+}
+
+extern "C" int fmi_mask_image(const float* image, const float* mask, int B, int C, int H, int W, float* out, void* stream) {
+  if (!image || !mask || !out || B < 0 || C <= 0 || H <= 0 || W <= 0) return fail(FMI_ERR_INVALID, "mask_image: bad arguments");
+  const int64_t HW = (int64_t)H * W, n = (int64_t)B * C * HW;
+  if (n == 0) return FMI_OK;
+  if (HW % 4 == 0 && aligned16(image) && aligned16(mask) && aligned16(out))
+    hipLaunchKernelGGL(mask_image_kernel<float4>, map_grid(n / 4), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(image),
+                       reinterpret_cast<const float4*>(mask), HW / 4, C, reinterpret_cast<float4*>(out), n / 4);
+  else
+    hipLaunchKernelGGL(mask_image_kernel<float>, map_grid(n), dim3(256), 0, (hipStream_t)stream, image, mask, HW, C, out, n);
+  FMI_LAUNCH_CHECK();
+  return FMI_OK;
+}
+
+extern "C" int fmi_fill_condition(const float* masked_latents, const float* mask, int B, int H, int W, float* cond_out, void* stream) {
+  if (!masked_latents || !mask || !cond_out || B < 0) return fail(FMI_ERR_INVALID, "fill_condition: bad arguments");
+  if (H <= 0 || W <= 0 || H % 16 || W % 16) return fail(FMI_ERR_INVALID, "fill_condition: H and W must be positive multiples of 16");
+  const int64_t items = (int64_t)B * (H / 16) * (W / 16) * 12;
+  if (items == 0) return FMI_OK;
+  if (aligned16(masked_latents) && aligned16(mask) && aligned16(cond_out))  // W % 16 == 0: every 16-pixel row segment is then 16-B aligned too
+    hipLaunchKernelGGL(fill_condition_kernel<true>, map_grid(items), dim3(256), 0, (hipStream_t)stream, masked_latents, mask, H, W, cond_out, items);
+  else
+    hipLaunchKernelGGL(fill_condition_kernel<false>, map_grid(items), dim3(256), 0, (hipStream_t)stream, masked_latents, mask, H, W, cond_out, items);
   FMI_LAUNCH_CHECK();
   return FMI_OK;
 }

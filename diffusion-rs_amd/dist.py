@@ -455,7 +455,7 @@ def sequence_parallel_rank_time(flux, world_size: int, timesteps, device, S: int
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
         Sl, Tl = S // N, T // N
-        lat = torch.randn((1, Sl, cfg["in_channels"]), generator=g, device=dev)
+        lat = torch.randn((1, Sl, cfg.get("out_channels") or cfg["in_channels"]), generator=g, device=dev)  # the state's width
         ids = torch.zeros((1, Sl, 3), device=dev)
         txt = torch.randn((1, Tl, cfg["joint_attention_dim"]), generator=g, device=dev).to(torch.bfloat16)
         tids = torch.zeros((1, Tl, 3), device=dev)

@@ -136,15 +136,47 @@ def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_
     return scale
 
 
+def state_channels(cfg: dict) -> int:
+    """The width of the state, of the prediction and of proj_out's rows: diffusers' out_channels, which a config without one (or with null) takes from
+    in_channels.  cfg["in_channels"] keeps diffusers' meaning, x_embedder's K; the difference is the conditioning channels."""
+    return int(cfg.get("out_channels") or cfg["in_channels"])
+
+
+def check_control_args(cond_channels: int, img_shape, control_shape=None, has_context: bool = False, cache_args: bool = False, sequence_parallel: bool = False):
+    """The control of FluxModel.forward / denoise (fmi_flux_forward_control / fmi_flux_denoise_control), checked without the library.
+    ValueError: a channel-conditioned model without control=; control= on a plain model; a control that is not (B,S,cond_channels) for img (B,S,C); a control
+    with context=, with the step cache's arguments, or under sequence parallelism."""
+    if control_shape is None:
+        if cond_channels:
+            raise ValueError(f"this model has {cond_channels} conditioning channels: control= (B,S,{cond_channels}) is required")
+        return
+    if not cond_channels:
+        raise ValueError("control= needs a channel-conditioned model (in_channels > out_channels: FLUX.1 Fill / Canny / Depth)")
+    if tuple(control_shape) != (int(img_shape[0]), int(img_shape[1]), cond_channels):
+        raise ValueError(f"control is {tuple(control_shape)}, expected {(int(img_shape[0]), int(img_shape[1]), cond_channels)} for img {tuple(img_shape)}")
+    if has_context:
+        raise ValueError("control= is not combined with context= (a reference image)")
+    if cache_args:
+        raise ValueError("control= is not combined with the step cache (cache_threshold= / cache_force=)")
+    if sequence_parallel:
+        raise ValueError("control= is not supported under sequence parallelism")
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
         self.cfg = dict(cfg)
+        # cfg["in_channels"] is x_embedder's K as in diffusers; the state is out_channels wide and the rest are conditioning channels (DESIGN.md 4.13)
+        self.state_channels = state_channels(cfg)
+        self.cond_channels = int(cfg["in_channels"]) - self.state_channels
         L.check(self.lib.fmi_init(device), self.lib)
-        c = L.FluxConfig(cfg["in_channels"], cfg["pooled_projection_dim"], cfg["joint_attention_dim"], cfg["num_attention_heads"],
+        c = L.FluxConfig(self.state_channels, cfg["pooled_projection_dim"], cfg["joint_attention_dim"], cfg["num_attention_heads"],
                          cfg["num_layers"], cfg["num_single_layers"], int(cfg["guidance_embeds"]), (C.c_int * 3)(*cfg["axes_dim"]), cfg["theta"])
         h = C.c_void_p()
-        L.check(self.lib.fmi_flux_create(C.byref(c), L.MODEL_BF16, C.byref(h)), self.lib)
+        if self.cond_channels:  # (a negative or misaligned difference is the library's FMI_ERR_INVALID)
+            L.check(self.lib.fmi_flux_create_cond(C.byref(c), self.cond_channels, L.MODEL_BF16, C.byref(h)), self.lib)
+        else:
+            L.check(self.lib.fmi_flux_create(C.byref(c), L.MODEL_BF16, C.byref(h)), self.lib)
         self.h = h
         self.hidden = cfg["num_attention_heads"] * 128
         self.device = torch.device("cuda", device)
@@ -374,19 +406,36 @@ class FluxModel:
         B, R = int(context.shape[0]), int(context.shape[1])
         if B != int(img_ids.shape[0]) or tuple(context_ids.shape) != (B, R, 3):
             raise ValueError(f"context is {tuple(context.shape)} and context_ids {tuple(context_ids.shape)} for a batch of {int(img_ids.shape[0])}")
-        if int(context.shape[2]) != self.cfg["in_channels"]:
-            raise ValueError(f"context has {int(context.shape[2])} channels, the model's in_channels is {self.cfg['in_channels']}")
+        if int(context.shape[2]) != self.state_channels:
+            raise ValueError(f"context has {int(context.shape[2])} channels, the model's state has {self.state_channels}")
         if context.device != img_ids.device or context_ids.device != img_ids.device:
             raise ValueError(f"context is on {context.device} and context_ids on {context_ids.device}, img_ids on {img_ids.device}")
         # (a tensor that is contiguous already is passed as it lies, whatever its address: the library picks the access width)
         keep = [context.contiguous(), context_ids.contiguous()]
         return L.FluxContext(_ptr(keep[0]), _TORCH_DT[context.dtype], _ptr(keep[1]), R), keep
 
-    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None):
+    def _control(self, img, control):
+        """fmi_flux_control of the conditioning channels (B,S,cond_channels) f32 | bf16, with the tensor it points into."""
+        if control.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("control must be float32 or bfloat16")
+        if control.device != img.device:
+            raise ValueError(f"control is on {control.device}, img on {img.device}")
+        keep = control.contiguous()
+        return L.FluxControl(_ptr(keep), _TORCH_DT[control.dtype]), keep
+
+    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None, control=None):
         """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.
-        context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's."""
+        context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's.
+        control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_forward_control): the
+        evaluation is Flux::forward on cat([img, control], 2) and the velocity stays img's width.  Required on such a model, refused on any other."""
+        check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
+                           False, getattr(self, "_sp_world", 1) > 1)
         inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
         pred = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        if control is not None:
+            ctl, keep_ctl = self._control(img, control)
+            L.check(self.lib.fmi_flux_forward_control(self.h, C.byref(inp), C.byref(ctl), _ptr(pred), _stream()), self.lib)
+            return pred
         if context is None and context_ids is None:
             L.check(self.lib.fmi_flux_forward(self.h, C.byref(inp), _ptr(pred), _stream()), self.lib)
             return pred
@@ -395,7 +444,7 @@ class FluxModel:
         return pred
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
-                cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None):
+                cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
@@ -409,8 +458,13 @@ class FluxModel:
         negative_txt= / negative_y= / true_cfg_scale=: true classifier-free guidance (fmi_flux_denoise_cfg).  The negative prompt's embeddings,
         shaped like txt and y (f32 | bf16); every step evaluates the prompt and the negative in ONE batch of 2 B samples on the same state, ids, guidance and
         context, and steps along neg + true_cfg_scale * (pos - neg) (default scale 1.0; any finite scale >= 0).  B <= 4; not with the step cache, not under
-        sequence parallelism; works with x0 / noise / mask and with context=."""
+        sequence parallelism; works with x0 / noise / mask and with context=.
+        control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_denoise_control), the same at
+        every step and, under true CFG, for the prompt and the negative; the state stays (B,S,C).  Required on such a model, refused on any other; works with
+        x0 / noise / mask and the negative, not with context=, the step cache or sequence parallelism."""
         n_steps = len(timesteps) - 1
+        check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
+                           cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
         cfg_scale = check_true_cfg_args(tuple(txt.shape), tuple(y.shape), None if negative_txt is None else tuple(negative_txt.shape),
                                         None if negative_y is None else tuple(negative_y.shape), true_cfg_scale,
                                         cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
@@ -425,6 +479,7 @@ class FluxModel:
         has_ctx = context is not None or context_ids is not None
         ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
         blend = [_ptr(t) for t in keep_blend]  # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
+        ctl, keep_ctl = self._control(img, control) if control is not None else (None, None)
         if cfg_scale is not None:
             for t, nm in ((negative_txt, "negative_txt"), (negative_y, "negative_y")):
                 if t.dtype not in (torch.float32, torch.bfloat16):
@@ -433,7 +488,12 @@ class FluxModel:
                     raise ValueError(f"{nm} is on {t.device}, img on {img.device}")
             keep_neg = [negative_txt.contiguous(), negative_y.contiguous()]
             tc = L.FluxTrueCfg(_ptr(keep_neg[0]), _TORCH_DT[negative_txt.dtype], _ptr(keep_neg[1]), _TORCH_DT[negative_y.dtype], cfg_scale)
-            st = self.lib.fmi_flux_denoise_cfg(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
+            if ctl is not None:
+                st = self.lib.fmi_flux_denoise_control(self.h, C.byref(inp), C.byref(ctl), C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
+            else:
+                st = self.lib.fmi_flux_denoise_cfg(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
+        elif ctl is not None:
+            st = self.lib.fmi_flux_denoise_control(self.h, C.byref(inp), C.byref(ctl), None, _ptr(img), ts, n_steps, *blend, _stream())
         elif thr is not None:
             decisions = np.zeros(max(n_steps, 0), np.int32)
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
@@ -596,6 +656,47 @@ def latent_mask(mask, Cc=16):
         raise ValueError(f"latent_mask: H and W must be multiples of 16, got {H} x {W}")
     out = torch.empty((B, (H // 16) * (W // 16), Cc * 4), dtype=torch.float32, device=mask.device)
     L.check(L.load().fmi_latent_mask(_ptr(mask), B, Cc, H, W, _ptr(out), _stream()))
+    return out
+
+
+# ---- channel-concatenated conditioning glue (FLUX.1 Fill / Canny / Depth)
+def cast_cols_bf16(src, dst, col0, rows=None):
+    """fmi_cast_cols_bf16, in place on dst and returning it: row r of src (rows_src, cols) f32 | bf16, read at r % rows_src, -> dst[r, col0 : col0 + cols] as
+    bf16 (round to nearest even), for r < rows (default: dst's rows); dst (rows, dst_ld) bf16, its other columns untouched.  cols, dst_ld, col0 multiples of 8."""
+    if src.dim() != 2 or dst.dim() != 2 or dst.dtype != torch.bfloat16 or src.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("cast_cols_bf16: src (rows_src, cols) float32 | bfloat16 and dst (rows, dst_ld) bfloat16 are required")
+    if not (src.is_contiguous() and dst.is_contiguous()) or src.device != dst.device:
+        raise TypeError("cast_cols_bf16: contiguous tensors on one device are required")
+    rows = int(dst.shape[0]) if rows is None else int(rows)
+    if rows > dst.shape[0]:
+        raise ValueError(f"cast_cols_bf16: {rows} rows do not fit dst {tuple(dst.shape)}")
+    L.check(L.load().fmi_cast_cols_bf16(_ptr(src), _TORCH_DT[src.dtype], rows, int(src.shape[0]), int(src.shape[1]), _ptr(dst), int(dst.shape[1]), int(col0), _stream()))
+    return dst
+
+
+def mask_image(image, mask):
+    """The masked image of a Fill request: image (B,C,H,W) f32 * (1 - b) with b = mask >= 0.5 (mask (B,H,W) f32, 1 = fill), as diffusers' FluxFillPipeline."""
+    image, mask = image.to(torch.float32).contiguous(), mask.to(torch.float32).contiguous()
+    B, Cc, H, W = image.shape
+    if tuple(mask.shape) != (B, H, W):
+        raise ValueError(f"mask_image: mask is {tuple(mask.shape)}, image is {tuple(image.shape)}")
+    out = torch.empty_like(image)
+    L.check(L.load().fmi_mask_image(_ptr(image), _ptr(mask), B, Cc, H, W, _ptr(out), _stream()))
+    return out
+
+
+def fill_condition(masked_latents, mask):
+    """FLUX.1 Fill's 320 conditioning channels (B,S,320) f32: the packed latents of the masked image (B,S,64) next to the binarised mask (B,H,W), pixel-
+    unshuffled by 8 and packed 2x2 (256 channels); H and W multiples of 16, S = (H/16)(W/16)."""
+    masked_latents, mask = masked_latents.to(torch.float32).contiguous(), mask.to(torch.float32).contiguous()
+    B, H, W = mask.shape
+    if H % 16 or W % 16:
+        raise ValueError(f"fill_condition: H and W must be multiples of 16, got {H} x {W}")
+    S = (H // 16) * (W // 16)
+    if tuple(masked_latents.shape) != (B, S, 64):
+        raise ValueError(f"fill_condition: masked_latents is {tuple(masked_latents.shape)}, expected {(B, S, 64)}")
+    out = torch.empty((B, S, 320), dtype=torch.float32, device=mask.device)
+    L.check(L.load().fmi_fill_condition(_ptr(masked_latents), _ptr(mask), B, H, W, _ptr(out), _stream()))
     return out
 
 

@@ -18,7 +18,7 @@ import mmap
 import os
 import struct
 import zipfile
-from typing import Dict, Iterator, List, Tuple
+from typing import Dict, Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -37,6 +37,31 @@ def check_pipeline_class(class_name) -> str:
     if class_name not in SUPPORTED_PIPELINES:
         raise ValueError("Only FluxPipeline is supported")
     return class_name
+
+
+# model_index.json's `_class_name` -> how the transformer is conditioned: None = on the text alone (a Kontext reference joins per request),
+# "control" = the 64 latent channels of a control image next to the state's (FLUX.1 Canny-dev / Depth-dev), "fill" = the 64 masked-image latents and 256 mask
+# channels of FLUX.1 Fill-dev.  The value is in_channels - out_channels of transformer/config.json.
+PIPELINE_CONDITIONING = {"FluxPipeline": None, "FluxKontextPipeline": None, "FluxControlPipeline": "control", "FluxFillPipeline": "fill"}
+CONDITIONING_CHANNELS = {None: 0, "control": 64, "fill": 320}
+
+
+def pipeline_conditioning(class_name) -> Optional[str]:
+    """The conditioning of a pipeline class this package loads (None | "control" | "fill"), or check_pipeline_class's ValueError for any other."""
+    if class_name not in PIPELINE_CONDITIONING:
+        raise ValueError("Only FluxPipeline is supported")
+    return PIPELINE_CONDITIONING[class_name]
+
+
+def check_conditioning_channels(class_name, in_channels: int, out_channels=None) -> Optional[str]:
+    """pipeline_conditioning(class_name), checked against transformer/config.json: in_channels - out_channels (null / absent: in_channels) must be the
+    class's 0 / 64 / 320, else ValueError."""
+    kind = pipeline_conditioning(class_name)
+    extra = int(in_channels) - int(out_channels or in_channels)
+    if extra != CONDITIONING_CHANNELS[kind]:
+        raise ValueError(f"{class_name} expects {CONDITIONING_CHANNELS[kind]} conditioning channels, transformer/config.json has in_channels {in_channels} and "
+                         f"out_channels {out_channels} ({extra})")
+    return kind
 
 
 def _safetensors_from_buffer(buf) -> Iterator[Tuple[str, torch.Tensor]]:

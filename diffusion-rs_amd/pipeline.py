@@ -204,6 +204,57 @@ class _Negative:
     token_ids: Optional[tuple] = None  # (t5 (1,T'), clip (1,.))
 
 
+@dataclass(frozen=True)
+class _Control:
+    """The control of a request to a channel-conditioned model (FLUX.1 Fill / Canny / Depth): ONE per request, shared by its prompts like the
+    negative — not a per-sample input, so no field of _Samples; every chunk and every rank of the request receives this same object and expands it to its rows.
+    kind "control": image is the control image (a Canny edge map, a depth map); kind "fill": image is the picture to fill and mask says where (1 = fill)."""
+    kind: str  # "control" | "fill"
+    image: torch.Tensor  # (1,3,H,W) f32 in [-1,1], on the device
+    mask: Optional[torch.Tensor] = None  # (1,H,W) f32, on the device; kind "fill" only
+
+
+def control_kind(cond_channels: int) -> Optional[str]:
+    """What a model's conditioning channels hold: 0 -> None, 64 -> "control" (the control image's latents), 320 -> "fill" (masked-image latents + 256 mask
+    channels); ValueError for any other width (no pipeline builds such a condition)."""
+    kinds = {0: None, 64: "control", 320: "fill"}
+    if cond_channels not in kinds:
+        raise ValueError(f"a model with {cond_channels} conditioning channels is neither FLUX.1 Canny / Depth (64) nor Fill (320): build the condition yourself "
+                         f"and call FluxModel.denoise(control=)")
+    return kinds[cond_channels]
+
+
+def check_control_request(kind: Optional[str], height: int, width: int, image_shape=None, image_is_u8: bool = False, mask_shape=None, reference: bool = False,
+                          cache_threshold: bool = False, sequence_parallel: bool = False):
+    """The control arguments of a request, checked without a device (kind: control_kind of the model).  ValueError: control_image= / control_mask= on a plain
+    model; a conditioned model without control_image=; control_mask= missing on a Fill model or given to a Canny / Depth model; a height or width that is no
+    multiple of 16; an image that is not u8 (H,W,3) or float (1,3,H,W) at the request's size; a mask that is not (H,W); reference=, cache_threshold= or
+    sequence parallelism next to a control."""
+    if kind is None:
+        if image_shape is not None or mask_shape is not None:
+            raise ValueError("control_image= / control_mask= need a channel-conditioned model (FLUX.1 Fill / Canny / Depth)")
+        return
+    if image_shape is None:
+        raise ValueError(f"this model is conditioned on an image ({'FLUX.1 Fill' if kind == 'fill' else 'FLUX.1 Canny / Depth'}): control_image= is required")
+    if kind == "fill" and mask_shape is None:
+        raise ValueError("a Fill model needs control_mask= ((H,W), 1 = fill)")
+    if kind != "fill" and mask_shape is not None:
+        raise ValueError("control_mask= goes with a Fill model; a Canny / Depth model takes control_image= alone")
+    if height % 16 or width % 16:
+        raise ValueError(f"control_image= needs height and width that are multiples of 16, got {height} x {width}")
+    want = (height, width, 3) if image_is_u8 else (1, 3, height, width)
+    if tuple(image_shape) != want:
+        raise ValueError(f"control_image must be uint8 ({height},{width},3) or float (1,3,{height},{width}) as params say, got {tuple(image_shape)}")
+    if mask_shape is not None and tuple(mask_shape) != (height, width):
+        raise ValueError(f"control_mask must be ({height},{width}) as params say, got {tuple(mask_shape)}")
+    if reference:
+        raise ValueError("a control is not combined with reference= (a context)")
+    if cache_threshold:
+        raise ValueError("a control is not combined with the step cache (cache_threshold=)")
+    if sequence_parallel:
+        raise ValueError("a control is not wired through sequence parallelism: disable_sequence_parallel() first")
+
+
 def _index_sets(B: int, max_batch: int, one_by_one: bool) -> list:
     """The row sets a request of any B runs in (pipelines/mod.rs:241-270): chunks of max_batch, or single samples (sequence parallel: ONE image at a time)."""
     n = 1 if one_by_one else max_batch
@@ -242,7 +293,8 @@ class Pipeline:
                 if rank == 0:
                     self._dit_loader()
                 self.vae = F.AutoEncoderKl(vcfg, device)
-                synth.fill_vae_random_device(self.vae, seed=source.seed + 1, device=self.device)
+                # (a channel-conditioned model encodes its control image at every request: the encoder's weights too — the decoder's keep their values)
+                synth.fill_vae_random_device(self.vae, seed=source.seed + 1, device=self.device, encoder=bool(self.flux.cond_channels))
                 if source.variant != "dev":
                     self.scheduler = F.SchedulerConfig(shift=1.0, use_dynamic_shifting=False)
                 if getattr(source, "text_encoders", False):
@@ -285,14 +337,16 @@ class Pipeline:
     def _load_checkpoint(self, path: str, transformer_path: Optional[str], load_dit: bool = True):
         from . import loader
         fl = loader.FileLoader(path)
-        loader.check_pipeline_class(fl.read_json("model_index.json").get("_class_name"))  # pipelines/mod.rs:146-149; FluxKontextPipeline has the same components
+        class_name = fl.read_json("model_index.json").get("_class_name")
+        loader.pipeline_conditioning(class_name)  # pipelines/mod.rs:146-149; Kontext, Control (Canny / Depth) and Fill have FluxPipeline's components
         sc = fl.read_json("scheduler/scheduler_config.json")
         self.scheduler = F.SchedulerConfig(sc["base_image_seq_len"], sc["base_shift"], sc["max_image_seq_len"], sc["max_shift"], sc["shift"],
                                            sc["use_dynamic_shifting"])
         tl = loader.FileLoader(transformer_path) if transformer_path else fl  # ModelIdWithTransformer (model_source.rs:22-25)
         tc = tl.read_json("transformer/config.json")
-        fcfg = dict(F.FLUX_DEV, **{k: tc[k] for k in ("in_channels", "pooled_projection_dim", "joint_attention_dim", "num_attention_heads", "num_layers",
-                                                     "num_single_layers", "guidance_embeds") if k in tc})
+        fcfg = dict(F.FLUX_DEV, **{k: tc[k] for k in ("in_channels", "out_channels", "pooled_projection_dim", "joint_attention_dim", "num_attention_heads",
+                                                     "num_layers", "num_single_layers", "guidance_embeds") if k in tc})
+        loader.check_conditioning_channels(class_name, fcfg["in_channels"], fcfg.get("out_channels"))  # the class and the embedder's width agree
         self.flux = F.FluxModel(fcfg, self.device_index)
         self._dit_loader = lambda: self.load_stats.update(loader.load_flux(self.flux, tl.tensors("transformer")))
         if load_dit:  # (multi-GPU: the other ranks receive the weight arenas, dist.broadcast_state)
@@ -416,7 +470,8 @@ class Pipeline:
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0):
+                        negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
+                        control_image=None, control_mask=None):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -446,9 +501,19 @@ class Pipeline:
         negative takes the prompt's T: with tokenizers it is tokenised and encoded together with the chunk's prompts; negative_embeddings= / negative_token_ids=
         must have the T of embeddings= / token_ids=.  A negative with true_cfg_scale <= 1 is ignored, as in diffusers (today's launches); true_cfg_scale > 1
         without a negative raises (diffusers only warns).  Combines with image= / strength= / mask= / reference=; raises with cache_threshold= and under
-        sequence parallelism.  No scale is recommended: there are no real weights here to judge one."""
+        sequence parallelism.  No scale is recommended: there are no real weights here to judge one.
+
+        Channel-concatenated conditioning (`control_image=` / `control_mask=`; FLUX.1 Canny-dev / Depth-dev and Fill-dev, diffusers'
+        FluxControlPipeline / FluxFillPipeline): ONE control per request, shared by its prompts.  control_image: u8 (H,W,3) or f32 (1,3,H,W) in [-1,1] at
+        params.height x width (multiples of 16; nothing is resized).  On a Canny / Depth model it is the control image: its VAE latents (the posterior MEAN, as for
+        image=; diffusers samples the posterior) are 64 more input channels of every model evaluation.  On a Fill model it is the picture to fill and
+        `control_mask=` ((H,W) bool / float, 1 = fill; binarised at 0.5) says where: the latents of image * (1 - mask) and the 256 unshuffled mask channels are the
+        320 more.  The loop starts from noise and runs the whole schedule; image= / strength= / mask= and the negative keep their meaning and combine with it.
+        Required on such a model and refused on any other; raises with reference=, cache_threshold= and under sequence parallelism.  No guidance scale is
+        recommended: there are no real weights here to judge one."""
         if cache_threshold is not None:
             F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
+        ctl = self._control(control_image, control_mask, params, reference, cache_threshold)
         neg = self._negative(negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids)
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
@@ -457,12 +522,48 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        # (the negative is a keyword of true-CFG requests only: any other request makes exactly the call it always made)
-        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **({} if neg is None else dict(negative=neg)))
+        # (the negative is a keyword of true-CFG requests only, the control of controlled ones: any other request makes exactly the call it always made)
+        extra = dict(**({} if neg is None else dict(negative=neg)), **({} if ctl is None else dict(control=ctl)))
+        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **extra)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
             return outs[0]
         return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
+
+    def _control(self, control_image, control_mask, params, reference, cache_threshold) -> Optional[_Control]:
+        """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share."""
+        def as_tensor(x, what):
+            t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+            if x is not None and not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what} must be a numpy array or a torch tensor")
+            return t
+
+        img, m = as_tensor(control_image, "control_image"), as_tensor(control_mask, "control_mask")
+        if img is not None and not (img.dtype == torch.uint8 or img.is_floating_point()):
+            raise ValueError(f"control_image must be uint8 or float, got {img.dtype}")
+        if m is not None and not (m.dtype == torch.bool or m.is_floating_point()):
+            raise ValueError("control_mask must be a bool or float numpy array or torch tensor")
+        kind = control_kind(getattr(getattr(self, "flux", None), "cond_channels", 0))
+        check_control_request(kind, params.height, params.width, None if img is None else tuple(img.shape), img is not None and img.dtype == torch.uint8,
+                              None if m is None else tuple(m.shape), reference is not None, cache_threshold is not None, getattr(self, "_sp", None) is not None)
+        if kind is None:
+            return None
+        if img.dtype == torch.uint8:
+            img = F.preprocess_u8(img.unsqueeze(0).to(self.device), interleaved=True)
+        else:
+            img = img.to(device=self.device, dtype=torch.float32).contiguous()
+        return _Control(kind, img, None if m is None else m.unsqueeze(0).to(device=self.device, dtype=torch.float32).contiguous())
+
+    def _control_condition(self, control: _Control, B: int):
+        """The conditioning channels (B,S,64 | 320) f32 of a chunk of B samples: built once at one row — VAE encode (the posterior mean), pack, and for Fill the
+        masked image in front of it and the mask channels behind — then expanded."""
+        sf, sh = self.vae.scale_factor(), self.vae.shift_factor()
+        if control.kind == "fill":
+            lat, _ = F.encode_latents(self.vae.encode(F.mask_image(control.image, control.mask)), sf, sh)
+            cond = F.fill_condition(lat, control.mask)
+        else:
+            cond, _ = F.encode_latents(self.vae.encode(control.image), sf, sh)
+        return cond.expand(B, -1, -1).contiguous()
 
     def _negative(self, negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids) -> Optional[_Negative]:
         """The negative of a request, checked once: None when true CFG is off (no negative, or a scale <= 1: diffusers' do_true_cfg), else the object its chunks share."""
@@ -546,9 +647,11 @@ class Pipeline:
         neg = (neg[0].to(t5_emb.dtype).expand(B, -1, -1).contiguous(), neg[1].to(clip_emb.dtype).expand(B, -1).contiguous())
         return t5_emb, clip_emb, neg
 
-    def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None):
+    def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
+                        control: Optional[_Control] = None):
         """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
-        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only."""
+        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only.  control: the request's control
+         — passed by requests to a channel-conditioned model only."""
         cfg = self.flux.cfg
         dev = self.device
         sp = getattr(self, "_sp", None)
@@ -581,6 +684,8 @@ class Pipeline:
             if s.reference is not None:  # its packed latents are rows of every evaluation, never of the state; mu and the schedule above know S only
                 ctx, _ = F.encode_latents(self.vae.encode(s.reference), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
                 context = dict(context=ctx, context_ids=F.latent_ids(B, s.reference.shape[2] // 16, s.reference.shape[3] // 16, id0=1.0, device=dev))
+            if control is not None:  # the same conditioning channels at every step, for every sample and for both halves of a true-CFG batch
+                context = dict(control=self._control_condition(control, B))
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
@@ -677,20 +782,23 @@ class Pipeline:
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
                 reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
-                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, **kw):
+                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
         image= / strength= / mask=: image to image and inpainting, reference=: reference-image conditioning, see generate_tensor; return_latents=True
         returns (images, final packed latents).  cache_threshold=: the first-block step cache, see generate_tensor (None: off); each rank of a sharded batch
         decides for its own prompts and keeps its own `last_cache_stats`.  negative_prompt= / negative_embeddings= / negative_token_ids= / true_cfg_scale=: true
-        classifier-free guidance, see generate_tensor — one negative per request, handed to every rank of a sharded batch unchanged."""
+        classifier-free guidance, see generate_tensor — one negative per request, handed to every rank of a sharded batch unchanged.  control_image= /
+        control_mask=: the control of a channel-conditioned model (FLUX.1 Fill / Canny / Depth), see generate_tensor — one per request, likewise."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
         if negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None or true_cfg_scale != 1.0:
             # (only when one of them is given: any other request makes exactly the generate_tensor call it always made)
             shared.update(negative_prompt=negative_prompt, negative_embeddings=negative_embeddings, negative_token_ids=negative_token_ids, true_cfg_scale=true_cfg_scale)
+        if control_image is not None or control_mask is not None:  # (likewise)
+            shared.update(control_image=control_image, control_mask=control_mask)
         per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if world > 1 and getattr(self, "_sp", None) is None:

@@ -12,7 +12,8 @@ import numpy as np
 def flux_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     D = cfg["num_attention_heads"] * sum(cfg["axes_dim"])
     M = 4 * D
-    C = cfg["in_channels"]
+    C = cfg["in_channels"]  # x_embedder's K, as in diffusers: the state's channels plus a Fill / Canny / Depth checkpoint's conditioning channels
+    Co = cfg.get("out_channels") or C  # the state's width: proj_out's rows
     hd = sum(cfg["axes_dim"])
     t = OrderedDict()
 
@@ -51,7 +52,7 @@ def flux_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
         lin(p + "proj_mlp", M, D)
         lin(p + "proj_out", D, D + M)
     lin("norm_out.linear", 2 * D, D)
-    lin("proj_out", C, D)
+    lin("proj_out", Co, D)
     return t
 
 

@@ -48,6 +48,8 @@ extern "C" {
  *   Then, still 6: the GEMM launcher's test seams — fmi_gemm_desc, fmi_gemm_group, fmi_splitk_resid_gate, fmi_set_gemm_kernel.
  *   Then, still 6: the first-block step cache of the denoise loop — fmi_flux_step_cache, fmi_flux_denoise_cached, fmi_flux_step_cache_bytes.
  *   Then, still 6: true classifier-free guidance (negative prompts) in the denoise loop — fmi_flux_true_cfg, fmi_flux_denoise_cfg, fmi_cfg_euler_step.
+ *   Then, still 6: channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth) — fmi_flux_create_cond, fmi_flux_cond_channels, fmi_flux_control,
+ *   fmi_flux_forward_control, fmi_flux_denoise_control, fmi_cast_cols_bf16, fmi_mask_image, fmi_fill_condition.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -118,6 +120,11 @@ void fmi_flux_default_config(fmi_flux_config* cfg, int guidance_embeds);
 /* Allocate the model: one bf16 weight arena in HBM sized from cfg (23.8 GB for FLUX.1),
  * zero-initialised.  == Flux::new (model.rs:722-787) minus the tensor reads. */
 int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out);
+/* The same for a channel-conditioned checkpoint (FLUX.1 Canny-dev / Depth-dev: cond_channels 64, Fill-dev: 320): x_embedder is
+ * (hidden, in_channels + cond_channels); cfg->in_channels keeps meaning the width of the state, of pred_out and of proj_out's rows (diffusers' out_channels).
+ * cond_channels >= 0, a multiple of 64, in_channels + cond_channels <= 512, else FMI_ERR_INVALID.  fmi_flux_create(cfg, ..) is fmi_flux_create_cond(cfg, 0, ..). */
+int fmi_flux_create_cond(const fmi_flux_config* cfg, int cond_channels, fmi_model_dtype dtype, fmi_flux** out);
+int fmi_flux_cond_channels(const fmi_flux*);
 void fmi_flux_destroy(fmi_flux*);
 
 /* Provide one tensor by its diffusers name, exactly the names VarBuilder looks up in
@@ -458,6 +465,24 @@ int fmi_flux_denoise_cfg(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_co
                          float* img_inout, const double* timesteps_host, int n_steps,
                          const float* x0, const float* noise, const float* mask /* all three or none */, void* stream);
 
+/* Channel-concatenated conditioning (diffusers' FluxControlPipeline and FluxFillPipeline; the reference has no counterpart).  On a model made by
+ * fmi_flux_create_cond with cond_channels > 0 one evaluation is Flux::forward on cat([img, cond], 2): the bf16 x_embedder operand (B*S, in_channels + cond_channels)
+ * takes the state in its first in_channels columns every step and the conditioning in the others once per call (fmi_cast_cols_bf16).  The prediction, the state,
+ * the Euler update, the blend and the CFG combine stay in_channels wide and keep their expressions; under true CFG both halves of the batch see the same cond.
+ * fmi_flux_denoise_control is fmi_flux_denoise_cfg without a context and with a control: cfg NULL is the plain loop, x0 / noise / mask select the blend.  The
+ * once-per-image modulation GEMM, txt_in and the RoPE table are hoisted as ever.  Both entries work in the bf16, int8 and e4m3 modes (x_embedder is not a block
+ * linear) and while int8 calibration records (the forward; the loop without cfg).
+ * FMI_ERR_INVALID, before any launch: ctl or ctl->cond NULL, or a cond_dtype that is not F32 / BF16, on a model with cond_channels > 0 — hence EVERY other forward
+ * / denoise entry on such a model —; a non-NULL ctl on a model with cond_channels == 0 (there a NULL ctl makes these two entries fmi_flux_forward and
+ * fmi_flux_denoise_cfg without a context).  FMI_ERR_UNSUPPORTED: sequence parallelism; a context (fmi_flux_context) together with a control. */
+typedef struct fmi_flux_control {
+  const void* cond; fmi_dtype cond_dtype;   /* (B,S,cond_channels) F32|BF16 */
+} fmi_flux_control;
+int fmi_flux_forward_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream);
+int fmi_flux_denoise_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg /* NULL ok */,
+                             float* img_inout, const double* timesteps_host, int n_steps,
+                             const float* x0, const float* noise, const float* mask /* all three or none */, void* stream);
+
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
  * With FMI_ROCTX=1 in the environment every phase is also a roctx range (roctxRangePushA / Pop from
@@ -627,6 +652,21 @@ int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, fl
  * FMI_ERR_INVALID: a null img / pos / neg, n < 0, a scale that is negative, NaN or infinite, x0 / noise / mask given in part. */
 int fmi_cfg_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n,
                        const float* x0, const float* noise, const float* mask, float s, void* stream);
+/* ---- channel-concatenated conditioning glue (FLUX.1 Fill / Canny / Depth; device pointers, no allocation) ----
+ * A column window of a wider bf16 matrix: row r of src, shaped (rows_src, cols) F32 | BF16 contiguous and read at r % rows_src, goes to
+ * dst[r * dst_ld + col0 .. + cols) as bf16 (round to nearest even; a bf16 source is copied), for r in [0, rows); columns outside the window are not touched.
+ * The per-step kernel of a conditioned model: the f32 state into columns [0, 64) of the (B*S, 64 + Cc) x_embedder operand, both halves of a true-CFG batch in
+ * one launch (rows_src = rows / 2); the conditioning into [64, 64 + Cc) once per call.  16-byte accesses when src and dst are 16-byte aligned, else scalar.
+ * FMI_ERR_INVALID: cols, dst_ld or col0 not a multiple of 8, a window that leaves the row, rows_src not dividing rows, a dtype that is not F32 / BF16. */
+int fmi_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t rows_src, int cols, void* dst_bf16, int dst_ld, int col0, void* stream);
+/* The masked image of a Fill request: out (B,C,H,W) = image * (1 - b), b = mask >= 0.5 ? 1 : 0 with mask (B,H,W) f32, 1 = fill — diffusers' mask processor
+ * binarises, then FluxFillPipeline takes image * (1 - mask). */
+int fmi_mask_image(const float* image, const float* mask, int B, int C, int H, int W, float* out, void* stream);
+/* The 320 conditioning channels of FLUX.1 Fill: cond_out (B,S,320) f32, S = (H/16)(W/16), H and W multiples of 16.  Columns [0, 64) are masked_latents (B,S,64),
+ * the packed VAE latents of the masked image; columns [64, 320) the binarised mask (B,H,W), pixel-unshuffled by 8 and packed 2x2 like the latents:
+ *   cond[b, i*(W/16) + j, 64 + (py*8 + px)*4 + dy*2 + dx] = (mask[b, 16i + 8dy + py, 16j + 8dx + px] >= 0.5)       py, px in 0..7, dy, dx in 0..1
+ * == mask.view(B,h,8,w,8).permute(0,2,4,1,3).reshape(B,64,h,w) followed by fmi_pack_latents. */
+int fmi_fill_condition(const float* masked_latents, const float* mask, int B, int H, int W, float* cond_out, void* stream);
 /* Deterministic N(0,1) latents from a counter-based Philox4x32-10 generator
  * (the reference's RNG is unseedable; this is the explicit-seed extension).
  * Elements 4q..4q+3 of sample b come from the four words of philox(counter = (q lo, q hi, s lo, s hi),
