@@ -834,58 +834,41 @@ int check_ready(fmi_flux* m) {
 // the handle's device becomes the calling thread's current device (hipSetDevice is per thread)
 int use_device(const fmi_flux* m) { return use_device_ordinal(m->device); }
 
+// What the evaluations of one call are conditioned on: the caller's options as validate() accepted them, with what it resolved from them.  Built once per call.
+struct EvalPlan {
+  fmi_flux_denoise_options o;  // every field null where the call has none
+  int R;                       // context rows per sample (0: none, the text-to-image launches)
+  int Bs;                      // the state's samples: in->B — under true CFG `in` is the loop's internal batch of 2 * Bs
+};
+
 // Everything of Flux::forward that does not depend on the timestep: input casts + RoPE table.
-// R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
-// cfg (true CFG): `in` is the loop's internal batch of 2 * Bs samples whose txt / y / ids / context pointers are the caller's Bs samples'; the
+// p.R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
+// p.o.cfg (true CFG): `in` is the loop's internal batch of 2 * Bs samples whose txt / y / ids / context pointers are the caller's Bs samples'; the
 // negative's txt and y fill the second halves, and samples Bs .. 2 Bs - 1 take the table and the context rows of samples 0 .. Bs - 1.  Null: nothing changes.
-// ctl (a channel-conditioned model): the conditioning (Bs, S, cond) goes into columns [C, C + cond) of every row of the img_in operand, once.
-int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, int R, hipStream_t s, const fmi_flux_true_cfg* cfg = nullptr,
-                   const fmi_flux_control* ctl = nullptr) {
+// p.o.ctl (a channel-conditioned model): the conditioning (Bs, S, cond) goes into columns [C, C + cond) of every row of the img_in operand, once.
+int prepare_static(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, hipStream_t s) {
   auto& w = m->ws;
-  const int B = in->B, Bs = cfg ? B / 2 : B, S = in->S, T = in->T, C = m->cfg.in_channels;
+  const fmi_flux_denoise_options& o = p.o;
+  const int B = in->B, Bs = p.Bs, R = p.R, S = in->S, T = in->T, C = m->cfg.in_channels;
   const int64_t n_txt = (int64_t)Bs * T * m->cfg.joint_attention_dim, n_y = (int64_t)Bs * m->cfg.pooled_projection_dim;
   PhaseTimer pt(m, s, PH_EMBED);
   FMI_TRY(launch_cast_to_bf16(in->txt, in->txt_dtype, w.txt_bf, n_txt, s));
   FMI_TRY(launch_cast_to_f32(in->y, in->y_dtype, w.yf, n_y, s));
-  if (cfg) {
-    FMI_TRY(launch_cast_to_bf16(cfg->neg_txt, cfg->neg_txt_dtype, w.txt_bf + n_txt, n_txt, s));
-    FMI_TRY(launch_cast_to_f32(cfg->neg_y, cfg->neg_y_dtype, w.yf + n_y, n_y, s));
+  if (o.cfg) {
+    FMI_TRY(launch_cast_to_bf16(o.cfg->neg_txt, o.cfg->neg_txt_dtype, w.txt_bf + n_txt, n_txt, s));
+    FMI_TRY(launch_cast_to_f32(o.cfg->neg_y, o.cfg->neg_y_dtype, w.yf + n_y, n_y, s));
   }
   // pe = EmbedNd(cat([txt_ids, img_ids], 1)) (model.rs:807-810); one table per batch element
   const int tables = in->ids_per_sample ? Bs : 1;
-  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, tables, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s, R ? ctx->ctx_ids : nullptr, R));
-  if (cfg && in->ids_per_sample) {
+  FMI_TRY(launch_rope_table(in->txt_ids, in->img_ids, tables, T, S, m->cfg.axes_dim, m->cfg.theta, w.pe, s, R ? o.ctx->ctx_ids : nullptr, R));
+  if (o.cfg && in->ids_per_sample) {
     const size_t half = (size_t)Bs * (T + S + R) * PE_ROW_FLOATS;
     FMI_HIP_TRY(hipMemcpyAsync(w.pe + half, w.pe, half * 4, hipMemcpyDeviceToDevice, s));
   }
-  if (ctl) return launch_cast_cols_bf16(ctl->cond, ctl->cond_dtype, (int64_t)B * S, (int64_t)Bs * S, m->cond, w.img_bf, C + m->cond, C, s);
+  if (o.ctl) return launch_cast_cols_bf16(o.ctl->cond, o.ctl->cond_dtype, (int64_t)B * S, (int64_t)Bs * S, m->cond, w.img_bf, C + m->cond, C, s);
   if (!R) return FMI_OK;
-  return launch_cast_rows_bf16(ctx->ctx, ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s, Bs);
+  return launch_cast_rows_bf16(o.ctx->ctx, o.ctx->ctx_dtype, (int64_t)R * C, w.img_bf + (size_t)S * C, (int64_t)(S + R) * C, B, (int64_t)R * C, s, Bs);
 }
-// The context of an evaluation, validated: R rows per sample (0: none, the text-to-image launches)
-int context_rows(const fmi_flux* m, const fmi_flux_context* ctx, int* R) {
-  *R = 0;
-  if (!ctx || ctx->R == 0) return FMI_OK;
-  if (ctx->R < 0) return fail(FMI_ERR_INVALID, "flux: context R must not be negative");
-  if (!ctx->ctx || !ctx->ctx_ids) return fail(FMI_ERR_INVALID, "flux: a context of R > 0 rows needs ctx and ctx_ids");
-  if (ctx->ctx_dtype != FMI_F32 && ctx->ctx_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux: ctx_dtype must be F32 or BF16");
-  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux: a context is not supported under sequence parallelism");
-  *R = ctx->R;
-  return FMI_OK;
-}
-
-// The control of an evaluation, validated: a channel-conditioned model needs one at every evaluation — so every entry without one refuses
-// such a model — and a plain model takes none.  R: the context rows context_rows() returned.
-int control_check(const fmi_flux* m, const fmi_flux_control* ctl, int R) {
-  if (!m->cond) return ctl ? fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)") : FMI_OK;
-  if (!ctl || !ctl->cond)
-    return fail(FMI_ERR_INVALID, "flux: this model has " + std::to_string(m->cond) + " conditioning channels: it is evaluated by fmi_flux_forward_control / fmi_flux_denoise_control with a control");
-  if (ctl->cond_dtype != FMI_F32 && ctl->cond_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux: cond_dtype must be F32 or BF16");
-  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux: a control is not supported under sequence parallelism");
-  if (R) return fail(FMI_ERR_UNSUPPORTED, "flux: a context and a control are not combined");
-  return FMI_OK;
-}
-
 // vec_ = time_in(temb(t)) [+ guidance_in(temb(g))] + vector_in(y)   (model.rs:813-820) -> vec_out (B, D) f32
 int compute_vec(fmi_flux* m, const fmi_flux_inputs* in, const float* timesteps_dev, float* vec_out, hipStream_t s) {
   auto& w = m->ws;
@@ -929,12 +912,9 @@ int compute_vec_steps(fmi_flux* m, const fmi_flux_inputs* in, const float* tv_de
   return launch_add2_rows(vec_steps, gterm, vterm, R, B, D, s);
 }
 
-// The first-block step cache of one fmi_flux_denoise_cached call: the caller's settings and the state the steps hand on.
+// The first-block step cache of one cached loop: the caller's settings and the state the steps hand on.
 struct StepCacheRun {
-  float threshold = 0.f;
-  const int8_t* force = nullptr;
-  int32_t* decisions_out = nullptr;
-  float* distances_out = nullptr;
+  const fmi_flux_step_cache* o;  // the caller's settings and outputs
   int step = 0;        // index of the evaluation under way
   bool valid = false;  // a computed step has left r_ref and the delta behind
   int ref = 0;         // m->sc_r[ref] is r_ref, m->sc_r[ref ^ 1] receives this step's residual
@@ -959,29 +939,29 @@ int step_cache_decide(fmi_flux* m, StepCacheRun* sc, int B, int S, int T, hipStr
     // d_b = num_b / den_b in double, +inf for den_b == 0, -1 while nothing has been computed yet; reported — and compared — as f32
     float d = -1.f;
     if (sc->valid) d = m->sc_host[2 * b + 1] == 0.0 ? INFINITY : (float)(m->sc_host[2 * b] / m->sc_host[2 * b + 1]);
-    if (sc->distances_out) sc->distances_out[(size_t)i * B + b] = d;
-    below = below && d < sc->threshold;
+    if (sc->o->distances_out) sc->o->distances_out[(size_t)i * B + b] = d;
+    below = below && d < sc->o->threshold;
   }
-  const int f = sc->force ? sc->force[i] : -1;
-  *reuse = sc->valid && (f == 1 || (f < 0 && sc->threshold > 0.f && below));
-  if (sc->decisions_out) sc->decisions_out[i] = *reuse ? 1 : 0;
+  const int f = sc->o->force ? sc->o->force[i] : -1;
+  *reuse = sc->valid && (f == 1 || (f < 0 && sc->o->threshold > 0.f && below));
+  if (sc->o->decisions_out) sc->o->decisions_out[i] = *reuse ? 1 : 0;
   if (*reuse) FMI_TRY(launch_step_cache_apply(w.x_img, n, m->sc_delta.as<float>(), w.x + (size_t)T * m->D, L * m->D, B, n, s));
   return FMI_OK;
 }
 
-// One model evaluation given prepared static inputs; img_f32 (B,S,C) -> pred (B,S,C) f32.
-// R: context rows per sample.  The image stream then has in->S + R rows per sample — rows [in->S, in->S + R) of w.img_bf and of the RoPE table were
-// written by prepare_static — and everything between the input assembly and the final layer sees only that longer stream; img_f32 and pred stay (B, in->S, C).
-// mod_pre: this step's (B, n_mod) modulation vectors if the caller precomputed them (fmi_flux_denoise), else null.
-// txt_pre: txt_in(txt) if the caller computed it once for all steps (fmi_flux_denoise: it does not depend on the latent or on t), else null.
-// sc: the step cache of a fmi_flux_denoise_cached call, else null — and with null every launch below is the one it always was.
-// Bs: samples of img_f32 when they are fewer than in->B (true CFG, DESIGN.md 4.12: sample b of the operand is the state's sample b % Bs), else 0 — the
-// input assembly is all that knows.
-int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, const float* timesteps_dev, float* pred, hipStream_t s,
-                 const float* mod_pre = nullptr, const float* txt_pre = nullptr, int R = 0, StepCacheRun* sc = nullptr, int Bs = 0) {
+// One model evaluation given prepared static inputs; img_f32 (Bs,S,C) -> pred (B,S,C) f32.
+// p.R: context rows per sample.  The image stream then has in->S + R rows per sample — rows [in->S, in->S + R) of w.img_bf and of the RoPE table were
+// written by prepare_static — and everything between the input assembly and the final layer sees only that longer stream; img_f32 and pred stay (., in->S, C).
+// p.Bs: samples of img_f32; fewer than in->B under true CFG (sample b of the operand is the state's sample b % Bs) — the input assembly is all
+// that knows.
+// mod_pre: this step's (B, n_mod) modulation vectors where the loop precomputed them, else null.
+// txt_pre: txt_in(txt) where the loop computed it once for all steps (it does not depend on the latent or on t), else null.
+// sc: the step cache of a cached loop, else null — and with null every launch below is the one it always was.
+int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, const float* img_f32, const float* timesteps_dev, float* pred, const float* mod_pre,
+                 const float* txt_pre, StepCacheRun* sc, hipStream_t s) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
-  const int B = in->B, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
+  const int B = in->B, Bs = p.Bs, R = p.R, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
   const int D = m->D, Mh = m->M, H = m->H, C = c.in_channels;
   const int nmod = (int)m->n_mod;
   const int64_t pe_bs = in->ids_per_sample ? (int64_t)L * PE_ROW_FLOATS : 0;
@@ -1004,8 +984,8 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const float* img_f32, c
   {
     PhaseTimer pt(m, s, PH_EMBED);
     if (m->cond)  // the state into columns [0, C) of the [state | conditioning] operand, both halves of a true-CFG batch in the one launch (no context: R == 0)
-      FMI_TRY(launch_cast_cols_bf16(img_f32, FMI_F32, (int64_t)B * S, (int64_t)(Bs ? Bs : B) * S, C, w.img_bf, m->img_in.K, 0, s));
-    else if (R || Bs) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s, Bs));  // the state rows into their places
+      FMI_TRY(launch_cast_cols_bf16(img_f32, FMI_F32, (int64_t)B * S, (int64_t)Bs * S, C, w.img_bf, m->img_in.K, 0, s));
+    else if (R || Bs != B) FMI_TRY(launch_cast_rows_bf16(img_f32, FMI_F32, (int64_t)Ss * C, w.img_bf, (int64_t)S * C, B, (int64_t)Ss * C, s, Bs));  // the state rows into their places
     else FMI_TRY(launch_cast_to_bf16(img_f32, FMI_F32, w.img_bf, (int64_t)B * S * C, s));
     if (!mod_pre) FMI_TRY(compute_vec(m, in, timesteps_dev, w.vec, s));
     // img = img_in(img), txt = txt_in(txt)   (model.rs:811-812) -> f32 residual streams
@@ -1275,6 +1255,55 @@ int check_inputs(fmi_flux* m, const fmi_flux_inputs* in) {
   if (!in->img_ids || !in->txt || !in->txt_ids || !in->y) return fail(FMI_ERR_INVALID, "flux: null input tensor");
   FMI_TRY(use_device(m));
   return check_ready(m);
+}
+
+// Every refusal of a forward or denoise call — of its arguments, each option and each combination (the table at fmi_flux_denoise_with) — in the one place, before the call's
+// stream is used or anything is launched or allocated for it (check_inputs makes the handle's device current and completes a freshly loaded model: the model's state, not the
+// call's).  *p: the accepted call's plan.  A forward is n_steps == 1 with ctx / ctl only.  bad_io: the entry's message when a pointer outside `in` and `o` is unusable, else null.
+int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options& o, int n_steps, const char* bad_io, EvalPlan* p) {
+  if ((o.x0 || o.noise || o.mask) && !(o.x0 && o.noise && o.mask)) return fail(FMI_ERR_INVALID, "flux_denoise: x0, noise and mask go together (all three or none)");
+  FMI_TRY(check_inputs(m, in));
+  if (bad_io) return fail(FMI_ERR_INVALID, bad_io);
+  const bool sp = m->sp_world > 1 && m->sp_a2a;
+  const auto f32_or_bf16 = [](fmi_dtype t) { return t == FMI_F32 || t == FMI_BF16; };
+  *p = EvalPlan{o, 0, in->B};
+  if (const fmi_flux_context* ctx = o.ctx; ctx && ctx->R != 0) {  // R == 0 is no context
+    if (ctx->R < 0) return fail(FMI_ERR_INVALID, "flux: context R must not be negative");
+    if (!ctx->ctx || !ctx->ctx_ids) return fail(FMI_ERR_INVALID, "flux: a context of R > 0 rows needs ctx and ctx_ids");
+    if (!f32_or_bf16(ctx->ctx_dtype)) return fail(FMI_ERR_INVALID, "flux: ctx_dtype must be F32 or BF16");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux: a context is not supported under sequence parallelism");
+    p->R = ctx->R;
+  }
+  if (!m->cond && o.ctl) return fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)");
+  if (m->cond) {  // a channel-conditioned model needs a control at every evaluation
+    if (!o.ctl || !o.ctl->cond)
+      return fail(FMI_ERR_INVALID, "flux: this model has " + std::to_string(m->cond) + " conditioning channels: every evaluation needs a control (fmi_flux_forward_control, fmi_flux_denoise_with)");
+    if (!f32_or_bf16(o.ctl->cond_dtype)) return fail(FMI_ERR_INVALID, "flux: cond_dtype must be F32 or BF16");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux: a control is not supported under sequence parallelism");
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: a context and a control are not combined");
+  }
+  if (const fmi_flux_true_cfg* cfg = o.cfg) {
+    if (o.cache) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: true CFG is not combined with the step cache");
+    if (!cfg->neg_txt || !cfg->neg_y) return fail(FMI_ERR_INVALID, "flux_denoise: true CFG needs neg_txt and neg_y");
+    if (!f32_or_bf16(cfg->neg_txt_dtype) || !f32_or_bf16(cfg->neg_y_dtype)) return fail(FMI_ERR_INVALID, "flux_denoise: neg_txt_dtype and neg_y_dtype must be F32 or BF16");
+    if (!(cfg->scale >= 0.f) || std::isinf(cfg->scale)) return fail(FMI_ERR_INVALID, "flux_denoise: the true-CFG scale must be finite and >= 0");
+    if (p->Bs > 4) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: B > 4 not supported under true CFG (the loop evaluates 2 B samples; the per-device limit is 8)");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: true CFG is not supported under sequence parallelism (it runs B = 1)");
+    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise: no true CFG while int8 calibration is recording");
+    if (m->cfg.guidance_embeds && !in->guidance) return fail(FMI_ERR_INVALID, "flux: guidance_embeds model needs a guidance vector");
+  }
+  if ((int64_t)n_steps * (o.cfg ? 2 : 1) * p->Bs > 4096) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: n_steps * B > 4096 (ws.tv holds 4096 rows; true CFG counts 2 B)");
+  if (const fmi_flux_step_cache* cache = o.cache) {
+    if (o.ctl) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the step cache is not combined with a control");
+    if (!(cache->threshold >= 0.f)) return fail(FMI_ERR_INVALID, "flux_denoise: the step-cache threshold must be >= 0 (and not NaN)");
+    for (int i = 0; cache->force && i < n_steps; ++i)
+      if (cache->force[i] < -1 || cache->force[i] > 1 || (i == 0 && cache->force[i] == 1))
+        return fail(FMI_ERR_INVALID, "flux_denoise: step-cache force entries are -1, 0 or 1, and step 0 cannot be reused (force[0] != 1)");
+    if (m->cfg.num_layers < 1) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the step cache needs at least one double block");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the step cache is not supported under sequence parallelism");
+    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise: no step cache while int8 calibration is recording");
+  }
+  return FMI_OK;
 }
 
 }  // namespace
@@ -1560,16 +1589,14 @@ extern "C" int fmi_flux_state_buffer(fmi_flux* m, int index, void** ptr, size_t*
 
 // One evaluation of every forward entry: over cat([img, ctx], 1) with a context, over cat([img, cond], 2) with a control.
 static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, float* pred_out, void* stream) {
-  FMI_TRY(check_inputs(m, in));
-  if (!in->img || !in->timesteps || !pred_out) return fail(FMI_ERR_INVALID, "flux_forward: null img/timesteps/pred_out");
-  int R = 0;
-  FMI_TRY(context_rows(m, ctx, &R));
-  FMI_TRY(control_check(m, ctl, R));
+  const fmi_flux_denoise_options o{ctx, ctl};  // (every other field null)
+  EvalPlan p;
+  FMI_TRY(validate(m, in, o, 1, in && in->img && in->timesteps && pred_out ? nullptr : "flux_forward: null img/timesteps/pred_out", &p));
   hipStream_t s = (hipStream_t)stream;
-  FMI_TRY(ensure_workspace(m, in->B, in->S + R, in->T));
-  FMI_TRY(prepare_static(m, in, ctx, R, s, nullptr, ctl));
+  FMI_TRY(ensure_workspace(m, in->B, in->S + p.R, in->T));
+  FMI_TRY(prepare_static(m, in, p, s));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, m->ws.img_f32, (int64_t)in->B * in->S * m->cfg.in_channels, s));
-  return forward_core(m, in, m->ws.img_f32, in->timesteps, pred_out, s, nullptr, nullptr, R);
+  return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, s);
 }
 // One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
 extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
@@ -1583,74 +1610,26 @@ extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* p
   return fmi_flux_forward_context(m, in, nullptr, pred_out, stream);
 }
 
-// The denoise loop of both entries.  x0 / noise / mask all null: fmi_flux_denoise, the plain Euler update.  All three set: fmi_flux_denoise_inpaint, the same
-// launches with the per-step update replaced by the masked one (launch_euler_blend); nothing before or inside the model evaluation knows the difference.
-// ctx: the reference-image rows every evaluation appends to the state's (fmi_flux_denoise_context); the state, the update and the blend stay (B,S,C).
-// cache: fmi_flux_denoise_cached's first-block step cache, null for every other entry — which then issue exactly the launches they always did.
-// cfg: fmi_flux_denoise_cfg's negative prompt, null for every other entry, likewise.  With it `in` below is the loop's own batch of 2 * Bs samples
-// — the prompt's rows, then the negative's — and only the input assembly (prepare_static, forward_core's state cast) and the update (launch_euler_cfg) know.
-// ctl: fmi_flux_denoise_control's conditioning channels, required by a channel-conditioned model and refused by every other: the input assembly
-// alone knows (prepare_static writes the operand's conditioning columns once, forward_core the state's every step); the state, the update and the blend stay (B,S,C).
-static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
-                        const float* x0, const float* noise, const float* mask, void* stream, const fmi_flux_step_cache* cache = nullptr,
-                        const fmi_flux_true_cfg* cfg = nullptr, const fmi_flux_control* ctl = nullptr) {
-  FMI_TRY(check_inputs(m, in_caller));
-  if (!img_inout || !timesteps_host || n_steps < 0) return fail(FMI_ERR_INVALID, "flux_denoise: null img/timesteps or negative n_steps");
-  int Rc = 0;  // context rows per sample
-  FMI_TRY(context_rows(m, ctx, &Rc));
-  FMI_TRY(control_check(m, ctl, Rc));
-  hipStream_t s = (hipStream_t)stream;
-  const int Bs = in_caller->B;  // the state's samples
-  fmi_flux_inputs in_cfg;
-  const fmi_flux_inputs* in = in_caller;
-  if (cfg) {  // every refusal comes before the first launch
-    if (cache) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: true CFG is not combined with the step cache");
-    if (!cfg->neg_txt || !cfg->neg_y) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: neg_txt and neg_y are required");
-    if ((cfg->neg_txt_dtype != FMI_F32 && cfg->neg_txt_dtype != FMI_BF16) || (cfg->neg_y_dtype != FMI_F32 && cfg->neg_y_dtype != FMI_BF16))
-      return fail(FMI_ERR_INVALID, "flux_denoise_cfg: neg_txt_dtype and neg_y_dtype must be F32 or BF16");
-    if (!(cfg->scale >= 0.f) || std::isinf(cfg->scale)) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: scale must be finite and >= 0");
-    if (Bs > 4) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: B > 4 not supported (the loop evaluates 2 B samples; the per-device limit is 8)");
-    if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cfg: true CFG is not supported under sequence parallelism (it runs B = 1)");
-    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise_cfg: not while int8 calibration is recording");
-    if (m->cfg.guidance_embeds && !in_caller->guidance) return fail(FMI_ERR_INVALID, "flux: guidance_embeds model needs a guidance vector");
-    in_cfg = *in_caller;
-    in_cfg.B = 2 * Bs;
-    in = &in_cfg;
+// (b) of the loop: the step cache's buffers for B streams of `rows` image rows, regrown when a larger shape comes.
+static int step_cache_ensure(fmi_flux* m, int B, int rows, hipStream_t s) {
+  const size_t per = (size_t)rows * m->D, elems = (size_t)B * per, part = (size_t)B * step_cache_groups((int64_t)per) * 2;
+  if (m->sc_elems < elems || m->sc_part_floats < part) {
+    FMI_HIP_TRY(hipStreamSynchronize(s));
+    m->sc_x0.reset(), m->sc_r[0].reset(), m->sc_r[1].reset(), m->sc_delta.reset(), m->sc_part.reset(), m->sc_elems = 0, m->sc_part_floats = 0;
+    for (DeviceBuffer* b : {&m->sc_x0, &m->sc_r[0], &m->sc_r[1], &m->sc_delta})
+      if (b->alloc(elems * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise: hipMalloc of a step-cache buffer (" + std::to_string(elems * 4) + " bytes) failed");
+    if (m->sc_part.alloc(part * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise: hipMalloc of the step cache's partial sums failed");
+    m->sc_elems = elems, m->sc_part_floats = part;
   }
+  if (!m->sc_sums) FMI_HIP_TRY(m->sc_sums.alloc(2 * 8 * sizeof(double)));  // (B <= 8, check_inputs)
+  if (!m->sc_host) FMI_HIP_TRY(hipHostMalloc((void**)&m->sc_host, 2 * 8 * sizeof(double), hipHostMallocDefault));
+  return FMI_OK;
+}
+
+// (c) of the loop, what the steps share, once per call: every step's timestep vector in ws.tv, every step's modulation vectors (*mod_steps; null where each step
+// computes its own) and txt_in(txt) (*txt_pre; likewise).
+static int hoist_steps(fmi_flux* m, const fmi_flux_inputs* in, const double* timesteps_host, int n_steps, hipStream_t s, const float** mod_steps, const float** txt_pre) {
   const int B = in->B;
-  if ((int64_t)n_steps * B > 4096) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: n_steps * B > 4096 (ws.tv holds 4096 rows; true CFG counts 2 B)");  // before any launch
-  StepCacheRun sc_run, *sc = nullptr;
-  if (cache) {  // every refusal comes before the first launch
-    if (!(cache->threshold >= 0.f)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: threshold must be >= 0 (and not NaN)");
-    for (int i = 0; cache->force && i < n_steps; ++i)
-      if (cache->force[i] < -1 || cache->force[i] > 1 || (i == 0 && cache->force[i] == 1))
-        return fail(FMI_ERR_INVALID, "flux_denoise_cached: force entries are -1, 0 or 1, and step 0 cannot be reused (force[0] != 1)");
-    if (m->cfg.num_layers < 1) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cached: the step cache needs at least one double block");
-    if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise_cached: the step cache is not supported under sequence parallelism");
-    if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise_cached: not while int8 calibration is recording");
-    const size_t per = (size_t)(in->S + Rc) * m->D, elems = (size_t)B * per, part = (size_t)B * step_cache_groups((int64_t)per) * 2;
-    if (m->sc_elems < elems || m->sc_part_floats < part) {
-      FMI_HIP_TRY(hipStreamSynchronize(s));
-      m->sc_x0.reset(), m->sc_r[0].reset(), m->sc_r[1].reset(), m->sc_delta.reset(), m->sc_part.reset(), m->sc_elems = 0, m->sc_part_floats = 0;
-      for (DeviceBuffer* b : {&m->sc_x0, &m->sc_r[0], &m->sc_r[1], &m->sc_delta})
-        if (b->alloc(elems * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise_cached: hipMalloc of a step-cache buffer (" + std::to_string(elems * 4) + " bytes) failed");
-      if (m->sc_part.alloc(part * 4) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_denoise_cached: hipMalloc of the step cache's partial sums failed");
-      m->sc_elems = elems, m->sc_part_floats = part;
-    }
-    if (!m->sc_sums) FMI_HIP_TRY(m->sc_sums.alloc(2 * 8 * sizeof(double)));  // (B <= 8, check_inputs)
-    if (!m->sc_host) FMI_HIP_TRY(hipHostMalloc((void**)&m->sc_host, 2 * 8 * sizeof(double), hipHostMallocDefault));
-    sc_run.threshold = cache->threshold, sc_run.force = cache->force, sc_run.decisions_out = cache->decisions_out, sc_run.distances_out = cache->distances_out;
-    sc = &sc_run;
-  }
-  FMI_TRY(ensure_workspace(m, B, in->S + Rc, in->T));
-  if (cfg && in->guidance) {  // the same guidance in both halves
-    if (!m->cfg_gd) FMI_HIP_TRY(m->cfg_gd.alloc(8 * sizeof(float)));  // (2 Bs <= 8; the other entries never allocate it)
-    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>(), in_caller->guidance, (size_t)Bs * 4, hipMemcpyDeviceToDevice, s));
-    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>() + Bs, in_caller->guidance, (size_t)Bs * 4, hipMemcpyDeviceToDevice, s));
-    in_cfg.guidance = m->cfg_gd.as<float>();
-  }
-  FMI_TRY(prepare_static(m, in, ctx, Rc, s, cfg, ctl));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
-  const int64_t n = (int64_t)Bs * in->S * m->cfg.in_channels;
   // t_vec = full(1f32, B) * t_curr  (sampling.rs:35,42): all steps' vectors uploaded once
   std::vector<float> tv((size_t)(n_steps > 0 ? n_steps : 1) * B);
   for (int i = 0; i < n_steps; ++i)
@@ -1660,7 +1639,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
   // The modulation vectors depend on (t, guidance, y) only, never on the latent: all steps' vectors are
   // computed up front, GEMV_MAXROWS rows per pass over the 6.5 GB modulation matrix (13 passes for 50
   // steps instead of 50: the per-step GEMV was 1.2 ms of pure HBM streaming per denoise step).
-  const float* mod_steps = nullptr;
+  *mod_steps = nullptr;
   const size_t R = (size_t)n_steps * B, nmod = (size_t)m->n_mod;
   if (n_steps > 1 && R * nmod * 4 <= (2ull << 30)) {
     if (m->mod_steps_rows < R) {
@@ -1692,64 +1671,91 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
                               (int)nmod, m->D, 1, 0, s));
       }
     }
-    mod_steps = m->mod_steps.as<float>();
+    *mod_steps = m->mod_steps.as<float>();
   }
-  const float* txt_pre = nullptr;
+  *txt_pre = nullptr;
   if (n_steps > 1) {  // txt = txt_in(txt) (model.rs:812) depends on the prompt only: once per image
     PhaseTimer pt(m, s, PH_EMBED);
     GemmProblem p = make_problem(m->txt_in, m->ws.txt_bf, m->cfg.joint_attention_dim, B * in->T, m->ws.x_txt0, m->D, EPI_STORE_F32);
     FMI_TRY(gemm1(m, p, m->txt_in, s));
-    txt_pre = m->ws.x_txt0;
+    *txt_pre = m->ws.x_txt0;
   }
+  return FMI_OK;
+}
+
+// (d) of the loop: the steps.  One evaluation each, then the update of the state — one of three, and all that knows about the negative prompt's scale or the blend.
+static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, float* img_inout, const double* timesteps_host, int n_steps, const float* mod_steps,
+                     const float* txt_pre, StepCacheRun* sc, hipStream_t s) {
+  const fmi_flux_denoise_options& o = p.o;
+  const size_t B = in->B, nmod = m->n_mod;
+  const int64_t n = (int64_t)p.Bs * in->S * m->cfg.in_channels;
   for (int i = 0; i < n_steps; ++i) {
-    FMI_TRY(forward_core(m, in, img_inout, m->ws.tv + (size_t)i * B, m->ws.pred_tmp, s, mod_steps ? mod_steps + (size_t)i * B * nmod : nullptr, txt_pre, Rc, sc,
-                         cfg ? Bs : 0));
+    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, s));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
-    if (cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
-      FMI_TRY(launch_euler_cfg(img_inout, m->ws.pred_tmp, m->ws.pred_tmp + n, cfg->scale, dt, n, s, x0, noise, mask, (float)timesteps_host[i + 1]));
-    else if (mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
-      FMI_TRY(launch_euler_blend(img_inout, m->ws.pred_tmp, x0, noise, mask, dt, (float)timesteps_host[i + 1], n, s));
+    if (o.cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
+      FMI_TRY(launch_euler_cfg(img_inout, m->ws.pred_tmp, m->ws.pred_tmp + n, o.cfg->scale, dt, n, s, o.x0, o.noise, o.mask, (float)timesteps_host[i + 1]));
+    else if (o.mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
+      FMI_TRY(launch_euler_blend(img_inout, m->ws.pred_tmp, o.x0, o.noise, o.mask, dt, (float)timesteps_host[i + 1], n, s));
     else
       FMI_TRY(launch_euler_update(img_inout, m->ws.pred_tmp, dt, n, s));
   }
   return FMI_OK;
 }
 
-extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
-                                void* stream) {
-  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, nullptr, nullptr, nullptr, stream);
+// The denoise loop of every entry (include/flux_mi355x.h: fmi_flux_denoise_with).  An option that is null changes no launch and no allocation, and each is
+// known to few places: the blend to the update alone; the context and the control to the input assembly (prepare_static writes the context's rows and the conditioning's columns
+// of the img_in operand once, forward_core the state's every step); the negative prompt to the input assembly and the update — `in` below is then the loop's own batch of
+// 2 * Bs samples, the prompt's rows, then the negative's —; the step cache to forward_core after double block 0.
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+  EvalPlan p;
+  FMI_TRY(validate(m, in_caller, o, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
+  hipStream_t s = (hipStream_t)stream;
+  fmi_flux_inputs in = *in_caller;
+  if (o.cfg) in.B = 2 * p.Bs;
+  StepCacheRun sc{o.cache};
+  if (o.cache) FMI_TRY(step_cache_ensure(m, in.B, in.S + p.R, s));
+  FMI_TRY(ensure_workspace(m, in.B, in.S + p.R, in.T));
+  if (o.cfg && in.guidance) {  // the same guidance in both halves
+    if (!m->cfg_gd) FMI_HIP_TRY(m->cfg_gd.alloc(8 * sizeof(float)));  // (2 Bs <= 8; a call without a negative never allocates it)
+    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>(), in_caller->guidance, (size_t)p.Bs * 4, hipMemcpyDeviceToDevice, s));
+    FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>() + p.Bs, in_caller->guidance, (size_t)p.Bs * 4, hipMemcpyDeviceToDevice, s));
+    in.guidance = m->cfg_gd.as<float>();
+  }
+  FMI_TRY(prepare_static(m, &in, p, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
+  const float *mod_steps, *txt_pre;
+  FMI_TRY(hoist_steps(m, &in, timesteps_host, n_steps, s, &mod_steps, &txt_pre));
+  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, s);
 }
 
-extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
-                                        const float* x0, const float* noise, const float* mask, void* stream) {
+extern "C" int fmi_flux_denoise_with(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, img_inout, timesteps_host, n_steps, stream);
+}
+
+// The entries from before fmi_flux_denoise_with: each fills the options its arguments name — {ctx, ctl, cfg, cache, x0, noise, mask} — and takes the same path.
+extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+  return denoise_loop(m, in, fmi_flux_denoise_options{}, img_inout, timesteps_host, n_steps, stream);
+}
+extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, const float* x0,
+                                        const float* noise, const float* mask, void* stream) {
   if (!x0 || !noise || !mask) return fail(FMI_ERR_INVALID, "flux_denoise_inpaint: x0, noise and mask are all required");
-  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
 }
-
 extern "C" int fmi_flux_denoise_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                         int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_context: x0, noise and mask go together (all three or none)");
-  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
 }
-
-// The loop of fmi_flux_denoise_context with the first-block step cache; a null cache IS fmi_flux_denoise_context.
 extern "C" int fmi_flux_denoise_cached(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                        int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream) {
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cached: x0, noise and mask go together (all three or none)");
-  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, cache);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, cache, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
 }
-// The loop of fmi_flux_denoise_context with a negative prompt (true CFG); a null cfg IS fmi_flux_denoise_context.
 extern "C" int fmi_flux_denoise_cfg(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_true_cfg* cfg, float* img_inout,
                                     const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_cfg: x0, noise and mask go together (all three or none)");
-  return denoise_loop(m, in, ctx, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, nullptr, cfg);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, cfg, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
 }
-// The loop of fmi_flux_denoise_cfg without a context and with a control; on a plain model a null ctl IS fmi_flux_denoise_cfg without a context.
 extern "C" int fmi_flux_denoise_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg, float* img_inout,
                                         const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "flux_denoise_control: x0, noise and mask go together (all three or none)");
-  return denoise_loop(m, in, nullptr, img_inout, timesteps_host, n_steps, x0, noise, mask, stream, nullptr, cfg, ctl);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, ctl, cfg, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
 }
 // device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
 extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {

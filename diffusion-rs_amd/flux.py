@@ -445,7 +445,7 @@ class FluxModel:
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
                 cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None):
-        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.
+        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_with call: the keywords fill its options.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
         context= / context_ids=: reference-image tokens every evaluation appends to the state's (fmi_flux_denoise_context); the state stays (B,S,C).
@@ -478,8 +478,9 @@ class FluxModel:
         keep_blend = [_like_img(t, nm, img) for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask"))]
         has_ctx = context is not None or context_ids is not None
         ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
-        blend = [_ptr(t) for t in keep_blend]  # a missing one of the three reaches the library as NULL: it answers FMI_ERR_INVALID
         ctl, keep_ctl = self._control(img, control) if control is not None else (None, None)
+        # (a missing one of x0 / noise / mask reaches the library as NULL: it answers FMI_ERR_INVALID)
+        opts = L.FluxDenoiseOptions(ctx and C.pointer(ctx), ctl and C.pointer(ctl), None, None, *[_ptr(t) for t in keep_blend])
         if cfg_scale is not None:
             for t, nm in ((negative_txt, "negative_txt"), (negative_y, "negative_y")):
                 if t.dtype not in (torch.float32, torch.bfloat16):
@@ -487,26 +488,13 @@ class FluxModel:
                 if t.device != img.device:
                     raise ValueError(f"{nm} is on {t.device}, img on {img.device}")
             keep_neg = [negative_txt.contiguous(), negative_y.contiguous()]
-            tc = L.FluxTrueCfg(_ptr(keep_neg[0]), _TORCH_DT[negative_txt.dtype], _ptr(keep_neg[1]), _TORCH_DT[negative_y.dtype], cfg_scale)
-            if ctl is not None:
-                st = self.lib.fmi_flux_denoise_control(self.h, C.byref(inp), C.byref(ctl), C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
-            else:
-                st = self.lib.fmi_flux_denoise_cfg(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, C.byref(tc), _ptr(img), ts, n_steps, *blend, _stream())
-        elif ctl is not None:
-            st = self.lib.fmi_flux_denoise_control(self.h, C.byref(inp), C.byref(ctl), None, _ptr(img), ts, n_steps, *blend, _stream())
-        elif thr is not None:
+            opts.cfg = C.pointer(L.FluxTrueCfg(_ptr(keep_neg[0]), _TORCH_DT[negative_txt.dtype], _ptr(keep_neg[1]), _TORCH_DT[negative_y.dtype], cfg_scale))
+        if thr is not None:
             decisions = np.zeros(max(n_steps, 0), np.int32)
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
-            sc = L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
-                                 decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float)))
-            st = self.lib.fmi_flux_denoise_cached(self.h, C.byref(inp), C.byref(ctx) if has_ctx else None, _ptr(img), ts, n_steps, *blend, C.byref(sc), _stream())
-        elif has_ctx:
-            st = self.lib.fmi_flux_denoise_context(self.h, C.byref(inp), C.byref(ctx), _ptr(img), ts, n_steps, *blend, _stream())
-        elif any(t is not None for t in (x0, noise, mask)):
-            st = self.lib.fmi_flux_denoise_inpaint(self.h, C.byref(inp), _ptr(img), ts, n_steps, *blend, _stream())
-        else:
-            st = self.lib.fmi_flux_denoise(self.h, C.byref(inp), _ptr(img), ts, n_steps, _stream())
-        L.check(st, self.lib)
+            opts.cache = C.pointer(L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
+                                                   decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float))))
+        L.check(self.lib.fmi_flux_denoise_with(self.h, C.byref(inp), C.byref(opts), _ptr(img), ts, n_steps, _stream()), self.lib)
         return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
 
     def step_cache_bytes(self) -> int:

@@ -50,6 +50,7 @@ extern "C" {
  *   Then, still 6: true classifier-free guidance (negative prompts) in the denoise loop — fmi_flux_true_cfg, fmi_flux_denoise_cfg, fmi_cfg_euler_step.
  *   Then, still 6: channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth) — fmi_flux_create_cond, fmi_flux_cond_channels, fmi_flux_control,
  *   fmi_flux_forward_control, fmi_flux_denoise_control, fmi_cast_cols_bf16, fmi_mask_image, fmi_fill_condition.
+ *   Then, still 6: the denoise loop's options in one struct — fmi_flux_denoise_options, fmi_flux_denoise_with; the six fmi_flux_denoise* entries remain.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -365,29 +366,19 @@ typedef struct fmi_flux_inputs {
 
 int fmi_flux_forward(fmi_flux*, const fmi_flux_inputs* in, float* pred_out, void* stream);
 
-/* The whole denoise loop == Sampler::sample(FlowMatchEulerDiscrete)
- * (pipelines/sampling.rs:25-48) around the step closure (pipelines/flux/mod.rs:305-318):
- *   for (t_curr,t_prev) in windows(timesteps): img += forward(img, t_curr) * (t_prev-t_curr)
- * `in->img` must be F32 and is the state: `img_inout` (B,S,C) f32 is updated in place
- * (in->img is ignored; in->timesteps is ignored, `timesteps_host` (n_steps+1 f64, host)
- * drives the loop, exactly the Vec<f64> of SchedulerConfig::get_timesteps).
- * The latent stays f32 between steps. */
-int fmi_flux_denoise(fmi_flux*, const fmi_flux_inputs* in, float* img_inout,
-                     const double* timesteps_host, int n_steps, void* stream);
-/* The same loop with the inpainting step (no counterpart in the reference; the flow-matching form of diffusers'
- * FluxInpaintPipeline).  After the model evaluation of step i, with s = f32(timesteps[i+1]):
- *   e = img + pred * dt                     (fmi_flux_denoise's update, same rounding)
+/* ---- What an evaluation can be conditioned on.  Each block below gives one option's struct and semantics; the loop that takes them all is
+ * fmi_flux_denoise_with, after them. ---- */
+
+/* The inpainting blend (no counterpart in the reference; the flow-matching form of diffusers' FluxInpaintPipeline): x0 / noise / mask.
+ * After the model evaluation of step i, with s = f32(timesteps[i+1]):
+ *   e = img + pred * dt                     (the plain update, same rounding)
  *   k = (1 - s) * x0 + s * noise            (the source re-noised to the step's target time, fmi_scale_noise's form)
  *   img = mask * e + (1 - mask) * k
  * mask = 1 gives e and mask = 0 gives k bit for bit; the schedule ends at s = 0, where k = x0 bit for bit, so kept
  * elements end as the source's exactly.  x0, noise, mask: (B,S,in_channels) f32 device buffers laid out like img_inout
  * (fmi_encode_latents, the packed noise the image would have started from, fmi_latent_mask); under sequence parallelism
- * this rank's rows, like img_inout.  All three are required (FMI_ERR_INVALID).  Everything else — arguments, errors,
- * asynchrony, allocations, every launch up to the per-step update — is fmi_flux_denoise's.
- * Plain image-to-image (no mask) needs no loop of its own: it is fmi_scale_noise at the first timestep of the cut
- * schedule followed by fmi_flux_denoise on that schedule. */
-int fmi_flux_denoise_inpaint(fmi_flux*, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
-                             const float* x0, const float* noise, const float* mask, void* stream);
+ * this rank's rows, like img_inout.  Nothing before or inside the model evaluation knows about the blend.
+ * Plain image-to-image (no mask) needs no blend: it is fmi_scale_noise at the first timestep of the cut schedule followed by the plain loop on that schedule. */
 
 /* Reference-image ("in-context") conditioning as in FLUX.1 Kontext (the reference has no counterpart).  The reference image is encoded and
  * packed like the latents (fmi_vae_encode, fmi_encode_latents) and its R tokens are appended to the image tokens with a 1 in axis 0 of their position ids
@@ -395,11 +386,11 @@ int fmi_flux_denoise_inpaint(fmi_flux*, const fmi_flux_inputs* in, float* img_in
  * image-stream rows per sample in every block — and the prediction is rows [0, S) of each sample: the final layer runs on those rows only.
  *   fmi_flux_forward_context  one such evaluation; `in` as for fmi_flux_forward, pred_out (B,S,in_channels) f32.  Bit for bit rows [0, S) of fmi_flux_forward on
  *                             the concatenated inputs.
- *   fmi_flux_denoise_context  the loop.  The state is img_inout alone, (B,S,in_channels) f32; the Euler update — and with x0 / noise / mask (all three or none)
- *                             fmi_flux_denoise_inpaint's blend — touch those rows only, with the same expressions and roundings.  The context's rows of the
- *                             model input and of the RoPE table are written once per call; each step casts only the S state rows.
- * With R = 0 or a NULL context both are fmi_flux_forward / fmi_flux_denoise / fmi_flux_denoise_inpaint: the same launches.
- * FMI_ERR_INVALID: R < 0; R > 0 with a NULL ctx or ctx_ids; a ctx_dtype other than F32 / BF16; x0 / noise / mask given only in part.
+ *   in the loop               the state is img_inout alone, (B,S,in_channels) f32; the update and the blend touch those rows only, with the same expressions and
+ *                             roundings.  The context's rows of the model input and of the RoPE table are written once per call; each step casts only the S
+ *                             state rows.
+ * With R = 0 or a NULL context the launches are those of an evaluation without one.
+ * FMI_ERR_INVALID: R < 0; R > 0 with a NULL ctx or ctx_ids; a ctx_dtype other than F32 / BF16.
  * FMI_ERR_UNSUPPORTED: a context (R > 0) under fmi_flux_set_sequence_parallel. */
 typedef struct fmi_flux_context {
   const void* ctx;      fmi_dtype ctx_dtype; /* (B,R,in_channels) F32|BF16: packed reference latents, fmi_encode_latents' output */
@@ -407,12 +398,10 @@ typedef struct fmi_flux_context {
   int R;                                     /* context tokens per sample; 0 (or a NULL struct) = no context */
 } fmi_flux_context;
 int fmi_flux_forward_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream);
-int fmi_flux_denoise_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
-                             const float* x0, const float* noise, const float* mask, void* stream);
 
 /* First-block step cache for the denoise loop (the method of ParaAttention's FBCache / diffusers' FirstBlockCacheConfig; the reference has no
- * counterpart).  fmi_flux_denoise_cached is fmi_flux_denoise_context — same arguments, same update and blend — with one addition.  Every step runs the input
- * embedding and double block 0, takes the block's residual r = X1 - X0 of the f32 image stream (S' = S + R rows per sample), and measures per sample
+ * counterpart).  Every step runs the input embedding and double block 0, takes the block's residual r = X1 - X0 of the f32 image stream (S' = S + R rows per
+ * sample), and measures per sample
  *   d_b = sum |r - r_ref| / sum |r_ref|         (r_ref: the residual of the last COMPUTED step; divided on the host in double, +inf for a zero denominator)
  * A step is reused when a computed step precedes it and force[i] == 1, or force[i] < 0 (or force NULL), threshold > 0 and EVERY sample's d_b < threshold — the
  * decision is per call, not per sample, so a batched call under a threshold may differ from its single-sample runs (under a forced mask it does not).  A reused
@@ -421,67 +410,104 @@ int fmi_flux_denoise_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flu
  * The distances are compared as the f32 values distances_out reports.  The sums use no atomics and a decomposition fixed by S' * D: the same bits from run to run
  * and for any B.
  * No threshold is recommended here: ParaAttention suggests 0.08 for FLUX.1-dev, which nothing in this project could verify (it has no real weights).
- * cache == NULL: fmi_flux_denoise_context, launch for launch.  With a cache, every step after the first computed one makes ONE small device-to-host copy and ONE
- * hipStreamSynchronize on `stream` (the decision is taken on the host): unlike the other loops this entry is not legal under stream capture; decisions_out and
- * distances_out are complete when it returns (the last step's launches may still be queued, as with the other loops).  The first cached call allocates four (B,S',D) f32
- * device buffers (regrown when a larger shape comes; fmi_flux_step_cache_bytes reports them); the other entries never allocate them.
+ * With a cache, every step after the first computed one makes ONE small device-to-host copy and ONE hipStreamSynchronize on `stream` (the decision is taken on
+ * the host): a cached loop is not legal under stream capture; decisions_out and distances_out are complete when it returns (the last step's launches may still be
+ * queued, as without a cache).  The first cached call allocates four (B,S',D) f32 device buffers (regrown when a larger shape comes; fmi_flux_step_cache_bytes
+ * reports them); a call without a cache never allocates them.
  * Works in the bf16, int8 and e4m3 modes, with nf4 weights and with LoRA adapters: it touches the f32 residual stream only.
  * FMI_ERR_INVALID: threshold negative or NaN; a force entry outside -1 / 0 / 1; force[0] == 1.  FMI_ERR_UNSUPPORTED: a model without double blocks
- * (num_layers < 1); sequence parallelism set (the distance would need an all-reduce).  FMI_ERR_STATE: while int8 calibration is recording.  All before any launch. */
+ * (num_layers < 1); sequence parallelism set (the distance would need an all-reduce).  FMI_ERR_STATE: while int8 calibration is recording. */
 typedef struct fmi_flux_step_cache {
   float threshold;          /* 0: never reuse by distance; > 0: reuse when every sample's distance < threshold */
   const int8_t* force;      /* NULL or n_steps entries: -1 decide by threshold, 0 compute, 1 reuse */
   int32_t* decisions_out;   /* NULL or n_steps: 0 computed, 1 reused (host) */
   float* distances_out;     /* NULL or n_steps * B, step-major: d_b, -1 where not measured (host) */
 } fmi_flux_step_cache;
-int fmi_flux_denoise_cached(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx /* NULL ok */, float* img_inout, const double* timesteps_host,
-                            int n_steps, const float* x0, const float* noise, const float* mask /* all three or none */,
-                            const fmi_flux_step_cache* cache /* NULL: == fmi_flux_denoise_context */, void* stream);
 size_t fmi_flux_step_cache_bytes(fmi_flux*);
 
 /* True classifier-free guidance in the denoise loop (diffusers' FluxPipeline with negative_prompt= and true_cfg_scale > 1, `do_true_cfg`; the
- * reference has no counterpart).  fmi_flux_denoise_cfg is fmi_flux_denoise_context — same arguments, same state (B,S,in_channels) f32 — whose every step evaluates
- * the model ONCE on an internal batch of 2B samples: rows [0,B) the prompt's (in->txt, in->y), rows [B,2B) the negative's (neg_txt, neg_y); the state, the ids, the
- * guidance vector and the context rows are the same in both halves.  With dt = f32(ts[i+1] - ts[i]) and s = f32(ts[i+1]) the update is one pass,
+ * reference has no counterpart).  Every step evaluates the model ONCE on an internal batch of 2B samples: rows [0,B) the prompt's (in->txt, in->y), rows [B,2B)
+ * the negative's (neg_txt, neg_y); the state (B,S,in_channels) f32, the ids, the guidance vector, the context rows and the control are the same in both halves.
+ * With dt = f32(ts[i+1] - ts[i]) and s = f32(ts[i+1]) the update is one pass,
  *   g = neg + scale * (pos - neg)             (diffusers' expression, the difference first: pos == neg or scale == 0 gives neg bit for bit;
  *                                              scale == 1 is NOT special-cased and is not pos bit for bit)
- *   e = img + g * dt                          (fmi_flux_denoise's update)
- *   img = e,  or with x0 / noise / mask       img = mask * e + (1 - mask) * ((1 - s) * x0 + s * noise)       (fmi_flux_denoise_inpaint's blend, unchanged)
+ *   e = img + g * dt                          (the plain update)
+ *   img = e,  or with x0 / noise / mask       img = mask * e + (1 - mask) * ((1 - s) * x0 + s * noise)       (the blend, unchanged)
  * The once-per-image modulation GEMM, txt_in, the context rows and the RoPE table are hoisted for the 2B rows exactly as for a batch of 2B prompts, and each
  * sample of the call equals its own B = 1 call bit for bit.  The workspace is that of a batch of 2B.
- * cfg == NULL: fmi_flux_denoise_context, launch for launch.  Works in the bf16, int8 and e4m3 modes, on models without a guidance vector (in->guidance NULL)
- * and with a context.  The step cache (fmi_flux_denoise_cached) is not combined with it.
- * FMI_ERR_INVALID: neg_txt or neg_y NULL; a dtype that is not F32 or BF16; scale negative, NaN or infinite; x0 / noise / mask given in part.
+ * Works in the bf16, int8 and e4m3 modes and on models without a guidance vector (in->guidance NULL).
+ * FMI_ERR_INVALID: neg_txt or neg_y NULL; a dtype that is not F32 or BF16; scale negative, NaN or infinite.
  * FMI_ERR_UNSUPPORTED: in->B > 4 (2B would exceed the per-device limit of 8); sequence parallelism set (it runs B = 1); n_steps * 2B > 4096 (the
- * loops' limit of n_steps * B rows, counted on the internal batch).
- * FMI_ERR_STATE: while int8 calibration is recording.  All before any launch. */
+ * loop's limit of n_steps * B rows, counted on the internal batch).
+ * FMI_ERR_STATE: while int8 calibration is recording. */
 typedef struct fmi_flux_true_cfg {
   const void* neg_txt; fmi_dtype neg_txt_dtype;   /* (B,T,joint_attention_dim) F32|BF16, same T as in->txt */
   const void* neg_y;   fmi_dtype neg_y_dtype;     /* (B,pooled_projection_dim) F32|BF16 */
   float scale;                                    /* finite, >= 0 */
 } fmi_flux_true_cfg;
-int fmi_flux_denoise_cfg(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx /* NULL ok */,
-                         const fmi_flux_true_cfg* cfg /* NULL: == fmi_flux_denoise_context */,
-                         float* img_inout, const double* timesteps_host, int n_steps,
-                         const float* x0, const float* noise, const float* mask /* all three or none */, void* stream);
 
 /* Channel-concatenated conditioning (diffusers' FluxControlPipeline and FluxFillPipeline; the reference has no counterpart).  On a model made by
  * fmi_flux_create_cond with cond_channels > 0 one evaluation is Flux::forward on cat([img, cond], 2): the bf16 x_embedder operand (B*S, in_channels + cond_channels)
  * takes the state in its first in_channels columns every step and the conditioning in the others once per call (fmi_cast_cols_bf16).  The prediction, the state,
  * the Euler update, the blend and the CFG combine stay in_channels wide and keep their expressions; under true CFG both halves of the batch see the same cond.
- * fmi_flux_denoise_control is fmi_flux_denoise_cfg without a context and with a control: cfg NULL is the plain loop, x0 / noise / mask select the blend.  The
- * once-per-image modulation GEMM, txt_in and the RoPE table are hoisted as ever.  Both entries work in the bf16, int8 and e4m3 modes (x_embedder is not a block
- * linear) and while int8 calibration records (the forward; the loop without cfg).
- * FMI_ERR_INVALID, before any launch: ctl or ctl->cond NULL, or a cond_dtype that is not F32 / BF16, on a model with cond_channels > 0 — hence EVERY other forward
- * / denoise entry on such a model —; a non-NULL ctl on a model with cond_channels == 0 (there a NULL ctl makes these two entries fmi_flux_forward and
- * fmi_flux_denoise_cfg without a context).  FMI_ERR_UNSUPPORTED: sequence parallelism; a context (fmi_flux_context) together with a control. */
+ * The once-per-image modulation GEMM, txt_in and the RoPE table are hoisted as ever.  The forward and the loop work in the bf16, int8 and e4m3 modes (x_embedder
+ * is not a block linear) and while int8 calibration records (the forward; the loop without cfg).
+ * FMI_ERR_INVALID: ctl or ctl->cond NULL, or a cond_dtype that is not F32 / BF16, on a model with cond_channels > 0 — hence EVERY forward / denoise call without
+ * a control on such a model —; a non-NULL ctl on a model with cond_channels == 0.  FMI_ERR_UNSUPPORTED: sequence parallelism. */
 typedef struct fmi_flux_control {
   const void* cond; fmi_dtype cond_dtype;   /* (B,S,cond_channels) F32|BF16 */
 } fmi_flux_control;
 int fmi_flux_forward_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream);
-int fmi_flux_denoise_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg /* NULL ok */,
+
+/* The whole denoise loop == Sampler::sample(FlowMatchEulerDiscrete)
+ * (pipelines/sampling.rs:25-48) around the step closure (pipelines/flux/mod.rs:305-318):
+ *   for (t_curr,t_prev) in windows(timesteps): img += forward(img, t_curr) * (t_prev-t_curr)
+ * `img_inout` (B,S,C) f32 is the state, updated in place (in->img and in->timesteps are ignored); `timesteps_host`
+ * (n_steps+1 f64, host) drives the loop, exactly the Vec<f64> of SchedulerConfig::get_timesteps.
+ * The latent stays f32 between steps.
+ * `opts` names what every evaluation and the per-step update are conditioned on; a NULL opts is a struct of NULLs, the reference's loop.  An option that is
+ * NULL costs nothing: the call then issues exactly the launches, and makes exactly the allocations, of a call that never heard of it.
+ * Which options combine (yes), and the code that refuses the pairs that do not:
+ *             ctl                   cfg    cache                 x0/noise/mask
+ *   ctx       FMI_ERR_UNSUPPORTED   yes    yes                   yes
+ *   ctl                             yes    FMI_ERR_UNSUPPORTED   yes
+ *   cfg                                    FMI_ERR_UNSUPPORTED   yes
+ *   cache                                                        yes
+ * Three or more combine when every pair among them does.  x0 / noise / mask given only in part: FMI_ERR_INVALID.  Each option's own refusals are listed at its
+ * struct above; n_steps * B > 4096 is FMI_ERR_UNSUPPORTED.  EVERY refusal — of an argument, an option or a combination — comes before any launch, any
+ * allocation and any use of `stream`: a refused call leaves img_inout, the outputs of `cache` and the model as they were. */
+typedef struct fmi_flux_denoise_options {
+  const fmi_flux_context*    ctx;    /* NULL or R == 0: none */
+  const fmi_flux_control*    ctl;    /* required on a cond_channels > 0 model, refused on any other */
+  const fmi_flux_true_cfg*   cfg;    /* NULL: no negative prompt */
+  const fmi_flux_step_cache* cache;  /* NULL: no step cache */
+  const float *x0, *noise, *mask;    /* all three or none */
+} fmi_flux_denoise_options;
+int fmi_flux_denoise_with(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */,
+                          float* img_inout, const double* timesteps_host, int n_steps, void* stream);
+
+/* The entries from before fmi_flux_denoise_with.  Each IS fmi_flux_denoise_with with the fields it names set from its arguments and every other field NULL —
+ * the same launches, bits, errors and allocations. */
+/* no field */
+int fmi_flux_denoise(fmi_flux*, const fmi_flux_inputs* in, float* img_inout,
+                     const double* timesteps_host, int n_steps, void* stream);
+/* x0, noise, mask — here all three are required (FMI_ERR_INVALID) */
+int fmi_flux_denoise_inpaint(fmi_flux*, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps,
+                             const float* x0, const float* noise, const float* mask, void* stream);
+/* ctx, x0, noise, mask */
+int fmi_flux_denoise_context(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host, int n_steps,
+                             const float* x0, const float* noise, const float* mask, void* stream);
+/* ctx, x0, noise, mask, cache */
+int fmi_flux_denoise_cached(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
+                            int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream);
+/* ctx, cfg, x0, noise, mask */
+int fmi_flux_denoise_cfg(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_true_cfg* cfg,
+                         float* img_inout, const double* timesteps_host, int n_steps,
+                         const float* x0, const float* noise, const float* mask, void* stream);
+/* ctl, cfg, x0, noise, mask */
+int fmi_flux_denoise_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg,
                              float* img_inout, const double* timesteps_host, int n_steps,
-                             const float* x0, const float* noise, const float* mask /* all three or none */, void* stream);
+                             const float* x0, const float* noise, const float* mask, void* stream);
 
 /* Per-phase device time of the last forward in ms (hipEvents; enabled by
  * fmi_flux_set_profiling(1), which also serialises phases).  Phases: see fmi_flux_phase_name.
