@@ -485,6 +485,10 @@ int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hip
 int launch_cast_rows_bf16(const void* src, fmi_dtype dt, int64_t src_bs, bf16_t* dst, int64_t dst_bs, int B, int64_t n, hipStream_t stream, int B_src = 0);
 // column-window cast: row r of src (rows_src, cols) F32 | BF16, read at r % rows_src, -> bf16 at dst[r * dst_ld + col0 .. + cols); the other columns stay (small_ops.hip)
 int launch_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t rows_src, int cols, bf16_t* dst, int dst_ld, int col0, hipStream_t stream);
+// controlnet.hip: x[b, r, :] = x[b, r, :] + c * f32(src[b, r, :]) for r < rows, sample b of x at x + b * x_bs and of src (B, rows, D) contiguous — one unfused
+// multiply and one add per element.  The residual injection of a ControlNet (bf16 samples) and its input sum (f32, c = 1).
+int launch_add_scaled_rows_bf16(float* x, int64_t x_bs, const bf16_t* src, int B, int64_t rows, int D, float c, hipStream_t stream);
+int launch_add_scaled_rows_f32(float* x, int64_t x_bs, const float* src, int B, int64_t rows, int D, float c, hipStream_t stream);
 int launch_silu_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream);
 // the masked (inpainting) step: img = mask * (img + pred * dt) + (1 - mask) * ((1 - s) * x0 + s * noise), one pass (small_ops.hip)

@@ -211,6 +211,17 @@ struct fmi_flux {
   std::map<std::string, DeviceBuffer> lora_backup;  // by weight name: private allocations, not part of the flat state (fmi_flux_state_*)
   DeviceBuffer lora_scratch;                        // the concatenated factors of the merge in flight (grow-only; released with the last adapter)
   std::vector<DeviceBuffer> lora_dead;              // blocks a LoRA call has retired (MOVED here, not freed): freed behind its one final synchronisation (lora_leave)
+  // ControlNet (fmi_flux_create_controlnet): a truncated FLUX without a final layer, whose every block's image rows go through a zero-initialised
+  // Linear(D, D) into a bf16 sample the main model's evaluation adds to its own f32 stream.  bf16 only: the 8-bit modes, LoRA and the quantised setters refuse it.
+  bool is_cn = false;
+  Dense cn_x;                         // controlnet_x_embedder (D, in_channels)
+  std::vector<Dense> cn_dbl, cn_sgl;  // controlnet_blocks.{i}, controlnet_single_blocks.{j}
+  // sized by the first evaluation, regrown when a larger shape comes (fmi_flux_size_in_bytes counts them); a handle that is no ControlNet never allocates them
+  DeviceBuffer cn_samples;  // bf16: sample k (k < nd: double block k; nd + j: single block j) at k * cn_elems, each (B, S, D)
+  DeviceBuffer cn_cx;       // f32 (B*S, D): controlnet_x_embedder(cond), once per call
+  DeviceBuffer cn_cond_bf;  // bf16 (B*S, in_channels): its operand
+  size_t cn_elems = 0;      // B * S * D of the evaluation the samples belong to
+  int cn_B = 0, cn_S = 0;
 };
 
 static int compute_attention_scales(fmi_flux* m);  // (defined with the 8-bit modes below)
@@ -287,8 +298,9 @@ void build_layout(fmi_flux* m) {
   }
   layout_dense(m, m->vecin1, D, c.pooled_projection_dim, AR_BASE);
   layout_dense(m, m->vecin2, D, D, AR_BASE);
-  layout_dense(m, m->final_proj, c.in_channels, D, AR_BASE);
-  m->n_mod = (int64_t)c.num_layers * 12 * D + (int64_t)c.num_single_layers * 3 * D + 2 * D;
+  if (m->is_cn) layout_dense(m, m->cn_x, D, c.in_channels, AR_BASE);  // (a ControlNet has no norm_out / proj_out)
+  else layout_dense(m, m->final_proj, c.in_channels, D, AR_BASE);
+  m->n_mod = (int64_t)c.num_layers * 12 * D + (int64_t)c.num_single_layers * 3 * D + (m->is_cn ? 0 : 2 * D);
   layout_dense(m, m->mod_all, (int)m->n_mod, D, AR_MOD);
   m->dbl.resize(c.num_layers);
   m->sgl.resize(c.num_single_layers);
@@ -321,6 +333,12 @@ void build_layout(fmi_flux* m) {
     moff += 3 * D;
   }
   m->mod_final_off = moff;
+  if (m->is_cn) {  // the zero-linears, one per block (sized before the first layout: `fused` keeps pointers into the vectors)
+    m->cn_dbl.resize(c.num_layers);
+    m->cn_sgl.resize(c.num_single_layers);
+    for (auto& d : m->cn_dbl) layout_dense(m, d, D, D, AR_BLOCKS);
+    for (auto& d : m->cn_sgl) layout_dense(m, d, D, D, AR_BLOCKS);
+  }
   for (int a = 0; a < AR_COUNT; ++a) m->arena[a].bytes = align_up(m->cursor[a], 256) + 256;
 }
 
@@ -332,7 +350,7 @@ void resolve_base_and_names(fmi_flux* m) {
   auto fix = [&](bf16_t*& p) {
     if (p) p = reinterpret_cast<bf16_t*>(base + (reinterpret_cast<uintptr_t>(p) - 1));
   };
-  std::vector<Dense*> small = {&m->img_in, &m->txt_in, &m->time1, &m->time2, &m->vecin1, &m->vecin2, &m->final_proj};
+  std::vector<Dense*> small = {&m->img_in, &m->txt_in, &m->time1, &m->time2, &m->vecin1, &m->vecin2, m->is_cn ? &m->cn_x : &m->final_proj};
   if (c.guidance_embeds) small.push_back(&m->guid1), small.push_back(&m->guid2);
   for (Dense* d : small) {
     d->w = reinterpret_cast<bf16_t*>(base + d->w_off);
@@ -353,8 +371,14 @@ void resolve_base_and_names(fmi_flux* m) {
   }
   reg_lin(m, "time_text_embed.text_embedder.linear_1", m->vecin1, 0, D);
   reg_lin(m, "time_text_embed.text_embedder.linear_2", m->vecin2, 0, D);
-  reg_lin(m, "proj_out", m->final_proj, 0, c.in_channels);
-  reg_lin(m, "norm_out.linear", m->mod_all, (int)m->mod_final_off, 2 * D);
+  if (m->is_cn) {
+    reg_lin(m, "controlnet_x_embedder", m->cn_x, 0, D);
+    for (int i = 0; i < c.num_layers; ++i) reg_lin(m, "controlnet_blocks." + std::to_string(i), m->cn_dbl[i], 0, D);
+    for (int i = 0; i < c.num_single_layers; ++i) reg_lin(m, "controlnet_single_blocks." + std::to_string(i), m->cn_sgl[i], 0, D);
+  } else {
+    reg_lin(m, "proj_out", m->final_proj, 0, c.in_channels);
+    reg_lin(m, "norm_out.linear", m->mod_all, (int)m->mod_final_off, 2 * D);
+  }
   for (int i = 0; i < c.num_layers; ++i) {
     auto& b = m->dbl[i];
     const std::string p = "transformer_blocks." + std::to_string(i) + ".";
@@ -839,7 +863,37 @@ struct EvalPlan {
   fmi_flux_denoise_options o;  // every field null where the call has none
   int R;                       // context rows per sample (0: none, the text-to-image launches)
   int Bs;                      // the state's samples: in->B — under true CFG `in` is the loop's internal batch of 2 * Bs
+  const fmi_flux_controlnet* cn = nullptr;  // the call's ControlNet, else null
 };
+// The injection hook of forward_core: the ControlNet whose samples the evaluation adds to its f32 stream, and this step's scale (never 0: such a step has no hook).
+struct CnInject {
+  const fmi_flux* net;
+  float c;
+};
+
+// The ControlNet's per-shape buffers, sized by the first evaluation and regrown when a larger shape comes.
+int cn_ensure(fmi_flux* net, int B, int S, hipStream_t s) {
+  const size_t elems = (size_t)B * S * net->D, n = net->cn_dbl.size() + net->cn_sgl.size();
+  if (net->cn_samples.bytes() < n * elems * 2 || net->cn_cx.bytes() < elems * 4) {
+    FMI_HIP_TRY(hipStreamSynchronize(s));
+    if (net->cn_samples.alloc(n * elems * 2) != hipSuccess || net->cn_cx.alloc(elems * 4) != hipSuccess ||
+        net->cn_cond_bf.alloc((size_t)B * S * net->cfg.in_channels * 2) != hipSuccess) {
+      net->cn_samples.reset(), net->cn_cx.reset(), net->cn_cond_bf.reset();
+      return fail(FMI_ERR_NOMEM, "flux controlnet: hipMalloc of the sample buffers failed");
+    }
+  }
+  net->cn_elems = elems, net->cn_B = B, net->cn_S = S;
+  return FMI_OK;
+}
+// controlnet_x_embedder(cond) for the B samples of the evaluations to come (cond holds Bs of them: both halves of a true-CFG batch see the same), once per call:
+// it does not depend on the state or on t.  Kept in f32 — the sum x_embedder(img) + controlnet_x_embedder(cond) is taken in f32 at every step.
+int cn_embed_cond(fmi_flux* net, const void* cond, fmi_dtype dt, int B, int Bs, int S, hipStream_t s) {
+  const int C = net->cfg.in_channels;
+  PhaseTimer pt(net, s, PH_EMBED);
+  FMI_TRY(launch_cast_cols_bf16(cond, dt, (int64_t)B * S, (int64_t)Bs * S, C, net->cn_cond_bf.as<bf16_t>(), C, 0, s));
+  GemmProblem p = make_problem(net->cn_x, net->cn_cond_bf.as<bf16_t>(), C, B * S, net->cn_cx.ptr, net->D, EPI_STORE_F32);
+  return gemm1(net, p, net->cn_x, s);
+}
 
 // Everything of Flux::forward that does not depend on the timestep: input casts + RoPE table.
 // p.R > 0 (a context evaluation): the context's rows of the table, and its rows [S, S + R) of every sample of the bf16 img_in operand
@@ -957,8 +1011,10 @@ int step_cache_decide(fmi_flux* m, StepCacheRun* sc, int B, int S, int T, hipStr
 // mod_pre: this step's (B, n_mod) modulation vectors where the loop precomputed them, else null.
 // txt_pre: txt_in(txt) where the loop computed it once for all steps (it does not depend on the latent or on t), else null.
 // sc: the step cache of a cached loop, else null — and with null every launch below is the one it always was.
+// inj: the ControlNet samples this evaluation adds to its f32 stream, else null — likewise.  On a ControlNet handle (m->is_cn) the evaluation
+// instead captures those samples after every block into m->cn_samples and ends after the last block: it has no final layer, and pred is not written.
 int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, const float* img_f32, const float* timesteps_dev, float* pred, const float* mod_pre,
-                 const float* txt_pre, StepCacheRun* sc, hipStream_t s) {
+                 const float* txt_pre, StepCacheRun* sc, const CnInject* inj, hipStream_t s) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
   const int B = in->B, Bs = p.Bs, R = p.R, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
@@ -980,7 +1036,24 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
   if (m->fp8_attn == 2 && !sp && !m->attn_scales_valid) FMI_TRY(compute_attention_scales(m));
   const bool qk8_any = m->fp8_attn == 2 && !sp;  // opt-in: e4m3 q, k in front of QK^T whatever the block linears run on
   const int BT = B * T;  // a8 / a8s rows: [txt (B*T) | img (B*S)]
-
+  // The two ControlNet hooks, after double block i (single = false) or single block i: `rows` = where the block left the image rows, sample b at rows + b * bs.
+  //   capture (a ControlNet handle)   sample = bf16(zero_linear(bf16(rows))): the rows cast into the free LayerNorm output buffer, then the existing GEMM launcher
+  //   inject (the main model)         rows += c * f32(sample[i // ceil(n_main / n_net)]), one launch (controlnet.hip)
+  const auto cn_hook = [&](bool single, int i, float* rows, int64_t bs) -> int {
+    if (m->is_cn) {
+      PhaseTimer pt(m, s, PH_EMBED);
+      FMI_TRY(launch_cast_rows_bf16(rows, FMI_F32, bs, w.xm, (int64_t)S * D, B, (int64_t)S * D, s));
+      Dense& zl = single ? m->cn_sgl[i] : m->cn_dbl[i];
+      GemmProblem q = make_problem(zl, w.xm, D, B * S, m->cn_samples.as<bf16_t>() + ((single ? m->cn_dbl.size() : 0) + i) * m->cn_elems, D, EPI_STORE_BF16);
+      return gemm1(m, q, zl, s);
+    }
+    if (!inj) return FMI_OK;
+    const int n_net = (int)(single ? inj->net->cn_sgl.size() : inj->net->cn_dbl.size()), n_main = single ? c.num_single_layers : c.num_layers;
+    if (!n_net) return FMI_OK;  // (a ControlNet without single blocks leaves the single blocks alone)
+    const int k = i / ((n_main + n_net - 1) / n_net);
+    PhaseTimer pt(m, s, PH_EMBED);
+    return launch_add_scaled_rows_bf16(rows, bs, inj->net->cn_samples.as<bf16_t>() + ((single ? inj->net->cn_dbl.size() : 0) + k) * inj->net->cn_elems, B, S, D, inj->c, s);
+  };
   {
     PhaseTimer pt(m, s, PH_EMBED);
     if (m->cond)  // the state into columns [0, C) of the [state | conditioning] operand, both halves of a true-CFG batch in the one launch (no context: R == 0)
@@ -999,6 +1072,8 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
     } else {
       FMI_TRY(gemm2(m, p, dn, 2, s));
     }
+    if (m->is_cn)  // x = x_embedder(img) + controlnet_x_embedder(cond), the second term computed once per call (cn_embed_cond); c = 1: one exact f32 addition
+      FMI_TRY(launch_add_scaled_rows_f32(w.x_img, (int64_t)S * D, m->cn_cx.as<float>(), B, S, D, 1.0f, s));
     // step cache: X0 leaves before block 0's epilogues update the stream in place
     if (sc) FMI_HIP_TRY(hipMemcpyAsync(m->sc_x0.ptr, w.x_img, (size_t)B * S * D * 4, hipMemcpyDeviceToDevice, s));
   }
@@ -1104,6 +1179,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       }
       FMI_HIP_TRY(hipEventRecord(m->ev_join, m->side));
       FMI_HIP_TRY(hipStreamWaitEvent(s, m->ev_join, 0));
+      FMI_TRY(cn_hook(false, i, w.x_img, (int64_t)S * D));  // (behind the join: the image chain ran on s, and the hook's launches are ordered after both chains)
       continue;
     }
     {
@@ -1166,6 +1242,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       Dense* dn2[2] = {&bw.mlp2[0], &bw.mlp2[1]};
       FMI_TRY(gemm2(m, p, dn2, 2, s));
     }
+    FMI_TRY(cn_hook(false, i, w.x_img, (int64_t)S * D));
   }
 
   // ---------------- cat([txt, img], 1) (model.rs:827) then single-stream blocks (model.rs:638-662)
@@ -1225,7 +1302,9 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       with_gate(p, mo + 2 * D, L, nmod);
       FMI_TRY(gemm1(m, p, bw.w2, s));
     }
+    FMI_TRY(cn_hook(true, i, w.x + (size_t)T * D, (int64_t)L * D));
   }
+  if (m->is_cn) return FMI_OK;
   if (sc) {
     if (!reuse) {  // a computed step: delta = XF - X1 (the copy taken with the residual), this step's residual becomes the reference
       PhaseTimer pt(m, s, PH_EMBED);
@@ -1260,7 +1339,8 @@ int check_inputs(fmi_flux* m, const fmi_flux_inputs* in) {
 // Every refusal of a forward or denoise call — of its arguments, each option and each combination (the table at fmi_flux_denoise_with) — in the one place, before the call's
 // stream is used or anything is launched or allocated for it (check_inputs makes the handle's device current and completes a freshly loaded model: the model's state, not the
 // call's).  *p: the accepted call's plan.  A forward is n_steps == 1 with ctx / ctl only.  bad_io: the entry's message when a pointer outside `in` and `o` is unusable, else null.
-int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options& o, int n_steps, const char* bad_io, EvalPlan* p) {
+int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, int n_steps, const char* bad_io, EvalPlan* p) {
+  if (m && m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "flux: a ControlNet handle is evaluated through the main model (fmi_flux_forward_controlnet / fmi_flux_denoise_controlnet) or fmi_flux_controlnet_eval");
   if ((o.x0 || o.noise || o.mask) && !(o.x0 && o.noise && o.mask)) return fail(FMI_ERR_INVALID, "flux_denoise: x0, noise and mask go together (all three or none)");
   FMI_TRY(check_inputs(m, in));
   if (bad_io) return fail(FMI_ERR_INVALID, bad_io);
@@ -1303,6 +1383,29 @@ int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_opti
     if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the step cache is not supported under sequence parallelism");
     if (m->calib) return fail(FMI_ERR_STATE, "flux_denoise: no step cache while int8 calibration is recording");
   }
+  if (cn) {  // one ControlNet; several at once, union modes and the pixel-space hint block are out of scope
+    fmi_flux* net = cn->net;
+    if (!net || !net->is_cn) return fail(FMI_ERR_INVALID, "flux: controlnet->net is not a ControlNet handle (fmi_flux_create_controlnet)");
+    if (!cn->cond) return fail(FMI_ERR_INVALID, "flux: a ControlNet needs cond, the packed latents of the control image (B,S,in_channels)");
+    if (!f32_or_bf16(cn->cond_dtype)) return fail(FMI_ERR_INVALID, "flux: controlnet cond_dtype must be F32 or BF16");
+    if (!std::isfinite(cn->scale)) return fail(FMI_ERR_INVALID, "flux: the ControlNet scale must be finite");
+    for (int i = 0; cn->step_scales && i < n_steps; ++i)
+      if (!std::isfinite(cn->step_scales[i])) return fail(FMI_ERR_INVALID, "flux_denoise: every entry of the ControlNet's step_scales must be finite");
+    const fmi_flux_config &a = m->cfg, &b = net->cfg;
+    if (net->D != m->D || a.num_attention_heads != b.num_attention_heads || a.joint_attention_dim != b.joint_attention_dim ||
+        a.pooled_projection_dim != b.pooled_projection_dim || a.in_channels != b.in_channels || a.theta != b.theta || a.axes_dim[0] != b.axes_dim[0] ||
+        a.axes_dim[1] != b.axes_dim[1] || a.axes_dim[2] != b.axes_dim[2])
+      return fail(FMI_ERR_INVALID, "flux: the ControlNet's width, heads, joint_attention_dim, pooled_projection_dim, axes_dim, theta and in_channels must be the main model's");
+    if (net->device != m->device) return fail(FMI_ERR_INVALID, "flux: the ControlNet lives on another device than the main model");
+    if (b.guidance_embeds && !in->guidance) return fail(FMI_ERR_INVALID, "flux: a guidance_embeds ControlNet needs a guidance vector");
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: a ControlNet is not combined with a context");
+    if (m->cond) return fail(FMI_ERR_UNSUPPORTED, "flux: a ControlNet is not combined with a channel-conditioned model (cond_channels > 0)");
+    if (o.cache) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: a ControlNet is not combined with the step cache");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux: a ControlNet is not supported under sequence parallelism");
+    FMI_TRY(net->missing.ready("flux controlnet"));
+    FMI_TRY(finalize(net));
+    p->cn = cn;
+  }
   return FMI_OK;
 }
 
@@ -1321,11 +1424,22 @@ extern "C" void fmi_flux_default_config(fmi_flux_config* cfg, int guidance_embed
   cfg->theta = 10000;
 }
 
-extern "C" int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out) { return fmi_flux_create_cond(cfg, 0, dtype, out); }
+static int flux_create(const fmi_flux_config* cfg, int cond_channels, bool controlnet, fmi_model_dtype dtype, fmi_flux** out);
+extern "C" int fmi_flux_create(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out) { return flux_create(cfg, 0, false, dtype, out); }
 extern "C" int fmi_flux_cond_channels(const fmi_flux* m) { return m ? m->cond : 0; }
+// A ControlNet (diffusers' FluxControlNetModel): cfg->num_layers / num_single_layers are the net's own (at least one double block; no single
+// blocks is allowed), everything else must be the main model's when the two meet.  No norm_out / proj_out; controlnet_x_embedder and one zero-linear per block more.
+extern "C" int fmi_flux_create_controlnet(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out) {
+  if (cfg && cfg->num_layers < 1) return fail(FMI_ERR_INVALID, "flux_create_controlnet: a ControlNet has at least one double block");
+  return flux_create(cfg, 0, true, dtype, out);
+}
+extern "C" int fmi_flux_is_controlnet(const fmi_flux* m) { return m && m->is_cn ? 1 : 0; }
 
 // x_embedder of a channel-conditioned checkpoint (FLUX.1 Fill / Canny / Depth) is (D, in_channels + cond_channels); everything else keeps in_channels.
 extern "C" int fmi_flux_create_cond(const fmi_flux_config* cfg, int cond_channels, fmi_model_dtype dtype, fmi_flux** out) {
+  return flux_create(cfg, cond_channels, false, dtype, out);
+}
+static int flux_create(const fmi_flux_config* cfg, int cond_channels, bool controlnet, fmi_model_dtype dtype, fmi_flux** out) {
   if (!cfg || !out) return fail(FMI_ERR_INVALID, "flux_create: null argument");
   if (cond_channels < 0 || cond_channels % 64 || (int64_t)cfg->in_channels + cond_channels > 512)
     return fail(FMI_ERR_INVALID, "flux_create_cond: cond_channels must be >= 0, a multiple of 64, and in_channels + cond_channels at most 512");
@@ -1339,6 +1453,7 @@ extern "C" int fmi_flux_create_cond(const fmi_flux_config* cfg, int cond_channel
   fmi_flux* m = new fmi_flux();
   m->cfg = *cfg;
   m->cond = cond_channels;
+  m->is_cn = controlnet;
   hipGetDevice(&m->device);
   m->H = cfg->num_attention_heads;
   m->D = m->H * 128;  // HIDDEN_SIZE (model.rs:17) generalised as heads * pe_dim
@@ -1425,6 +1540,7 @@ int expand_small(const Dest& dst, const void* q, size_t qbytes, const float* sc,
 extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const uint8_t* packed, const float* absmax, int blocksize,
                                         int quant_type, int out_features, int in_features) {
   if (!m || !prefix || !packed || !absmax) return fail(FMI_ERR_INVALID, "set_linear_bnb4: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
   if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_bnb4: the model was quantised to fp8");
   if (quant_type != 1 && quant_type != 2) return fail(FMI_ERR_INVALID, "set_linear_bnb4: quant_type must be 1 (fp4) or 2 (nf4)");
   if (blocksize % 64 || blocksize <= 0 || in_features % blocksize)
@@ -1466,6 +1582,7 @@ extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const u
 // fused matrices keep the int8 weight and are expanded right before their GEMM (or once, with the dense cache).
 extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const int8_t* weight, const float* scb, int out_features, int in_features) {
   if (!m || !prefix || !weight || !scb) return fail(FMI_ERR_INVALID, "set_linear_int8: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_int8: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
   if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_int8: the model was quantised to fp8");
   FMI_TRY(use_device(m));
   const std::string wname = std::string(prefix) + ".weight";
@@ -1510,6 +1627,7 @@ extern "C" const char* fmi_flux_missing_name(const fmi_flux* m, int i) { return 
 extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
   if (!m) return 0;
   size_t b = m->ws.base.bytes() + m->fp8_arena.bytes() + m->wscratch[0].bytes() + m->wscratch[1].bytes() + m->mod_steps_rows * ((size_t)m->n_mod * 4 + (size_t)m->D * 6);
+  b += m->cn_samples.bytes() + m->cn_cx.bytes() + m->cn_cond_bf.bytes();  // (a ControlNet's per-shape buffers; 0 on any other handle)
   for (int a = 0; a < AR_COUNT; ++a)
     if (m->arena[a].base) b += m->arena[a].bytes;
   for (const Dense* d : m->fused)
@@ -1588,23 +1706,48 @@ extern "C" int fmi_flux_state_buffer(fmi_flux* m, int index, void** ptr, size_t*
 }
 
 // One evaluation of every forward entry: over cat([img, ctx], 1) with a context, over cat([img, cond], 2) with a control.
-static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, float* pred_out, void* stream) {
+// The plan of the ControlNet's own evaluations: the main call's negative prompt and batch, nothing else of its options.
+static EvalPlan cn_plan(const EvalPlan& p) { return EvalPlan{fmi_flux_denoise_options{nullptr, nullptr, p.o.cfg}, 0, p.Bs}; }
+// Once per call, on the ControlNet: its workspace and sample buffers for the call's batch, its input casts and RoPE table (prepare_static, as on the main model —
+// the table is built once per call), and controlnet_x_embedder(cond).
+static int cn_prepare(fmi_flux* net, const fmi_flux_inputs* in, const EvalPlan& p, hipStream_t s) {
+  FMI_TRY(ensure_workspace(net, in->B, in->S, in->T));
+  FMI_TRY(cn_ensure(net, in->B, in->S, s));
+  FMI_TRY(prepare_static(net, in, cn_plan(p), s));
+  return cn_embed_cond(net, p.cn->cond, p.cn->cond_dtype, in->B, p.Bs, in->S, s);
+}
+
+static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, const fmi_flux_controlnet* cn, float* pred_out,
+                        void* stream) {
   const fmi_flux_denoise_options o{ctx, ctl};  // (every other field null)
   EvalPlan p;
-  FMI_TRY(validate(m, in, o, 1, in && in->img && in->timesteps && pred_out ? nullptr : "flux_forward: null img/timesteps/pred_out", &p));
+  fmi_flux_controlnet one;  // a single evaluation ignores step_scales
+  if (cn) one = *cn, one.step_scales = nullptr, cn = &one;
+  FMI_TRY(validate(m, in, o, cn, 1, in && in->img && in->timesteps && pred_out ? nullptr : "flux_forward: null img/timesteps/pred_out", &p));
   hipStream_t s = (hipStream_t)stream;
   FMI_TRY(ensure_workspace(m, in->B, in->S + p.R, in->T));
   FMI_TRY(prepare_static(m, in, p, s));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, m->ws.img_f32, (int64_t)in->B * in->S * m->cfg.in_channels, s));
-  return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, s);
+  if (cn && cn->scale != 0.f) {  // (scale 0: the plain evaluation, launch for launch)
+    fmi_flux* net = cn->net;
+    FMI_TRY(cn_prepare(net, in, p, s));
+    FMI_TRY(forward_core(net, in, cn_plan(p), m->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+    const CnInject inj{net, cn->scale};
+    return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, &inj, s);
+  }
+  return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, /*inj*/ nullptr, s);
 }
 // One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
 extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
-  return forward_eval(m, in, ctx, nullptr, pred_out, stream);
+  return forward_eval(m, in, ctx, nullptr, nullptr, pred_out, stream);
 }
 // One evaluation over cat([img, cond], 2) of a channel-conditioned model; pred_out is (B,S,in_channels).  A plain model with ctl NULL: fmi_flux_forward.
 extern "C" int fmi_flux_forward_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream) {
-  return forward_eval(m, in, nullptr, ctl, pred_out, stream);
+  return forward_eval(m, in, nullptr, ctl, nullptr, pred_out, stream);
+}
+// One evaluation with a ControlNet's residuals injected after every block.  cn NULL: fmi_flux_forward.
+extern "C" int fmi_flux_forward_controlnet(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_controlnet* cn, float* pred_out, void* stream) {
+  return forward_eval(m, in, nullptr, nullptr, cn, pred_out, stream);
 }
 extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* pred_out, void* stream) {
   return fmi_flux_forward_context(m, in, nullptr, pred_out, stream);
@@ -1684,13 +1827,26 @@ static int hoist_steps(fmi_flux* m, const fmi_flux_inputs* in, const double* tim
 }
 
 // (d) of the loop: the steps.  One evaluation each, then the update of the state — one of three, and all that knows about the negative prompt's scale or the blend.
+// The ControlNet of one loop: what its steps share (hoisted like the main model's, null where each step computes its own) and each step's scale.
+struct CnRun {
+  fmi_flux* net;
+  const float *mod_steps, *txt_pre;
+  std::vector<float> c;  // scale * step_scales[i]; a step whose c is 0 launches neither the ControlNet nor an injection: it is the plain step
+};
 static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, float* img_inout, const double* timesteps_host, int n_steps, const float* mod_steps,
-                     const float* txt_pre, StepCacheRun* sc, hipStream_t s) {
+                     const float* txt_pre, StepCacheRun* sc, const CnRun* cn, hipStream_t s) {
   const fmi_flux_denoise_options& o = p.o;
   const size_t B = in->B, nmod = m->n_mod;
   const int64_t n = (int64_t)p.Bs * in->S * m->cfg.in_channels;
   for (int i = 0; i < n_steps; ++i) {
-    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, s));
+    CnInject inj{};
+    if (cn && cn->c[i] != 0.f) {  // the ControlNet on the step's state, then the main model with its samples
+      fmi_flux* net = cn->net;
+      FMI_TRY(forward_core(net, in, cn_plan(p), img_inout, net->ws.tv + i * B, nullptr, cn->mod_steps ? cn->mod_steps + i * B * (size_t)net->n_mod : nullptr, cn->txt_pre,
+                           nullptr, nullptr, s));
+      inj = CnInject{net, cn->c[i]};
+    }
+    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, inj.net ? &inj : nullptr, s));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
     if (o.cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
@@ -1707,9 +1863,10 @@ static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, 
 // known to few places: the blend to the update alone; the context and the control to the input assembly (prepare_static writes the context's rows and the conditioning's columns
 // of the img_in operand once, forward_core the state's every step); the negative prompt to the input assembly and the update — `in` below is then the loop's own batch of
 // 2 * Bs samples, the prompt's rows, then the negative's —; the step cache to forward_core after double block 0.
-static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, float* img_inout,
+                        const double* timesteps_host, int n_steps, void* stream) {
   EvalPlan p;
-  FMI_TRY(validate(m, in_caller, o, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
+  FMI_TRY(validate(m, in_caller, o, cn, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
   hipStream_t s = (hipStream_t)stream;
   fmi_flux_inputs in = *in_caller;
   if (o.cfg) in.B = 2 * p.Bs;
@@ -1725,37 +1882,52 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
   FMI_TRY(prepare_static(m, &in, p, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
   const float *mod_steps, *txt_pre;
   FMI_TRY(hoist_steps(m, &in, timesteps_host, n_steps, s, &mod_steps, &txt_pre));
-  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, s);
+  CnRun cr{cn ? cn->net : nullptr, nullptr, nullptr, {}};
+  bool cn_active = false;  // a ControlNet whose every step has scale 0 prepares nothing: the call is the plain loop, launch for launch
+  for (int i = 0; cn && i < n_steps; ++i) {
+    cr.c.push_back(cn->step_scales ? cn->scale * cn->step_scales[i] : cn->scale);
+    cn_active = cn_active || cr.c.back() != 0.f;
+  }
+  if (cn_active) {  // the ControlNet's once-per-image work, hoisted like the main model's: controlnet_x_embedder(cond), every step's modulation vectors, txt_in
+    FMI_TRY(cn_prepare(cr.net, &in, p, s));
+    FMI_TRY(hoist_steps(cr.net, &in, timesteps_host, n_steps, s, &cr.mod_steps, &cr.txt_pre));
+  }
+  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, cn_active ? &cr : nullptr, s);
 }
 
 extern "C" int fmi_flux_denoise_with(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
-  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, nullptr, img_inout, timesteps_host, n_steps, stream);
+}
+// The same loop with a ControlNet; cn NULL IS fmi_flux_denoise_with.
+extern "C" int fmi_flux_denoise_controlnet(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, const fmi_flux_controlnet* cn, float* img_inout,
+                                           const double* timesteps_host, int n_steps, void* stream) {
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, img_inout, timesteps_host, n_steps, stream);
 }
 
 // The entries from before fmi_flux_denoise_with: each fills the options its arguments name — {ctx, ctl, cfg, cache, x0, noise, mask} — and takes the same path.
 extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
-  return denoise_loop(m, in, fmi_flux_denoise_options{}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, fmi_flux_denoise_options{}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, const float* x0,
                                         const float* noise, const float* mask, void* stream) {
   if (!x0 || !noise || !mask) return fail(FMI_ERR_INVALID, "flux_denoise_inpaint: x0, noise and mask are all required");
-  return denoise_loop(m, in, {/*ctx*/ nullptr, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                         int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_cached(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                        int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, cache, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, cache, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_cfg(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_true_cfg* cfg, float* img_inout,
                                     const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, cfg, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg, float* img_inout,
                                         const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {/*ctx*/ nullptr, ctl, cfg, /*cache*/ nullptr, x0, noise, mask}, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, ctl, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 // device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
 extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {
@@ -1801,6 +1973,7 @@ extern "C" int fmi_flux_set_modulation_gemm(fmi_flux* m, int enable) {
 // how quantised block linears are multiplied: 0 (default) by size, 1 expanded once into bf16 copies (dense cache), 2 always fused
 extern "C" int fmi_flux_set_sequence_parallel(fmi_flux* m, int rank, int world_size, fmi_all_to_all_fn a2a, void* user) {
   if (!m) return fail(FMI_ERR_INVALID, "set_sequence_parallel: null handle");
+  if (m->is_cn && world_size > 1) return fail(FMI_ERR_UNSUPPORTED, "set_sequence_parallel: a ControlNet is not supported under sequence parallelism");
   if (world_size < 1 || rank < 0 || rank >= world_size) return fail(FMI_ERR_INVALID, "set_sequence_parallel: rank outside [0, world_size)");
   if (world_size > 1 && !a2a) return fail(FMI_ERR_INVALID, "set_sequence_parallel: world_size > 1 needs the all-to-all callback");
   if (m->H % world_size) return fail(FMI_ERR_INVALID, "set_sequence_parallel: " + std::to_string(m->H) + " heads do not split over " + std::to_string(world_size) + " ranks");
@@ -1878,6 +2051,7 @@ static int compute_attention_scales(fmi_flux* m) {
 // 8-bit modes: quantise the block Linears of `mask` once (bf16 arena -> e4m3 / int8 codes + per-output-channel scale); see the header.
 static int quantize_8bit(fmi_flux* m, int kind, unsigned mask, void* stream) {
   if (!m) return fail(FMI_ERR_INVALID, "null handle");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "quantize: a ControlNet runs in bf16 only (the main model may be in any mode: the injection touches its f32 stream)");
   FMI_TRY(use_device(m));
   FMI_TRY(check_ready(m));
   if (m->fp8) {
@@ -1969,6 +2143,7 @@ static int quantize_8bit(fmi_flux* m, int kind, unsigned mask, void* stream) {
 // statistics (the next quantise is the unsmoothed recipe).  Without a calibration fmi_flux_quantize_int8 is bit for bit what it was.
 extern "C" int fmi_flux_calibrate_int8(fmi_flux* m, int enable) {
   if (!m) return fail(FMI_ERR_INVALID, "null handle");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "calibrate_int8: a ControlNet runs in bf16 only");
   FMI_TRY(use_device(m));
   if (m->fp8) return fail(FMI_ERR_STATE, "calibrate_int8: the model already holds an 8-bit form (calibrate before quantising)");
   std::vector<Dense*> lin;
@@ -2013,6 +2188,7 @@ extern "C" int fmi_flux_quantize_int8(fmi_flux* m, unsigned linear_mask, void* s
 extern "C" int fmi_flux_set_fp8_attention(fmi_flux* m, int enable) {
   if (!m) return fail(FMI_ERR_INVALID, "null handle");
   if (enable < 0 || enable > 2) return fail(FMI_ERR_INVALID, "set_fp8_attention: 0 (off), 1 (on in the 8-bit modes) or 2 (on in every mode)");
+  if (m->is_cn && enable == 2) return fail(FMI_ERR_UNSUPPORTED, "set_fp8_attention: a ControlNet runs in bf16 only");
   m->fp8_attn = enable;
   // 2 in bf16 mode: the static scales come from the QkNorm weights — taken here when the weights are complete (not inside the next evaluation: they
   // are small synchronous copies), else at the first evaluation after the last tensor arrived
@@ -2151,6 +2327,7 @@ int lora_upload_f32(const void* src, fmi_dtype dtype, int64_t n, DeviceBuffer& o
 
 extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* prefix, const void* A, const void* B, fmi_dtype dtype, int rank, float scale) {
   if (!m || !adapter || !prefix || !A || !B) return fail(FMI_ERR_INVALID, "lora_add: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "lora_add: LoRA-patched ControlNets are out of scope");
   if (m->fp8) return fail(FMI_ERR_STATE, "lora_add: the model was quantised to 8 bits; adapters go in before fmi_flux_quantize_fp8 / fmi_flux_quantize_int8");
   if (!*adapter) return fail(FMI_ERR_INVALID, "lora_add: empty adapter name");
   if (rank < 1) return fail(FMI_ERR_INVALID, "lora_add: rank must be at least 1");
@@ -2179,6 +2356,7 @@ extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* p
 
 extern "C" int fmi_flux_lora_set_weight(fmi_flux* m, const char* adapter, float weight) {
   if (!m || !adapter) return fail(FMI_ERR_INVALID, "lora_set_weight: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "lora_set_weight: LoRA-patched ControlNets are out of scope");
   if (m->fp8) return fail(FMI_ERR_STATE, "lora_set_weight: the model was quantised to 8 bits (the codes were taken from the merged weights)");
   if (!std::isfinite(weight)) return fail(FMI_ERR_INVALID, "lora_set_weight: weight must be finite");
   auto it = m->loras.find(adapter);
@@ -2195,6 +2373,7 @@ extern "C" int fmi_flux_lora_set_weight(fmi_flux* m, const char* adapter, float 
 
 extern "C" int fmi_flux_lora_remove(fmi_flux* m, const char* adapter) {
   if (!m) return fail(FMI_ERR_INVALID, "lora_remove: null handle");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "lora_remove: LoRA-patched ControlNets are out of scope");
   if (m->fp8) return fail(FMI_ERR_STATE, "lora_remove: the model was quantised to 8 bits (the codes were taken from the merged weights)");
   if (adapter && !m->loras.count(adapter)) return fail(FMI_ERR_INVALID, std::string("lora_remove: unknown adapter '") + adapter + "'");
   if (m->loras.empty()) return FMI_OK;
@@ -2264,4 +2443,33 @@ extern "C" int fmi_flux_get_tensor(fmi_flux* m, const char* name, void* out, fmi
   if (rc == FMI_OK && e == hipSuccess) e = hipMemcpy(out, tmp.ptr, (size_t)d.numel * 4, hipMemcpyDefault);
   if (rc == FMI_OK && e != hipSuccess) rc = fail(FMI_ERR_HIP, std::string("flux_get_tensor: ") + hipGetErrorString(e));
   return rc;
+}
+
+// ---- ControlNet test seams
+// The ControlNet alone: one evaluation on `in` (img, timesteps and every other field as for fmi_flux_forward) and cond (B,S,in_channels); the samples stay in the
+// handle, for fmi_flux_controlnet_sample to widen.
+extern "C" int fmi_flux_controlnet_eval(fmi_flux* net, const fmi_flux_inputs* in, const void* cond, fmi_dtype cond_dtype, void* stream) {
+  if (!net || !net->is_cn) return fail(FMI_ERR_INVALID, "flux_controlnet_eval: not a ControlNet handle");
+  FMI_TRY(check_inputs(net, in));
+  if (!in->img || !in->timesteps || !cond) return fail(FMI_ERR_INVALID, "flux_controlnet_eval: null img/timesteps/cond");
+  if (cond_dtype != FMI_F32 && cond_dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "flux_controlnet_eval: cond_dtype must be F32 or BF16");
+  if (net->cfg.guidance_embeds && !in->guidance) return fail(FMI_ERR_INVALID, "flux: a guidance_embeds ControlNet needs a guidance vector");
+  hipStream_t s = (hipStream_t)stream;
+  const fmi_flux_controlnet cn{net, cond, cond_dtype, 1.0f, nullptr};
+  EvalPlan p{fmi_flux_denoise_options{}, 0, in->B, &cn};
+  FMI_TRY(cn_prepare(net, in, p, s));
+  FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, net->ws.img_f32, (int64_t)in->B * in->S * net->cfg.in_channels, s));
+  return forward_core(net, in, cn_plan(p), net->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+}
+// Sample `index` of the double (single == 0) or single blocks of the last evaluation, widened exactly: out_f32 (B,S,D) device.  Synchronises the device.
+extern "C" int fmi_flux_controlnet_sample(fmi_flux* net, int single, int index, float* out_f32) {
+  if (!net || !net->is_cn || !out_f32) return fail(FMI_ERR_INVALID, "flux_controlnet_sample: not a ControlNet handle, or a null output");
+  const int n = (int)(single ? net->cn_sgl.size() : net->cn_dbl.size());
+  if (index < 0 || index >= n) return fail(FMI_ERR_INVALID, "flux_controlnet_sample: index outside the net's blocks");
+  if (!net->cn_samples || !net->cn_elems) return fail(FMI_ERR_STATE, "flux_controlnet_sample: the ControlNet has not been evaluated yet");
+  FMI_TRY(use_device(net));
+  FMI_HIP_TRY(hipDeviceSynchronize());
+  FMI_TRY(launch_cast_to_f32(net->cn_samples.as<bf16_t>() + ((single ? net->cn_dbl.size() : 0) + index) * net->cn_elems, FMI_BF16, out_f32, (int64_t)net->cn_elems, nullptr));
+  FMI_HIP_TRY(hipDeviceSynchronize());
+  return FMI_OK;
 }

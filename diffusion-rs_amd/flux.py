@@ -162,6 +162,61 @@ def check_control_args(cond_channels: int, img_shape, control_shape=None, has_co
         raise ValueError("control= is not supported under sequence parallelism")
 
 
+def controlnet_index_map(n_main: int, n_net: int) -> List[int]:
+    """Which of a ControlNet's n_net samples each of the main model's n_main blocks takes: i // ceil(n_main / n_net), diffusers' interval_control (DESIGN.md 4.15).
+    Empty for n_net == 0 (a net without single blocks injects nothing into the single blocks)."""
+    if n_net <= 0:
+        return []
+    k = -(-n_main // n_net)
+    return [i // k for i in range(n_main)]
+
+
+def controlnet_step_scales(n_steps: int, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0) -> List[float]:
+    """diffusers' controlnet_keep over the n_steps actually run: keep_i = 0 if i / n < control_guidance_start or (i + 1) / n > control_guidance_end, else 1."""
+    return [0.0 if (i / n_steps < control_guidance_start or (i + 1) / n_steps > control_guidance_end) else 1.0 for i in range(n_steps)]
+
+
+def check_controlnet_args(cfg: dict, net_cfg=None, img_shape=None, cond_shape=None, scale=1.0, step_scales=None, n_steps=None, has_context: bool = False,
+                          cond_channels: int = 0, cache_args: bool = False, sequence_parallel: bool = False):
+    """The ControlNet of FluxModel.forward / denoise (fmi_flux_forward_controlnet / fmi_flux_denoise_controlnet), checked without the library; cfg is
+    the main model's config, net_cfg the ControlNet's (None: no ControlNet).  Returns step_scales as a float32 array of n_steps entries, or None.
+    ValueError: controlnet_cond= without controlnet= or the reverse; a net whose width-defining fields differ from the main model's; a cond that is not
+    (B,S,in_channels) for img (B,S,C); a scale or step scale that is not finite; step_scales not n_steps entries; a ControlNet with context=, on a channel-
+    conditioned model, with the step cache's arguments or under sequence parallelism.  Several ControlNets, union modes and the XLabs hint block are out of scope."""
+    if net_cfg is None:
+        if cond_shape is not None:
+            raise ValueError("controlnet_cond= needs controlnet=")
+        if step_scales is not None:
+            raise ValueError("controlnet_step_scales= needs controlnet=")
+        return None
+    if cond_shape is None:
+        raise ValueError("controlnet= needs controlnet_cond=, the packed latents of the control image (B,S,in_channels)")
+    for k in ("num_attention_heads", "joint_attention_dim", "pooled_projection_dim", "axes_dim", "theta", "in_channels"):
+        a, b = cfg[k], net_cfg[k]
+        if (list(a) != list(b)) if k == "axes_dim" else (a != b):
+            raise ValueError(f"the ControlNet's {k} is {b!r}, the main model's {a!r}")
+    if tuple(cond_shape) != (int(img_shape[0]), int(img_shape[1]), int(net_cfg["in_channels"])):
+        raise ValueError(f"controlnet_cond is {tuple(cond_shape)}, expected {(int(img_shape[0]), int(img_shape[1]), int(net_cfg['in_channels']))} for img {tuple(img_shape)}")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"controlnet_scale must be finite, got {scale!r}")
+    if has_context:
+        raise ValueError("a ControlNet is not combined with context= (a reference image)")
+    if cond_channels:
+        raise ValueError("a ControlNet is not combined with a channel-conditioned model (FLUX.1 Fill / Canny / Depth)")
+    if cache_args:
+        raise ValueError("a ControlNet is not combined with the step cache (cache_threshold= / cache_force=)")
+    if sequence_parallel:
+        raise ValueError("a ControlNet is not supported under sequence parallelism")
+    if step_scales is None:
+        return None
+    ss = np.asarray(step_scales, np.float32)
+    if ss.ndim != 1 or (n_steps is not None and ss.shape[0] != n_steps):
+        raise ValueError(f"controlnet_step_scales must have one entry per step ({n_steps}), got shape {ss.shape}")
+    if not np.isfinite(ss).all():
+        raise ValueError("controlnet_step_scales entries must be finite")
+    return np.ascontiguousarray(ss)
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
@@ -423,15 +478,39 @@ class FluxModel:
         keep = control.contiguous()
         return L.FluxControl(_ptr(keep), _TORCH_DT[control.dtype]), keep
 
-    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None, control=None):
+    def _controlnet(self, img, controlnet, controlnet_cond, scale, step_scales, n_steps, has_ctx, cache_args):
+        """fmi_flux_controlnet for controlnet= / controlnet_cond=, with what it points into; (None, None) without a ControlNet."""
+        ss = check_controlnet_args(self.cfg, None if controlnet is None else controlnet.cfg, tuple(img.shape), None if controlnet_cond is None else tuple(controlnet_cond.shape),
+                                   scale, step_scales, n_steps, has_ctx, self.cond_channels, cache_args, getattr(self, "_sp_world", 1) > 1)
+        if controlnet is None:
+            return None, None
+        if not isinstance(controlnet, FluxControlNetModel):
+            raise TypeError("controlnet= must be a FluxControlNetModel")
+        if controlnet_cond.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("controlnet_cond must be float32 or bfloat16")
+        if controlnet_cond.device != img.device:
+            raise ValueError(f"controlnet_cond is on {controlnet_cond.device}, img on {img.device}")
+        keep = [controlnet_cond.contiguous(), ss]
+        return L.FluxControlNet(controlnet.h, _ptr(keep[0]), _TORCH_DT[controlnet_cond.dtype], float(scale),
+                                ss.ctypes.data_as(C.POINTER(C.c_float)) if ss is not None else None), keep
+
+    def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None, control=None, controlnet=None, controlnet_cond=None,
+                controlnet_scale=1.0):
         """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.
         context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's.
         control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_forward_control): the
-        evaluation is Flux::forward on cat([img, control], 2) and the velocity stays img's width.  Required on such a model, refused on any other."""
+        evaluation is Flux::forward on cat([img, control], 2) and the velocity stays img's width.  Required on such a model, refused on any other.
+        controlnet= / controlnet_cond= / controlnet_scale=: a FluxControlNetModel evaluated on the same inputs and controlnet_cond (B,S,in_channels) f32 | bf16, the
+        packed latents of the control image; its per-block samples, times the scale, are added to this model's stream after every block
+        (fmi_flux_forward_controlnet).  Not with context=, control= or sequence parallelism."""
+        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, None, None, context is not None or context_ids is not None, False)
         check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
                            False, getattr(self, "_sp_world", 1) > 1)
         inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
         pred = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        if cn is not None:
+            L.check(self.lib.fmi_flux_forward_controlnet(self.h, C.byref(inp), C.byref(cn), _ptr(pred), _stream()), self.lib)
+            return pred
         if control is not None:
             ctl, keep_ctl = self._control(img, control)
             L.check(self.lib.fmi_flux_forward_control(self.h, C.byref(inp), C.byref(ctl), _ptr(pred), _stream()), self.lib)
@@ -444,7 +523,8 @@ class FluxModel:
         return pred
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
-                cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None):
+                cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None,
+                controlnet=None, controlnet_cond=None, controlnet_scale=1.0, controlnet_step_scales=None):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_with call: the keywords fill its options.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
@@ -461,8 +541,14 @@ class FluxModel:
         sequence parallelism; works with x0 / noise / mask and with context=.
         control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_denoise_control), the same at
         every step and, under true CFG, for the prompt and the negative; the state stays (B,S,C).  Required on such a model, refused on any other; works with
-        x0 / noise / mask and the negative, not with context=, the step cache or sequence parallelism."""
+        x0 / noise / mask and the negative, not with context=, the step cache or sequence parallelism.
+        controlnet= / controlnet_cond= / controlnet_scale= / controlnet_step_scales=: a FluxControlNetModel (fmi_flux_denoise_controlnet).  Step i
+        evaluates it on the step's state and controlnet_cond (B,S,in_channels) f32 | bf16 and adds its samples at controlnet_scale * controlnet_step_scales[i] (one
+        entry per step; None: 1 everywhere); a step whose scale is 0 is the plain step.  Works with x0 / noise / mask and with the negative (which the ControlNet
+        then sees as well); not with context=, control=, the step cache or sequence parallelism."""
         n_steps = len(timesteps) - 1
+        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, controlnet_step_scales, n_steps, context is not None or context_ids is not None,
+                                       cache_threshold is not None or cache_force is not None)
         check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
                            cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
         cfg_scale = check_true_cfg_args(tuple(txt.shape), tuple(y.shape), None if negative_txt is None else tuple(negative_txt.shape),
@@ -494,7 +580,10 @@ class FluxModel:
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             opts.cache = C.pointer(L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
                                                    decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float))))
-        L.check(self.lib.fmi_flux_denoise_with(self.h, C.byref(inp), C.byref(opts), _ptr(img), ts, n_steps, _stream()), self.lib)
+        if cn is not None:
+            L.check(self.lib.fmi_flux_denoise_controlnet(self.h, C.byref(inp), C.byref(opts), C.byref(cn), _ptr(img), ts, n_steps, _stream()), self.lib)
+        else:
+            L.check(self.lib.fmi_flux_denoise_with(self.h, C.byref(inp), C.byref(opts), _ptr(img), ts, n_steps, _stream()), self.lib)
         return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
 
     def step_cache_bytes(self) -> int:
@@ -509,6 +598,49 @@ class FluxModel:
         out = (C.c_float * n)()
         L.check(self.lib.fmi_flux_phase_ms(self.h, out), self.lib)
         return {self.lib.fmi_flux_phase_name(i).decode(): out[i] for i in range(n)}
+
+
+class FluxControlNetModel(FluxModel):
+    """A FLUX ControlNet (diffusers' FluxControlNetModel; fmi_flux_create_controlnet): cfg as FluxModel's, with the net's own num_layers (>= 1) and
+    num_single_layers (>= 0).  Handed to FluxModel.forward / denoise as controlnet=; eval() runs it alone.  bf16 only: the 8-bit modes, LoRA, the quantised
+    setters and sequence parallelism raise FmiError (FMI_ERR_UNSUPPORTED), as do forward() and denoise() on the net itself."""
+
+    def __init__(self, cfg: dict, device: int = 0):
+        self.lib = L.load()
+        self.cfg = dict(cfg)
+        self.state_channels, self.cond_channels = int(cfg["in_channels"]), 0
+        L.check(self.lib.fmi_init(device), self.lib)
+        c = L.FluxConfig(cfg["in_channels"], cfg["pooled_projection_dim"], cfg["joint_attention_dim"], cfg["num_attention_heads"],
+                         cfg["num_layers"], cfg["num_single_layers"], int(cfg["guidance_embeds"]), (C.c_int * 3)(*cfg["axes_dim"]), cfg["theta"])
+        h = C.c_void_p()
+        L.check(self.lib.fmi_flux_create_controlnet(C.byref(c), L.MODEL_BF16, C.byref(h)), self.lib)
+        self.h = h
+        self.hidden = cfg["num_attention_heads"] * 128
+        self.device = torch.device("cuda", device)
+
+    def _shapes(self):
+        if getattr(self, "_shape_cache", None) is None:
+            from . import synth
+            self._shape_cache = synth.controlnet_tensor_shapes(self.cfg)
+        return self._shape_cache
+
+    def eval(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, cond=None):
+        """The ControlNet alone (fmi_flux_controlnet_eval): returns (double_samples, single_samples), lists of (B,S,D) f32 tensors — the stored bf16 samples, widened."""
+        if cond is None or cond.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("eval: cond (B,S,in_channels) float32 | bfloat16 is required")
+        if tuple(cond.shape) != (int(img.shape[0]), int(img.shape[1]), int(self.cfg["in_channels"])):
+            raise ValueError(f"cond is {tuple(cond.shape)}, img is {tuple(img.shape)}")
+        inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
+        cond = cond.contiguous()
+        L.check(self.lib.fmi_flux_controlnet_eval(self.h, C.byref(inp), _ptr(cond), _TORCH_DT[cond.dtype], _stream()), self.lib)
+        out = []
+        for single, n in ((0, self.cfg["num_layers"]), (1, self.cfg["num_single_layers"])):
+            out.append([])
+            for i in range(n):
+                t = torch.empty((int(img.shape[0]), int(img.shape[1]), self.hidden), dtype=torch.float32, device=img.device)
+                L.check(self.lib.fmi_flux_controlnet_sample(self.h, single, i, _ptr(t)), self.lib)
+                out[-1].append(t)
+        return out[0], out[1]
 
 
 class AutoEncoderKl:
@@ -660,6 +792,22 @@ def cast_cols_bf16(src, dst, col0, rows=None):
         raise ValueError(f"cast_cols_bf16: {rows} rows do not fit dst {tuple(dst.shape)}")
     L.check(L.load().fmi_cast_cols_bf16(_ptr(src), _TORCH_DT[src.dtype], rows, int(src.shape[0]), int(src.shape[1]), _ptr(dst), int(dst.shape[1]), int(col0), _stream()))
     return dst
+
+
+def add_scaled_rows_bf16(x, src, scale, rows=None, row0=0):
+    """fmi_add_scaled_rows_bf16, the ControlNet injection kernel on its own, in place on x and returning it: x[b, row0 + r, :] += scale * src[b, r, :]
+    in f32, one unfused multiply and add per element, for r < rows (default: all of src's); x (B,Lx,D) float32, src (B,rows,D) bfloat16, both as they lie in memory
+    (contiguous; x may be a view that starts anywhere).  Rows outside [row0, row0 + rows) are not touched."""
+    if x.dim() != 3 or src.dim() != 3 or x.dtype != torch.float32 or src.dtype != torch.bfloat16 or x.device != src.device:
+        raise TypeError("add_scaled_rows_bf16: x (B,Lx,D) float32 and src (B,rows,D) bfloat16 on one device are required")
+    if not (x.is_contiguous() and src.is_contiguous()):
+        raise TypeError("add_scaled_rows_bf16: contiguous tensors are required")
+    Bn, Lx, D = (int(v) for v in x.shape)
+    rows = int(src.shape[1]) if rows is None else int(rows)
+    if int(src.shape[0]) != Bn or int(src.shape[2]) != D or int(src.shape[1]) != rows or row0 < 0 or row0 + rows > Lx:
+        raise ValueError(f"add_scaled_rows_bf16: src {tuple(src.shape)} does not fit rows [{row0}, {row0 + rows}) of x {tuple(x.shape)}")
+    L.check(L.load().fmi_add_scaled_rows_bf16(C.c_void_p(x.data_ptr() + 4 * row0 * D), Lx * D, _ptr(src), Bn, rows, D, float(scale), _stream()))
+    return x
 
 
 def mask_image(image, mask):

@@ -221,6 +221,52 @@ def load_flux(flux, tensors: Iterator[Tuple[str, torch.Tensor]]) -> dict:
     return stats
 
 
+def controlnet_config(config: dict) -> dict:
+    """The FluxControlNetModel configuration of a diffusers config.json as this package's cfg dict, or ValueError naming the field: `_class_name`
+    is not FluxControlNetModel; `num_mode` not null (union ControlNets); `conditioning_embedding_channels` not null (XLabs' pixel-space hint block);
+    `attention_head_dim` != 128.  Out of scope, all three."""
+    if config.get("_class_name") != "FluxControlNetModel":
+        raise ValueError(f"_class_name is {config.get('_class_name')!r}: only FluxControlNetModel is a ControlNet this package loads")
+    if config.get("num_mode") is not None:
+        raise ValueError(f"num_mode = {config['num_mode']!r}: union ControlNets are not supported")
+    if config.get("conditioning_embedding_channels") is not None:
+        raise ValueError(f"conditioning_embedding_channels = {config['conditioning_embedding_channels']!r}: the pixel-space hint block (XLabs) is not supported")
+    if int(config.get("attention_head_dim", 128)) != 128:
+        raise ValueError(f"attention_head_dim = {config['attention_head_dim']!r}: only 128 is supported")
+    axes = [int(v) for v in config.get("axes_dims_rope", [16, 56, 56])]
+    return dict(in_channels=int(config.get("in_channels", 64)), pooled_projection_dim=int(config.get("pooled_projection_dim", 768)),
+                joint_attention_dim=int(config.get("joint_attention_dim", 4096)), num_attention_heads=int(config.get("num_attention_heads", 24)),
+                num_layers=int(config.get("num_layers", 19)), num_single_layers=int(config.get("num_single_layers", 38)),
+                guidance_embeds=bool(config.get("guidance_embeds", False)), axes_dim=axes, theta=10000)
+
+
+def load_controlnet(path: str):
+    """A diffusers ControlNet directory — config.json with `_class_name` FluxControlNetModel next to diffusion_pytorch_model*.safetensors — as
+    (cfg, {name: tensor}): what Pipeline.load_controlnet and FluxControlNetModel.load_state_dict take.  No device is touched.  ValueError as controlnet_config's,
+    for a tensor the configuration does not list, and for one it lists that the files lack."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"{path}: not a directory (a ControlNet is a diffusers directory: config.json + diffusion_pytorch_model*.safetensors)")
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = controlnet_config(json.load(f))
+    want = synth.controlnet_tensor_shapes(cfg)
+    sd = {}
+    for fn in sorted(os.listdir(path)):
+        if not (fn.startswith("diffusion_pytorch_model") and fn.endswith(".safetensors")):
+            continue
+        with open(os.path.join(path, fn), "rb") as f:
+            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        for name, t in _safetensors_from_buffer(memoryview(mm)):
+            if name not in want:
+                raise ValueError(f"{fn}: tensor {name} is not part of a FluxControlNetModel of this configuration (quantised ControlNets are not supported)")
+            if tuple(t.shape) != tuple(want[name]):
+                raise ValueError(f"{fn}: {name} is {tuple(t.shape)}, the configuration says {tuple(want[name])}")
+            sd[name] = t
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise ValueError(f"{path}: {len(missing)} ControlNet tensors missing, e.g. {missing[:3]}")
+    return cfg, sd
+
+
 def load_vae(vae, tensors: Iterator[Tuple[str, torch.Tensor]]) -> int:
     want = synth.vae_tensor_shapes(vae.cfg, encoder=True)  # encoder tensors are loaded when the checkpoint has them
     n = 0

@@ -214,6 +214,45 @@ class _Control:
     mask: Optional[torch.Tensor] = None  # (1,H,W) f32, on the device; kind "fill" only
 
 
+@dataclass(frozen=True)
+class _ControlNetInput:
+    """The ControlNet conditioning of a request: ONE per request, shared by its prompts like the negative and the control — not a per-sample
+    input, so no field of _Samples; every chunk and every rank of the request receives this same object and expands it to its rows."""
+    image: torch.Tensor  # (1,3,H,W) f32 in [-1,1], on the device
+    scale: float         # controlnet_conditioning_scale
+    start: float         # control_guidance_start
+    end: float           # control_guidance_end
+
+
+def check_controlnet_request(loaded: bool, height: int, width: int, image_shape=None, image_is_u8: bool = False, scale: float = 1.0, start: float = 0.0,
+                             end: float = 1.0, reference: bool = False, cache_threshold: bool = False, cond_channels: int = 0, sequence_parallel: bool = False):
+    """The ControlNet arguments of a request, checked without a device.  ValueError: controlnet_image= without a loaded ControlNet (Pipeline.load_controlnet); a
+    height or width that is no multiple of 16; an image that is not u8 (H,W,3) or float (B,3,H,W) with B == 1 at the request's size (nothing is resized); a scale
+    that is not finite; control_guidance_start / _end outside 0 <= start <= end <= 1; reference=, cache_threshold=, a Fill / Canny / Depth checkpoint or sequence
+    parallelism next to it.  A request without controlnet_image= is not conditioned, whatever is loaded."""
+    if image_shape is None:
+        return
+    if not loaded:
+        raise ValueError("controlnet_image= needs a loaded ControlNet: Pipeline.load_controlnet(path) first")
+    if height % 16 or width % 16:
+        raise ValueError(f"controlnet_image= needs height and width that are multiples of 16, got {height} x {width}")
+    want = (height, width, 3) if image_is_u8 else (1, 3, height, width)
+    if tuple(image_shape) != want:
+        raise ValueError(f"controlnet_image must be uint8 ({height},{width},3) or float (1,3,{height},{width}) as params say, got {tuple(image_shape)}")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"controlnet_conditioning_scale must be finite, got {scale!r}")
+    if not (0.0 <= float(start) <= float(end) <= 1.0):
+        raise ValueError(f"control_guidance_start / control_guidance_end must satisfy 0 <= start <= end <= 1, got {start!r} / {end!r}")
+    if reference:
+        raise ValueError("a ControlNet is not combined with reference= (a context)")
+    if cache_threshold:
+        raise ValueError("a ControlNet is not combined with the step cache (cache_threshold=)")
+    if cond_channels:
+        raise ValueError("a ControlNet is not combined with a channel-conditioned checkpoint (FLUX.1 Fill / Canny / Depth)")
+    if sequence_parallel:
+        raise ValueError("a ControlNet is not wired through sequence parallelism: disable_sequence_parallel() first")
+
+
 def control_kind(cond_channels: int) -> Optional[str]:
     """What a model's conditioning channels hold: 0 -> None, 64 -> "control" (the control image's latents), 320 -> "fill" (masked-image latents + 256 mask
     channels); ValueError for any other width (no pipeline builds such a condition)."""
@@ -471,7 +510,8 @@ class Pipeline:
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
                         negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
-                        control_image=None, control_mask=None):
+                        control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
+                        control_guidance_start: float = 0.0, control_guidance_end: float = 1.0):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -510,7 +550,16 @@ class Pipeline:
         `control_mask=` ((H,W) bool / float, 1 = fill; binarised at 0.5) says where: the latents of image * (1 - mask) and the 256 unshuffled mask channels are the
         320 more.  The loop starts from noise and runs the whole schedule; image= / strength= / mask= and the negative keep their meaning and combine with it.
         Required on such a model and refused on any other; raises with reference=, cache_threshold= and under sequence parallelism.  No guidance scale is
-        recommended: there are no real weights here to judge one."""
+        recommended: there are no real weights here to judge one.
+
+        ControlNet conditioning (`controlnet_image=` with a ControlNet loaded by load_controlnet; diffusers' FluxControlNetPipeline): ONE control
+        image per request, shared by its prompts — u8 (H,W,3) or f32 (1,3,H,W) in [-1,1] at params.height x width (multiples of 16; nothing is resized), encoded
+        like image= (the posterior MEAN).  Step i of the n steps actually run (after a strength= cut) evaluates the ControlNet and adds its residuals to the
+        transformer's stream at controlnet_conditioning_scale * keep_i, keep_i = 0 if i / n < control_guidance_start or (i + 1) / n > control_guidance_end else
+        1; a step with scale 0 is the plain step.  Combines with the negative (the ControlNet then sees it as well) and with image= / strength= / mask=;
+        raises with reference=, cache_threshold=, on a Fill / Canny / Depth checkpoint, under sequence parallelism and without a loaded ControlNet.  No
+        conditioning scale is recommended: there are no real weights here to judge one."""
+        cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params, reference, cache_threshold)
         if cache_threshold is not None:
             F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
         ctl = self._control(control_image, control_mask, params, reference, cache_threshold)
@@ -522,8 +571,9 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        # (the negative is a keyword of true-CFG requests only, the control of controlled ones: any other request makes exactly the call it always made)
-        extra = dict(**({} if neg is None else dict(negative=neg)), **({} if ctl is None else dict(control=ctl)))
+        # (the negative is a keyword of true-CFG requests only, the control of controlled ones: any other request makes exactly the call it always made; a request has
+        # ONE control object, the channel conditioning's or the ControlNet's — the two are never combined, check_controlnet_request)
+        extra = dict(**({} if neg is None else dict(negative=neg)), **({} if ctl is None and cn is None else dict(control=ctl if cn is None else cn)))
         outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **extra)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
@@ -553,6 +603,48 @@ class Pipeline:
         else:
             img = img.to(device=self.device, dtype=torch.float32).contiguous()
         return _Control(kind, img, None if m is None else m.unsqueeze(0).to(device=self.device, dtype=torch.float32).contiguous())
+
+    def _controlnet_input(self, image, scale, start, end, params, reference, cache_threshold) -> Optional[_ControlNetInput]:
+        """The ControlNet conditioning of a request, checked once and brought to its device form: None without controlnet_image=, else the object its chunks share."""
+        if image is None:
+            return None
+        img = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
+        if not isinstance(img, torch.Tensor) or not (img.dtype == torch.uint8 or img.is_floating_point()):
+            raise ValueError("controlnet_image must be a uint8 or float numpy array or torch tensor")
+        check_controlnet_request(getattr(self, "controlnet", None) is not None, params.height, params.width, tuple(img.shape), img.dtype == torch.uint8, scale, start, end,
+                                 reference is not None, cache_threshold is not None, getattr(getattr(self, "flux", None), "cond_channels", 0),
+                                 getattr(self, "_sp", None) is not None)
+        if img.dtype == torch.uint8:
+            img = F.preprocess_u8(img.unsqueeze(0).to(self.device), interleaved=True)
+        else:
+            img = img.to(device=self.device, dtype=torch.float32).contiguous()
+        return _ControlNetInput(img, float(scale), float(start), float(end))
+
+    def load_controlnet(self, source):
+        """Load ONE ControlNet next to the transformer: a diffusers directory (loader.load_controlnet: config.json with _class_name
+        FluxControlNetModel + diffusion_pytorch_model*.safetensors) or a (cfg, state_dict) pair.  It replaces a loaded one; requests use it only when they pass
+        controlnet_image=.  ValueError for a ControlNet whose width-defining fields differ from the transformer's; union modes, the XLabs hint block and several
+        ControlNets at once are out of scope."""
+        from . import loader
+        cfg, sd = loader.load_controlnet(os.fspath(source)) if isinstance(source, (str, os.PathLike)) else source
+        for k in ("num_attention_heads", "joint_attention_dim", "pooled_projection_dim", "axes_dim", "theta"):
+            if list(np.atleast_1d(cfg[k])) != list(np.atleast_1d(self.flux.cfg[k])):
+                raise ValueError(f"the ControlNet's {k} is {cfg[k]!r}, the transformer's {self.flux.cfg[k]!r}")
+        if int(cfg["in_channels"]) != self.flux.state_channels:
+            raise ValueError(f"the ControlNet's in_channels is {cfg['in_channels']}, the transformer's state has {self.flux.state_channels}")
+        with self._lock:
+            net = F.FluxControlNetModel(cfg, self.device.index or 0)
+            net.load_state_dict(sd)
+            old, self.controlnet = getattr(self, "controlnet", None), net
+            if old is not None:
+                old.close()
+        return net
+
+    def unload_controlnet(self):
+        with self._lock:
+            net, self.controlnet = getattr(self, "controlnet", None), None
+            if net is not None:
+                net.close()
 
     def _control_condition(self, control: _Control, B: int):
         """The conditioning channels (B,S,64 | 320) f32 of a chunk of B samples: built once at one row — VAE encode (the posterior mean), pack, and for Fill the
@@ -648,10 +740,12 @@ class Pipeline:
         return t5_emb, clip_emb, neg
 
     def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
-                        control: Optional[_Control] = None):
+                        control=None):
         """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
-        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only.  control: the request's control
-         — passed by requests to a channel-conditioned model only."""
+        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only.  control: the request's control —
+        a _Control, passed by requests to a channel-conditioned model only, or a _ControlNetInput, passed by requests with
+        controlnet_image= only; a request never has both."""
+        controlnet, control = (control, None) if isinstance(control, _ControlNetInput) else (None, control)
         cfg = self.flux.cfg
         dev = self.device
         sp = getattr(self, "_sp", None)
@@ -686,6 +780,11 @@ class Pipeline:
                 context = dict(context=ctx, context_ids=F.latent_ids(B, s.reference.shape[2] // 16, s.reference.shape[3] // 16, id0=1.0, device=dev))
             if control is not None:  # the same conditioning channels at every step, for every sample and for both halves of a true-CFG batch
                 context = dict(control=self._control_condition(control, B))
+            cn_kw = {}
+            if controlnet is not None:  # the control image's packed latents (the posterior mean), one row expanded; the scales over the steps actually run
+                cond, _ = F.encode_latents(self.vae.encode(controlnet.image), self.vae.scale_factor(), self.vae.shift_factor())
+                cn_kw = dict(controlnet=self.controlnet, controlnet_cond=cond.expand(B, -1, -1).contiguous(), controlnet_scale=controlnet.scale,
+                             controlnet_step_scales=F.controlnet_step_scales(len(timesteps) - 1, controlnet.start, controlnet.end))
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
@@ -694,7 +793,7 @@ class Pipeline:
             else:
                 cache = {} if cache_threshold is None else dict(cache_threshold=cache_threshold, return_cache_stats=True)
                 true_cfg = {} if neg is None else dict(negative_txt=neg[0], negative_y=neg[1], true_cfg_scale=negative.scale)
-                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, **cache, **true_cfg)
+                img = self.flux.denoise(img, img_ids, t5_emb, txt_ids, clip_emb, guidance, timesteps, **inpaint, **context, **cache, **true_cfg, **cn_kw)
                 if cache:
                     img, st = img
                     stats.append(st)
@@ -782,7 +881,8 @@ class Pipeline:
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
                 reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
-                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, **kw):
+                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
+                controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
@@ -790,7 +890,9 @@ class Pipeline:
         returns (images, final packed latents).  cache_threshold=: the first-block step cache, see generate_tensor (None: off); each rank of a sharded batch
         decides for its own prompts and keeps its own `last_cache_stats`.  negative_prompt= / negative_embeddings= / negative_token_ids= / true_cfg_scale=: true
         classifier-free guidance, see generate_tensor — one negative per request, handed to every rank of a sharded batch unchanged.  control_image= /
-        control_mask=: the control of a channel-conditioned model (FLUX.1 Fill / Canny / Depth), see generate_tensor — one per request, likewise."""
+        control_mask=: the control of a channel-conditioned model (FLUX.1 Fill / Canny / Depth), see generate_tensor — one per request, likewise.
+        controlnet_image= / controlnet_conditioning_scale= / control_guidance_start= / control_guidance_end=: the ControlNet of load_controlnet, see generate_tensor —
+        one control image per request, likewise (every rank loads the same ControlNet)."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -799,6 +901,9 @@ class Pipeline:
             shared.update(negative_prompt=negative_prompt, negative_embeddings=negative_embeddings, negative_token_ids=negative_token_ids, true_cfg_scale=true_cfg_scale)
         if control_image is not None or control_mask is not None:  # (likewise)
             shared.update(control_image=control_image, control_mask=control_mask)
+        if controlnet_image is not None:  # (likewise)
+            shared.update(controlnet_image=controlnet_image, controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
+                          control_guidance_end=control_guidance_end)
         per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if world > 1 and getattr(self, "_sp", None) is None:

@@ -107,6 +107,56 @@ def fill_flux_random_device(model, seed=0, w_std=0.02, mod_std=0.01, bias_std=0.
     model.assert_complete()
 
 
+def controlnet_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
+    """A diffusers FluxControlNetModel of cfg["num_layers"] double and cfg["num_single_layers"] (>= 0) single blocks: FLUX's names without
+    norm_out / proj_out, then controlnet_x_embedder and one zero-initialised Linear(D, D) per block."""
+    D = cfg["num_attention_heads"] * sum(cfg["axes_dim"])
+    t = OrderedDict((k, v) for k, v in flux_tensor_shapes(cfg).items() if not (k.startswith("norm_out.") or k.startswith("proj_out.")))
+    for p, shape in [("controlnet_x_embedder", (D, cfg["in_channels"]))] + [(f"controlnet_blocks.{i}", (D, D)) for i in range(cfg["num_layers"])] + \
+            [(f"controlnet_single_blocks.{j}", (D, D)) for j in range(cfg["num_single_layers"])]:
+        t[p + ".weight"] = shape
+        t[p + ".bias"] = shape[:1]
+    return t
+
+
+def controlnet_state_dict_numpy(cfg, seed=0, w_std=0.02, mod_std=0.01, bias_std=0.02, norm_jitter=0.1, cn_std=0.05, cn_x_std=None, round_bf16=True):
+    """Synthetic ControlNet weights, drawn like flux_state_dict_numpy's from a generator of their own (the FLUX checkpoints' draws are untouched).  A trained
+    ControlNet's zero-linears start at zero; here the zero-linears' weights are N(0, cn_std^2) and controlnet_x_embedder's N(0, cn_x_std^2) (None: cn_std), so that the samples carry something and depend
+    on the control image."""
+    rng = np.random.default_rng([seed, 0xC0])
+    out = OrderedDict()
+    for name, shape in controlnet_tensor_shapes(cfg).items():
+        if name.endswith("norm_q.weight") or name.endswith("norm_k.weight") or name.endswith("norm_added_q.weight") or name.endswith("norm_added_k.weight"):
+            a = 1.0 + norm_jitter * rng.standard_normal(shape)
+        elif name.endswith(".bias"):
+            a = bias_std * rng.standard_normal(shape)
+        elif name.startswith("controlnet_"):
+            a = (cn_std if cn_x_std is None or not name.startswith("controlnet_x_embedder") else cn_x_std) * rng.standard_normal(shape)
+        else:
+            a = _std_for(name, w_std, mod_std) * rng.standard_normal(shape)
+        a = a.astype(np.float32)
+        out[name] = to_bf16_f32(a) if round_bf16 else a
+    return out
+
+
+def fill_controlnet_random_device(model, seed=0, w_std=0.02, mod_std=0.01, device="cuda"):
+    """Full-size random ControlNet weights generated on the GPU (measurements), as fill_flux_random_device does for the main model."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    for name, shape in controlnet_tensor_shapes(model.cfg).items():
+        if "norm_q.weight" in name or "norm_k.weight" in name or "norm_added" in name:
+            t = torch.ones(shape, dtype=torch.bfloat16, device=device)
+        elif name.endswith(".bias"):
+            t = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        else:
+            t = torch.randn(shape, generator=g, device=device, dtype=torch.bfloat16)
+            t.mul_(_std_for(name, w_std, mod_std))
+        model.set_tensor(name, t)
+        del t
+    model.assert_complete()
+
+
 def vae_tensor_shapes(cfg, encoder=False) -> "OrderedDict[str, tuple]":
     """Decoder tensors (vae.rs:371-433); with encoder=True also the encoder's (vae.rs:249-327) and quant_conv."""
     boc = list(cfg["block_out_channels"])

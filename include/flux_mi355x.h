@@ -459,6 +459,60 @@ typedef struct fmi_flux_control {
 } fmi_flux_control;
 int fmi_flux_forward_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream);
 
+/* FLUX ControlNets: residual conditioning (diffusers' FluxControlNetModel, FluxTransformer2DModel.forward(controlnet_block_samples=,
+ * controlnet_single_block_samples=) and FluxControlNetPipeline; the reference has no counterpart).  A ControlNet is a truncated FLUX transformer of nd >= 1 double
+ * and ns >= 0 single blocks at the main model's width D, with the same embedders, no norm_out / proj_out, and
+ *   controlnet_x_embedder         Linear(in_channels -> D) on cond, the packed VAE latents of the control image (B,S,in_channels), as fmi_encode_latents makes them
+ *   controlnet_blocks.{i}         Linear(D -> D), one per double block            controlnet_single_blocks.{j}   Linear(D -> D), one per single block
+ * Its evaluation on the main model's img, ids, txt, t, y, guidance (the guidance only if the net has guidance_embeds) is
+ *   x = x_embedder(img) + controlnet_x_embedder(cond);  txt = context_embedder(txt);  vec, pe as ever
+ *   for i < nd:  x, txt = transformer_blocks[i](x, txt, vec, pe);  d_i = controlnet_blocks[i](x)
+ *   xs = cat([txt, x], 1);  for j < ns:  xs = single_transformer_blocks[j](xs, vec, pe);  s_j = controlnet_single_blocks[j](xs[:, T:])
+ * and the main model (ND double, NS single blocks), with kd = ceil(ND / nd), ks = ceil(NS / ns), adds
+ *   after double block i:  x_img += c * d[i / kd]            after single block j:  xs[:, T:, :] += c * s[j / ks]      (nothing if ns == 0)
+ * Decisions of this library:
+ *   - the samples d_i, s_j are stored as bf16: the round-to-nearest-even of the GEMM's f32 accumulator plus bias;
+ *   - the scale is applied at the injection, in f32, as one __fmul_rn and one __fadd_rn per element, x = x + c * f32(sample), never contracted;
+ *   - a step (or a forward) whose c is 0 launches neither the ControlNet's evaluation nor any injection: it is the plain step, launch for launch;
+ *   - controlnet_x_embedder(cond) is computed once per call and kept in f32; each evaluation adds it to x_embedder(img) in f32;
+ *   - in the loop the ControlNet's modulation vectors of all steps and its txt_in are hoisted like the main model's; its RoPE table is built once per call;
+ *   - under true CFG the ControlNet runs on the same internal batch of 2B: the negative half sees the negative's txt / y, the same state and the same cond.
+ * fmi_flux_create_controlnet makes an fmi_flux of this kind: cfg->num_layers / num_single_layers are the net's (num_single_layers == 0 is allowed).  It takes
+ * FLUX's tensor names without norm_out.* / proj_out.*, plus controlnet_x_embedder.{weight,bias}, controlnet_blocks.{i}.{weight,bias} and
+ * controlnet_single_blocks.{j}.{weight,bias}, through fmi_flux_set_tensor / fmi_flux_get_tensor / fmi_flux_missing_*.  Its sample buffers are sized by its first
+ * evaluation and counted by fmi_flux_size_in_bytes; a call without a ControlNet allocates none.
+ * The net runs in bf16 only.  On a ControlNet handle FMI_ERR_UNSUPPORTED: fmi_flux_quantize_fp8 / _int8, fmi_flux_calibrate_int8, fmi_flux_set_fp8_attention(2),
+ * fmi_flux_lora_*, fmi_flux_set_linear_bnb4 / _int8, fmi_flux_set_sequence_parallel (world_size > 1), and every fmi_flux_forward* / fmi_flux_denoise* entry (and
+ * with them the step cache).  The main model may be in any mode: the injection touches only its f32 stream.
+ * Out of scope, refused where it would enter: several ControlNets at once, union modes (num_mode), the XLabs pixel-space hint block
+ * (conditioning_embedding_channels), controlnet_blocks_repeat, quantised or LoRA-patched ControlNets, a ControlNet with a context, the step cache, channel
+ * conditioning or sequence parallelism, resizing the control image, and fusing the injection into the blocks' last GEMM epilogue.
+ * With a fmi_flux_controlnet — FMI_ERR_INVALID: net NULL or not a ControlNet; cond NULL; a cond_dtype that is not F32 / BF16; a scale or a step_scales entry that
+ * is not finite; a net whose width, head count, joint_attention_dim, pooled_projection_dim, axes_dim, theta or in_channels differ from the main model's, or that
+ * lives on another device; a guidance_embeds net without in->guidance.  FMI_ERR_UNSUPPORTED: see the table at fmi_flux_denoise_with.  FMI_ERR_STATE: a net
+ * with missing tensors. */
+int fmi_flux_create_controlnet(const fmi_flux_config* cfg, fmi_model_dtype dtype, fmi_flux** out);
+int fmi_flux_is_controlnet(const fmi_flux*);
+typedef struct fmi_flux_controlnet {
+  fmi_flux* net;                            /* fmi_flux_create_controlnet's handle, every tensor set */
+  const void* cond; fmi_dtype cond_dtype;   /* (B,S,in_channels) F32|BF16 */
+  float scale;                              /* finite; the conditioning scale c */
+  const float* step_scales;                 /* NULL, or n_steps host floats multiplied onto scale (c_i = scale * step_scales[i], in f32); a single forward ignores it */
+} fmi_flux_controlnet;
+/* One evaluation of the main model with the ControlNet's samples injected; pred_out (B,S,in_channels) f32.  cn NULL: fmi_flux_forward. */
+int fmi_flux_forward_controlnet(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_controlnet* cn, float* pred_out, void* stream);
+/* Test seams.  fmi_flux_controlnet_eval runs the ControlNet alone (`in` as for fmi_flux_forward, cond (B,S,in_channels)) and leaves its samples in the handle;
+ * fmi_flux_controlnet_sample widens sample `index` of the double (single == 0) or single blocks of the last evaluation into out_f32 (B,S,D), a device buffer
+ * (it synchronises the device). */
+int fmi_flux_controlnet_eval(fmi_flux* net, const fmi_flux_inputs* in, const void* cond, fmi_dtype cond_dtype, void* stream);
+int fmi_flux_controlnet_sample(fmi_flux* net, int single, int index, float* out_f32);
+/* The injection kernel on its own (op-level glue; device pointers, no allocation): for b < B, r < rows, d < D
+ *   x[b * x_batch_stride + r * D + d] = x[...] + scale * f32(src[(b * rows + r) * D + d])          (__fadd_rn(x, __fmul_rn(scale, src)): numpy reproduces the bits)
+ * x_batch_stride >= rows * D, in floats: (B*S, D) contiguous is stride S * D; the image rows [T, T + S) of every (T + S)-row sample of the joint stream are the
+ * pointer advanced by T * D with stride (T + S) * D.  Nothing outside those rows is touched.  16-byte accesses when rows * D % 8 == 0, x_batch_stride % 4 == 0
+ * and both pointers are 16-byte aligned, else scalar ones: the same bits either way.  FMI_ERR_INVALID: a null pointer, a negative size, a stride below rows * D. */
+int fmi_add_scaled_rows_bf16(float* x_f32, int64_t x_batch_stride, const void* src_bf16, int B, int64_t rows, int D, float scale, void* stream);
+
 /* The whole denoise loop == Sampler::sample(FlowMatchEulerDiscrete)
  * (pipelines/sampling.rs:25-48) around the step closure (pipelines/flux/mod.rs:305-318):
  *   for (t_curr,t_prev) in windows(timesteps): img += forward(img, t_curr) * (t_prev-t_curr)
@@ -473,6 +527,8 @@ int fmi_flux_forward_control(fmi_flux*, const fmi_flux_inputs* in, const fmi_flu
  *   ctl                             yes    FMI_ERR_UNSUPPORTED   yes
  *   cfg                                    FMI_ERR_UNSUPPORTED   yes
  *   cache                                                        yes
+ *   cn        ctx: FMI_ERR_UNSUPPORTED   ctl (a cond_channels > 0 model): FMI_ERR_UNSUPPORTED   cfg: yes   cache: FMI_ERR_UNSUPPORTED   x0/noise/mask: yes
+ * (cn: the ControlNet argument of fmi_flux_denoise_controlnet below, not a field of this struct; under sequence parallelism FMI_ERR_UNSUPPORTED.)
  * Three or more combine when every pair among them does.  x0 / noise / mask given only in part: FMI_ERR_INVALID.  Each option's own refusals are listed at its
  * struct above; n_steps * B > 4096 is FMI_ERR_UNSUPPORTED.  EVERY refusal — of an argument, an option or a combination — comes before any launch, any
  * allocation and any use of `stream`: a refused call leaves img_inout, the outputs of `cache` and the model as they were. */
@@ -485,6 +541,11 @@ typedef struct fmi_flux_denoise_options {
 } fmi_flux_denoise_options;
 int fmi_flux_denoise_with(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */,
                           float* img_inout, const double* timesteps_host, int n_steps, void* stream);
+/* The same loop with a ControlNet (see fmi_flux_controlnet above): step i evaluates the ControlNet on the step's state and injects its samples at
+ * c_i = cn->scale * step_scales[i] (cn->scale without step_scales); a step whose c_i is 0 is the plain step.  The ControlNet is an argument of its own — the
+ * options struct keeps its 7 fields — and fmi_flux_denoise_with IS this call with cn == NULL: the same launches, bits, errors and allocations. */
+int fmi_flux_denoise_controlnet(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */, const fmi_flux_controlnet* cn,
+                                float* img_inout, const double* timesteps_host, int n_steps, void* stream);
 
 /* The entries from before fmi_flux_denoise_with.  Each IS fmi_flux_denoise_with with the fields it names set from its arguments and every other field NULL —
  * the same launches, bits, errors and allocations. */
