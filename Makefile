@@ -74,7 +74,11 @@ clean:
 	rm -rf build $(LIB) $(ALT_LIB)
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib alt oracle clean FORCE
+# GGUF measurements (needs an MI355X): stand-alone block dequantisation per format next to the nf4 kernel, and the FLUX.1-dev shape with Q8_0 / Q4_K weights
+gguf-bench: lib
+	python3 tools/gguf_bench.py --out profiles/gguf.txt
+
+.PHONY: all lib alt oracle clean gguf-bench FORCE
 
 print-build-id:
 	@echo $(BUILD_ID)

@@ -9,6 +9,7 @@
 //   MOD     the modulation matrix in bf16 (6.5 GB)                             (allocated when a dense part arrives)
 //   BLOCKS  the block linears in bf16 (17.0 GB)                                (allocated when a dense part arrives)
 //   Q4      the same matrices as bitsandbytes nf4 / fp4 codes + f32 absmax     (allocated when a 4-bit part arrives)
+// LLM.int8 matrices and ggml blocks (fmi_flux_set_linear_gguf: 4.5 to 8.5 bits per weight) do not fit Q4's slots: the matrix owns them (Dense::own_wq, Dense::gq).
 // so a bf16 checkpoint occupies 23.8 GB and an nf4 one 6.7 GB — no bf16 duplicate of a quantised layer is resident
 // unless the caller asks for the expanded cache (fmi_flux_set_quant_dense_cache).  The arenas are also the unit of
 // the multi-GPU weight broadcast (fmi_flux_state_*).  Activations live in a per-(B,S,T) workspace that is allocated
@@ -34,7 +35,9 @@ struct Arena {
   DeviceBuffer base;
   size_t bytes = 0;  // layout size (known before the arena is allocated)
 };
-enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_DENSE = 100 };
+// PS_GGUF0 + ggml type id (2 .. 14): the part is resident as ggml blocks (fmi_flux_set_linear_gguf), in Dense::gq
+enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_GGUF0 = 16, PS_GGUF_END = 48, PS_DENSE = 100 };
+inline bool is_gguf(int state) { return state >= PS_GGUF0 && state < PS_GGUF_END; }
 
 struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N) bf16
   bf16_t* w = nullptr;  // null until the arena `ar` is allocated
@@ -46,7 +49,10 @@ struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N)
   uint8_t* wq = nullptr;   // Q4 arena (4-bit) or own_wq (int8): what the kernels read
   float* absmax = nullptr;
   DeviceBuffer own_wq, own_absmax;  // int8 matrices own their storage (1 B per weight: they do not fit the 4-bit arena's slots)
-  int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N))
+  int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N)), PS_GGUF0 + ggml type (blocks in gq; wq stays null)
+  // ggml blocks of the parts loaded with fmi_flux_set_linear_gguf, one allocation per part (5 to 8.5 bits per weight: they do not fit the 4-bit
+  // arena's slots, and the parts of one matrix may differ in type until finalize() decides); empty on a matrix that never saw such a part
+  std::vector<DeviceBuffer> gq;
   // optional fp8 form (fmi_flux_quantize_fp8): e4m3 (N,K) + per-output-channel f32 scale, used instead of w
   uint8_t* w8 = nullptr;
   float* w8_scale = nullptr;
@@ -426,6 +432,20 @@ int dequant_rows(Dense& d, int r0, int rows, int kind, int blocksize, hipStream_
   return FMI_OK;
 }
 
+// ggml blocks of part `part` of `d` -> its bf16 rows of `dst` (a (N, K) image of the matrix: d.w or the scratch)
+int expand_gguf_part(Dense& d, int part, bf16_t* dst, hipStream_t s) {
+  const Dense::Part& pt = d.parts[part];
+  return fmi_gguf_dequantize(pt.state - PS_GGUF0, d.gq[part].ptr, (int64_t)pt.rows * d.K, dst + (size_t)pt.r0 * d.K, FMI_BF16, s);
+}
+int expand_gguf(Dense& d, bf16_t* dst, hipStream_t s) {
+  for (int i = 0; i < (int)d.parts.size(); ++i) FMI_TRY(expand_gguf_part(d, i, dst, s));
+  return FMI_OK;
+}
+// a part stops being resident as ggml blocks (another setter takes it over)
+void drop_gguf_part(Dense& d, int part) {
+  if (part < (int)d.gq.size()) d.gq[part].reset();
+}
+
 // Decide how every fused matrix is multiplied: all parts the same quantised kind -> that kind (packed form only);
 // all dense -> dense; a mixture (e.g. a checkpoint that quantises to_q but not to_v) -> the quantised parts are
 // expanded into the dense arena once and the matrix is dense.
@@ -445,12 +465,15 @@ int finalize(fmi_flux* m) {
     }
     if (!uniform) {
       FMI_TRY(ensure_arena(m, d->ar));
-      for (auto& pt : d->parts)
-        if (pt.state != PS_DENSE) {
-          FMI_TRY(dequant_rows(*d, pt.r0, pt.rows, pt.state, pt.blocksize, nullptr));
-          pt.state = PS_DENSE, pt.blocksize = 0;
-        }
+      for (int i = 0; i < (int)d->parts.size(); ++i) {
+        auto& pt = d->parts[i];
+        if (pt.state == PS_DENSE) continue;
+        if (is_gguf(pt.state)) FMI_TRY(expand_gguf_part(*d, i, d->w, nullptr));
+        else FMI_TRY(dequant_rows(*d, pt.r0, pt.rows, pt.state, pt.blocksize, nullptr));
+        pt.state = PS_DENSE, pt.blocksize = 0;
+      }
       FMI_HIP_TRY(hipDeviceSynchronize());
+      d->gq.clear();  // (after the synchronisation: the expansions have read the blocks)
     }
     d->q_type = 0, d->q_blocksize = 0;
   }
@@ -632,7 +655,7 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
   // one decision per launch group (the img + txt problems of a double block stay one grouped launch)
   bool scratch = false;
   for (int i = 0; i < n && i < 2; ++i)
-    if (dn[i] && p[i].q_type && m->quant_mode != 1 && m->quant_mode != 2)
+    if (dn[i] && p[i].q_type && !is_gguf(p[i].q_type) && m->quant_mode != 1 && m->quant_mode != 2)
       scratch = scratch || p[i].M > (p[i].q_type == 3 ? INT8_FUSED_MAX_ROWS : Q4_FUSED_MAX_ROWS);
   // A matrix of 2^31 or more weights (the fused modulation matrix of FLUX.1: 344 D x D = 3.2e9) never goes through the scratch —
   // the stand-alone dequant launchers count elements in 32 bits and the scratch is sized for the block matrices — it stays on
@@ -642,9 +665,11 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
   for (int i = 0; i < n && i < 2; ++i) {
     Dense* d = dn[i];
     if (!d || !p[i].q_type) continue;
-    if (!m->dense_cache && !scratch) continue;  // fused paths (launch_gemm picks the kernel)
+    // ggml blocks (fmi_flux_set_linear_gguf) have no fused dequant-GEMM: at every row count the matrix is expanded, once (modes 1 and 3) or per call (0 and 2)
+    const bool gguf = is_gguf(p[i].q_type);
+    if (!m->dense_cache && !scratch && !gguf) continue;  // fused paths (launch_gemm picks the kernel)
     const size_t elems = (size_t)p[i].N * p[i].K;
-    bool once = m->dense_cache || (scratch && resolve_quant_mode(m) == 3);
+    bool once = m->dense_cache || ((scratch || gguf) && resolve_quant_mode(m) == 3);
     if (once && !m->dense_cache && m->quant_auto && !m->arena[d->ar].base) {
       // the "by memory" policy decided on ONE hipMemGetInfo snapshot: if the arena cannot be had after all — memory taken since, or a
       // later arena of the same model — fall back to the packed-only policy for good instead of answering every forward with FMI_ERR_NOMEM
@@ -659,7 +684,9 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
       if (!m->dense_ready.count(d)) {
         // expanded once, in row chunks of at most 2^28 elements (chunk starts stay multiples of the quantisation block: K % 64 == 0)
         const int chunk = std::max(64, (int)std::min<int64_t>(d->N, ((1ll << 28) / d->K) / 64 * 64));  // (the dequant kernels index in 32 bits: stay well below 2^31)
-        for (int r0 = 0; r0 < d->N; r0 += chunk) FMI_TRY(dequant_rows(*d, r0, std::min(chunk, d->N - r0), d->q_type, d->q_blocksize, s));
+        if (gguf) FMI_TRY(expand_gguf(*d, d->w, s));
+        else
+          for (int r0 = 0; r0 < d->N; r0 += chunk) FMI_TRY(dequant_rows(*d, r0, std::min(chunk, d->N - r0), d->q_type, d->q_blocksize, s));
         m->dense_ready.insert(d);
       }
       p[i].W = d->w;
@@ -670,7 +697,8 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
         for (int k = 0; k < 2; ++k) FMI_HIP_TRY(m->wscratch[k].alloc(want * sizeof(bf16_t)));
       }
       bf16_t* ws_i = m->wscratch[i].as<bf16_t>();
-      if (p[i].q_type == 3) FMI_TRY(launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(p[i].Wq), p[i].absmax, ws_i, p[i].K, (int64_t)elems, s));
+      if (gguf) FMI_TRY(expand_gguf(*d, ws_i, s));
+      else if (p[i].q_type == 3) FMI_TRY(launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(p[i].Wq), p[i].absmax, ws_i, p[i].K, (int64_t)elems, s));
       else if (p[i].q_type == 2) dequantize_blockwise_bf16_nf4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
       else dequantize_blockwise_bf16_fp4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
       p[i].W = ws_i;
@@ -1519,6 +1547,7 @@ extern "C" int fmi_flux_set_tensor(fmi_flux* m, const char* name, const void* da
   FMI_TRY(upload_as_bf16(data, dtype, numel, (bf16_t*)dst));
   if (d.d && !d.bias) {
     d.d->parts[d.part].state = PS_DENSE, d.d->parts[d.part].blocksize = 0;
+    drop_gguf_part(*d.d, d.part);
     m->dense_ready.erase(d.d);
     m->finalized = false;
   }
@@ -1571,6 +1600,7 @@ extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const u
   FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K / 2, packed, n / 2, hipMemcpyDefault));
   FMI_HIP_TRY(hipMemcpy(d->absmax + (size_t)pt.r0 * d->K / blocksize, absmax, n / blocksize * 4, hipMemcpyDefault));
   pt.state = (uint8_t)quant_type, pt.blocksize = blocksize;
+  drop_gguf_part(*d, dst.part);
   m->dense_ready.erase(d);
   m->finalized = false;
   m->missing.erase(wname);
@@ -1616,6 +1646,56 @@ extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const i
   FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K, weight, n, hipMemcpyDefault));
   FMI_HIP_TRY(hipMemcpy(d->absmax + pt.r0, scb, (size_t)out_features * 4, hipMemcpyDefault));
   pt.state = PS_INT8, pt.blocksize = 0;
+  drop_gguf_part(*d, dst.part);
+  m->dense_ready.erase(d);
+  m->finalized = false;
+  m->missing.erase(wname);
+  return FMI_OK;
+}
+
+// A Linear as ggml blocks (llama.cpp's .gguf files; gguf_dequant.hip): row-major, in_features / block_elems blocks per row.  Embedders, the final layer
+// and the modulation linears are expanded into their bf16 rows here (the fused modulation matrix never goes through densify()'s scratch, and as dense
+// rows it keeps the bf16 model's GEMV); the parts of a fused block matrix keep their blocks (Dense::gq) and finalize() / densify() decide.
+extern "C" int fmi_flux_set_linear_gguf(fmi_flux* m, const char* prefix, int ggml_type, const void* data, int out_features, int in_features) {
+  if (!m || !prefix || !data) return fail(FMI_ERR_INVALID, "set_linear_gguf: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_gguf: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
+  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_gguf: the model was quantised to 8 bits");
+  int be = 0, bb = 0;
+  FMI_TRY(fmi_gguf_block_info(ggml_type, &be, &bb));
+  if (in_features <= 0 || out_features <= 0 || in_features % be)
+    return fail(FMI_ERR_INVALID, "set_linear_gguf: in_features must be a positive multiple of the block's " + std::to_string(be) + " elements");
+  FMI_TRY(use_device(m));
+  const std::string wname = std::string(prefix) + ".weight";
+  auto it = m->names.find(wname);
+  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_gguf: unknown linear '") + prefix + "'");
+  for (const auto& ad : m->loras)
+    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_gguf: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
+  const Dest& dst = it->second;
+  Dense* d = dst.d;
+  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_gguf: shape mismatch for " + wname);
+  const int64_t n = (int64_t)out_features * in_features;
+  const size_t bytes = (size_t)(n / be) * bb;
+  DeviceBuffer blocks;
+  FMI_HIP_TRY(blocks.alloc(bytes));
+  FMI_HIP_TRY(hipMemcpy(blocks.ptr, data, bytes, hipMemcpyDefault));
+  Dense::Part& pt = d->parts[dst.part];
+  if (d->ar == AR_BASE || d->ar == AR_MOD) {
+    FMI_TRY(ensure_arena(m, d->ar));
+    FMI_TRY(fmi_gguf_dequantize(ggml_type, blocks.ptr, n, d->w + (size_t)pt.r0 * d->K, FMI_BF16, nullptr));
+    FMI_HIP_TRY(hipDeviceSynchronize());
+    if (d->ar == AR_MOD) {
+      pt.state = PS_DENSE, pt.blocksize = 0;
+      m->dense_ready.erase(d);
+      m->finalized = false;
+    }
+    m->attn_scales_valid = false;
+    m->missing.erase(wname);
+    return FMI_OK;
+  }
+  if (d->gq.size() < d->parts.size()) d->gq.resize(d->parts.size());
+  FMI_HIP_TRY(hipDeviceSynchronize());  // (a replaced part's blocks may still be read by an expansion in flight)
+  d->gq[dst.part] = std::move(blocks);
+  pt.state = (uint8_t)(PS_GGUF0 + ggml_type), pt.blocksize = 0;
   m->dense_ready.erase(d);
   m->finalized = false;
   m->missing.erase(wname);
@@ -1632,6 +1712,8 @@ extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
     if (m->arena[a].base) b += m->arena[a].bytes;
   for (const Dense* d : m->fused)
     if (d->own_wq) b += (size_t)d->N * d->K + (size_t)d->N * 4;
+  for (const Dense* d : m->fused)
+    for (const DeviceBuffer& g : d->gq) b += g.bytes();
   for (const auto& ad : m->loras)
     for (const auto& pr : ad.second.pairs) {
       const Dest& dst = m->names.at(pr.first);
@@ -1664,6 +1746,7 @@ extern "C" int fmi_flux_state_export(fmi_flux* m, uint8_t* blob_host, size_t cap
   for (int a = 0; a < AR_COUNT; ++a) *o++ = m->arena[a].base ? 1 : 0;
   for (const Dense* d : m->fused) {
     if (d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_export: LLM.int8 matrices are not part of the flat weight state");
+    if (is_gguf(d->q_type)) return fail(FMI_ERR_UNSUPPORTED, "state_export: matrices resident as ggml blocks are not part of the flat weight state");
     *o++ = (uint8_t)d->q_type;
     const uint32_t bs = (uint32_t)d->q_blocksize;
     memcpy(o, &bs, 4);
@@ -1688,6 +1771,8 @@ extern "C" int fmi_flux_state_adopt(fmi_flux* m, const uint8_t* blob_host, size_
     memcpy(&bs, o, 4);
     o += 4;
     if (qt == 3 || d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
+    if (is_gguf(qt)) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: matrices resident as ggml blocks are not part of the flat weight state");
+    d->gq.clear();
     d->q_type = qt, d->q_blocksize = (int)bs;
     for (auto& pt : d->parts) pt.state = qt ? (uint8_t)qt : (uint8_t)PS_DENSE, pt.blocksize = (int)bs;
     if (qt ? !m->arena[AR_Q4].base : !m->arena[d->ar].base) return fail(FMI_ERR_INVALID, "state_adopt: blob is inconsistent (matrix stored in an arena that is not present)");

@@ -328,6 +328,23 @@ class FluxModel:
             wp, sp = C.c_void_p(w.ctypes.data), C.c_void_p(sc.ctypes.data)
         L.check(self.lib.fmi_flux_set_linear_int8(self.h, prefix.encode(), wp, sp, out_features, in_features), self.lib)
 
+    def set_linear_gguf(self, prefix: str, ggml_type: int, data, out_features: int, in_features: int):
+        """A Linear as ggml blocks (llama.cpp's .gguf; include/flux_mi355x.h: fmi_flux_set_linear_gguf): row-major, in_features / block_elems blocks per
+        row.  `data`: a uint8 torch tensor (host or device), or anything with the buffer protocol (numpy array, memoryview of an mmap) — not copied here."""
+        if isinstance(data, torch.Tensor):
+            keep = data.contiguous()
+            assert keep.dtype == torch.uint8
+            p, nbytes = C.c_void_p(keep.data_ptr()), keep.numel()
+        else:
+            keep = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+            p, nbytes = C.c_void_p(keep.ctypes.data), keep.size
+        be, bb = C.c_int(), C.c_int()
+        L.check(self.lib.fmi_gguf_block_info(int(ggml_type), C.byref(be), C.byref(bb)), self.lib)
+        if in_features % be.value == 0 and nbytes != out_features * (in_features // be.value) * bb.value:
+            raise L.FmiError(f"set_linear_gguf: {prefix}: {nbytes} bytes of blocks for a ({out_features}, {in_features}) Linear of ggml type {ggml_type}, expected "
+                             f"{out_features * (in_features // be.value) * bb.value}", code=L.ERR_INVALID)
+        L.check(self.lib.fmi_flux_set_linear_gguf(self.h, prefix.encode(), int(ggml_type), p, out_features, in_features), self.lib)
+
     def quantize_fp8(self, stream=None):
         """Switch the DiT block linears to the fp8 (OCP e4m3) MFMA path: weights quantised once per output
         channel from the loaded bf16 values, activations per token on the fly (BASELINE configs[4])."""
@@ -368,7 +385,8 @@ class FluxModel:
         """Quantised linears, launches above 383 (nf4 / fp4) / 256 (LLM.int8) rows — smaller ones always multiply from the packed codes:
         -1 (default) = by memory: 3 when the device has the room, else 0; 0 / False = packed only: per-call expansion into a 264 MB
         scratch + dense GEMM; 1 / True = every matrix expanded once into the bf16 arenas; 2 = always the fused kernels; 3 = the matrices
-        of the large launches expanded once.  Same bits in every mode."""
+        of the large launches expanded once.  Same bits in every mode.  Matrices resident as ggml blocks (set_linear_gguf) have no fused kernel:
+        at every row count they are expanded once (1, 3, and -1 with the room) or per call (0, and 2 — which has no fused kernel to select there)."""
         L.check(self.lib.fmi_flux_set_quant_dense_cache(self.h, int(mode)), self.lib)
 
     def set_split_k(self, on: bool):

@@ -296,3 +296,292 @@ def load_text_encoder(model, tensors: Iterator[Tuple[str, torch.Tensor]]) -> int
         raise ValueError(f"{len(m)} text-encoder tensors missing, e.g. {m[0]}")
     model.load_stats = stats
     return stats["dense"] + stats["bnb4"] + stats["int8"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# GGUF transformers: llama.cpp's single-file format with the ggml block quantisations, as most quantised FLUX.1
+# transformers are distributed (flux1-dev-Q8_0.gguf, -Q4_K_S, ...).  The file layout is the reference's gguf_file.rs (never wired to FLUX
+# there); the blocks are expanded on the device (csrc/gguf_dequant.hip).
+GGML_F32, GGML_F16, GGML_BF16 = 0, 1, 30
+GGML_TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 9: "Q8_1", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K",
+                   14: "Q6_K", 15: "Q8_K", 16: "IQ2_XXS", 17: "IQ2_XS", 18: "IQ3_XXS", 19: "IQ1_S", 20: "IQ4_NL", 21: "IQ3_S", 22: "IQ2_S", 23: "IQ4_XS",
+                   24: "I8", 25: "I16", 26: "I32", 27: "I64", 28: "F64", 29: "IQ1_M", 30: "BF16"}
+# ggml type -> (elements per block, bytes per block) of every type whose size this reader knows; the library expands the first eight block formats
+GGML_BLOCKS = {2: (32, 18), 3: (32, 20), 6: (32, 22), 7: (32, 24), 8: (32, 34), 12: (256, 144), 13: (256, 176), 14: (256, 210),
+               0: (1, 4), 1: (1, 2), 30: (1, 2), 9: (32, 36), 10: (256, 84), 11: (256, 110), 15: (256, 292), 24: (1, 1), 25: (1, 2), 26: (1, 4), 27: (1, 8),
+               28: (1, 8)}
+GGUF_QUANT_TYPES = (2, 3, 6, 7, 8, 12, 13, 14)
+_GGUF_SCALARS = {0: "<B", 1: "<b", 2: "<H", 3: "<h", 4: "<I", 5: "<i", 6: "<f", 7: "<?", 10: "<Q", 11: "<q", 12: "<d"}
+
+
+def ggml_type_name(t: int) -> str:
+    return GGML_TYPE_NAMES.get(int(t), f"type {t}")
+
+
+class GgufFile:
+    """mmap reader of a GGUF v2 / v3 file, little-endian (gguf_file.rs): magic and version, counts, metadata key/values of every value type (arrays
+    included), tensor infos, and the data section aligned to `general.alignment` (default 32).  GGUF stores dims innermost-first: a Linear (out, in)
+    arrives as [in, out]; `tensors` and iteration give the shape outer-first.  Iterating yields (name, ggml_type, shape, memoryview) without copying.
+    ValueError: bad magic, version 1 (or any other than 2 / 3), a tensor running past the end of the file, a duplicate tensor name."""
+
+    def __init__(self, path: str):
+        self.path = path
+        self._f = open(path, "rb")
+        self._mm = mmap.mmap(self._f.fileno(), 0, access=mmap.ACCESS_READ)
+        self._view = memoryview(self._mm)
+        self._pos = 0
+        size = len(self._mm)
+        if size < 24 or bytes(self._view[:4]) != b"GGUF":
+            raise ValueError(f"{path}: not a GGUF file (bad magic)")
+        self._pos = 4
+        self.version = self._scalar("<I")
+        if self.version not in (2, 3):
+            raise ValueError(f"{path}: GGUF version {self.version} is not supported (2 and 3 are; a value like {self.version} can also mean a big-endian file)")
+        n_tensors, n_kv = self._scalar("<Q"), self._scalar("<Q")
+        self.metadata = {}
+        for _ in range(n_kv):
+            key = self._string()
+            self.metadata[key] = self._value(self._scalar("<I"))
+        infos = []
+        seen = set()
+        for _ in range(n_tensors):
+            name = self._string()
+            if name in seen:
+                raise ValueError(f"{path}: duplicate tensor name {name}")
+            seen.add(name)
+            n_dims = self._scalar("<I")
+            dims = [self._scalar("<Q") for _ in range(n_dims)]
+            ggml_type, offset = self._scalar("<I"), self._scalar("<Q")
+            infos.append((name, ggml_type, tuple(reversed(dims)), offset))
+        self.alignment = int(self.metadata.get("general.alignment", 32))
+        if self.alignment <= 0:
+            raise ValueError(f"{path}: general.alignment = {self.alignment}")
+        self.data_offset = (self._pos + self.alignment - 1) // self.alignment * self.alignment
+        self.tensors = {}
+        for name, ggml_type, shape, offset in infos:
+            numel = 1
+            for d in shape:
+                numel *= d
+            nbytes = None
+            if ggml_type in GGML_BLOCKS:
+                be, bb = GGML_BLOCKS[ggml_type]
+                if shape and shape[-1] % be:
+                    raise ValueError(f"{path}: {name}: innermost dimension {shape[-1]} is not a multiple of {ggml_type_name(ggml_type)}'s {be}-element block")
+                nbytes = numel // be * bb
+            start = self.data_offset + offset
+            if start > size or (nbytes is not None and start + nbytes > size):
+                raise ValueError(f"{path}: tensor {name} runs past the end of the file ({start} + {nbytes} > {size})")
+            self.tensors[name] = (ggml_type, shape, start, nbytes)
+
+    def _need(self, n):
+        if self._pos + n > len(self._mm):
+            raise ValueError(f"{self.path}: truncated GGUF header")
+
+    def _scalar(self, fmt):
+        n = struct.calcsize(fmt)
+        self._need(n)
+        v = struct.unpack_from(fmt, self._mm, self._pos)[0]
+        self._pos += n
+        return v
+
+    def _string(self):
+        n = self._scalar("<Q")
+        self._need(n)
+        s = bytes(self._view[self._pos:self._pos + n]).decode("utf-8", errors="replace")
+        self._pos += n
+        return s
+
+    def _value(self, vt):
+        if vt in _GGUF_SCALARS:
+            return self._scalar(_GGUF_SCALARS[vt])
+        if vt == 8:
+            return self._string()
+        if vt == 9:
+            et, n = self._scalar("<I"), self._scalar("<Q")
+            return [self._value(et) for _ in range(n)]
+        raise ValueError(f"{self.path}: unknown GGUF metadata value type {vt}")
+
+    def names(self) -> List[str]:
+        return list(self.tensors)
+
+    def data(self, name: str) -> memoryview:
+        ggml_type, shape, start, nbytes = self.tensors[name]
+        if nbytes is None:
+            raise ValueError(f"{self.path}: {name}: the size of ggml type {ggml_type_name(ggml_type)} is not known to this reader")
+        return self._view[start:start + nbytes]
+
+    def __iter__(self):
+        for name, (ggml_type, shape, start, nbytes) in self.tensors.items():
+            yield name, ggml_type, shape, (self._view[start:start + nbytes] if nbytes is not None else None)
+
+
+_BFL_TOP = {"time_in.in_layer": "time_text_embed.timestep_embedder.linear_1", "time_in.out_layer": "time_text_embed.timestep_embedder.linear_2",
+            "vector_in.in_layer": "time_text_embed.text_embedder.linear_1", "vector_in.out_layer": "time_text_embed.text_embedder.linear_2",
+            "guidance_in.in_layer": "time_text_embed.guidance_embedder.linear_1", "guidance_in.out_layer": "time_text_embed.guidance_embedder.linear_2",
+            "txt_in": "context_embedder", "img_in": "x_embedder", "final_layer.linear": "proj_out"}
+_BFL_NORMS = {"img_attn.norm.query_norm.scale": "attn.norm_q.weight", "img_attn.norm.key_norm.scale": "attn.norm_k.weight",
+              "txt_attn.norm.query_norm.scale": "attn.norm_added_q.weight", "txt_attn.norm.key_norm.scale": "attn.norm_added_k.weight"}
+_BFL_SINGLE_NORMS = {"norm.query_norm.scale": "attn.norm_q.weight", "norm.key_norm.scale": "attn.norm_k.weight"}
+
+
+def bfl_to_diffusers(name: str, rows: int, hidden: int):
+    """One tensor of a BFL-named FLUX checkpoint (`rows` = its outer dimension) as the diffusers tensors it holds: [(diffusers name, [(r0, r1), ...])] —
+    the row ranges of the source, concatenated in this order, are the diffusers tensor.  Follows diffusers' convert_flux_transformer_checkpoint_to_diffusers:
+    qkv into thirds, a single block's linear1 into D, D, D, M rows, and final_layer.adaLN_modulation.1 with its two halves exchanged (BFL stores
+    shift | scale, diffusers scale | shift).  None for a name that is not part of the transformer.  The block-level module map is lora.py's."""
+    from . import lora
+    whole = [(0, rows)]
+    for suffix in (".weight", ".bias", ".scale"):
+        if name.endswith(suffix):
+            mod, kind = name[:-len(suffix)], suffix[1:]
+            break
+    else:
+        return None
+    if kind == "scale":
+        parts = name.split(".", 2)
+        if len(parts) == 3 and parts[0] == "double_blocks" and parts[2] in _BFL_NORMS:
+            return [(f"transformer_blocks.{parts[1]}.{_BFL_NORMS[parts[2]]}", whole)]
+        if len(parts) == 3 and parts[0] == "single_blocks" and parts[2] in _BFL_SINGLE_NORMS:
+            return [(f"single_transformer_blocks.{parts[1]}.{_BFL_SINGLE_NORMS[parts[2]]}", whole)]
+        return None
+    if mod in _BFL_TOP:
+        return [(f"{_BFL_TOP[mod]}.{kind}", whole)]
+    if mod == "final_layer.adaLN_modulation.1":
+        if rows % 2:
+            return None
+        return [(f"norm_out.linear.{kind}", [(rows // 2, rows), (0, rows // 2)])]
+    parts = mod.split(".", 2)
+    if len(parts) != 3 or not parts[1].isdigit():
+        return None
+    if parts[0] == "double_blocks" and parts[2] in lora.BFL_DOUBLE:
+        targets, prefix = lora.BFL_DOUBLE[parts[2]], f"transformer_blocks.{parts[1]}."
+        bounds = [rows * i // len(targets) for i in range(len(targets) + 1)]
+        if rows % len(targets):
+            return None
+    elif parts[0] == "single_blocks" and parts[2] in lora.BFL_SINGLE:
+        targets, prefix = lora.BFL_SINGLE[parts[2]], f"single_transformer_blocks.{parts[1]}."
+        bounds = [0, hidden, 2 * hidden, 3 * hidden, rows] if len(targets) == 4 else [0, rows]
+        if len(targets) == 4 and rows <= 3 * hidden:
+            return None
+    else:
+        return None
+    return [(f"{prefix}{t}.{kind}", [(bounds[i], bounds[i + 1])]) for i, t in enumerate(targets)]
+
+
+def gguf_flux_entries(gguf: "GgufFile"):
+    """The tensors of a FLUX transformer GGUF under their diffusers names: [(diffusers name, ggml_type, shape, source tensor, row ranges)], and the source
+    names that are no part of the transformer.  BFL naming or diffusers naming as is, told apart by `double_blocks.0.` against `transformer_blocks.0.`; an
+    optional `model.diffusion_model.` prefix is stripped.  ValueError for a file with neither."""
+    strip = "model.diffusion_model."
+    names = {(n[len(strip):] if n.startswith(strip) else n): n for n in gguf.names()}
+    bfl = any(n.startswith("double_blocks.0.") for n in names)
+    if not bfl and not any(n.startswith("transformer_blocks.0.") for n in names):
+        raise ValueError(f"{gguf.path}: neither BFL (double_blocks.0.*) nor diffusers (transformer_blocks.0.*) FLUX transformer tensors")
+    hidden = None
+    for key in ("img_in.weight", "x_embedder.weight"):
+        if key in names:
+            hidden = gguf.tensors[names[key]][1][0]
+    entries, skipped = [], []
+    for short, full in names.items():
+        ggml_type, shape, _, _ = gguf.tensors[full]
+        if not shape:
+            skipped.append(full)
+            continue
+        if not bfl:
+            entries.append((short, ggml_type, shape, full, [(0, shape[0])]))
+            continue
+        mapped = bfl_to_diffusers(short, shape[0], hidden or 0)
+        if mapped is None:
+            skipped.append(full)
+            continue
+        for dname, ranges in mapped:
+            entries.append((dname, ggml_type, (sum(b - a for a, b in ranges),) + tuple(shape[1:]), full, ranges))
+    return entries, skipped
+
+
+def flux_config_from_gguf(gguf: "GgufFile", base_config: Optional[dict] = None) -> dict:
+    """The model configuration of a FLUX transformer GGUF, inferred from its shapes (a BFL file has no config.json): in_channels, out_channels,
+    pooled_projection_dim, joint_attention_dim, num_attention_heads (D / 128), num_layers, num_single_layers, guidance_embeds; the RoPE constants are
+    FLUX.1's.  base_config: a transformer/config.json the result must agree with, field by field, else a ValueError names the field."""
+    from . import flux as F
+    entries, _ = gguf_flux_entries(gguf)
+    shapes = {n: s for n, _, s, _, _ in entries}
+
+    def need(name):
+        if name not in shapes:
+            raise ValueError(f"{gguf.path}: no {name}: cannot infer the FLUX configuration")
+        return shapes[name]
+
+    D, cin = need("x_embedder.weight")
+    if D % 128:
+        raise ValueError(f"{gguf.path}: hidden size {D} is not a multiple of the 128-wide attention head")
+
+    def count(prefix):
+        idx = {int(n[len(prefix):].split(".", 1)[0]) for n in shapes if n.startswith(prefix)}
+        return max(idx) + 1 if idx else 0
+
+    cfg = dict(F.FLUX_DEV, in_channels=int(cin), out_channels=int(need("proj_out.weight")[0]),
+               pooled_projection_dim=int(need("time_text_embed.text_embedder.linear_1.weight")[1]), joint_attention_dim=int(need("context_embedder.weight")[1]),
+               num_attention_heads=int(D // 128), num_layers=count("transformer_blocks."), num_single_layers=count("single_transformer_blocks."),
+               guidance_embeds="time_text_embed.guidance_embedder.linear_1.weight" in shapes)
+    if base_config is not None:
+        for k in ("in_channels", "out_channels", "pooled_projection_dim", "joint_attention_dim", "num_attention_heads", "num_layers", "num_single_layers",
+                  "guidance_embeds"):
+            if k not in base_config:
+                continue
+            have = base_config[k]
+            if k == "out_channels" and have is None:
+                have = base_config.get("in_channels", cfg["in_channels"])
+            if type(cfg[k])(have) != cfg[k]:
+                raise ValueError(f"{gguf.path}: {k} = {cfg[k]} by the file's shapes, transformer/config.json says {base_config[k]}")
+    return cfg
+
+
+def _gguf_rows(view, row_bytes: int, ranges) -> np.ndarray:
+    """Rows [r0, r1) ... of a row-major byte image, concatenated; one range: a view, no copy."""
+    a = np.frombuffer(view, np.uint8)
+    pieces = [a[r0 * row_bytes:r1 * row_bytes] for r0, r1 in ranges]
+    return pieces[0] if len(pieces) == 1 else np.concatenate(pieces)
+
+
+def load_flux_gguf(flux, gguf) -> dict:
+    """Feed a FluxModel from a GGUF file (a path or a GgufFile).  Plain tensors (F32 / F16 / BF16) go through set_tensor, block-quantised Linears through
+    set_linear_gguf; the row splits of the BFL naming and the exchange of the final layer's halves are done on the packed bytes (a row is a whole number
+    of blocks, so no block is cut).  Returns load_flux's stats plus "gguf" (block-quantised Linears) and "types" ({ggml type name: tensors})."""
+    if not isinstance(gguf, GgufFile):
+        gguf = GgufFile(gguf)
+    want = synth.flux_tensor_shapes(flux.cfg)
+    entries, skipped = gguf_flux_entries(gguf)
+    stats = {"dense": 0, "bnb4": 0, "int8": 0, "gguf": 0, "types": {}, "skipped": list(skipped)}
+    plain = {GGML_F32: (np.float32, 4), GGML_F16: (np.float16, 2), GGML_BF16: (np.uint16, 2)}
+    for dname, ggml_type, shape, src, ranges in entries:
+        if dname not in want:
+            stats["skipped"].append(src)
+            continue
+        if tuple(shape) != tuple(want[dname]):
+            raise ValueError(f"{gguf.path}: {src} -> {dname} is {tuple(shape)}, the configuration says {tuple(want[dname])}")
+        tname = ggml_type_name(ggml_type)
+        inner = 1
+        for d in shape[1:]:
+            inner *= d
+        if ggml_type in plain:
+            npdt, size = plain[ggml_type]
+            a = _gguf_rows(gguf.data(src), inner * size, ranges).view(npdt).reshape(shape)
+            with warnings.catch_warnings():  # (read-only mmap views are intended: the tensor is only copied to the device)
+                warnings.simplefilter("ignore", UserWarning)
+                t = torch.from_numpy(a)
+            flux.set_tensor(dname, t.view(torch.bfloat16) if ggml_type == GGML_BF16 else t)
+            stats["dense"] += 1
+        else:
+            if ggml_type not in GGUF_QUANT_TYPES or len(shape) != 2 or not dname.endswith(".weight"):
+                if ggml_type in GGUF_QUANT_TYPES:
+                    raise ValueError(f"{gguf.path}: {src}: only 2-D Linear weights can be block-quantised, this is {tuple(shape)}")
+                from . import _lib as L
+                L.check(flux.lib.fmi_gguf_block_info(int(ggml_type), None, None), flux.lib)  # refused by name (FMI_ERR_UNSUPPORTED)
+                raise ValueError(f"{gguf.path}: {src}: unsupported ggml type {tname}")
+            be, bb = GGML_BLOCKS[ggml_type]
+            flux.set_linear_gguf(dname[:-len(".weight")], ggml_type, _gguf_rows(gguf.data(src), shape[1] // be * bb, ranges), shape[0], shape[1])
+            stats["gguf"] += 1
+        stats["types"][tname] = stats["types"].get(tname, 0) + 1
+    flux.assert_complete()
+    return stats

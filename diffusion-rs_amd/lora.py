@@ -33,6 +33,9 @@ _KOHYA_SINGLE = {
     "linear2": ("proj_out",),
     "modulation_lin": ("norm.linear",),
 }
+# the same block-level map keyed by the BFL module path (img_attn.qkv, modulation.lin, ...): what loader.load_flux_gguf reads a BFL-named checkpoint with
+BFL_DOUBLE = {k.replace("_attn_", "_attn.").replace("_mlp_", "_mlp.").replace("_mod_", "_mod."): v for k, v in _KOHYA_DOUBLE.items()}
+BFL_SINGLE = {k.replace("modulation_", "modulation."): v for k, v in _KOHYA_SINGLE.items()}
 _KOHYA_BLOCK = re.compile(r"^lora_unet_(double|single)_blocks_(\d+)_(.+)$")
 _KOHYA_SUFFIXES = (".lora_down.weight", ".lora_up.weight", ".alpha")
 _PEFT_SUFFIXES = (".lora_A.weight", ".lora_B.weight", ".alpha")

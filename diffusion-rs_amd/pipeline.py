@@ -68,6 +68,12 @@ class ModelSource:
             raise ValueError("Expected model ID for the model source")
         return ModelSource("model_id", model_id=self.model_id, transformer_model_id=model_id)
 
+    def override_transformer_gguf(self, file: str) -> "ModelSource":
+        """The transformer from a single GGUF file (llama.cpp's block quantisations, BFL or diffusers tensor naming); model_index.json, the
+        scheduler, the VAE, the text encoders and the tokenizers still come from this source's directory.  override_transformer_model_id with a path that
+        ends in .gguf is the same."""
+        return self.override_transformer_model_id(file)
+
     @staticmethod
     def DdufFile(file: str) -> "ModelSource":
         return ModelSource("dduf", file=file)
@@ -381,13 +387,20 @@ class Pipeline:
         sc = fl.read_json("scheduler/scheduler_config.json")
         self.scheduler = F.SchedulerConfig(sc["base_image_seq_len"], sc["base_shift"], sc["max_image_seq_len"], sc["max_shift"], sc["shift"],
                                            sc["use_dynamic_shifting"])
-        tl = loader.FileLoader(transformer_path) if transformer_path else fl  # ModelIdWithTransformer (model_source.rs:22-25)
-        tc = tl.read_json("transformer/config.json")
-        fcfg = dict(F.FLUX_DEV, **{k: tc[k] for k in ("in_channels", "out_channels", "pooled_projection_dim", "joint_attention_dim", "num_attention_heads",
-                                                     "num_layers", "num_single_layers", "guidance_embeds") if k in tc})
+        if transformer_path and transformer_path.lower().endswith(".gguf"):
+            # a GGUF transformer: the configuration comes from the file's shapes — a BFL file has no config.json — and must agree with the
+            # base directory's transformer/config.json where there is one
+            gg = loader.GgufFile(transformer_path)
+            fcfg = loader.flux_config_from_gguf(gg, fl.read_json("transformer/config.json") if fl.has("transformer/config.json") else None)
+            self._dit_loader = lambda: self.load_stats.update(loader.load_flux_gguf(self.flux, gg))
+        else:
+            tl = loader.FileLoader(transformer_path) if transformer_path else fl  # ModelIdWithTransformer (model_source.rs:22-25)
+            tc = tl.read_json("transformer/config.json")
+            fcfg = dict(F.FLUX_DEV, **{k: tc[k] for k in ("in_channels", "out_channels", "pooled_projection_dim", "joint_attention_dim", "num_attention_heads",
+                                                         "num_layers", "num_single_layers", "guidance_embeds") if k in tc})
+            self._dit_loader = lambda: self.load_stats.update(loader.load_flux(self.flux, tl.tensors("transformer")))
         loader.check_conditioning_channels(class_name, fcfg["in_channels"], fcfg.get("out_channels"))  # the class and the embedder's width agree
         self.flux = F.FluxModel(fcfg, self.device_index)
-        self._dit_loader = lambda: self.load_stats.update(loader.load_flux(self.flux, tl.tensors("transformer")))
         if load_dit:  # (multi-GPU: the other ranks receive the weight arenas, dist.broadcast_state)
             self._dit_loader()
         vc = fl.read_json("vae/config.json")

@@ -415,6 +415,33 @@ def quantize_nf4_device(w, blocksize=64):
     return packed.contiguous(), absmax.contiguous()
 
 
+def quantize_gguf_device(w, ggml_type: int):
+    """A simple valid ggml quantiser on the GPU for synthetic GGUF weights (tools/gguf_bench.py): Q8_0 (8: absmax / 127 per 32 weights) and Q4_K (12: min / max
+    per 32 weights, the 6-bit sub-block scales and minima rounded up) — not llama.cpp's search, any well-formed blocks are a valid file.  w: (out, in) with
+    `in` a multiple of the block; returns the row-major block bytes as a flat uint8 tensor."""
+    import torch
+    x = w.float()
+    if ggml_type == 8:
+        x = x.reshape(-1, 32)
+        d = (x.abs().amax(1) / 127).to(torch.float16)
+        q = torch.round(x / d.float().clamp_min(1e-30)[:, None]).clamp(-127, 127).to(torch.int8)
+        return torch.cat([d.view(torch.uint8).reshape(-1, 2), q.view(torch.uint8)], 1).reshape(-1)
+    if ggml_type != 12:
+        raise ValueError(f"quantize_gguf_device: ggml type {ggml_type} (Q8_0 = 8 and Q4_K = 12 are generated)")
+    xs = x.reshape(-1, 8, 32)
+    mins = (-xs.amin(2)).clamp_min(0)
+    scl = (xs.amax(2) + mins) / 15
+    d = (scl.amax(1) / 63).to(torch.float16)
+    dmin = (mins.amax(1) / 63).to(torch.float16)
+    sc = torch.ceil(scl / d.float().clamp_min(1e-30)[:, None]).clamp(0, 63).to(torch.uint8)
+    mn = torch.ceil(mins / dmin.float().clamp_min(1e-30)[:, None]).clamp(0, 63).to(torch.uint8)
+    step = (d.float()[:, None] * sc).clamp_min(1e-30)
+    q = torch.round((xs + (dmin.float()[:, None] * mn)[:, :, None]) / step[:, :, None]).clamp(0, 15).to(torch.uint8)
+    scales = torch.cat([(sc[:, :4] & 63) | ((sc[:, 4:] >> 4) << 6), (mn[:, :4] & 63) | ((mn[:, 4:] >> 4) << 6), (sc[:, 4:] & 15) | ((mn[:, 4:] & 15) << 4)], 1)
+    qs = (q[:, 0::2, :] | (q[:, 1::2, :] << 4)).reshape(-1, 128)
+    return torch.cat([d.view(torch.uint8).reshape(-1, 2), dmin.view(torch.uint8).reshape(-1, 2), scales, qs], 1).reshape(-1)
+
+
 def is_block_linear(name):
     """Linears of the DiT blocks that take the fused 4-bit GEMM path (everything a bnb checkpoint
     quantises inside transformer_blocks / single_transformer_blocks except the modulation linears)."""

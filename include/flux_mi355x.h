@@ -51,6 +51,7 @@ extern "C" {
  *   Then, still 6: channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth) — fmi_flux_create_cond, fmi_flux_cond_channels, fmi_flux_control,
  *   fmi_flux_forward_control, fmi_flux_denoise_control, fmi_cast_cols_bf16, fmi_mask_image, fmi_fill_condition.
  *   Then, still 6: the denoise loop's options in one struct — fmi_flux_denoise_options, fmi_flux_denoise_with; the six fmi_flux_denoise* entries remain.
+ *   Then, still 6: GGUF transformers (ggml block formats) — fmi_gguf_block_info, fmi_gguf_dequantize, fmi_flux_set_linear_gguf.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -169,6 +170,36 @@ int fmi_flux_set_linear_int8(fmi_flux*, const char* prefix, const int8_t* weight
  *    3 as 0, but a matrix that 0 would expand per call is expanded once into its dense slot (small launches stay on the codes).
  * All of them produce the same bits. */
 int fmi_flux_set_quant_dense_cache(fmi_flux*, int mode);
+
+/* ggml block formats (llama.cpp's .gguf files).  Supported ggml type ids: Q4_0 2, Q4_1 3, Q5_0 6, Q5_1 7, Q8_0 8 (32 weights per block of
+ * 18 / 20 / 22 / 24 / 34 bytes) and Q4_K 12, Q5_K 13, Q6_K 14 (256 weights per block of 144 / 176 / 210 bytes).  Every other id — Q2_K, Q3_K,
+ * Q8_1, Q8_K, the IQ family — is refused by name with FMI_ERR_UNSUPPORTED; F32 / F16 / BF16 tensors (0 / 1 / 30) are plain and go through
+ * fmi_flux_set_tensor.  block_elems / block_bytes may be NULL. */
+int fmi_gguf_block_info(int ggml_type, int* block_elems, int* block_bytes);
+/* n_elems weights of `blocks` (DEVICE pointer, 2-byte aligned, n_elems / block_elems consecutive blocks) -> out (DEVICE pointer, BF16 or F32).
+ * Values are those of ggml's dequantize_row_* evaluated in f32 with every multiply and add rounded on its own, then one RNE rounding to bf16:
+ * bit-equal to a scalar float32 restatement.  FMI_ERR_INVALID: n_elems not a multiple of the block's elements, another out_dtype, a null or
+ * misaligned pointer.  Indexes in 64 bits. */
+int fmi_gguf_dequantize(int ggml_type, const void* blocks, int64_t n_elems, void* out, fmi_dtype out_dtype, void* stream);
+/* A Linear given as ggml blocks: row-major, each of the out_features rows is in_features / block_elems blocks (in_features % block_elems != 0:
+ * FMI_ERR_INVALID).  Host or device pointer.  Same prefix rules and refusals as fmi_flux_set_linear_bnb4 (unknown prefix, shape mismatch: INVALID; a
+ * ControlNet handle: UNSUPPORTED; a model in an 8-bit mode, a weight with LoRA adapters merged: STATE).
+ *   - embedders and the final layer are expanded into their bf16 slot at load;
+ *   - modulation linears (norm1.linear, norm1_context.linear, norm.linear, norm_out.linear) are expanded at load into the fused modulation matrix,
+ *     in every mode: that matrix has 3.2e9 weights in FLUX.1-dev and never goes through the per-call scratch, so a packed-only GGUF FLUX.1-dev
+ *     holds the blocks of the block linears PLUS 6.5 GB of dense modulation weights;
+ *   - parts of a fused block matrix keep their packed blocks resident, in storage the matrix owns.  If all parts of a matrix have the same ggml
+ *     type, only the blocks are resident; a mixture of types, or of GGUF and dense / bitsandbytes parts, is expanded into the dense arena once.
+ * There is no fused dequant-GEMM for these formats: at EVERY row count the matrix is expanded, once into its dense slot or per call into the
+ * scratch, as fmi_flux_set_quant_dense_cache says: -1 by free memory, 0 per call, 1 and 3 once, 2 per call as 0 (there is no fused kernel for 2
+ * to select).  Every mode computes the bits of a bf16 model loaded with the dequantised weights.  fmi_flux_get_tensor and fmi_flux_lora_add on
+ * a Linear resident as blocks, fmi_flux_quantize_fp8 / _int8 / fmi_flux_calibrate_int8 and fmi_flux_state_export on such a model return
+ * FMI_ERR_UNSUPPORTED, as for nf4.  fmi_flux_size_in_bytes counts the blocks.
+ * Not verified: no file written by ggml itself was available — conformance rests on the reference's to_float code and on literal known answers; the
+ * FLUX.1-dev-size model was run and timed on generated blocks (profiles/gguf.txt), its values were checked at the small test configuration only; one
+ * expansion past 2^31 weights is checked at the op level on a periodic input, none inside the model (the modulation matrix arrives as 77 Linears of at
+ * most 5.7e7 weights each). */
+int fmi_flux_set_linear_gguf(fmi_flux*, const char* prefix, int ggml_type, const void* data, int out_features, int in_features);
 
 /* Read back the CURRENT value of any tensor fmi_flux_set_tensor accepts (same names, same shapes; `shape` / `rank` are checked): the row range of
  * the fused matrix it lives in, bf16 converted exactly to `dtype` F32 or BF16.  `out` may be a host or device pointer.  Synchronises the device.
