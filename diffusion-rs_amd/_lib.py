@@ -67,6 +67,12 @@ class FluxControlNet(C.Structure):
     _fields_ = [("net", C.c_void_p), ("cond", C.c_void_p), ("cond_dtype", C.c_int), ("scale", C.c_float), ("step_scales", C.POINTER(C.c_float))]
 
 
+class FluxIp(C.Structure):
+    """fmi_flux_ip: the IP-Adapter of fmi_flux_forward_ip / fmi_flux_denoise_ip."""
+    _fields_ = [("adapter", C.c_void_p), ("embeds", C.c_void_p), ("embeds_dtype", C.c_int), ("neg_embeds", C.c_void_p), ("scale", C.c_float),
+                ("step_scales", C.POINTER(C.c_float))]
+
+
 class FluxDenoiseOptions(C.Structure):
     """fmi_flux_denoise_options: what fmi_flux_denoise_with's loop is conditioned on, every field NULL for none."""
     _fields_ = [("ctx", C.POINTER(FluxContext)), ("ctl", C.POINTER(FluxControl)), ("cfg", C.POINTER(FluxTrueCfg)), ("cache", C.POINTER(FluxStepCache)),
@@ -251,6 +257,19 @@ def _declare(lib):
     lib.fmi_flux_controlnet_eval.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.c_void_p, C.c_int, C.c_void_p]
     lib.fmi_flux_controlnet_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_add_scaled_rows_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p]
+    lib.fmi_ip_adapter_create.argtypes = [C.POINTER(FluxConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.fmi_ip_adapter_destroy.argtypes = [C.c_void_p]
+    lib.fmi_ip_adapter_destroy.restype = None
+    lib.fmi_ip_adapter_set_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
+    lib.fmi_ip_adapter_missing_count.argtypes = [C.c_void_p]
+    lib.fmi_ip_adapter_missing_name.argtypes = [C.c_void_p, C.c_int]
+    lib.fmi_ip_adapter_missing_name.restype = C.c_char_p
+    lib.fmi_ip_adapter_size_in_bytes.argtypes = [C.c_void_p]
+    lib.fmi_ip_adapter_size_in_bytes.restype = C.c_size_t
+    lib.fmi_flux_forward_ip.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxControl), C.POINTER(FluxControlNet), C.POINTER(FluxIp), C.c_void_p, C.c_void_p]
+    lib.fmi_flux_denoise_ip.argtypes = head + [C.POINTER(FluxDenoiseOptions), C.POINTER(FluxControlNet), C.POINTER(FluxIp)] + loop + [C.c_void_p]
+    lib.fmi_ip_attention.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                     C.c_int, C.c_void_p]
     lib.fmi_cast_cols_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_mask_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.fmi_fill_condition.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -351,6 +370,8 @@ EXPORTED = [
     "fmi_flux_set_tensor", "fmi_flux_set_linear_bnb4", "fmi_flux_set_linear_int8", "fmi_flux_set_linear_gguf", "fmi_gguf_block_info", "fmi_gguf_dequantize", "fmi_flux_get_tensor", "fmi_flux_lora_add", "fmi_flux_lora_set_weight", "fmi_flux_lora_remove", "fmi_flux_lora_count", "fmi_flux_lora_name", "fmi_flux_set_quant_dense_cache", "fmi_flux_set_sequence_parallel", "fmi_flux_set_split_k", "fmi_set_bnb4_onewave_min_rows", "fmi_flux_set_attention_rescale_threshold", "fmi_flux_set_attention_kernel", "fmi_flux_state_buffer_count", "fmi_flux_state_export", "fmi_flux_state_adopt", "fmi_flux_state_buffer", "fmi_flux_set_modulation_gemm", "fmi_flux_quantize_fp8", "fmi_flux_quantize_int8", "fmi_flux_calibrate_int8", "fmi_flux_set_fp8_attention", "fmi_flux_missing_count", "fmi_flux_missing_name", "fmi_flux_size_in_bytes",
     "fmi_flux_forward", "fmi_flux_denoise", "fmi_flux_denoise_inpaint", "fmi_flux_forward_context", "fmi_flux_denoise_context", "fmi_flux_denoise_cached", "fmi_flux_step_cache_bytes", "fmi_flux_denoise_cfg", "fmi_flux_create_cond", "fmi_flux_cond_channels", "fmi_flux_forward_control", "fmi_flux_denoise_control", "fmi_flux_denoise_with",
     "fmi_flux_create_controlnet", "fmi_flux_is_controlnet", "fmi_flux_forward_controlnet", "fmi_flux_denoise_controlnet", "fmi_flux_controlnet_eval", "fmi_flux_controlnet_sample", "fmi_add_scaled_rows_bf16",
+    "fmi_ip_adapter_create", "fmi_ip_adapter_destroy", "fmi_ip_adapter_set_tensor", "fmi_ip_adapter_missing_count", "fmi_ip_adapter_missing_name", "fmi_ip_adapter_size_in_bytes",
+    "fmi_flux_forward_ip", "fmi_flux_denoise_ip", "fmi_ip_attention",
     "fmi_flux_set_profiling", "fmi_flux_set_fused_qkv_relayout", "fmi_flux_phase_count", "fmi_flux_phase_name", "fmi_flux_phase_ms",
     "fmi_vae_default_config", "fmi_vae_create", "fmi_vae_destroy", "fmi_vae_set_tensor", "fmi_vae_missing_count", "fmi_vae_missing_name",
     "fmi_vae_scale_factor", "fmi_vae_shift_factor", "fmi_vae_decode", "fmi_vae_encode", "fmi_vae_mid_attention",

@@ -25,6 +25,7 @@
 #include <dlfcn.h>
 
 #include "common.h"
+#include "ip_adapter.h"
 
 using namespace fmi;
 
@@ -898,6 +899,12 @@ struct CnInject {
   const fmi_flux* net;
   float c;
 };
+// The IP-Adapter hook of forward_core: the adapter whose K / V (projected once per call, ip_prepare) the image queries of every double block attend to, and this
+// step's scale (never 0: such a step has no hook and keeps the fused q|k|v relayout).
+struct IpInject {
+  const fmi_ip_adapter* a;
+  float c;
+};
 
 // The ControlNet's per-shape buffers, sized by the first evaluation and regrown when a larger shape comes.
 int cn_ensure(fmi_flux* net, int B, int S, hipStream_t s) {
@@ -1041,8 +1048,10 @@ int step_cache_decide(fmi_flux* m, StepCacheRun* sc, int B, int S, int T, hipStr
 // sc: the step cache of a cached loop, else null — and with null every launch below is the one it always was.
 // inj: the ControlNet samples this evaluation adds to its f32 stream, else null — likewise.  On a ControlNet handle (m->is_cn) the evaluation
 // instead captures those samples after every block into m->cn_samples and ends after the last block: it has no final layer, and pred is not written.
+// ipj: the IP-Adapter of this evaluation, else null — likewise.  With it the image stream's q|k|v projection of every double block takes the plain
+// bf16 epilogue (the fused relayout keeps only the rotated q) and the block ends with x_img += c * ip(raw q), before the ControlNet's injection.
 int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, const float* img_f32, const float* timesteps_dev, float* pred, const float* mod_pre,
-                 const float* txt_pre, StepCacheRun* sc, const CnInject* inj, hipStream_t s) {
+                 const float* txt_pre, StepCacheRun* sc, const CnInject* inj, const IpInject* ipj, hipStream_t s) {
   auto& w = m->ws;
   const fmi_flux_config& c = m->cfg;
   const int B = in->B, Bs = p.Bs, R = p.R, Ss = in->S, S = Ss + R, T = in->T, L = S + T;  // Ss: the state's rows, S: the image stream's
@@ -1081,6 +1090,14 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
     const int k = i / ((n_main + n_net - 1) / n_net);
     PhaseTimer pt(m, s, PH_EMBED);
     return launch_add_scaled_rows_bf16(rows, bs, inj->net->cn_samples.as<bf16_t>() + ((single ? inj->net->cn_dbl.size() : 0) + k) * inj->net->cn_elems, B, S, D, inj->c, s);
+  };
+  // The IP-Adapter hook, at the end of double block i and before the ControlNet's: the image-prompt attention of the block's own raw queries — the q third of
+  // qkv_img, which nothing has overwritten since the block's q|k|v GEMM — added to the image stream, one launch (ip_adapter.hip).
+  const auto ip_hook = [&](int i) -> int {
+    if (!ipj) return FMI_OK;
+    PhaseTimer pt(m, s, PH_ATTN);
+    return launch_ip_attention(w.qkv_img, 3 * D, (int64_t)S * 3 * D, m->dbl[i].nq[0], ipj->a->k_of(i), ipj->a->v_of(i), w.x_img, (int64_t)S * D, B, H, S, ipj->a->N, ipj->c,
+                               0, s);
   };
   {
     PhaseTimer pt(m, s, PH_EMBED);
@@ -1155,7 +1172,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       // fp8 attention operands only when BOTH streams take the fused epilogue (the stand-alone kernels write bf16)
       qk8 = ((q_qkv && m->fp8_attn) || (qk8_any && !bw.qkv[0].q_type && !bw.qkv[1].q_type)) && can_fuse_relayout(m, B * S, S, T) && can_fuse_relayout(m, B * T, T, 0);  // (either 8-bit mode; opt-in: any)
       const float q8 = qk8 ? m->q8_dbl[i] : 0.f, k8 = qk8 ? m->k8_dbl[i] : 0.f;
-      fused_img = with_qkv_relayout(m, p[0], bw.nq[0], bw.nk[0], pe_bs, S, T, L, q8, k8);
+      fused_img = !ipj && with_qkv_relayout(m, p[0], bw.nq[0], bw.nk[0], pe_bs, S, T, L, q8, k8);  // (an adapter reads the raw q from qkv_img at the block's end)
       fused_txt = with_qkv_relayout(m, p[1], bw.nq[1], bw.nk[1], pe_bs, T, 0, L, q8, k8);
       Dense* dn[2] = {&bw.qkv[0], &bw.qkv[1]};
       FMI_TRY(gemm2(m, p, dn, 2, s));
@@ -1207,6 +1224,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       }
       FMI_HIP_TRY(hipEventRecord(m->ev_join, m->side));
       FMI_HIP_TRY(hipStreamWaitEvent(s, m->ev_join, 0));
+      FMI_TRY(ip_hook(i));
       FMI_TRY(cn_hook(false, i, w.x_img, (int64_t)S * D));  // (behind the join: the image chain ran on s, and the hook's launches are ordered after both chains)
       continue;
     }
@@ -1270,6 +1288,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       Dense* dn2[2] = {&bw.mlp2[0], &bw.mlp2[1]};
       FMI_TRY(gemm2(m, p, dn2, 2, s));
     }
+    FMI_TRY(ip_hook(i));
     FMI_TRY(cn_hook(false, i, w.x_img, (int64_t)S * D));
   }
 
@@ -1367,7 +1386,8 @@ int check_inputs(fmi_flux* m, const fmi_flux_inputs* in) {
 // Every refusal of a forward or denoise call — of its arguments, each option and each combination (the table at fmi_flux_denoise_with) — in the one place, before the call's
 // stream is used or anything is launched or allocated for it (check_inputs makes the handle's device current and completes a freshly loaded model: the model's state, not the
 // call's).  *p: the accepted call's plan.  A forward is n_steps == 1 with ctx / ctl only.  bad_io: the entry's message when a pointer outside `in` and `o` is unusable, else null.
-int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, int n_steps, const char* bad_io, EvalPlan* p) {
+int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip, int n_steps, const char* bad_io,
+             EvalPlan* p) {
   if (m && m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "flux: a ControlNet handle is evaluated through the main model (fmi_flux_forward_controlnet / fmi_flux_denoise_controlnet) or fmi_flux_controlnet_eval");
   if ((o.x0 || o.noise || o.mask) && !(o.x0 && o.noise && o.mask)) return fail(FMI_ERR_INVALID, "flux_denoise: x0, noise and mask go together (all three or none)");
   FMI_TRY(check_inputs(m, in));
@@ -1433,6 +1453,24 @@ int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_opti
     FMI_TRY(net->missing.ready("flux controlnet"));
     FMI_TRY(finalize(net));
     p->cn = cn;
+  }
+  if (ip) {  // one IP-Adapter; a CLIP vision encoder, several adapters at once and image prompts in the single blocks are out of scope
+    const fmi_ip_adapter* a = ip->adapter;
+    if (!a) return fail(FMI_ERR_INVALID, "flux: ip->adapter is NULL (fmi_ip_adapter_create)");
+    if (!ip->embeds) return fail(FMI_ERR_INVALID, "flux: an IP-Adapter needs embeds, the image embeddings (B,embed_dim)");
+    if (!f32_or_bf16(ip->embeds_dtype)) return fail(FMI_ERR_INVALID, "flux: the IP-Adapter's embeds_dtype must be F32 or BF16");
+    if (!std::isfinite(ip->scale)) return fail(FMI_ERR_INVALID, "flux: the IP-Adapter scale must be finite");
+    for (int i = 0; ip->step_scales && i < n_steps; ++i)
+      if (!std::isfinite(ip->step_scales[i])) return fail(FMI_ERR_INVALID, "flux_denoise: every entry of the IP-Adapter's step_scales must be finite");
+    if (a->D != m->D || a->J != m->cfg.joint_attention_dim || a->nd != m->cfg.num_layers)
+      return fail(FMI_ERR_INVALID, "flux: the IP-Adapter's width, joint_attention_dim and number of double blocks must be the main model's");
+    if (a->device != m->device) return fail(FMI_ERR_INVALID, "flux: the IP-Adapter lives on another device than the main model");
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: an IP-Adapter is not combined with a context (reference rows)");
+    if (o.cache) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: an IP-Adapter is not combined with the step cache");
+    if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux: an IP-Adapter is not supported under sequence parallelism");
+    if (m->fp8) return fail(FMI_ERR_UNSUPPORTED, std::string("flux: an IP-Adapter is not supported in the ") + (m->q8_kind == 2 ? "int8" : "fp8") + " mode (it reads the bf16 q of the q|k|v projection)");
+    if (m->fp8_attn == 2) return fail(FMI_ERR_UNSUPPORTED, "flux: an IP-Adapter is not supported with fp8 attention operands in every mode (fmi_flux_set_fp8_attention(m, 2))");
+    FMI_TRY(a->missing.ready("flux ip_adapter"));
   }
   return FMI_OK;
 }
@@ -1802,37 +1840,48 @@ static int cn_prepare(fmi_flux* net, const fmi_flux_inputs* in, const EvalPlan& 
   return cn_embed_cond(net, p.cn->cond, p.cn->cond_dtype, in->B, p.Bs, in->S, s);
 }
 
-static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, const fmi_flux_controlnet* cn, float* pred_out,
-                        void* stream) {
+static int forward_eval(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_control* ctl, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip,
+                        float* pred_out, void* stream) {
   const fmi_flux_denoise_options o{ctx, ctl};  // (every other field null)
   EvalPlan p;
   fmi_flux_controlnet one;  // a single evaluation ignores step_scales
   if (cn) one = *cn, one.step_scales = nullptr, cn = &one;
-  FMI_TRY(validate(m, in, o, cn, 1, in && in->img && in->timesteps && pred_out ? nullptr : "flux_forward: null img/timesteps/pred_out", &p));
+  fmi_flux_ip one_ip;
+  if (ip) one_ip = *ip, one_ip.step_scales = nullptr, ip = &one_ip;
+  FMI_TRY(validate(m, in, o, cn, ip, 1, in && in->img && in->timesteps && pred_out ? nullptr : "flux_forward: null img/timesteps/pred_out", &p));
   hipStream_t s = (hipStream_t)stream;
   FMI_TRY(ensure_workspace(m, in->B, in->S + p.R, in->T));
   FMI_TRY(prepare_static(m, in, p, s));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, m->ws.img_f32, (int64_t)in->B * in->S * m->cfg.in_channels, s));
+  IpInject ipj{ip ? ip->adapter : nullptr, ip ? ip->scale : 0.f};
+  const IpInject* ipp = ip && ip->scale != 0.f ? &ipj : nullptr;  // (scale 0: the plain evaluation, launch for launch)
+  if (ipp) FMI_TRY(ip_prepare(ip->adapter, ip->embeds, nullptr, ip->embeds_dtype, in->B, false, s));
   if (cn && cn->scale != 0.f) {  // (scale 0: the plain evaluation, launch for launch)
     fmi_flux* net = cn->net;
     FMI_TRY(cn_prepare(net, in, p, s));
-    FMI_TRY(forward_core(net, in, cn_plan(p), m->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+    FMI_TRY(forward_core(net, in, cn_plan(p), m->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
     const CnInject inj{net, cn->scale};
-    return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, &inj, s);
+    return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, &inj, ipp, s);
   }
-  return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, /*inj*/ nullptr, s);
+  return forward_core(m, in, p, m->ws.img_f32, in->timesteps, pred_out, /*mod_pre*/ nullptr, /*txt_pre*/ nullptr, /*sc*/ nullptr, /*inj*/ nullptr, ipp, s);
 }
 // One evaluation over cat([img, ctx], 1); pred_out is the img rows' (DESIGN.md 4.9).  No context: fmi_flux_forward.
 extern "C" int fmi_flux_forward_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* pred_out, void* stream) {
-  return forward_eval(m, in, ctx, nullptr, nullptr, pred_out, stream);
+  return forward_eval(m, in, ctx, nullptr, nullptr, nullptr, pred_out, stream);
 }
 // One evaluation over cat([img, cond], 2) of a channel-conditioned model; pred_out is (B,S,in_channels).  A plain model with ctl NULL: fmi_flux_forward.
 extern "C" int fmi_flux_forward_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, float* pred_out, void* stream) {
-  return forward_eval(m, in, nullptr, ctl, nullptr, pred_out, stream);
+  return forward_eval(m, in, nullptr, ctl, nullptr, nullptr, pred_out, stream);
 }
 // One evaluation with a ControlNet's residuals injected after every block.  cn NULL: fmi_flux_forward.
 extern "C" int fmi_flux_forward_controlnet(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_controlnet* cn, float* pred_out, void* stream) {
-  return forward_eval(m, in, nullptr, nullptr, cn, pred_out, stream);
+  return forward_eval(m, in, nullptr, nullptr, cn, nullptr, pred_out, stream);
+}
+// One evaluation with an IP-Adapter's image-prompt attention in every double block, and a ControlNet's residuals if cn is given.  ip NULL:
+// fmi_flux_forward_controlnet.  A model with conditioning channels takes its control through ctl (NULL on any other model).
+extern "C" int fmi_flux_forward_ip(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip, float* pred_out,
+                                   void* stream) {
+  return forward_eval(m, in, nullptr, ctl, cn, ip, pred_out, stream);
 }
 extern "C" int fmi_flux_forward(fmi_flux* m, const fmi_flux_inputs* in, float* pred_out, void* stream) {
   return fmi_flux_forward_context(m, in, nullptr, pred_out, stream);
@@ -1918,20 +1967,27 @@ struct CnRun {
   const float *mod_steps, *txt_pre;
   std::vector<float> c;  // scale * step_scales[i]; a step whose c is 0 launches neither the ControlNet nor an injection: it is the plain step
 };
+// The IP-Adapter of one loop: the adapter (its K / V projected once, before the first step) and each step's scale; a step whose c is 0 is the plain step.
+struct IpRun {
+  const fmi_ip_adapter* a;
+  std::vector<float> c;
+};
 static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, float* img_inout, const double* timesteps_host, int n_steps, const float* mod_steps,
-                     const float* txt_pre, StepCacheRun* sc, const CnRun* cn, hipStream_t s) {
+                     const float* txt_pre, StepCacheRun* sc, const CnRun* cn, const IpRun* ip, hipStream_t s) {
   const fmi_flux_denoise_options& o = p.o;
   const size_t B = in->B, nmod = m->n_mod;
   const int64_t n = (int64_t)p.Bs * in->S * m->cfg.in_channels;
   for (int i = 0; i < n_steps; ++i) {
     CnInject inj{};
+    const IpInject ipj{ip && ip->c[i] != 0.f ? ip->a : nullptr, ip ? ip->c[i] : 0.f};
     if (cn && cn->c[i] != 0.f) {  // the ControlNet on the step's state, then the main model with its samples
       fmi_flux* net = cn->net;
       FMI_TRY(forward_core(net, in, cn_plan(p), img_inout, net->ws.tv + i * B, nullptr, cn->mod_steps ? cn->mod_steps + i * B * (size_t)net->n_mod : nullptr, cn->txt_pre,
-                           nullptr, nullptr, s));
+                           nullptr, nullptr, nullptr, s));
       inj = CnInject{net, cn->c[i]};
     }
-    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, inj.net ? &inj : nullptr, s));
+    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, inj.net ? &inj : nullptr,
+                         ipj.a ? &ipj : nullptr, s));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
     const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
     if (o.cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
@@ -1948,10 +2004,10 @@ static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, 
 // known to few places: the blend to the update alone; the context and the control to the input assembly (prepare_static writes the context's rows and the conditioning's columns
 // of the img_in operand once, forward_core the state's every step); the negative prompt to the input assembly and the update — `in` below is then the loop's own batch of
 // 2 * Bs samples, the prompt's rows, then the negative's —; the step cache to forward_core after double block 0.
-static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, float* img_inout,
-                        const double* timesteps_host, int n_steps, void* stream) {
+static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip,
+                        float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
   EvalPlan p;
-  FMI_TRY(validate(m, in_caller, o, cn, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
+  FMI_TRY(validate(m, in_caller, o, cn, ip, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
   hipStream_t s = (hipStream_t)stream;
   fmi_flux_inputs in = *in_caller;
   if (o.cfg) in.B = 2 * p.Bs;
@@ -1977,42 +2033,55 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
     FMI_TRY(cn_prepare(cr.net, &in, p, s));
     FMI_TRY(hoist_steps(cr.net, &in, timesteps_host, n_steps, s, &cr.mod_steps, &cr.txt_pre));
   }
-  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, cn_active ? &cr : nullptr, s);
+  IpRun ir{ip ? ip->adapter : nullptr, {}};
+  bool ip_active = false;  // likewise: an adapter whose every step has scale 0 projects nothing, and every step keeps the fused q|k|v relayout
+  for (int i = 0; ip && i < n_steps; ++i) {
+    ir.c.push_back(ip->step_scales ? ip->scale * ip->step_scales[i] : ip->scale);
+    ip_active = ip_active || ir.c.back() != 0.f;
+  }
+  // the adapter's once-per-call work: tok and every block's K / V, for the prompt's embeds and — under true CFG — the negative's (zeros without neg_embeds)
+  if (ip_active) FMI_TRY(ip_prepare(ip->adapter, ip->embeds, ip->neg_embeds, ip->embeds_dtype, p.Bs, o.cfg != nullptr, s));
+  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, cn_active ? &cr : nullptr, ip_active ? &ir : nullptr, s);
 }
 
 extern "C" int fmi_flux_denoise_with(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
-  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 // The same loop with a ControlNet; cn NULL IS fmi_flux_denoise_with.
 extern "C" int fmi_flux_denoise_controlnet(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, const fmi_flux_controlnet* cn, float* img_inout,
                                            const double* timesteps_host, int n_steps, void* stream) {
-  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, nullptr, img_inout, timesteps_host, n_steps, stream);
+}
+// The same loop with an IP-Adapter, and a ControlNet if cn is given; ip NULL IS fmi_flux_denoise_controlnet.
+extern "C" int fmi_flux_denoise_ip(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip,
+                                   float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, ip, img_inout, timesteps_host, n_steps, stream);
 }
 
 // The entries from before fmi_flux_denoise_with: each fills the options its arguments name — {ctx, ctl, cfg, cache, x0, noise, mask} — and takes the same path.
 extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
-  return denoise_loop(m, in, fmi_flux_denoise_options{}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, fmi_flux_denoise_options{}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_inpaint(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, const float* x0,
                                         const float* noise, const float* mask, void* stream) {
   if (!x0 || !noise || !mask) return fail(FMI_ERR_INVALID, "flux_denoise_inpaint: x0, noise and mask are all required");
-  return denoise_loop(m, in, {/*ctx*/ nullptr, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_context(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                         int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, /*cache*/ nullptr, x0, noise, mask}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_cached(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, float* img_inout, const double* timesteps_host,
                                        int n_steps, const float* x0, const float* noise, const float* mask, const fmi_flux_step_cache* cache, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, cache, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, /*cfg*/ nullptr, cache, x0, noise, mask}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_cfg(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_context* ctx, const fmi_flux_true_cfg* cfg, float* img_inout,
                                     const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {ctx, /*ctl*/ nullptr, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 extern "C" int fmi_flux_denoise_control(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_true_cfg* cfg, float* img_inout,
                                         const double* timesteps_host, int n_steps, const float* x0, const float* noise, const float* mask, void* stream) {
-  return denoise_loop(m, in, {/*ctx*/ nullptr, ctl, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, img_inout, timesteps_host, n_steps, stream);
+  return denoise_loop(m, in, {/*ctx*/ nullptr, ctl, cfg, /*cache*/ nullptr, x0, noise, mask}, nullptr, nullptr, img_inout, timesteps_host, n_steps, stream);
 }
 // device bytes the step cache holds (0 until the first fmi_flux_denoise_cached call with a cache)
 extern "C" size_t fmi_flux_step_cache_bytes(fmi_flux* m) {
@@ -2544,7 +2613,7 @@ extern "C" int fmi_flux_controlnet_eval(fmi_flux* net, const fmi_flux_inputs* in
   EvalPlan p{fmi_flux_denoise_options{}, 0, in->B, &cn};
   FMI_TRY(cn_prepare(net, in, p, s));
   FMI_TRY(launch_cast_to_f32(in->img, in->img_dtype, net->ws.img_f32, (int64_t)in->B * in->S * net->cfg.in_channels, s));
-  return forward_core(net, in, cn_plan(p), net->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+  return forward_core(net, in, cn_plan(p), net->ws.img_f32, in->timesteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
 }
 // Sample `index` of the double (single == 0) or single blocks of the last evaluation, widened exactly: out_f32 (B,S,D) device.  Synchronises the device.
 extern "C" int fmi_flux_controlnet_sample(fmi_flux* net, int single, int index, float* out_f32) {

@@ -217,6 +217,57 @@ def check_controlnet_args(cfg: dict, net_cfg=None, img_shape=None, cond_shape=No
     return np.ascontiguousarray(ss)
 
 
+IP_MAX_TOKENS = 32  # fmi_ip_attention's 1 <= N <= 32
+
+
+def check_ip_adapter_args(cfg: dict, adapter=None, img_shape=None, embeds_shape=None, negative_embeds_shape=None, scale=1.0, step_scales=None, n_steps=None,
+                          has_context: bool = False, cache_args: bool = False, sequence_parallel: bool = False, eight_bit=None, has_negative: bool = False):
+    """The IP-Adapter of FluxModel.forward / denoise (fmi_flux_forward_ip / fmi_flux_denoise_ip), checked without the library.  cfg is the main model's
+    config; adapter is None (no adapter) or a dict(num_heads=, joint_attention_dim=, num_layers=, embed_dim=, num_tokens=) — FluxIPAdapter.dims.  Returns step_scales
+    as a float32 array of n_steps entries, or None.  ValueError: embeddings, a scale or step scales without ip_adapter= or an adapter without embeddings; an adapter
+    whose width, joint_attention_dim or number of double blocks differ from the model's; embeds that are not (B, embed_dim) for img (B,S,C); negative embeddings of
+    another shape or without a negative prompt; a scale or step scale that is not finite; step_scales not n_steps entries; an adapter with context= (reference rows),
+    the step cache's arguments, sequence parallelism or an 8-bit mode (eight_bit: "fp8" / "int8")."""
+    if adapter is None:
+        for v, nm in ((embeds_shape, "ip_adapter_image_embeds="), (negative_embeds_shape, "negative_ip_adapter_image_embeds="), (step_scales, "ip_adapter_step_scales=")):
+            if v is not None:
+                raise ValueError(f"{nm} needs ip_adapter=")
+        return None
+    if embeds_shape is None:
+        raise ValueError("ip_adapter= needs ip_adapter_image_embeds=, the image embeddings (B, embed_dim)")
+    for k, mk in (("num_heads", "num_attention_heads"), ("joint_attention_dim", "joint_attention_dim"), ("num_layers", "num_layers")):
+        if int(adapter[k]) != int(cfg[mk]):
+            raise ValueError(f"the IP-Adapter's {k} is {adapter[k]!r}, the main model's {mk} {cfg[mk]!r}")
+    if not 1 <= int(adapter["num_tokens"]) <= IP_MAX_TOKENS:
+        raise ValueError(f"the IP-Adapter's num_tokens is {adapter['num_tokens']}: 1 <= N <= {IP_MAX_TOKENS} is supported")
+    want = (int(img_shape[0]), int(adapter["embed_dim"]))
+    if tuple(embeds_shape) != want:
+        raise ValueError(f"ip_adapter_image_embeds is {tuple(embeds_shape)}, expected {want} for img {tuple(img_shape)}")
+    if negative_embeds_shape is not None:
+        if not has_negative:
+            raise ValueError("negative_ip_adapter_image_embeds= needs a negative prompt (negative_txt= / negative_y=)")
+        if tuple(negative_embeds_shape) != want:
+            raise ValueError(f"negative_ip_adapter_image_embeds is {tuple(negative_embeds_shape)}, expected {want}")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"ip_adapter_scale must be finite, got {scale!r}")
+    if has_context:
+        raise ValueError("an IP-Adapter is not combined with context= (a reference image's rows)")
+    if cache_args:
+        raise ValueError("an IP-Adapter is not combined with the step cache (cache_threshold= / cache_force=)")
+    if sequence_parallel:
+        raise ValueError("an IP-Adapter is not supported under sequence parallelism")
+    if eight_bit:
+        raise ValueError(f"an IP-Adapter is not supported in the {eight_bit} mode (it reads the bf16 q of the q|k|v projection)")
+    if step_scales is None:
+        return None
+    ss = np.asarray(step_scales, np.float32)
+    if ss.ndim != 1 or (n_steps is not None and ss.shape[0] != n_steps):
+        raise ValueError(f"ip_adapter_step_scales must have one entry per step ({n_steps}), got shape {ss.shape}")
+    if not np.isfinite(ss).all():
+        raise ValueError("ip_adapter_step_scales entries must be finite")
+    return np.ascontiguousarray(ss)
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
@@ -349,6 +400,7 @@ class FluxModel:
         """Switch the DiT block linears to the fp8 (OCP e4m3) MFMA path: weights quantised once per output
         channel from the loaded bf16 values, activations per token on the fly (BASELINE configs[4])."""
         L.check(self.lib.fmi_flux_quantize_fp8(self.h, stream), self.lib)
+        self._eight_bit = "fp8"
 
     def quantize_int8(self, mask: int = None, stream=None):
         """Switch the DiT block linears named by `mask` (Q8_* bits; default INT8_DEFAULT_MASK) to the int8 MFMA path: symmetric per-row
@@ -357,6 +409,7 @@ class FluxModel:
         on) the blocks whose q|k|v linear is in the mask hand q and k to the attention as e4m3 with static scales (QK^T on the fp8
         MFMA; P.V stays bf16).  set_fp8_attention(0) keeps bf16 operands."""
         L.check(self.lib.fmi_flux_quantize_int8(self.h, INT8_DEFAULT_MASK if mask is None else int(mask), stream), self.lib)
+        self._eight_bit = "int8"
 
     def calibrate_int8(self, on: bool = True):
         """Start (or drop) the calibration of the smoothed int8 recipe: while on, every forward / denoise evaluation (bf16 mode) also records the per-channel
@@ -512,20 +565,48 @@ class FluxModel:
         return L.FluxControlNet(controlnet.h, _ptr(keep[0]), _TORCH_DT[controlnet_cond.dtype], float(scale),
                                 ss.ctypes.data_as(C.POINTER(C.c_float)) if ss is not None else None), keep
 
+    def _ip(self, img, ip_adapter, embeds, negative_embeds, scale, step_scales, n_steps, has_ctx, cache_args, has_negative):
+        """fmi_flux_ip for ip_adapter= / ip_adapter_image_embeds=, with what it points into; (None, None) without an adapter."""
+        if ip_adapter is not None and not isinstance(ip_adapter, FluxIPAdapter):
+            raise TypeError("ip_adapter= must be a FluxIPAdapter")
+        ss = check_ip_adapter_args(self.cfg, None if ip_adapter is None else ip_adapter.dims, tuple(img.shape), None if embeds is None else tuple(embeds.shape),
+                                   None if negative_embeds is None else tuple(negative_embeds.shape), scale, step_scales, n_steps, has_ctx, cache_args,
+                                   getattr(self, "_sp_world", 1) > 1, getattr(self, "_eight_bit", None), has_negative)
+        if ip_adapter is None:
+            return None, None
+        for t, nm in ((embeds, "ip_adapter_image_embeds"), (negative_embeds, "negative_ip_adapter_image_embeds")):
+            if t is None:
+                continue
+            if t.dtype not in (torch.float32, torch.bfloat16) or t.dtype != embeds.dtype:
+                raise TypeError(f"{nm} must be float32 or bfloat16 (both of one dtype)")
+            if t.device != img.device:
+                raise ValueError(f"{nm} is on {t.device}, img on {img.device}")
+        keep = [embeds.contiguous(), None if negative_embeds is None else negative_embeds.contiguous(), ss]
+        return L.FluxIp(ip_adapter.h, _ptr(keep[0]), _TORCH_DT[embeds.dtype], _ptr(keep[1]), float(scale),
+                        ss.ctypes.data_as(C.POINTER(C.c_float)) if ss is not None else None), keep
+
     def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None, control=None, controlnet=None, controlnet_cond=None,
-                controlnet_scale=1.0):
+                controlnet_scale=1.0, ip_adapter=None, ip_adapter_image_embeds=None, ip_adapter_scale=1.0):
         """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.
         context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's.
         control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_forward_control): the
         evaluation is Flux::forward on cat([img, control], 2) and the velocity stays img's width.  Required on such a model, refused on any other.
         controlnet= / controlnet_cond= / controlnet_scale=: a FluxControlNetModel evaluated on the same inputs and controlnet_cond (B,S,in_channels) f32 | bf16, the
         packed latents of the control image; its per-block samples, times the scale, are added to this model's stream after every block
-        (fmi_flux_forward_controlnet).  Not with context=, control= or sequence parallelism."""
+        (fmi_flux_forward_controlnet).  Not with context=, control= or sequence parallelism.
+        ip_adapter= / ip_adapter_image_embeds= / ip_adapter_scale=: a FluxIPAdapter and one image embedding (B, embed_dim) f32 | bf16 per sample; every double block
+        adds scale * softmax(q K^T / sqrt(128)) V of its un-rotated, RMS-normed image queries against the adapter's tokens to the image stream
+        (fmi_flux_forward_ip).  Works with control= and controlnet=; not with context=, sequence parallelism or the 8-bit modes."""
         cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, None, None, context is not None or context_ids is not None, False)
+        ip, keep_ip = self._ip(img, ip_adapter, ip_adapter_image_embeds, None, ip_adapter_scale, None, None, context is not None or context_ids is not None, False, False)
         check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
                            False, getattr(self, "_sp_world", 1) > 1)
         inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
         pred = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        if ip is not None:
+            ctl, keep_ctl = self._control(img, control) if control is not None else (None, None)
+            L.check(self.lib.fmi_flux_forward_ip(self.h, C.byref(inp), ctl and C.byref(ctl), cn and C.byref(cn), C.byref(ip), _ptr(pred), _stream()), self.lib)
+            return pred
         if cn is not None:
             L.check(self.lib.fmi_flux_forward_controlnet(self.h, C.byref(inp), C.byref(cn), _ptr(pred), _stream()), self.lib)
             return pred
@@ -542,7 +623,8 @@ class FluxModel:
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
                 cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None,
-                controlnet=None, controlnet_cond=None, controlnet_scale=1.0, controlnet_step_scales=None):
+                controlnet=None, controlnet_cond=None, controlnet_scale=1.0, controlnet_step_scales=None, ip_adapter=None, ip_adapter_image_embeds=None,
+                negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0, ip_adapter_step_scales=None):
         """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_with call: the keywords fill its options.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
@@ -563,8 +645,17 @@ class FluxModel:
         controlnet= / controlnet_cond= / controlnet_scale= / controlnet_step_scales=: a FluxControlNetModel (fmi_flux_denoise_controlnet).  Step i
         evaluates it on the step's state and controlnet_cond (B,S,in_channels) f32 | bf16 and adds its samples at controlnet_scale * controlnet_step_scales[i] (one
         entry per step; None: 1 everywhere); a step whose scale is 0 is the plain step.  Works with x0 / noise / mask and with the negative (which the ControlNet
-        then sees as well); not with context=, control=, the step cache or sequence parallelism."""
+        then sees as well); not with context=, control=, the step cache or sequence parallelism.
+        ip_adapter= / ip_adapter_image_embeds= / negative_ip_adapter_image_embeds= / ip_adapter_scale= / ip_adapter_step_scales=: a FluxIPAdapter
+        (fmi_flux_denoise_ip) and one image embedding (B, embed_dim) f32 | bf16 per sample.  The adapter's tokens and every block's K / V are
+        projected once per call; every double block of step i adds ip_adapter_scale * ip_adapter_step_scales[i] times the image-prompt attention to the image
+        stream, and a step whose scale is 0 is the plain step.  Under true CFG the negative half attends to negative_ip_adapter_image_embeds, or to zero
+        embeddings through the same projection.  Works with the negative, x0 / noise / mask, control= and controlnet=; not with context=, the step cache,
+        sequence parallelism or the 8-bit modes."""
         n_steps = len(timesteps) - 1
+        ip, keep_ip = self._ip(img, ip_adapter, ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_step_scales, n_steps,
+                               context is not None or context_ids is not None, cache_threshold is not None or cache_force is not None,
+                               negative_txt is not None or negative_y is not None)
         cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, controlnet_step_scales, n_steps, context is not None or context_ids is not None,
                                        cache_threshold is not None or cache_force is not None)
         check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
@@ -598,7 +689,9 @@ class FluxModel:
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             opts.cache = C.pointer(L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
                                                    decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float))))
-        if cn is not None:
+        if ip is not None:
+            L.check(self.lib.fmi_flux_denoise_ip(self.h, C.byref(inp), C.byref(opts), cn and C.byref(cn), C.byref(ip), _ptr(img), ts, n_steps, _stream()), self.lib)
+        elif cn is not None:
             L.check(self.lib.fmi_flux_denoise_controlnet(self.h, C.byref(inp), C.byref(opts), C.byref(cn), _ptr(img), ts, n_steps, _stream()), self.lib)
         else:
             L.check(self.lib.fmi_flux_denoise_with(self.h, C.byref(inp), C.byref(opts), _ptr(img), ts, n_steps, _stream()), self.lib)
@@ -659,6 +752,56 @@ class FluxControlNetModel(FluxModel):
                 L.check(self.lib.fmi_flux_controlnet_sample(self.h, single, i, _ptr(t)), self.lib)
                 out[-1].append(t)
         return out[0], out[1]
+
+
+class FluxIPAdapter:
+    """A FLUX IP-Adapter (XLabs flux-ip-adapter; diffusers' FluxIPAdapterMixin; fmi_ip_adapter_create) for a transformer of config cfg: the image
+    projection Linear(embed_dim -> num_tokens * joint_attention_dim) + LayerNorm, and to_k_ip / to_v_ip per double block.  Tensor names are the diffusers-converted
+    ones (synth.ip_adapter_tensor_shapes; loader.ip_adapter_key_map brings XLabs names to them).  Handed to FluxModel.forward / denoise as ip_adapter=."""
+
+    def __init__(self, cfg: dict, embed_dim: int, num_tokens: int, device: int = 0):
+        self.lib = L.load()
+        self.cfg = dict(cfg)
+        self.embed_dim, self.num_tokens = int(embed_dim), int(num_tokens)
+        self.dims = dict(num_heads=int(cfg["num_attention_heads"]), joint_attention_dim=int(cfg["joint_attention_dim"]), num_layers=int(cfg["num_layers"]),
+                         embed_dim=self.embed_dim, num_tokens=self.num_tokens)
+        L.check(self.lib.fmi_init(device), self.lib)
+        c = L.FluxConfig(state_channels(cfg), cfg["pooled_projection_dim"], cfg["joint_attention_dim"], cfg["num_attention_heads"], cfg["num_layers"],
+                         cfg["num_single_layers"], int(cfg["guidance_embeds"]), (C.c_int * 3)(*cfg["axes_dim"]), cfg["theta"])
+        h = C.c_void_p()
+        L.check(self.lib.fmi_ip_adapter_create(C.byref(c), self.embed_dim, self.num_tokens, C.byref(h)), self.lib)
+        self.h = h
+        self.device = torch.device("cuda", device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.fmi_ip_adapter_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_tensor(self, name: str, t):
+        p, dt, shape, keep = _tensor_arg(t)
+        sh = (C.c_int64 * len(shape))(*shape)
+        L.check(self.lib.fmi_ip_adapter_set_tensor(self.h, name.encode(), p, dt, sh, len(shape)), self.lib)
+
+    def missing(self) -> List[str]:
+        n = self.lib.fmi_ip_adapter_missing_count(self.h)
+        return [self.lib.fmi_ip_adapter_missing_name(self.h, i).decode() for i in range(n)]
+
+    def load_state_dict(self, tensors: dict):
+        for k, v in tensors.items():
+            self.set_tensor(k, v)
+        m = self.missing()
+        if m:
+            raise L.FmiError(f"{len(m)} IP-Adapter tensors missing, e.g. {m[:4]}")
+
+    def size_in_bytes(self) -> int:
+        return int(self.lib.fmi_ip_adapter_size_in_bytes(self.h))
 
 
 class AutoEncoderKl:
@@ -825,6 +968,25 @@ def add_scaled_rows_bf16(x, src, scale, rows=None, row0=0):
     if int(src.shape[0]) != Bn or int(src.shape[2]) != D or int(src.shape[1]) != rows or row0 < 0 or row0 + rows > Lx:
         raise ValueError(f"add_scaled_rows_bf16: src {tuple(src.shape)} does not fit rows [{row0}, {row0 + rows}) of x {tuple(x.shape)}")
     L.check(L.load().fmi_add_scaled_rows_bf16(C.c_void_p(x.data_ptr() + 4 * row0 * D), Lx * D, _ptr(src), Bn, rows, D, float(scale), _stream()))
+    return x
+
+
+def ip_attention(q, norm_q, k, v, x, scale, max_row_blocks=0):
+    """fmi_ip_attention, the IP-Adapter's image-prompt attention kernel on its own, in place on x and returning it: for every sample, row and head
+    x[b, r, h * 128 :][:128] += scale * softmax(rmsnorm(q[b, r, h]) * norm_q . k[b, h]^T / sqrt(128)) . v[b, h].  q (B,S,H,128) bfloat16, possibly a strided view
+    (the q third of a (B,S,3,H,128) projection); norm_q (128) bfloat16; k, v (B,H,N,128) bfloat16 contiguous; x (B,S,H*128) float32 whose rows are contiguous and
+    whose samples may lie further apart.  max_row_blocks: a cap on the grid's row dimension (0: the launcher's choice) — the bits do not depend on it."""
+    if q.dim() != 4 or k.dim() != 4 or x.dim() != 3 or q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16 or \
+            norm_q.dtype != torch.bfloat16 or x.dtype != torch.float32:
+        raise TypeError("ip_attention: q (B,S,H,128), norm_q (128), k / v (B,H,N,128) bfloat16 and x (B,S,H*128) float32 are required")
+    Bn, S, H, d = (int(t) for t in q.shape)
+    N = int(k.shape[2])
+    if d != 128 or tuple(k.shape) != (Bn, H, N, 128) or tuple(v.shape) != tuple(k.shape) or tuple(x.shape) != (Bn, S, H * 128) or tuple(norm_q.shape) != (128,):
+        raise ValueError(f"ip_attention: shapes q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, x {tuple(x.shape)} do not fit")
+    if not (k.is_contiguous() and v.is_contiguous() and norm_q.is_contiguous()) or q.stride(3) != 1 or q.stride(2) != 128 or x.stride(2) != 1 or x.stride(1) != H * 128:
+        raise TypeError("ip_attention: k, v, norm_q contiguous, q with unit strides inside a row and x with contiguous rows are required")
+    L.check(L.load().fmi_ip_attention(_ptr(q), int(q.stride(1)), int(q.stride(0)), _ptr(norm_q), _ptr(k), _ptr(v), _ptr(x), int(x.stride(0)), Bn, H, S, N, float(scale),
+                                      int(max_row_blocks), _stream()))
     return x
 
 

@@ -267,6 +267,70 @@ def load_controlnet(path: str):
     return cfg, sd
 
 
+def ip_adapter_key_map(name: str) -> Optional[str]:
+    """An IP-Adapter tensor's name under either naming as the diffusers-converted one this package uses, or None for a name of neither:
+      XLabs      ip_adapter_proj_model.{proj,norm}.*                    double_blocks.{i}.processor.ip_adapter_double_stream_{k,v}_proj.*
+      diffusers  image_proj.{image_embeds,norm}.*                       ip_adapter.{i}.to_{k,v}_ip.*"""
+    parts = name.split(".")
+    if parts[-1] not in ("weight", "bias"):
+        return None
+    if len(parts) == 3 and parts[0] == "ip_adapter_proj_model" and parts[1] in ("proj", "norm"):
+        return f"image_proj.{'image_embeds' if parts[1] == 'proj' else 'norm'}.{parts[2]}"
+    if len(parts) == 3 and parts[0] == "image_proj" and parts[1] in ("image_embeds", "norm"):
+        return name
+    if len(parts) == 5 and parts[0] == "double_blocks" and parts[1].isdigit() and parts[2] == "processor" and \
+            parts[3] in ("ip_adapter_double_stream_k_proj", "ip_adapter_double_stream_v_proj"):
+        return f"ip_adapter.{int(parts[1])}.to_{parts[3][-6]}_ip.{parts[4]}"
+    if len(parts) == 4 and parts[0] == "ip_adapter" and parts[1].isdigit() and parts[2] in ("to_k_ip", "to_v_ip"):
+        return f"ip_adapter.{int(parts[1])}.{parts[2]}.{parts[3]}"
+    return None
+
+
+def ip_adapter_from_tensors(cfg: dict, tensors, where: str = "ip_adapter"):
+    """(embed_dim, num_tokens, {converted name: tensor}) of an IP-Adapter's tensors under either naming, for a transformer of config cfg; N and E are read from
+    the shapes.  ValueError naming the keys: a name of neither naming; a required tensor the file lacks (the biases of to_k_ip / to_v_ip are optional); a shape
+    that does not fit cfg; an image projection whose rows are no multiple of joint_attention_dim."""
+    sd, unexpected = {}, []
+    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
+        k = ip_adapter_key_map(name)
+        if k is None:
+            unexpected.append(name)
+        else:
+            sd[k] = t
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (neither XLabs nor diffusers IP-Adapter names), e.g. {sorted(unexpected)[:3]}")
+    J = int(cfg["joint_attention_dim"])
+    pw = sd.get("image_proj.image_embeds.weight")
+    if pw is None or len(pw.shape) != 2:
+        raise ValueError(f"{where}: 1 IP-Adapter tensors missing, e.g. ['image_proj.image_embeds.weight']")
+    rows, E = int(pw.shape[0]), int(pw.shape[1])
+    if rows % J or rows == 0:
+        raise ValueError(f"{where}: image_proj.image_embeds.weight has {rows} rows, no multiple of joint_attention_dim = {J}")
+    N = rows // J
+    want = synth.ip_adapter_tensor_shapes(cfg, E, N)
+    optional = {k for k in want if k.startswith("ip_adapter.") and k.endswith(".bias")}
+    extra = sorted(k for k in sd if k not in want)
+    if extra:
+        raise ValueError(f"{where}: {len(extra)} unexpected tensors (the transformer has {cfg['num_layers']} double blocks), e.g. {extra[:3]}")
+    missing = [k for k in want if k not in sd and k not in optional]
+    if missing:
+        raise ValueError(f"{where}: {len(missing)} IP-Adapter tensors missing, e.g. {missing[:3]}")
+    for k, t in sd.items():
+        if tuple(t.shape) != tuple(want[k]):
+            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
+    return E, N, sd
+
+
+def load_ip_adapter(path: str, cfg: dict):
+    """An IP-Adapter file (.safetensors, XLabs or diffusers-converted names) for a transformer of config cfg as (embed_dim, num_tokens, {name: tensor}).  No device
+    is touched.  ValueError as ip_adapter_from_tensors'."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path}: not a file (an IP-Adapter is one .safetensors file)")
+    with open(path, "rb") as f:
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    return ip_adapter_from_tensors(cfg, dict(_safetensors_from_buffer(memoryview(mm))), os.path.basename(path))
+
+
 def load_vae(vae, tensors: Iterator[Tuple[str, torch.Tensor]]) -> int:
     want = synth.vae_tensor_shapes(vae.cfg, encoder=True)  # encoder tensors are loaded when the checkpoint has them
     n = 0

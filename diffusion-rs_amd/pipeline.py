@@ -27,7 +27,7 @@ import os
 import struct
 import threading
 import zlib
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, fields, replace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -257,6 +257,50 @@ def check_controlnet_request(loaded: bool, height: int, width: int, image_shape=
         raise ValueError("a ControlNet is not combined with a channel-conditioned checkpoint (FLUX.1 Fill / Canny / Depth)")
     if sequence_parallel:
         raise ValueError("a ControlNet is not wired through sequence parallelism: disable_sequence_parallel() first")
+
+
+@dataclass(frozen=True)
+class _IpAdapterInput:
+    """The image prompt of a request (DESIGN.md 4.17): ONE embedding per request, shared by its prompts like the negative and the controls — not a per-sample input;
+    every chunk of the request receives this same object and expands it to its rows."""
+    embeds: torch.Tensor                     # (1,E) f32, on the device
+    negative_embeds: Optional[torch.Tensor]  # (1,E) f32 or None (zeros)
+    scale: float                             # ip_adapter_scale
+    start: float                             # ip_adapter_start, a step fraction
+    end: float                               # ip_adapter_end
+    control: object = None                   # the request's control next to it: None, a _Control or a _ControlNetInput
+
+
+def check_ip_adapter_request(loaded: bool, embed_dim: int = 0, embeds_shape=None, negative_embeds_shape=None, scale: float = 1.0, start: float = 0.0, end: float = 1.0,
+                             reference: bool = False, cache_threshold: bool = False, sequence_parallel: bool = False, eight_bit=None, has_negative: bool = False):
+    """The IP-Adapter arguments of a request, checked without a device.  ValueError: ip_adapter_image_embeds= without a loaded adapter (Pipeline.load_ip_adapter);
+    negative_ip_adapter_image_embeds= without ip_adapter_image_embeds= or without a negative prompt; embeddings that are not (embed_dim,) or (1, embed_dim) — one per
+    request, shared by its prompts; a scale that is not finite; ip_adapter_start / ip_adapter_end outside 0 <= start <= end <= 1; reference=, cache_threshold=,
+    sequence parallelism or an 8-bit transformer (eight_bit: "fp8" / "int8") next to it.  A request without ip_adapter_image_embeds= is not conditioned, whatever
+    is loaded."""
+    if embeds_shape is None:
+        if negative_embeds_shape is not None:
+            raise ValueError("negative_ip_adapter_image_embeds= needs ip_adapter_image_embeds=")
+        return
+    if not loaded:
+        raise ValueError("ip_adapter_image_embeds= needs a loaded IP-Adapter: Pipeline.load_ip_adapter(path) first")
+    for shp, nm in ((embeds_shape, "ip_adapter_image_embeds"), (negative_embeds_shape, "negative_ip_adapter_image_embeds")):
+        if shp is not None and tuple(shp) not in ((embed_dim,), (1, embed_dim)):
+            raise ValueError(f"{nm} must be ({embed_dim},) or (1,{embed_dim}), one embedding per request, got {tuple(shp)}")
+    if negative_embeds_shape is not None and not has_negative:
+        raise ValueError("negative_ip_adapter_image_embeds= needs a negative prompt (true classifier-free guidance)")
+    if not np.isfinite(float(scale)):
+        raise ValueError(f"ip_adapter_scale must be finite, got {scale!r}")
+    if not (0.0 <= float(start) <= float(end) <= 1.0):
+        raise ValueError(f"ip_adapter_start / ip_adapter_end must satisfy 0 <= start <= end <= 1, got {start!r} / {end!r}")
+    if reference:
+        raise ValueError("an IP-Adapter is not combined with reference= (a context)")
+    if cache_threshold:
+        raise ValueError("an IP-Adapter is not combined with the step cache (cache_threshold=)")
+    if sequence_parallel:
+        raise ValueError("an IP-Adapter is not wired through sequence parallelism: disable_sequence_parallel() first")
+    if eight_bit:
+        raise ValueError(f"an IP-Adapter is not supported on a transformer in the {eight_bit} mode")
 
 
 def control_kind(cond_channels: int) -> Optional[str]:
@@ -524,7 +568,8 @@ class Pipeline:
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
                         negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
-                        control_guidance_start: float = 0.0, control_guidance_end: float = 1.0):
+                        control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
+                        negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -571,7 +616,17 @@ class Pipeline:
         transformer's stream at controlnet_conditioning_scale * keep_i, keep_i = 0 if i / n < control_guidance_start or (i + 1) / n > control_guidance_end else
         1; a step with scale 0 is the plain step.  Combines with the negative (the ControlNet then sees it as well) and with image= / strength= / mask=;
         raises with reference=, cache_threshold=, on a Fill / Canny / Depth checkpoint, under sequence parallelism and without a loaded ControlNet.  No
-        conditioning scale is recommended: there are no real weights here to judge one."""
+        conditioning scale is recommended: there are no real weights here to judge one.
+
+        Image prompts (`ip_adapter_image_embeds=` with an IP-Adapter loaded by load_ip_adapter; diffusers' ip_adapter_image_embeds): ONE image
+        embedding per request, (E,) or (1,E), shared by its prompts.  A CLIP vision encoder is out of scope: the embedding is supplied.  Step i of the n steps
+        actually run adds the image-prompt attention in every double block at ip_adapter_scale * keep_i, keep_i = 0 if i / n < ip_adapter_start or
+        (i + 1) / n > ip_adapter_end else 1; a step with scale 0 is the plain step.  Under a negative prompt the negative half attends to
+        negative_ip_adapter_image_embeds=, or to zero embeddings through the same projection.  Combines with the negative, image= / strength= / mask=, a Fill /
+        Canny / Depth control and a ControlNet; raises with reference=, cache_threshold=, under sequence parallelism, on an 8-bit transformer and without a loaded
+        adapter."""
+        ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end, reference,
+                                     cache_threshold, negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None)
         cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params, reference, cache_threshold)
         if cache_threshold is not None:
             F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
@@ -587,6 +642,8 @@ class Pipeline:
         # (the negative is a keyword of true-CFG requests only, the control of controlled ones: any other request makes exactly the call it always made; a request has
         # ONE control object, the channel conditioning's or the ControlNet's — the two are never combined, check_controlnet_request)
         extra = dict(**({} if neg is None else dict(negative=neg)), **({} if ctl is None and cn is None else dict(control=ctl if cn is None else cn)))
+        if ipa is not None:  # the image prompt rides on the same keyword, around whichever control the request has (it combines with both kinds)
+            extra["control"] = replace(ipa, control=extra.get("control"))
         outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **extra)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
@@ -632,6 +689,48 @@ class Pipeline:
         else:
             img = img.to(device=self.device, dtype=torch.float32).contiguous()
         return _ControlNetInput(img, float(scale), float(start), float(end))
+
+    def _ip_adapter_input(self, embeds, negative_embeds, scale, start, end, reference, cache_threshold, has_negative) -> Optional[_IpAdapterInput]:
+        """The image prompt of a request, checked once and brought to its device form: None without ip_adapter_image_embeds=, else the object its chunks share."""
+        def as_tensor(x, what):
+            t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+            if x is not None and not (isinstance(t, torch.Tensor) and t.is_floating_point()):
+                raise ValueError(f"{what} must be a float numpy array or torch tensor")
+            return t
+        e, n = as_tensor(embeds, "ip_adapter_image_embeds"), as_tensor(negative_embeds, "negative_ip_adapter_image_embeds")
+        ada = getattr(self, "ip_adapter", None)
+        flux = getattr(self, "flux", None)
+        check_ip_adapter_request(ada is not None, 0 if ada is None else ada.embed_dim, None if e is None else tuple(e.shape), None if n is None else tuple(n.shape), scale,
+                                 start, end, reference is not None, cache_threshold is not None, getattr(self, "_sp", None) is not None,
+                                 "int8" if getattr(self, "_int8_pending", False) else getattr(flux, "_eight_bit", None), has_negative)
+        if e is None:
+            return None
+        dev = lambda t: None if t is None else t.to(device=self.device, dtype=torch.float32).reshape(1, -1).contiguous()
+        return _IpAdapterInput(dev(e), dev(n), float(scale), float(start), float(end))
+
+    def load_ip_adapter(self, source):
+        """Load ONE IP-Adapter next to the transformer: a .safetensors file under XLabs' names (ip_adapter_proj_model.*, double_blocks.{i}.processor.
+        ip_adapter_double_stream_{k,v}_proj.*) or the diffusers-converted ones (image_proj.*, ip_adapter.{i}.to_{k,v}_ip.*), or a {name: tensor} dict of either.  The
+        number of tokens and the embedding width are read from the shapes; missing and unexpected keys raise ValueError by name.  It replaces a loaded one; requests
+        use it only when they pass ip_adapter_image_embeds=.  A CLIP vision encoder is not part of this package: embeddings are supplied."""
+        from . import loader
+        if isinstance(source, (str, os.PathLike)):
+            E, N, sd = loader.load_ip_adapter(os.fspath(source), self.flux.cfg)
+        else:
+            E, N, sd = loader.ip_adapter_from_tensors(self.flux.cfg, source)
+        with self._lock:
+            ada = F.FluxIPAdapter(self.flux.cfg, E, N, self.device.index or 0)
+            ada.load_state_dict(sd)
+            old, self.ip_adapter = getattr(self, "ip_adapter", None), ada
+            if old is not None:
+                old.close()
+        return ada
+
+    def unload_ip_adapter(self):
+        with self._lock:
+            ada, self.ip_adapter = getattr(self, "ip_adapter", None), None
+            if ada is not None:
+                ada.close()
 
     def load_controlnet(self, source):
         """Load ONE ControlNet next to the transformer: a diffusers directory (loader.load_controlnet: config.json with _class_name
@@ -757,7 +856,9 @@ class Pipeline:
         """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
         generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only.  control: the request's control —
         a _Control, passed by requests to a channel-conditioned model only, or a _ControlNetInput, passed by requests with
-        controlnet_image= only; a request never has both."""
+        controlnet_image= only; a request never has both.  A request with ip_adapter_image_embeds= passes its _IpAdapterInput, which carries
+        the control of either kind inside."""
+        ip, control = (control, control.control) if isinstance(control, _IpAdapterInput) else (None, control)
         controlnet, control = (control, None) if isinstance(control, _ControlNetInput) else (None, control)
         cfg = self.flux.cfg
         dev = self.device
@@ -798,6 +899,11 @@ class Pipeline:
                 cond, _ = F.encode_latents(self.vae.encode(controlnet.image), self.vae.scale_factor(), self.vae.shift_factor())
                 cn_kw = dict(controlnet=self.controlnet, controlnet_cond=cond.expand(B, -1, -1).contiguous(), controlnet_scale=controlnet.scale,
                              controlnet_step_scales=F.controlnet_step_scales(len(timesteps) - 1, controlnet.start, controlnet.end))
+            if ip is not None:  # one embedding row expanded to the chunk; the scales over the steps actually run, like the ControlNet's
+                cn_kw.update(ip_adapter=self.ip_adapter, ip_adapter_image_embeds=ip.embeds.expand(B, -1).contiguous(), ip_adapter_scale=ip.scale,
+                             ip_adapter_step_scales=F.controlnet_step_scales(len(timesteps) - 1, ip.start, ip.end))
+                if ip.negative_embeds is not None:
+                    cn_kw.update(negative_ip_adapter_image_embeds=ip.negative_embeds.expand(B, -1).contiguous())
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
@@ -895,7 +1001,8 @@ class Pipeline:
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
                 reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
                 negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
-                controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, **kw):
+                controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
+                negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
@@ -905,7 +1012,9 @@ class Pipeline:
         classifier-free guidance, see generate_tensor — one negative per request, handed to every rank of a sharded batch unchanged.  control_image= /
         control_mask=: the control of a channel-conditioned model (FLUX.1 Fill / Canny / Depth), see generate_tensor — one per request, likewise.
         controlnet_image= / controlnet_conditioning_scale= / control_guidance_start= / control_guidance_end=: the ControlNet of load_controlnet, see generate_tensor —
-        one control image per request, likewise (every rank loads the same ControlNet)."""
+        one control image per request, likewise (every rank loads the same ControlNet).
+        ip_adapter_image_embeds= / negative_ip_adapter_image_embeds= / ip_adapter_scale= / ip_adapter_start= / ip_adapter_end=: the image prompt of the IP-Adapter of
+        load_ip_adapter, see generate_tensor — one embedding per request, likewise (every rank loads the same adapter)."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -917,6 +1026,9 @@ class Pipeline:
         if controlnet_image is not None:  # (likewise)
             shared.update(controlnet_image=controlnet_image, controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
                           control_guidance_end=control_guidance_end)
+        if ip_adapter_image_embeds is not None or negative_ip_adapter_image_embeds is not None:  # (likewise)
+            shared.update(ip_adapter_image_embeds=ip_adapter_image_embeds, negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds,
+                          ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start, ip_adapter_end=ip_adapter_end)
         per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if world > 1 and getattr(self, "_sp", None) is None:

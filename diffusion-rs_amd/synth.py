@@ -157,6 +157,55 @@ def fill_controlnet_random_device(model, seed=0, w_std=0.02, mod_std=0.01, devic
     model.assert_complete()
 
 
+def ip_adapter_tensor_shapes(cfg, embed_dim, num_tokens, kv_bias=True) -> "OrderedDict[str, tuple]":
+    """A FLUX IP-Adapter under its diffusers-converted names: image_proj (Linear(E -> N * J) + LayerNorm(J)) and to_k_ip / to_v_ip (Linear(J -> D))
+    for every double block of cfg.  kv_bias=False: a file without the biases of to_k_ip / to_v_ip (they are optional)."""
+    D, J = cfg["num_attention_heads"] * sum(cfg["axes_dim"]), cfg["joint_attention_dim"]
+    t = OrderedDict()
+    t["image_proj.image_embeds.weight"], t["image_proj.image_embeds.bias"] = (num_tokens * J, embed_dim), (num_tokens * J,)
+    t["image_proj.norm.weight"], t["image_proj.norm.bias"] = (J,), (J,)
+    for i in range(cfg["num_layers"]):
+        for kv in ("to_k_ip", "to_v_ip"):
+            t[f"ip_adapter.{i}.{kv}.weight"] = (D, J)
+            if kv_bias:
+                t[f"ip_adapter.{i}.{kv}.bias"] = (D,)
+    return t
+
+
+def ip_adapter_state_dict_numpy(cfg, embed_dim, num_tokens, seed=0, proj_std=0.05, k_std=0.05, v_std=0.05, bias_std=0.02, norm_jitter=0.1, kv_bias=True, round_bf16=True):
+    """Synthetic IP-Adapter weights from a generator of their own: the projection N(0, proj_std^2), to_k_ip N(0, k_std^2), to_v_ip N(0, v_std^2), biases
+    N(0, bias_std^2), the LayerNorm weight 1 + norm_jitter * N(0, 1)."""
+    rng = np.random.default_rng([seed, 0x1A])
+    out = OrderedDict()
+    for name, shape in ip_adapter_tensor_shapes(cfg, embed_dim, num_tokens, kv_bias).items():
+        if name == "image_proj.norm.weight":
+            a = 1.0 + norm_jitter * rng.standard_normal(shape)
+        elif name.endswith(".bias"):
+            a = bias_std * rng.standard_normal(shape)
+        else:
+            a = (k_std if "to_k_ip" in name else v_std if "to_v_ip" in name else proj_std) * rng.standard_normal(shape)
+        a = a.astype(np.float32)
+        out[name] = to_bf16_f32(a) if round_bf16 else a
+    return out
+
+
+def fill_ip_adapter_random_device(adapter, seed=0, std=0.02, device="cuda"):
+    """Full-size random IP-Adapter weights generated on the GPU (measurements)."""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    for name, shape in ip_adapter_tensor_shapes(adapter.cfg, adapter.embed_dim, adapter.num_tokens).items():
+        if name == "image_proj.norm.weight":
+            t = torch.ones(shape, dtype=torch.bfloat16, device=device)
+        elif name.endswith(".bias"):
+            t = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        else:
+            t = torch.randn(shape, generator=g, device=device, dtype=torch.bfloat16)
+            t.mul_(std)
+        adapter.set_tensor(name, t)
+        del t
+
+
 def vae_tensor_shapes(cfg, encoder=False) -> "OrderedDict[str, tuple]":
     """Decoder tensors (vae.rs:371-433); with encoder=True also the encoder's (vae.rs:249-327) and quant_conv."""
     boc = list(cfg["block_out_channels"])

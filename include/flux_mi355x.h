@@ -52,6 +52,7 @@ extern "C" {
  *   fmi_flux_forward_control, fmi_flux_denoise_control, fmi_cast_cols_bf16, fmi_mask_image, fmi_fill_condition.
  *   Then, still 6: the denoise loop's options in one struct — fmi_flux_denoise_options, fmi_flux_denoise_with; the six fmi_flux_denoise* entries remain.
  *   Then, still 6: GGUF transformers (ggml block formats) — fmi_gguf_block_info, fmi_gguf_dequantize, fmi_flux_set_linear_gguf.
+ *   Then, still 6: FLUX IP-Adapters (image prompts) — fmi_ip_adapter_*, fmi_flux_ip, fmi_flux_forward_ip, fmi_flux_denoise_ip, fmi_ip_attention.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -544,6 +545,53 @@ int fmi_flux_controlnet_sample(fmi_flux* net, int single, int index, float* out_
  * and both pointers are 16-byte aligned, else scalar ones: the same bits either way.  FMI_ERR_INVALID: a null pointer, a negative size, a stride below rows * D. */
 int fmi_add_scaled_rows_bf16(float* x_f32, int64_t x_batch_stride, const void* src_bf16, int B, int64_t rows, int D, float scale, void* stream);
 
+/* FLUX IP-Adapter: image-prompt attention in the double blocks (XLabs flux-ip-adapter / -v2, diffusers' FluxIPAdapterMixin and
+ * FluxIPAdapterAttnProcessor; the reference has no counterpart).  With D = H * 128, J = joint_attention_dim, an adapter of N tokens on embeddings of width E holds
+ *   image_proj.image_embeds   Linear(E -> N * J)           image_proj.norm   LayerNorm(J, eps 1e-5, affine)
+ *   ip_adapter.{i}.to_k_ip / to_v_ip   Linear(J -> D), one pair per double block i; their biases are optional (zero unless set)
+ * Once per call:   tok = LayerNorm(Linear(embeds)).reshape(B, N, J);   K_i = to_k_ip_i(tok), V_i = to_v_ip_i(tok), viewed (B, N, H, 128) — no QkNorm, no RoPE.
+ * In double block i of every evaluation, with q = norm_q_i(to_q_i(LayerNorm-modulated image rows)) — after the block's RMSNorm, BEFORE RoPE —
+ *   ip = softmax(q K_i^T / sqrt(128)) V_i   per sample and head, over the N tokens, for every image row;   after the block: x_img += c * ip   (f32)
+ * ip does not pass the attention's output projection and is not gated; text rows and single blocks are untouched; a ControlNet's residual is added after it.
+ * Decisions of this library:
+ *   - the raw q is the bf16 the q|k|v GEMM stores; RMSNorm, scores and softmax are f32 (the normed q is not rounded to bf16); tok is f32; K_i / V_i are the f32
+ *     accumulator plus bias rounded once to bf16; ip accumulates in f32; the update is one __fmul_rn and one __fadd_rn per element, x = x + c * ip;
+ *   - while an adapter with c != 0 is attached, the image stream's q|k|v projection of the double blocks takes the plain epilogue and the stand-alone relayout
+ *     kernels (the fused relayout epilogue keeps only the rotated q); a call without an adapter, and a step whose c is 0, keeps the fused path, launch for launch;
+ *   - tok and every K_i / V_i are computed once per call into buffers the adapter owns (sized by the first call, regrown when a larger batch comes);
+ *   - under true CFG the prompt half attends to embeds, the negative half to neg_embeds or — NULL — to all-zero embeddings through the same projection (the bias
+ *     and the LayerNorm make those tokens non-zero), as diffusers does; the ControlNet's own evaluation is not image-prompted.
+ * 1 <= N <= 32 (XLabs: 4); another N is FMI_ERR_UNSUPPORTED.  E and J multiples of 8, at most 16384.  A CLIP vision encoder is out of scope: embeddings are supplied.
+ * With a fmi_flux_ip — FMI_ERR_INVALID: adapter or embeds NULL; an embeds_dtype that is not F32 / BF16; a scale or step_scales entry that is not finite; an adapter
+ * whose width, joint_attention_dim or number of double blocks differ from the model's, or that lives on another device.  FMI_ERR_UNSUPPORTED: a context (R > 0),
+ * the step cache, sequence parallelism, the fp8 / int8 modes, fmi_flux_set_fp8_attention(m, 2).  FMI_ERR_STATE: an adapter with missing tensors.  It combines
+ * with the negative, x0 / noise / mask, a control (ctl) and a ControlNet. */
+typedef struct fmi_ip_adapter fmi_ip_adapter; /* opaque */
+/* cfg: the transformer's (num_attention_heads, joint_attention_dim and num_layers are used).  The weights (bf16) are allocated here, zero-initialised. */
+int fmi_ip_adapter_create(const fmi_flux_config* cfg, int embed_dim, int num_tokens, fmi_ip_adapter** out);
+void fmi_ip_adapter_destroy(fmi_ip_adapter*);
+/* One tensor by the names above plus .weight / .bias (host or device pointer, F32 / F16 / BF16, shape checked; synchronous).  FMI_ERR_INVALID: unknown name, wrong shape. */
+int fmi_ip_adapter_set_tensor(fmi_ip_adapter*, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank);
+int fmi_ip_adapter_missing_count(const fmi_ip_adapter*);
+const char* fmi_ip_adapter_missing_name(const fmi_ip_adapter*, int i);
+size_t fmi_ip_adapter_size_in_bytes(const fmi_ip_adapter*); /* weights + the per-call projection buffers */
+typedef struct fmi_flux_ip {
+  fmi_ip_adapter* adapter;                       /* every required tensor set */
+  const void* embeds; fmi_dtype embeds_dtype;    /* (B,E) F32|BF16: one image embedding per sample */
+  const void* neg_embeds;                        /* (B,E) of embeds_dtype, or NULL (zeros): the negative half's under true CFG; ignored without a negative */
+  float scale;                                   /* finite; the adapter scale c */
+  const float* step_scales;                      /* NULL, or n_steps host floats multiplied onto scale (c_i = scale * step_scales[i], in f32); a single forward ignores it */
+} fmi_flux_ip;
+/* One evaluation with the adapter; ctl (a cond_channels > 0 model's control) and cn may be NULL.  ip NULL: fmi_flux_forward_controlnet / _control. */
+int fmi_flux_forward_ip(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_control* ctl, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip, float* pred_out, void* stream);
+/* The image-prompt attention kernel on its own (op-level; device pointers, no allocation): for b < B, r < S, h < H
+ *   x[b * x_batch_stride + r * H * 128 + h * 128 + :] += scale * ip(q[b * q_batch_stride + r * q_row_stride + h * 128 + :], norm_q, k[b, h, :, :], v[b, h, :, :])
+ * with q bf16 (the q|k|v GEMM's plain output: row stride 3 * H * 128 there), norm_q (128) bf16, k / v (B, H, N, 128) bf16, x f32, by the recipe above.  Strides in
+ * elements; every pointer 16-byte aligned, the q strides multiples of 8, x_batch_stride a multiple of 4 and >= S * H * 128.  max_row_blocks: 0, or a cap on the
+ * grid's row dimension (a test seam: the bits do not depend on it).  FMI_ERR_UNSUPPORTED: N outside [1, 32].  FMI_ERR_INVALID: everything else. */
+int fmi_ip_attention(const void* q_bf16, int q_row_stride, int64_t q_batch_stride, const void* norm_q_bf16, const void* k_bf16, const void* v_bf16, float* x_f32,
+                     int64_t x_batch_stride, int B, int H, int S, int N, float scale, int max_row_blocks, void* stream);
+
 /* The whole denoise loop == Sampler::sample(FlowMatchEulerDiscrete)
  * (pipelines/sampling.rs:25-48) around the step closure (pipelines/flux/mod.rs:305-318):
  *   for (t_curr,t_prev) in windows(timesteps): img += forward(img, t_curr) * (t_prev-t_curr)
@@ -560,6 +608,8 @@ int fmi_add_scaled_rows_bf16(float* x_f32, int64_t x_batch_stride, const void* s
  *   cache                                                        yes
  *   cn        ctx: FMI_ERR_UNSUPPORTED   ctl (a cond_channels > 0 model): FMI_ERR_UNSUPPORTED   cfg: yes   cache: FMI_ERR_UNSUPPORTED   x0/noise/mask: yes
  * (cn: the ControlNet argument of fmi_flux_denoise_controlnet below, not a field of this struct; under sequence parallelism FMI_ERR_UNSUPPORTED.)
+ *   ip        ctx: FMI_ERR_UNSUPPORTED   ctl: yes   cfg: yes   cache: FMI_ERR_UNSUPPORTED   x0/noise/mask: yes   cn: yes
+ * (ip: the IP-Adapter argument of fmi_flux_denoise_ip below; FMI_ERR_UNSUPPORTED under sequence parallelism and in the fp8 / int8 modes.)
  * Three or more combine when every pair among them does.  x0 / noise / mask given only in part: FMI_ERR_INVALID.  Each option's own refusals are listed at its
  * struct above; n_steps * B > 4096 is FMI_ERR_UNSUPPORTED.  EVERY refusal — of an argument, an option or a combination — comes before any launch, any
  * allocation and any use of `stream`: a refused call leaves img_inout, the outputs of `cache` and the model as they were. */
@@ -577,6 +627,11 @@ int fmi_flux_denoise_with(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_d
  * options struct keeps its 7 fields — and fmi_flux_denoise_with IS this call with cn == NULL: the same launches, bits, errors and allocations. */
 int fmi_flux_denoise_controlnet(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */, const fmi_flux_controlnet* cn,
                                 float* img_inout, const double* timesteps_host, int n_steps, void* stream);
+/* The same loop with an IP-Adapter (see fmi_flux_ip above), and a ControlNet if cn is not NULL: every double block of step i adds the image-prompt attention at
+ * c_i = ip->scale * step_scales[i] (ip->scale without step_scales); a step whose c_i is 0 is the plain step, launch for launch.  The projection of the embeddings
+ * runs once per call, never per step.  fmi_flux_denoise_controlnet IS this call with ip == NULL: the same launches, bits, errors and allocations. */
+int fmi_flux_denoise_ip(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */, const fmi_flux_controlnet* cn,
+                        const fmi_flux_ip* ip, float* img_inout, const double* timesteps_host, int n_steps, void* stream);
 
 /* The entries from before fmi_flux_denoise_with.  Each IS fmi_flux_denoise_with with the fields it names set from its arguments and every other field NULL —
  * the same launches, bits, errors and allocations. */
