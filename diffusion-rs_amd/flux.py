@@ -83,15 +83,54 @@ class SchedulerConfig:
         return L.load().fmi_calculate_shift(image_seq_len, self.base_image_seq_len, self.max_image_seq_len, self.base_shift, self.max_shift)
 
 
-def check_step_cache_args(n_steps: int, threshold=None, force=None, sequence_parallel: bool = False):
+# Which options of one call do not combine: the table at fmi_flux_denoise_with (include/flux_mi355x.h), which validate() enforces in the library.  Python states it
+# once, here, for FluxModel and for Pipeline; the checks below look at each option's own arguments only.  An option is present when it is given and has passed
+# its own check: "context", "control" (the model has conditioning channels), "true_cfg", "cache" (a threshold or a forced mask), "blend" (x0 / noise / mask, which
+# combines with everything), "controlnet", "ip_adapter".
+REFUSED_PAIRS = (("ip_adapter", "context"), ("ip_adapter", "cache"), ("controlnet", "context"), ("controlnet", "control"), ("controlnet", "cache"),
+                 ("control", "context"), ("control", "cache"), ("true_cfg", "cache"))
+# ... and the modes of the model an option does not run in (sequence parallelism: the step cache's distance would need an all-reduce over the ranks, the others
+# are not wired through it; the 8-bit modes: the adapter reads the bf16 q of the q|k|v projection)
+REFUSED_MODES = (("ip_adapter", "sequence_parallel"), ("ip_adapter", "fp8"), ("ip_adapter", "int8"), ("controlnet", "sequence_parallel"),
+                 ("control", "sequence_parallel"), ("true_cfg", "sequence_parallel"), ("cache", "sequence_parallel"))
+# what FluxModel.forward / denoise call each of them in a message (Pipeline has its own keywords: pipeline.REQUEST_NAMES)
+OPTION_NAMES = dict(context="context= (a reference image)", control="control= (a channel-conditioned model: FLUX.1 Fill / Canny / Depth)",
+                    true_cfg="true CFG (negative_txt= / negative_y=)", cache="the step cache (cache_threshold= / cache_force=)", controlnet="a ControlNet",
+                    ip_adapter="an IP-Adapter", sequence_parallel="supported under sequence parallelism",
+                    fp8="supported in the fp8 mode (it reads the bf16 q of the q|k|v projection)",
+                    int8="supported in the int8 mode (it reads the bf16 q of the q|k|v projection)")
+
+
+def check_combination(present, names=OPTION_NAMES):
+    """ValueError for the first row of REFUSED_PAIRS, then of REFUSED_MODES, whose two members are both in `present` (any container of the names above; the
+    modes are "sequence_parallel", "fp8", "int8").  names: what the calling layer calls each of them."""
+    for a, b in REFUSED_PAIRS:
+        if a in present and b in present:
+            raise ValueError(f"{names[a]} is not combined with {names[b]}")
+    for a, mode in REFUSED_MODES:
+        if a in present and mode in present:
+            raise ValueError(f"{names[a]} is not {names[mode]}")
+
+
+def check_step_scales(step_scales, n_steps, name: str):
+    """An option's per-step scales (`name`: its keyword) as a contiguous float32 array; None stays None.  ValueError unless 1-D, n_steps entries (None: any), finite."""
+    if step_scales is None:
+        return None
+    ss = np.asarray(step_scales, np.float32)
+    if ss.ndim != 1 or (n_steps is not None and ss.shape[0] != n_steps):
+        raise ValueError(f"{name} must have one entry per step ({n_steps}), got shape {ss.shape}")
+    if not np.isfinite(ss).all():
+        raise ValueError(f"{name} entries must be finite")
+    return np.ascontiguousarray(ss)
+
+
+def check_step_cache_args(n_steps: int, threshold=None, force=None):
     """The arguments of the first-block step cache (FluxModel.denoise / fmi_flux_denoise_cached), checked without the library.
     Returns (threshold as float, force as an int8 array of n_steps entries or None); (None, None) when neither is given: no cache, the plain loop.
     ValueError: a negative or NaN threshold; `force` not n_steps entries of -1 (decide by threshold) / 0 (compute) / 1 (reuse); force[0] == 1 (step 0 has
-    nothing to reuse); either of them under sequence parallelism (the distance would need an all-reduce over the ranks)."""
+    nothing to reuse)."""
     if threshold is None and force is None:
         return None, None
-    if sequence_parallel:
-        raise ValueError("the step cache (cache_threshold= / cache_force=) is not supported under sequence parallelism")
     thr = 0.0 if threshold is None else float(threshold)
     if not thr >= 0.0:
         raise ValueError(f"cache_threshold must be >= 0, got {threshold!r}")
@@ -107,13 +146,12 @@ def check_step_cache_args(n_steps: int, threshold=None, force=None, sequence_par
     return thr, np.ascontiguousarray(f, dtype=np.int8)
 
 
-def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_shape=None, true_cfg_scale=None, cache_args: bool = False,
-                        sequence_parallel: bool = False):
+def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_shape=None, true_cfg_scale=None):
     """The arguments of true classifier-free guidance (FluxModel.denoise / fmi_flux_denoise_cfg), checked without the library: the shapes
     of the prompt's txt (B,T,J) and y (B,P), of the negative's, and the scale.  Returns the scale as a float (1.0 when none is given), or None when no
     negative is given: the plain loop.
     ValueError: one negative without the other; a scale without a negative; shapes — and with them T — that differ from the prompt's; B > 4 (the loop
-    evaluates 2 B samples and the per-device limit is 8); a scale that is negative, NaN or infinite; the step cache's arguments; sequence parallelism."""
+    evaluates 2 B samples and the per-device limit is 8); a scale that is negative, NaN or infinite."""
     if negative_txt_shape is None and negative_y_shape is None:
         if true_cfg_scale is not None:
             raise ValueError("true_cfg_scale= needs negative_txt= and negative_y=")
@@ -129,10 +167,6 @@ def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_
     scale = 1.0 if true_cfg_scale is None else float(true_cfg_scale)
     if not (scale >= 0.0 and scale != float("inf")):
         raise ValueError(f"true_cfg_scale must be finite and >= 0, got {true_cfg_scale!r}")
-    if cache_args:
-        raise ValueError("true CFG (negative_txt= / negative_y=) is not combined with the step cache (cache_threshold= / cache_force=)")
-    if sequence_parallel:
-        raise ValueError("true CFG (negative_txt= / negative_y=) is not supported under sequence parallelism")
     return scale
 
 
@@ -142,10 +176,9 @@ def state_channels(cfg: dict) -> int:
     return int(cfg.get("out_channels") or cfg["in_channels"])
 
 
-def check_control_args(cond_channels: int, img_shape, control_shape=None, has_context: bool = False, cache_args: bool = False, sequence_parallel: bool = False):
+def check_control_args(cond_channels: int, img_shape, control_shape=None):
     """The control of FluxModel.forward / denoise (fmi_flux_forward_control / fmi_flux_denoise_control), checked without the library.
-    ValueError: a channel-conditioned model without control=; control= on a plain model; a control that is not (B,S,cond_channels) for img (B,S,C); a control
-    with context=, with the step cache's arguments, or under sequence parallelism."""
+    ValueError: a channel-conditioned model without control=; control= on a plain model; a control that is not (B,S,cond_channels) for img (B,S,C)."""
     if control_shape is None:
         if cond_channels:
             raise ValueError(f"this model has {cond_channels} conditioning channels: control= (B,S,{cond_channels}) is required")
@@ -154,12 +187,6 @@ def check_control_args(cond_channels: int, img_shape, control_shape=None, has_co
         raise ValueError("control= needs a channel-conditioned model (in_channels > out_channels: FLUX.1 Fill / Canny / Depth)")
     if tuple(control_shape) != (int(img_shape[0]), int(img_shape[1]), cond_channels):
         raise ValueError(f"control is {tuple(control_shape)}, expected {(int(img_shape[0]), int(img_shape[1]), cond_channels)} for img {tuple(img_shape)}")
-    if has_context:
-        raise ValueError("control= is not combined with context= (a reference image)")
-    if cache_args:
-        raise ValueError("control= is not combined with the step cache (cache_threshold= / cache_force=)")
-    if sequence_parallel:
-        raise ValueError("control= is not supported under sequence parallelism")
 
 
 def controlnet_index_map(n_main: int, n_net: int) -> List[int]:
@@ -176,13 +203,12 @@ def controlnet_step_scales(n_steps: int, control_guidance_start: float = 0.0, co
     return [0.0 if (i / n_steps < control_guidance_start or (i + 1) / n_steps > control_guidance_end) else 1.0 for i in range(n_steps)]
 
 
-def check_controlnet_args(cfg: dict, net_cfg=None, img_shape=None, cond_shape=None, scale=1.0, step_scales=None, n_steps=None, has_context: bool = False,
-                          cond_channels: int = 0, cache_args: bool = False, sequence_parallel: bool = False):
+def check_controlnet_args(cfg: dict, net_cfg=None, img_shape=None, cond_shape=None, scale=1.0, step_scales=None, n_steps=None):
     """The ControlNet of FluxModel.forward / denoise (fmi_flux_forward_controlnet / fmi_flux_denoise_controlnet), checked without the library; cfg is
     the main model's config, net_cfg the ControlNet's (None: no ControlNet).  Returns step_scales as a float32 array of n_steps entries, or None.
     ValueError: controlnet_cond= without controlnet= or the reverse; a net whose width-defining fields differ from the main model's; a cond that is not
-    (B,S,in_channels) for img (B,S,C); a scale or step scale that is not finite; step_scales not n_steps entries; a ControlNet with context=, on a channel-
-    conditioned model, with the step cache's arguments or under sequence parallelism.  Several ControlNets, union modes and the XLabs hint block are out of scope."""
+    (B,S,in_channels) for img (B,S,C); a scale or step scale that is not finite; step_scales not n_steps entries.  Several ControlNets, union modes and the XLabs
+    hint block are out of scope."""
     if net_cfg is None:
         if cond_shape is not None:
             raise ValueError("controlnet_cond= needs controlnet=")
@@ -199,35 +225,19 @@ def check_controlnet_args(cfg: dict, net_cfg=None, img_shape=None, cond_shape=No
         raise ValueError(f"controlnet_cond is {tuple(cond_shape)}, expected {(int(img_shape[0]), int(img_shape[1]), int(net_cfg['in_channels']))} for img {tuple(img_shape)}")
     if not np.isfinite(float(scale)):
         raise ValueError(f"controlnet_scale must be finite, got {scale!r}")
-    if has_context:
-        raise ValueError("a ControlNet is not combined with context= (a reference image)")
-    if cond_channels:
-        raise ValueError("a ControlNet is not combined with a channel-conditioned model (FLUX.1 Fill / Canny / Depth)")
-    if cache_args:
-        raise ValueError("a ControlNet is not combined with the step cache (cache_threshold= / cache_force=)")
-    if sequence_parallel:
-        raise ValueError("a ControlNet is not supported under sequence parallelism")
-    if step_scales is None:
-        return None
-    ss = np.asarray(step_scales, np.float32)
-    if ss.ndim != 1 or (n_steps is not None and ss.shape[0] != n_steps):
-        raise ValueError(f"controlnet_step_scales must have one entry per step ({n_steps}), got shape {ss.shape}")
-    if not np.isfinite(ss).all():
-        raise ValueError("controlnet_step_scales entries must be finite")
-    return np.ascontiguousarray(ss)
+    return check_step_scales(step_scales, n_steps, "controlnet_step_scales")
 
 
 IP_MAX_TOKENS = 32  # fmi_ip_attention's 1 <= N <= 32
 
 
 def check_ip_adapter_args(cfg: dict, adapter=None, img_shape=None, embeds_shape=None, negative_embeds_shape=None, scale=1.0, step_scales=None, n_steps=None,
-                          has_context: bool = False, cache_args: bool = False, sequence_parallel: bool = False, eight_bit=None, has_negative: bool = False):
+                          has_negative: bool = False):
     """The IP-Adapter of FluxModel.forward / denoise (fmi_flux_forward_ip / fmi_flux_denoise_ip), checked without the library.  cfg is the main model's
     config; adapter is None (no adapter) or a dict(num_heads=, joint_attention_dim=, num_layers=, embed_dim=, num_tokens=) — FluxIPAdapter.dims.  Returns step_scales
     as a float32 array of n_steps entries, or None.  ValueError: embeddings, a scale or step scales without ip_adapter= or an adapter without embeddings; an adapter
     whose width, joint_attention_dim or number of double blocks differ from the model's; embeds that are not (B, embed_dim) for img (B,S,C); negative embeddings of
-    another shape or without a negative prompt; a scale or step scale that is not finite; step_scales not n_steps entries; an adapter with context= (reference rows),
-    the step cache's arguments, sequence parallelism or an 8-bit mode (eight_bit: "fp8" / "int8")."""
+    another shape or without a negative prompt; a scale or step scale that is not finite; step_scales not n_steps entries."""
     if adapter is None:
         for v, nm in ((embeds_shape, "ip_adapter_image_embeds="), (negative_embeds_shape, "negative_ip_adapter_image_embeds="), (step_scales, "ip_adapter_step_scales=")):
             if v is not None:
@@ -250,22 +260,7 @@ def check_ip_adapter_args(cfg: dict, adapter=None, img_shape=None, embeds_shape=
             raise ValueError(f"negative_ip_adapter_image_embeds is {tuple(negative_embeds_shape)}, expected {want}")
     if not np.isfinite(float(scale)):
         raise ValueError(f"ip_adapter_scale must be finite, got {scale!r}")
-    if has_context:
-        raise ValueError("an IP-Adapter is not combined with context= (a reference image's rows)")
-    if cache_args:
-        raise ValueError("an IP-Adapter is not combined with the step cache (cache_threshold= / cache_force=)")
-    if sequence_parallel:
-        raise ValueError("an IP-Adapter is not supported under sequence parallelism")
-    if eight_bit:
-        raise ValueError(f"an IP-Adapter is not supported in the {eight_bit} mode (it reads the bf16 q of the q|k|v projection)")
-    if step_scales is None:
-        return None
-    ss = np.asarray(step_scales, np.float32)
-    if ss.ndim != 1 or (n_steps is not None and ss.shape[0] != n_steps):
-        raise ValueError(f"ip_adapter_step_scales must have one entry per step ({n_steps}), got shape {ss.shape}")
-    if not np.isfinite(ss).all():
-        raise ValueError("ip_adapter_step_scales entries must be finite")
-    return np.ascontiguousarray(ss)
+    return check_step_scales(step_scales, n_steps, "ip_adapter_step_scales")
 
 
 class FluxModel:
@@ -541,7 +536,10 @@ class FluxModel:
         return L.FluxContext(_ptr(keep[0]), _TORCH_DT[context.dtype], _ptr(keep[1]), R), keep
 
     def _control(self, img, control):
-        """fmi_flux_control of the conditioning channels (B,S,cond_channels) f32 | bf16, with the tensor it points into."""
+        """fmi_flux_control of the conditioning channels (B,S,cond_channels) f32 | bf16, with the tensor it points into; (None, None) on a plain model."""
+        check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape))
+        if control is None:
+            return None, None
         if control.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("control must be float32 or bfloat16")
         if control.device != img.device:
@@ -549,10 +547,10 @@ class FluxModel:
         keep = control.contiguous()
         return L.FluxControl(_ptr(keep), _TORCH_DT[control.dtype]), keep
 
-    def _controlnet(self, img, controlnet, controlnet_cond, scale, step_scales, n_steps, has_ctx, cache_args):
+    def _controlnet(self, img, controlnet, controlnet_cond, scale, step_scales, n_steps):
         """fmi_flux_controlnet for controlnet= / controlnet_cond=, with what it points into; (None, None) without a ControlNet."""
         ss = check_controlnet_args(self.cfg, None if controlnet is None else controlnet.cfg, tuple(img.shape), None if controlnet_cond is None else tuple(controlnet_cond.shape),
-                                   scale, step_scales, n_steps, has_ctx, self.cond_channels, cache_args, getattr(self, "_sp_world", 1) > 1)
+                                   scale, step_scales, n_steps)
         if controlnet is None:
             return None, None
         if not isinstance(controlnet, FluxControlNetModel):
@@ -565,13 +563,12 @@ class FluxModel:
         return L.FluxControlNet(controlnet.h, _ptr(keep[0]), _TORCH_DT[controlnet_cond.dtype], float(scale),
                                 ss.ctypes.data_as(C.POINTER(C.c_float)) if ss is not None else None), keep
 
-    def _ip(self, img, ip_adapter, embeds, negative_embeds, scale, step_scales, n_steps, has_ctx, cache_args, has_negative):
+    def _ip(self, img, ip_adapter, embeds, negative_embeds, scale, step_scales, n_steps, has_negative):
         """fmi_flux_ip for ip_adapter= / ip_adapter_image_embeds=, with what it points into; (None, None) without an adapter."""
         if ip_adapter is not None and not isinstance(ip_adapter, FluxIPAdapter):
             raise TypeError("ip_adapter= must be a FluxIPAdapter")
         ss = check_ip_adapter_args(self.cfg, None if ip_adapter is None else ip_adapter.dims, tuple(img.shape), None if embeds is None else tuple(embeds.shape),
-                                   None if negative_embeds is None else tuple(negative_embeds.shape), scale, step_scales, n_steps, has_ctx, cache_args,
-                                   getattr(self, "_sp_world", 1) > 1, getattr(self, "_eight_bit", None), has_negative)
+                                   None if negative_embeds is None else tuple(negative_embeds.shape), scale, step_scales, n_steps, has_negative)
         if ip_adapter is None:
             return None, None
         for t, nm in ((embeds, "ip_adapter_image_embeds"), (negative_embeds, "negative_ip_adapter_image_embeds")):
@@ -585,9 +582,14 @@ class FluxModel:
         return L.FluxIp(ip_adapter.h, _ptr(keep[0]), _TORCH_DT[embeds.dtype], _ptr(keep[1]), float(scale),
                         ss.ctypes.data_as(C.POINTER(C.c_float)) if ss is not None else None), keep
 
+    def _check_combination(self, **given):
+        """check_combination of the options a call has (one keyword each, true when present) and the modes this model is in."""
+        modes = ("sequence_parallel" if getattr(self, "_sp_world", 1) > 1 else None, getattr(self, "_eight_bit", None))
+        check_combination({k for k, v in given.items() if v} | {m for m in modes if m})
+
     def forward(self, img, img_ids, txt, txt_ids, timesteps, y, guidance=None, context=None, context_ids=None, control=None, controlnet=None, controlnet_cond=None,
                 controlnet_scale=1.0, ip_adapter=None, ip_adapter_image_embeds=None, ip_adapter_scale=1.0):
-        """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.
+        """== Flux::forward (model.rs:790-833).  Returns the velocity (B,S,C) f32.  One call: fmi_flux_forward_context with a context, else fmi_flux_forward_ip.
         context= / context_ids=: reference-image tokens appended to the image tokens for this evaluation (fmi_flux_forward_context); the velocity is img's.
         control=: the conditioning channels (B,S,cond_channels) f32 | bf16 of a channel-conditioned model (fmi_flux_forward_control): the
         evaluation is Flux::forward on cat([img, control], 2) and the velocity stays img's width.  Required on such a model, refused on any other.
@@ -597,35 +599,27 @@ class FluxModel:
         ip_adapter= / ip_adapter_image_embeds= / ip_adapter_scale=: a FluxIPAdapter and one image embedding (B, embed_dim) f32 | bf16 per sample; every double block
         adds scale * softmax(q K^T / sqrt(128)) V of its un-rotated, RMS-normed image queries against the adapter's tokens to the image stream
         (fmi_flux_forward_ip).  Works with control= and controlnet=; not with context=, sequence parallelism or the 8-bit modes."""
-        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, None, None, context is not None or context_ids is not None, False)
-        ip, keep_ip = self._ip(img, ip_adapter, ip_adapter_image_embeds, None, ip_adapter_scale, None, None, context is not None or context_ids is not None, False, False)
-        check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
-                           False, getattr(self, "_sp_world", 1) > 1)
+        has_ctx = context is not None or context_ids is not None
+        # (every keep_*, like keep, holds the tensors behind the pointers until the call has returned)
+        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, None, None)
+        ip, keep_ip = self._ip(img, ip_adapter, ip_adapter_image_embeds, None, ip_adapter_scale, None, None, False)
+        ctl, keep_ctl = self._control(img, control)
+        self._check_combination(context=has_ctx, control=ctl, controlnet=cn, ip_adapter=ip)
         inp, keep = self._inputs(img, img_ids, txt, txt_ids, timesteps, y, guidance)
         pred = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        if ip is not None:
-            ctl, keep_ctl = self._control(img, control) if control is not None else (None, None)
-            L.check(self.lib.fmi_flux_forward_ip(self.h, C.byref(inp), ctl and C.byref(ctl), cn and C.byref(cn), C.byref(ip), _ptr(pred), _stream()), self.lib)
-            return pred
-        if cn is not None:
-            L.check(self.lib.fmi_flux_forward_controlnet(self.h, C.byref(inp), C.byref(cn), _ptr(pred), _stream()), self.lib)
-            return pred
-        if control is not None:
-            ctl, keep_ctl = self._control(img, control)
-            L.check(self.lib.fmi_flux_forward_control(self.h, C.byref(inp), C.byref(ctl), _ptr(pred), _stream()), self.lib)
-            return pred
-        if context is None and context_ids is None:
-            L.check(self.lib.fmi_flux_forward(self.h, C.byref(inp), _ptr(pred), _stream()), self.lib)
-            return pred
-        ctx, keep_ctx = self._context(img_ids, context, context_ids)  # (keep_ctx, like keep, holds the tensors until the call has returned)
-        L.check(self.lib.fmi_flux_forward_context(self.h, C.byref(inp), C.byref(ctx), _ptr(pred), _stream()), self.lib)
+        if has_ctx:  # (alone: the table refuses it next to each of the other three)
+            ctx, keep_ctx = self._context(img_ids, context, context_ids)
+            L.check(self.lib.fmi_flux_forward_context(self.h, C.byref(inp), C.byref(ctx), _ptr(pred), _stream()), self.lib)
+        else:  # fmi_flux_forward_ip with NULL for what is not given is the shorter entry of the rest (include/flux_mi355x.h)
+            L.check(self.lib.fmi_flux_forward_ip(self.h, C.byref(inp), ctl and C.byref(ctl), cn and C.byref(cn), ip and C.byref(ip), _ptr(pred), _stream()), self.lib)
         return pred
 
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
                 cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None,
                 controlnet=None, controlnet_cond=None, controlnet_scale=1.0, controlnet_step_scales=None, ip_adapter=None, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0, ip_adapter_step_scales=None):
-        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_with call: the keywords fill its options.
+        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_ip call: the keywords fill its options
+        and its ControlNet and adapter arguments; which of them combine is REFUSED_PAIRS / REFUSED_MODES above.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
         context= / context_ids=: reference-image tokens every evaluation appends to the state's (fmi_flux_denoise_context); the state stays (B,S,C).
@@ -653,27 +647,23 @@ class FluxModel:
         embeddings through the same projection.  Works with the negative, x0 / noise / mask, control= and controlnet=; not with context=, the step cache,
         sequence parallelism or the 8-bit modes."""
         n_steps = len(timesteps) - 1
+        has_ctx = context is not None or context_ids is not None
+        # (every keep_*, like keep, holds the tensors behind the pointers until the call has returned)
         ip, keep_ip = self._ip(img, ip_adapter, ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_step_scales, n_steps,
-                               context is not None or context_ids is not None, cache_threshold is not None or cache_force is not None,
                                negative_txt is not None or negative_y is not None)
-        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, controlnet_step_scales, n_steps, context is not None or context_ids is not None,
-                                       cache_threshold is not None or cache_force is not None)
-        check_control_args(self.cond_channels, tuple(img.shape), None if control is None else tuple(control.shape), context is not None or context_ids is not None,
-                           cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
+        cn, keep_cn = self._controlnet(img, controlnet, controlnet_cond, controlnet_scale, controlnet_step_scales, n_steps)
+        ctl, keep_ctl = self._control(img, control)
         cfg_scale = check_true_cfg_args(tuple(txt.shape), tuple(y.shape), None if negative_txt is None else tuple(negative_txt.shape),
-                                        None if negative_y is None else tuple(negative_y.shape), true_cfg_scale,
-                                        cache_threshold is not None or cache_force is not None, getattr(self, "_sp_world", 1) > 1)
-        thr, force = check_step_cache_args(n_steps, cache_threshold, cache_force, getattr(self, "_sp_world", 1) > 1)
+                                        None if negative_y is None else tuple(negative_y.shape), true_cfg_scale)
+        thr, force = check_step_cache_args(n_steps, cache_threshold, cache_force)
+        self._check_combination(context=has_ctx, control=ctl, true_cfg=cfg_scale is not None, cache=thr is not None, controlnet=cn, ip_adapter=ip)
         if return_cache_stats and thr is None:
             raise ValueError("return_cache_stats needs cache_threshold= or cache_force=")
         img = img.to(torch.float32).clone().contiguous()
         inp, keep = self._inputs(None, img_ids, txt, txt_ids, None, y, guidance)
         ts = (C.c_double * len(timesteps))(*timesteps)
-        # (keep_blend and keep_ctx, like keep, hold the tensors behind the pointers until the call has returned)
         keep_blend = [_like_img(t, nm, img) for t, nm in ((x0, "x0"), (noise, "noise"), (mask, "mask"))]
-        has_ctx = context is not None or context_ids is not None
         ctx, keep_ctx = self._context(img_ids, context, context_ids) if has_ctx else (None, None)
-        ctl, keep_ctl = self._control(img, control) if control is not None else (None, None)
         # (a missing one of x0 / noise / mask reaches the library as NULL: it answers FMI_ERR_INVALID)
         opts = L.FluxDenoiseOptions(ctx and C.pointer(ctx), ctl and C.pointer(ctl), None, None, *[_ptr(t) for t in keep_blend])
         if cfg_scale is not None:
@@ -689,12 +679,8 @@ class FluxModel:
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             opts.cache = C.pointer(L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
                                                    decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float))))
-        if ip is not None:
-            L.check(self.lib.fmi_flux_denoise_ip(self.h, C.byref(inp), C.byref(opts), cn and C.byref(cn), C.byref(ip), _ptr(img), ts, n_steps, _stream()), self.lib)
-        elif cn is not None:
-            L.check(self.lib.fmi_flux_denoise_controlnet(self.h, C.byref(inp), C.byref(opts), C.byref(cn), _ptr(img), ts, n_steps, _stream()), self.lib)
-        else:
-            L.check(self.lib.fmi_flux_denoise_with(self.h, C.byref(inp), C.byref(opts), _ptr(img), ts, n_steps, _stream()), self.lib)
+        # (with cn and ip NULL this IS fmi_flux_denoise_with, with ip NULL fmi_flux_denoise_controlnet: include/flux_mi355x.h)
+        L.check(self.lib.fmi_flux_denoise_ip(self.h, C.byref(inp), C.byref(opts), cn and C.byref(cn), ip and C.byref(ip), _ptr(img), ts, n_steps, _stream()), self.lib)
         return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
 
     def step_cache_bytes(self) -> int:

@@ -22,12 +22,13 @@ prompts — prompt i runs on rank i % world — and gathers the images to rank 0
 """
 import enum
 import hashlib
+import inspect
 import json
 import os
 import struct
 import threading
 import zlib
-from dataclasses import dataclass, fields, replace
+from dataclasses import dataclass, fields
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -167,6 +168,24 @@ def check_reference(t: torch.Tensor, B: int) -> torch.Tensor:
     return t
 
 
+def _host_image(x, what: str) -> torch.Tensor:
+    """One image input of a request (`what`: its keyword) as a tensor where it lies: a numpy array or a torch tensor, uint8 or float; ValueError otherwise.
+    The caller's shape rule comes next, then Pipeline._device_image."""
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what} must be a numpy array or a torch tensor")
+    if not (t.dtype == torch.uint8 or t.is_floating_point()):
+        raise ValueError(f"{what} must be uint8 or float, got {t.dtype}")
+    return t
+
+
+# what a request calls the options and modes of flux.REFUSED_PAIRS / REFUSED_MODES (an 8-bit transformer: "fp8" / "int8")
+REQUEST_NAMES = dict(context="reference= (a context)", control="a control (a channel-conditioned checkpoint: FLUX.1 Fill / Canny / Depth)",
+                     true_cfg="true CFG (a negative with true_cfg_scale > 1)", cache="the step cache (cache_threshold= / cache_force=)", controlnet="a ControlNet",
+                     ip_adapter="an IP-Adapter", sequence_parallel="supported under sequence parallelism: disable_sequence_parallel() first",
+                     fp8="supported on a transformer in the fp8 mode", int8="supported on a transformer in the int8 mode")
+
+
 def _rows(x, idx):
     """Rows `idx` (a slice or a list of ints) of one per-sample input: a tensor, a numpy array, a list, or a pair (tuple) of those; None stays None."""
     if x is None:
@@ -231,11 +250,10 @@ class _ControlNetInput:
 
 
 def check_controlnet_request(loaded: bool, height: int, width: int, image_shape=None, image_is_u8: bool = False, scale: float = 1.0, start: float = 0.0,
-                             end: float = 1.0, reference: bool = False, cache_threshold: bool = False, cond_channels: int = 0, sequence_parallel: bool = False):
+                             end: float = 1.0):
     """The ControlNet arguments of a request, checked without a device.  ValueError: controlnet_image= without a loaded ControlNet (Pipeline.load_controlnet); a
     height or width that is no multiple of 16; an image that is not u8 (H,W,3) or float (B,3,H,W) with B == 1 at the request's size (nothing is resized); a scale
-    that is not finite; control_guidance_start / _end outside 0 <= start <= end <= 1; reference=, cache_threshold=, a Fill / Canny / Depth checkpoint or sequence
-    parallelism next to it.  A request without controlnet_image= is not conditioned, whatever is loaded."""
+    that is not finite; control_guidance_start / _end outside 0 <= start <= end <= 1.  A request without controlnet_image= is not conditioned, whatever is loaded."""
     if image_shape is None:
         return
     if not loaded:
@@ -249,14 +267,6 @@ def check_controlnet_request(loaded: bool, height: int, width: int, image_shape=
         raise ValueError(f"controlnet_conditioning_scale must be finite, got {scale!r}")
     if not (0.0 <= float(start) <= float(end) <= 1.0):
         raise ValueError(f"control_guidance_start / control_guidance_end must satisfy 0 <= start <= end <= 1, got {start!r} / {end!r}")
-    if reference:
-        raise ValueError("a ControlNet is not combined with reference= (a context)")
-    if cache_threshold:
-        raise ValueError("a ControlNet is not combined with the step cache (cache_threshold=)")
-    if cond_channels:
-        raise ValueError("a ControlNet is not combined with a channel-conditioned checkpoint (FLUX.1 Fill / Canny / Depth)")
-    if sequence_parallel:
-        raise ValueError("a ControlNet is not wired through sequence parallelism: disable_sequence_parallel() first")
 
 
 @dataclass(frozen=True)
@@ -268,16 +278,14 @@ class _IpAdapterInput:
     scale: float                             # ip_adapter_scale
     start: float                             # ip_adapter_start, a step fraction
     end: float                               # ip_adapter_end
-    control: object = None                   # the request's control next to it: None, a _Control or a _ControlNetInput
 
 
 def check_ip_adapter_request(loaded: bool, embed_dim: int = 0, embeds_shape=None, negative_embeds_shape=None, scale: float = 1.0, start: float = 0.0, end: float = 1.0,
-                             reference: bool = False, cache_threshold: bool = False, sequence_parallel: bool = False, eight_bit=None, has_negative: bool = False):
+                             has_negative: bool = False):
     """The IP-Adapter arguments of a request, checked without a device.  ValueError: ip_adapter_image_embeds= without a loaded adapter (Pipeline.load_ip_adapter);
     negative_ip_adapter_image_embeds= without ip_adapter_image_embeds= or without a negative prompt; embeddings that are not (embed_dim,) or (1, embed_dim) — one per
-    request, shared by its prompts; a scale that is not finite; ip_adapter_start / ip_adapter_end outside 0 <= start <= end <= 1; reference=, cache_threshold=,
-    sequence parallelism or an 8-bit transformer (eight_bit: "fp8" / "int8") next to it.  A request without ip_adapter_image_embeds= is not conditioned, whatever
-    is loaded."""
+    request, shared by its prompts; a scale that is not finite; ip_adapter_start / ip_adapter_end outside 0 <= start <= end <= 1.  A request without
+    ip_adapter_image_embeds= is not conditioned, whatever is loaded."""
     if embeds_shape is None:
         if negative_embeds_shape is not None:
             raise ValueError("negative_ip_adapter_image_embeds= needs ip_adapter_image_embeds=")
@@ -293,14 +301,6 @@ def check_ip_adapter_request(loaded: bool, embed_dim: int = 0, embeds_shape=None
         raise ValueError(f"ip_adapter_scale must be finite, got {scale!r}")
     if not (0.0 <= float(start) <= float(end) <= 1.0):
         raise ValueError(f"ip_adapter_start / ip_adapter_end must satisfy 0 <= start <= end <= 1, got {start!r} / {end!r}")
-    if reference:
-        raise ValueError("an IP-Adapter is not combined with reference= (a context)")
-    if cache_threshold:
-        raise ValueError("an IP-Adapter is not combined with the step cache (cache_threshold=)")
-    if sequence_parallel:
-        raise ValueError("an IP-Adapter is not wired through sequence parallelism: disable_sequence_parallel() first")
-    if eight_bit:
-        raise ValueError(f"an IP-Adapter is not supported on a transformer in the {eight_bit} mode")
 
 
 def control_kind(cond_channels: int) -> Optional[str]:
@@ -313,12 +313,10 @@ def control_kind(cond_channels: int) -> Optional[str]:
     return kinds[cond_channels]
 
 
-def check_control_request(kind: Optional[str], height: int, width: int, image_shape=None, image_is_u8: bool = False, mask_shape=None, reference: bool = False,
-                          cache_threshold: bool = False, sequence_parallel: bool = False):
+def check_control_request(kind: Optional[str], height: int, width: int, image_shape=None, image_is_u8: bool = False, mask_shape=None):
     """The control arguments of a request, checked without a device (kind: control_kind of the model).  ValueError: control_image= / control_mask= on a plain
     model; a conditioned model without control_image=; control_mask= missing on a Fill model or given to a Canny / Depth model; a height or width that is no
-    multiple of 16; an image that is not u8 (H,W,3) or float (1,3,H,W) at the request's size; a mask that is not (H,W); reference=, cache_threshold= or
-    sequence parallelism next to a control."""
+    multiple of 16; an image that is not u8 (H,W,3) or float (1,3,H,W) at the request's size; a mask that is not (H,W)."""
     if kind is None:
         if image_shape is not None or mask_shape is not None:
             raise ValueError("control_image= / control_mask= need a channel-conditioned model (FLUX.1 Fill / Canny / Depth)")
@@ -336,12 +334,6 @@ def check_control_request(kind: Optional[str], height: int, width: int, image_sh
         raise ValueError(f"control_image must be uint8 ({height},{width},3) or float (1,3,{height},{width}) as params say, got {tuple(image_shape)}")
     if mask_shape is not None and tuple(mask_shape) != (height, width):
         raise ValueError(f"control_mask must be ({height},{width}) as params say, got {tuple(mask_shape)}")
-    if reference:
-        raise ValueError("a control is not combined with reference= (a context)")
-    if cache_threshold:
-        raise ValueError("a control is not combined with the step cache (cache_threshold=)")
-    if sequence_parallel:
-        raise ValueError("a control is not wired through sequence parallelism: disable_sequence_parallel() first")
 
 
 def _index_sets(B: int, max_batch: int, one_by_one: bool) -> list:
@@ -524,21 +516,14 @@ class Pipeline:
 
         if isinstance(image, (list, tuple)):  # the list of (H,W,3) arrays output="rgb" returns
             image = np.stack([np.asarray(i) for i in image])
-        t = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("image must be a numpy array or a torch tensor")
+        t = _host_image(image, "image")
         if t.dtype == torch.uint8:  # (B,H,W,3) or (H,W,3): what output="rgb" returns
             t = t.unsqueeze(0) if t.dim() == 3 else t
             if t.dim() != 4 or tuple(t.shape[1:]) != (H, W, 3):
                 raise ValueError(f"a uint8 image must be (B,{H},{W},3) or ({H},{W},3) as params say, got {tuple(t.shape)}")
-            t = F.preprocess_u8(t.to(self.device), interleaved=True)
-        elif t.is_floating_point():  # (B,3,H,W) in [-1,1]
-            if t.dim() != 4 or tuple(t.shape[1:]) != (3, H, W):
-                raise ValueError(f"a float image must be (B,3,{H},{W}) as params say, got {tuple(t.shape)}")
-            t = t.to(device=self.device, dtype=torch.float32)
-        else:
-            raise ValueError(f"image must be uint8 or float, got {t.dtype}")
-        image = batched(t, "image")
+        elif t.dim() != 4 or tuple(t.shape[1:]) != (3, H, W):  # (B,3,H,W) in [-1,1]
+            raise ValueError(f"a float image must be (B,3,{H},{W}) as params say, got {tuple(t.shape)}")
+        image = batched(self._device_image(t), "image")
         if mask is not None:
             m = torch.from_numpy(np.ascontiguousarray(mask)) if isinstance(mask, np.ndarray) else mask
             if not isinstance(m, torch.Tensor) or not (m.dtype == torch.bool or m.is_floating_point()):
@@ -555,13 +540,16 @@ class Pipeline:
             return None
         if getattr(self, "_sp", None) is not None:
             raise ValueError("reference= is not wired through sequence parallelism: disable_sequence_parallel() first")
-        t = torch.from_numpy(np.ascontiguousarray(reference)) if isinstance(reference, np.ndarray) else reference
-        t = check_reference(t, B)
-        if t.dtype == torch.uint8:
-            t = F.preprocess_u8(t.to(self.device), interleaved=True)
-        else:
-            t = t.to(device=self.device, dtype=torch.float32)
+        t = self._device_image(check_reference(_host_image(reference, "reference"), B))
         return t if t.shape[0] == B else t.expand(B, *t.shape[1:])
+
+    def _device_image(self, t: torch.Tensor) -> torch.Tensor:
+        """An image that has passed _host_image and its caller's shape rule, in device form: uint8 (n,H,W,3) or float (n,3,H,W) -> f32 (n,3,H,W) in [-1,1]."""
+        return F.preprocess_u8(t.to(self.device), interleaved=True) if t.dtype == torch.uint8 else t.to(device=self.device, dtype=torch.float32)
+
+    def _encode(self, image: torch.Tensor) -> torch.Tensor:
+        """The packed latents (n,S,64) f32 of an image in device form: VAE encode (the posterior MEAN: deterministic, no second noise stream), scale, shift, pack."""
+        return F.encode_latents(self.vae.encode(image), self.vae.scale_factor(), self.vae.shift_factor())[0]
 
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
@@ -625,13 +613,18 @@ class Pipeline:
         negative_ip_adapter_image_embeds=, or to zero embeddings through the same projection.  Combines with the negative, image= / strength= / mask=, a Fill /
         Canny / Depth control and a ControlNet; raises with reference=, cache_threshold=, under sequence parallelism, on an 8-bit transformer and without a loaded
         adapter."""
-        ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end, reference,
-                                     cache_threshold, negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None)
-        cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params, reference, cache_threshold)
-        if cache_threshold is not None:
-            F.check_step_cache_args(params.num_steps, cache_threshold, None, getattr(self, "_sp", None) is not None)
-        ctl = self._control(control_image, control_mask, params, reference, cache_threshold)
-        neg = self._negative(negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids)
+        ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
+                                     negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None)
+        cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params)
+        F.check_step_cache_args(params.num_steps, cache_threshold)
+        ctl = self._control(control_image, control_mask, params)
+        neg = self._negative(negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, embeddings, token_ids)
+        # the request's shared options, one keyword of _generate_chunk each, passed only by a request that has it: any other makes exactly the call it always made
+        shared = {k: v for k, v in (("negative", neg), ("control", ctl), ("controlnet", cn), ("ip_adapter", ipa)) if v is not None}
+        modes = {"sequence_parallel" if getattr(self, "_sp", None) is not None else None,
+                 "int8" if getattr(self, "_int8_pending", False) else getattr(getattr(self, "flux", None), "_eight_bit", None)}
+        present = dict(context=reference, cache=cache_threshold, true_cfg=neg, control=ctl, controlnet=cn, ip_adapter=ipa)  # (a negative at a scale <= 1: neg is None)
+        F.check_combination({k for k, v in present.items() if v is not None} | modes, REQUEST_NAMES)
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
         if not s.prompts:
@@ -639,58 +632,38 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        # (the negative is a keyword of true-CFG requests only, the control of controlled ones: any other request makes exactly the call it always made; a request has
-        # ONE control object, the channel conditioning's or the ControlNet's — the two are never combined, check_controlnet_request)
-        extra = dict(**({} if neg is None else dict(negative=neg)), **({} if ctl is None and cn is None else dict(control=ctl if cn is None else cn)))
-        if ipa is not None:  # the image prompt rides on the same keyword, around whichever control the request has (it combines with both kinds)
-            extra["control"] = replace(ipa, control=extra.get("control"))
-        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **extra)
+        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
             return outs[0]
         return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
 
-    def _control(self, control_image, control_mask, params, reference, cache_threshold) -> Optional[_Control]:
-        """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share."""
-        def as_tensor(x, what):
-            t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-            if x is not None and not isinstance(t, torch.Tensor):
-                raise ValueError(f"{what} must be a numpy array or a torch tensor")
-            return t
-
-        img, m = as_tensor(control_image, "control_image"), as_tensor(control_mask, "control_mask")
-        if img is not None and not (img.dtype == torch.uint8 or img.is_floating_point()):
-            raise ValueError(f"control_image must be uint8 or float, got {img.dtype}")
+    def _control(self, control_image, control_mask, params, *_) -> Optional[_Control]:
+        """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share.  (Callers from before
+        check_combination pass two more arguments, about the request's other options; they are not looked at.)"""
+        img = None if control_image is None else _host_image(control_image, "control_image")
+        m = torch.from_numpy(np.ascontiguousarray(control_mask)) if isinstance(control_mask, np.ndarray) else control_mask
+        if m is not None and not isinstance(m, torch.Tensor):
+            raise ValueError("control_mask must be a numpy array or a torch tensor")
         if m is not None and not (m.dtype == torch.bool or m.is_floating_point()):
             raise ValueError("control_mask must be a bool or float numpy array or torch tensor")
         kind = control_kind(getattr(getattr(self, "flux", None), "cond_channels", 0))
         check_control_request(kind, params.height, params.width, None if img is None else tuple(img.shape), img is not None and img.dtype == torch.uint8,
-                              None if m is None else tuple(m.shape), reference is not None, cache_threshold is not None, getattr(self, "_sp", None) is not None)
+                              None if m is None else tuple(m.shape))
         if kind is None:
             return None
-        if img.dtype == torch.uint8:
-            img = F.preprocess_u8(img.unsqueeze(0).to(self.device), interleaved=True)
-        else:
-            img = img.to(device=self.device, dtype=torch.float32).contiguous()
+        img = self._device_image(img.unsqueeze(0) if img.dtype == torch.uint8 else img)
         return _Control(kind, img, None if m is None else m.unsqueeze(0).to(device=self.device, dtype=torch.float32).contiguous())
 
-    def _controlnet_input(self, image, scale, start, end, params, reference, cache_threshold) -> Optional[_ControlNetInput]:
+    def _controlnet_input(self, image, scale, start, end, params) -> Optional[_ControlNetInput]:
         """The ControlNet conditioning of a request, checked once and brought to its device form: None without controlnet_image=, else the object its chunks share."""
         if image is None:
             return None
-        img = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
-        if not isinstance(img, torch.Tensor) or not (img.dtype == torch.uint8 or img.is_floating_point()):
-            raise ValueError("controlnet_image must be a uint8 or float numpy array or torch tensor")
-        check_controlnet_request(getattr(self, "controlnet", None) is not None, params.height, params.width, tuple(img.shape), img.dtype == torch.uint8, scale, start, end,
-                                 reference is not None, cache_threshold is not None, getattr(getattr(self, "flux", None), "cond_channels", 0),
-                                 getattr(self, "_sp", None) is not None)
-        if img.dtype == torch.uint8:
-            img = F.preprocess_u8(img.unsqueeze(0).to(self.device), interleaved=True)
-        else:
-            img = img.to(device=self.device, dtype=torch.float32).contiguous()
-        return _ControlNetInput(img, float(scale), float(start), float(end))
+        img = _host_image(image, "controlnet_image")
+        check_controlnet_request(getattr(self, "controlnet", None) is not None, params.height, params.width, tuple(img.shape), img.dtype == torch.uint8, scale, start, end)
+        return _ControlNetInput(self._device_image(img.unsqueeze(0) if img.dtype == torch.uint8 else img), float(scale), float(start), float(end))
 
-    def _ip_adapter_input(self, embeds, negative_embeds, scale, start, end, reference, cache_threshold, has_negative) -> Optional[_IpAdapterInput]:
+    def _ip_adapter_input(self, embeds, negative_embeds, scale, start, end, has_negative) -> Optional[_IpAdapterInput]:
         """The image prompt of a request, checked once and brought to its device form: None without ip_adapter_image_embeds=, else the object its chunks share."""
         def as_tensor(x, what):
             t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
@@ -699,10 +672,8 @@ class Pipeline:
             return t
         e, n = as_tensor(embeds, "ip_adapter_image_embeds"), as_tensor(negative_embeds, "negative_ip_adapter_image_embeds")
         ada = getattr(self, "ip_adapter", None)
-        flux = getattr(self, "flux", None)
         check_ip_adapter_request(ada is not None, 0 if ada is None else ada.embed_dim, None if e is None else tuple(e.shape), None if n is None else tuple(n.shape), scale,
-                                 start, end, reference is not None, cache_threshold is not None, getattr(self, "_sp", None) is not None,
-                                 "int8" if getattr(self, "_int8_pending", False) else getattr(flux, "_eight_bit", None), has_negative)
+                                 start, end, has_negative)
         if e is None:
             return None
         dev = lambda t: None if t is None else t.to(device=self.device, dtype=torch.float32).reshape(1, -1).contiguous()
@@ -761,15 +732,13 @@ class Pipeline:
     def _control_condition(self, control: _Control, B: int):
         """The conditioning channels (B,S,64 | 320) f32 of a chunk of B samples: built once at one row — VAE encode (the posterior mean), pack, and for Fill the
         masked image in front of it and the mask channels behind — then expanded."""
-        sf, sh = self.vae.scale_factor(), self.vae.shift_factor()
         if control.kind == "fill":
-            lat, _ = F.encode_latents(self.vae.encode(F.mask_image(control.image, control.mask)), sf, sh)
-            cond = F.fill_condition(lat, control.mask)
+            cond = F.fill_condition(self._encode(F.mask_image(control.image, control.mask)), control.mask)
         else:
-            cond, _ = F.encode_latents(self.vae.encode(control.image), sf, sh)
+            cond = self._encode(control.image)
         return cond.expand(B, -1, -1).contiguous()
 
-    def _negative(self, negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, cache_threshold, embeddings, token_ids) -> Optional[_Negative]:
+    def _negative(self, negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, embeddings, token_ids) -> Optional[_Negative]:
         """The negative of a request, checked once: None when true CFG is off (no negative, or a scale <= 1: diffusers' do_true_cfg), else the object its chunks share."""
         scale = float(true_cfg_scale)
         given = [x is not None for x in (negative_prompt, negative_embeddings, negative_token_ids)]
@@ -783,10 +752,6 @@ class Pipeline:
             return None
         if scale <= 1.0:
             return None
-        if cache_threshold is not None:
-            raise ValueError("true CFG (a negative with true_cfg_scale > 1) is not combined with the step cache (cache_threshold=)")
-        if getattr(self, "_sp", None) is not None:
-            raise ValueError("true CFG is not wired through sequence parallelism: disable_sequence_parallel() first")
         if embeddings is not None and negative_embeddings is None:
             raise ValueError("with embeddings= the negative comes as negative_embeddings= (t5 (1,T,J), clip (1,P))")
         if embeddings is None and token_ids is not None and negative_prompt is not None:
@@ -852,14 +817,11 @@ class Pipeline:
         return t5_emb, clip_emb, neg
 
     def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
-                        control=None):
+                        control: Optional[_Control] = None, controlnet: Optional[_ControlNetInput] = None, ip_adapter: Optional[_IpAdapterInput] = None):
         """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
-        generate_tensor does.  negative: the request's true-CFG negative — passed by true-CFG requests only.  control: the request's control —
-        a _Control, passed by requests to a channel-conditioned model only, or a _ControlNetInput, passed by requests with
-        controlnet_image= only; a request never has both.  A request with ip_adapter_image_embeds= passes its _IpAdapterInput, which carries
-        the control of either kind inside."""
-        ip, control = (control, control.control) if isinstance(control, _IpAdapterInput) else (None, control)
-        controlnet, control = (control, None) if isinstance(control, _ControlNetInput) else (None, control)
+        generate_tensor does.  The request's shared options, each passed only by a request that has it — negative: its true-CFG negative (DESIGN.md 4.12);
+        control: the control of a request to a channel-conditioned model; controlnet: the conditioning of one with controlnet_image=
+        (DESIGN.md 4.15); ip_adapter: the image prompt of one with ip_adapter_image_embeds=."""
         cfg = self.flux.cfg
         dev = self.device
         sp = getattr(self, "_sp", None)
@@ -882,7 +844,7 @@ class Pipeline:
             guidance = torch.full((B,), float(params.guidance_scale), dtype=torch.float32, device=dev) if self.flux.is_guidance() else None
             inpaint = {}
             if s.image is not None:  # start from the source noised to the cut schedule's first value (at strength 1 that is the noise itself, bit for bit)
-                x0, _ = F.encode_latents(self.vae.encode(s.image), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
+                x0 = self._encode(s.image)
                 timesteps = img2img_timesteps(timesteps, strength)
                 noise = img
                 img = F.scale_noise(x0, noise, timesteps[0])
@@ -890,20 +852,18 @@ class Pipeline:
                     inpaint = dict(x0=x0, noise=noise, mask=F.latent_mask(s.mask, x0.shape[2] // 4))
             context = {}
             if s.reference is not None:  # its packed latents are rows of every evaluation, never of the state; mu and the schedule above know S only
-                ctx, _ = F.encode_latents(self.vae.encode(s.reference), self.vae.scale_factor(), self.vae.shift_factor())  # the posterior mean
-                context = dict(context=ctx, context_ids=F.latent_ids(B, s.reference.shape[2] // 16, s.reference.shape[3] // 16, id0=1.0, device=dev))
+                context = dict(context=self._encode(s.reference), context_ids=F.latent_ids(B, s.reference.shape[2] // 16, s.reference.shape[3] // 16, id0=1.0, device=dev))
             if control is not None:  # the same conditioning channels at every step, for every sample and for both halves of a true-CFG batch
                 context = dict(control=self._control_condition(control, B))
             cn_kw = {}
-            if controlnet is not None:  # the control image's packed latents (the posterior mean), one row expanded; the scales over the steps actually run
-                cond, _ = F.encode_latents(self.vae.encode(controlnet.image), self.vae.scale_factor(), self.vae.shift_factor())
-                cn_kw = dict(controlnet=self.controlnet, controlnet_cond=cond.expand(B, -1, -1).contiguous(), controlnet_scale=controlnet.scale,
+            if controlnet is not None:  # the control image's packed latents, one row expanded; the scales over the steps actually run
+                cn_kw = dict(controlnet=self.controlnet, controlnet_cond=self._encode(controlnet.image).expand(B, -1, -1).contiguous(), controlnet_scale=controlnet.scale,
                              controlnet_step_scales=F.controlnet_step_scales(len(timesteps) - 1, controlnet.start, controlnet.end))
-            if ip is not None:  # one embedding row expanded to the chunk; the scales over the steps actually run, like the ControlNet's
-                cn_kw.update(ip_adapter=self.ip_adapter, ip_adapter_image_embeds=ip.embeds.expand(B, -1).contiguous(), ip_adapter_scale=ip.scale,
-                             ip_adapter_step_scales=F.controlnet_step_scales(len(timesteps) - 1, ip.start, ip.end))
-                if ip.negative_embeds is not None:
-                    cn_kw.update(negative_ip_adapter_image_embeds=ip.negative_embeds.expand(B, -1).contiguous())
+            if ip_adapter is not None:  # one embedding row expanded to the chunk; the scales over the steps actually run, like the ControlNet's
+                cn_kw.update(ip_adapter=self.ip_adapter, ip_adapter_image_embeds=ip_adapter.embeds.expand(B, -1).contiguous(), ip_adapter_scale=ip_adapter.scale,
+                             ip_adapter_step_scales=F.controlnet_step_scales(len(timesteps) - 1, ip_adapter.start, ip_adapter.end))
+                if ip_adapter.negative_embeds is not None:
+                    cn_kw.update(negative_ip_adapter_image_embeds=ip_adapter.negative_embeds.expand(B, -1).contiguous())
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
@@ -1018,17 +978,17 @@ class Pipeline:
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
-        if negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None or true_cfg_scale != 1.0:
-            # (only when one of them is given: any other request makes exactly the generate_tensor call it always made)
-            shared.update(negative_prompt=negative_prompt, negative_embeddings=negative_embeddings, negative_token_ids=negative_token_ids, true_cfg_scale=true_cfg_scale)
-        if control_image is not None or control_mask is not None:  # (likewise)
-            shared.update(control_image=control_image, control_mask=control_mask)
-        if controlnet_image is not None:  # (likewise)
-            shared.update(controlnet_image=controlnet_image, controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
-                          control_guidance_end=control_guidance_end)
-        if ip_adapter_image_embeds is not None or negative_ip_adapter_image_embeds is not None:  # (likewise)
-            shared.update(ip_adapter_image_embeds=ip_adapter_image_embeds, negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds,
-                          ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start, ip_adapter_end=ip_adapter_end)
+        options = dict(negative_prompt=negative_prompt, negative_embeddings=negative_embeddings, negative_token_ids=negative_token_ids, true_cfg_scale=true_cfg_scale,
+                       control_image=control_image, control_mask=control_mask, controlnet_image=controlnet_image,
+                       controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
+                       control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
+                       negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
+                       ip_adapter_end=ip_adapter_end)
+        defaults = inspect.signature(Pipeline.generate_tensor).parameters
+        for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
+            default = defaults[name].default
+            if (value is not None) if default is None else value != default:
+                shared[name] = value
         per_sample = dict(kw, image=image, mask=mask, reference=reference)  # with embeddings= / token_ids= / latents= / first_sample=, which ride in **kw
         final = None  # return_latents=True: the final packed latents, returned next to the images
         if world > 1 and getattr(self, "_sp", None) is None:

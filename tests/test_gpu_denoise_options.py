@@ -180,3 +180,56 @@ def test_refusals_come_with_their_code_before_any_launch_or_allocation(env):
     finally:
         for gm in models.values():
             gm.close()
+
+
+# ------------------------------------------------------------------------------------------------ Python's table against the library's
+PAIR_NAMES = dict(ctx="context", ctl="control", cfg="true_cfg", cache="cache", blend="blend", cn="controlnet", ip="ip_adapter")  # the struct's names -> flux.REFUSED_PAIRS'
+
+
+def test_the_library_refuses_exactly_the_pairs_python_refuses(env):
+    """flux.REFUSED_PAIRS against validate(): of the 21 pairs of {ctx, ctl, cfg, cache, x0 / noise / mask, cn, ip}, handed to fmi_flux_denoise_ip as ctypes structs, the
+    library answers FMI_ERR_UNSUPPORTED — before any launch, the state untouched — exactly for the pairs Python's table holds, and runs the others (one step).
+    B = 1, the 6x4 grid, T = 32; the conditioned twin for the pairs with ctl; a 1+1-block ControlNet and a 4-token adapter.  The rows of flux.REFUSED_MODES
+    (sequence parallelism, the 8-bit modes) are held against the library by the refusal tests of test_gpu_step_cache, test_gpu_true_cfg, test_gpu_control,
+    test_gpu_controlnet and test_gpu_ip_adapter, and against this table by tests/test_host_denoise_options.py."""
+    import itertools
+    from diffusion_rs_amd import _lib as L
+    from diffusion_rs_amd import flux as F
+    torch, d = env["torch"], env["d"]
+    E, R = 16, R_HW[0] * R_HW[1]
+    s = dict(zip(("img", "ids", "txt", "txt_ids", "y"), flux_inputs(SMALL_FLUX, 1, GRIDS["aligned"], T, seed=41)))
+    rng = np.random.default_rng(47)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    k = dict(x0=dev(rng.standard_normal(s["img"].shape).astype(np.float32)), noise=dev(s["img"]), mask=dev((rng.random(s["img"].shape) < 0.5).astype(np.float32)),
+             ntxt=dev(rng.standard_normal(s["txt"].shape).astype(np.float32), torch.bfloat16), ny=dev(rng.standard_normal(s["y"].shape).astype(np.float32)),
+             cond=dev(rng.standard_normal(s["img"].shape[:2] + (K - 64,)).astype(np.float32)), ctx=dev(rng.standard_normal((1, R, 64)).astype(np.float32)),
+             ctx_ids=d.latent_ids(1, *R_HW, id0=1.0), cn_cond=dev(rng.standard_normal(s["img"].shape).astype(np.float32)),
+             emb=dev(rng.standard_normal((1, E)).astype(np.float32)))
+    net_cfg = dict(SMALL_FLUX, num_layers=1, num_single_layers=1)
+    net, ada = d.FluxControlNetModel(net_cfg), d.FluxIPAdapter(SMALL_FLUX, E, 4)
+    refused_in_python = {frozenset(r) for r in F.REFUSED_PAIRS}
+    try:
+        net.load_state_dict(d.synth.controlnet_state_dict_numpy(net_cfg, seed=3))
+        ada.load_state_dict(d.synth.ip_adapter_state_dict_numpy(SMALL_FLUX, E, 4, seed=5))
+        for pair in itertools.combinations(PAIR_NAMES, 2):
+            gm = env["cond" if "ctl" in pair else "plain"]
+            dec, dist = np.zeros(1, np.int32), np.zeros((1, 1), np.float32)
+            st = dict(ctx=L.FluxContext(vp(k["ctx"]), L.F32, vp(k["ctx_ids"]), R), ctl=L.FluxControl(vp(k["cond"]), L.F32),
+                      cfg=L.FluxTrueCfg(vp(k["ntxt"]), L.BF16, vp(k["ny"]), L.F32, SCALE),
+                      cache=L.FluxStepCache(0.1, None, dec.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float))),
+                      cn=L.FluxControlNet(net.h, vp(k["cn_cond"]), L.F32, 1.0, None), ip=L.FluxIp(ada.h, vp(k["emb"]), L.F32, None, 1.0, None))
+            opts = L.FluxDenoiseOptions(*[C.pointer(st[n]) if n in pair else None for n in ("ctx", "ctl", "cfg", "cache")],
+                                        *[vp(k[n]) if "blend" in pair else None for n in ("x0", "noise", "mask")])
+            img = dev(s["img"]).clone()
+            inp, keep = _inp(env, gm, s)
+            rc = gm.lib.fmi_flux_denoise_ip(gm.h, C.byref(inp), C.byref(opts), C.byref(st["cn"]) if "cn" in pair else None, C.byref(st["ip"]) if "ip" in pair else None,
+                                            C.c_void_p(img.data_ptr()), (C.c_double * 2)(1.0, 0.0), 1, None)
+            torch.cuda.synchronize()
+            if frozenset(PAIR_NAMES[n] for n in pair) in refused_in_python:
+                assert rc == L.ERR_UNSUPPORTED, (pair, rc, gm.lib.fmi_last_error())
+                np.testing.assert_array_equal(host(img).view(np.uint32), s["img"].view(np.uint32), err_msg=str(pair))
+            else:
+                assert rc == 0, (pair, rc, gm.lib.fmi_last_error())
+                assert np.isfinite(host(img)).all() and not np.array_equal(host(img), s["img"]), pair
+    finally:
+        net.close(), ada.close()

@@ -139,11 +139,11 @@ def test_check_control_args():
         with pytest.raises(ValueError, match="control is"):
             chk(64, img, bad)
     with pytest.raises(ValueError, match="context="):
-        chk(64, img, (2, 24, 64), has_context=True)
+        F.check_combination({"control", "context"})
     with pytest.raises(ValueError, match="step cache"):
-        chk(64, img, (2, 24, 64), cache_args=True)
+        F.check_combination({"control", "cache"})
     with pytest.raises(ValueError, match="sequence parallelism"):
-        chk(64, img, (2, 24, 64), sequence_parallel=True)
+        F.check_combination({"control", "sequence_parallel"})
 
 
 def test_check_control_request():
@@ -175,11 +175,11 @@ def test_check_control_request():
     with pytest.raises(ValueError, match="control_mask must be"):
         chk("fill", H, W, (1, 3, H, W), False, (1, H, W))
     with pytest.raises(ValueError, match="reference="):
-        chk("control", H, W, (1, 3, H, W), reference=True)
+        F.check_combination({"control", "context"}, pl.REQUEST_NAMES)
     with pytest.raises(ValueError, match="step cache"):
-        chk("control", H, W, (1, 3, H, W), cache_threshold=True)
+        F.check_combination({"control", "cache"}, pl.REQUEST_NAMES)
     with pytest.raises(ValueError, match="sequence parallelism"):
-        chk("control", H, W, (1, 3, H, W), sequence_parallel=True)
+        F.check_combination({"control", "sequence_parallel"}, pl.REQUEST_NAMES)
 
 
 # ------------------------------------------------------------------------------------------------ the request path
@@ -217,7 +217,7 @@ def test_samples_has_no_control_field_and_the_chunk_signature_ends_with_it():
     with pytest.raises(dataclasses.FrozenInstanceError):
         pl._Control("control", torch.zeros(1, 3, H, W)).kind = "fill"
     assert list(inspect.signature(pl.Pipeline._generate_chunk).parameters) == ["self", "s", "params", "seed", "strength", "return_latents", "cache_threshold", "stats",
-                                                                               "negative", "control"]
+                                                                               "negative", "control", "controlnet", "ip_adapter"]
 
 
 def test_one_control_is_shared_by_every_chunk():

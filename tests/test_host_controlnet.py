@@ -251,13 +251,13 @@ def test_check_controlnet_args():
     with pytest.raises(ValueError, match="one entry per step"):
         chk(main, net, img, (2, 24, 64), 1.0, [1, 1, 1], 4)
     with pytest.raises(ValueError, match="context="):
-        chk(main, net, img, (2, 24, 64), has_context=True)
+        F.check_combination({"controlnet", "context"})
     with pytest.raises(ValueError, match="channel-conditioned"):
-        chk(main, net, img, (2, 24, 64), cond_channels=64)
+        F.check_combination({"controlnet", "control"})
     with pytest.raises(ValueError, match="step cache"):
-        chk(main, net, img, (2, 24, 64), cache_args=True)
+        F.check_combination({"controlnet", "cache"})
     with pytest.raises(ValueError, match="sequence parallelism"):
-        chk(main, net, img, (2, 24, 64), sequence_parallel=True)
+        F.check_combination({"controlnet", "sequence_parallel"})
     # a negative scale is a scale: -2 passes
     assert chk(main, net, img, (2, 24, 64), -2.0) is None
 
@@ -278,10 +278,9 @@ def test_check_controlnet_request_and_the_request_path():
     for start, end in ((-0.1, 1.0), (0.0, 1.5), (0.75, 0.5)):
         with pytest.raises(ValueError, match="control_guidance_start"):
             chk(True, 64, 64, (64, 64, 3), True, 1.0, start, end)
-    for kw, msg in ((dict(reference=True), "reference="), (dict(cache_threshold=True), "step cache"), (dict(cond_channels=64), "channel-conditioned"),
-                    (dict(sequence_parallel=True), "sequence parallelism")):
+    for other, msg in (("context", "reference="), ("cache", "step cache"), ("control", "channel-conditioned"), ("sequence_parallel", "sequence parallelism")):
         with pytest.raises(ValueError, match=msg):
-            chk(True, 64, 64, (64, 64, 3), True, **kw)
+            F.check_combination({"controlnet", other}, pl.REQUEST_NAMES)
     # the control image is ONE per request: a per-request object like the negative and the control, never a field of _Samples
     assert "controlnet_image" not in [f.name for f in dataclasses.fields(pl._Samples)]
     assert [f.name for f in dataclasses.fields(pl._ControlNetInput)] == ["image", "scale", "start", "end"]
@@ -289,7 +288,8 @@ def test_check_controlnet_request_and_the_request_path():
         p = inspect.signature(fn).parameters
         assert (p["controlnet_image"].default, p["controlnet_conditioning_scale"].default, p["control_guidance_start"].default, p["control_guidance_end"].default) == \
             (None, 1.0, 0.0, 1.0)
-    assert list(inspect.signature(pl.Pipeline._generate_chunk).parameters)[-1] == "control"  # the request's ONE control object: a _Control or a _ControlNetInput
+    assert "controlnet" in inspect.signature(pl.Pipeline._generate_chunk).parameters  # a keyword of its own, like every shared option
+    assert "control" not in [f.name for f in dataclasses.fields(pl._IpAdapterInput)]  # ... and none of them carries another inside
     assert hasattr(pl.Pipeline, "load_controlnet") and hasattr(pl.Pipeline, "unload_controlnet")
     for fn, names in ((F.FluxModel.forward, ("controlnet", "controlnet_cond", "controlnet_scale")),
                       (F.FluxModel.denoise, ("controlnet", "controlnet_cond", "controlnet_scale", "controlnet_step_scales"))):

@@ -144,11 +144,13 @@ def test_flux_layer_refusals_without_a_device():
            (dict(adapter=dict(ADA, num_layers=2)), "num_layers"), (dict(adapter=dict(ADA, num_tokens=33)), "1 <= N <= 32"), (dict(adapter=dict(ADA, num_tokens=0)), "1 <= N <= 32"),
            (dict(negative_embeds_shape=(2, IR.E)), "needs a negative prompt"), (dict(negative_embeds_shape=(2, 8), has_negative=True), "expected"),
            (dict(scale=float("nan")), "finite"), (dict(scale=float("inf")), "finite"), (dict(step_scales=[1, 2, 3], n_steps=4), "one entry per step"),
-           (dict(step_scales=[1, float("nan"), 1, 1], n_steps=4), "finite"), (dict(has_context=True), "context="), (dict(cache_args=True), "step cache"),
-           (dict(sequence_parallel=True), "sequence parallelism"), (dict(eight_bit="fp8"), "fp8 mode"), (dict(eight_bit="int8"), "int8 mode")]
+           (dict(step_scales=[1, float("nan"), 1, 1], n_steps=4), "finite")]
     for kw, msg in bad:
         with pytest.raises(ValueError, match=msg):
             F.check_ip_adapter_args(**dict(ok, **kw))
+    for other, msg in (("context", "context="), ("cache", "step cache"), ("sequence_parallel", "sequence parallelism"), ("fp8", "fp8 mode"), ("int8", "int8 mode")):
+        with pytest.raises(ValueError, match=msg):
+            F.check_combination({"ip_adapter", other})
 
 
 def test_pipeline_layer_refusals_without_a_device():
@@ -162,12 +164,13 @@ def test_pipeline_layer_refusals_without_a_device():
            (dict(embeds_shape=(E,), negative_embeds_shape=(2, E), has_negative=True), "one embedding per request"),
            (dict(embeds_shape=(E,), negative_embeds_shape=(E,)), "negative prompt"), (dict(embeds_shape=(E,), scale=float("nan")), "finite"),
            (dict(embeds_shape=(E,), start=0.6, end=0.5), "0 <= start <= end <= 1"), (dict(embeds_shape=(E,), end=1.5), "0 <= start <= end <= 1"),
-           (dict(embeds_shape=(E,), start=-0.1), "0 <= start <= end <= 1"), (dict(embeds_shape=(E,), reference=True), "reference="),
-           (dict(embeds_shape=(E,), cache_threshold=True), "step cache"), (dict(embeds_shape=(E,), sequence_parallel=True), "sequence parallelism"),
-           (dict(embeds_shape=(E,), eight_bit="int8"), "int8 mode"), (dict(embeds_shape=(E,), eight_bit="fp8"), "fp8 mode")]
+           (dict(embeds_shape=(E,), start=-0.1), "0 <= start <= end <= 1")]
     for kw, msg in bad:
         with pytest.raises(ValueError, match=msg):
             P.check_ip_adapter_request(**dict(dict(loaded=True, embed_dim=E), **kw))
+    for other, msg in (("context", "reference="), ("cache", "step cache"), ("sequence_parallel", "sequence parallelism"), ("int8", "int8 mode"), ("fp8", "fp8 mode")):
+        with pytest.raises(ValueError, match=msg):
+            F.check_combination({"ip_adapter", other}, P.REQUEST_NAMES)
     assert IR.keep(4, 0.25, 0.75) == F.controlnet_step_scales(4, 0.25, 0.75) == [0.0, 1.0, 1.0, 0.0]
 
 

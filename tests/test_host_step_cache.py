@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from diffusion_rs_amd import _lib as L
-from diffusion_rs_amd.flux import check_step_cache_args
+from diffusion_rs_amd.flux import check_combination, check_step_cache_args
 from tests import step_cache_ref as R
 from tests.util import rel_l2
 
@@ -69,11 +69,11 @@ def test_argument_checker():
         check_step_cache_args(3, 0.1, [0, 2, 0])
     with pytest.raises(ValueError, match=r"cache_force\[0\]"):
         check_step_cache_args(3, 0.1, [1, 0, 0])
-    with pytest.raises(ValueError, match="sequence parallelism"):
-        check_step_cache_args(8, 0.1, None, sequence_parallel=True)
-    with pytest.raises(ValueError, match="sequence parallelism"):
-        check_step_cache_args(3, None, [0, 0, 0], sequence_parallel=True)
-    assert check_step_cache_args(8, None, None, sequence_parallel=True) == (None, None)  # no cache asked for: nothing to refuse
+    for n, thr, force in ((8, 0.1, None), (3, None, [0, 0, 0])):  # either of them asks for the cache (a threshold comes back): "cache" is present
+        assert check_step_cache_args(n, thr, force)[0] is not None
+        with pytest.raises(ValueError, match="sequence parallelism"):
+            check_combination({"cache", "sequence_parallel"})
+    assert check_step_cache_args(8, None, None) == (None, None) and check_combination({"sequence_parallel"}) is None  # no cache asked for: nothing to refuse
 
 
 def test_new_symbols_are_declared_exported_and_bound():

@@ -81,9 +81,9 @@ def test_check_true_cfg_args():
         with pytest.raises(ValueError, match="finite and >= 0"):
             chk(txt, y, txt, y, bad)
     with pytest.raises(ValueError, match="step cache"):
-        chk(txt, y, txt, y, 4.0, cache_args=True)
+        F.check_combination({"true_cfg", "cache"})
     with pytest.raises(ValueError, match="sequence parallelism"):
-        chk(txt, y, txt, y, 4.0, sequence_parallel=True)
+        F.check_combination({"true_cfg", "sequence_parallel"})
 
 
 # ------------------------------------------------------------------------------------------------ the request path
