@@ -331,6 +331,117 @@ def load_ip_adapter(path: str, cfg: dict):
     return ip_adapter_from_tensors(cfg, dict(_safetensors_from_buffer(memoryview(mm))), os.path.basename(path))
 
 
+from .text import CLIP_IMAGE_MEAN, CLIP_IMAGE_STD, CLIP_VISION_L  # noqa: E402
+
+CLIP_VISION_KEYS = tuple(CLIP_VISION_L)
+
+
+def clip_vision_config(config: dict) -> dict:
+    """The vision tower's configuration (CLIP_VISION_KEYS) from a config.json: a CLIPVisionConfig, or a full CLIPConfig, whose `vision_config` is used (with the
+    top level's projection_dim where the nested one has none).  ValueError by name for a missing field, an activation other than quick_gelu and a
+    layer_norm_eps other than 1e-5 — what the kernels compute."""
+    if not isinstance(config, dict):
+        raise ValueError("config.json of an image encoder must hold an object")
+    vc = config
+    if isinstance(config.get("vision_config"), dict):
+        vc = dict(config["vision_config"])
+        vc.setdefault("projection_dim", config.get("projection_dim"))
+    elif config.get("model_type") not in (None, "clip_vision_model"):
+        raise ValueError(f"config.json has model_type {config.get('model_type')!r} and no vision_config: a CLIPVisionConfig or a CLIPConfig is expected "
+                         f"(SigLIP and other towers are not supported)")
+    missing = [k for k in CLIP_VISION_KEYS if vc.get(k) is None]
+    if missing:
+        raise ValueError(f"the image encoder's config.json lacks {missing}")
+    if vc.get("hidden_act", "quick_gelu") != "quick_gelu":
+        raise ValueError(f"the image encoder's hidden_act is {vc['hidden_act']!r}: only quick_gelu (CLIP ViT-L/14) is supported")
+    if abs(float(vc.get("layer_norm_eps", 1e-5)) - 1e-5) > 1e-12:
+        raise ValueError(f"the image encoder's layer_norm_eps is {vc['layer_norm_eps']!r}: only 1e-05 is supported")
+    if int(vc.get("num_channels", 3)) != 3:
+        raise ValueError(f"the image encoder's num_channels is {vc['num_channels']!r}: only 3 (RGB) is supported")
+    return {k: int(vc[k]) for k in CLIP_VISION_KEYS}
+
+
+def clip_image_processor(pre: Optional[dict], image_size: int) -> Tuple[tuple, tuple]:
+    """(image_mean, image_std) of a preprocessor_config.json (None: CLIP's constants).  What ClipVisionModel.preprocess does is fixed — bicubic resize of the
+    shortest edge to image_size, centre crop to image_size, rescale by 1 / 255, normalise — so a processor that asks for anything else is refused by name."""
+    if pre is None:
+        return CLIP_IMAGE_MEAN, CLIP_IMAGE_STD
+    for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
+        if not pre.get(flag, True):
+            raise ValueError(f"preprocessor_config.json has {flag} = false: the image encoder always resizes, centre-crops, rescales and normalises")
+    if int(pre.get("resample", 3)) != 3:
+        raise ValueError(f"preprocessor_config.json has resample = {pre['resample']!r}: only 3 (PIL's BICUBIC) is supported")
+    if abs(float(pre.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
+        raise ValueError(f"preprocessor_config.json has rescale_factor = {pre['rescale_factor']!r}: only 1 / 255 is supported")
+
+    def edge(v, keys):
+        if isinstance(v, dict):
+            vals = {int(v[k]) for k in keys if k in v}
+            if len(vals) != 1 or set(v) - set(keys):
+                return None
+            return vals.pop()
+        return None if v is None else int(v)
+
+    size, crop = pre.get("size", image_size), pre.get("crop_size", image_size)
+    if edge(size, ("shortest_edge",)) != image_size:
+        raise ValueError(f"preprocessor_config.json has size = {size!r}: the shortest edge is resized to the model's image_size = {image_size}")
+    if edge(crop, ("height", "width")) != image_size:
+        raise ValueError(f"preprocessor_config.json has crop_size = {crop!r}: the centre crop is the model's image_size = {image_size}")
+    mean, std = pre.get("image_mean", CLIP_IMAGE_MEAN), pre.get("image_std", CLIP_IMAGE_STD)
+    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
+        raise ValueError(f"preprocessor_config.json: image_mean / image_std must hold 3 values, the std positive, got {mean!r} / {std!r}")
+    return tuple(float(m) for m in mean), tuple(float(s) for s in std)
+
+
+def _clip_vision_ignored(name: str) -> bool:
+    """The keys of a full CLIP checkpoint (openai/clip-vit-large-patch14) the vision tower does not read: the text tower, its projection, the logit scale, and
+    the position_ids buffer older checkpoints carry."""
+    return name.startswith("text_model.") or name in ("text_projection.weight", "logit_scale", "vision_model.embeddings.position_ids")
+
+
+def clip_vision_from_tensors(cfg: dict, tensors, where: str = "image encoder") -> dict:
+    """{name: tensor} of the vision tower of configuration cfg from a CLIPVisionModelWithProjection or a full CLIPModel checkpoint's tensors.  ValueError naming
+    the keys: an unexpected tensor (anything but the ignored ones of a full checkpoint), a missing one, a shape that does not fit cfg."""
+    want = synth.clip_vision_tensor_shapes(cfg)
+    sd, unexpected = {}, []
+    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
+        if name in want:
+            sd[name] = t
+        elif not _clip_vision_ignored(name):
+            unexpected.append(name)
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not CLIPVisionModelWithProjection's), e.g. {sorted(unexpected)[:3]}")
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise ValueError(f"{where}: {len(missing)} image-encoder tensors missing, e.g. {missing[:3]}")
+    for k, t in sd.items():
+        if tuple(t.shape) != tuple(want[k]):
+            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
+    return sd
+
+
+def load_clip_vision(path: str):
+    """A CLIP image-encoder directory — config.json (a CLIPVisionConfig or a full CLIPConfig) next to *.safetensors, with an optional preprocessor_config.json —
+    as (cfg, {name: tensor}): cfg holds CLIP_VISION_KEYS plus image_mean / image_std, what Pipeline.load_image_encoder and ClipVisionModel take.  No device is
+    touched.  ValueError as clip_vision_config's, clip_image_processor's and clip_vision_from_tensors'."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"{path}: not a directory (an image encoder is a directory: config.json + *.safetensors)")
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = clip_vision_config(json.load(f))
+    pre = None
+    if os.path.isfile(os.path.join(path, "preprocessor_config.json")):
+        with open(os.path.join(path, "preprocessor_config.json")) as f:
+            pre = json.load(f)
+    mean, std = clip_image_processor(pre, cfg["image_size"])
+    tensors = {}
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with open(os.path.join(path, fn), "rb") as f:
+                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            tensors.update(_safetensors_from_buffer(memoryview(mm)))
+    return dict(cfg, image_mean=mean, image_std=std), clip_vision_from_tensors(cfg, tensors, os.path.basename(os.path.normpath(path)))
+
+
 def load_vae(vae, tensors: Iterator[Tuple[str, torch.Tensor]]) -> int:
     want = synth.vae_tensor_shapes(vae.cfg, encoder=True)  # encoder tensors are loaded when the checkpoint has them
     n = 0

@@ -281,17 +281,42 @@ class _IpAdapterInput:
 
 
 def check_ip_adapter_request(loaded: bool, embed_dim: int = 0, embeds_shape=None, negative_embeds_shape=None, scale: float = 1.0, start: float = 0.0, end: float = 1.0,
-                             has_negative: bool = False):
+                             has_negative: bool = False, *, image_shape=None, image_is_u8: bool = False, negative_image_shape=None, negative_image_is_u8: bool = False,
+                             encoder_dim: Optional[int] = None, encoder_image_size: int = 0):
     """The IP-Adapter arguments of a request, checked without a device.  ValueError: ip_adapter_image_embeds= without a loaded adapter (Pipeline.load_ip_adapter);
     negative_ip_adapter_image_embeds= without ip_adapter_image_embeds= or without a negative prompt; embeddings that are not (embed_dim,) or (1, embed_dim) — one per
     request, shared by its prompts; a scale that is not finite; ip_adapter_start / ip_adapter_end outside 0 <= start <= end <= 1.  A request without
-    ip_adapter_image_embeds= is not conditioned, whatever is loaded."""
-    if embeds_shape is None:
+    ip_adapter_image_embeds= is not conditioned, whatever is loaded.
+
+    The keyword arguments are the picture form of the same prompt: image_shape / negative_image_shape (with *_is_u8) are the shapes of
+    ip_adapter_image= / negative_ip_adapter_image=, encoder_dim the loaded image encoder's projection_dim (None: none loaded) and encoder_image_size its S.
+    ValueError: a picture together with the embedding of the same side; a picture without a loaded adapter or without a loaded encoder
+    (Pipeline.load_image_encoder); an encoder whose projection_dim is not the adapter's embed_dim; a picture that is not u8 (H,W,3) or float (1,3,S,S); a
+    negative without a positive, or without a negative prompt.  Everything else is checked as for the embeddings the pictures become."""
+    for img, emb, nm in ((image_shape, embeds_shape, "ip_adapter_image"), (negative_image_shape, negative_embeds_shape, "negative_ip_adapter_image")):
+        if img is not None and emb is not None:
+            raise ValueError(f"{nm}= and {nm}_embeds= exclude one another: a request has one image prompt")
+    if image_shape is None and embeds_shape is None:
         if negative_embeds_shape is not None:
             raise ValueError("negative_ip_adapter_image_embeds= needs ip_adapter_image_embeds=")
+        if negative_image_shape is not None:
+            raise ValueError("negative_ip_adapter_image= needs ip_adapter_image= (or ip_adapter_image_embeds=)")
         return
+    given = "ip_adapter_image" if image_shape is not None else "ip_adapter_image_embeds"
     if not loaded:
-        raise ValueError("ip_adapter_image_embeds= needs a loaded IP-Adapter: Pipeline.load_ip_adapter(path) first")
+        raise ValueError(f"{given}= needs a loaded IP-Adapter: Pipeline.load_ip_adapter(path) first")
+    if image_shape is not None or negative_image_shape is not None:
+        nm = "ip_adapter_image" if image_shape is not None else "negative_ip_adapter_image"
+        if encoder_dim is None:
+            raise ValueError(f"{nm}= needs a loaded image encoder: Pipeline.load_image_encoder(path) first (or pass {nm}_embeds=)")
+        if int(encoder_dim) != int(embed_dim):
+            raise ValueError(f"the image encoder's projection_dim is {encoder_dim}, the IP-Adapter's embed_dim {embed_dim}: {nm}= cannot feed this adapter")
+        S = int(encoder_image_size)
+        for shp, u8, what in ((image_shape, image_is_u8, "ip_adapter_image"), (negative_image_shape, negative_image_is_u8, "negative_ip_adapter_image")):
+            if shp is not None and not ((len(shp) == 3 and shp[2] == 3 and min(shp[:2]) > 0) if u8 else tuple(shp) == (1, 3, S, S)):
+                raise ValueError(f"{what} must be a uint8 (H,W,3) picture of any size or float (1,3,{S},{S}) pixel_values, one per request, got {tuple(shp)}")
+    if negative_image_shape is not None and not has_negative:
+        raise ValueError("negative_ip_adapter_image= needs a negative prompt (true classifier-free guidance)")
     for shp, nm in ((embeds_shape, "ip_adapter_image_embeds"), (negative_embeds_shape, "negative_ip_adapter_image_embeds")):
         if shp is not None and tuple(shp) not in ((embed_dim,), (1, embed_dim)):
             raise ValueError(f"{nm} must be ({embed_dim},) or (1,{embed_dim}), one embedding per request, got {tuple(shp)}")
@@ -557,7 +582,8 @@ class Pipeline:
                         negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
-                        negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0):
+                        negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
+                        ip_adapter_image=None, negative_ip_adapter_image=None):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -607,14 +633,18 @@ class Pipeline:
         conditioning scale is recommended: there are no real weights here to judge one.
 
         Image prompts (`ip_adapter_image_embeds=` with an IP-Adapter loaded by load_ip_adapter; diffusers' ip_adapter_image_embeds): ONE image
-        embedding per request, (E,) or (1,E), shared by its prompts.  A CLIP vision encoder is out of scope: the embedding is supplied.  Step i of the n steps
+        embedding per request, (E,) or (1,E), shared by its prompts — or `ip_adapter_image=`, the picture itself, with a CLIP vision encoder loaded by
+        load_image_encoder: u8 (H,W,3) of any size, as output="rgb" returns it, or f32 (1,3,S,S) pixel_values that are already preprocessed; it is
+        encoded once, before the request is chunked, and is from there on the embedding encode_image returns.  `negative_ip_adapter_image=` likewise for
+        negative_ip_adapter_image_embeds=.  A picture and the embedding of the same side exclude one another.  Step i of the n steps
         actually run adds the image-prompt attention in every double block at ip_adapter_scale * keep_i, keep_i = 0 if i / n < ip_adapter_start or
         (i + 1) / n > ip_adapter_end else 1; a step with scale 0 is the plain step.  Under a negative prompt the negative half attends to
         negative_ip_adapter_image_embeds=, or to zero embeddings through the same projection.  Combines with the negative, image= / strength= / mask=, a Fill /
         Canny / Depth control and a ControlNet; raises with reference=, cache_threshold=, under sequence parallelism, on an 8-bit transformer and without a loaded
         adapter."""
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
-                                     negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None)
+                                     negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
+                                     image=ip_adapter_image, negative_image=negative_ip_adapter_image)
         cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params)
         F.check_step_cache_args(params.num_steps, cache_threshold)
         ctl = self._control(control_image, control_mask, params)
@@ -663,17 +693,26 @@ class Pipeline:
         check_controlnet_request(getattr(self, "controlnet", None) is not None, params.height, params.width, tuple(img.shape), img.dtype == torch.uint8, scale, start, end)
         return _ControlNetInput(self._device_image(img.unsqueeze(0) if img.dtype == torch.uint8 else img), float(scale), float(start), float(end))
 
-    def _ip_adapter_input(self, embeds, negative_embeds, scale, start, end, has_negative) -> Optional[_IpAdapterInput]:
-        """The image prompt of a request, checked once and brought to its device form: None without ip_adapter_image_embeds=, else the object its chunks share."""
+    def _ip_adapter_input(self, embeds, negative_embeds, scale, start, end, has_negative, *, image=None, negative_image=None) -> Optional[_IpAdapterInput]:
+        """The image prompt of a request, checked once and brought to its device form: None without ip_adapter_image_embeds= / ip_adapter_image=, else the object
+        its chunks share.  A picture (image= / negative_image=) is encoded here, once, by the loaded image encoder: from here on it is its embedding."""
         def as_tensor(x, what):
             t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
             if x is not None and not (isinstance(t, torch.Tensor) and t.is_floating_point()):
                 raise ValueError(f"{what} must be a float numpy array or torch tensor")
             return t
         e, n = as_tensor(embeds, "ip_adapter_image_embeds"), as_tensor(negative_embeds, "negative_ip_adapter_image_embeds")
-        ada = getattr(self, "ip_adapter", None)
-        check_ip_adapter_request(ada is not None, 0 if ada is None else ada.embed_dim, None if e is None else tuple(e.shape), None if n is None else tuple(n.shape), scale,
-                                 start, end, has_negative)
+        img = None if image is None else _host_image(image, "ip_adapter_image")
+        nimg = None if negative_image is None else _host_image(negative_image, "negative_ip_adapter_image")
+        ada, enc = getattr(self, "ip_adapter", None), getattr(self, "image_encoder", None)
+        shape, is_u8 = (lambda t: None if t is None else tuple(t.shape)), (lambda t: t is not None and t.dtype == torch.uint8)
+        check_ip_adapter_request(ada is not None, 0 if ada is None else ada.embed_dim, shape(e), shape(n), scale, start, end, has_negative, image_shape=shape(img),
+                                 image_is_u8=is_u8(img), negative_image_shape=shape(nimg), negative_image_is_u8=is_u8(nimg),
+                                 encoder_dim=None if enc is None else enc.projection_dim, encoder_image_size=0 if enc is None else enc.cfg["image_size"])
+        if img is not None or nimg is not None:
+            with self._lock:
+                e = e if img is None else enc.encode(img)
+                n = n if nimg is None else enc.encode(nimg)
         if e is None:
             return None
         dev = lambda t: None if t is None else t.to(device=self.device, dtype=torch.float32).reshape(1, -1).contiguous()
@@ -683,7 +722,8 @@ class Pipeline:
         """Load ONE IP-Adapter next to the transformer: a .safetensors file under XLabs' names (ip_adapter_proj_model.*, double_blocks.{i}.processor.
         ip_adapter_double_stream_{k,v}_proj.*) or the diffusers-converted ones (image_proj.*, ip_adapter.{i}.to_{k,v}_ip.*), or a {name: tensor} dict of either.  The
         number of tokens and the embedding width are read from the shapes; missing and unexpected keys raise ValueError by name.  It replaces a loaded one; requests
-        use it only when they pass ip_adapter_image_embeds=.  A CLIP vision encoder is not part of this package: embeddings are supplied."""
+        use it only when they pass ip_adapter_image_embeds= — or ip_adapter_image=, a picture, once load_image_encoder has loaded the CLIP vision encoder whose
+        projection_dim is the adapter's embedding width."""
         from . import loader
         if isinstance(source, (str, os.PathLike)):
             E, N, sd = loader.load_ip_adapter(os.fspath(source), self.flux.cfg)
@@ -702,6 +742,46 @@ class Pipeline:
             ada, self.ip_adapter = getattr(self, "ip_adapter", None), None
             if ada is not None:
                 ada.close()
+
+    def load_image_encoder(self, source):
+        """Load ONE CLIP vision encoder (openai/clip-vit-large-patch14 is what the FLUX IP-Adapters were trained with): a directory (loader.
+        load_clip_vision: config.json — a CLIPVisionConfig or a full CLIPConfig — next to *.safetensors and an optional preprocessor_config.json) or a (cfg,
+        {name: tensor}) pair, cfg holding CLIPVisionConfig's keys and optionally image_mean / image_std.  Missing and unexpected keys raise ValueError by name; a
+        full CLIP checkpoint's text tower is ignored.  It replaces a loaded one; requests use it only when they pass ip_adapter_image= /
+        negative_ip_adapter_image=, and encode_image."""
+        from . import loader, text
+        if isinstance(source, (str, os.PathLike)):
+            cfg, sd = loader.load_clip_vision(os.fspath(source))
+        else:
+            cfg, sd = source
+            cfg = dict(loader.clip_vision_config(cfg), **{k: cfg[k] for k in ("image_mean", "image_std") if k in cfg})
+            sd = loader.clip_vision_from_tensors(cfg, sd)
+        with self._lock:
+            enc = text.ClipVisionModel(cfg, self.device.index or 0, cfg.get("image_mean"), cfg.get("image_std"))
+            enc.load_state_dict(sd)
+            old, self.image_encoder = getattr(self, "image_encoder", None), enc
+            if old is not None:
+                old.close()
+        return enc
+
+    def unload_image_encoder(self):
+        with self._lock:
+            enc, self.image_encoder = getattr(self, "image_encoder", None), None
+            if enc is not None:
+                enc.close()
+
+    def encode_image(self, image) -> torch.Tensor:
+        """The image prompt of a picture: u8 (H,W,3) of any size, or float (1,3,S,S) pixel_values -> (1,E) f32 on the device, what ip_adapter_image_embeds= takes and
+        what ip_adapter_image= passes on.  ValueError without a loaded image encoder."""
+        enc = getattr(self, "image_encoder", None)
+        if enc is None:
+            raise ValueError("encode_image needs a loaded image encoder: Pipeline.load_image_encoder(path) first")
+        img = _host_image(image, "image")
+        S = enc.cfg["image_size"]
+        if not ((img.dim() == 3 and img.shape[2] == 3) if img.dtype == torch.uint8 else tuple(img.shape) == (1, 3, S, S)):
+            raise ValueError(f"image must be a uint8 (H,W,3) picture of any size or float (1,3,{S},{S}) pixel_values, got {tuple(img.shape)}")
+        with self._lock:
+            return enc.encode(img)
 
     def load_controlnet(self, source):
         """Load ONE ControlNet next to the transformer: a diffusers directory (loader.load_controlnet: config.json with _class_name
@@ -962,7 +1042,8 @@ class Pipeline:
                 reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
                 negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
-                negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0, **kw):
+                negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
+                ip_adapter_image=None, negative_ip_adapter_image=None, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
@@ -974,7 +1055,9 @@ class Pipeline:
         controlnet_image= / controlnet_conditioning_scale= / control_guidance_start= / control_guidance_end=: the ControlNet of load_controlnet, see generate_tensor —
         one control image per request, likewise (every rank loads the same ControlNet).
         ip_adapter_image_embeds= / negative_ip_adapter_image_embeds= / ip_adapter_scale= / ip_adapter_start= / ip_adapter_end=: the image prompt of the IP-Adapter of
-        load_ip_adapter, see generate_tensor — one embedding per request, likewise (every rank loads the same adapter)."""
+        load_ip_adapter, see generate_tensor — one embedding per request, likewise (every rank loads the same adapter).  ip_adapter_image= /
+        negative_ip_adapter_image=: the same prompt as a picture, encoded by the image encoder of load_image_encoder (every rank loads the same one and encodes
+        the picture itself)."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -983,7 +1066,7 @@ class Pipeline:
                        controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
-                       ip_adapter_end=ip_adapter_end)
+                       ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

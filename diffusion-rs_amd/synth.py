@@ -546,13 +546,43 @@ def clip_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     return out
 
 
+def clip_vision_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
+    """Tensor names/shapes of HuggingFace's CLIPVisionModelWithProjection (the vision half of a CLIPModel checkpoint), cfg: CLIPVisionConfig's keys."""
+    D, F, P = cfg["hidden_size"], cfg["intermediate_size"], cfg["patch_size"]
+    out = OrderedDict()
+    vm = "vision_model."
+    out[vm + "embeddings.class_embedding"] = (D,)
+    out[vm + "embeddings.patch_embedding.weight"] = (D, 3, P, P)
+    out[vm + "embeddings.position_embedding.weight"] = (1 + (cfg["image_size"] // P) ** 2, D)
+    out[vm + "pre_layrnorm.weight"] = (D,)  # (HuggingFace's spelling)
+    out[vm + "pre_layrnorm.bias"] = (D,)
+    for l in range(cfg["num_hidden_layers"]):
+        p = vm + f"encoder.layers.{l}."
+        for ln in ("layer_norm1", "layer_norm2"):
+            out[p + ln + ".weight"] = (D,)
+            out[p + ln + ".bias"] = (D,)
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            out[p + f"self_attn.{n}.weight"] = (D, D)
+            out[p + f"self_attn.{n}.bias"] = (D,)
+        out[p + "mlp.fc1.weight"] = (F, D)
+        out[p + "mlp.fc1.bias"] = (F,)
+        out[p + "mlp.fc2.weight"] = (D, F)
+        out[p + "mlp.fc2.bias"] = (D,)
+    out[vm + "post_layernorm.weight"] = (D,)
+    out[vm + "post_layernorm.bias"] = (D,)
+    out["visual_projection.weight"] = (cfg["projection_dim"], D)
+    return out
+
+
 def text_state_dict_numpy(shapes, seed=0, round_bf16=True):
-    """Seeded synthetic encoder weights: matrices ~N(0, 1/fan_in), embeddings ~N(0,1) (T5 relative
+    """Seeded synthetic encoder weights: matrices ~N(0, 1/fan_in) (a convolution's (out, in, k, k) weight too), embeddings ~N(0,1) (T5 relative
     bias ~N(0,1)), norm weights 1 + 0.1 N(0,1), biases 0.1 N(0,1); rounded to bf16 values."""
     rng = np.random.default_rng(seed)
     sd = OrderedDict()
     for name, shp in shapes.items():
-        if len(shp) == 2 and ("embedding" in name or name == "shared.weight" or "relative_attention_bias" in name):
+        if len(shp) == 4:
+            a = rng.standard_normal(shp) / np.sqrt(shp[1] * shp[2] * shp[3])
+        elif len(shp) == 2 and ("embedding" in name or name == "shared.weight" or "relative_attention_bias" in name):
             a = rng.standard_normal(shp)
         elif len(shp) == 2:
             a = rng.standard_normal(shp) / np.sqrt(shp[1])
@@ -573,7 +603,9 @@ def fill_text_random_device(model, seed=0, device="cuda"):
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     for name, shp in model.tensor_names().items():
-        if len(shp) == 2 and ("embedding" in name or name == "shared.weight" or "relative_attention_bias" in name):
+        if len(shp) == 4:
+            t = torch.randn(shp, generator=g, device=device) / (shp[1] * shp[2] * shp[3]) ** 0.5
+        elif len(shp) == 2 and ("embedding" in name or name == "shared.weight" or "relative_attention_bias" in name):
             t = torch.randn(shp, generator=g, device=device)
         elif len(shp) == 2:
             t = torch.randn(shp, generator=g, device=device) / shp[1] ** 0.5

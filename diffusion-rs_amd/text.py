@@ -2,6 +2,7 @@
 
     T5EncoderModel        <-> diffusion_rs_core::models::t5::T5EncoderModel        (t5/mod.rs:609-632)
     ClipTextTransformer   <-> diffusion_rs_core::models::clip::text::ClipTextTransformer (clip/text.rs:243-317)
+    ClipVisionModel       <-> HuggingFace's CLIPVisionModelWithProjection + CLIPImageProcessor (not in the reference)
     tokenize_and_pad      <-> FluxPipeline::tokenize_and_pad (pipelines/flux/mod.rs:202-221)
     load_bpe_tokenizer    <-> diffusion_rs_common::load_bpe_tokenizer (tokenizer.rs:7-23)
 
@@ -21,6 +22,10 @@ T5_XXL = dict(vocab_size=32128, d_model=4096, d_kv=64, d_ff=10240, num_layers=24
               relative_attention_max_distance=128, layer_norm_epsilon=1e-6, feed_forward_proj="gated-gelu")
 CLIP_L = dict(vocab_size=49408, projection_dim=768, intermediate_size=3072, max_position_embeddings=77, num_hidden_layers=12, num_attention_heads=12)
 _T5_ACT = {"relu": 0, "gated-gelu": 1, "gated-silu": 2}
+# openai/clip-vit-large-patch14's vision tower and its image processor's constants (preprocessor_config.json)
+CLIP_VISION_L = dict(image_size=224, patch_size=14, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, projection_dim=768)
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 class _Encoder:
@@ -143,6 +148,95 @@ class ClipTextTransformer(_Encoder):
         hid = torch.empty((B, T, D), dtype=torch.float32, device=self.device) if return_hidden else None
         L.check(self.lib.fmi_clip_forward(self.h, _ptr(ids), B, T, _ptr(pooled), L.F32, _ptr(hid) if hid is not None else None, _stream()), self.lib)
         return (pooled, hid) if return_hidden else pooled
+
+
+def clip_resize_shape(h: int, w: int, size: int):
+    """(nh, nw) of CLIP's resize: the shortest edge becomes `size`, the long one int(size * long / short) — transformers' get_resize_output_image_size with
+    default_to_square=False, Python's float division and truncation included."""
+    if h <= 0 or w <= 0 or size <= 0:
+        raise ValueError(f"an image of {h} x {w} cannot be resized to a shortest edge of {size}")
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(size * long / short)
+    return (new_long, size) if w <= h else (size, new_long)
+
+
+def clip_crop_offsets(nh: int, nw: int, size: int):
+    """(top, left) of the centre crop of an (nh, nw) image to size x size: what fmi_clip_preprocess_u8 computes."""
+    if nh < size or nw < size:
+        raise ValueError(f"a centre crop to {size} x {size} needs an image of at least that size, got {nh} x {nw}")
+    return (nh - size) // 2, (nw - size) // 2
+
+
+class ClipVisionModel(_Encoder):
+    """CLIP's vision tower with its projection and its image processor on the GPU: a picture -> image_embeds (1, projection_dim), what
+    ip_adapter_image_embeds= takes.  cfg: HuggingFace's CLIPVisionConfig keys (CLIP_VISION_L by default); image_mean / image_std: the processor's constants."""
+    _kind = "clip_vision"
+
+    def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None):
+        self.lib = L.load()
+        L.check(self.lib.fmi_init(device), self.lib)
+        self.device = torch.device("cuda", device)
+        cfg = {k: int((CLIP_VISION_L if cfg is None else cfg)[k]) for k in CLIP_VISION_L}
+        self.cfg = cfg
+        self.image_mean = tuple(float(v) for v in (CLIP_IMAGE_MEAN if image_mean is None else image_mean))
+        self.image_std = tuple(float(v) for v in (CLIP_IMAGE_STD if image_std is None else image_std))
+        if len(self.image_mean) != 3 or len(self.image_std) != 3:
+            raise ValueError("image_mean and image_std hold one value per RGB channel")
+        c = L.ClipVisionConfig(*(cfg[k] for k in CLIP_VISION_L))
+        h = C.c_void_p()
+        L.check(self.lib.fmi_clip_vision_create(C.byref(c), C.byref(h)), self.lib)
+        self.h = h
+
+    @property
+    def projection_dim(self) -> int:
+        return self.cfg["projection_dim"]
+
+    def tensor_names(self):
+        from . import synth
+        return synth.clip_vision_tensor_shapes(self.cfg)
+
+    def forward(self, pixel_values, return_hidden: bool = False):
+        """== CLIPVisionModelWithProjection.forward: pixel_values (B,3,S,S) float -> image_embeds (B,projection_dim) f32; with return_hidden also the encoder's
+        output before post_layernorm, (B, 1 + (S / P)^2, hidden_size) f32 (HF's last_hidden_state)."""
+        S, D = self.cfg["image_size"], self.cfg["hidden_size"]
+        t = torch.from_numpy(pixel_values) if not isinstance(pixel_values, torch.Tensor) else pixel_values
+        if t.dim() != 4 or tuple(t.shape[1:]) != (3, S, S) or not t.is_floating_point():
+            raise ValueError(f"pixel_values must be float (B,3,{S},{S}), got {t.dtype} {tuple(t.shape)}")
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        B, T = int(t.shape[0]), 1 + (S // self.cfg["patch_size"]) ** 2
+        out = torch.empty((B, self.cfg["projection_dim"]), dtype=torch.float32, device=self.device)
+        hid = torch.empty((B, T, D), dtype=torch.float32, device=self.device) if return_hidden else None
+        L.check(self.lib.fmi_clip_vision_forward(self.h, _ptr(t), B, _ptr(out), L.F32, _ptr(hid) if hid is not None else None, _stream()), self.lib)
+        return (out, hid) if return_hidden else out
+
+    def resize(self, image_u8, nh: int, nw: int):
+        """u8 (h,w,3) -> u8 (nh,nw,3) on the device, PIL's Image.resize(BICUBIC) (fmi_resize_bicubic_u8)."""
+        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
+        t = t.to(self.device).contiguous()
+        out = torch.empty((int(nh), int(nw), 3), dtype=torch.uint8, device=self.device)
+        L.check(self.lib.fmi_resize_bicubic_u8(_ptr(t), int(t.shape[0]), int(t.shape[1]), _ptr(out), int(nh), int(nw), _stream()), self.lib)
+        return out
+
+    def preprocess(self, image_u8):
+        """CLIPImageProcessor on the device: u8 (H,W,3) of any size -> pixel_values (1,3,S,S) f32 — the shortest edge resized to S (clip_resize_shape), the centre
+        crop, (v / 255 - mean) / std."""
+        S = self.cfg["image_size"]
+        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
+        nh, nw = clip_resize_shape(int(t.shape[0]), int(t.shape[1]), S)
+        r = self.resize(t, nh, nw)
+        out = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
+        mean, std = (C.c_float * 3)(*self.image_mean), (C.c_float * 3)(*self.image_std)
+        L.check(self.lib.fmi_clip_preprocess_u8(_ptr(r), nh, nw, S, mean, std, _ptr(out), _stream()), self.lib)
+        return out
+
+    def encode(self, image):
+        """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> image_embeds f32."""
+        t = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
+        return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
 
 
 # ---------------------------------------------------------------------------------- tokenisation

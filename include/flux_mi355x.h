@@ -53,6 +53,7 @@ extern "C" {
  *   Then, still 6: the denoise loop's options in one struct — fmi_flux_denoise_options, fmi_flux_denoise_with; the six fmi_flux_denoise* entries remain.
  *   Then, still 6: GGUF transformers (ggml block formats) — fmi_gguf_block_info, fmi_gguf_dequantize, fmi_flux_set_linear_gguf.
  *   Then, still 6: FLUX IP-Adapters (image prompts) — fmi_ip_adapter_*, fmi_flux_ip, fmi_flux_forward_ip, fmi_flux_denoise_ip, fmi_ip_attention.
+ *   Then, still 6: the CLIP vision encoder (an image prompt from a picture) — fmi_resize_bicubic_u8, fmi_clip_preprocess_u8, fmi_clip_vision_*.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -780,6 +781,46 @@ size_t fmi_clip_size_in_bytes(const fmi_clip*);
  * hidden state at argmax(token id) of each row, FMI_F32 or FMI_BF16; hidden_out (B,T,dim) f32
  * optional (NULL to skip).  Synchronises the stream before returning. */
 int fmi_clip_forward(fmi_clip*, const int32_t* input_ids, int B, int T, void* pooled_out, fmi_dtype pooled_dtype, float* hidden_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * CLIP vision encoder (not in the reference): the image prompt of the IP-Adapter (fmi_flux_ip.embeds) from
+ * a picture.  It runs once per request in front of the denoise loop, like the text encoders.
+ * ---------------------------------------------------------------------------------- */
+/* u8 (h,w,3) device image -> u8 (nh,nw,3), PIL's Image.resize(BICUBIC) as CLIP's image processor calls it: two separable
+ * passes, horizontal first, then vertical (a pass whose size stays is skipped), the value rounded to nearest and clamped to
+ * [0,255] after each.  Along an axis, output o reads the inputs [lo, hi): scale = in / out, fs = max(scale, 1), support =
+ * 2 fs, centre = (o + 0.5) scale, lo = max(0, int(centre - support + 0.5)), hi = min(in, int(centre + support + 0.5)), with
+ * the weights k((j - centre + 0.5) / fs) normalised to sum 1, k = Keys' cubic at a = -0.5.  f32 arithmetic, one thread per
+ * output pixel, no atomics: the same bits for any launch grid.  PIL itself works in 22-bit fixed point: a value can differ
+ * from PIL's by 1.  FMI_ERR_INVALID for h, w, nh, nw <= 0. */
+int fmi_resize_bicubic_u8(const uint8_t* in, int h, int w, uint8_t* out, int nh, int nw, void* stream);
+/* u8 (nh,nw,3) device image -> pixel_values (3,S,S) f32: the centre crop at top = (nh - S) / 2, left = (nw - S) / 2 (integer
+ * division), then (v / 255 - mean[c]) / std[c] as three f32 operations.  mean, std: 3 host floats.  FMI_ERR_INVALID for
+ * nh < S or nw < S (the crop never pads). */
+int fmi_clip_preprocess_u8(const uint8_t* in, int nh, int nw, int S, const float* mean, const float* std_, float* out, void* stream);
+/* HuggingFace's CLIPVisionConfig; hidden_act is quick_gelu and layer_norm_eps 1e-5, as in every CLIP checkpoint */
+typedef struct fmi_clip_vision_config {
+  int image_size, patch_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads, projection_dim;
+} fmi_clip_vision_config;
+typedef struct fmi_clip_vision fmi_clip_vision;
+void fmi_clip_vision_default_config(fmi_clip_vision_config*); /* openai/clip-vit-large-patch14's vision tower: 224 / 14 / 1024 / 4096 / 24 / 16 / 768 */
+/* head dim (hidden_size / num_attention_heads) must be 64, the three widths multiples of 64, image_size a multiple of
+ * patch_size, and 1 + (image_size / patch_size)^2 tokens at most 1024 (the encoder attention's limit) */
+int fmi_clip_vision_create(const fmi_clip_vision_config*, fmi_clip_vision** out);
+void fmi_clip_vision_destroy(fmi_clip_vision*);
+/* HuggingFace's names (CLIPVisionModelWithProjection, and the vision half of a CLIPModel checkpoint):
+ * vision_model.embeddings.{class_embedding (D), patch_embedding.weight (D,3,P,P), position_embedding.weight (1 + Np, D)},
+ * vision_model.pre_layrnorm.{weight,bias} (their spelling), vision_model.encoder.layers.N.* as the text tower's,
+ * vision_model.post_layernorm.{weight,bias}, visual_projection.weight (projection_dim, D) */
+int fmi_clip_vision_set_tensor(fmi_clip_vision*, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank);
+int fmi_clip_vision_missing_count(const fmi_clip_vision*);
+const char* fmi_clip_vision_missing_name(fmi_clip_vision*, int i);
+size_t fmi_clip_vision_size_in_bytes(const fmi_clip_vision*);
+/* == CLIPVisionModelWithProjection.forward: pixel_values (B,3,S,S) f32 device, S = image_size -> image_embeds
+ * (B,projection_dim), FMI_F32 or FMI_BF16 = visual_projection(post_layernorm(class row)); hidden_out (B, 1 + Np, D) f32
+ * optional (NULL to skip): the encoder's output before post_layernorm, HF's last_hidden_state.  Synchronises the stream
+ * before returning. */
+int fmi_clip_vision_forward(fmi_clip_vision*, const float* pixel_values, int B, void* image_embeds_out, fmi_dtype dtype, float* hidden_out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Pipeline glue on device — the tensor code of FluxPipeline::forward
