@@ -5,7 +5,8 @@ from .flux import (AutoEncoderKl, FLUX_DEV, FLUX_SCHNELL, FluxModel, SchedulerCo
                    postprocess_u8, preprocess_u8, randn_latents, scale_noise, unpack_latents, cfg_euler_step, cast_cols_bf16, fill_condition, mask_image,
                    FluxControlNetModel, add_scaled_rows_bf16, FluxIPAdapter, ip_attention)
 from .pipeline import DiffusionGenerationParams, ModelDType, ModelSource, Offloading, Pipeline, encode_png, img2img_timesteps  # noqa: F401
-from .text import CLIP_L, CLIP_VISION_L, T5_XXL, ClipTextTransformer, ClipVisionModel, T5EncoderModel, load_bpe_tokenizer, tokenize_and_pad  # noqa: F401
+from .text import (CLIP_L, CLIP_VISION_L, SIGLIP_SO400M, T5_XXL, ClipTextTransformer, ClipVisionModel, ReduxImageEmbedder, SiglipVisionModel, T5EncoderModel,  # noqa: F401
+                   load_bpe_tokenizer, tokenize_and_pad)
 from . import synth  # noqa: F401
 from . import lora  # noqa: F401
 from .lora import read_lora  # noqa: F401

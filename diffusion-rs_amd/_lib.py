@@ -110,6 +110,12 @@ class ClipVisionConfig(C.Structure):
                 ("num_attention_heads", C.c_int), ("projection_dim", C.c_int)]
 
 
+class SiglipVisionConfig(C.Structure):
+    """fmi_siglip_vision_config == HuggingFace's SiglipVisionConfig."""
+    _fields_ = [("image_size", C.c_int), ("patch_size", C.c_int), ("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_hidden_layers", C.c_int),
+                ("num_attention_heads", C.c_int), ("layer_norm_eps", C.c_float)]
+
+
 class GemmDesc(C.Structure):
     """fmi_gemm_desc: one problem of fmi_gemm_group, the test seam into the GEMM launcher (include/flux_mi355x.h)."""
     _fields_ = [("a", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("gate", C.c_void_p), ("resid", C.c_void_p),
@@ -230,7 +236,7 @@ def _declare(lib):
     lib.fmi_flux_set_attention_rescale_threshold.argtypes = [C.c_void_p, C.c_int]
     lib.fmi_flux_set_attention_kernel.argtypes = [C.c_void_p, C.c_int]
     lib.fmi_flux_forward.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.c_void_p, C.c_void_p]
-    for enc in ("t5", "clip", "clip_vision"):
+    for enc in ("t5", "clip", "clip_vision", "siglip_vision", "redux"):
         getattr(lib, f"fmi_{enc}_set_tensor").argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
         getattr(lib, f"fmi_{enc}_missing_name").restype = C.c_char_p
         getattr(lib, f"fmi_{enc}_missing_name").argtypes = [C.c_void_p, C.c_int]
@@ -245,6 +251,11 @@ def _declare(lib):
     lib.fmi_clip_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.fmi_clip_vision_create.argtypes = [C.POINTER(ClipVisionConfig), C.POINTER(C.c_void_p)]
     lib.fmi_clip_vision_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.fmi_siglip_vision_create.argtypes = [C.POINTER(SiglipVisionConfig), C.POINTER(C.c_void_p)]
+    lib.fmi_siglip_vision_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.fmi_siglip_vision_poison_workspace.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.fmi_redux_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.fmi_redux_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
     lib.fmi_resize_bicubic_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_clip_preprocess_u8.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     lib.fmi_flux_forward_context.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxContext), C.c_void_p, C.c_void_p]
@@ -389,7 +400,11 @@ EXPORTED = [
     "fmi_t5_size_in_bytes", "fmi_t5_forward", "fmi_clip_default_config", "fmi_clip_create", "fmi_clip_destroy", "fmi_clip_set_tensor",
     "fmi_clip_missing_count", "fmi_clip_missing_name", "fmi_clip_size_in_bytes", "fmi_clip_forward",
     "fmi_resize_bicubic_u8", "fmi_clip_preprocess_u8", "fmi_clip_vision_default_config", "fmi_clip_vision_create", "fmi_clip_vision_destroy", "fmi_clip_vision_set_tensor",
-    "fmi_clip_vision_missing_count", "fmi_clip_vision_missing_name", "fmi_clip_vision_size_in_bytes", "fmi_clip_vision_forward", "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
+    "fmi_clip_vision_missing_count", "fmi_clip_vision_missing_name", "fmi_clip_vision_size_in_bytes", "fmi_clip_vision_forward",
+    "fmi_siglip_vision_default_config", "fmi_siglip_vision_create", "fmi_siglip_vision_destroy", "fmi_siglip_vision_set_tensor", "fmi_siglip_vision_missing_count",
+    "fmi_siglip_vision_missing_name", "fmi_siglip_vision_size_in_bytes", "fmi_siglip_vision_forward", "fmi_siglip_vision_poison_workspace",
+    "fmi_redux_create", "fmi_redux_destroy", "fmi_redux_set_tensor", "fmi_redux_missing_count", "fmi_redux_missing_name", "fmi_redux_size_in_bytes", "fmi_redux_forward",
+    "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
     "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids", "fmi_cfg_euler_step", "fmi_cast_cols_bf16", "fmi_mask_image", "fmi_fill_condition",
     "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
     "fmi_release_scratch", "fmi_timestep_embedding", "fmi_rope_table", "fmi_rmsnorm_rope",

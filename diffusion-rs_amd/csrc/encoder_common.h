@@ -5,6 +5,7 @@
 #pragma once
 #include <math.h>
 
+#include <algorithm>
 #include <map>
 #include <set>
 #include <string>
@@ -132,6 +133,7 @@ struct Dest {
   int rows, cols;  // cols == 0 -> 1-D
   int ld = 0;      // row stride in the arena when it is wider than cols (the columns [cols, ld) are zero); 0 -> cols
   int inner[3] = {0, 0, 0};  // inner[0] != 0: the tensor arrives as rank 4, (rows, inner[0], inner[1], inner[2]) with cols = their product
+  int own[2] = {0, 0};       // own[0] != 0: the tensor arrives as (own[0], own[1]) (own[1] == 0: 1-D) and is stored as `rows` chunks of `cols` elements (reg_chunks)
 };
 struct Registry {
   DeviceBuffer arena;
@@ -154,6 +156,15 @@ struct Registry {
     names[name] = d;
     missing.insert(name);
   }
+  // a tensor (s0, s1) (s1 == 0: 1-D) cut into `chunks` contiguous pieces of `chunk` elements, piece i stored at element i * ld of the slot, zero in
+  // [chunk, ld): rows that scatter into padded head slots (a q / k / v projection (H hd, D): H pieces of hd D elements at a stride of 128 D; its bias: H
+  // pieces of hd at 128) and columns that do (an out_proj (D, H hd): D H pieces of hd at 128)
+  void reg_chunks(const std::string& name, bf16_t* p, int s0, int s1, int chunks, int chunk, int ld) {
+    Dest d{p, chunks, chunk};
+    d.ld = ld, d.own[0] = s0, d.own[1] = s1;
+    names[name] = d;
+    missing.insert(name);
+  }
   int set(const char* who, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
     if (!name || !data) return fail(FMI_ERR_INVALID, std::string(who) + ": null argument");
     auto it = names.find(name);
@@ -164,6 +175,10 @@ struct Registry {
     if (d.inner[0]) {
       ok = rank == 4 && shape[0] == d.rows && shape[1] == d.inner[0] && shape[2] == d.inner[1] && shape[3] == d.inner[2];
       want = std::to_string(d.rows) + "," + std::to_string(d.inner[0]) + "," + std::to_string(d.inner[1]) + "," + std::to_string(d.inner[2]);
+    }
+    if (d.own[0]) {
+      ok = d.own[1] ? (rank == 2 && shape[0] == d.own[0] && shape[1] == d.own[1]) : (rank == 1 && shape[0] == d.own[0]);
+      want = std::to_string(d.own[0]) + (d.own[1] ? "," + std::to_string(d.own[1]) : "");
     }
     if (!ok) return fail(FMI_ERR_INVALID, std::string(who) + ": shape mismatch for " + name + " (expected (" + want + "))");
     if (dtype != FMI_F32 && dtype != FMI_F16 && dtype != FMI_BF16) return fail(FMI_ERR_INVALID, std::string(who) + ": dtype must be F32/F16/BF16");
@@ -268,6 +283,85 @@ int clip_layers(const std::vector<ClipLayer>& layers, const ClipLayerBuffers& w,
     FMI_TRY(launch_gemm(&p, 1, s));
     hipLaunchKernelGGL(enc_act_kernel, dim3(256), dim3(256), 0, s, w.h, rows, F, 3, 0, w.g);  // QuickGelu (:13-19)
     p = lin(w.g, F, L.f2, L.f2b, w.x, D, rows, D, F, EPI_RESID_GATE_F32);
+    p.gate = w.ones;
+    FMI_TRY(launch_gemm(&p, 1, s));
+  }
+  return FMI_OK;
+}
+
+// ------------------------------------------------------------------- the SigLIP encoder layer (siglip_vision.hip)
+// HF's SiglipEncoderLayer: LayerNorm(eps) -> fused q|k|v -> attention at head dim hd = D / H on the transformer's MFMA attention (d = 128) -> out_proj into
+// the f32 stream -> LayerNorm -> fc1 -> tanh-GELU -> fc2 into the stream.  The heads are zero-padded to 128 IN THE WEIGHTS: head h's q / k / v rows sit at rows
+// h * 128 .. h * 128 + hd of a (3 H 128, D) operand, out_proj's K is (D, H 128) with zero pad columns, so the q|k|v GEMM writes 128-wide heads whose lanes
+// [hd, 128) are exactly 0 (zero weight rows, zero bias) and contribute 0 to every score and meet zero out_proj columns.  F is padded to Fp = a multiple of 64 the
+// same way: zero fc1 rows and bias, gelu(0) = 0, zero fc2 columns.
+struct SiglipLayer {
+  bf16_t *l1w, *l1b, *qkv, *qkvb, *o, *ob, *l2w, *l2b, *f1, *f1b, *f2, *f2b;
+};
+// the layer's slots and names under prefix p; the arena must be zero before the tensors arrive (the fc1 pad rows and every bias pad are never written)
+void siglip_layer_layout(Registry& r, const std::string& p, int D, int H, int F, SiglipLayer& L) {
+  const int hd = D / H, HP = H * 128, Fp = (int)align_up(F, 64);
+  L.l1w = r.take(D), L.l1b = r.take(D);
+  r.reg(p + "layer_norm1.weight", L.l1w, D, 0), r.reg(p + "layer_norm1.bias", L.l1b, D, 0);
+  L.qkv = r.take((size_t)3 * HP * D), L.qkvb = r.take((size_t)3 * HP);
+  const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
+  for (int i = 0; i < 3; ++i) {
+    r.reg_chunks(p + "self_attn." + nm[i] + ".weight", L.qkv ? L.qkv + (size_t)i * HP * D : nullptr, D, D, H, hd * D, 128 * D);
+    r.reg_chunks(p + "self_attn." + nm[i] + ".bias", L.qkvb ? L.qkvb + (size_t)i * HP : nullptr, D, 0, H, hd, 128);
+  }
+  L.o = r.take((size_t)D * HP), L.ob = r.take(D);
+  r.reg_chunks(p + "self_attn.out_proj.weight", L.o, D, D, D * H, hd, 128), r.reg(p + "self_attn.out_proj.bias", L.ob, D, 0);
+  L.l2w = r.take(D), L.l2b = r.take(D);
+  r.reg(p + "layer_norm2.weight", L.l2w, D, 0), r.reg(p + "layer_norm2.bias", L.l2b, D, 0);
+  L.f1 = r.take((size_t)Fp * D), L.f1b = r.take(Fp);  // (the rows [F, Fp) stay zero)
+  r.reg(p + "mlp.fc1.weight", L.f1, F, D), r.reg(p + "mlp.fc1.bias", L.f1b, F, 0);
+  L.f2 = r.take((size_t)D * Fp), L.f2b = r.take(D);
+  r.reg_chunks(p + "mlp.fc2.weight", L.f2, D, F, D, F, Fp), r.reg(p + "mlp.fc2.bias", L.f2b, D, 0);
+}
+
+// q and k of token-major q|k|v rows (rows = B * T, 3 HP columns, head h at columns h * 128 of each third) -> head-major (B, H, T, 128): what the attention
+// reads.  One 16-byte load and store per 8 elements, each read once; v stays where it is (launch_v_transpose reads it in place).
+__global__ __launch_bounds__(256) void qk_head_major_kernel(const bf16_t* __restrict__ qkv, int T, int H, bf16_t* __restrict__ qh, bf16_t* __restrict__ kh, int64_t n16) {
+  const int hp8 = H * 16;  // 16-byte pieces per row of one third
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n16; i += (int64_t)gridDim.x * blockDim.x) {
+    const int part = i >= n16;
+    const int64_t j = i - part * n16, row = j / hp8;
+    const int c8 = (int)(j - row * hp8), h = c8 >> 4, c = c8 & 15;
+    const int64_t b = row / T, t = row - b * T;
+    const uint4 v = *reinterpret_cast<const uint4*>(qkv + (row * 3 + part) * (int64_t)(hp8 * 8) + c8 * 8);
+    *reinterpret_cast<uint4*>((part ? kh : qh) + (((b * H + h) * T + t) * 128 + c * 8)) = v;
+  }
+}
+
+// the buffers a run of SigLIP layers works in, rows = B * T, HP = H * 128, Fp = F rounded up to 64, Lp = T rounded up to 64: x (rows, D) f32 the stream (in /
+// out), n (rows, D), qkv (rows, 3 HP), qh and kh (B, H, T, 128), vt (B, H, 128, Lp) with its tail [T, Lp) ZERO (launch_vt_zero_pad, once: the transposes never
+// write there), a (rows, HP), h and g (rows, Fp) bf16, ones (D) f32 of 1.0
+struct SiglipLayerBuffers {
+  float* x;
+  bf16_t *n, *qkv, *qh, *kh, *vt, *a, *h, *g;
+  const float* ones;
+};
+int siglip_layers(const std::vector<SiglipLayer>& layers, const SiglipLayerBuffers& w, int B, int T, int D, int H, int F, float eps, hipStream_t s) {
+  const int rows = B * T, nb = (rows + 3) / 4, HP = H * 128, Fp = (int)align_up(F, 64), Lp = (int)align_up(T, 64);
+  const float scale = 1.0f / sqrtf((float)(D / H));  // head_dim^-0.5 of the real head, not of the padded one
+  const int64_t n16 = (int64_t)rows * H * 16;
+  const dim3 flat((unsigned)std::min<int64_t>(cdiv64(2 * n16, 256), 4096));
+  for (const SiglipLayer& L : layers) {
+    hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l1w, L.l1b, eps, rows, D, w.n, (float*)nullptr);
+    GemmProblem p = lin(w.n, D, L.qkv, L.qkvb, w.qkv, 3 * HP, rows, 3 * HP, D, EPI_STORE_BF16);
+    FMI_TRY(launch_gemm(&p, 1, s));
+    hipLaunchKernelGGL(qk_head_major_kernel, flat, dim3(256), 0, s, w.qkv, T, H, w.qh, w.kh, n16);
+    FMI_LAUNCH_CHECK();
+    FMI_TRY(launch_v_transpose(w.qkv + 2 * HP, 3 * HP, (int64_t)T * 3 * HP, w.vt, B, H, T, 0, Lp, s));
+    FMI_TRY(launch_attention(w.qh, w.kh, w.vt, w.a, B, H, T, T, Lp, scale, /*out_token_major=*/1, s));
+    p = lin(w.a, HP, L.o, L.ob, w.x, D, rows, D, HP, EPI_RESID_GATE_F32);
+    p.gate = w.ones;
+    FMI_TRY(launch_gemm(&p, 1, s));
+    hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l2w, L.l2b, eps, rows, D, w.n, (float*)nullptr);
+    p = lin(w.n, D, L.f1, L.f1b, w.h, Fp, rows, Fp, D, EPI_STORE_BF16);
+    FMI_TRY(launch_gemm(&p, 1, s));
+    hipLaunchKernelGGL(enc_act_kernel, dim3(256), dim3(256), 0, s, w.h, rows, Fp, 1, 0, w.g);  // gelu_pytorch_tanh
+    p = lin(w.g, Fp, L.f2, L.f2b, w.x, D, rows, D, Fp, EPI_RESID_GATE_F32);
     p.gate = w.ones;
     FMI_TRY(launch_gemm(&p, 1, s));
   }

@@ -348,7 +348,7 @@ def clip_vision_config(config: dict) -> dict:
         vc.setdefault("projection_dim", config.get("projection_dim"))
     elif config.get("model_type") not in (None, "clip_vision_model"):
         raise ValueError(f"config.json has model_type {config.get('model_type')!r} and no vision_config: a CLIPVisionConfig or a CLIPConfig is expected "
-                         f"(SigLIP and other towers are not supported)")
+                         f"(a SigLIP tower is FLUX.1 Redux's: load_siglip_vision; other towers are not supported)")
     missing = [k for k in CLIP_VISION_KEYS if vc.get(k) is None]
     if missing:
         raise ValueError(f"the image encoder's config.json lacks {missing}")
@@ -440,6 +440,163 @@ def load_clip_vision(path: str):
                 mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
             tensors.update(_safetensors_from_buffer(memoryview(mm)))
     return dict(cfg, image_mean=mean, image_std=std), clip_vision_from_tensors(cfg, tensors, os.path.basename(os.path.normpath(path)))
+
+
+from .text import SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD, SIGLIP_SO400M  # noqa: E402
+
+SIGLIP_VISION_KEYS = tuple(SIGLIP_SO400M)
+
+
+def _safetensors_in(path: str) -> dict:
+    """Every tensor of the *.safetensors files of a directory, in file-name order."""
+    tensors = {}
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with open(os.path.join(path, fn), "rb") as f:
+                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            tensors.update(_safetensors_from_buffer(memoryview(mm)))
+    return tensors
+
+
+def siglip_vision_config(config: dict) -> dict:
+    """The vision tower's configuration (SIGLIP_VISION_KEYS) from a config.json: a SiglipVisionConfig, or a full SiglipConfig, whose `vision_config` is used and
+    whose text tower is ignored.  Fields a SiglipVisionConfig leaves out take HuggingFace's defaults where it has them (layer_norm_eps 1e-6, hidden_act
+    gelu_pytorch_tanh, num_channels 3).  ValueError by name for a missing field, an activation other than gelu_pytorch_tanh, channels other than 3, and a
+    model_type that is no SigLIP's."""
+    if not isinstance(config, dict):
+        raise ValueError("config.json of a SigLIP image encoder must hold an object")
+    vc = config
+    if isinstance(config.get("vision_config"), dict):
+        if config.get("model_type") not in (None, "siglip"):
+            raise ValueError(f"config.json has model_type {config.get('model_type')!r}: a SiglipVisionConfig or a SiglipConfig is expected")
+        vc = dict(config["vision_config"])
+    if vc.get("model_type") not in (None, "siglip_vision_model"):
+        raise ValueError(f"config.json has model_type {vc.get('model_type')!r}: a SiglipVisionConfig or a SiglipConfig is expected (a CLIP tower is the "
+                         f"IP-Adapter's: load_clip_vision)")
+    missing = [k for k in SIGLIP_VISION_KEYS if k != "layer_norm_eps" and vc.get(k) is None]
+    if missing:
+        raise ValueError(f"the SigLIP image encoder's config.json lacks {missing}")
+    if vc.get("hidden_act", "gelu_pytorch_tanh") != "gelu_pytorch_tanh":
+        raise ValueError(f"the SigLIP image encoder's hidden_act is {vc['hidden_act']!r}: only gelu_pytorch_tanh is supported")
+    if int(vc.get("num_channels", 3)) != 3:
+        raise ValueError(f"the SigLIP image encoder's num_channels is {vc['num_channels']!r}: only 3 (RGB) is supported")
+    eps = float(vc.get("layer_norm_eps", 1e-6))
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError(f"the SigLIP image encoder's layer_norm_eps is {vc['layer_norm_eps']!r}: it must be positive")
+    return dict({k: int(vc[k]) for k in SIGLIP_VISION_KEYS if k != "layer_norm_eps"}, layer_norm_eps=eps)
+
+
+def siglip_image_processor(pre: Optional[dict], image_size: int) -> Tuple[tuple, tuple]:
+    """(image_mean, image_std) of a preprocessor_config.json (None: SigLIP's constants, 0.5 each).  What SiglipVisionModel.preprocess does is fixed — a bicubic
+    resize straight to image_size x image_size, rescale by 1 / 255, normalise — so a processor that asks for anything else is refused by name."""
+    if pre is None:
+        return SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD
+    for flag in ("do_resize", "do_rescale", "do_normalize"):
+        if not pre.get(flag, True):
+            raise ValueError(f"preprocessor_config.json has {flag} = false: the SigLIP image encoder always resizes, rescales and normalises")
+    if pre.get("do_center_crop", False):
+        raise ValueError("preprocessor_config.json has do_center_crop = true: the SigLIP image encoder resizes straight to the square and never crops")
+    if int(pre.get("resample", 3)) != 3:
+        raise ValueError(f"preprocessor_config.json has resample = {pre['resample']!r}: only 3 (PIL's BICUBIC) is supported")
+    if abs(float(pre.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
+        raise ValueError(f"preprocessor_config.json has rescale_factor = {pre['rescale_factor']!r}: only 1 / 255 is supported")
+    size = pre.get("size", image_size)
+    hw = (size.get("height"), size.get("width")) if isinstance(size, dict) and set(size) == {"height", "width"} else (size, size) if isinstance(size, int) else None
+    if hw is None or tuple(int(v) for v in hw) != (image_size, image_size):
+        raise ValueError(f"preprocessor_config.json has size = {size!r}: the picture is resized to the model's image_size = {image_size}, height and width")
+    mean, std = pre.get("image_mean", SIGLIP_IMAGE_MEAN), pre.get("image_std", SIGLIP_IMAGE_STD)
+    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
+        raise ValueError(f"preprocessor_config.json: image_mean / image_std must hold 3 values, the std positive, got {mean!r} / {std!r}")
+    return tuple(float(m) for m in mean), tuple(float(s) for s in std)
+
+
+def siglip_vision_from_tensors(cfg: dict, tensors, where: str = "SigLIP image encoder") -> dict:
+    """{name: tensor} of the vision tower of configuration cfg, under the `vision_model.` names, from a SiglipVisionModel or a full SiglipModel checkpoint's
+    tensors.  A checkpoint may carry the tower's keys with the `vision_model.` prefix (the published ones) or without it (what transformers 5 writes for a
+    bare SiglipVisionModel); the pooling head (`head.*`) and a full checkpoint's text tower, logit_scale and logit_bias are ignored.  ValueError naming the
+    keys: any other unexpected tensor, a missing one, a shape that does not fit cfg."""
+    want = synth.siglip_vision_tensor_shapes(cfg)
+    vm = "vision_model."
+    sd, unexpected = {}, []
+    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
+        full = name if name.startswith(vm) else vm + name
+        if full in want and (name.startswith(vm) or full not in sd):
+            sd[full] = t
+        elif full.startswith(vm + "head.") or name.startswith("text_model.") or name in ("logit_scale", "logit_bias", vm + "embeddings.position_ids", "embeddings.position_ids"):
+            continue
+        else:
+            unexpected.append(name)
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not SiglipVisionModel's), e.g. {sorted(unexpected)[:3]}")
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise ValueError(f"{where}: {len(missing)} SigLIP image-encoder tensors missing, e.g. {missing[:3]}")
+    for k, t in sd.items():
+        if tuple(t.shape) != tuple(want[k]):
+            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
+    return sd
+
+
+def load_siglip_vision(path: str, preprocessor: Optional[str] = None):
+    """A SigLIP image-encoder directory — config.json (a SiglipVisionConfig or a full SiglipConfig) next to *.safetensors, with an optional
+    preprocessor_config.json (in the directory, or in `preprocessor`: FLUX.1-Redux-dev keeps it in feature_extractor/) — as (cfg, {name: tensor}): cfg holds
+    SIGLIP_VISION_KEYS plus image_mean / image_std, what Pipeline.load_redux and SiglipVisionModel take.  No device is touched.  ValueError as
+    siglip_vision_config's, siglip_image_processor's and siglip_vision_from_tensors'."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"{path}: not a directory (a SigLIP image encoder is a directory: config.json + *.safetensors)")
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = siglip_vision_config(json.load(f))
+    pre = None
+    for d in (path, preprocessor):
+        if d is not None and pre is None and os.path.isfile(os.path.join(d, "preprocessor_config.json")):
+            with open(os.path.join(d, "preprocessor_config.json")) as f:
+                pre = json.load(f)
+    mean, std = siglip_image_processor(pre, cfg["image_size"])
+    return dict(cfg, image_mean=mean, image_std=std), siglip_vision_from_tensors(cfg, _safetensors_in(path), os.path.basename(os.path.normpath(path)))
+
+
+def redux_from_tensors(tensors, where: str = "Redux embedder", redux_dim: Optional[int] = None, txt_dim: Optional[int] = None):
+    """(redux_dim, txt_dim, {name: tensor}) of a Redux embedder's four tensors (redux_up.{weight,bias}, redux_down.{weight,bias}): the dimensions are read off
+    redux_up.weight (3 J, D) and checked against the given ones (a config.json's).  ValueError naming the keys: an unexpected tensor, a missing one, a shape that
+    does not fit."""
+    sd = dict(tensors.items() if isinstance(tensors, dict) else tensors)
+    names = tuple(synth.redux_tensor_shapes(64, 64))
+    unexpected = sorted(k for k in sd if k not in names)
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not ReduxImageEncoder's), e.g. {unexpected[:3]}")
+    missing = [k for k in names if k not in sd]
+    if missing:
+        raise ValueError(f"{where}: {len(missing)} Redux tensors missing, e.g. {missing[:3]}")
+    up = tuple(sd["redux_up.weight"].shape)
+    if len(up) != 2 or up[0] % 3:
+        raise ValueError(f"{where}: redux_up.weight is {up}, expected (3 * txt_in_features, redux_dim)")
+    D, J = int(up[1]), int(up[0]) // 3
+    for given, got, what in ((redux_dim, D, "redux_dim"), (txt_dim, J, "txt_in_features")):
+        if given is not None and int(given) != got:
+            raise ValueError(f"{where}: config.json has {what} = {given}, redux_up.weight {up} says {got}")
+    for k, shp in synth.redux_tensor_shapes(D, J).items():
+        if tuple(sd[k].shape) != tuple(shp):
+            raise ValueError(f"{where}: {k} is {tuple(sd[k].shape)}, expected {tuple(shp)}")
+    return D, J, sd
+
+
+def load_redux(path: str):
+    """A Redux embedder — diffusers' image_embedder/ directory (config.json with redux_dim and txt_in_features next to *.safetensors) or BFL's single
+    flux1-redux-dev.safetensors, which holds the same four names — as (redux_dim, txt_dim, {name: tensor}).  No device is touched.  ValueError as
+    redux_from_tensors', and for a config.json that lacks redux_dim / txt_in_features."""
+    where = os.path.basename(os.path.normpath(path))
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json")) as f:
+            config = json.load(f)
+        lacking = [k for k in ("redux_dim", "txt_in_features") if not isinstance(config, dict) or config.get(k) is None]
+        if lacking:
+            raise ValueError(f"{where}: config.json lacks {lacking}")
+        return redux_from_tensors(_safetensors_in(path), where, config["redux_dim"], config["txt_in_features"])
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path}: neither an image_embedder directory nor a .safetensors file")
+    with open(path, "rb") as f:
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    return redux_from_tensors(dict(_safetensors_from_buffer(memoryview(mm))), where)
 
 
 def load_vae(vae, tensors: Iterator[Tuple[str, torch.Tensor]]) -> int:

@@ -28,7 +28,7 @@ import os
 import struct
 import threading
 import zlib
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, fields, replace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -182,7 +182,8 @@ def _host_image(x, what: str) -> torch.Tensor:
 # what a request calls the options and modes of flux.REFUSED_PAIRS / REFUSED_MODES (an 8-bit transformer: "fp8" / "int8")
 REQUEST_NAMES = dict(context="reference= (a context)", control="a control (a channel-conditioned checkpoint: FLUX.1 Fill / Canny / Depth)",
                      true_cfg="true CFG (a negative with true_cfg_scale > 1)", cache="the step cache (cache_threshold= / cache_force=)", controlnet="a ControlNet",
-                     ip_adapter="an IP-Adapter", sequence_parallel="supported under sequence parallelism: disable_sequence_parallel() first",
+                     ip_adapter="an IP-Adapter", redux="Redux (redux_image= / redux_image_embeds=)",
+                     sequence_parallel="supported under sequence parallelism: disable_sequence_parallel() first",
                      fp8="supported on a transformer in the fp8 mode", int8="supported on a transformer in the int8 mode")
 
 
@@ -326,6 +327,42 @@ def check_ip_adapter_request(loaded: bool, embed_dim: int = 0, embeds_shape=None
         raise ValueError(f"ip_adapter_scale must be finite, got {scale!r}")
     if not (0.0 <= float(start) <= float(end) <= 1.0):
         raise ValueError(f"ip_adapter_start / ip_adapter_end must satisfy 0 <= start <= end <= 1, got {start!r} / {end!r}")
+
+
+@dataclass(frozen=True)
+class _ReduxInput:
+    """The Redux image tokens of a request: ONE picture per request, shared by its prompts like the negative — not a per-sample input, so no
+    field of _Samples.  Redux changes the text rows only: a chunk of such a request becomes an embeddings= chunk whose T5 rows end with these tokens
+    (Pipeline._generate_chunk_redux), and _generate_chunk never learns of it."""
+    tokens: torch.Tensor  # (1, Np, J) f32 on the device, redux_scale already applied
+
+
+def check_redux_request(loaded: bool, num_patches: int = 0, txt_dim: int = 0, image_size: int = 0, image_shape=None, image_is_u8: bool = False, embeds_shape=None,
+                        scale: float = 1.0, sequence_parallel: bool = False):
+    """The Redux arguments of a request, checked without a device.  ValueError: redux_image= / redux_image_embeds= without a loaded Redux (Pipeline.load_redux);
+    both of them (a picture and its embedding exclude one another); a picture that is not u8 (H,W,3) of any size or float (1,3,S,S) pixel_values, S = image_size
+    of the loaded tower; embeddings that are not (Np,J) or (1,Np,J), Np = num_patches, J = txt_dim; a redux_scale that is not finite or is negative; sequence
+    parallelism.  A request without either is not conditioned, whatever is loaded."""
+    if image_shape is None and embeds_shape is None:
+        return
+    if image_shape is not None and embeds_shape is not None:
+        raise ValueError("redux_image= and redux_image_embeds= exclude one another: a request has one picture, or its embedding")
+    given = "redux_image" if image_shape is not None else "redux_image_embeds"
+    if not loaded:
+        raise ValueError(f"{given}= needs a loaded Redux: Pipeline.load_redux(path) first")
+    if sequence_parallel:
+        raise ValueError(f"{REQUEST_NAMES['redux']} is not {REQUEST_NAMES['sequence_parallel']}")
+    if image_shape is not None:
+        shp, S = tuple(image_shape), image_size
+        if not ((len(shp) == 3 and shp[2] == 3 and shp[0] > 0 and shp[1] > 0) if image_is_u8 else shp == (1, 3, S, S)):
+            raise ValueError(f"redux_image= must be a uint8 (H,W,3) picture of any size or float (1,3,{S},{S}) pixel_values (one picture per request), got {shp}")
+    else:
+        shp = tuple(embeds_shape)
+        if shp not in ((num_patches, txt_dim), (1, num_patches, txt_dim)):
+            raise ValueError(f"redux_image_embeds= must be ({num_patches},{txt_dim}) or (1,{num_patches},{txt_dim}) (one picture per request, shared by its prompts), "
+                             f"got {shp}")
+    if not (np.isfinite(scale) and scale >= 0.0):
+        raise ValueError(f"redux_scale must be finite and >= 0, got {scale!r}")
 
 
 def control_kind(cond_channels: int) -> Optional[str]:
@@ -583,7 +620,7 @@ class Pipeline:
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                         negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
-                        ip_adapter_image=None, negative_ip_adapter_image=None):
+                        ip_adapter_image=None, negative_ip_adapter_image=None, redux_image=None, redux_image_embeds=None, redux_scale: float = 1.0):
         """== ModelPipeline::forward for FluxPipeline (pipelines/flux/mod.rs:224-335) on THIS device.
         Returns (B,3,H,W) u8 on the device.  `sample_ids` (default first_sample + 0..B-1) name the Philox streams of
         the samples, so that a sample draws the same noise whichever rank / chunk it runs in.
@@ -641,7 +678,18 @@ class Pipeline:
         (i + 1) / n > ip_adapter_end else 1; a step with scale 0 is the plain step.  Under a negative prompt the negative half attends to
         negative_ip_adapter_image_embeds=, or to zero embeddings through the same projection.  Combines with the negative, image= / strength= / mask=, a Fill /
         Canny / Depth control and a ControlNet; raises with reference=, cache_threshold=, under sequence parallelism, on an 8-bit transformer and without a loaded
-        adapter."""
+        adapter.
+
+        Image variation (`redux_image=` with FLUX.1 Redux loaded by load_redux; diffusers' FluxPriorReduxPipeline): ONE picture per request,
+        shared by its prompts — u8 (H,W,3) of any size, as output="rgb" returns it, or f32 (1,3,S,S) pixel_values that are already preprocessed — or
+        `redux_image_embeds=`, the (Np,J) / (1,Np,J) image tokens encode_redux_image returns.  A picture and its embedding exclude one another.  The picture
+        is encoded once, before the request is chunked (SigLIP tower, Redux embedder), and redux_scale * tokens are appended behind the T5 rows of every sample,
+        whether the prompt came as text, token_ids= or embeddings=: the model sees T = T_prompt + Np text rows with zero txt_ids, the pooled CLIP embedding is
+        unchanged, the denoise loop is untouched.  redux_scale = 0 still appends the rows, as zeros.  Under a negative prompt (true CFG) both halves keep one T:
+        the negative half receives ZERO rows in place of the image tokens (the IP-Adapter's zero-embeddings rule).  Redux changes the text rows only, so it combines
+        with everything the text rows combine with — image= / strength= / mask=, reference=, a control, a ControlNet, an IP-Adapter, cache_threshold=, the 8-bit
+        modes; it raises under sequence parallelism and without a loaded Redux."""
+        rdx = self._redux_input(redux_image, redux_image_embeds, redux_scale)
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
                                      negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
                                      image=ip_adapter_image, negative_image=negative_ip_adapter_image)
@@ -662,7 +710,8 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        outs = [self._generate_chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
+        chunk = self._generate_chunk if rdx is None else (lambda *a, **kw: self._generate_chunk_redux(rdx, *a, **kw))
+        outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
             return outs[0]
@@ -782,6 +831,95 @@ class Pipeline:
             raise ValueError(f"image must be a uint8 (H,W,3) picture of any size or float (1,3,{S},{S}) pixel_values, got {tuple(img.shape)}")
         with self._lock:
             return enc.encode(img)
+
+    def _redux_input(self, image, embeds, scale) -> Optional[_ReduxInput]:
+        """The Redux tokens of a request, checked once and brought to their device form: None without redux_image= / redux_image_embeds=, else the object its
+        chunks share.  A picture is encoded here, once; the scale is applied here, once (an f32 multiply)."""
+        if image is None and embeds is None:
+            return None
+        img = None if image is None else _host_image(image, "redux_image")
+        e = torch.from_numpy(np.ascontiguousarray(embeds)) if isinstance(embeds, np.ndarray) else embeds
+        if e is not None and not (isinstance(e, torch.Tensor) and e.is_floating_point()):
+            raise ValueError("redux_image_embeds must be a float numpy array or torch tensor")
+        rdx = getattr(self, "redux", None)
+        tower, emb = rdx if rdx is not None else (None, None)
+        check_redux_request(rdx is not None, 0 if tower is None else tower.num_patches, 0 if emb is None else emb.txt_dim, 0 if tower is None else tower.cfg["image_size"],
+                            None if img is None else tuple(img.shape), img is not None and img.dtype == torch.uint8, None if e is None else tuple(e.shape), float(scale),
+                            getattr(self, "_sp", None) is not None)
+        tokens = self.encode_redux_image(img) if img is not None else e.to(device=self.device, dtype=torch.float32).reshape(1, tower.num_patches, emb.txt_dim)
+        return _ReduxInput((tokens * float(scale)).contiguous())
+
+    def _generate_chunk_redux(self, redux: _ReduxInput, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
+                              **shared):
+        """One denoise call of a request with Redux tokens: the chunk's text embeddings are made as always (_chunk_embeddings: text, token_ids= or embeddings=,
+        the negative with them), the tokens are appended behind the T5 rows of every sample — zero rows behind the negative's — and the chunk goes on as the
+        embeddings= chunk that it now is."""
+        with self._lock:
+            t5_emb, clip_emb, neg = self._chunk_embeddings(s, negative)
+        tok = redux.tokens.to(t5_emb.dtype)
+        s = replace(s, embeddings=(torch.cat([t5_emb, tok.expand(t5_emb.shape[0], -1, -1)], 1), clip_emb), token_ids=None)
+        if neg is not None:
+            negative = _Negative(negative.scale, embeddings=(torch.cat([neg[0][:1], torch.zeros_like(tok)], 1), neg[1][:1]))
+        return self._generate_chunk(s, params, seed, strength, return_latents, cache_threshold, stats, **({} if negative is None else dict(negative=negative)), **shared)
+
+    def load_redux(self, path, image_encoder=None):
+        """Load FLUX.1 Redux: a SigLIP vision tower and the Redux embedder.  `path` is a FLUX.1-Redux-dev directory (image_encoder/,
+        image_embedder/, feature_extractor/), or the embedder alone — an image_embedder/ directory, BFL's flux1-redux-dev.safetensors, or a {name: tensor} dict —
+        with the tower in `image_encoder=`: a directory (loader.load_siglip_vision) or a (cfg, {name: tensor}) pair.  The embedder's txt_in_features must equal the
+        transformer's joint_attention_dim and its redux_dim the tower's hidden_size: ValueError by name otherwise, as for missing and unexpected keys.  It replaces a
+        loaded one; requests use it only when they pass redux_image= / redux_image_embeds=, and encode_redux_image."""
+        from . import loader, text
+        if isinstance(path, (str, os.PathLike)):
+            path = os.fspath(path)
+            if image_encoder is None:
+                if not os.path.isdir(os.path.join(path, "image_encoder")) or not os.path.isdir(os.path.join(path, "image_embedder")):
+                    raise ValueError(f"{path}: not a FLUX.1-Redux-dev directory (image_encoder/ and image_embedder/); pass the embedder with image_encoder=")
+                image_encoder, path = (os.path.join(path, "image_encoder"), os.path.join(path, "feature_extractor")), os.path.join(path, "image_embedder")
+            D, J, rsd = loader.load_redux(path)
+        else:
+            D, J, rsd = loader.redux_from_tensors(path)
+        if image_encoder is None:
+            raise ValueError("load_redux: an embedder alone needs the SigLIP tower in image_encoder=")
+        if isinstance(image_encoder, tuple) and isinstance(image_encoder[0], dict):
+            cfg, sd = image_encoder
+            cfg = dict(loader.siglip_vision_config(cfg), **{k: cfg[k] for k in ("image_mean", "image_std") if k in cfg})
+            sd = loader.siglip_vision_from_tensors(cfg, sd)
+        else:
+            enc_dir, pre_dir = image_encoder if isinstance(image_encoder, tuple) else (image_encoder, None)
+            cfg, sd = loader.load_siglip_vision(os.fspath(enc_dir), pre_dir)
+        if J != self.flux.cfg["joint_attention_dim"]:
+            raise ValueError(f"the Redux embedder's txt_in_features is {J}, the transformer's joint_attention_dim is {self.flux.cfg['joint_attention_dim']}")
+        if D != cfg["hidden_size"]:
+            raise ValueError(f"the Redux embedder's redux_dim is {D}, the SigLIP tower's hidden_size is {cfg['hidden_size']}")
+        with self._lock:
+            tower = text.SiglipVisionModel(cfg, self.device.index or 0, cfg.get("image_mean"), cfg.get("image_std"))
+            tower.load_state_dict(sd)
+            emb = text.ReduxImageEmbedder(D, J, self.device.index or 0)
+            emb.load_state_dict(rsd)
+            old, self.redux = getattr(self, "redux", None), (tower, emb)
+            for m in old or ():
+                m.close()
+        return self.redux
+
+    def unload_redux(self):
+        with self._lock:
+            old, self.redux = getattr(self, "redux", None), None
+            for m in old or ():
+                m.close()
+
+    def encode_redux_image(self, image) -> torch.Tensor:
+        """The Redux image tokens of a picture: u8 (H,W,3) of any size, or float (1,3,S,S) pixel_values -> (1,Np,J) f32 on the device, before any scale: what
+        redux_image_embeds= takes and what redux_image= passes on.  ValueError without a loaded Redux."""
+        rdx = getattr(self, "redux", None)
+        if rdx is None:
+            raise ValueError("encode_redux_image needs a loaded Redux: Pipeline.load_redux(path) first")
+        tower, emb = rdx
+        img = _host_image(image, "image")
+        S = tower.cfg["image_size"]
+        if not ((img.dim() == 3 and img.shape[2] == 3) if img.dtype == torch.uint8 else tuple(img.shape) == (1, 3, S, S)):
+            raise ValueError(f"image must be a uint8 (H,W,3) picture of any size or float (1,3,{S},{S}) pixel_values, got {tuple(img.shape)}")
+        with self._lock:
+            return emb.forward(tower.encode(img))
 
     def load_controlnet(self, source):
         """Load ONE ControlNet next to the transformer: a diffusers directory (loader.load_controlnet: config.json with _class_name
@@ -1043,7 +1181,7 @@ class Pipeline:
                 negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
-                ip_adapter_image=None, negative_ip_adapter_image=None, **kw):
+                ip_adapter_image=None, negative_ip_adapter_image=None, redux_image=None, redux_image_embeds=None, redux_scale: float = 1.0, **kw):
         """== Pipeline::forward (pipelines/mod.rs:241-270) + the PNG encode of the pyo3 binding.
         With torch.distributed initialised the batch is sharded (prompt i on rank i % world, no data-path collective) and
         the images are gathered to rank 0; every rank must make the same call, ranks != 0 return None.
@@ -1057,7 +1195,9 @@ class Pipeline:
         ip_adapter_image_embeds= / negative_ip_adapter_image_embeds= / ip_adapter_scale= / ip_adapter_start= / ip_adapter_end=: the image prompt of the IP-Adapter of
         load_ip_adapter, see generate_tensor — one embedding per request, likewise (every rank loads the same adapter).  ip_adapter_image= /
         negative_ip_adapter_image=: the same prompt as a picture, encoded by the image encoder of load_image_encoder (every rank loads the same one and encodes
-        the picture itself)."""
+        the picture itself).
+        redux_image= / redux_image_embeds= / redux_scale=: FLUX.1 Redux image variation (load_redux), see generate_tensor — one picture per request, likewise
+        (every rank loads the same Redux and encodes the picture itself)."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -1066,7 +1206,8 @@ class Pipeline:
                        controlnet_conditioning_scale=controlnet_conditioning_scale, control_guidance_start=control_guidance_start,
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
-                       ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image)
+                       ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image,
+                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

@@ -574,6 +574,38 @@ def clip_vision_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     return out
 
 
+def siglip_vision_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
+    """Tensor names/shapes of HuggingFace's SiglipVisionModel without its pooling head (vision_model.head.*), cfg: SiglipVisionConfig's keys."""
+    D, F, P = cfg["hidden_size"], cfg["intermediate_size"], cfg["patch_size"]
+    out = OrderedDict()
+    vm = "vision_model."
+    out[vm + "embeddings.patch_embedding.weight"] = (D, 3, P, P)
+    out[vm + "embeddings.patch_embedding.bias"] = (D,)
+    out[vm + "embeddings.position_embedding.weight"] = ((cfg["image_size"] // P) ** 2, D)
+    for l in range(cfg["num_hidden_layers"]):
+        p = vm + f"encoder.layers.{l}."
+        for ln in ("layer_norm1", "layer_norm2"):
+            out[p + ln + ".weight"] = (D,)
+            out[p + ln + ".bias"] = (D,)
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            out[p + f"self_attn.{n}.weight"] = (D, D)
+            out[p + f"self_attn.{n}.bias"] = (D,)
+        out[p + "mlp.fc1.weight"] = (F, D)
+        out[p + "mlp.fc1.bias"] = (F,)
+        out[p + "mlp.fc2.weight"] = (D, F)
+        out[p + "mlp.fc2.bias"] = (D,)
+    out[vm + "post_layernorm.weight"] = (D,)
+    out[vm + "post_layernorm.bias"] = (D,)
+    return out
+
+
+def redux_tensor_shapes(redux_dim: int, txt_dim: int) -> "OrderedDict[str, tuple]":
+    """Tensor names/shapes of diffusers' ReduxImageEncoder (and of BFL's flux1-redux-dev.safetensors): redux_dim = the tower's hidden_size, txt_dim = the
+    transformer's joint_attention_dim."""
+    D, J = int(redux_dim), int(txt_dim)
+    return OrderedDict([("redux_up.weight", (3 * J, D)), ("redux_up.bias", (3 * J,)), ("redux_down.weight", (J, 3 * J)), ("redux_down.bias", (J,))])
+
+
 def text_state_dict_numpy(shapes, seed=0, round_bf16=True):
     """Seeded synthetic encoder weights: matrices ~N(0, 1/fan_in) (a convolution's (out, in, k, k) weight too), embeddings ~N(0,1) (T5 relative
     bias ~N(0,1)), norm weights 1 + 0.1 N(0,1), biases 0.1 N(0,1); rounded to bf16 values."""

@@ -3,6 +3,8 @@
     T5EncoderModel        <-> diffusion_rs_core::models::t5::T5EncoderModel        (t5/mod.rs:609-632)
     ClipTextTransformer   <-> diffusion_rs_core::models::clip::text::ClipTextTransformer (clip/text.rs:243-317)
     ClipVisionModel       <-> HuggingFace's CLIPVisionModelWithProjection + CLIPImageProcessor (not in the reference)
+    SiglipVisionModel     <-> HuggingFace's SiglipVisionModel.last_hidden_state + SiglipImageProcessor (not in the reference)
+    ReduxImageEmbedder    <-> diffusers' ReduxImageEncoder (not in the reference)
     tokenize_and_pad      <-> FluxPipeline::tokenize_and_pad (pipelines/flux/mod.rs:202-221)
     load_bpe_tokenizer    <-> diffusion_rs_common::load_bpe_tokenizer (tokenizer.rs:7-23)
 
@@ -26,6 +28,10 @@ _T5_ACT = {"relu": 0, "gated-gelu": 1, "gated-silu": 2}
 CLIP_VISION_L = dict(image_size=224, patch_size=14, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, projection_dim=768)
 CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+# google/siglip-so400m-patch14-384's vision tower (the image encoder of FLUX.1 Redux) and its image processor's constants
+SIGLIP_SO400M = dict(image_size=384, patch_size=14, hidden_size=1152, intermediate_size=4304, num_hidden_layers=27, num_attention_heads=16, layer_norm_eps=1e-6)
+SIGLIP_IMAGE_MEAN = (0.5, 0.5, 0.5)
+SIGLIP_IMAGE_STD = (0.5, 0.5, 0.5)
 
 
 class _Encoder:
@@ -237,6 +243,116 @@ class ClipVisionModel(_Encoder):
         """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> image_embeds f32."""
         t = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
         return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
+
+
+class SiglipVisionModel(_Encoder):
+    """SigLIP's vision tower with its image processor on the GPU: a picture -> last_hidden_state (1, Np, hidden_size), what the Redux embedder
+    reads.  cfg: HuggingFace's SiglipVisionConfig keys (SIGLIP_SO400M by default); image_mean / image_std: the processor's constants.  The pooling head of the
+    checkpoint is not part of the model."""
+    _kind = "siglip_vision"
+
+    def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None):
+        self.lib = L.load()
+        L.check(self.lib.fmi_init(device), self.lib)
+        self.device = torch.device("cuda", device)
+        src = SIGLIP_SO400M if cfg is None else cfg
+        cfg = {k: (float(src.get(k, 1e-6)) if k == "layer_norm_eps" else int(src[k])) for k in SIGLIP_SO400M}
+        self.cfg = cfg
+        self.image_mean = tuple(float(v) for v in (SIGLIP_IMAGE_MEAN if image_mean is None else image_mean))
+        self.image_std = tuple(float(v) for v in (SIGLIP_IMAGE_STD if image_std is None else image_std))
+        if len(self.image_mean) != 3 or len(self.image_std) != 3:
+            raise ValueError("image_mean and image_std hold one value per RGB channel")
+        c = L.SiglipVisionConfig(*(cfg[k] for k in SIGLIP_SO400M))
+        h = C.c_void_p()
+        L.check(self.lib.fmi_siglip_vision_create(C.byref(c), C.byref(h)), self.lib)
+        self.h = h
+
+    @property
+    def hidden_size(self) -> int:
+        return self.cfg["hidden_size"]
+
+    @property
+    def num_patches(self) -> int:
+        return (self.cfg["image_size"] // self.cfg["patch_size"]) ** 2
+
+    def tensor_names(self):
+        from . import synth
+        return synth.siglip_vision_tensor_shapes(self.cfg)
+
+    def forward(self, pixel_values, dtype=torch.float32):
+        """== SiglipVisionModel.forward(...).last_hidden_state: pixel_values (B,3,S,S) float -> (B, Np, hidden_size) f32 (or bf16): post_layernorm of every row."""
+        S, D = self.cfg["image_size"], self.cfg["hidden_size"]
+        t = torch.from_numpy(pixel_values) if not isinstance(pixel_values, torch.Tensor) else pixel_values
+        if t.dim() != 4 or tuple(t.shape[1:]) != (3, S, S) or not t.is_floating_point():
+            raise ValueError(f"pixel_values must be float (B,3,{S},{S}), got {t.dtype} {tuple(t.shape)}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        B = int(t.shape[0])
+        out = torch.empty((B, self.num_patches, D), dtype=dtype, device=self.device)
+        L.check(self.lib.fmi_siglip_vision_forward(self.h, _ptr(t), B, _ptr(out), L.F32 if dtype == torch.float32 else L.BF16, _stream()), self.lib)
+        return out
+
+    def poison_workspace(self, B: int = 1):
+        """Test seam (fmi_siglip_vision_poison_workspace): the workspace of a batch of B, every byte 0xff — NaNs wherever a forward reads what it did not write."""
+        L.check(self.lib.fmi_siglip_vision_poison_workspace(self.h, int(B), _stream()), self.lib)
+
+    def resize(self, image_u8, nh: int, nw: int):
+        """u8 (h,w,3) -> u8 (nh,nw,3) on the device, PIL's Image.resize(BICUBIC) (fmi_resize_bicubic_u8)."""
+        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
+        t = t.to(self.device).contiguous()
+        out = torch.empty((int(nh), int(nw), 3), dtype=torch.uint8, device=self.device)
+        L.check(self.lib.fmi_resize_bicubic_u8(_ptr(t), int(t.shape[0]), int(t.shape[1]), _ptr(out), int(nh), int(nw), _stream()), self.lib)
+        return out
+
+    def preprocess(self, image_u8):
+        """SiglipImageProcessor on the device: u8 (H,W,3) of any size -> pixel_values (1,3,S,S) f32 — resized straight to S x S (no aspect rule, no crop),
+        (v / 255 - mean) / std."""
+        S = self.cfg["image_size"]
+        r = self.resize(image_u8, S, S)
+        out = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
+        mean, std = (C.c_float * 3)(*self.image_mean), (C.c_float * 3)(*self.image_std)
+        L.check(self.lib.fmi_clip_preprocess_u8(_ptr(r), S, S, S, mean, std, _ptr(out), _stream()), self.lib)  # (nh = nw = S: the crop takes everything)
+        return out
+
+    def encode(self, image):
+        """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> last_hidden_state f32."""
+        t = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
+        return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
+
+
+class ReduxImageEmbedder(_Encoder):
+    """diffusers' ReduxImageEncoder on the GPU: SigLIP hidden states (.., Np, redux_dim) -> image tokens (.., Np, txt_dim) =
+    scale * redux_down(silu(redux_up(h)))."""
+    _kind = "redux"
+
+    def __init__(self, redux_dim: int = 1152, txt_dim: int = 4096, device: int = 0):
+        self.lib = L.load()
+        L.check(self.lib.fmi_init(device), self.lib)
+        self.device = torch.device("cuda", device)
+        self.redux_dim, self.txt_dim = int(redux_dim), int(txt_dim)
+        h = C.c_void_p()
+        L.check(self.lib.fmi_redux_create(self.redux_dim, self.txt_dim, C.byref(h)), self.lib)
+        self.h = h
+
+    def tensor_names(self):
+        from . import synth
+        return synth.redux_tensor_shapes(self.redux_dim, self.txt_dim)
+
+    def forward(self, hidden, scale: float = 1.0, dtype=torch.float32):
+        """hidden (.., redux_dim) float -> (.., txt_dim) f32 (or bf16)."""
+        t = torch.from_numpy(hidden) if not isinstance(hidden, torch.Tensor) else hidden
+        if t.dim() < 2 or t.shape[-1] != self.redux_dim or not t.is_floating_point() or t.numel() == 0:
+            raise ValueError(f"hidden must be float (.., {self.redux_dim}), got {t.dtype} {tuple(t.shape)}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        rows = t.numel() // self.redux_dim
+        out = torch.empty(tuple(t.shape[:-1]) + (self.txt_dim,), dtype=dtype, device=self.device)
+        L.check(self.lib.fmi_redux_forward(self.h, _ptr(t), rows, float(scale), _ptr(out), L.F32 if dtype == torch.float32 else L.BF16, _stream()), self.lib)
+        return out
 
 
 # ---------------------------------------------------------------------------------- tokenisation

@@ -54,6 +54,7 @@ extern "C" {
  *   Then, still 6: GGUF transformers (ggml block formats) — fmi_gguf_block_info, fmi_gguf_dequantize, fmi_flux_set_linear_gguf.
  *   Then, still 6: FLUX IP-Adapters (image prompts) — fmi_ip_adapter_*, fmi_flux_ip, fmi_flux_forward_ip, fmi_flux_denoise_ip, fmi_ip_attention.
  *   Then, still 6: the CLIP vision encoder (an image prompt from a picture) — fmi_resize_bicubic_u8, fmi_clip_preprocess_u8, fmi_clip_vision_*.
+ *   Then, still 6: FLUX.1 Redux (image variation: a SigLIP vision tower and the Redux embedder) — fmi_siglip_vision_*, fmi_redux_*.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -821,6 +822,56 @@ size_t fmi_clip_vision_size_in_bytes(const fmi_clip_vision*);
  * optional (NULL to skip): the encoder's output before post_layernorm, HF's last_hidden_state.  Synchronises the stream
  * before returning. */
 int fmi_clip_vision_forward(fmi_clip_vision*, const float* pixel_values, int B, void* image_embeds_out, fmi_dtype dtype, float* hidden_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * FLUX.1 Redux (not in the reference; diffusers' FluxPriorReduxPipeline): image variation.  A SigLIP
+ * vision tower turns a picture into (Np, D) hidden states, the Redux embedder turns those into (Np, J) image tokens, and
+ * the caller appends scale * tokens behind the T5 rows of fmi_flux_inputs.txt (T = T_prompt + Np, txt_ids zeros): the
+ * denoise loop itself is unchanged.  The picture is prepared by fmi_resize_bicubic_u8 straight to S x S and
+ * fmi_clip_preprocess_u8 with nh = nw = S, which crops nothing.
+ * ---------------------------------------------------------------------------------- */
+/* HuggingFace's SiglipVisionConfig; hidden_act is gelu_pytorch_tanh */
+typedef struct fmi_siglip_vision_config {
+  int image_size, patch_size, hidden_size, intermediate_size, num_hidden_layers, num_attention_heads;
+  float layer_norm_eps;
+} fmi_siglip_vision_config;
+typedef struct fmi_siglip_vision fmi_siglip_vision;
+void fmi_siglip_vision_default_config(fmi_siglip_vision_config*); /* google/siglip-so400m-patch14-384: 384 / 14 / 1152 / 4304 / 27 / 16 / 1e-6 */
+/* hidden_size a multiple of 64; head dim (hidden_size / num_attention_heads) any multiple of 8 up to 128 — the attention
+ * runs at d = 128 on heads that are zero-padded in the weights; intermediate_size any positive size (padded to the next
+ * multiple of 64 the same way); image_size >= patch_size: the convolution has no padding, so there are G = image_size /
+ * patch_size (rounded down) patches per side, Np = G^2, and the pixels past G * patch_size are not read (384 / 14: 27) */
+int fmi_siglip_vision_create(const fmi_siglip_vision_config*, fmi_siglip_vision** out);
+void fmi_siglip_vision_destroy(fmi_siglip_vision*);
+/* HuggingFace's names (SiglipVisionModel): vision_model.embeddings.{patch_embedding.{weight (D,3,P,P), bias (D)},
+ * position_embedding.weight (Np, D)}, vision_model.encoder.layers.N.{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2,
+ * mlp.fc1, mlp.fc2}.{weight,bias}, vision_model.post_layernorm.{weight,bias}.  The pooling head (vision_model.head.*) is
+ * not part of the model: the caller drops it. */
+int fmi_siglip_vision_set_tensor(fmi_siglip_vision*, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank);
+int fmi_siglip_vision_missing_count(const fmi_siglip_vision*);
+const char* fmi_siglip_vision_missing_name(fmi_siglip_vision*, int i);
+size_t fmi_siglip_vision_size_in_bytes(const fmi_siglip_vision*);
+/* == SiglipVisionModel.forward(...).last_hidden_state: pixel_values (B,3,S,S) f32 device -> hidden_out (B, Np, D), FMI_F32
+ * or FMI_BF16, Np = (S / P rounded down)^2: post_layernorm of every row.  Synchronises the stream before returning. */
+int fmi_siglip_vision_forward(fmi_siglip_vision*, const float* pixel_values, int B, void* hidden_out, fmi_dtype dtype, void* stream);
+/* Test seam: sizes the handle's workspace for a batch of B and fills every byte of it with 0xff (a NaN in bf16 and in f32),
+ * so that a following forward shows whether anything reads a lane it did not write.  Synchronises the stream. */
+int fmi_siglip_vision_poison_workspace(fmi_siglip_vision*, int B, void* stream);
+
+/* diffusers' ReduxImageEncoder: redux_up Linear(redux_dim -> 3 txt_dim), SiLU, redux_down Linear(3 txt_dim -> txt_dim), both
+ * biased; redux_dim and txt_dim multiples of 64 */
+typedef struct fmi_redux fmi_redux;
+int fmi_redux_create(int redux_dim, int txt_dim, fmi_redux** out);
+void fmi_redux_destroy(fmi_redux*);
+/* redux_up.{weight (3 J, D), bias (3 J)}, redux_down.{weight (J, 3 J), bias (J)} */
+int fmi_redux_set_tensor(fmi_redux*, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank);
+int fmi_redux_missing_count(const fmi_redux*);
+const char* fmi_redux_missing_name(fmi_redux*, int i);
+size_t fmi_redux_size_in_bytes(const fmi_redux*);
+/* hidden (rows, redux_dim) f32 device (rounded to bf16 for the first GEMM) -> out (rows, txt_dim), FMI_F32 or FMI_BF16 =
+ * scale * redux_down(silu(redux_up(hidden))): the scale multiplies the biased result, in f32, before the one rounding of a
+ * bf16 output.  scale finite.  Synchronises the stream before returning. */
+int fmi_redux_forward(fmi_redux*, const float* hidden, int rows, float scale, void* out, fmi_dtype dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Pipeline glue on device — the tensor code of FluxPipeline::forward
