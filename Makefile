@@ -78,7 +78,11 @@ clean:
 gguf-bench: lib
 	python3 tools/gguf_bench.py --out profiles/gguf.txt
 
-.PHONY: all lib alt oracle clean gguf-bench FORCE
+# single-file fp8 checkpoint measurements (needs an MI355X): fmi_f8_dequantize next to the Q8_0 and nf4 kernels, and the FLUX.1-dev shape with e4m3 weights
+single-file-bench: lib
+	python3 tools/single_file_bench.py --out profiles/single_file.txt
+
+.PHONY: all lib alt oracle clean gguf-bench single-file-bench FORCE
 
 print-build-id:
 	@echo $(BUILD_ID)

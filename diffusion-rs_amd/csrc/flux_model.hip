@@ -9,7 +9,8 @@
 //   MOD     the modulation matrix in bf16 (6.5 GB)                             (allocated when a dense part arrives)
 //   BLOCKS  the block linears in bf16 (17.0 GB)                                (allocated when a dense part arrives)
 //   Q4      the same matrices as bitsandbytes nf4 / fp4 codes + f32 absmax     (allocated when a 4-bit part arrives)
-// LLM.int8 matrices and ggml blocks (fmi_flux_set_linear_gguf: 4.5 to 8.5 bits per weight) do not fit Q4's slots: the matrix owns them (Dense::own_wq, Dense::gq).
+// LLM.int8 matrices, ggml blocks (fmi_flux_set_linear_gguf: 4.5 to 8.5 bits per weight) and 8-bit float codes (fmi_flux_set_linear_f8) do not fit Q4's slots:
+// the matrix owns them (Dense::own_wq, Dense::gq).
 // so a bf16 checkpoint occupies 23.8 GB and an nf4 one 6.7 GB — no bf16 duplicate of a quantised layer is resident
 // unless the caller asks for the expanded cache (fmi_flux_set_quant_dense_cache).  The arenas are also the unit of
 // the multi-GPU weight broadcast (fmi_flux_state_*).  Activations live in a per-(B,S,T) workspace that is allocated
@@ -37,8 +38,12 @@ struct Arena {
   size_t bytes = 0;  // layout size (known before the arena is allocated)
 };
 // PS_GGUF0 + ggml type id (2 .. 14): the part is resident as ggml blocks (fmi_flux_set_linear_gguf), in Dense::gq
-enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_GGUF0 = 16, PS_GGUF_END = 48, PS_DENSE = 100 };
+// PS_F8_E4M3 / PS_F8_E5M2: the part is resident as OCP e4m3fn / e5m2 codes (fmi_flux_set_linear_f8), in Dense::gq too, its scale in Dense::gscale
+enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_GGUF0 = 16, PS_GGUF_END = 48, PS_F8_E4M3 = 48, PS_F8_E5M2 = 49, PS_DENSE = 100 };
 inline bool is_gguf(int state) { return state >= PS_GGUF0 && state < PS_GGUF_END; }
+inline bool is_f8(int state) { return state == PS_F8_E4M3 || state == PS_F8_E5M2; }
+// kinds that have no fused dequant-GEMM and live in Dense::gq: always expanded, once or per call
+inline bool is_codes(int state) { return is_gguf(state) || is_f8(state); }
 
 struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N) bf16
   bf16_t* w = nullptr;  // null until the arena `ar` is allocated
@@ -50,10 +55,13 @@ struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N)
   uint8_t* wq = nullptr;   // Q4 arena (4-bit) or own_wq (int8): what the kernels read
   float* absmax = nullptr;
   DeviceBuffer own_wq, own_absmax;  // int8 matrices own their storage (1 B per weight: they do not fit the 4-bit arena's slots)
-  int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N)), PS_GGUF0 + ggml type (blocks in gq; wq stays null)
+  int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N)), PS_GGUF0 + ggml type / PS_F8_* (blocks or codes in gq; wq stays null)
   // ggml blocks of the parts loaded with fmi_flux_set_linear_gguf, one allocation per part (5 to 8.5 bits per weight: they do not fit the 4-bit
   // arena's slots, and the parts of one matrix may differ in type until finalize() decides); empty on a matrix that never saw such a part
+  // The 8-bit float codes of fmi_flux_set_linear_f8 live here as well, with one scale per part in gscale (the parts' scales may differ: the expansion
+  // runs per part).
   std::vector<DeviceBuffer> gq;
+  std::vector<float> gscale;
   // optional fp8 form (fmi_flux_quantize_fp8): e4m3 (N,K) + per-output-channel f32 scale, used instead of w
   uint8_t* w8 = nullptr;
   float* w8_scale = nullptr;
@@ -433,16 +441,18 @@ int dequant_rows(Dense& d, int r0, int rows, int kind, int blocksize, hipStream_
   return FMI_OK;
 }
 
-// ggml blocks of part `part` of `d` -> its bf16 rows of `dst` (a (N, K) image of the matrix: d.w or the scratch)
+// ggml blocks / 8-bit float codes of part `part` of `d` -> its bf16 rows of `dst` (a (N, K) image of the matrix: d.w or the scratch)
 int expand_gguf_part(Dense& d, int part, bf16_t* dst, hipStream_t s) {
   const Dense::Part& pt = d.parts[part];
+  if (is_f8(pt.state))
+    return fmi_f8_dequantize(pt.state == PS_F8_E4M3 ? 1 : 2, d.gq[part].ptr, (int64_t)pt.rows * d.K, d.gscale[part], dst + (size_t)pt.r0 * d.K, FMI_BF16, s);
   return fmi_gguf_dequantize(pt.state - PS_GGUF0, d.gq[part].ptr, (int64_t)pt.rows * d.K, dst + (size_t)pt.r0 * d.K, FMI_BF16, s);
 }
 int expand_gguf(Dense& d, bf16_t* dst, hipStream_t s) {
   for (int i = 0; i < (int)d.parts.size(); ++i) FMI_TRY(expand_gguf_part(d, i, dst, s));
   return FMI_OK;
 }
-// a part stops being resident as ggml blocks (another setter takes it over)
+// a part stops being resident as ggml blocks / 8-bit float codes (another setter takes it over)
 void drop_gguf_part(Dense& d, int part) {
   if (part < (int)d.gq.size()) d.gq[part].reset();
 }
@@ -469,12 +479,12 @@ int finalize(fmi_flux* m) {
       for (int i = 0; i < (int)d->parts.size(); ++i) {
         auto& pt = d->parts[i];
         if (pt.state == PS_DENSE) continue;
-        if (is_gguf(pt.state)) FMI_TRY(expand_gguf_part(*d, i, d->w, nullptr));
+        if (is_codes(pt.state)) FMI_TRY(expand_gguf_part(*d, i, d->w, nullptr));
         else FMI_TRY(dequant_rows(*d, pt.r0, pt.rows, pt.state, pt.blocksize, nullptr));
         pt.state = PS_DENSE, pt.blocksize = 0;
       }
       FMI_HIP_TRY(hipDeviceSynchronize());
-      d->gq.clear();  // (after the synchronisation: the expansions have read the blocks)
+      d->gq.clear(), d->gscale.clear();  // (after the synchronisation: the expansions have read the blocks)
     }
     d->q_type = 0, d->q_blocksize = 0;
   }
@@ -656,7 +666,7 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
   // one decision per launch group (the img + txt problems of a double block stay one grouped launch)
   bool scratch = false;
   for (int i = 0; i < n && i < 2; ++i)
-    if (dn[i] && p[i].q_type && !is_gguf(p[i].q_type) && m->quant_mode != 1 && m->quant_mode != 2)
+    if (dn[i] && p[i].q_type && !is_codes(p[i].q_type) && m->quant_mode != 1 && m->quant_mode != 2)
       scratch = scratch || p[i].M > (p[i].q_type == 3 ? INT8_FUSED_MAX_ROWS : Q4_FUSED_MAX_ROWS);
   // A matrix of 2^31 or more weights (the fused modulation matrix of FLUX.1: 344 D x D = 3.2e9) never goes through the scratch —
   // the stand-alone dequant launchers count elements in 32 bits and the scratch is sized for the block matrices — it stays on
@@ -666,8 +676,9 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
   for (int i = 0; i < n && i < 2; ++i) {
     Dense* d = dn[i];
     if (!d || !p[i].q_type) continue;
-    // ggml blocks (fmi_flux_set_linear_gguf) have no fused dequant-GEMM: at every row count the matrix is expanded, once (modes 1 and 3) or per call (0 and 2)
-    const bool gguf = is_gguf(p[i].q_type);
+    // ggml blocks (fmi_flux_set_linear_gguf) and 8-bit float codes (fmi_flux_set_linear_f8) have no fused dequant-GEMM: at every row count the matrix is
+    // expanded, once (modes 1 and 3) or per call (0 and 2)
+    const bool gguf = is_codes(p[i].q_type);
     if (!m->dense_cache && !scratch && !gguf) continue;  // fused paths (launch_gemm picks the kernel)
     const size_t elems = (size_t)p[i].N * p[i].K;
     bool once = m->dense_cache || ((scratch || gguf) && resolve_quant_mode(m) == 3);
@@ -1740,6 +1751,55 @@ extern "C" int fmi_flux_set_linear_gguf(fmi_flux* m, const char* prefix, int ggm
   return FMI_OK;
 }
 
+// A Linear as OCP e4m3fn / e5m2 codes with one scale (single-file fp8 checkpoints; f8_dequant.hip).  As fmi_flux_set_linear_gguf: embedders, the final
+// layer and the modulation linears are expanded into their bf16 rows here; the parts of a fused block matrix keep their codes (Dense::gq) and their
+// scale (Dense::gscale), and finalize() / densify() decide.
+extern "C" int fmi_flux_set_linear_f8(fmi_flux* m, const char* prefix, int format, const void* codes, float scale, int out_features, int in_features) {
+  if (!m || !prefix || !codes) return fail(FMI_ERR_INVALID, "set_linear_f8: null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_f8: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
+  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_f8: the model was quantised to 8 bits");
+  if (format != 1 && format != 2) return fail(FMI_ERR_INVALID, "set_linear_f8: format must be 1 (OCP e4m3fn) or 2 (OCP e5m2), got " + std::to_string(format));
+  if (!std::isfinite(scale) || !(scale > 0.f)) return fail(FMI_ERR_INVALID, "set_linear_f8: scale must be finite and > 0");
+  if (in_features <= 0 || out_features <= 0) return fail(FMI_ERR_INVALID, "set_linear_f8: in_features and out_features must be positive");
+  FMI_TRY(use_device(m));
+  const std::string wname = std::string(prefix) + ".weight";
+  auto it = m->names.find(wname);
+  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_f8: unknown linear '") + prefix + "'");
+  for (const auto& ad : m->loras)
+    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_f8: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
+  const Dest& dst = it->second;
+  Dense* d = dst.d;
+  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_f8: shape mismatch for " + wname);
+  const int64_t n = (int64_t)out_features * in_features;
+  DeviceBuffer buf;
+  FMI_HIP_TRY(buf.alloc((size_t)n));
+  FMI_HIP_TRY(hipMemcpy(buf.ptr, codes, (size_t)n, hipMemcpyDefault));
+  Dense::Part& pt = d->parts[dst.part];
+  if (d->ar == AR_BASE || d->ar == AR_MOD) {
+    FMI_TRY(ensure_arena(m, d->ar));
+    FMI_TRY(fmi_f8_dequantize(format, buf.ptr, n, scale, d->w + (size_t)pt.r0 * d->K, FMI_BF16, nullptr));
+    FMI_HIP_TRY(hipDeviceSynchronize());
+    if (d->ar == AR_MOD) {
+      pt.state = PS_DENSE, pt.blocksize = 0;
+      m->dense_ready.erase(d);
+      m->finalized = false;
+    }
+    m->attn_scales_valid = false;
+    m->missing.erase(wname);
+    return FMI_OK;
+  }
+  if (d->gq.size() < d->parts.size()) d->gq.resize(d->parts.size());
+  if (d->gscale.size() < d->parts.size()) d->gscale.resize(d->parts.size(), 1.0f);
+  FMI_HIP_TRY(hipDeviceSynchronize());  // (a replaced part's codes may still be read by an expansion in flight)
+  d->gq[dst.part] = std::move(buf);
+  d->gscale[dst.part] = scale;
+  pt.state = (uint8_t)(format == 1 ? PS_F8_E4M3 : PS_F8_E5M2), pt.blocksize = 0;
+  m->dense_ready.erase(d);
+  m->finalized = false;
+  m->missing.erase(wname);
+  return FMI_OK;
+}
+
 extern "C" int fmi_flux_missing_count(const fmi_flux* m) { return m ? m->missing.count() : 0; }
 extern "C" const char* fmi_flux_missing_name(const fmi_flux* m, int i) { return m ? m->missing.name(i) : nullptr; }
 extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
@@ -1785,6 +1845,7 @@ extern "C" int fmi_flux_state_export(fmi_flux* m, uint8_t* blob_host, size_t cap
   for (const Dense* d : m->fused) {
     if (d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_export: LLM.int8 matrices are not part of the flat weight state");
     if (is_gguf(d->q_type)) return fail(FMI_ERR_UNSUPPORTED, "state_export: matrices resident as ggml blocks are not part of the flat weight state");
+    if (is_f8(d->q_type)) return fail(FMI_ERR_UNSUPPORTED, "state_export: matrices resident as 8-bit float codes are not part of the flat weight state");
     *o++ = (uint8_t)d->q_type;
     const uint32_t bs = (uint32_t)d->q_blocksize;
     memcpy(o, &bs, 4);
@@ -1809,8 +1870,8 @@ extern "C" int fmi_flux_state_adopt(fmi_flux* m, const uint8_t* blob_host, size_
     memcpy(&bs, o, 4);
     o += 4;
     if (qt == 3 || d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
-    if (is_gguf(qt)) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: matrices resident as ggml blocks are not part of the flat weight state");
-    d->gq.clear();
+    if (is_codes(qt)) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: matrices resident as ggml blocks or 8-bit float codes are not part of the flat weight state");
+    d->gq.clear(), d->gscale.clear();
     d->q_type = qt, d->q_blocksize = (int)bs;
     for (auto& pt : d->parts) pt.state = qt ? (uint8_t)qt : (uint8_t)PS_DENSE, pt.blocksize = (int)bs;
     if (qt ? !m->arena[AR_Q4].base : !m->arena[d->ar].base) return fail(FMI_ERR_INVALID, "state_adopt: blob is inconsistent (matrix stored in an arena that is not present)");

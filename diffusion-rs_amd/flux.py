@@ -391,6 +391,23 @@ class FluxModel:
                              f"{out_features * (in_features // be.value) * bb.value}", code=L.ERR_INVALID)
         L.check(self.lib.fmi_flux_set_linear_gguf(self.h, prefix.encode(), int(ggml_type), p, out_features, in_features), self.lib)
 
+    def set_linear_f8(self, prefix: str, fmt, codes, scale: float, out_features: int, in_features: int):
+        """A Linear as 8-bit float codes with one scale (include/flux_mi355x.h: fmi_flux_set_linear_f8): row-major (out_features, in_features), one code per
+        weight.  fmt: "e4m3" | "e5m2" (or 1 | 2).  `codes`: a torch tensor of dtype float8_e4m3fn / float8_e5m2 / uint8 (host or device), or anything with the
+        buffer protocol (numpy uint8 array, memoryview of an mmap) — not copied here."""
+        if isinstance(codes, torch.Tensor):
+            keep = codes.contiguous()
+            if keep.dtype in F8_TORCH.values():
+                keep = keep.view(torch.uint8)
+            assert keep.dtype == torch.uint8
+            p, nbytes = C.c_void_p(keep.data_ptr()), keep.numel()
+        else:
+            keep = np.frombuffer(codes, np.uint8) if not isinstance(codes, np.ndarray) else np.ascontiguousarray(codes).view(np.uint8).reshape(-1)
+            p, nbytes = C.c_void_p(keep.ctypes.data), keep.size
+        if nbytes != out_features * in_features:
+            raise L.FmiError(f"set_linear_f8: {prefix}: {nbytes} codes for a ({out_features}, {in_features}) Linear", code=L.ERR_INVALID)
+        L.check(self.lib.fmi_flux_set_linear_f8(self.h, prefix.encode(), f8_format(fmt), p, float(scale), out_features, in_features), self.lib)
+
     def quantize_fp8(self, stream=None):
         """Switch the DiT block linears to the fp8 (OCP e4m3) MFMA path: weights quantised once per output
         channel from the loaded bf16 values, activations per token on the fly (BASELINE configs[4])."""
@@ -433,7 +450,7 @@ class FluxModel:
         """Quantised linears, launches above 383 (nf4 / fp4) / 256 (LLM.int8) rows — smaller ones always multiply from the packed codes:
         -1 (default) = by memory: 3 when the device has the room, else 0; 0 / False = packed only: per-call expansion into a 264 MB
         scratch + dense GEMM; 1 / True = every matrix expanded once into the bf16 arenas; 2 = always the fused kernels; 3 = the matrices
-        of the large launches expanded once.  Same bits in every mode.  Matrices resident as ggml blocks (set_linear_gguf) have no fused kernel:
+        of the large launches expanded once.  Same bits in every mode.  Matrices resident as ggml blocks (set_linear_gguf) or 8-bit float codes (set_linear_f8) have no fused kernel:
         at every row count they are expanded once (1, 3, and -1 with the room) or per call (0, and 2 — which has no fused kernel to select there)."""
         L.check(self.lib.fmi_flux_set_quant_dense_cache(self.h, int(mode)), self.lib)
 
@@ -923,6 +940,33 @@ def latent_mask(mask, Cc=16):
         raise ValueError(f"latent_mask: H and W must be multiples of 16, got {H} x {W}")
     out = torch.empty((B, (H // 16) * (W // 16), Cc * 4), dtype=torch.float32, device=mask.device)
     L.check(L.load().fmi_latent_mask(_ptr(mask), B, Cc, H, W, _ptr(out), _stream()))
+    return out
+
+
+# ---- 8-bit float weights of single-file checkpoints
+F8_FORMATS = {"e4m3": 1, "e5m2": 2}  # fmi_f8_dequantize's format argument: OCP e4m3fn / OCP e5m2
+F8_TORCH = {1: torch.float8_e4m3fn, 2: torch.float8_e5m2}
+
+
+def f8_format(fmt) -> int:
+    """"e4m3" | "e5m2" | a torch float8 dtype | 1 | 2 as the C ABI's format id; anything else is passed through as an int for the library to refuse."""
+    if fmt in F8_FORMATS:
+        return F8_FORMATS[fmt]
+    for k, dt in F8_TORCH.items():
+        if fmt is dt:
+            return k
+    return int(fmt)
+
+
+def f8_dequantize(codes, fmt, scale: float = 1.0, dtype=torch.bfloat16):
+    """fmi_f8_dequantize: the values of `codes` (a device tensor of dtype uint8 or torch's float8_e4m3fn / float8_e5m2; any shape, contiguous, any byte offset)
+    times `scale`, as a new tensor of the same shape: f32(code) exactly, one rounded f32 multiply, and for bfloat16 one RNE rounding."""
+    if not codes.is_cuda or not codes.is_contiguous() or codes.element_size() != 1:
+        raise TypeError("f8_dequantize: a contiguous device tensor of one-byte elements is required")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("f8_dequantize: dtype must be bfloat16 or float32")
+    out = torch.empty(codes.shape, dtype=dtype, device=codes.device)
+    L.check(L.load().fmi_f8_dequantize(f8_format(fmt), _ptr(codes), codes.numel(), float(scale), _ptr(out), _TORCH_DT[dtype], _stream()))
     return out
 
 

@@ -9,6 +9,9 @@ tensor naming, feeding the C-ABI's fmi_flux_set_tensor / fmi_flux_set_linear_bnb
                       diffusion_rs_backend::linear_b (lib.rs:197-266): a linear whose prefix has
                       `weight.absmax` / `weight.quant_state.bitsandbytes__{nf4,fp4}` is 4-bit
                       (bitsandbytes/mod.rs:137-222), nested absmax resolved as mod.rs:230-239.
+  load_flux_gguf / load_flux_single_file
+                      single-file transformers (not wired to FLUX in the reference): a .gguf of ggml blocks, or one .safetensors in BFL /
+                      diffusers naming whose weights may be 8-bit floats (F8_E4M3 / F8_E5M2) — DESIGN.md 4.16 and 4.20.
 There is no network here: hub model ids must already be local directories.
 """
 import io
@@ -26,7 +29,8 @@ import torch
 from . import synth
 
 _ST_DTYPES = {"F32": (torch.float32, 4), "F16": (torch.float16, 2), "BF16": (torch.bfloat16, 2), "U8": (torch.uint8, 1), "I8": (torch.int8, 1),
-              "I32": (torch.int32, 4), "I64": (torch.int64, 8), "F64": (torch.float64, 8)}
+              "I32": (torch.int32, 4), "I64": (torch.int64, 8), "F64": (torch.float64, 8),
+              "F8_E4M3": (torch.float8_e4m3fn, 1), "F8_E5M2": (torch.float8_e5m2, 1)}  # (OCP e4m3fn / e5m2: single-file fp8 checkpoints)
 
 
 SUPPORTED_PIPELINES = ("FluxPipeline", "FluxKontextPipeline")  # Kontext: the same components, FLUX.1-dev's transformer
@@ -800,53 +804,59 @@ def bfl_to_diffusers(name: str, rows: int, hidden: int):
     return [(f"{prefix}{t}.{kind}", [(bounds[i], bounds[i + 1])]) for i, t in enumerate(targets)]
 
 
-def gguf_flux_entries(gguf: "GgufFile"):
-    """The tensors of a FLUX transformer GGUF under their diffusers names: [(diffusers name, ggml_type, shape, source tensor, row ranges)], and the source
-    names that are no part of the transformer.  BFL naming or diffusers naming as is, told apart by `double_blocks.0.` against `transformer_blocks.0.`; an
-    optional `model.diffusion_model.` prefix is stripped.  ValueError for a file with neither."""
+def flux_entries_from_shapes(shapes: Dict[str, tuple], where: str):
+    """The tensors of a single-file FLUX transformer ({source name: shape, outer dimension first}) under their diffusers names: [(diffusers name, shape, source
+    tensor, row ranges)], and the source names that are no part of the transformer.  BFL naming or diffusers naming as is, told apart by `double_blocks.0.`
+    against `transformer_blocks.0.`; an optional `model.diffusion_model.` prefix is stripped.  ValueError for a file with neither.  Shared by the GGUF and the
+    single-file safetensors readers."""
     strip = "model.diffusion_model."
-    names = {(n[len(strip):] if n.startswith(strip) else n): n for n in gguf.names()}
+    names = {(n[len(strip):] if n.startswith(strip) else n): n for n in shapes}
     bfl = any(n.startswith("double_blocks.0.") for n in names)
     if not bfl and not any(n.startswith("transformer_blocks.0.") for n in names):
-        raise ValueError(f"{gguf.path}: neither BFL (double_blocks.0.*) nor diffusers (transformer_blocks.0.*) FLUX transformer tensors")
+        raise ValueError(f"{where}: neither BFL (double_blocks.0.*) nor diffusers (transformer_blocks.0.*) FLUX transformer tensors")
     hidden = None
     for key in ("img_in.weight", "x_embedder.weight"):
         if key in names:
-            hidden = gguf.tensors[names[key]][1][0]
+            hidden = shapes[names[key]][0]
     entries, skipped = [], []
     for short, full in names.items():
-        ggml_type, shape, _, _ = gguf.tensors[full]
+        shape = tuple(shapes[full])
         if not shape:
             skipped.append(full)
             continue
         if not bfl:
-            entries.append((short, ggml_type, shape, full, [(0, shape[0])]))
+            entries.append((short, shape, full, [(0, shape[0])]))
             continue
         mapped = bfl_to_diffusers(short, shape[0], hidden or 0)
         if mapped is None:
             skipped.append(full)
             continue
         for dname, ranges in mapped:
-            entries.append((dname, ggml_type, (sum(b - a for a, b in ranges),) + tuple(shape[1:]), full, ranges))
+            entries.append((dname, (sum(b - a for a, b in ranges),) + tuple(shape[1:]), full, ranges))
     return entries, skipped
 
 
-def flux_config_from_gguf(gguf: "GgufFile", base_config: Optional[dict] = None) -> dict:
-    """The model configuration of a FLUX transformer GGUF, inferred from its shapes (a BFL file has no config.json): in_channels, out_channels,
-    pooled_projection_dim, joint_attention_dim, num_attention_heads (D / 128), num_layers, num_single_layers, guidance_embeds; the RoPE constants are
-    FLUX.1's.  base_config: a transformer/config.json the result must agree with, field by field, else a ValueError names the field."""
+def gguf_flux_entries(gguf: "GgufFile"):
+    """flux_entries_from_shapes of a FLUX transformer GGUF, with each tensor's ggml type: [(diffusers name, ggml_type, shape, source tensor, row ranges)], and
+    the source names that are no part of the transformer."""
+    entries, skipped = flux_entries_from_shapes({n: gguf.tensors[n][1] for n in gguf.names()}, gguf.path)
+    return [(dname, gguf.tensors[src][0], shape, src, ranges) for dname, shape, src, ranges in entries], skipped
+
+
+def flux_config_from_shapes(shapes: Dict[str, tuple], where: str, base_config: Optional[dict] = None) -> dict:
+    """The model configuration of a FLUX transformer from the shapes of its tensors under their diffusers names (a BFL file has no config.json): in_channels,
+    out_channels, pooled_projection_dim, joint_attention_dim, num_attention_heads (D / 128), num_layers, num_single_layers, guidance_embeds; the RoPE constants
+    are FLUX.1's.  base_config: a transformer/config.json the result must agree with, field by field, else a ValueError names the field."""
     from . import flux as F
-    entries, _ = gguf_flux_entries(gguf)
-    shapes = {n: s for n, _, s, _, _ in entries}
 
     def need(name):
         if name not in shapes:
-            raise ValueError(f"{gguf.path}: no {name}: cannot infer the FLUX configuration")
+            raise ValueError(f"{where}: no {name}: cannot infer the FLUX configuration")
         return shapes[name]
 
     D, cin = need("x_embedder.weight")
     if D % 128:
-        raise ValueError(f"{gguf.path}: hidden size {D} is not a multiple of the 128-wide attention head")
+        raise ValueError(f"{where}: hidden size {D} is not a multiple of the 128-wide attention head")
 
     def count(prefix):
         idx = {int(n[len(prefix):].split(".", 1)[0]) for n in shapes if n.startswith(prefix)}
@@ -865,8 +875,14 @@ def flux_config_from_gguf(gguf: "GgufFile", base_config: Optional[dict] = None) 
             if k == "out_channels" and have is None:
                 have = base_config.get("in_channels", cfg["in_channels"])
             if type(cfg[k])(have) != cfg[k]:
-                raise ValueError(f"{gguf.path}: {k} = {cfg[k]} by the file's shapes, transformer/config.json says {base_config[k]}")
+                raise ValueError(f"{where}: {k} = {cfg[k]} by the file's shapes, transformer/config.json says {base_config[k]}")
     return cfg
+
+
+def flux_config_from_gguf(gguf: "GgufFile", base_config: Optional[dict] = None) -> dict:
+    """flux_config_from_shapes of a FLUX transformer GGUF."""
+    entries, _ = gguf_flux_entries(gguf)
+    return flux_config_from_shapes({n: s for n, _, s, _, _ in entries}, gguf.path, base_config)
 
 
 def _gguf_rows(view, row_bytes: int, ranges) -> np.ndarray:
@@ -915,5 +931,110 @@ def load_flux_gguf(flux, gguf) -> dict:
             flux.set_linear_gguf(dname[:-len(".weight")], ggml_type, _gguf_rows(gguf.data(src), shape[1] // be * bb, ranges), shape[0], shape[1])
             stats["gguf"] += 1
         stats["types"][tname] = stats["types"].get(tname, 0) + 1
+    flux.assert_complete()
+    return stats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Single-file FLUX checkpoints: one .safetensors file in BFL's tensor naming (flux1-dev.safetensors, community fine-tunes) or diffusers',
+# with or without `model.diffusion_model.`, in F32 / F16 / BF16 or as 8-bit floats (flux1-dev-fp8.safetensors, *_fp8_e4m3fn, *_fp8_e5m2: the safetensors
+# dtypes F8_E4M3 / F8_E5M2).  An fp8 Linear stays resident as codes and is expanded on the device (csrc/f8_dequant.hip).
+_ST_F8 = {torch.float8_e4m3fn: "e4m3", torch.float8_e5m2: "e5m2"}
+# what an all-in-one file carries next to the transformer: the VAE and the text encoders keep coming from the base directory
+SINGLE_FILE_OTHER_COMPONENTS = ("vae.", "first_stage_model.", "text_encoders.", "cond_stage_model.")
+
+
+class SingleFile:
+    """mmap view of one .safetensors file: `tensors` {name: zero-copy torch tensor} (float8 dtypes included), `path`."""
+
+    def __init__(self, path: str):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: not a file (a single-file checkpoint is one .safetensors file)")
+        self.path = path
+        with open(path, "rb") as f:
+            self._mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        self.tensors = dict(_safetensors_from_buffer(memoryview(self._mm)))
+
+
+def single_file_flux_entries(sf: "SingleFile"):
+    """The transformer's tensors of a single-file checkpoint under their diffusers names: ([(diffusers name, shape, source tensor, row ranges)], {source weight
+    name: scale_weight tensor name}, skipped source names).  Skipped: the other components of an all-in-one file (SINGLE_FILE_OTHER_COMPONENTS), the
+    `scaled_fp8` marker and every `<linear>.scale_input` of a "scaled fp8" file (activation scales belong to another runtime's fp8 matmul), and whatever else
+    is no transformer tensor.  `<linear>.scale_weight` is the scale of `<linear>.weight`."""
+    shapes, scales, skipped = {}, {}, []
+    for name, t in sf.tensors.items():
+        if name.startswith(SINGLE_FILE_OTHER_COMPONENTS):
+            skipped.append(name)
+        elif name.endswith(".scale_input") or name == "scaled_fp8" or name.endswith(".scaled_fp8"):
+            skipped.append(name)
+        elif name.endswith(".scale_weight"):
+            scales[name[:-len(".scale_weight")] + ".weight"] = name
+        else:
+            shapes[name] = tuple(t.shape)
+    entries, more = flux_entries_from_shapes(shapes, sf.path)
+    for wname, sname in scales.items():
+        if wname not in shapes:
+            more.append(sname)
+    return entries, scales, skipped + more
+
+
+def flux_config_from_single_file(path, base_config: Optional[dict] = None) -> dict:
+    """flux_config_from_shapes of a single-file checkpoint (a path or a SingleFile)."""
+    sf = path if isinstance(path, SingleFile) else SingleFile(path)
+    entries, _, _ = single_file_flux_entries(sf)
+    return flux_config_from_shapes({n: s for n, s, _, _ in entries}, sf.path, base_config)
+
+
+def _single_file_scale(sf: "SingleFile", sname: str) -> float:
+    t = sf.tensors[sname]
+    if t.dtype != torch.float32 or tuple(t.shape) not in ((), (1,)):
+        raise ValueError(f"{sf.path}: {sname} is {str(t.dtype).replace('torch.', '')} {tuple(t.shape)}: a scale_weight must be one F32 element, of shape () or (1,) "
+                         f"(per-row and block scales are not supported)")
+    v = float(t.reshape(-1)[0])
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"{sf.path}: {sname} = {v}: a scale_weight must be finite and > 0")
+    return v
+
+
+def load_flux_single_file(flux, path, expand: bool = False) -> dict:
+    """Feed a FluxModel from a single-file checkpoint (a path or a SingleFile).  F32 / F16 / BF16 tensors go through set_tensor; fp8 2-D `.weight` tensors through
+    set_linear_f8 with their `scale_weight` (1 without one) — the row splits of the BFL naming and the exchange of the final layer's halves are done on the rows
+    of the stored bytes —; fp8 tensors of any other rank (biases, norm scales) are widened on the host, exactly, and go through set_tensor.  expand=True: every
+    fp8 Linear is dequantised at load by the same kernel into its plain bf16 slot, and the model is an ordinary bf16 model (LoRA, get_tensor, the 8-bit modes and
+    state_export work).  Returns load_flux's stats plus "f8" (Linears fed as codes or expanded from them) and "formats" ({"e4m3" | "e5m2": Linears})."""
+    from . import flux as F
+    sf = path if isinstance(path, SingleFile) else SingleFile(path)
+    want = synth.flux_tensor_shapes(flux.cfg)
+    entries, scales, skipped = single_file_flux_entries(sf)
+    stats = {"dense": 0, "bnb4": 0, "int8": 0, "f8": 0, "formats": {}, "skipped": list(skipped)}
+    for dname, shape, src, ranges in entries:
+        if dname not in want:
+            stats["skipped"].append(src)
+            continue
+        if tuple(shape) != tuple(want[dname]):
+            raise ValueError(f"{sf.path}: {src} -> {dname} is {tuple(shape)}, the configuration says {tuple(want[dname])}")
+        t = sf.tensors[src]
+        fmt = _ST_F8.get(t.dtype)
+        if src in scales and not (fmt and len(shape) == 2 and dname.endswith(".weight")):
+            raise ValueError(f"{sf.path}: {scales[src]} belongs to {src}, which is no 2-D fp8 weight ({str(t.dtype).replace('torch.', '')} {tuple(t.shape)})")
+        if fmt and len(shape) == 2 and dname.endswith(".weight"):
+            scale = _single_file_scale(sf, scales[src]) if src in scales else 1.0
+            codes = _gguf_rows(t.view(torch.uint8).numpy().reshape(-1), shape[1], ranges)
+            if expand:
+                dev = torch.from_numpy(np.ascontiguousarray(codes)).to(flux.device)
+                flux.set_tensor(dname, F.f8_dequantize(dev, fmt, scale).reshape(shape))
+            else:
+                flux.set_linear_f8(dname[:-len(".weight")], fmt, codes, scale, shape[0], shape[1])
+            stats["f8"] += 1
+            stats["formats"][fmt] = stats["formats"].get(fmt, 0) + 1
+            continue
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16) and not fmt:
+            raise ValueError(f"{sf.path}: {src}: dtype {str(t.dtype).replace('torch.', '')} is not a transformer tensor's (F32, F16, BF16, F8_E4M3, F8_E5M2)")
+        if fmt:
+            t = t.to(torch.float32)  # (exact: every code is an f32 value)
+        if len(ranges) != 1 or ranges[0] != (0, t.shape[0]):
+            t = torch.cat([t[r0:r1] for r0, r1 in ranges])
+        flux.set_tensor(dname, t)
+        stats["dense"] += 1
     flux.assert_complete()
     return stats

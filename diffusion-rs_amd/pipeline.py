@@ -75,6 +75,17 @@ class ModelSource:
         ends in .gguf is the same."""
         return self.override_transformer_model_id(file)
 
+    def override_transformer_file(self, file: str, expand: bool = False) -> "ModelSource":
+        """The transformer from a single .safetensors file (BFL or diffusers tensor naming, with or without `model.diffusion_model.`; F32 / F16 / BF16 or the 8-bit
+        float dtypes F8_E4M3 / F8_E5M2, plain or "scaled"); model_index.json, the scheduler, the VAE, the text encoders and the tokenizers
+        still come from this source's directory — also when the file is an all-in-one that carries its own.  fp8 Linears stay resident as codes; expand=True
+        dequantises them at load into an ordinary bf16 model (LoRA, the 8-bit modes).  override_transformer_model_id with a path that ends in .safetensors
+        is the same as expand=False."""
+        src = self.override_transformer_model_id(file)
+        if expand:
+            src.transformer_expand = True
+        return src
+
     @staticmethod
     def DdufFile(file: str) -> "ModelSource":
         return ModelSource("dduf", file=file)
@@ -447,7 +458,8 @@ class Pipeline:
                     self.clip = text.ClipTextTransformer(source.clip_cfg, device)
                     synth.fill_text_random_device(self.clip, seed=source.seed + 3, device=self.device)
             elif source.kind == "model_id":
-                self._load_checkpoint(source.model_id, getattr(source, "transformer_model_id", None), load_dit=(rank == 0))
+                self._load_checkpoint(source.model_id, getattr(source, "transformer_model_id", None), load_dit=(rank == 0),
+                                      transformer_expand=bool(getattr(source, "transformer_expand", False)))
             else:
                 self._load_checkpoint(source.file, None, load_dit=(rank == 0))
         except Exception as e:  # a rank that fails here must not leave the others blocked in the broadcast below
@@ -477,7 +489,7 @@ class Pipeline:
     # Pipeline::load (pipelines/mod.rs:120-236) for a local diffusers directory or a DDUF file:
     # model_index.json -> FluxPipeline only; scheduler / transformer / vae components, plus text_encoder (CLIP),
     # text_encoder_2 (T5) and their tokenizers when the checkpoint ships them (flux/mod.rs:74-127).
-    def _load_checkpoint(self, path: str, transformer_path: Optional[str], load_dit: bool = True):
+    def _load_checkpoint(self, path: str, transformer_path: Optional[str], load_dit: bool = True, transformer_expand: bool = False):
         from . import loader
         fl = loader.FileLoader(path)
         class_name = fl.read_json("model_index.json").get("_class_name")
@@ -491,6 +503,11 @@ class Pipeline:
             gg = loader.GgufFile(transformer_path)
             fcfg = loader.flux_config_from_gguf(gg, fl.read_json("transformer/config.json") if fl.has("transformer/config.json") else None)
             self._dit_loader = lambda: self.load_stats.update(loader.load_flux_gguf(self.flux, gg))
+        elif transformer_path and transformer_path.lower().endswith(".safetensors"):
+            # a single-file transformer, fp8 or not: the configuration comes from the file's shapes, as for GGUF
+            sf = loader.SingleFile(transformer_path)
+            fcfg = loader.flux_config_from_single_file(sf, fl.read_json("transformer/config.json") if fl.has("transformer/config.json") else None)
+            self._dit_loader = lambda: self.load_stats.update(loader.load_flux_single_file(self.flux, sf, expand=transformer_expand))
         else:
             tl = loader.FileLoader(transformer_path) if transformer_path else fl  # ModelIdWithTransformer (model_source.rs:22-25)
             tc = tl.read_json("transformer/config.json")

@@ -55,6 +55,7 @@ extern "C" {
  *   Then, still 6: FLUX IP-Adapters (image prompts) — fmi_ip_adapter_*, fmi_flux_ip, fmi_flux_forward_ip, fmi_flux_denoise_ip, fmi_ip_attention.
  *   Then, still 6: the CLIP vision encoder (an image prompt from a picture) — fmi_resize_bicubic_u8, fmi_clip_preprocess_u8, fmi_clip_vision_*.
  *   Then, still 6: FLUX.1 Redux (image variation: a SigLIP vision tower and the Redux embedder) — fmi_siglip_vision_*, fmi_redux_*.
+ *   Then, still 6: single-file fp8 checkpoints (OCP e4m3fn / e5m2 weights resident as codes) — fmi_f8_dequantize, fmi_flux_set_linear_f8.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -203,6 +204,38 @@ int fmi_gguf_dequantize(int ggml_type, const void* blocks, int64_t n_elems, void
  * expansion past 2^31 weights is checked at the op level on a periodic input, none inside the model (the modulation matrix arrives as 77 Linears of at
  * most 5.7e7 weights each). */
 int fmi_flux_set_linear_gguf(fmi_flux*, const char* prefix, int ggml_type, const void* data, int out_features, int in_features);
+
+/* 8-bit float weights (single-file .safetensors checkpoints whose tensors carry the dtypes F8_E4M3 / F8_E5M2).  format: 1 = OCP e4m3fn (no
+ * infinities; 0x7f / 0xff are NaN; largest finite value 448), 2 = OCP e5m2 (IEEE-like; largest finite value 57344).
+ * n_elems codes of `codes` (DEVICE pointer, ANY byte alignment) -> out (DEVICE pointer aligned to its element size, BF16 or F32).  The semantics are
+ * this library's own decision:
+ *   y = f32(code)            exact: every code of either format is an f32 value
+ *   y = y * scale            ONE f32 multiply, rounded to nearest even (__fmul_rn)
+ *   BF16 output: then ONE RNE rounding to bf16
+ * so scale == 1.0f gives the code's value exactly, and the result is bit-equal to (codes as torch.float8_*).float() * scale [.to(bfloat16)] for every
+ * non-NaN code.  A NaN code gives a NaN of unspecified payload; e5m2's infinities stay infinities.  Results that are bf16 / f32 subnormals are outside
+ * the contract (keep scale within [2^-40, 2^40]).  FMI_ERR_INVALID: another format, another out_dtype, scale not finite or not > 0, n_elems < 0, a null
+ * pointer with n_elems > 0, out not aligned to its element size — all refused before any launch.  n_elems == 0 returns 0.  Indexes in 64 bits. */
+int fmi_f8_dequantize(int format, const void* codes, int64_t n_elems, float scale, void* out, fmi_dtype out_dtype, void* stream);
+/* A Linear given as 8-bit float codes: row-major (out_features, in_features), one code per weight, and ONE scale for the Linear (1.0f for a plain
+ * cast; a "scaled fp8" file's scale_weight): its values are those of fmi_f8_dequantize.  Host or device pointer.  Same prefix rules and refusals as
+ * fmi_flux_set_linear_gguf (unknown prefix, shape mismatch, another format, scale not finite or not > 0: INVALID; a ControlNet handle: UNSUPPORTED; a
+ * model in an 8-bit mode, a weight with LoRA adapters merged: STATE).
+ *   - embedders and the final layer are expanded into their bf16 slot at load;
+ *   - modulation linears (norm1.linear, norm1_context.linear, norm.linear, norm_out.linear) are expanded at load into the fused modulation matrix,
+ *     in every mode, as for GGUF: an fp8 FLUX.1-dev holds the codes of the block linears (11.9 GB) PLUS 6.5 GB of dense modulation weights;
+ *   - parts of a fused block matrix keep their codes resident, in storage the matrix owns, each part with its own scale.  If all parts of a matrix
+ *     have the same format, only the codes are resident (the parts' scales may differ: the expansion runs per part); a mixture — e4m3 with e5m2, or
+ *     fp8 with dense, GGUF or bitsandbytes parts — is expanded into the dense arena once.
+ * There is no fused dequant-GEMM for these codes (feeding them to the e4m3 GEMM mode is another recipe with other values): at EVERY row count the
+ * matrix is expanded, once into its dense slot or per call into the scratch, as fmi_flux_set_quant_dense_cache says: -1 by free memory, 0 per call,
+ * 1 and 3 once, 2 per call as 0.  Every mode computes the bits of a bf16 model loaded with the dequantised weights.  fmi_flux_get_tensor and
+ * fmi_flux_lora_add on a Linear resident as codes, fmi_flux_quantize_fp8 / _int8 / fmi_flux_calibrate_int8 and fmi_flux_state_export on such a model
+ * return FMI_ERR_UNSUPPORTED, as for GGUF.  fmi_flux_size_in_bytes counts the codes.
+ * Not verified: no fp8 checkpoint written by another program was available — the "scaled fp8" naming (scale_weight, scale_input, scaled_fp8) is
+ * ComfyUI's as remembered; the FLUX.1-dev-size model was run and timed on generated codes, its values were checked at the small test configuration
+ * only. */
+int fmi_flux_set_linear_f8(fmi_flux*, const char* prefix, int format, const void* codes, float scale, int out_features, int in_features);
 
 /* Read back the CURRENT value of any tensor fmi_flux_set_tensor accepts (same names, same shapes; `shape` / `rank` are checked): the row range of
  * the fused matrix it lives in, bf16 converted exactly to `dtype` F32 or BF16.  `out` may be a host or device pointer.  Synchronises the device.

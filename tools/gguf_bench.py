@@ -73,7 +73,8 @@ def part_dequant():
         print(f"{name:<26}{nb:>12}{med:>10.1f}{lo:>9.1f}{hi:>9.1f}{bw:>18.0f}{bw / base:>9.2f}")
 
 
-def part_model(quant):
+def part_model(quant, feed=None):
+    """feed(model, name, w) -> bool: another way to load a weight (tools/single_file_bench.py); True = it took the tensor"""
     import torch
     import diffusion_rs_amd as d
     from diffusion_rs_amd import synth
@@ -90,7 +91,9 @@ def part_model(quant):
         else:
             w = torch.randn(shape, generator=g, device=dev, dtype=torch.bfloat16)
             w.mul_(synth._std_for(name, 0.02, 0.01))
-        if t is not None and len(shape) == 2 and shape[1] % 256 == 0:  # what a GGUF file quantises: every 2-D weight whose rows are whole blocks
+        if feed is not None and feed(model, name, w):
+            pass
+        elif t is not None and len(shape) == 2 and shape[1] % 256 == 0:  # what a GGUF file quantises: every 2-D weight whose rows are whole blocks
             model.set_linear_gguf(name[:-len(".weight")], t, synth.quantize_gguf_device(w, t), shape[0], shape[1])
         else:
             model.set_tensor(name, w)
@@ -109,7 +112,7 @@ def part_model(quant):
     txt_ids = torch.zeros((1, T, 3), dtype=torch.float32, device=dev)
     img, img_ids = d.pack_latents(d.randn_latents(1, 16, h, w_, seed=1234, device=dev))
     loaded = model.size_in_bytes()
-    for mode in ((0, 3) if t is not None else (-1,)):  # (0 first: its resident bytes are then the packed-only figure)
+    for mode in ((0, 3) if t is not None or feed is not None else (-1,)):  # (0 first: its resident bytes are then the packed-only figure)
         model.set_quant_dense_cache(mode)
         run = lambda: model.denoise(img.clone(), img_ids, txt, txt_ids, y, guidance, ts)  # noqa: E731
         med, lo, hi = event_median_us(torch, run, warm=2, reps=7, inner=1)
