@@ -1,12 +1,14 @@
-// encoder_common.h — what the encoders in front of the denoise loop share (text_encoders.hip: T5 and the CLIP text tower; clip_vision.hip: the CLIP
-// vision tower): the single-pass kernels of a pre-norm transformer layer on an f32 residual stream, the d = 64 lane-per-key attention, the named-tensor
-// registry over one bf16 weight arena, the grow-only workspace, and the CLIP encoder layer both CLIP towers run.  Everything is file-local to the
-// translation unit that includes it (anonymous namespace): the encoders run once per request, their kernels are small.
+// encoder_common.h — what the encoders in front of the denoise loop share (text_encoders.hip: T5 and the CLIP text tower; vision_encoders.hip: the CLIP and
+// SigLIP vision towers and the Redux embedder): the single-pass kernels of a pre-norm transformer layer on an f32 residual stream, the d = 64 lane-per-key
+// attention, the handle frame (the named-tensor registry over one bf16 weight arena, the grow-only workspace and its carving, the arena's creation and the
+// entry points every handle has), and the encoder layer that the CLIP towers and the SigLIP tower run.  Everything is file-local to the translation unit that
+// includes it (anonymous namespace): the encoders run once per request, their kernels are small.
 #pragma once
 #include <math.h>
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <vector>
@@ -140,6 +142,11 @@ struct Registry {
   size_t bytes = 0, used = 0;  // bytes: the layout size (known before the arena exists)
   std::map<std::string, Dest> names;
   MissingSet missing;
+  void begin_layout() {  // a layout pass starts from nothing: no bytes taken, no names
+    used = 0;
+    names.clear();
+    missing.names.clear();
+  }
   bf16_t* take(size_t count) {
     const size_t off = align_up(used, 256);
     used = off + count * sizeof(bf16_t);
@@ -201,13 +208,55 @@ struct Registry {
 
 struct Workspace {
   DeviceBuffer base;
-  int B = 0, T = 0;
   int reserve(size_t need) {  // grow-only
     if (need <= base.bytes()) return FMI_OK;
     FMI_HIP_TRY(base.alloc(need));
     return FMI_OK;
   }
+  template <class T>
+  T* at(size_t off) const {  // the region a Carve put at byte `off`
+    return reinterpret_cast<T*>(base.as<char>() + off);
+  }
 };
+// Lays regions out in a workspace, in call order: k(bytes) is the region's offset, every region starts on a multiple of 256, k.total is what to reserve
+struct Carve {
+  size_t total = 0;
+  size_t operator()(size_t bytes) {
+    const size_t o = total;
+    total = align_up(total + bytes, 256);
+    return o;
+  }
+};
+
+// ------------------------------------------------------------------------------ the handle frame
+// What every encoder handle (fmi_t5, fmi_clip, fmi_clip_vision, fmi_siglip_vision, fmi_redux) is: a device, named weights in one arena, a workspace.  The
+// handle's own struct adds its configuration and its pointers into the arena; its C entry points forward here with their own name as `who`.
+struct EncoderHandle {
+  int device = current_device();
+  Registry r;
+  Workspace ws;
+};
+// The arena of a new handle.  layout(m) takes and registers every tensor: pass 0 runs it without an arena and only sizes, pass 1 hands out the pointers.
+// zero: the arena starts as zeros (a layout with pads that no tensor writes).
+template <class M>
+int create_arena(const char* who, M* m, void (*layout)(M*), bool zero) {
+  Registry& r = m->r;
+  r.begin_layout(), layout(m);
+  r.bytes = align_up(r.used, 256);
+  hipError_t e = r.arena.alloc(r.bytes);
+  if (e == hipSuccess && zero) e = hipMemset(r.arena.ptr, 0, r.bytes);
+  if (e != hipSuccess) return fail(FMI_ERR_HIP, std::string(who) + ": hipMalloc of the weight arena: " + hipGetErrorString(e));
+  r.begin_layout(), layout(m);
+  return FMI_OK;
+}
+int enc_set_tensor(EncoderHandle* m, const char* who, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
+  if (!m) return fail(FMI_ERR_INVALID, std::string(who) + ": null model");
+  FMI_TRY(use_device_ordinal(m->device));
+  return m->r.set(who, name, data, dtype, shape, rank);
+}
+int enc_missing_count(const EncoderHandle* m) { return m ? m->r.missing.count() : 0; }
+const char* enc_missing_name(const EncoderHandle* m, int i) { return m ? m->r.missing.name(i) : nullptr; }
+size_t enc_size_in_bytes(const EncoderHandle* m) { return m ? m->r.bytes + m->ws.base.bytes() : 0; }
 
 GemmProblem lin(const bf16_t* A, int lda, const bf16_t* W, const bf16_t* bias, void* out, int ldo, int M, int N, int K, int epi) {
   GemmProblem p{};
@@ -235,137 +284,75 @@ int write_out(const float* src_f32, const bf16_t* src_bf, void* out, fmi_dtype d
   return fail(FMI_ERR_INVALID, "text encoder output dtype must be F32 or BF16");
 }
 
-// ------------------------------------------------------------------- the CLIP encoder layer (both towers)
-// ClipEncoderLayer (clip/text.rs:228-238; HF's CLIPEncoderLayer is the same for the vision tower): LayerNorm -> fused q|k|v -> attention at head dim 64 ->
-// out_proj into the f32 stream -> LayerNorm -> fc1 -> quick-GELU -> fc2 into the stream.
-struct ClipLayer {
+// ------------------------------------------------------------------- the encoder layer of the CLIP towers and the SigLIP tower
+// ClipEncoderLayer (clip/text.rs:228-238; HF's CLIPEncoderLayer and SiglipEncoderLayer are the same layer): LayerNorm(eps) -> fused q|k|v -> attention ->
+// out_proj into the f32 stream -> LayerNorm -> fc1 -> activation -> fc2 into the stream.  What differs between the towers is data: eps, the activation
+// (quick-GELU for CLIP, tanh-GELU for SigLIP), the attention step, and the widths the GEMMs run at.  Head h's q / k / v rows sit at rows h * head_slot ..
+// h * head_slot + hd of a (3 H head_slot, D) operand and out_proj's K is (D, H head_slot).  The CLIP towers run encoder_common's d = 64 attention: head_slot
+// = hd = 64, nothing is padded.  The SigLIP tower runs the transformer's MFMA attention (d = 128) at hd = D / H <= 128: head_slot = 128, the heads are
+// zero-padded IN THE WEIGHTS, so the q|k|v GEMM writes 128-wide heads whose lanes [hd, 128) are exactly 0 (zero weight rows, zero bias), contribute 0 to every
+// score and meet zero out_proj columns.  F is padded to Fp = a multiple of 64 the same way: zero fc1 rows and bias, act(0) = 0, zero fc2 columns.
+struct EncLayer {
   bf16_t *l1w, *l1b, *qkv, *qkvb, *o, *ob, *l2w, *l2b, *f1, *f1b, *f2, *f2b;
 };
-// the layer's slots in the arena and its names under prefix p ("text_model.encoder.layers.3."), width D, MLP width F
-void clip_layer_layout(Registry& r, const std::string& p, int D, int F, ClipLayer& L) {
-  L.l1w = r.take(D), L.l1b = r.take(D);
-  r.reg(p + "layer_norm1.weight", L.l1w, D, 0), r.reg(p + "layer_norm1.bias", L.l1b, D, 0);
-  L.qkv = r.take((size_t)3 * D * D), L.qkvb = r.take((size_t)3 * D);
-  const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
-  for (int i = 0; i < 3; ++i) {
-    r.reg(p + "self_attn." + nm[i] + ".weight", L.qkv ? L.qkv + (size_t)i * D * D : nullptr, D, D);
-    r.reg(p + "self_attn." + nm[i] + ".bias", L.qkvb ? L.qkvb + (size_t)i * D : nullptr, D, 0);
-  }
-  L.o = r.take((size_t)D * D), L.ob = r.take(D);
-  r.reg(p + "self_attn.out_proj.weight", L.o, D, D), r.reg(p + "self_attn.out_proj.bias", L.ob, D, 0);
-  L.l2w = r.take(D), L.l2b = r.take(D);
-  r.reg(p + "layer_norm2.weight", L.l2w, D, 0), r.reg(p + "layer_norm2.bias", L.l2b, D, 0);
-  L.f1 = r.take((size_t)F * D), L.f1b = r.take(F);
-  r.reg(p + "mlp.fc1.weight", L.f1, F, D), r.reg(p + "mlp.fc1.bias", L.f1b, F, 0);
-  L.f2 = r.take((size_t)D * F), L.f2b = r.take(D);
-  r.reg(p + "mlp.fc2.weight", L.f2, D, F), r.reg(p + "mlp.fc2.bias", L.f2b, D, 0);
-}
-// the buffers a run of layers works in, rows = B * T: x (rows, D) f32 the stream (in / out), n (rows, D), qkv (rows, 3 D), a (rows, D), h and g (rows, F) bf16,
-// ones (D) f32 of 1.0 (the residual epilogue's gate)
-struct ClipLayerBuffers {
-  float* x;
-  bf16_t *n, *qkv, *a, *h, *g;
-  const float* ones;
-};
-int clip_layers(const std::vector<ClipLayer>& layers, const ClipLayerBuffers& w, int B, int T, int D, int H, int F, int causal, hipStream_t s) {
-  const int rows = B * T, nb = (rows + 3) / 4;
-  const float scale = 1.0f / sqrtf(64.0f);  // (head_dim)^-0.5, clip/text.rs:101
-  for (const ClipLayer& L : layers) {
-    hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l1w, L.l1b, 1e-5f, rows, D, w.n, (float*)nullptr);
-    GemmProblem p = lin(w.n, D, L.qkv, L.qkvb, w.qkv, 3 * D, rows, 3 * D, D, EPI_STORE_BF16);
-    FMI_TRY(launch_gemm(&p, 1, s));
-    FMI_TRY(enc_attention(w.qkv, nullptr, B, T, H, scale, causal, w.a, s));  // text: causal mask (:273-291); q * scale (:130)
-    p = lin(w.a, D, L.o, L.ob, w.x, D, rows, D, D, EPI_RESID_GATE_F32);
-    p.gate = w.ones;
-    FMI_TRY(launch_gemm(&p, 1, s));
-    hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l2w, L.l2b, 1e-5f, rows, D, w.n, (float*)nullptr);
-    p = lin(w.n, D, L.f1, L.f1b, w.h, F, rows, F, D, EPI_STORE_BF16);
-    FMI_TRY(launch_gemm(&p, 1, s));
-    hipLaunchKernelGGL(enc_act_kernel, dim3(256), dim3(256), 0, s, w.h, rows, F, 3, 0, w.g);  // QuickGelu (:13-19)
-    p = lin(w.g, F, L.f2, L.f2b, w.x, D, rows, D, F, EPI_RESID_GATE_F32);
-    p.gate = w.ones;
-    FMI_TRY(launch_gemm(&p, 1, s));
-  }
-  return FMI_OK;
-}
-
-// ------------------------------------------------------------------- the SigLIP encoder layer (siglip_vision.hip)
-// HF's SiglipEncoderLayer: LayerNorm(eps) -> fused q|k|v -> attention at head dim hd = D / H on the transformer's MFMA attention (d = 128) -> out_proj into
-// the f32 stream -> LayerNorm -> fc1 -> tanh-GELU -> fc2 into the stream.  The heads are zero-padded to 128 IN THE WEIGHTS: head h's q / k / v rows sit at rows
-// h * 128 .. h * 128 + hd of a (3 H 128, D) operand, out_proj's K is (D, H 128) with zero pad columns, so the q|k|v GEMM writes 128-wide heads whose lanes
-// [hd, 128) are exactly 0 (zero weight rows, zero bias) and contribute 0 to every score and meet zero out_proj columns.  F is padded to Fp = a multiple of 64 the
-// same way: zero fc1 rows and bias, gelu(0) = 0, zero fc2 columns.
-struct SiglipLayer {
-  bf16_t *l1w, *l1b, *qkv, *qkvb, *o, *ob, *l2w, *l2b, *f1, *f1b, *f2, *f2b;
-};
-// the layer's slots and names under prefix p; the arena must be zero before the tensors arrive (the fc1 pad rows and every bias pad are never written)
-void siglip_layer_layout(Registry& r, const std::string& p, int D, int H, int F, SiglipLayer& L) {
-  const int hd = D / H, HP = H * 128, Fp = (int)align_up(F, 64);
+// the layer's slots in the arena and its names under prefix p ("text_model.encoder.layers.3."), width D, H heads in slots of head_slot, MLP width F.  Where
+// there are pads (head_slot > D / H, or F no multiple of 64) the arena must be zero before the tensors arrive: the fc1 pad rows and every bias pad are never
+// written.  (A tensor whose pieces fill their slots — every one of CLIP's — is stored as it arrives.)
+EncLayer enc_layer_layout(Registry& r, const std::string& p, int D, int H, int F, int head_slot) {
+  const int hd = D / H, HP = H * head_slot, Fp = (int)align_up(F, 64);
+  EncLayer L;
   L.l1w = r.take(D), L.l1b = r.take(D);
   r.reg(p + "layer_norm1.weight", L.l1w, D, 0), r.reg(p + "layer_norm1.bias", L.l1b, D, 0);
   L.qkv = r.take((size_t)3 * HP * D), L.qkvb = r.take((size_t)3 * HP);
   const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
   for (int i = 0; i < 3; ++i) {
-    r.reg_chunks(p + "self_attn." + nm[i] + ".weight", L.qkv ? L.qkv + (size_t)i * HP * D : nullptr, D, D, H, hd * D, 128 * D);
-    r.reg_chunks(p + "self_attn." + nm[i] + ".bias", L.qkvb ? L.qkvb + (size_t)i * HP : nullptr, D, 0, H, hd, 128);
+    r.reg_chunks(p + "self_attn." + nm[i] + ".weight", L.qkv ? L.qkv + (size_t)i * HP * D : nullptr, D, D, H, hd * D, head_slot * D);
+    r.reg_chunks(p + "self_attn." + nm[i] + ".bias", L.qkvb ? L.qkvb + (size_t)i * HP : nullptr, D, 0, H, hd, head_slot);
   }
   L.o = r.take((size_t)D * HP), L.ob = r.take(D);
-  r.reg_chunks(p + "self_attn.out_proj.weight", L.o, D, D, D * H, hd, 128), r.reg(p + "self_attn.out_proj.bias", L.ob, D, 0);
+  r.reg_chunks(p + "self_attn.out_proj.weight", L.o, D, D, D * H, hd, head_slot), r.reg(p + "self_attn.out_proj.bias", L.ob, D, 0);
   L.l2w = r.take(D), L.l2b = r.take(D);
   r.reg(p + "layer_norm2.weight", L.l2w, D, 0), r.reg(p + "layer_norm2.bias", L.l2b, D, 0);
   L.f1 = r.take((size_t)Fp * D), L.f1b = r.take(Fp);  // (the rows [F, Fp) stay zero)
   r.reg(p + "mlp.fc1.weight", L.f1, F, D), r.reg(p + "mlp.fc1.bias", L.f1b, F, 0);
   L.f2 = r.take((size_t)D * Fp), L.f2b = r.take(D);
   r.reg_chunks(p + "mlp.fc2.weight", L.f2, D, F, D, F, Fp), r.reg(p + "mlp.fc2.bias", L.f2b, D, 0);
+  return L;
 }
-
-// q and k of token-major q|k|v rows (rows = B * T, 3 HP columns, head h at columns h * 128 of each third) -> head-major (B, H, T, 128): what the attention
-// reads.  One 16-byte load and store per 8 elements, each read once; v stays where it is (launch_v_transpose reads it in place).
-__global__ __launch_bounds__(256) void qk_head_major_kernel(const bf16_t* __restrict__ qkv, int T, int H, bf16_t* __restrict__ qh, bf16_t* __restrict__ kh, int64_t n16) {
-  const int hp8 = H * 16;  // 16-byte pieces per row of one third
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n16; i += (int64_t)gridDim.x * blockDim.x) {
-    const int part = i >= n16;
-    const int64_t j = i - part * n16, row = j / hp8;
-    const int c8 = (int)(j - row * hp8), h = c8 >> 4, c = c8 & 15;
-    const int64_t b = row / T, t = row - b * T;
-    const uint4 v = *reinterpret_cast<const uint4*>(qkv + (row * 3 + part) * (int64_t)(hp8 * 8) + c8 * 8);
-    *reinterpret_cast<uint4*>((part ? kh : qh) + (((b * H + h) * T + t) * 128 + c * 8)) = v;
-  }
-}
-
-// the buffers a run of SigLIP layers works in, rows = B * T, HP = H * 128, Fp = F rounded up to 64, Lp = T rounded up to 64: x (rows, D) f32 the stream (in /
-// out), n (rows, D), qkv (rows, 3 HP), qh and kh (B, H, T, 128), vt (B, H, 128, Lp) with its tail [T, Lp) ZERO (launch_vt_zero_pad, once: the transposes never
-// write there), a (rows, HP), h and g (rows, Fp) bf16, ones (D) f32 of 1.0
-struct SiglipLayerBuffers {
+// the buffers a run of layers works in, HP = H * head_slot, Fp = F rounded up to 64: x (rows, D) f32 the stream (in / out), n (rows, D), qkv (rows, 3 HP),
+// a (rows, HP), h and g (rows, Fp) bf16, ones (D) f32 of 1.0 (the residual epilogue's gate)
+struct EncLayerBuffers {
   float* x;
-  bf16_t *n, *qkv, *qh, *kh, *vt, *a, *h, *g;
+  bf16_t *n, *qkv, *a, *h, *g;
   const float* ones;
 };
-int siglip_layers(const std::vector<SiglipLayer>& layers, const SiglipLayerBuffers& w, int B, int T, int D, int H, int F, float eps, hipStream_t s) {
-  const int rows = B * T, nb = (rows + 3) / 4, HP = H * 128, Fp = (int)align_up(F, 64), Lp = (int)align_up(T, 64);
-  const float scale = 1.0f / sqrtf((float)(D / H));  // head_dim^-0.5 of the real head, not of the padded one
-  const int64_t n16 = (int64_t)rows * H * 16;
-  const dim3 flat((unsigned)std::min<int64_t>(cdiv64(2 * n16, 256), 4096));
-  for (const SiglipLayer& L : layers) {
+// act: enc_act_kernel's code.  attention(qkv, out): the tower's attention step, token-major q|k|v rows (rows, 3 HP) -> (rows, HP)
+template <class Attention>
+int enc_layers(const std::vector<EncLayer>& layers, const EncLayerBuffers& w, int rows, int D, int HP, int Fp, float eps, int act, hipStream_t s, Attention attention) {
+  const int nb = (rows + 3) / 4;
+  for (const EncLayer& L : layers) {
     hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l1w, L.l1b, eps, rows, D, w.n, (float*)nullptr);
     GemmProblem p = lin(w.n, D, L.qkv, L.qkvb, w.qkv, 3 * HP, rows, 3 * HP, D, EPI_STORE_BF16);
     FMI_TRY(launch_gemm(&p, 1, s));
-    hipLaunchKernelGGL(qk_head_major_kernel, flat, dim3(256), 0, s, w.qkv, T, H, w.qh, w.kh, n16);
-    FMI_LAUNCH_CHECK();
-    FMI_TRY(launch_v_transpose(w.qkv + 2 * HP, 3 * HP, (int64_t)T * 3 * HP, w.vt, B, H, T, 0, Lp, s));
-    FMI_TRY(launch_attention(w.qh, w.kh, w.vt, w.a, B, H, T, T, Lp, scale, /*out_token_major=*/1, s));
+    FMI_TRY(attention(w.qkv, w.a));
     p = lin(w.a, HP, L.o, L.ob, w.x, D, rows, D, HP, EPI_RESID_GATE_F32);
     p.gate = w.ones;
     FMI_TRY(launch_gemm(&p, 1, s));
     hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, w.x, L.l2w, L.l2b, eps, rows, D, w.n, (float*)nullptr);
     p = lin(w.n, D, L.f1, L.f1b, w.h, Fp, rows, Fp, D, EPI_STORE_BF16);
     FMI_TRY(launch_gemm(&p, 1, s));
-    hipLaunchKernelGGL(enc_act_kernel, dim3(256), dim3(256), 0, s, w.h, rows, Fp, 1, 0, w.g);  // gelu_pytorch_tanh
+    hipLaunchKernelGGL(enc_act_kernel, dim3(256), dim3(256), 0, s, w.h, rows, Fp, act, 0, w.g);
     p = lin(w.g, Fp, L.f2, L.f2b, w.x, D, rows, D, Fp, EPI_RESID_GATE_F32);
     p.gate = w.ones;
     FMI_TRY(launch_gemm(&p, 1, s));
   }
   return FMI_OK;
+}
+// the CLIP towers' attention step (head dim 64, q * (head_dim)^-0.5, clip/text.rs:101,130; the text tower's causal mask, :273-291) and their other constants
+constexpr float CLIP_LN_EPS = 1e-5f;
+constexpr int ACT_QUICK_GELU = 3, ACT_GELU_TANH = 1;  // QuickGelu (clip/text.rs:13-19); gelu_pytorch_tanh
+auto clip_attention(int B, int T, int H, int causal, hipStream_t s) {
+  return [=](const bf16_t* qkv, bf16_t* out) { return enc_attention(qkv, nullptr, B, T, H, 1.0f / sqrtf(64.0f), causal, out, s); };
 }
 
 }  // namespace

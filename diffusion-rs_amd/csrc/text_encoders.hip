@@ -7,7 +7,7 @@
 // epilogue), norms / activations / embedding gathers are single-pass HBM kernels, and the d=64
 // attention (T5: additive relative-position bias, no 1/sqrt(d); CLIP: causal) is a small
 // lane-per-key kernel — L <= 512 keys, 64 heads: 0.1 TFLOP per prompt, not worth an MFMA pipeline.
-// What the CLIP vision tower (clip_vision.hip) runs as well — the layer kernels, the weight registry, the CLIP encoder layer — is in encoder_common.h.
+// What the vision towers (vision_encoders.hip) run as well — the layer kernels, the handle frame, the encoder layer — is in encoder_common.h.
 #include "encoder_common.h"
 
 namespace fmi {
@@ -90,11 +90,8 @@ int t5_bucket_of(int rel, int num_buckets_total, int max_distance) {
 using namespace fmi;
 
 // =============================================================================================== T5
-struct fmi_t5 {
+struct fmi_t5 : EncoderHandle {
   fmi_t5_config cfg;
-  int device = current_device();
-  Registry r;
-  Workspace ws;
   bf16_t *shared = nullptr, *rel = nullptr, *final_ln = nullptr;
   struct Layer {
     bf16_t *ln0, *qkv, *o, *ln1, *wi, *wo;
@@ -108,9 +105,6 @@ static void t5_layout(fmi_t5* m) {
   const int D = c.d_model, I = c.num_heads * c.d_kv, F = c.d_ff;
   const bool gated = c.feed_forward_act != FMI_T5_RELU;
   Registry& r = m->r;
-  r.used = 0;
-  r.names.clear();
-  r.missing.names.clear();
   m->shared = r.take((size_t)c.vocab_size * D);
   r.reg("shared.weight", m->shared, c.vocab_size, D);
   m->rel = r.take((size_t)c.relative_attention_num_buckets * c.num_heads);
@@ -158,26 +152,15 @@ extern "C" int fmi_t5_create(const fmi_t5_config* cfg, fmi_t5** out) {
     return fail(FMI_ERR_INVALID, "t5_create: d_model and d_ff must be positive multiples of 64");
   if (cfg->feed_forward_act < FMI_T5_RELU || cfg->feed_forward_act > FMI_T5_GATED_SILU) return fail(FMI_ERR_INVALID, "t5_create: bad feed_forward_act");
   if (cfg->relative_attention_num_buckets < 4 || cfg->relative_attention_max_distance < 2) return fail(FMI_ERR_INVALID, "t5_create: bad relative attention config");
-  fmi_t5* m = new fmi_t5();
+  std::unique_ptr<fmi_t5> m(new fmi_t5());
   m->cfg = *cfg;
-  t5_layout(m);  // pass 0: size
-  m->r.bytes = align_up(m->r.used, 256);
-  hipError_t e = m->r.arena.alloc(m->r.bytes);
-  if (e != hipSuccess) {
-    delete m;
-    return fail(FMI_ERR_HIP, std::string("t5_create: hipMalloc of the weight arena: ") + hipGetErrorString(e));
-  }
-  t5_layout(m);  // pass 1: pointers
-  *out = m;
+  FMI_TRY(create_arena("t5_create", m.get(), t5_layout, /*zero=*/false));
+  *out = m.release();
   return FMI_OK;
 }
-extern "C" void fmi_t5_destroy(fmi_t5* m) {
-  delete m;  // (the weight arena and the workspace are DeviceBuffers)
-}
+extern "C" void fmi_t5_destroy(fmi_t5* m) { delete m; }  // (the weight arena and the workspace are DeviceBuffers)
 extern "C" int fmi_t5_set_tensor(fmi_t5* m, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
-  if (m) FMI_TRY(use_device_ordinal(m->device));
-  if (!m) return fail(FMI_ERR_INVALID, "t5_set_tensor: null model");
-  return m->r.set("t5_set_tensor", name, data, dtype, shape, rank);
+  return enc_set_tensor(m, "t5_set_tensor", name, data, dtype, shape, rank);
 }
 // Quantised T5 Linears.  The reference builds every T5 Linear through `linear_no_bias(.., &cfg.quantization_config, ..)`
 // (t5/mod.rs:132-133,164-173,258-261) -> BnbLinear (bitsandbytes/mod.rs:111-239), whose forward is "dequantise W, then matmul"
@@ -232,9 +215,9 @@ extern "C" int fmi_t5_set_linear_int8(fmi_t5* m, const char* prefix, const int8_
   m->r.missing.erase(wname);
   return FMI_OK;
 }
-extern "C" int fmi_t5_missing_count(const fmi_t5* m) { return m ? m->r.missing.count() : 0; }
-extern "C" const char* fmi_t5_missing_name(fmi_t5* m, int i) { return m ? m->r.missing.name(i) : nullptr; }
-extern "C" size_t fmi_t5_size_in_bytes(const fmi_t5* m) { return m ? m->r.bytes + m->ws.base.bytes() : 0; }
+extern "C" int fmi_t5_missing_count(const fmi_t5* m) { return enc_missing_count(m); }
+extern "C" const char* fmi_t5_missing_name(fmi_t5* m, int i) { return enc_missing_name(m, i); }
+extern "C" size_t fmi_t5_size_in_bytes(const fmi_t5* m) { return enc_size_in_bytes(m); }
 
 extern "C" int fmi_t5_forward(fmi_t5* m, const int32_t* input_ids, int B, int T, void* out, fmi_dtype out_dtype, void* stream) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
@@ -246,30 +229,16 @@ extern "C" int fmi_t5_forward(fmi_t5* m, const int32_t* input_ids, int B, int T,
   const int D = c.d_model, H = c.num_heads, I = H * 64, F = c.d_ff, rows = B * T;
   const bool gated = c.feed_forward_act != FMI_T5_RELU;
   const int FW = gated ? 2 * F : F;
-  // workspace carve
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carve carve;
   const size_t o_x = carve((size_t)rows * D * 4), o_n = carve((size_t)rows * D * 2), o_qkv = carve((size_t)rows * 3 * I * 2), o_a = carve((size_t)rows * I * 2);
   const size_t o_h = carve((size_t)rows * FW * 2), o_g = carve((size_t)rows * F * 2), o_bias = carve((size_t)H * T * T * 4), o_ones = carve((size_t)D * 4);
   const size_t o_ids = carve((size_t)rows * 4), o_bkt = carve((size_t)(2 * T - 1) * 4), o_err = carve(4), o_of = carve((size_t)rows * D * 4);
-  FMI_TRY(m->ws.reserve(off));
-  char* w = m->ws.base.as<char>();
-  float* x = (float*)(w + o_x);
-  bf16_t* n = (bf16_t*)(w + o_n);
-  bf16_t* qkv = (bf16_t*)(w + o_qkv);
-  bf16_t* a = (bf16_t*)(w + o_a);
-  bf16_t* h = (bf16_t*)(w + o_h);
-  bf16_t* g = (bf16_t*)(w + o_g);
-  float* bias = (float*)(w + o_bias);
-  float* ones = (float*)(w + o_ones);
-  int32_t* ids = (int32_t*)(w + o_ids);
-  int* bkt = (int*)(w + o_bkt);
-  int* err = (int*)(w + o_err);
-  float* of = (float*)(w + o_of);
+  FMI_TRY(m->ws.reserve(carve.total));
+  const Workspace& ws = m->ws;
+  float *x = ws.at<float>(o_x), *bias = ws.at<float>(o_bias), *ones = ws.at<float>(o_ones), *of = ws.at<float>(o_of);
+  bf16_t *n = ws.at<bf16_t>(o_n), *qkv = ws.at<bf16_t>(o_qkv), *a = ws.at<bf16_t>(o_a), *h = ws.at<bf16_t>(o_h), *g = ws.at<bf16_t>(o_g);
+  int32_t* ids = ws.at<int32_t>(o_ids);
+  int *bkt = ws.at<int>(o_bkt), *err = ws.at<int>(o_err);
 
   FMI_HIP_TRY(hipMemcpyAsync(ids, input_ids, (size_t)rows * 4, hipMemcpyDefault, s));
   FMI_HIP_TRY(hipMemsetAsync(err, 0, 4, s));
@@ -312,29 +281,23 @@ extern "C" int fmi_t5_forward(fmi_t5* m, const int32_t* input_ids, int B, int T,
 }
 
 // ============================================================================================= CLIP
-struct fmi_clip {
+struct fmi_clip : EncoderHandle {
   fmi_clip_config cfg;
-  int device = current_device();
-  Registry r;
-  Workspace ws;
   bf16_t *tok = nullptr, *pos = nullptr, *fw = nullptr, *fb = nullptr;
-  std::vector<ClipLayer> layers;
+  std::vector<EncLayer> layers;
 };
 
 static void clip_layout(fmi_clip* m) {
   const fmi_clip_config& c = m->cfg;
   const int D = c.projection_dim, F = c.intermediate_size;
   Registry& r = m->r;
-  r.used = 0;
-  r.names.clear();
-  r.missing.names.clear();
   const std::string tm = "text_model.";
   m->tok = r.take((size_t)c.vocab_size * D);
   r.reg(tm + "embeddings.token_embedding.weight", m->tok, c.vocab_size, D);
   m->pos = r.take((size_t)c.max_position_embeddings * D);
   r.reg(tm + "embeddings.position_embedding.weight", m->pos, c.max_position_embeddings, D);
   m->layers.resize(c.num_hidden_layers);
-  for (int l = 0; l < c.num_hidden_layers; ++l) clip_layer_layout(r, tm + "encoder.layers." + std::to_string(l) + ".", D, F, m->layers[l]);
+  for (int l = 0; l < c.num_hidden_layers; ++l) m->layers[l] = enc_layer_layout(r, tm + "encoder.layers." + std::to_string(l) + ".", D, c.num_attention_heads, F, 64);
   m->fw = r.take(D), m->fb = r.take(D);
   r.reg(tm + "final_layer_norm.weight", m->fw, D, 0), r.reg(tm + "final_layer_norm.bias", m->fb, D, 0);
 }
@@ -350,30 +313,19 @@ extern "C" int fmi_clip_create(const fmi_clip_config* cfg, fmi_clip** out) {
     return fail(FMI_ERR_UNSUPPORTED, "clip_create: head dim (projection_dim / num_attention_heads) must be 64");
   if (cfg->projection_dim % 64 || cfg->intermediate_size % 64 || cfg->intermediate_size <= 0 || cfg->num_hidden_layers <= 0 || cfg->vocab_size <= 0 || cfg->max_position_embeddings <= 0)
     return fail(FMI_ERR_INVALID, "clip_create: widths must be positive multiples of 64");
-  fmi_clip* m = new fmi_clip();
+  std::unique_ptr<fmi_clip> m(new fmi_clip());
   m->cfg = *cfg;
-  clip_layout(m);
-  m->r.bytes = align_up(m->r.used, 256);
-  hipError_t e = m->r.arena.alloc(m->r.bytes);
-  if (e != hipSuccess) {
-    delete m;
-    return fail(FMI_ERR_HIP, std::string("clip_create: hipMalloc of the weight arena: ") + hipGetErrorString(e));
-  }
-  clip_layout(m);
-  *out = m;
+  FMI_TRY(create_arena("clip_create", m.get(), clip_layout, /*zero=*/false));
+  *out = m.release();
   return FMI_OK;
 }
-extern "C" void fmi_clip_destroy(fmi_clip* m) {
-  delete m;  // (the weight arena and the workspace are DeviceBuffers)
-}
+extern "C" void fmi_clip_destroy(fmi_clip* m) { delete m; }  // (the weight arena and the workspace are DeviceBuffers)
 extern "C" int fmi_clip_set_tensor(fmi_clip* m, const char* name, const void* data, fmi_dtype dtype, const int64_t* shape, int rank) {
-  if (m) FMI_TRY(use_device_ordinal(m->device));
-  if (!m) return fail(FMI_ERR_INVALID, "clip_set_tensor: null model");
-  return m->r.set("clip_set_tensor", name, data, dtype, shape, rank);
+  return enc_set_tensor(m, "clip_set_tensor", name, data, dtype, shape, rank);
 }
-extern "C" int fmi_clip_missing_count(const fmi_clip* m) { return m ? m->r.missing.count() : 0; }
-extern "C" const char* fmi_clip_missing_name(fmi_clip* m, int i) { return m ? m->r.missing.name(i) : nullptr; }
-extern "C" size_t fmi_clip_size_in_bytes(const fmi_clip* m) { return m ? m->r.bytes + m->ws.base.bytes() : 0; }
+extern "C" int fmi_clip_missing_count(const fmi_clip* m) { return enc_missing_count(m); }
+extern "C" const char* fmi_clip_missing_name(fmi_clip* m, int i) { return enc_missing_name(m, i); }
+extern "C" size_t fmi_clip_size_in_bytes(const fmi_clip* m) { return enc_size_in_bytes(m); }
 
 extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, int T, void* pooled_out, fmi_dtype pooled_dtype, float* hidden_out, void* stream) {
   if (m) FMI_TRY(use_device_ordinal(m->device));
@@ -384,29 +336,17 @@ extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, in
   FMI_TRY(m->r.missing.ready("clip_forward"));
   hipStream_t s = (hipStream_t)stream;
   const int D = c.projection_dim, H = c.num_attention_heads, F = c.intermediate_size, rows = B * T;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carve carve;
   const size_t o_x = carve((size_t)rows * D * 4), o_n = carve((size_t)rows * D * 2), o_qkv = carve((size_t)rows * 3 * D * 2), o_a = carve((size_t)rows * D * 2);
   const size_t o_h = carve((size_t)rows * F * 2), o_g = carve((size_t)rows * F * 2), o_ones = carve((size_t)D * 4), o_ids = carve((size_t)rows * 4), o_err = carve(4);
   const size_t o_hf = carve((size_t)rows * D * 4), o_pf = carve((size_t)B * D * 4), o_pb = carve((size_t)B * D * 2);
-  FMI_TRY(m->ws.reserve(off));
-  char* w = m->ws.base.as<char>();
-  float* x = (float*)(w + o_x);
-  bf16_t* n = (bf16_t*)(w + o_n);
-  bf16_t* qkv = (bf16_t*)(w + o_qkv);
-  bf16_t* a = (bf16_t*)(w + o_a);
-  bf16_t* h = (bf16_t*)(w + o_h);
-  bf16_t* g = (bf16_t*)(w + o_g);
-  float* ones = (float*)(w + o_ones);
-  int32_t* ids = (int32_t*)(w + o_ids);
-  int* err = (int*)(w + o_err);
-  float* hf = (float*)(w + o_hf);
-  float* pf = (float*)(w + o_pf);
-  bf16_t* pb = (bf16_t*)(w + o_pb);
+  FMI_TRY(m->ws.reserve(carve.total));
+  const Workspace& ws = m->ws;
+  float *x = ws.at<float>(o_x), *ones = ws.at<float>(o_ones), *hf = ws.at<float>(o_hf), *pf = ws.at<float>(o_pf);
+  bf16_t* pb = ws.at<bf16_t>(o_pb);
+  int32_t* ids = ws.at<int32_t>(o_ids);
+  int* err = ws.at<int>(o_err);
+  const EncLayerBuffers lw{x, ws.at<bf16_t>(o_n), ws.at<bf16_t>(o_qkv), ws.at<bf16_t>(o_a), ws.at<bf16_t>(o_h), ws.at<bf16_t>(o_g), ones};
 
   FMI_HIP_TRY(hipMemcpyAsync(ids, input_ids, (size_t)rows * 4, hipMemcpyDefault, s));
   FMI_HIP_TRY(hipMemsetAsync(err, 0, 4, s));
@@ -414,8 +354,8 @@ extern "C" int fmi_clip_forward(fmi_clip* m, const int32_t* input_ids, int B, in
   hipLaunchKernelGGL(embed_gather_kernel, dim3(rows), dim3(256), 0, s, ids, m->tok, m->pos, T, D, c.vocab_size, x, err);
   FMI_LAUNCH_CHECK();
   const int nb = (rows + 3) / 4;
-  FMI_TRY(clip_layers(m->layers, ClipLayerBuffers{x, n, qkv, a, h, g, ones}, B, T, D, H, F, /*causal=*/1, s));  // ClipEncoder::forward (clip/text.rs:273-291)
-  hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, x, m->fw, m->fb, 1e-5f, rows, D, (bf16_t*)nullptr, hf);
+  FMI_TRY(enc_layers(m->layers, lw, rows, D, D, F, CLIP_LN_EPS, ACT_QUICK_GELU, s, clip_attention(B, T, H, /*causal=*/1, s)));  // ClipEncoder::forward (clip/text.rs:273-291)
+  hipLaunchKernelGGL(layernorm_affine_kernel, dim3(nb), dim3(256), 0, s, x, m->fw, m->fb, CLIP_LN_EPS, rows, D, (bf16_t*)nullptr, hf);
   hipLaunchKernelGGL(clip_pool_kernel, dim3(B), dim3(256), 0, s, hf, ids, T, D, pf);
   FMI_LAUNCH_CHECK();
   if (pooled_dtype == FMI_BF16) FMI_TRY(launch_cast_to_bf16(pf, FMI_F32, pb, (int64_t)B * D, s));

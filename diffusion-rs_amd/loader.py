@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .text import CLIP_IMAGE_MEAN, CLIP_IMAGE_STD, CLIP_VISION_L, SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD, SIGLIP_SO400M
 
 _ST_DTYPES = {"F32": (torch.float32, 4), "F16": (torch.float16, 2), "BF16": (torch.bfloat16, 2), "U8": (torch.uint8, 1), "I8": (torch.int8, 1),
               "I32": (torch.int32, 4), "I64": (torch.int64, 8), "F64": (torch.float64, 8),
@@ -335,9 +336,60 @@ def load_ip_adapter(path: str, cfg: dict):
     return ip_adapter_from_tensors(cfg, dict(_safetensors_from_buffer(memoryview(mm))), os.path.basename(path))
 
 
-from .text import CLIP_IMAGE_MEAN, CLIP_IMAGE_STD, CLIP_VISION_L  # noqa: E402
-
 CLIP_VISION_KEYS = tuple(CLIP_VISION_L)
+
+
+def _safetensors_in(path: str) -> dict:
+    """Every tensor of the *.safetensors files of a directory, in file-name order."""
+    tensors = {}
+    for fn in sorted(os.listdir(path)):
+        if fn.endswith(".safetensors"):
+            with open(os.path.join(path, fn), "rb") as f:
+                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            tensors.update(_safetensors_from_buffer(memoryview(mm)))
+    return tensors
+
+
+def _image_processor(pre: Optional[dict], defaults, switches, size_rule) -> Tuple[tuple, tuple]:
+    """(image_mean, image_std) of a preprocessor_config.json (None: `defaults`, the tower's constants).  What a tower's preprocess does is fixed, so a processor
+    that asks for anything else is refused by name: a switch that is not as the tower has it (switches: (flag, the value it must have, what the tower does
+    instead, in the refusal's words)), a resample other than bicubic, a rescale factor other than 1 / 255, a size the tower's own size_rule(pre) raises for."""
+    if pre is None:
+        return defaults
+    for flag, wanted, instead in switches:
+        if bool(pre.get(flag, wanted)) != wanted:
+            raise ValueError(f"preprocessor_config.json has {flag} = {'false' if wanted else 'true'}: {instead}")
+    if int(pre.get("resample", 3)) != 3:
+        raise ValueError(f"preprocessor_config.json has resample = {pre['resample']!r}: only 3 (PIL's BICUBIC) is supported")
+    if abs(float(pre.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
+        raise ValueError(f"preprocessor_config.json has rescale_factor = {pre['rescale_factor']!r}: only 1 / 255 is supported")
+    size_rule(pre)
+    mean, std = pre.get("image_mean", defaults[0]), pre.get("image_std", defaults[1])
+    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
+        raise ValueError(f"preprocessor_config.json: image_mean / image_std must hold 3 values, the std positive, got {mean!r} / {std!r}")
+    return tuple(float(m) for m in mean), tuple(float(s) for s in std)
+
+
+def _tower_from_tensors(want: dict, tensors, where: str, rename, ignored, model: str, part: str) -> dict:
+    """{name: tensor} of the tensors `want` ({name: shape}) out of a checkpoint's.  rename(name): the model's name of a checkpoint key (a key that already is
+    one wins over a key that becomes the same one); ignored(name): a key the checkpoint may carry and the model does not read.  ValueError naming the keys: an
+    unexpected tensor ("not <model>'s"), a missing one ("<part> tensors missing"), a shape that does not fit."""
+    sd, unexpected = {}, []
+    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
+        full = rename(name)
+        if full in want and (full == name or full not in sd):
+            sd[full] = t
+        elif not ignored(name):
+            unexpected.append(name)
+    if unexpected:
+        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not {model}'s), e.g. {sorted(unexpected)[:3]}")
+    missing = [k for k in want if k not in sd]
+    if missing:
+        raise ValueError(f"{where}: {len(missing)} {part} tensors missing, e.g. {missing[:3]}")
+    for k, t in sd.items():
+        if tuple(t.shape) != tuple(want[k]):
+            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
+    return sd
 
 
 def clip_vision_config(config: dict) -> dict:
@@ -368,15 +420,7 @@ def clip_vision_config(config: dict) -> dict:
 def clip_image_processor(pre: Optional[dict], image_size: int) -> Tuple[tuple, tuple]:
     """(image_mean, image_std) of a preprocessor_config.json (None: CLIP's constants).  What ClipVisionModel.preprocess does is fixed — bicubic resize of the
     shortest edge to image_size, centre crop to image_size, rescale by 1 / 255, normalise — so a processor that asks for anything else is refused by name."""
-    if pre is None:
-        return CLIP_IMAGE_MEAN, CLIP_IMAGE_STD
-    for flag in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
-        if not pre.get(flag, True):
-            raise ValueError(f"preprocessor_config.json has {flag} = false: the image encoder always resizes, centre-crops, rescales and normalises")
-    if int(pre.get("resample", 3)) != 3:
-        raise ValueError(f"preprocessor_config.json has resample = {pre['resample']!r}: only 3 (PIL's BICUBIC) is supported")
-    if abs(float(pre.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
-        raise ValueError(f"preprocessor_config.json has rescale_factor = {pre['rescale_factor']!r}: only 1 / 255 is supported")
+    always = "the image encoder always resizes, centre-crops, rescales and normalises"
 
     def edge(v, keys):
         if isinstance(v, dict):
@@ -386,15 +430,14 @@ def clip_image_processor(pre: Optional[dict], image_size: int) -> Tuple[tuple, t
             return vals.pop()
         return None if v is None else int(v)
 
-    size, crop = pre.get("size", image_size), pre.get("crop_size", image_size)
-    if edge(size, ("shortest_edge",)) != image_size:
-        raise ValueError(f"preprocessor_config.json has size = {size!r}: the shortest edge is resized to the model's image_size = {image_size}")
-    if edge(crop, ("height", "width")) != image_size:
-        raise ValueError(f"preprocessor_config.json has crop_size = {crop!r}: the centre crop is the model's image_size = {image_size}")
-    mean, std = pre.get("image_mean", CLIP_IMAGE_MEAN), pre.get("image_std", CLIP_IMAGE_STD)
-    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
-        raise ValueError(f"preprocessor_config.json: image_mean / image_std must hold 3 values, the std positive, got {mean!r} / {std!r}")
-    return tuple(float(m) for m in mean), tuple(float(s) for s in std)
+    def size_rule(pre):
+        size, crop = pre.get("size", image_size), pre.get("crop_size", image_size)
+        if edge(size, ("shortest_edge",)) != image_size:
+            raise ValueError(f"preprocessor_config.json has size = {size!r}: the shortest edge is resized to the model's image_size = {image_size}")
+        if edge(crop, ("height", "width")) != image_size:
+            raise ValueError(f"preprocessor_config.json has crop_size = {crop!r}: the centre crop is the model's image_size = {image_size}")
+
+    return _image_processor(pre, (CLIP_IMAGE_MEAN, CLIP_IMAGE_STD), [(f, True, always) for f in ("do_resize", "do_center_crop", "do_rescale", "do_normalize")], size_rule)
 
 
 def _clip_vision_ignored(name: str) -> bool:
@@ -406,22 +449,7 @@ def _clip_vision_ignored(name: str) -> bool:
 def clip_vision_from_tensors(cfg: dict, tensors, where: str = "image encoder") -> dict:
     """{name: tensor} of the vision tower of configuration cfg from a CLIPVisionModelWithProjection or a full CLIPModel checkpoint's tensors.  ValueError naming
     the keys: an unexpected tensor (anything but the ignored ones of a full checkpoint), a missing one, a shape that does not fit cfg."""
-    want = synth.clip_vision_tensor_shapes(cfg)
-    sd, unexpected = {}, []
-    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
-        if name in want:
-            sd[name] = t
-        elif not _clip_vision_ignored(name):
-            unexpected.append(name)
-    if unexpected:
-        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not CLIPVisionModelWithProjection's), e.g. {sorted(unexpected)[:3]}")
-    missing = [k for k in want if k not in sd]
-    if missing:
-        raise ValueError(f"{where}: {len(missing)} image-encoder tensors missing, e.g. {missing[:3]}")
-    for k, t in sd.items():
-        if tuple(t.shape) != tuple(want[k]):
-            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
-    return sd
+    return _tower_from_tensors(synth.clip_vision_tensor_shapes(cfg), tensors, where, lambda name: name, _clip_vision_ignored, "CLIPVisionModelWithProjection", "image-encoder")
 
 
 def load_clip_vision(path: str):
@@ -437,29 +465,10 @@ def load_clip_vision(path: str):
         with open(os.path.join(path, "preprocessor_config.json")) as f:
             pre = json.load(f)
     mean, std = clip_image_processor(pre, cfg["image_size"])
-    tensors = {}
-    for fn in sorted(os.listdir(path)):
-        if fn.endswith(".safetensors"):
-            with open(os.path.join(path, fn), "rb") as f:
-                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-            tensors.update(_safetensors_from_buffer(memoryview(mm)))
-    return dict(cfg, image_mean=mean, image_std=std), clip_vision_from_tensors(cfg, tensors, os.path.basename(os.path.normpath(path)))
+    return dict(cfg, image_mean=mean, image_std=std), clip_vision_from_tensors(cfg, _safetensors_in(path), os.path.basename(os.path.normpath(path)))
 
-
-from .text import SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD, SIGLIP_SO400M  # noqa: E402
 
 SIGLIP_VISION_KEYS = tuple(SIGLIP_SO400M)
-
-
-def _safetensors_in(path: str) -> dict:
-    """Every tensor of the *.safetensors files of a directory, in file-name order."""
-    tensors = {}
-    for fn in sorted(os.listdir(path)):
-        if fn.endswith(".safetensors"):
-            with open(os.path.join(path, fn), "rb") as f:
-                mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-            tensors.update(_safetensors_from_buffer(memoryview(mm)))
-    return tensors
 
 
 def siglip_vision_config(config: dict) -> dict:
@@ -493,25 +502,17 @@ def siglip_vision_config(config: dict) -> dict:
 def siglip_image_processor(pre: Optional[dict], image_size: int) -> Tuple[tuple, tuple]:
     """(image_mean, image_std) of a preprocessor_config.json (None: SigLIP's constants, 0.5 each).  What SiglipVisionModel.preprocess does is fixed — a bicubic
     resize straight to image_size x image_size, rescale by 1 / 255, normalise — so a processor that asks for anything else is refused by name."""
-    if pre is None:
-        return SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD
-    for flag in ("do_resize", "do_rescale", "do_normalize"):
-        if not pre.get(flag, True):
-            raise ValueError(f"preprocessor_config.json has {flag} = false: the SigLIP image encoder always resizes, rescales and normalises")
-    if pre.get("do_center_crop", False):
-        raise ValueError("preprocessor_config.json has do_center_crop = true: the SigLIP image encoder resizes straight to the square and never crops")
-    if int(pre.get("resample", 3)) != 3:
-        raise ValueError(f"preprocessor_config.json has resample = {pre['resample']!r}: only 3 (PIL's BICUBIC) is supported")
-    if abs(float(pre.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
-        raise ValueError(f"preprocessor_config.json has rescale_factor = {pre['rescale_factor']!r}: only 1 / 255 is supported")
-    size = pre.get("size", image_size)
-    hw = (size.get("height"), size.get("width")) if isinstance(size, dict) and set(size) == {"height", "width"} else (size, size) if isinstance(size, int) else None
-    if hw is None or tuple(int(v) for v in hw) != (image_size, image_size):
-        raise ValueError(f"preprocessor_config.json has size = {size!r}: the picture is resized to the model's image_size = {image_size}, height and width")
-    mean, std = pre.get("image_mean", SIGLIP_IMAGE_MEAN), pre.get("image_std", SIGLIP_IMAGE_STD)
-    if len(mean) != 3 or len(std) != 3 or not all(float(s) > 0 for s in std):
-        raise ValueError(f"preprocessor_config.json: image_mean / image_std must hold 3 values, the std positive, got {mean!r} / {std!r}")
-    return tuple(float(m) for m in mean), tuple(float(s) for s in std)
+    always = "the SigLIP image encoder always resizes, rescales and normalises"
+    switches = [(f, True, always) for f in ("do_resize", "do_rescale", "do_normalize")]
+    switches.append(("do_center_crop", False, "the SigLIP image encoder resizes straight to the square and never crops"))
+
+    def size_rule(pre):
+        size = pre.get("size", image_size)
+        hw = (size.get("height"), size.get("width")) if isinstance(size, dict) and set(size) == {"height", "width"} else (size, size) if isinstance(size, int) else None
+        if hw is None or tuple(int(v) for v in hw) != (image_size, image_size):
+            raise ValueError(f"preprocessor_config.json has size = {size!r}: the picture is resized to the model's image_size = {image_size}, height and width")
+
+    return _image_processor(pre, (SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD), switches, size_rule)
 
 
 def siglip_vision_from_tensors(cfg: dict, tensors, where: str = "SigLIP image encoder") -> dict:
@@ -519,26 +520,13 @@ def siglip_vision_from_tensors(cfg: dict, tensors, where: str = "SigLIP image en
     tensors.  A checkpoint may carry the tower's keys with the `vision_model.` prefix (the published ones) or without it (what transformers 5 writes for a
     bare SiglipVisionModel); the pooling head (`head.*`) and a full checkpoint's text tower, logit_scale and logit_bias are ignored.  ValueError naming the
     keys: any other unexpected tensor, a missing one, a shape that does not fit cfg."""
-    want = synth.siglip_vision_tensor_shapes(cfg)
     vm = "vision_model."
-    sd, unexpected = {}, []
-    for name, t in (tensors.items() if isinstance(tensors, dict) else tensors):
-        full = name if name.startswith(vm) else vm + name
-        if full in want and (name.startswith(vm) or full not in sd):
-            sd[full] = t
-        elif full.startswith(vm + "head.") or name.startswith("text_model.") or name in ("logit_scale", "logit_bias", vm + "embeddings.position_ids", "embeddings.position_ids"):
-            continue
-        else:
-            unexpected.append(name)
-    if unexpected:
-        raise ValueError(f"{where}: {len(unexpected)} unexpected tensors (not SiglipVisionModel's), e.g. {sorted(unexpected)[:3]}")
-    missing = [k for k in want if k not in sd]
-    if missing:
-        raise ValueError(f"{where}: {len(missing)} SigLIP image-encoder tensors missing, e.g. {missing[:3]}")
-    for k, t in sd.items():
-        if tuple(t.shape) != tuple(want[k]):
-            raise ValueError(f"{where}: {k} is {tuple(t.shape)}, expected {tuple(want[k])}")
-    return sd
+
+    def ignored(name):
+        return name.startswith((vm + "head.", "head.", "text_model.")) or name in ("logit_scale", "logit_bias", vm + "embeddings.position_ids", "embeddings.position_ids")
+
+    return _tower_from_tensors(synth.siglip_vision_tensor_shapes(cfg), tensors, where, lambda name: name if name.startswith(vm) else vm + name, ignored,
+                               "SiglipVisionModel", "SigLIP image-encoder")
 
 
 def load_siglip_vision(path: str, preprocessor: Optional[str] = None):

@@ -522,6 +522,21 @@ def t5_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     return out
 
 
+def _encoder_layer_shapes(out, p, D, F):
+    """The names and shapes of one CLIP-style encoder layer (CLIP's text and vision towers, SigLIP's) under prefix p, appended to `out`.  The order is part of
+    the synthetic weights: text_state_dict_numpy draws from one seeded stream in the order of the names."""
+    for ln in ("layer_norm1", "layer_norm2"):
+        out[p + ln + ".weight"] = (D,)
+        out[p + ln + ".bias"] = (D,)
+    for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+        out[p + f"self_attn.{n}.weight"] = (D, D)
+        out[p + f"self_attn.{n}.bias"] = (D,)
+    out[p + "mlp.fc1.weight"] = (F, D)
+    out[p + "mlp.fc1.bias"] = (F,)
+    out[p + "mlp.fc2.weight"] = (D, F)
+    out[p + "mlp.fc2.bias"] = (D,)
+
+
 def clip_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     """Tensor names/shapes ClipTextTransformer::new reads under vb.pp("text_model") (clip/text.rs:251-262)."""
     D, F = cfg["projection_dim"], cfg["intermediate_size"]
@@ -530,17 +545,7 @@ def clip_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     out[tm + "embeddings.token_embedding.weight"] = (cfg["vocab_size"], D)
     out[tm + "embeddings.position_embedding.weight"] = (cfg["max_position_embeddings"], D)
     for l in range(cfg["num_hidden_layers"]):
-        p = tm + f"encoder.layers.{l}."
-        for ln in ("layer_norm1", "layer_norm2"):
-            out[p + ln + ".weight"] = (D,)
-            out[p + ln + ".bias"] = (D,)
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            out[p + f"self_attn.{n}.weight"] = (D, D)
-            out[p + f"self_attn.{n}.bias"] = (D,)
-        out[p + "mlp.fc1.weight"] = (F, D)
-        out[p + "mlp.fc1.bias"] = (F,)
-        out[p + "mlp.fc2.weight"] = (D, F)
-        out[p + "mlp.fc2.bias"] = (D,)
+        _encoder_layer_shapes(out, tm + f"encoder.layers.{l}.", D, F)
     out[tm + "final_layer_norm.weight"] = (D,)
     out[tm + "final_layer_norm.bias"] = (D,)
     return out
@@ -557,17 +562,7 @@ def clip_vision_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     out[vm + "pre_layrnorm.weight"] = (D,)  # (HuggingFace's spelling)
     out[vm + "pre_layrnorm.bias"] = (D,)
     for l in range(cfg["num_hidden_layers"]):
-        p = vm + f"encoder.layers.{l}."
-        for ln in ("layer_norm1", "layer_norm2"):
-            out[p + ln + ".weight"] = (D,)
-            out[p + ln + ".bias"] = (D,)
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            out[p + f"self_attn.{n}.weight"] = (D, D)
-            out[p + f"self_attn.{n}.bias"] = (D,)
-        out[p + "mlp.fc1.weight"] = (F, D)
-        out[p + "mlp.fc1.bias"] = (F,)
-        out[p + "mlp.fc2.weight"] = (D, F)
-        out[p + "mlp.fc2.bias"] = (D,)
+        _encoder_layer_shapes(out, vm + f"encoder.layers.{l}.", D, F)
     out[vm + "post_layernorm.weight"] = (D,)
     out[vm + "post_layernorm.bias"] = (D,)
     out["visual_projection.weight"] = (cfg["projection_dim"], D)
@@ -583,17 +578,7 @@ def siglip_vision_tensor_shapes(cfg) -> "OrderedDict[str, tuple]":
     out[vm + "embeddings.patch_embedding.bias"] = (D,)
     out[vm + "embeddings.position_embedding.weight"] = ((cfg["image_size"] // P) ** 2, D)
     for l in range(cfg["num_hidden_layers"]):
-        p = vm + f"encoder.layers.{l}."
-        for ln in ("layer_norm1", "layer_norm2"):
-            out[p + ln + ".weight"] = (D,)
-            out[p + ln + ".bias"] = (D,)
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            out[p + f"self_attn.{n}.weight"] = (D, D)
-            out[p + f"self_attn.{n}.bias"] = (D,)
-        out[p + "mlp.fc1.weight"] = (F, D)
-        out[p + "mlp.fc1.bias"] = (F,)
-        out[p + "mlp.fc2.weight"] = (D, F)
-        out[p + "mlp.fc2.bias"] = (D,)
+        _encoder_layer_shapes(out, vm + f"encoder.layers.{l}.", D, F)
     out[vm + "post_layernorm.weight"] = (D,)
     out[vm + "post_layernorm.bias"] = (D,)
     return out

@@ -34,8 +34,22 @@ SIGLIP_IMAGE_MEAN = (0.5, 0.5, 0.5)
 SIGLIP_IMAGE_STD = (0.5, 0.5, 0.5)
 
 
+def _as_tensor(x):
+    """A tensor as it is, anything else (a numpy array) through torch.from_numpy."""
+    return x if isinstance(x, torch.Tensor) else torch.from_numpy(x)
+
+
 class _Encoder:
     _kind = ""
+
+    def _open(self, device, create_fn, *args):
+        """The constructor steps every handle shares: the library, the device, and the handle that the library's `create_fn(*args, &handle)` makes."""
+        self.lib = L.load()
+        L.check(self.lib.fmi_init(device), self.lib)
+        self.device = torch.device("cuda", device)
+        h = C.c_void_p()
+        L.check(getattr(self.lib, create_fn)(*args, C.byref(h)), self.lib)
+        self.h = h
 
     def close(self):
         if getattr(self, "h", None):
@@ -85,18 +99,13 @@ class T5EncoderModel(_Encoder):
     _kind = "t5"
 
     def __init__(self, cfg: dict = None, device: int = 0):
-        self.lib = L.load()
-        L.check(self.lib.fmi_init(device), self.lib)
-        self.device = torch.device("cuda", device)
         cfg = dict(T5_XXL if cfg is None else cfg)
         # `quantization_config` (bitsandbytes nf4 / fp4 / LLM.int8, t5/mod.rs:85-90): the quantised Linears arrive through
         # set_linear_bnb4 / set_linear_int8 (loader.load_text_encoder); nothing to configure up front
         self.cfg = cfg
         c = L.T5Config(cfg["vocab_size"], cfg["d_model"], cfg["d_kv"], cfg["d_ff"], cfg["num_layers"], cfg["num_heads"], cfg["relative_attention_num_buckets"],
                        cfg.get("relative_attention_max_distance", 128), cfg["layer_norm_epsilon"], _T5_ACT[cfg.get("feed_forward_proj", "relu")])
-        h = C.c_void_p()
-        L.check(self.lib.fmi_t5_create(C.byref(c), C.byref(h)), self.lib)
-        self.h = h
+        self._open(device, "fmi_t5_create", C.byref(c))
 
     def tensor_names(self):
         from . import synth
@@ -130,16 +139,11 @@ class ClipTextTransformer(_Encoder):
     _kind = "clip"
 
     def __init__(self, cfg: dict = None, device: int = 0):
-        self.lib = L.load()
-        L.check(self.lib.fmi_init(device), self.lib)
-        self.device = torch.device("cuda", device)
         cfg = dict(CLIP_L if cfg is None else cfg)
         self.cfg = cfg
         c = L.ClipConfig(cfg["vocab_size"], cfg["projection_dim"], cfg["intermediate_size"], cfg["max_position_embeddings"], cfg["num_hidden_layers"],
                          cfg["num_attention_heads"])
-        h = C.c_void_p()
-        L.check(self.lib.fmi_clip_create(C.byref(c), C.byref(h)), self.lib)
-        self.h = h
+        self._open(device, "fmi_clip_create", C.byref(c))
 
     def tensor_names(self):
         from . import synth
@@ -173,25 +177,67 @@ def clip_crop_offsets(nh: int, nw: int, size: int):
     return (nh - size) // 2, (nw - size) // 2
 
 
-class ClipVisionModel(_Encoder):
+class _VisionTower(_Encoder):
+    """What the vision towers share: the image processor on the GPU (a bicubic resize to the tower's own shape, the centre crop to image_size, (v / 255 - mean) /
+    std) and the checks of what goes into forward.  A tower adds its resize rule (`_resized`), its forward and its properties."""
+
+    def _open_tower(self, device, cfg, image_mean, image_std, default_mean, default_std, create_fn, config):
+        self.cfg = cfg
+        self.image_mean = tuple(float(v) for v in (default_mean if image_mean is None else image_mean))
+        self.image_std = tuple(float(v) for v in (default_std if image_std is None else image_std))
+        if len(self.image_mean) != 3 or len(self.image_std) != 3:
+            raise ValueError("image_mean and image_std hold one value per RGB channel")
+        self._open(device, create_fn, C.byref(config))
+
+    def _pixel_values(self, pixel_values):
+        """forward's input, checked, as f32 (B,3,S,S) on the device."""
+        S = self.cfg["image_size"]
+        t = _as_tensor(pixel_values)
+        if t.dim() != 4 or tuple(t.shape[1:]) != (3, S, S) or not t.is_floating_point():
+            raise ValueError(f"pixel_values must be float (B,3,{S},{S}), got {t.dtype} {tuple(t.shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def _picture(image_u8):
+        t = _as_tensor(image_u8)
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
+            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    def resize(self, image_u8, nh: int, nw: int):
+        """u8 (h,w,3) -> u8 (nh,nw,3) on the device, PIL's Image.resize(BICUBIC) (fmi_resize_bicubic_u8)."""
+        t = self._picture(image_u8).to(self.device).contiguous()
+        out = torch.empty((int(nh), int(nw), 3), dtype=torch.uint8, device=self.device)
+        L.check(self.lib.fmi_resize_bicubic_u8(_ptr(t), int(t.shape[0]), int(t.shape[1]), _ptr(out), int(nh), int(nw), _stream()), self.lib)
+        return out
+
+    def preprocess(self, image_u8):
+        """The tower's image processor on the device: u8 (H,W,3) of any size -> pixel_values (1,3,S,S) f32 — resized to the tower's `_resized` shape, the centre
+        crop to S x S (which takes everything where the resize went straight to the square), (v / 255 - mean) / std."""
+        S = self.cfg["image_size"]
+        t = self._picture(image_u8)
+        nh, nw = self._resized(int(t.shape[0]), int(t.shape[1]))
+        r = self.resize(t, nh, nw)
+        out = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
+        mean, std = (C.c_float * 3)(*self.image_mean), (C.c_float * 3)(*self.image_std)
+        L.check(self.lib.fmi_clip_preprocess_u8(_ptr(r), nh, nw, S, mean, std, _ptr(out), _stream()), self.lib)
+        return out
+
+    def encode(self, image):
+        """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> what forward returns, f32."""
+        t = _as_tensor(image)
+        return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
+
+
+class ClipVisionModel(_VisionTower):
     """CLIP's vision tower with its projection and its image processor on the GPU: a picture -> image_embeds (1, projection_dim), what
     ip_adapter_image_embeds= takes.  cfg: HuggingFace's CLIPVisionConfig keys (CLIP_VISION_L by default); image_mean / image_std: the processor's constants."""
     _kind = "clip_vision"
 
     def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None):
-        self.lib = L.load()
-        L.check(self.lib.fmi_init(device), self.lib)
-        self.device = torch.device("cuda", device)
         cfg = {k: int((CLIP_VISION_L if cfg is None else cfg)[k]) for k in CLIP_VISION_L}
-        self.cfg = cfg
-        self.image_mean = tuple(float(v) for v in (CLIP_IMAGE_MEAN if image_mean is None else image_mean))
-        self.image_std = tuple(float(v) for v in (CLIP_IMAGE_STD if image_std is None else image_std))
-        if len(self.image_mean) != 3 or len(self.image_std) != 3:
-            raise ValueError("image_mean and image_std hold one value per RGB channel")
-        c = L.ClipVisionConfig(*(cfg[k] for k in CLIP_VISION_L))
-        h = C.c_void_p()
-        L.check(self.lib.fmi_clip_vision_create(C.byref(c), C.byref(h)), self.lib)
-        self.h = h
+        self._open_tower(device, cfg, image_mean, image_std, CLIP_IMAGE_MEAN, CLIP_IMAGE_STD, "fmi_clip_vision_create",
+                         L.ClipVisionConfig(*(cfg[k] for k in CLIP_VISION_L)))
 
     @property
     def projection_dim(self) -> int:
@@ -201,71 +247,33 @@ class ClipVisionModel(_Encoder):
         from . import synth
         return synth.clip_vision_tensor_shapes(self.cfg)
 
+    def _resized(self, h: int, w: int):
+        """CLIPImageProcessor's resize: the shortest edge to S (clip_resize_shape); the centre crop does the rest."""
+        return clip_resize_shape(h, w, self.cfg["image_size"])
+
     def forward(self, pixel_values, return_hidden: bool = False):
         """== CLIPVisionModelWithProjection.forward: pixel_values (B,3,S,S) float -> image_embeds (B,projection_dim) f32; with return_hidden also the encoder's
         output before post_layernorm, (B, 1 + (S / P)^2, hidden_size) f32 (HF's last_hidden_state)."""
         S, D = self.cfg["image_size"], self.cfg["hidden_size"]
-        t = torch.from_numpy(pixel_values) if not isinstance(pixel_values, torch.Tensor) else pixel_values
-        if t.dim() != 4 or tuple(t.shape[1:]) != (3, S, S) or not t.is_floating_point():
-            raise ValueError(f"pixel_values must be float (B,3,{S},{S}), got {t.dtype} {tuple(t.shape)}")
-        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        t = self._pixel_values(pixel_values)
         B, T = int(t.shape[0]), 1 + (S // self.cfg["patch_size"]) ** 2
         out = torch.empty((B, self.cfg["projection_dim"]), dtype=torch.float32, device=self.device)
         hid = torch.empty((B, T, D), dtype=torch.float32, device=self.device) if return_hidden else None
         L.check(self.lib.fmi_clip_vision_forward(self.h, _ptr(t), B, _ptr(out), L.F32, _ptr(hid) if hid is not None else None, _stream()), self.lib)
         return (out, hid) if return_hidden else out
 
-    def resize(self, image_u8, nh: int, nw: int):
-        """u8 (h,w,3) -> u8 (nh,nw,3) on the device, PIL's Image.resize(BICUBIC) (fmi_resize_bicubic_u8)."""
-        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
-        t = t.to(self.device).contiguous()
-        out = torch.empty((int(nh), int(nw), 3), dtype=torch.uint8, device=self.device)
-        L.check(self.lib.fmi_resize_bicubic_u8(_ptr(t), int(t.shape[0]), int(t.shape[1]), _ptr(out), int(nh), int(nw), _stream()), self.lib)
-        return out
 
-    def preprocess(self, image_u8):
-        """CLIPImageProcessor on the device: u8 (H,W,3) of any size -> pixel_values (1,3,S,S) f32 — the shortest edge resized to S (clip_resize_shape), the centre
-        crop, (v / 255 - mean) / std."""
-        S = self.cfg["image_size"]
-        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
-        nh, nw = clip_resize_shape(int(t.shape[0]), int(t.shape[1]), S)
-        r = self.resize(t, nh, nw)
-        out = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
-        mean, std = (C.c_float * 3)(*self.image_mean), (C.c_float * 3)(*self.image_std)
-        L.check(self.lib.fmi_clip_preprocess_u8(_ptr(r), nh, nw, S, mean, std, _ptr(out), _stream()), self.lib)
-        return out
-
-    def encode(self, image):
-        """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> image_embeds f32."""
-        t = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
-        return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
-
-
-class SiglipVisionModel(_Encoder):
+class SiglipVisionModel(_VisionTower):
     """SigLIP's vision tower with its image processor on the GPU: a picture -> last_hidden_state (1, Np, hidden_size), what the Redux embedder
     reads.  cfg: HuggingFace's SiglipVisionConfig keys (SIGLIP_SO400M by default); image_mean / image_std: the processor's constants.  The pooling head of the
     checkpoint is not part of the model."""
     _kind = "siglip_vision"
 
     def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None):
-        self.lib = L.load()
-        L.check(self.lib.fmi_init(device), self.lib)
-        self.device = torch.device("cuda", device)
         src = SIGLIP_SO400M if cfg is None else cfg
         cfg = {k: (float(src.get(k, 1e-6)) if k == "layer_norm_eps" else int(src[k])) for k in SIGLIP_SO400M}
-        self.cfg = cfg
-        self.image_mean = tuple(float(v) for v in (SIGLIP_IMAGE_MEAN if image_mean is None else image_mean))
-        self.image_std = tuple(float(v) for v in (SIGLIP_IMAGE_STD if image_std is None else image_std))
-        if len(self.image_mean) != 3 or len(self.image_std) != 3:
-            raise ValueError("image_mean and image_std hold one value per RGB channel")
-        c = L.SiglipVisionConfig(*(cfg[k] for k in SIGLIP_SO400M))
-        h = C.c_void_p()
-        L.check(self.lib.fmi_siglip_vision_create(C.byref(c), C.byref(h)), self.lib)
-        self.h = h
+        self._open_tower(device, cfg, image_mean, image_std, SIGLIP_IMAGE_MEAN, SIGLIP_IMAGE_STD, "fmi_siglip_vision_create",
+                         L.SiglipVisionConfig(*(cfg[k] for k in SIGLIP_SO400M)))
 
     @property
     def hidden_size(self) -> int:
@@ -279,48 +287,23 @@ class SiglipVisionModel(_Encoder):
         from . import synth
         return synth.siglip_vision_tensor_shapes(self.cfg)
 
+    def _resized(self, h: int, w: int):
+        """SiglipImageProcessor's resize: straight to S x S (no aspect rule, no crop)."""
+        return self.cfg["image_size"], self.cfg["image_size"]
+
     def forward(self, pixel_values, dtype=torch.float32):
         """== SiglipVisionModel.forward(...).last_hidden_state: pixel_values (B,3,S,S) float -> (B, Np, hidden_size) f32 (or bf16): post_layernorm of every row."""
-        S, D = self.cfg["image_size"], self.cfg["hidden_size"]
-        t = torch.from_numpy(pixel_values) if not isinstance(pixel_values, torch.Tensor) else pixel_values
-        if t.dim() != 4 or tuple(t.shape[1:]) != (3, S, S) or not t.is_floating_point():
-            raise ValueError(f"pixel_values must be float (B,3,{S},{S}), got {t.dtype} {tuple(t.shape)}")
+        t = self._pixel_values(pixel_values)
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        t = t.to(device=self.device, dtype=torch.float32).contiguous()
         B = int(t.shape[0])
-        out = torch.empty((B, self.num_patches, D), dtype=dtype, device=self.device)
+        out = torch.empty((B, self.num_patches, self.cfg["hidden_size"]), dtype=dtype, device=self.device)
         L.check(self.lib.fmi_siglip_vision_forward(self.h, _ptr(t), B, _ptr(out), L.F32 if dtype == torch.float32 else L.BF16, _stream()), self.lib)
         return out
 
     def poison_workspace(self, B: int = 1):
         """Test seam (fmi_siglip_vision_poison_workspace): the workspace of a batch of B, every byte 0xff — NaNs wherever a forward reads what it did not write."""
         L.check(self.lib.fmi_siglip_vision_poison_workspace(self.h, int(B), _stream()), self.lib)
-
-    def resize(self, image_u8, nh: int, nw: int):
-        """u8 (h,w,3) -> u8 (nh,nw,3) on the device, PIL's Image.resize(BICUBIC) (fmi_resize_bicubic_u8)."""
-        t = torch.from_numpy(image_u8) if not isinstance(image_u8, torch.Tensor) else image_u8
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8:
-            raise ValueError(f"a picture must be uint8 (H,W,3), got {t.dtype} {tuple(t.shape)}")
-        t = t.to(self.device).contiguous()
-        out = torch.empty((int(nh), int(nw), 3), dtype=torch.uint8, device=self.device)
-        L.check(self.lib.fmi_resize_bicubic_u8(_ptr(t), int(t.shape[0]), int(t.shape[1]), _ptr(out), int(nh), int(nw), _stream()), self.lib)
-        return out
-
-    def preprocess(self, image_u8):
-        """SiglipImageProcessor on the device: u8 (H,W,3) of any size -> pixel_values (1,3,S,S) f32 — resized straight to S x S (no aspect rule, no crop),
-        (v / 255 - mean) / std."""
-        S = self.cfg["image_size"]
-        r = self.resize(image_u8, S, S)
-        out = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
-        mean, std = (C.c_float * 3)(*self.image_mean), (C.c_float * 3)(*self.image_std)
-        L.check(self.lib.fmi_clip_preprocess_u8(_ptr(r), S, S, S, mean, std, _ptr(out), _stream()), self.lib)  # (nh = nw = S: the crop takes everything)
-        return out
-
-    def encode(self, image):
-        """A u8 (H,W,3) picture, or float (B,3,S,S) pixel_values that are already preprocessed -> last_hidden_state f32."""
-        t = torch.from_numpy(image) if not isinstance(image, torch.Tensor) else image
-        return self.forward(self.preprocess(t) if t.dtype == torch.uint8 else t)
 
 
 class ReduxImageEmbedder(_Encoder):
@@ -329,13 +312,8 @@ class ReduxImageEmbedder(_Encoder):
     _kind = "redux"
 
     def __init__(self, redux_dim: int = 1152, txt_dim: int = 4096, device: int = 0):
-        self.lib = L.load()
-        L.check(self.lib.fmi_init(device), self.lib)
-        self.device = torch.device("cuda", device)
         self.redux_dim, self.txt_dim = int(redux_dim), int(txt_dim)
-        h = C.c_void_p()
-        L.check(self.lib.fmi_redux_create(self.redux_dim, self.txt_dim, C.byref(h)), self.lib)
-        self.h = h
+        self._open(device, "fmi_redux_create", self.redux_dim, self.txt_dim)
 
     def tensor_names(self):
         from . import synth
@@ -343,7 +321,7 @@ class ReduxImageEmbedder(_Encoder):
 
     def forward(self, hidden, scale: float = 1.0, dtype=torch.float32):
         """hidden (.., redux_dim) float -> (.., txt_dim) f32 (or bf16)."""
-        t = torch.from_numpy(hidden) if not isinstance(hidden, torch.Tensor) else hidden
+        t = _as_tensor(hidden)
         if t.dim() < 2 or t.shape[-1] != self.redux_dim or not t.is_floating_point() or t.numel() == 0:
             raise ValueError(f"hidden must be float (.., {self.redux_dim}), got {t.dtype} {tuple(t.shape)}")
         if dtype not in (torch.float32, torch.bfloat16):

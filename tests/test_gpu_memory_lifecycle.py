@@ -1,9 +1,10 @@
-"""Device memory of the four model handles over their whole life: every path on which a handle allocates, regrows or retires a block is walked once
+"""Device memory of the model handles over their whole life: every path on which a handle allocates, regrows or retires a block is walked once
 (`lifecycle()`), every handle is closed, and two things are asserted.
 
   * `size_in_bytes()` after each numbered step equals tests/golden/size_in_bytes_small.json, integer for integer.  That file was written by
     tests/golden/gen_size_in_bytes_small.py from this same walk on the commit BEFORE the handles' blocks became DeviceBuffer members: the accounting
-    did not move.
+    did not move.  The steps of the vision towers and the Redux embedder (8, 9) were written the same way on the commit before the five encoder handles
+    came to share one frame (arena creation, workspace carving, encoder layer); steps 1 - 6 came out of that run as they were.
   * Five passes of the walk leave the device's free memory where one pass left it (no growth with the number of passes = no leaked block).
 
 Which branch each step takes at these shapes (SMALL_FLUX: D = 256, MLP width 1024, 2 heads; read off flux_model.hip):
@@ -25,6 +26,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import clip_vision_ref as CVR
+from tests import redux_ref as RR
 from tests.test_gpu_text import SMALL_CLIP, SMALL_T5
 from tests.util import SMALL_FLUX, SMALL_VAE, dev, flux_inputs
 
@@ -44,6 +47,12 @@ def _weights(kind):
         return d.synth.flux_state_dict_numpy(SMALL_FLUX, seed=0)
     if kind == "vae":
         return d.synth.vae_state_dict_numpy(SMALL_VAE, seed=0, encoder=True)
+    if kind == "clip_vision":
+        return CVR.state_dict(CVR.CONFIGS["s56p14"])
+    if kind == "siglip_vision":
+        return RR.state_dict(RR.CONFIGS["h72_t16"])
+    if kind == "redux":
+        return RR.redux_state_dict(128, 64)
     return d.synth.text_state_dict_numpy(d.synth.t5_tensor_shapes(SMALL_T5) if kind == "t5" else d.synth.clip_tensor_shapes(SMALL_CLIP), seed=0)
 
 
@@ -195,6 +204,39 @@ def lifecycle():
     vae.encode(dev(np.random.default_rng(6).uniform(-1, 1, (1, 3, 32, 48)).astype(np.float32)))
     torch.cuda.synchronize()
     vae.close()
+
+    # ---- 8. CLIP vision tower (s56p14: 17 tokens)
+    cv = d.ClipVisionModel(CVR.CONFIGS["s56p14"])
+    cv.load_state_dict(_weights("clip_vision"))
+    sizes["8.0 clip vision loaded"] = cv.size_in_bytes()
+    pix = CVR.pixel_values(CVR.CONFIGS["s56p14"], 2)
+    for B in (1, 2):  # the workspace regrows
+        cv.forward(pix[:B])
+        sizes[f"8.1 clip vision forward B={B}"] = cv.size_in_bytes()
+    torch.cuda.synchronize()
+    cv.close()
+
+    # ---- 9. SigLIP vision tower (h72_t16: heads and MLP padded in the weights) and the Redux embedder
+    sv = d.SiglipVisionModel(RR.CONFIGS["h72_t16"])
+    sv.load_state_dict(_weights("siglip_vision"))
+    sizes["9.0 siglip vision loaded"] = sv.size_in_bytes()
+    sv.poison_workspace(1)  # the test seam allocates the workspace of a batch of 1
+    sizes["9.1 siglip vision poison_workspace(1)"] = sv.size_in_bytes()
+    pix = RR.pixel_values(RR.CONFIGS["h72_t16"], 2)
+    for B in (1, 2):
+        sv.forward(pix[:B])
+        sizes[f"9.2 siglip vision forward B={B}"] = sv.size_in_bytes()
+    torch.cuda.synchronize()
+    sv.close()
+    rx = d.ReduxImageEmbedder(128, 64)
+    rx.load_state_dict(_weights("redux"))
+    sizes["9.3 redux loaded"] = rx.size_in_bytes()
+    hidden = np.random.default_rng(7).standard_normal((81, 128)).astype(np.float32)
+    for rows in (16, 81):
+        rx.forward(hidden[:rows])
+        sizes[f"9.4 redux forward rows={rows}"] = rx.size_in_bytes()
+    torch.cuda.synchronize()
+    rx.close()
     return sizes
 
 

@@ -8,7 +8,7 @@
   (c) google/siglip-so400m-patch14-384's tower and the FLUX.1-dev embedder (1152 -> 12288 -> 4096) on random weights, B = 1, a 301 x 517 u8 picture already on the
       device: `runs` (default 20) calls after 3 warm-up calls, each timed by a host clock around a call that ends in a stream synchronise (the forwards synchronise
       themselves); the median and the spread of the whole encode, of resize + preprocess, of the tower and of the embedder.  The attention's share: the tower's
-      27 attention calls are the op-level fmi_sdpa_bf16 at B = 1, H = 16, L = 729, d = 128 (V transpose + attention, the launches siglip_layers makes), timed by
+      27 attention calls are the op-level fmi_sdpa_bf16 at B = 1, H = 16, L = 729, d = 128 (V transpose + attention, the launches siglip_attention makes), timed by
       device events over 27 x `runs` calls on the same stream;
   (d) the denoise loop of the FLUX.1-dev shape (random weights) at 1024 x 1024, B = 1: `steps` (default 20) steps at T = 512 + 729 text rows beside T = 512, the
       plain step of the same build, ms per step, 3 timed loops each after a warm-up loop."""
