@@ -470,8 +470,6 @@ int launch_col_absmax(const bf16_t* x, int ld, int rows, int K, float* amax, hip
 void smooth_factors_host(const float* act_amax, const float* w_amax, int K, float* s_out, float* inv_out);  // host arrays; median-floored SmoothQuant (fp8.hip)
 int launch_gemv(const float* x, const bf16_t* W, const bf16_t* bias, float* y, int M, int N, int K,
                 int silu_in, int accumulate, hipStream_t stream);
-// bf16 out = w_i8 * SCB[row] / 127 (dequant.cu:205-214) on `stream`
-int launch_dequant_int8_scb_bf16(const int8_t* w, const float* scb, bf16_t* out, int col, int64_t n, hipStream_t stream);
 // LoRA merge (lora.hip): w rows = bf16_rne(w0 rows + sum_j Bt[j, n] * A[j, k]), f64 FMAs in ascending j, one rounding.  w0 / w: (rows, K) bf16, leading
 // dimension K; A (Rpad, K) f32; Bt (Rpad, rows_pad) f64 = the up-projections transposed, weight * scale folded in; Rpad % LORA_RANK_CHUNK == 0 and
 // rows_pad % LORA_TILE_ROWS == 0, zero beyond the real rank / rows.  launch_lora_pack writes one adapter's rank rows [off, off + r) of both: Acat = A, Bt[off + j, n] = coef * B[n, j] (0 for n >= rows).

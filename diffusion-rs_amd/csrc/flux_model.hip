@@ -9,8 +9,7 @@
 //   MOD     the modulation matrix in bf16 (6.5 GB)                             (allocated when a dense part arrives)
 //   BLOCKS  the block linears in bf16 (17.0 GB)                                (allocated when a dense part arrives)
 //   Q4      the same matrices as bitsandbytes nf4 / fp4 codes + f32 absmax     (allocated when a 4-bit part arrives)
-// LLM.int8 matrices, ggml blocks (fmi_flux_set_linear_gguf: 4.5 to 8.5 bits per weight) and 8-bit float codes (fmi_flux_set_linear_f8) do not fit Q4's slots:
-// the matrix owns them (Dense::own_wq, Dense::gq).
+// LLM.int8 matrices, ggml blocks (4.5 to 8.5 bits per weight) and 8-bit float codes do not fit Q4's slots: the matrix owns them (struct Dense),
 // so a bf16 checkpoint occupies 23.8 GB and an nf4 one 6.7 GB — no bf16 duplicate of a quantised layer is resident
 // unless the caller asks for the expanded cache (fmi_flux_set_quant_dense_cache).  The arenas are also the unit of
 // the multi-GPU weight broadcast (fmi_flux_state_*).  Activations live in a per-(B,S,T) workspace that is allocated
@@ -27,6 +26,7 @@
 
 #include "common.h"
 #include "ip_adapter.h"
+#include "quant_kinds.h"
 
 using namespace fmi;
 
@@ -37,29 +37,21 @@ struct Arena {
   DeviceBuffer base;
   size_t bytes = 0;  // layout size (known before the arena is allocated)
 };
-// PS_GGUF0 + ggml type id (2 .. 14): the part is resident as ggml blocks (fmi_flux_set_linear_gguf), in Dense::gq
-// PS_F8_E4M3 / PS_F8_E5M2: the part is resident as OCP e4m3fn / e5m2 codes (fmi_flux_set_linear_f8), in Dense::gq too, its scale in Dense::gscale
-enum PartState : uint8_t { PS_UNSET = 0, PS_FP4 = 1, PS_NF4 = 2, PS_INT8 = 3, PS_GGUF0 = 16, PS_GGUF_END = 48, PS_F8_E4M3 = 48, PS_F8_E5M2 = 49, PS_DENSE = 100 };
-inline bool is_gguf(int state) { return state >= PS_GGUF0 && state < PS_GGUF_END; }
-inline bool is_f8(int state) { return state == PS_F8_E4M3 || state == PS_F8_E5M2; }
-// kinds that have no fused dequant-GEMM and live in Dense::gq: always expanded, once or per call
-inline bool is_codes(int state) { return is_gguf(state) || is_f8(state); }
-
 struct Dense {  // one (possibly fused) Linear: W (N,K) bf16 row-major, bias (N) bf16
   bf16_t* w = nullptr;  // null until the arena `ar` is allocated
   bf16_t* b = nullptr;  // BASE arena
   int N = 0, K = 0;
   int ar = AR_BASE;
   size_t w_off = 0, q_off = 0, am_off = 0;  // byte offsets in `ar` / in Q4 (packed codes, absmax sized for blocksize 64)
-  // quantised form, used instead of w when q_type != 0 (set by finalize(): every part holds the same kind)
-  uint8_t* wq = nullptr;   // Q4 arena (4-bit) or own_wq (int8): what the kernels read
+  // Quantised form, used instead of w when q_type != 0: the PartState (quant_kinds.h) that every part holds, set by finalize().  Where each kind lives:
+  //   fp4, nf4     wq / absmax = the matrix's slot of the Q4 arena: packed codes (N, K / 2) + f32 absmax per blocksize weights
+  //   LLM.int8     wq / absmax = own_wq / own_absmax: int8 (N, K) + SCB (N), allocated with the matrix's first int8 part and kept from then on
+  //   gguf, f8     gq[part]: the part's ggml blocks or 8-bit float codes, one allocation per part (the parts of one matrix may differ in type and in
+  //                scale until finalize() decides; empty on a matrix that never saw such a part), gscale[part]: the f8 scale (1 for ggml blocks)
+  uint8_t* wq = nullptr;  // what the kernels read
   float* absmax = nullptr;
-  DeviceBuffer own_wq, own_absmax;  // int8 matrices own their storage (1 B per weight: they do not fit the 4-bit arena's slots)
-  int q_type = 0, q_blocksize = 0;  // 1 fp4, 2 nf4, 3 LLM.int8 (wq = int8 (N,K), absmax = SCB (N)), PS_GGUF0 + ggml type / PS_F8_* (blocks or codes in gq; wq stays null)
-  // ggml blocks of the parts loaded with fmi_flux_set_linear_gguf, one allocation per part (5 to 8.5 bits per weight: they do not fit the 4-bit
-  // arena's slots, and the parts of one matrix may differ in type until finalize() decides); empty on a matrix that never saw such a part
-  // The 8-bit float codes of fmi_flux_set_linear_f8 live here as well, with one scale per part in gscale (the parts' scales may differ: the expansion
-  // runs per part).
+  DeviceBuffer own_wq, own_absmax;
+  int q_type = 0, q_blocksize = 0;
   std::vector<DeviceBuffer> gq;
   std::vector<float> gscale;
   // optional fp8 form (fmi_flux_quantize_fp8): e4m3 (N,K) + per-output-channel f32 scale, used instead of w
@@ -428,33 +420,51 @@ void resolve_base_and_names(fmi_flux* m) {
   }
 }
 
-// 4-bit / int8 rows [r0, r0+rows) of `d` -> bf16 rows of d.w (the stand-alone kernels of bnb_dequant.hip)
-int dequant_rows(Dense& d, int r0, int rows, int kind, int blocksize, hipStream_t s) {
-  const int64_t n = (int64_t)rows * d.K;
-  if (n >= (1ll << 31)) return fail(FMI_ERR_UNSUPPORTED, "flux: quantised linear too large");
-  bf16_t* dst = d.w + (size_t)r0 * d.K;
-  if (kind == PS_INT8) return launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(d.wq) + (size_t)r0 * d.K, d.absmax + r0, dst, d.K, n, s);
-  const uint8_t* src = d.wq + (size_t)r0 * d.K / 2;
-  const float* am = d.absmax + (size_t)r0 * d.K / blocksize;
-  if (kind == PS_NF4) dequantize_blockwise_bf16_nf4(nullptr, src, am, dst, blocksize, (int)n, s);
-  else dequantize_blockwise_bf16_fp4(nullptr, src, am, dst, blocksize, (int)n, s);
+// Rows [r0, r0 + rows) of a matrix whose codes are in wq / absmax (fp4, nf4, int8) -> the same rows of `image`, an (N, K) bf16 image of the matrix (d.w or
+// the scratch): one launch per chunk of at most 2^28 elements (the dequant kernels index in 32 bits; chunk starts stay multiples of the quantisation
+// block: K % 64 == 0).  Every FLUX block matrix is a single chunk.
+int expand_wq_rows(Dense& d, int r0, int rows, int kind, int blocksize, bf16_t* image, hipStream_t s) {
+  const int chunk = std::max(64, (int)std::min<int64_t>(rows, ((1ll << 28) / d.K) / 64 * 64));
+  for (const int end = r0 + rows; r0 < end; r0 += chunk) {
+    const size_t e0 = (size_t)r0 * d.K;
+    const void* src = kind == PS_INT8 ? d.wq + e0 : d.wq + e0 / 2;
+    const float* scales = kind == PS_INT8 ? d.absmax + r0 : d.absmax + e0 / blocksize;
+    FMI_TRY(dequant_to_bf16(kind, blocksize, src, scales, 0.f, d.K, (int64_t)std::min(chunk, end - r0) * d.K, image + e0, s));
+  }
+  return FMI_OK;
+}
+// Part `part` of `d`, resident as any quantised kind, -> its bf16 rows of `image`
+int expand_part(Dense& d, int part, bf16_t* image, hipStream_t s) {
+  const Dense::Part& pt = d.parts[part];
+  if (!is_codes(pt.state)) return expand_wq_rows(d, pt.r0, pt.rows, pt.state, pt.blocksize, image, s);
+  return dequant_to_bf16(pt.state, 0, d.gq[part].ptr, nullptr, d.gscale[part], d.K, (int64_t)pt.rows * d.K, image + (size_t)pt.r0 * d.K, s);
+}
+// A matrix of one kind (q_type != 0) -> `image`.  fp4 / nf4 / int8 in one pass over the whole matrix; ggml blocks and 8-bit float codes part by part (their
+// types and scales are per part).
+int expand_matrix(Dense& d, bf16_t* image, hipStream_t s) {
+  if (!is_codes(d.q_type)) return expand_wq_rows(d, 0, d.N, d.q_type, d.q_blocksize, image, s);
+  for (int i = 0; i < (int)d.parts.size(); ++i) FMI_TRY(expand_part(d, i, image, s));
   return FMI_OK;
 }
 
-// ggml blocks / 8-bit float codes of part `part` of `d` -> its bf16 rows of `dst` (a (N, K) image of the matrix: d.w or the scratch)
-int expand_gguf_part(Dense& d, int part, bf16_t* dst, hipStream_t s) {
-  const Dense::Part& pt = d.parts[part];
-  if (is_f8(pt.state))
-    return fmi_f8_dequantize(pt.state == PS_F8_E4M3 ? 1 : 2, d.gq[part].ptr, (int64_t)pt.rows * d.K, d.gscale[part], dst + (size_t)pt.r0 * d.K, FMI_BF16, s);
-  return fmi_gguf_dequantize(pt.state - PS_GGUF0, d.gq[part].ptr, (int64_t)pt.rows * d.K, dst + (size_t)pt.r0 * d.K, FMI_BF16, s);
+// The tail of every setter that has put the weight of part `part` of `d` in place as `state`: a part that stops being ggml blocks / 8-bit float codes gives
+// up its buffer, and whatever was derived from the matrix's earlier contents (its cached expansion, finalize()'s decision) goes.
+void part_loaded(fmi_flux* m, Dense& d, int part, int state, int blocksize, const std::string& wname) {
+  d.parts[part].state = (uint8_t)state, d.parts[part].blocksize = blocksize;
+  if (!is_codes(state) && part < (int)d.gq.size()) d.gq[part].reset();
+  m->dense_ready.erase(&d);
+  m->finalized = false;
+  m->missing.erase(wname);
 }
-int expand_gguf(Dense& d, bf16_t* dst, hipStream_t s) {
-  for (int i = 0; i < (int)d.parts.size(); ++i) FMI_TRY(expand_gguf_part(d, i, dst, s));
-  return FMI_OK;
-}
-// a part stops being resident as ggml blocks / 8-bit float codes (another setter takes it over)
-void drop_gguf_part(Dense& d, int part) {
-  if (part < (int)d.gq.size()) d.gq[part].reset();
+
+// part `part` of `d` is resident as plain bf16 rows of d.w (what a LoRA merge patches and fmi_flux_get_tensor reads): a Linear outside the fused matrices,
+// or a dense part of a matrix that finalize() left dense (such a part's arena exists: every path that marks a part dense has allocated it)
+bool part_is_plain(const Dense& d, int part) { return d.ar == AR_BASE || (d.q_type == 0 && d.parts[part].state == PS_DENSE && d.w); }
+// the device bytes a matrix owns outside the arenas: its LLM.int8 weight and SCB, its parts' ggml blocks / 8-bit float codes
+size_t resident_code_bytes(const Dense& d) {
+  size_t b = d.own_wq ? (size_t)d.N * d.K + (size_t)d.N * 4 : 0;
+  for (const DeviceBuffer& g : d.gq) b += g.bytes();
+  return b;
 }
 
 // Decide how every fused matrix is multiplied: all parts the same quantised kind -> that kind (packed form only);
@@ -479,8 +489,7 @@ int finalize(fmi_flux* m) {
       for (int i = 0; i < (int)d->parts.size(); ++i) {
         auto& pt = d->parts[i];
         if (pt.state == PS_DENSE) continue;
-        if (is_codes(pt.state)) FMI_TRY(expand_gguf_part(*d, i, d->w, nullptr));
-        else FMI_TRY(dequant_rows(*d, pt.r0, pt.rows, pt.state, pt.blocksize, nullptr));
+        FMI_TRY(expand_part(*d, i, d->w, nullptr));
         pt.state = PS_DENSE, pt.blocksize = 0;
       }
       FMI_HIP_TRY(hipDeviceSynchronize());
@@ -667,7 +676,7 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
   bool scratch = false;
   for (int i = 0; i < n && i < 2; ++i)
     if (dn[i] && p[i].q_type && !is_codes(p[i].q_type) && m->quant_mode != 1 && m->quant_mode != 2)
-      scratch = scratch || p[i].M > (p[i].q_type == 3 ? INT8_FUSED_MAX_ROWS : Q4_FUSED_MAX_ROWS);
+      scratch = scratch || p[i].M > (p[i].q_type == PS_INT8 ? INT8_FUSED_MAX_ROWS : Q4_FUSED_MAX_ROWS);
   // A matrix of 2^31 or more weights (the fused modulation matrix of FLUX.1: 344 D x D = 3.2e9) never goes through the scratch —
   // the stand-alone dequant launchers count elements in 32 bits and the scratch is sized for the block matrices — it stays on
   // the fused dequant-GEMM kernels at any row count (8 prompts x 50 steps = 400 rows of the modulation precompute).
@@ -694,11 +703,7 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
     if (once) {
       FMI_TRY(ensure_arena(m, d->ar));
       if (!m->dense_ready.count(d)) {
-        // expanded once, in row chunks of at most 2^28 elements (chunk starts stay multiples of the quantisation block: K % 64 == 0)
-        const int chunk = std::max(64, (int)std::min<int64_t>(d->N, ((1ll << 28) / d->K) / 64 * 64));  // (the dequant kernels index in 32 bits: stay well below 2^31)
-        if (gguf) FMI_TRY(expand_gguf(*d, d->w, s));
-        else
-          for (int r0 = 0; r0 < d->N; r0 += chunk) FMI_TRY(dequant_rows(*d, r0, std::min(chunk, d->N - r0), d->q_type, d->q_blocksize, s));
+        FMI_TRY(expand_matrix(*d, d->w, s));
         m->dense_ready.insert(d);
       }
       p[i].W = d->w;
@@ -709,10 +714,7 @@ int densify(fmi_flux* m, GemmProblem* p, Dense* const* dn, int n, hipStream_t s)
         for (int k = 0; k < 2; ++k) FMI_HIP_TRY(m->wscratch[k].alloc(want * sizeof(bf16_t)));
       }
       bf16_t* ws_i = m->wscratch[i].as<bf16_t>();
-      if (gguf) FMI_TRY(expand_gguf(*d, ws_i, s));
-      else if (p[i].q_type == 3) FMI_TRY(launch_dequant_int8_scb_bf16(reinterpret_cast<const int8_t*>(p[i].Wq), p[i].absmax, ws_i, p[i].K, (int64_t)elems, s));
-      else if (p[i].q_type == 2) dequantize_blockwise_bf16_nf4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
-      else dequantize_blockwise_bf16_fp4(nullptr, p[i].Wq, p[i].absmax, ws_i, p[i].q_blocksize, (int)elems, s);
+      FMI_TRY(expand_matrix(*d, ws_i, s));
       p[i].W = ws_i;
     }
     p[i].ldw = p[i].K;
@@ -1594,22 +1596,45 @@ extern "C" int fmi_flux_set_tensor(fmi_flux* m, const char* name, const void* da
     dst = d.d->w + (size_t)d.d->parts[d.part].r0 * d.d->K;
   }
   FMI_TRY(upload_as_bf16(data, dtype, numel, (bf16_t*)dst));
-  if (d.d && !d.bias) {
-    d.d->parts[d.part].state = PS_DENSE, d.d->parts[d.part].blocksize = 0;
-    drop_gguf_part(*d.d, d.part);
-    m->dense_ready.erase(d.d);
-    m->finalized = false;
-  }
-  m->missing.erase(name);
+  if (d.d && !d.bias) part_loaded(m, *d.d, d.part, PS_DENSE, 0, name);
+  else m->missing.erase(name);
   return FMI_OK;
 }
 
+// ---- The quantised setters: one head (the shared refusals and the lookup), the setter's own storage, one tail (part_loaded).
 namespace {
-// a quantised Linear that is not a fused GEMM matrix (embedders, final projection): expanded once into the BASE arena
-template <typename F>
-int expand_small(const Dest& dst, const void* q, size_t qbytes, const float* sc, size_t scbytes, F&& run) {
-  bf16_t* out = dst.d->w + (size_t)dst.d->parts[dst.part].r0 * dst.d->K;
-  return with_staged_pair(q, qbytes, sc, scbytes, [&](void* dq, void* ds) { return run(dq, (const float*)ds, out); });
+struct LinearSlot {  // the Linear `prefix` names: its weight's name, where it lands, and its part of the (fused) matrix
+  std::string wname;
+  const Dest* dst = nullptr;
+  Dense* d = nullptr;
+  Dense::Part* pt = nullptr;
+};
+// The refusals the setters share, in their order: of the handle (null_arg: one of the setter's pointers is null; q8: how it words the 8-bit modes), then own()
+// — the setter's checks of its own arguments — then the lookup: a Linear of this model, no LoRA adapter merged into it, of the stated shape.
+template <class Own>
+int setter_head(fmi_flux* m, const std::string& fn, bool null_arg, const char* q8, const char* prefix, int out_features, int in_features, Own&& own, LinearSlot* t) {
+  if (null_arg) return fail(FMI_ERR_INVALID, fn + ": null argument");
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, fn + ": a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
+  if (m->fp8) return fail(FMI_ERR_STATE, fn + ": the model was quantised to " + q8);
+  FMI_TRY(own());
+  FMI_TRY(use_device(m));
+  t->wname = std::string(prefix) + ".weight";
+  auto it = m->names.find(t->wname);
+  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, fn + ": unknown linear '" + prefix + "'");
+  for (const auto& ad : m->loras)
+    if (ad.second.pairs.count(t->wname)) return fail(FMI_ERR_STATE, fn + ": " + t->wname + " has LoRA adapters merged into it; remove the adapters first");
+  t->dst = &it->second, t->d = it->second.d, t->pt = &t->d->parts[it->second.part];
+  if (t->dst->rows != out_features || t->dst->cols != in_features) return fail(FMI_ERR_INVALID, fn + ": shape mismatch for " + t->wname);
+  return FMI_OK;
+}
+// a quantised Linear that is not a fused GEMM matrix (embedders, final projection): staged on the device and expanded, once, into its rows of the BASE arena
+int expand_small(fmi_flux* m, const LinearSlot& t, int kind, int blocksize, const void* q, size_t qbytes, const float* sc, size_t scbytes) {
+  const Dense& d = *t.d;
+  FMI_TRY(with_staged_pair(q, qbytes, sc, scbytes, [&](void* dq, void* ds) {
+    return dequant_to_bf16(kind, blocksize, dq, (const float*)ds, 0.f, d.K, (int64_t)t.pt->rows * d.K, d.w + (size_t)t.pt->r0 * d.K, nullptr);
+  }));
+  m->missing.erase(t.wname);
+  return FMI_OK;
 }
 }  // namespace
 
@@ -1617,42 +1642,24 @@ int expand_small(const Dest& dst, const void* q, size_t qbytes, const float* sc,
 // first) + f32 absmax per `blocksize` weights.  Block linears and modulation linears keep this form (Q4 arena).
 extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const uint8_t* packed, const float* absmax, int blocksize,
                                         int quant_type, int out_features, int in_features) {
-  if (!m || !prefix || !packed || !absmax) return fail(FMI_ERR_INVALID, "set_linear_bnb4: null argument");
-  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
-  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_bnb4: the model was quantised to fp8");
-  if (quant_type != 1 && quant_type != 2) return fail(FMI_ERR_INVALID, "set_linear_bnb4: quant_type must be 1 (fp4) or 2 (nf4)");
-  if (blocksize % 64 || blocksize <= 0 || in_features % blocksize)
-    return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: blocksize must be a multiple of 64 dividing in_features");
-  FMI_TRY(use_device(m));
-  const std::string wname = std::string(prefix) + ".weight";
-  auto it = m->names.find(wname);
-  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_bnb4: unknown linear '") + prefix + "'");
-  for (const auto& ad : m->loras)
-    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_bnb4: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
-  const Dest& dst = it->second;
-  Dense* d = dst.d;
-  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_bnb4: shape mismatch for " + wname);
+  LinearSlot t;
+  FMI_TRY(setter_head(m, "set_linear_bnb4", !m || !prefix || !packed || !absmax, "fp8", prefix, out_features, in_features, [&] {
+    if (quant_type != 1 && quant_type != 2) return fail(FMI_ERR_INVALID, "set_linear_bnb4: quant_type must be 1 (fp4) or 2 (nf4)");
+    if (blocksize % 64 || blocksize <= 0 || in_features % blocksize)
+      return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: blocksize must be a multiple of 64 dividing in_features");
+    return (int)FMI_OK;
+  }, &t));
+  Dense* d = t.d;
   const size_t n = (size_t)out_features * in_features;
   if (d->ar == AR_BASE) {
     if (n >= (1ull << 31)) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: linear too large");
-    FMI_TRY(expand_small(dst, packed, n / 2, absmax, n / blocksize * 4, [&](void* dq, const float* da, bf16_t* out) {
-      if (quant_type == 2) dequantize_blockwise_bf16_nf4(nullptr, (const uint8_t*)dq, da, out, blocksize, (int)n, nullptr);
-      else dequantize_blockwise_bf16_fp4(nullptr, (const uint8_t*)dq, da, out, blocksize, (int)n, nullptr);
-      return (int)FMI_OK;
-    }));
-    m->missing.erase(wname);
-    return FMI_OK;
+    return expand_small(m, t, quant_type, blocksize, packed, n / 2, absmax, n / blocksize * 4);
   }
   if (d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "set_linear_bnb4: this fused projection already holds int8 parts");
   FMI_TRY(ensure_arena(m, AR_Q4));
-  Dense::Part& pt = d->parts[dst.part];
-  FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K / 2, packed, n / 2, hipMemcpyDefault));
-  FMI_HIP_TRY(hipMemcpy(d->absmax + (size_t)pt.r0 * d->K / blocksize, absmax, n / blocksize * 4, hipMemcpyDefault));
-  pt.state = (uint8_t)quant_type, pt.blocksize = blocksize;
-  drop_gguf_part(*d, dst.part);
-  m->dense_ready.erase(d);
-  m->finalized = false;
-  m->missing.erase(wname);
+  FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)t.pt->r0 * d->K / 2, packed, n / 2, hipMemcpyDefault));
+  FMI_HIP_TRY(hipMemcpy(d->absmax + (size_t)t.pt->r0 * d->K / blocksize, absmax, n / blocksize * 4, hipMemcpyDefault));
+  part_loaded(m, *d, t.dst->part, quant_type, blocksize, t.wname);
   return FMI_OK;
 }
 
@@ -1660,26 +1667,11 @@ extern "C" int fmi_flux_set_linear_bnb4(fmi_flux* m, const char* prefix, const u
 // forward = dequantize_8bit (w * SCB[row] / 127, dequant.cu:205-214) then matmul (mod.rs:293-300):
 // fused matrices keep the int8 weight and are expanded right before their GEMM (or once, with the dense cache).
 extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const int8_t* weight, const float* scb, int out_features, int in_features) {
-  if (!m || !prefix || !weight || !scb) return fail(FMI_ERR_INVALID, "set_linear_int8: null argument");
-  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_int8: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
-  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_int8: the model was quantised to fp8");
-  FMI_TRY(use_device(m));
-  const std::string wname = std::string(prefix) + ".weight";
-  auto it = m->names.find(wname);
-  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_int8: unknown linear '") + prefix + "'");
-  for (const auto& ad : m->loras)
-    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_int8: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
-  const Dest& dst = it->second;
-  Dense* d = dst.d;
-  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_int8: shape mismatch for " + wname);
-  const int64_t n = (int64_t)out_features * in_features;
-  if (d->ar == AR_BASE) {
-    FMI_TRY(expand_small(dst, weight, (size_t)n, scb, (size_t)out_features * 4, [&](void* dq, const float* ds, bf16_t* out) {
-      return launch_dequant_int8_scb_bf16((const int8_t*)dq, ds, out, in_features, n, nullptr);
-    }));
-    m->missing.erase(wname);
-    return FMI_OK;
-  }
+  LinearSlot t;
+  FMI_TRY(setter_head(m, "set_linear_int8", !m || !prefix || !weight || !scb, "fp8", prefix, out_features, in_features, [] { return (int)FMI_OK; }, &t));
+  Dense* d = t.d;
+  const size_t n = (size_t)out_features * in_features;
+  if (d->ar == AR_BASE) return expand_small(m, t, PS_INT8, 0, weight, n, scb, (size_t)out_features * 4);
   for (auto& pt : d->parts)
     if (pt.state == PS_FP4 || pt.state == PS_NF4) return fail(FMI_ERR_UNSUPPORTED, "set_linear_int8: this fused projection already holds 4-bit parts");
   if (!d->own_wq) {  // the matrix changes only once both blocks exist and are zeroed
@@ -1691,113 +1683,64 @@ extern "C" int fmi_flux_set_linear_int8(fmi_flux* m, const char* prefix, const i
     d->own_wq = std::move(wq), d->own_absmax = std::move(sc);
     d->wq = d->own_wq.as<uint8_t>(), d->absmax = d->own_absmax.as<float>();
   }
-  Dense::Part& pt = d->parts[dst.part];
-  FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)pt.r0 * d->K, weight, n, hipMemcpyDefault));
-  FMI_HIP_TRY(hipMemcpy(d->absmax + pt.r0, scb, (size_t)out_features * 4, hipMemcpyDefault));
-  pt.state = PS_INT8, pt.blocksize = 0;
-  drop_gguf_part(*d, dst.part);
-  m->dense_ready.erase(d);
-  m->finalized = false;
-  m->missing.erase(wname);
+  FMI_HIP_TRY(hipMemcpy(d->wq + (size_t)t.pt->r0 * d->K, weight, n, hipMemcpyDefault));
+  FMI_HIP_TRY(hipMemcpy(d->absmax + t.pt->r0, scb, (size_t)out_features * 4, hipMemcpyDefault));
+  part_loaded(m, *d, t.dst->part, PS_INT8, 0, t.wname);
   return FMI_OK;
 }
 
-// A Linear as ggml blocks (llama.cpp's .gguf files; gguf_dequant.hip): row-major, in_features / block_elems blocks per row.  Embedders, the final layer
-// and the modulation linears are expanded into their bf16 rows here (the fused modulation matrix never goes through densify()'s scratch, and as dense
-// rows it keeps the bf16 model's GEMV); the parts of a fused block matrix keep their blocks (Dense::gq) and finalize() / densify() decide.
-extern "C" int fmi_flux_set_linear_gguf(fmi_flux* m, const char* prefix, int ggml_type, const void* data, int out_features, int in_features) {
-  if (!m || !prefix || !data) return fail(FMI_ERR_INVALID, "set_linear_gguf: null argument");
-  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_gguf: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
-  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_gguf: the model was quantised to 8 bits");
-  int be = 0, bb = 0;
-  FMI_TRY(fmi_gguf_block_info(ggml_type, &be, &bb));
-  if (in_features <= 0 || out_features <= 0 || in_features % be)
-    return fail(FMI_ERR_INVALID, "set_linear_gguf: in_features must be a positive multiple of the block's " + std::to_string(be) + " elements");
-  FMI_TRY(use_device(m));
-  const std::string wname = std::string(prefix) + ".weight";
-  auto it = m->names.find(wname);
-  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_gguf: unknown linear '") + prefix + "'");
-  for (const auto& ad : m->loras)
-    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_gguf: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
-  const Dest& dst = it->second;
-  Dense* d = dst.d;
-  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_gguf: shape mismatch for " + wname);
-  const int64_t n = (int64_t)out_features * in_features;
-  const size_t bytes = (size_t)(n / be) * bb;
-  DeviceBuffer blocks;
-  FMI_HIP_TRY(blocks.alloc(bytes));
-  FMI_HIP_TRY(hipMemcpy(blocks.ptr, data, bytes, hipMemcpyDefault));
-  Dense::Part& pt = d->parts[dst.part];
-  if (d->ar == AR_BASE || d->ar == AR_MOD) {
-    FMI_TRY(ensure_arena(m, d->ar));
-    FMI_TRY(fmi_gguf_dequantize(ggml_type, blocks.ptr, n, d->w + (size_t)pt.r0 * d->K, FMI_BF16, nullptr));
-    FMI_HIP_TRY(hipDeviceSynchronize());
-    if (d->ar == AR_MOD) {
-      pt.state = PS_DENSE, pt.blocksize = 0;
-      m->dense_ready.erase(d);
-      m->finalized = false;
-    }
-    m->attn_scales_valid = false;
-    m->missing.erase(wname);
-    return FMI_OK;
-  }
-  if (d->gq.size() < d->parts.size()) d->gq.resize(d->parts.size());
-  FMI_HIP_TRY(hipDeviceSynchronize());  // (a replaced part's blocks may still be read by an expansion in flight)
-  d->gq[dst.part] = std::move(blocks);
-  pt.state = (uint8_t)(PS_GGUF0 + ggml_type), pt.blocksize = 0;
-  m->dense_ready.erase(d);
-  m->finalized = false;
-  m->missing.erase(wname);
-  return FMI_OK;
-}
-
-// A Linear as OCP e4m3fn / e5m2 codes with one scale (single-file fp8 checkpoints; f8_dequant.hip).  As fmi_flux_set_linear_gguf: embedders, the final
-// layer and the modulation linears are expanded into their bf16 rows here; the parts of a fused block matrix keep their codes (Dense::gq) and their
-// scale (Dense::gscale), and finalize() / densify() decide.
-extern "C" int fmi_flux_set_linear_f8(fmi_flux* m, const char* prefix, int format, const void* codes, float scale, int out_features, int in_features) {
-  if (!m || !prefix || !codes) return fail(FMI_ERR_INVALID, "set_linear_f8: null argument");
-  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "set_linear_f8: a ControlNet runs in bf16 only (quantised ControlNets are out of scope)");
-  if (m->fp8) return fail(FMI_ERR_STATE, "set_linear_f8: the model was quantised to 8 bits");
-  if (format != 1 && format != 2) return fail(FMI_ERR_INVALID, "set_linear_f8: format must be 1 (OCP e4m3fn) or 2 (OCP e5m2), got " + std::to_string(format));
-  if (!std::isfinite(scale) || !(scale > 0.f)) return fail(FMI_ERR_INVALID, "set_linear_f8: scale must be finite and > 0");
-  if (in_features <= 0 || out_features <= 0) return fail(FMI_ERR_INVALID, "set_linear_f8: in_features and out_features must be positive");
-  FMI_TRY(use_device(m));
-  const std::string wname = std::string(prefix) + ".weight";
-  auto it = m->names.find(wname);
-  if (it == m->names.end() || !it->second.d) return fail(FMI_ERR_INVALID, std::string("set_linear_f8: unknown linear '") + prefix + "'");
-  for (const auto& ad : m->loras)
-    if (ad.second.pairs.count(wname)) return fail(FMI_ERR_STATE, std::string("set_linear_f8: ") + wname + " has LoRA adapters merged into it; remove the adapters first");
-  const Dest& dst = it->second;
-  Dense* d = dst.d;
-  if (dst.rows != out_features || dst.cols != in_features) return fail(FMI_ERR_INVALID, "set_linear_f8: shape mismatch for " + wname);
-  const int64_t n = (int64_t)out_features * in_features;
+namespace {
+// The two kinds that have no fused dequant-GEMM — ggml blocks, 8-bit float codes with one scale — behind the head: `bytes` of `data` go to the device.
+// Embedders, the final layer and the modulation linears are expanded into their bf16 rows here (the fused modulation matrix never goes through densify()'s
+// scratch, and as dense rows it keeps the bf16 model's GEMV); the parts of a fused block matrix keep their blocks / codes (Dense::gq) and their scale
+// (Dense::gscale), and finalize() / densify() decide.
+int set_linear_codes(fmi_flux* m, const LinearSlot& t, int kind, const void* data, size_t bytes, float scale) {
+  Dense* d = t.d;
   DeviceBuffer buf;
-  FMI_HIP_TRY(buf.alloc((size_t)n));
-  FMI_HIP_TRY(hipMemcpy(buf.ptr, codes, (size_t)n, hipMemcpyDefault));
-  Dense::Part& pt = d->parts[dst.part];
+  FMI_HIP_TRY(buf.alloc(bytes));
+  FMI_HIP_TRY(hipMemcpy(buf.ptr, data, bytes, hipMemcpyDefault));
   if (d->ar == AR_BASE || d->ar == AR_MOD) {
     FMI_TRY(ensure_arena(m, d->ar));
-    FMI_TRY(fmi_f8_dequantize(format, buf.ptr, n, scale, d->w + (size_t)pt.r0 * d->K, FMI_BF16, nullptr));
+    FMI_TRY(dequant_to_bf16(kind, 0, buf.ptr, nullptr, scale, d->K, (int64_t)t.pt->rows * d->K, d->w + (size_t)t.pt->r0 * d->K, nullptr));
     FMI_HIP_TRY(hipDeviceSynchronize());
-    if (d->ar == AR_MOD) {
-      pt.state = PS_DENSE, pt.blocksize = 0;
-      m->dense_ready.erase(d);
-      m->finalized = false;
-    }
     m->attn_scales_valid = false;
-    m->missing.erase(wname);
+    if (d->ar == AR_MOD) part_loaded(m, *d, t.dst->part, PS_DENSE, 0, t.wname);
+    else m->missing.erase(t.wname);
     return FMI_OK;
   }
   if (d->gq.size() < d->parts.size()) d->gq.resize(d->parts.size());
   if (d->gscale.size() < d->parts.size()) d->gscale.resize(d->parts.size(), 1.0f);
-  FMI_HIP_TRY(hipDeviceSynchronize());  // (a replaced part's codes may still be read by an expansion in flight)
-  d->gq[dst.part] = std::move(buf);
-  d->gscale[dst.part] = scale;
-  pt.state = (uint8_t)(format == 1 ? PS_F8_E4M3 : PS_F8_E5M2), pt.blocksize = 0;
-  m->dense_ready.erase(d);
-  m->finalized = false;
-  m->missing.erase(wname);
+  FMI_HIP_TRY(hipDeviceSynchronize());  // (a replaced part's blocks / codes may still be read by an expansion in flight)
+  d->gq[t.dst->part] = std::move(buf);
+  d->gscale[t.dst->part] = scale;
+  part_loaded(m, *d, t.dst->part, kind, 0, t.wname);
   return FMI_OK;
+}
+}  // namespace
+
+// A Linear as ggml blocks (llama.cpp's .gguf files; gguf_dequant.hip): row-major, in_features / block_elems blocks per row.
+extern "C" int fmi_flux_set_linear_gguf(fmi_flux* m, const char* prefix, int ggml_type, const void* data, int out_features, int in_features) {
+  LinearSlot t;
+  int be = 0, bb = 0;
+  FMI_TRY(setter_head(m, "set_linear_gguf", !m || !prefix || !data, "8 bits", prefix, out_features, in_features, [&] {
+    FMI_TRY(fmi_gguf_block_info(ggml_type, &be, &bb));
+    if (in_features <= 0 || out_features <= 0 || in_features % be)
+      return fail(FMI_ERR_INVALID, "set_linear_gguf: in_features must be a positive multiple of the block's " + std::to_string(be) + " elements");
+    return (int)FMI_OK;
+  }, &t));
+  return set_linear_codes(m, t, PS_GGUF0 + ggml_type, data, (size_t)((int64_t)out_features * in_features / be) * bb, 1.0f);
+}
+
+// A Linear as OCP e4m3fn / e5m2 codes with one scale (single-file fp8 checkpoints; f8_dequant.hip): row-major, one code per weight.
+extern "C" int fmi_flux_set_linear_f8(fmi_flux* m, const char* prefix, int format, const void* codes, float scale, int out_features, int in_features) {
+  LinearSlot t;
+  FMI_TRY(setter_head(m, "set_linear_f8", !m || !prefix || !codes, "8 bits", prefix, out_features, in_features, [&] {
+    if (format != 1 && format != 2) return fail(FMI_ERR_INVALID, "set_linear_f8: format must be 1 (OCP e4m3fn) or 2 (OCP e5m2), got " + std::to_string(format));
+    if (!std::isfinite(scale) || !(scale > 0.f)) return fail(FMI_ERR_INVALID, "set_linear_f8: scale must be finite and > 0");
+    if (in_features <= 0 || out_features <= 0) return fail(FMI_ERR_INVALID, "set_linear_f8: in_features and out_features must be positive");
+    return (int)FMI_OK;
+  }, &t));
+  return set_linear_codes(m, t, format == 1 ? PS_F8_E4M3 : PS_F8_E5M2, codes, (size_t)out_features * in_features, scale);
 }
 
 extern "C" int fmi_flux_missing_count(const fmi_flux* m) { return m ? m->missing.count() : 0; }
@@ -1808,10 +1751,7 @@ extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
   b += m->cn_samples.bytes() + m->cn_cx.bytes() + m->cn_cond_bf.bytes();  // (a ControlNet's per-shape buffers; 0 on any other handle)
   for (int a = 0; a < AR_COUNT; ++a)
     if (m->arena[a].base) b += m->arena[a].bytes;
-  for (const Dense* d : m->fused)
-    if (d->own_wq) b += (size_t)d->N * d->K + (size_t)d->N * 4;
-  for (const Dense* d : m->fused)
-    for (const DeviceBuffer& g : d->gq) b += g.bytes();
+  for (const Dense* d : m->fused) b += resident_code_bytes(*d);
   for (const auto& ad : m->loras)
     for (const auto& pr : ad.second.pairs) {
       const Dest& dst = m->names.at(pr.first);
@@ -1869,7 +1809,7 @@ extern "C" int fmi_flux_state_adopt(fmi_flux* m, const uint8_t* blob_host, size_
     uint32_t bs = 0;
     memcpy(&bs, o, 4);
     o += 4;
-    if (qt == 3 || d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
+    if (qt == PS_INT8 || d->own_wq) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: LLM.int8 matrices are not part of the flat weight state");
     if (is_codes(qt)) return fail(FMI_ERR_UNSUPPORTED, "state_adopt: matrices resident as ggml blocks or 8-bit float codes are not part of the flat weight state");
     d->gq.clear(), d->gscale.clear();
     d->q_type = qt, d->q_blocksize = (int)bs;
@@ -2555,7 +2495,7 @@ extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* p
   FMI_TRY(lora_enter(m, "lora_add"));
   const Dest& dst = it->second;
   const Dense* d = dst.d;
-  if (d->ar != AR_BASE && (d->q_type != 0 || d->parts[dst.part].state != PS_DENSE))
+  if (!part_is_plain(*d, dst.part))
     return fail(FMI_ERR_UNSUPPORTED, std::string("lora_add: ") + prefix + " is resident as nf4 / fp4 / LLM.int8 codes; merging into packed codes is not implemented");
   if (dst.cols % 8) return fail(FMI_ERR_UNSUPPORTED, "lora_add: in_features must be a multiple of 8");
   fmi_flux::LoraPair np;
@@ -2643,7 +2583,7 @@ extern "C" int fmi_flux_get_tensor(fmi_flux* m, const char* name, void* out, fmi
   if (m->missing.names.empty()) FMI_TRY(finalize(m));  // (a quantised part of a mixed fused matrix becomes dense rows here, as at the first evaluation)
   const void* src = d.ptr;
   if (d.d && !d.bias) {
-    if (d.d->ar != AR_BASE && (d.d->q_type != 0 || d.d->parts[d.part].state != PS_DENSE || !d.d->w))
+    if (!part_is_plain(*d.d, d.part))
       return fail(FMI_ERR_UNSUPPORTED, std::string("flux_get_tensor: ") + name + " is resident only as packed nf4 / fp4 / LLM.int8 codes");
     src = d.d->w + (size_t)d.d->parts[d.part].r0 * d.d->K;  // the row range of the fused matrix
   }

@@ -9,6 +9,7 @@
 // lane-per-key kernel — L <= 512 keys, 64 heads: 0.1 TFLOP per prompt, not worth an MFMA pipeline.
 // What the vision towers (vision_encoders.hip) run as well — the layer kernels, the handle frame, the encoder layer — is in encoder_common.h.
 #include "encoder_common.h"
+#include "quant_kinds.h"
 
 namespace fmi {
 namespace {
@@ -191,9 +192,7 @@ extern "C" int fmi_t5_set_linear_bnb4(fmi_t5* m, const char* prefix, const uint8
   std::string wname;
   FMI_TRY(t5_linear_dest(m, "t5_set_linear_bnb4", prefix, out_features, in_features, &d, &wname));
   const int rc = with_staged_pair(packed, (size_t)n / 2, absmax, (size_t)(n / blocksize) * sizeof(float), [&](void* dq, void* da) {
-    if (quant_type == 2) dequantize_blockwise_bf16_nf4(nullptr, (const uint8_t*)dq, (const float*)da, d.ptr, blocksize, (int)n, nullptr);
-    else dequantize_blockwise_bf16_fp4(nullptr, (const uint8_t*)dq, (const float*)da, d.ptr, blocksize, (int)n, nullptr);
-    return (int)FMI_OK;
+    return dequant_to_bf16(quant_type, blocksize, dq, (const float*)da, 0.f, in_features, n, d.ptr, nullptr);
   });
   if (rc == FMI_ERR_HIP) return fail(FMI_ERR_HIP, std::string("t5_set_linear_bnb4: ") + fmi_last_error());
   if (rc) return rc;
@@ -208,7 +207,7 @@ extern "C" int fmi_t5_set_linear_int8(fmi_t5* m, const char* prefix, const int8_
   std::string wname;
   FMI_TRY(t5_linear_dest(m, "t5_set_linear_int8", prefix, out_features, in_features, &d, &wname));
   const int rc = with_staged_pair(weight, (size_t)n, scb, (size_t)out_features * sizeof(float), [&](void* dw, void* ds) {
-    return launch_dequant_int8_scb_bf16((const int8_t*)dw, (const float*)ds, d.ptr, in_features, n, nullptr);
+    return dequant_to_bf16(PS_INT8, 0, dw, (const float*)ds, 0.f, in_features, n, d.ptr, nullptr);
   });
   if (rc == FMI_ERR_HIP) return fail(FMI_ERR_HIP, std::string("t5_set_linear_int8: ") + fmi_last_error());
   if (rc) return rc;

@@ -49,6 +49,23 @@ def _tensor_arg(t):
     return C.c_void_p(t.data_ptr()), _TORCH_DT[t.dtype], tuple(t.shape), t
 
 
+def _linear_arg(x, dtype, raw=False, views=()):
+    """(keepalive, pointer, nbytes) of one array of a quantised Linear, host or device (the C side copies with hipMemcpyDefault), checked to be `dtype`.
+    A torch tensor, made contiguous (its values cast for the f32 scales; a dtype in `views` reinterpreted), or a numpy array / sequence converted to the
+    dtype; raw: anything with the buffer protocol instead, taken as the bytes it holds."""
+    if isinstance(x, torch.Tensor):
+        keep = x.to(torch.float32).contiguous() if dtype == torch.float32 else x.contiguous()
+        if keep.dtype in views:
+            keep = keep.view(dtype)
+        assert keep.dtype == dtype
+        return keep, C.c_void_p(keep.data_ptr()), keep.numel() * keep.element_size()
+    if not raw:
+        keep = np.ascontiguousarray(x, {torch.uint8: np.uint8, torch.int8: np.int8, torch.float32: np.float32}[dtype])
+    else:
+        keep = np.ascontiguousarray(x).view(np.uint8).reshape(-1) if isinstance(x, np.ndarray) else np.frombuffer(x, np.uint8)
+    return keep, C.c_void_p(keep.ctypes.data), keep.nbytes
+
+
 def _as_f32(t):
     return np.asarray(t, np.float32) if isinstance(t, np.ndarray) else t.to(torch.float32)
 
@@ -352,38 +369,20 @@ class FluxModel:
 
     def set_linear_bnb4(self, prefix: str, packed, absmax, blocksize: int, quant_type: str, out_features: int, in_features: int):
         q = {"fp4": 1, "nf4": 2}[quant_type]
-        if isinstance(packed, torch.Tensor):  # host or device tensors: the C side copies with hipMemcpyDefault
-            pk, am = packed.contiguous(), absmax.to(torch.float32).contiguous()
-            assert pk.dtype == torch.uint8
-            pp, ap = C.c_void_p(pk.data_ptr()), C.c_void_p(am.data_ptr())
-        else:
-            pk = np.ascontiguousarray(packed, np.uint8)
-            am = np.ascontiguousarray(absmax, np.float32)
-            pp, ap = C.c_void_p(pk.ctypes.data), C.c_void_p(am.ctypes.data)
+        pk, pp, _ = _linear_arg(packed, torch.uint8)
+        am, ap, _ = _linear_arg(absmax, torch.float32)
         L.check(self.lib.fmi_flux_set_linear_bnb4(self.h, prefix.encode(), pp, ap, blocksize, q, out_features, in_features), self.lib)
 
     def set_linear_int8(self, prefix: str, weight, scb, out_features: int, in_features: int):
         """LLM.int8 linear (BnbLinear::Int8): weight int8 (out,in), SCB f32 (out)."""
-        if isinstance(weight, torch.Tensor):
-            w, sc = weight.contiguous(), scb.to(torch.float32).contiguous()
-            assert w.dtype == torch.int8
-            wp, sp = C.c_void_p(w.data_ptr()), C.c_void_p(sc.data_ptr())
-        else:
-            w = np.ascontiguousarray(weight, np.int8)
-            sc = np.ascontiguousarray(scb, np.float32)
-            wp, sp = C.c_void_p(w.ctypes.data), C.c_void_p(sc.ctypes.data)
+        w, wp, _ = _linear_arg(weight, torch.int8)
+        sc, sp, _ = _linear_arg(scb, torch.float32)
         L.check(self.lib.fmi_flux_set_linear_int8(self.h, prefix.encode(), wp, sp, out_features, in_features), self.lib)
 
     def set_linear_gguf(self, prefix: str, ggml_type: int, data, out_features: int, in_features: int):
         """A Linear as ggml blocks (llama.cpp's .gguf; include/flux_mi355x.h: fmi_flux_set_linear_gguf): row-major, in_features / block_elems blocks per
         row.  `data`: a uint8 torch tensor (host or device), or anything with the buffer protocol (numpy array, memoryview of an mmap) — not copied here."""
-        if isinstance(data, torch.Tensor):
-            keep = data.contiguous()
-            assert keep.dtype == torch.uint8
-            p, nbytes = C.c_void_p(keep.data_ptr()), keep.numel()
-        else:
-            keep = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-            p, nbytes = C.c_void_p(keep.ctypes.data), keep.size
+        keep, p, nbytes = _linear_arg(data, torch.uint8, raw=True)
         be, bb = C.c_int(), C.c_int()
         L.check(self.lib.fmi_gguf_block_info(int(ggml_type), C.byref(be), C.byref(bb)), self.lib)
         if in_features % be.value == 0 and nbytes != out_features * (in_features // be.value) * bb.value:
@@ -395,15 +394,7 @@ class FluxModel:
         """A Linear as 8-bit float codes with one scale (include/flux_mi355x.h: fmi_flux_set_linear_f8): row-major (out_features, in_features), one code per
         weight.  fmt: "e4m3" | "e5m2" (or 1 | 2).  `codes`: a torch tensor of dtype float8_e4m3fn / float8_e5m2 / uint8 (host or device), or anything with the
         buffer protocol (numpy uint8 array, memoryview of an mmap) — not copied here."""
-        if isinstance(codes, torch.Tensor):
-            keep = codes.contiguous()
-            if keep.dtype in F8_TORCH.values():
-                keep = keep.view(torch.uint8)
-            assert keep.dtype == torch.uint8
-            p, nbytes = C.c_void_p(keep.data_ptr()), keep.numel()
-        else:
-            keep = np.frombuffer(codes, np.uint8) if not isinstance(codes, np.ndarray) else np.ascontiguousarray(codes).view(np.uint8).reshape(-1)
-            p, nbytes = C.c_void_p(keep.ctypes.data), keep.size
+        keep, p, nbytes = _linear_arg(codes, torch.uint8, raw=True, views=tuple(F8_TORCH.values()))
         if nbytes != out_features * in_features:
             raise L.FmiError(f"set_linear_f8: {prefix}: {nbytes} codes for a ({out_features}, {in_features}) Linear", code=L.ERR_INVALID)
         L.check(self.lib.fmi_flux_set_linear_f8(self.h, prefix.encode(), f8_format(fmt), p, float(scale), out_features, in_features), self.lib)
