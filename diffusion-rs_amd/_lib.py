@@ -73,6 +73,14 @@ class FluxIp(C.Structure):
                 ("step_scales", C.POINTER(C.c_float))]
 
 
+SOLVER_EULER, SOLVER_HEUN, SOLVER_DPMPP_2M = 0, 1, 2  # FMI_SOLVER_*
+
+
+class FluxSolver(C.Structure):
+    """fmi_flux_solver: the integrator of fmi_flux_denoise_solver."""
+    _fields_ = [("kind", C.c_int)]
+
+
 class FluxDenoiseOptions(C.Structure):
     """fmi_flux_denoise_options: what fmi_flux_denoise_with's loop is conditioned on, every field NULL for none."""
     _fields_ = [("ctx", C.POINTER(FluxContext)), ("ctl", C.POINTER(FluxControl)), ("cfg", C.POINTER(FluxTrueCfg)), ("cache", C.POINTER(FluxStepCache)),
@@ -291,6 +299,14 @@ def _declare(lib):
     lib.fmi_ip_adapter_size_in_bytes.restype = C.c_size_t
     lib.fmi_flux_forward_ip.argtypes = [C.c_void_p, C.POINTER(FluxInputs), C.POINTER(FluxControl), C.POINTER(FluxControlNet), C.POINTER(FluxIp), C.c_void_p, C.c_void_p]
     lib.fmi_flux_denoise_ip.argtypes = head + [C.POINTER(FluxDenoiseOptions), C.POINTER(FluxControlNet), C.POINTER(FluxIp)] + loop + [C.c_void_p]
+    lib.fmi_flux_denoise_solver.argtypes = head + [C.POINTER(FluxDenoiseOptions), C.POINTER(FluxControlNet), C.POINTER(FluxIp), C.POINTER(FluxSolver)] + loop + [C.c_void_p]
+    lib.fmi_flux_solver_bytes.argtypes = [C.c_void_p]
+    lib.fmi_flux_solver_bytes.restype = C.c_size_t
+    step = [C.c_float, C.c_float, C.c_int64]  # scale, dt, n
+    lib.fmi_heun_predict.argtypes = [C.c_void_p] * 3 + step + [C.c_void_p] * 2 + blend + [C.c_float, C.c_void_p]
+    lib.fmi_heun_correct.argtypes = [C.c_void_p] * 4 + step + blend + [C.c_float, C.c_void_p]
+    lib.fmi_dpmpp_2m_step.argtypes = [C.c_void_p] * 3 + [C.c_float] * 5 + [C.c_int64, C.c_void_p] + blend + [C.c_float, C.c_void_p]
+    lib.fmi_dpmpp_2m_coefficients.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 3
     lib.fmi_ip_attention.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                      C.c_int, C.c_void_p]
     lib.fmi_cast_cols_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -395,6 +411,7 @@ EXPORTED = [
     "fmi_flux_create_controlnet", "fmi_flux_is_controlnet", "fmi_flux_forward_controlnet", "fmi_flux_denoise_controlnet", "fmi_flux_controlnet_eval", "fmi_flux_controlnet_sample", "fmi_add_scaled_rows_bf16",
     "fmi_ip_adapter_create", "fmi_ip_adapter_destroy", "fmi_ip_adapter_set_tensor", "fmi_ip_adapter_missing_count", "fmi_ip_adapter_missing_name", "fmi_ip_adapter_size_in_bytes",
     "fmi_flux_forward_ip", "fmi_flux_denoise_ip", "fmi_ip_attention",
+    "fmi_flux_denoise_solver", "fmi_flux_solver_bytes", "fmi_heun_predict", "fmi_heun_correct", "fmi_dpmpp_2m_step", "fmi_dpmpp_2m_coefficients",
     "fmi_flux_set_profiling", "fmi_flux_set_fused_qkv_relayout", "fmi_flux_phase_count", "fmi_flux_phase_name", "fmi_flux_phase_ms",
     "fmi_vae_default_config", "fmi_vae_create", "fmi_vae_destroy", "fmi_vae_set_tensor", "fmi_vae_missing_count", "fmi_vae_missing_name",
     "fmi_vae_scale_factor", "fmi_vae_shift_factor", "fmi_vae_decode", "fmi_vae_encode", "fmi_vae_mid_attention",

@@ -494,6 +494,17 @@ int launch_euler_blend(float* img, const float* pred, const float* x0, const flo
 // the true-CFG step: g = neg + scale * (pos - neg), img = img + g * dt — or, with x0 / noise / mask (all three or none), launch_euler_blend's blend of that — one pass
 int launch_euler_cfg(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0 = nullptr,
                      const float* noise = nullptr, const float* mask = nullptr, float s = 0.f);
+// the second-order solvers' updates (small_ops.hip), one pass each.  neg null: no guidance (g = pos); x0 / noise / mask all three or none, blended at time s.
+//   predictor: g1 = g, xt = blend(img + g * dt) — the state is only read;  corrector: img = blend(img + ((g1 + g) * 0.5) * dt)
+//   2M: D = img - t * g, D' = D + w * (D - hist) (w == 0: hist unread), img = blend(a * img + c * D'), hist = D
+int launch_heun_predict(const float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, float* xt, float* g1, hipStream_t stream, const float* x0,
+                        const float* noise, const float* mask, float s);
+int launch_heun_correct(float* img, const float* g1, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0,
+                        const float* noise, const float* mask, float s);
+int launch_dpmpp_2m(float* img, const float* pos, const float* neg, float scale, float t, float a, float c, float w, int64_t n, float* hist, hipStream_t stream,
+                    const float* x0, const float* noise, const float* mask, float s);
+int check_solver_schedule(const double* ts, int n_steps, const char* who);  // FMI_ERR_INVALID unless strictly decreasing inside [0, 1]
+void dpmpp_2m_coefficients(const double* ts, int i, float* a, float* c, float* w);  // step i's scalars, f64 rounded once (0 <= i < n_steps of a checked schedule)
 int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, float* out, hipStream_t stream);  // out = (1 - t) * x0 + t * noise
 int launch_add2_rows(float* y, const float* g, const float* v, int R, int B, int N, hipStream_t stream);  // y[r] = (y[r] + g[r % B]) + v[r % B] (g may be null)
 // split-K reduce: out[m][n] += gate_b[n] * (part_0 + part_1 + ... + part_{S-1} + bias[n]), the parts added in index order

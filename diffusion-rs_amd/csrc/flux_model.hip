@@ -155,6 +155,9 @@ struct fmi_flux {
   DeviceBuffer sc_x0, sc_r[2], sc_delta, sc_part, sc_sums;
   DeviceBuffer cfg_gd;  // true CFG: the guidance vector once for each half of the 2B batch, 8 floats, allocated by the first fmi_flux_denoise_cfg call
   size_t sc_elems = 0, sc_part_floats = 0;
+  // the second-order solvers (fmi_flux_denoise_solver): state-sized f32 buffers — Heun's predicted state and first slope, or 2M's history in [0].
+  // Allocated by the first solver call, regrown when a larger state comes, never touched by a loop without a solver.
+  DeviceBuffer solver_buf[2];
   double* sc_host = nullptr;  // pinned: (num, den) per sample, read by the host after the per-step synchronisation
   bool fuse_qkv_relayout = true;  // QkNorm + RoPE + head/transposed relayout in the QKV GEMM's epilogue
   // Quantised block linears (nf4 / fp4 / LLM.int8): only the packed codes are resident; small launches multiply from them
@@ -1749,6 +1752,7 @@ extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
   if (!m) return 0;
   size_t b = m->ws.base.bytes() + m->fp8_arena.bytes() + m->wscratch[0].bytes() + m->wscratch[1].bytes() + m->mod_steps_rows * ((size_t)m->n_mod * 4 + (size_t)m->D * 6);
   b += m->cn_samples.bytes() + m->cn_cx.bytes() + m->cn_cond_bf.bytes();  // (a ControlNet's per-shape buffers; 0 on any other handle)
+  b += m->solver_buf[0].bytes() + m->solver_buf[1].bytes();               // (0 until the first Heun / 2M loop)
   for (int a = 0; a < AR_COUNT; ++a)
     if (m->arena[a].base) b += m->arena[a].bytes;
   for (const Dense* d : m->fused) b += resident_code_bytes(*d);
@@ -1904,8 +1908,33 @@ static int step_cache_ensure(fmi_flux* m, int B, int rows, hipStream_t s) {
   return FMI_OK;
 }
 
+// The solver's own refusals, after validate()'s and like them before anything is launched or allocated.  Euler refuses nothing: the loop as it was.
+static int check_solver(const fmi_flux* m, const fmi_flux_denoise_options& o, const EvalPlan& p, int solver, const double* timesteps_host, int n_steps) {
+  if (solver == FMI_SOLVER_EULER) return FMI_OK;
+  if (solver != FMI_SOLVER_HEUN && solver != FMI_SOLVER_DPMPP_2M) return fail(FMI_ERR_INVALID, "flux_denoise: solver kind must be FMI_SOLVER_EULER, _HEUN or _DPMPP_2M");
+  FMI_TRY(check_solver_schedule(timesteps_host, n_steps, "flux_denoise"));
+  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the heun and dpmpp_2m solvers are not supported under sequence parallelism");
+  if (solver == FMI_SOLVER_HEUN && o.cache)
+    return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: the heun solver is not combined with the step cache (its two evaluations per step are at different times)");
+  if (solver == FMI_SOLVER_HEUN && ((int64_t)n_steps + 1) * (o.cfg ? 2 : 1) * p.Bs > 4096)
+    return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: (n_steps + 1) * B > 4096 under the heun solver (ws.tv holds 4096 rows; true CFG counts 2 B)");
+  return FMI_OK;
+}
+// The solver's buffers for a state of `elems` floats: two for Heun, one for 2M, regrown when a larger state comes.
+static int solver_ensure(fmi_flux* m, int solver, size_t elems, hipStream_t s) {
+  for (int k = 0; k < (solver == FMI_SOLVER_HEUN ? 2 : 1); ++k) {
+    DeviceBuffer& b = m->solver_buf[k];
+    if (b.bytes() >= elems * 4 && b) continue;
+    if (b) FMI_HIP_TRY(hipStreamSynchronize(s));
+    if (b.alloc(std::max<size_t>(elems, 1) * 4) != hipSuccess)
+      return fail(FMI_ERR_NOMEM, "flux_denoise: hipMalloc of a solver buffer (" + std::to_string(elems * 4) + " bytes) failed");
+  }
+  return FMI_OK;
+}
+
 // (c) of the loop, what the steps share, once per call: every step's timestep vector in ws.tv, every step's modulation vectors (*mod_steps; null where each step
-// computes its own) and txt_in(txt) (*txt_pre; likewise).
+// computes its own) and txt_in(txt) (*txt_pre; likewise).  n_steps counts the times that get a row: the loop's steps, and under Heun one more,
+// the last step's target time, so that the second evaluation of step i reads row i + 1.
 static int hoist_steps(fmi_flux* m, const fmi_flux_inputs* in, const double* timesteps_host, int n_steps, hipStream_t s, const float** mod_steps, const float** txt_pre) {
   const int B = in->B;
   // t_vec = full(1f32, B) * t_curr  (sampling.rs:35,42): all steps' vectors uploaded once
@@ -1973,30 +2002,49 @@ struct IpRun {
   const fmi_ip_adapter* a;
   std::vector<float> c;
 };
+// solver: FMI_SOLVER_* (DESIGN.md 4.21).  Euler is the loop as it always was; Heun evaluates twice per step — the second time on its predicted state, at the
+// hoisted row of the step's target time — and 2M once, each followed by its own one-pass update, which knows the scale and the blend exactly as Euler's does.
 static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, float* img_inout, const double* timesteps_host, int n_steps, const float* mod_steps,
-                     const float* txt_pre, StepCacheRun* sc, const CnRun* cn, const IpRun* ip, hipStream_t s) {
+                     const float* txt_pre, StepCacheRun* sc, const CnRun* cn, const IpRun* ip, int solver, hipStream_t s) {
   const fmi_flux_denoise_options& o = p.o;
   const size_t B = in->B, nmod = m->n_mod;
   const int64_t n = (int64_t)p.Bs * in->S * m->cfg.in_channels;
-  for (int i = 0; i < n_steps; ++i) {
+  // One evaluation into ws.pred_tmp: of the state x at the time of hoisted row `row`, at step i's ControlNet and adapter scales.
+  const auto eval = [&](const float* x, int row, int i) -> int {
     CnInject inj{};
     const IpInject ipj{ip && ip->c[i] != 0.f ? ip->a : nullptr, ip ? ip->c[i] : 0.f};
     if (cn && cn->c[i] != 0.f) {  // the ControlNet on the step's state, then the main model with its samples
       fmi_flux* net = cn->net;
-      FMI_TRY(forward_core(net, in, cn_plan(p), img_inout, net->ws.tv + i * B, nullptr, cn->mod_steps ? cn->mod_steps + i * B * (size_t)net->n_mod : nullptr, cn->txt_pre,
+      FMI_TRY(forward_core(net, in, cn_plan(p), x, net->ws.tv + row * B, nullptr, cn->mod_steps ? cn->mod_steps + row * B * (size_t)net->n_mod : nullptr, cn->txt_pre,
                            nullptr, nullptr, nullptr, s));
       inj = CnInject{net, cn->c[i]};
     }
-    FMI_TRY(forward_core(m, in, p, img_inout, m->ws.tv + i * B, m->ws.pred_tmp, mod_steps ? mod_steps + i * B * nmod : nullptr, txt_pre, sc, inj.net ? &inj : nullptr,
-                         ipj.a ? &ipj : nullptr, s));
+    return forward_core(m, in, p, x, m->ws.tv + row * B, m->ws.pred_tmp, mod_steps ? mod_steps + row * B * nmod : nullptr, txt_pre, sc, inj.net ? &inj : nullptr,
+                        ipj.a ? &ipj : nullptr, s);
+  };
+  // pred_tmp is (2 Bs, S, C) under true CFG: the prompt's predictions, then the negative's; the blend's arguments are null without a mask
+  const float *pos = m->ws.pred_tmp, *neg = o.cfg ? m->ws.pred_tmp + n : nullptr;
+  const float scale = o.cfg ? o.cfg->scale : 0.f;
+  for (int i = 0; i < n_steps; ++i) {
+    FMI_TRY(eval(img_inout, i, i));
     // img = img + pred * (t_prev - t_curr)  (sampling.rs:43), scalar rounded to f32 like candle's affine
-    const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]);
-    if (o.cfg)  // pred_tmp is (2 Bs, S, C): the prompt's predictions, then the negative's; the blend's arguments are null without a mask
-      FMI_TRY(launch_euler_cfg(img_inout, m->ws.pred_tmp, m->ws.pred_tmp + n, o.cfg->scale, dt, n, s, o.x0, o.noise, o.mask, (float)timesteps_host[i + 1]));
-    else if (o.mask)  // the re-noised source at the step's target time, blended in where the mask keeps it
-      FMI_TRY(launch_euler_blend(img_inout, m->ws.pred_tmp, o.x0, o.noise, o.mask, dt, (float)timesteps_host[i + 1], n, s));
-    else
-      FMI_TRY(launch_euler_update(img_inout, m->ws.pred_tmp, dt, n, s));
+    const float dt = (float)(timesteps_host[i + 1] - timesteps_host[i]), t_next = (float)timesteps_host[i + 1];
+    if (solver == FMI_SOLVER_DPMPP_2M) {  // the history is buffer 0: written by every step, read from the first step whose w is not 0
+      float a, c, w;
+      dpmpp_2m_coefficients(timesteps_host, i, &a, &c, &w);
+      FMI_TRY(launch_dpmpp_2m(img_inout, pos, neg, scale, (float)timesteps_host[i], a, c, w, n, m->solver_buf[0].as<float>(), s, o.x0, o.noise, o.mask, t_next));
+    } else if (solver == FMI_SOLVER_HEUN && timesteps_host[i + 1] != 0.0) {  // (into t = 0 the step is Euler's, below: the model is not evaluated at 0)
+      float *xt = m->solver_buf[0].as<float>(), *g1 = m->solver_buf[1].as<float>();
+      FMI_TRY(launch_heun_predict(img_inout, pos, neg, scale, dt, n, xt, g1, s, o.x0, o.noise, o.mask, t_next));
+      FMI_TRY(eval(xt, i + 1, i));
+      FMI_TRY(launch_heun_correct(img_inout, g1, pos, neg, scale, dt, n, s, o.x0, o.noise, o.mask, t_next));
+    } else if (o.cfg) {
+      FMI_TRY(launch_euler_cfg(img_inout, pos, neg, scale, dt, n, s, o.x0, o.noise, o.mask, t_next));
+    } else if (o.mask) {  // the re-noised source at the step's target time, blended in where the mask keeps it
+      FMI_TRY(launch_euler_blend(img_inout, pos, o.x0, o.noise, o.mask, dt, t_next, n, s));
+    } else {
+      FMI_TRY(launch_euler_update(img_inout, pos, dt, n, s));
+    }
   }
   return FMI_OK;
 }
@@ -2006,15 +2054,19 @@ static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, 
 // of the img_in operand once, forward_core the state's every step); the negative prompt to the input assembly and the update — `in` below is then the loop's own batch of
 // 2 * Bs samples, the prompt's rows, then the negative's —; the step cache to forward_core after double block 0.
 static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi_flux_denoise_options& o, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip,
-                        float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+                        float* img_inout, const double* timesteps_host, int n_steps, void* stream, const fmi_flux_solver* solver_arg = nullptr) {
   EvalPlan p;
   FMI_TRY(validate(m, in_caller, o, cn, ip, n_steps, img_inout && timesteps_host && n_steps >= 0 ? nullptr : "flux_denoise: null img/timesteps or negative n_steps", &p));
+  const int solver = solver_arg ? solver_arg->kind : FMI_SOLVER_EULER;
+  FMI_TRY(check_solver(m, o, p, solver, timesteps_host, n_steps));
   hipStream_t s = (hipStream_t)stream;
   fmi_flux_inputs in = *in_caller;
   if (o.cfg) in.B = 2 * p.Bs;
   StepCacheRun sc{o.cache};
   if (o.cache) FMI_TRY(step_cache_ensure(m, in.B, in.S + p.R, s));
   FMI_TRY(ensure_workspace(m, in.B, in.S + p.R, in.T));
+  if (solver != FMI_SOLVER_EULER) FMI_TRY(solver_ensure(m, solver, (size_t)p.Bs * in.S * m->cfg.in_channels, s));
+  const int n_rows = solver == FMI_SOLVER_HEUN ? n_steps + 1 : n_steps;  // the times that get a hoisted row: Heun's last second evaluation runs at ts[n_steps]
   if (o.cfg && in.guidance) {  // the same guidance in both halves
     if (!m->cfg_gd) FMI_HIP_TRY(m->cfg_gd.alloc(8 * sizeof(float)));  // (2 Bs <= 8; a call without a negative never allocates it)
     FMI_HIP_TRY(hipMemcpyAsync(m->cfg_gd.as<float>(), in_caller->guidance, (size_t)p.Bs * 4, hipMemcpyDeviceToDevice, s));
@@ -2023,7 +2075,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
   }
   FMI_TRY(prepare_static(m, &in, p, s));  // txt cast, y cast, the RoPE table and the context's rows of the img_in operand are loop invariant
   const float *mod_steps, *txt_pre;
-  FMI_TRY(hoist_steps(m, &in, timesteps_host, n_steps, s, &mod_steps, &txt_pre));
+  FMI_TRY(hoist_steps(m, &in, timesteps_host, n_rows, s, &mod_steps, &txt_pre));
   CnRun cr{cn ? cn->net : nullptr, nullptr, nullptr, {}};
   bool cn_active = false;  // a ControlNet whose every step has scale 0 prepares nothing: the call is the plain loop, launch for launch
   for (int i = 0; cn && i < n_steps; ++i) {
@@ -2032,7 +2084,7 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
   }
   if (cn_active) {  // the ControlNet's once-per-image work, hoisted like the main model's: controlnet_x_embedder(cond), every step's modulation vectors, txt_in
     FMI_TRY(cn_prepare(cr.net, &in, p, s));
-    FMI_TRY(hoist_steps(cr.net, &in, timesteps_host, n_steps, s, &cr.mod_steps, &cr.txt_pre));
+    FMI_TRY(hoist_steps(cr.net, &in, timesteps_host, n_rows, s, &cr.mod_steps, &cr.txt_pre));
   }
   IpRun ir{ip ? ip->adapter : nullptr, {}};
   bool ip_active = false;  // likewise: an adapter whose every step has scale 0 projects nothing, and every step keeps the fused q|k|v relayout
@@ -2042,7 +2094,8 @@ static int denoise_loop(fmi_flux* m, const fmi_flux_inputs* in_caller, const fmi
   }
   // the adapter's once-per-call work: tok and every block's K / V, for the prompt's embeds and — under true CFG — the negative's (zeros without neg_embeds)
   if (ip_active) FMI_TRY(ip_prepare(ip->adapter, ip->embeds, ip->neg_embeds, ip->embeds_dtype, p.Bs, o.cfg != nullptr, s));
-  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, cn_active ? &cr : nullptr, ip_active ? &ir : nullptr, s);
+  return run_steps(m, &in, p, img_inout, timesteps_host, n_steps, mod_steps, txt_pre, o.cache ? &sc : nullptr, cn_active ? &cr : nullptr, ip_active ? &ir : nullptr, solver,
+                   s);
 }
 
 extern "C" int fmi_flux_denoise_with(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
@@ -2058,6 +2111,13 @@ extern "C" int fmi_flux_denoise_ip(fmi_flux* m, const fmi_flux_inputs* in, const
                                    float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
   return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, ip, img_inout, timesteps_host, n_steps, stream);
 }
+// The same loop with a second-order solver; solver NULL (or FMI_SOLVER_EULER) IS fmi_flux_denoise_ip.
+extern "C" int fmi_flux_denoise_solver(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts, const fmi_flux_controlnet* cn, const fmi_flux_ip* ip,
+                                       const fmi_flux_solver* solver, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {
+  return denoise_loop(m, in, opts ? *opts : fmi_flux_denoise_options{}, cn, ip, img_inout, timesteps_host, n_steps, stream, solver);
+}
+// device bytes the solvers' buffers hold (0 until the first Heun / 2M call)
+extern "C" size_t fmi_flux_solver_bytes(fmi_flux* m) { return m ? m->solver_buf[0].bytes() + m->solver_buf[1].bytes() : 0; }
 
 // The entries from before fmi_flux_denoise_with: each fills the options its arguments name — {ctx, ctl, cfg, cache, x0, noise, mask} — and takes the same path.
 extern "C" int fmi_flux_denoise(fmi_flux* m, const fmi_flux_inputs* in, float* img_inout, const double* timesteps_host, int n_steps, void* stream) {

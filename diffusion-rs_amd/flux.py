@@ -163,6 +163,28 @@ def check_step_cache_args(n_steps: int, threshold=None, force=None):
     return thr, np.ascontiguousarray(f, dtype=np.int8)
 
 
+SOLVERS = {"euler": 0, "heun": 1, "dpmpp_2m": 2}  # FMI_SOLVER_*
+
+
+def check_solver_args(solver, timesteps, cache=False, sequence_parallel=False):
+    """The integrator of FluxModel.denoise (fmi_flux_denoise_solver), checked without the library.  Returns the FMI_SOLVER_* kind, or None for
+    solver None / "euler": the loop as it always was, which keeps accepting any schedule.  ValueError: a name that is none of SOLVERS; for "heun" / "dpmpp_2m" a
+    schedule that is not strictly decreasing inside [0, 1]; "heun" with the step cache (cache: one is present); either of them under sequence parallelism.
+    These two refusals are the solver's own, not rows of REFUSED_PAIRS / REFUSED_MODES."""
+    if solver is None or solver == "euler":
+        return None
+    if not isinstance(solver, str) or solver not in SOLVERS:
+        raise ValueError(f"solver must be None or one of {sorted(SOLVERS)}, got {solver!r}")
+    ts = [float(t) for t in timesteps]
+    if len(ts) < 1 or not ts[0] <= 1.0 or not ts[-1] >= 0.0 or not all(b < a for a, b in zip(ts, ts[1:])):
+        raise ValueError(f"solver={solver!r} needs a strictly decreasing schedule inside [0, 1] (1 >= timesteps[0], timesteps[-1] >= 0)")
+    if sequence_parallel:
+        raise ValueError(f"solver={solver!r} is not supported under sequence parallelism")
+    if solver == "heun" and cache:
+        raise ValueError("solver='heun' is not combined with the step cache (cache_threshold= / cache_force=): its two evaluations per step are at different times")
+    return SOLVERS[solver]
+
+
 def check_true_cfg_args(txt_shape, y_shape, negative_txt_shape=None, negative_y_shape=None, true_cfg_scale=None):
     """The arguments of true classifier-free guidance (FluxModel.denoise / fmi_flux_denoise_cfg), checked without the library: the shapes
     of the prompt's txt (B,T,J) and y (B,P), of the negative's, and the scale.  Returns the scale as a float (1.0 when none is given), or None when no
@@ -625,8 +647,8 @@ class FluxModel:
     def denoise(self, img, img_ids, txt, txt_ids, y, guidance, timesteps: List[float], x0=None, noise=None, mask=None, context=None, context_ids=None,
                 cache_threshold=None, cache_force=None, return_cache_stats=False, negative_txt=None, negative_y=None, true_cfg_scale=None, control=None,
                 controlnet=None, controlnet_cond=None, controlnet_scale=1.0, controlnet_step_scales=None, ip_adapter=None, ip_adapter_image_embeds=None,
-                negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0, ip_adapter_step_scales=None):
-        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_ip call: the keywords fill its options
+                negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0, ip_adapter_step_scales=None, solver=None):
+        """== Sampler::sample around Flux::forward (sampling.rs:25-48). `img` f32 (B,S,C), updated copy returned.  One fmi_flux_denoise_solver call: the keywords fill its options
         and its ControlNet and adapter arguments; which of them combine is REFUSED_PAIRS / REFUSED_MODES above.
         x0 / noise / mask (all three or none; f32, shaped like img): the inpainting loop fmi_flux_denoise_inpaint — after every step the source
         latents x0, re-noised with `noise` to the step's target time, are blended back in where mask is 0 (include/flux_mi355x.h).
@@ -653,7 +675,11 @@ class FluxModel:
         projected once per call; every double block of step i adds ip_adapter_scale * ip_adapter_step_scales[i] times the image-prompt attention to the image
         stream, and a step whose scale is 0 is the plain step.  Under true CFG the negative half attends to negative_ip_adapter_image_embeds, or to zero
         embeddings through the same projection.  Works with the negative, x0 / noise / mask, control= and controlnet=; not with context=, the step cache,
-        sequence parallelism or the 8-bit modes."""
+        sequence parallelism or the 8-bit modes.
+        solver=: None | "euler" (the loop as it always was) | "heun" | "dpmpp_2m" (fmi_flux_denoise_solver): a second-order integrator over the
+        same schedule, which must then be strictly decreasing inside [0, 1].  "heun" evaluates the model twice per step (once on the last step of a schedule that
+        ends at 0), "dpmpp_2m" once, keeping one step of history.  Both work with every option above, except "heun" with the step cache and either under
+        sequence parallelism.  A capability, not a recommendation: no step count is suggested for either."""
         n_steps = len(timesteps) - 1
         has_ctx = context is not None or context_ids is not None
         # (every keep_*, like keep, holds the tensors behind the pointers until the call has returned)
@@ -665,6 +691,7 @@ class FluxModel:
                                         None if negative_y is None else tuple(negative_y.shape), true_cfg_scale)
         thr, force = check_step_cache_args(n_steps, cache_threshold, cache_force)
         self._check_combination(context=has_ctx, control=ctl, true_cfg=cfg_scale is not None, cache=thr is not None, controlnet=cn, ip_adapter=ip)
+        kind = check_solver_args(solver, timesteps, cache=thr is not None, sequence_parallel=getattr(self, "_sp_world", 1) > 1)
         if return_cache_stats and thr is None:
             raise ValueError("return_cache_stats needs cache_threshold= or cache_force=")
         img = img.to(torch.float32).clone().contiguous()
@@ -687,9 +714,15 @@ class FluxModel:
             distances = np.full((max(n_steps, 0), int(img_ids.shape[0])), -1.0, np.float32)
             opts.cache = C.pointer(L.FluxStepCache(thr, force.ctypes.data_as(C.POINTER(C.c_int8)) if force is not None else None,
                                                    decisions.ctypes.data_as(C.POINTER(C.c_int32)), distances.ctypes.data_as(C.POINTER(C.c_float))))
-        # (with cn and ip NULL this IS fmi_flux_denoise_with, with ip NULL fmi_flux_denoise_controlnet: include/flux_mi355x.h)
-        L.check(self.lib.fmi_flux_denoise_ip(self.h, C.byref(inp), C.byref(opts), cn and C.byref(cn), ip and C.byref(ip), _ptr(img), ts, n_steps, _stream()), self.lib)
+        # (with solver NULL this IS fmi_flux_denoise_ip, with ip NULL too fmi_flux_denoise_controlnet, with cn NULL too fmi_flux_denoise_with: include/flux_mi355x.h)
+        sv = None if kind is None else L.FluxSolver(kind)
+        L.check(self.lib.fmi_flux_denoise_solver(self.h, C.byref(inp), C.byref(opts), cn and C.byref(cn), ip and C.byref(ip), sv and C.byref(sv), _ptr(img), ts, n_steps,
+                                                 _stream()), self.lib)
         return (img, {"decisions": decisions, "distances": distances}) if return_cache_stats else img
+
+    def solver_bytes(self) -> int:
+        """Device bytes the solvers' buffers hold: 0 until the first denoise with solver="heun" / "dpmpp_2m" (a loop without a solver never allocates them)."""
+        return int(self.lib.fmi_flux_solver_bytes(self.h))
 
     def step_cache_bytes(self) -> int:
         """Device bytes the step cache holds: 0 until the first denoise with cache_threshold= / cache_force= (the plain loops never allocate it)."""
@@ -1078,6 +1111,51 @@ def cfg_euler_step(img, pos, neg, scale, dt, x0=None, noise=None, mask=None, s=0
             raise TypeError("cfg_euler_step: contiguous float32 tensors of one shape on one device are required")
     L.check(L.load().fmi_cfg_euler_step(_ptr(img), _ptr(pos), _ptr(neg), float(scale), float(dt), img.numel(), _ptr(x0), _ptr(noise), _ptr(mask), float(s), _stream()))
     return img
+
+
+def _solver_step_tensors(who, img, others, x0, noise, mask):
+    blend = [t for t in (x0, noise, mask) if t is not None]
+    if len(blend) not in (0, 3):
+        raise ValueError(f"{who}: x0, noise and mask go together (all three or none)")
+    for t in [img] + [t for t in others if t is not None] + blend:
+        if t.dtype != torch.float32 or t.shape != img.shape or not t.is_contiguous() or t.device != img.device:
+            raise TypeError(f"{who}: contiguous float32 tensors of one shape on one device are required")
+
+
+def heun_predict(img, pos, neg=None, scale=1.0, dt=0.0, x0=None, noise=None, mask=None, s=0.0):
+    """The Heun predictor on its own (fmi_heun_predict): returns (x_pred, g1), two new tensors; img is only read.  g1 = pos, or with neg
+    neg + scale * (pos - neg); x_pred = img + g1 * dt, or with x0 / noise / mask (all three or none) its blend at the target time s, as in cfg_euler_step."""
+    _solver_step_tensors("heun_predict", img, (pos, neg), x0, noise, mask)
+    x_pred, g1 = torch.empty_like(img), torch.empty_like(img)
+    L.check(L.load().fmi_heun_predict(_ptr(img), _ptr(pos), _ptr(neg), float(scale), float(dt), img.numel(), _ptr(x_pred), _ptr(g1), _ptr(x0), _ptr(noise), _ptr(mask),
+                                      float(s), _stream()))
+    return x_pred, g1
+
+
+def heun_correct(img, g1, pos, neg=None, scale=1.0, dt=0.0, x0=None, noise=None, mask=None, s=0.0):
+    """The Heun corrector on its own (fmi_heun_correct), in place on img and returning it: img = img + ((g1 + g2) * 0.5) * dt with g2 = pos or the guided
+    combination of the evaluation on x_pred, blended like the predictor's."""
+    _solver_step_tensors("heun_correct", img, (g1, pos, neg), x0, noise, mask)
+    L.check(L.load().fmi_heun_correct(_ptr(img), _ptr(g1), _ptr(pos), _ptr(neg), float(scale), float(dt), img.numel(), _ptr(x0), _ptr(noise), _ptr(mask), float(s),
+                                      _stream()))
+    return img
+
+
+def dpmpp_2m_step(img, pos, history, t, a, c, w, neg=None, scale=1.0, x0=None, noise=None, mask=None, s=0.0):
+    """The DPM-Solver++ 2M step on its own (fmi_dpmpp_2m_step), in place on img and history, returning img: D = img - t * g, D' = D + w * (D - history) (w == 0: the
+    history is not read), img = a * img + c * D', blended; history = D.  a, c, w: dpmpp_2m_coefficients."""
+    _solver_step_tensors("dpmpp_2m_step", img, (pos, neg, history), x0, noise, mask)
+    L.check(L.load().fmi_dpmpp_2m_step(_ptr(img), _ptr(pos), _ptr(neg), float(scale), float(t), float(a), float(c), float(w), img.numel(), _ptr(history), _ptr(x0),
+                                       _ptr(noise), _ptr(mask), float(s), _stream()))
+    return img
+
+
+def dpmpp_2m_coefficients(timesteps, i: int):
+    """(a, c, w) of step i of the schedule, as the library's loop uses them (fmi_dpmpp_2m_coefficients: computed in double, rounded once to float32).  No device."""
+    ts = (C.c_double * len(timesteps))(*timesteps)
+    a, c, w = C.c_float(), C.c_float(), C.c_float()
+    L.check(L.load().fmi_dpmpp_2m_coefficients(ts, len(timesteps) - 1, int(i), C.byref(a), C.byref(c), C.byref(w)))
+    return a.value, c.value, w.value
 
 
 def randn_latents(B, Cc, h, w, seed, first_sample=0, device="cuda"):

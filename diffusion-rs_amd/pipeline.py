@@ -633,7 +633,7 @@ class Pipeline:
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
+                        solver: Optional[str] = None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                         negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -705,13 +705,21 @@ class Pipeline:
         unchanged, the denoise loop is untouched.  redux_scale = 0 still appends the rows, as zeros.  Under a negative prompt (true CFG) both halves keep one T:
         the negative half receives ZERO rows in place of the image tokens (the IP-Adapter's zero-embeddings rule).  Redux changes the text rows only, so it combines
         with everything the text rows combine with — image= / strength= / mask=, reference=, a control, a ControlNet, an IP-Adapter, cache_threshold=, the 8-bit
-        modes; it raises under sequence parallelism and without a loaded Redux."""
+        modes; it raises under sequence parallelism and without a loaded Redux.
+
+        Integrator (`solver=`; None | "euler": the loop as it always was): "heun" (diffusers' FlowMatchHeunDiscreteScheduler, ComfyUI's heun) or
+        "dpmpp_2m" (DPMSolverMultistepScheduler with use_flow_sigmas, ComfyUI's dpmpp_2m) over the request's own schedule — after a strength= cut the schedule
+        starts below 1 and "dpmpp_2m" uses its history from step 1 on.  "heun" evaluates the model twice per step but the last, "dpmpp_2m" once.  Both combine
+        with everything above except "heun" with cache_threshold= and either under sequence parallelism.  A capability, not a recommendation: no step count is
+        suggested for either, there are no real weights here to judge one."""
         rdx = self._redux_input(redux_image, redux_image_embeds, redux_scale)
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
                                      negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
                                      image=ip_adapter_image, negative_image=negative_ip_adapter_image)
         cn = self._controlnet_input(controlnet_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, params)
         F.check_step_cache_args(params.num_steps, cache_threshold)
+        # (the schedule is the scheduler's own, strictly decreasing from 1 to 0: the name and the solver's two refusals are what a request can get wrong)
+        kind = F.check_solver_args(solver, [1.0, 0.0], cache=cache_threshold is not None, sequence_parallel=getattr(self, "_sp", None) is not None)
         ctl = self._control(control_image, control_mask, params)
         neg = self._negative(negative_prompt, negative_embeddings, negative_token_ids, true_cfg_scale, embeddings, token_ids)
         # the request's shared options, one keyword of _generate_chunk each, passed only by a request that has it: any other makes exactly the call it always made
@@ -727,7 +735,9 @@ class Pipeline:
             S = ((params.height + 15) // 16) * ((params.width + 15) // 16)
             return (u8, torch.empty((0, S, 64), dtype=torch.float32, device=self.device)) if return_latents else u8
         stats = []  # one list per request, shared by the chunks it is cut into
-        chunk = self._generate_chunk if rdx is None else (lambda *a, **kw: self._generate_chunk_redux(rdx, *a, **kw))
+        # a request with a solver takes the chunk body through _generate_chunk_solver; any other makes exactly the call it always made
+        base = self._generate_chunk if kind is None else (lambda *a, **kw: self._generate_chunk_solver(solver, *a, **kw))
+        chunk = base if rdx is None else (lambda *a, **kw: self._generate_chunk_redux(rdx, *a, **({} if kind is None else dict(chunk=base)), **kw))
         outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
                 for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         if len(outs) == 1:
@@ -867,17 +877,18 @@ class Pipeline:
         return _ReduxInput((tokens * float(scale)).contiguous())
 
     def _generate_chunk_redux(self, redux: _ReduxInput, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
-                              **shared):
+                              chunk=None, **shared):
         """One denoise call of a request with Redux tokens: the chunk's text embeddings are made as always (_chunk_embeddings: text, token_ids= or embeddings=,
         the negative with them), the tokens are appended behind the T5 rows of every sample — zero rows behind the negative's — and the chunk goes on as the
-        embeddings= chunk that it now is."""
+        embeddings= chunk that it now is (through `chunk`, the solver's chunk call, where the request has a solver)."""
         with self._lock:
             t5_emb, clip_emb, neg = self._chunk_embeddings(s, negative)
         tok = redux.tokens.to(t5_emb.dtype)
         s = replace(s, embeddings=(torch.cat([t5_emb, tok.expand(t5_emb.shape[0], -1, -1)], 1), clip_emb), token_ids=None)
         if neg is not None:
             negative = _Negative(negative.scale, embeddings=(torch.cat([neg[0][:1], torch.zeros_like(tok)], 1), neg[1][:1]))
-        return self._generate_chunk(s, params, seed, strength, return_latents, cache_threshold, stats, **({} if negative is None else dict(negative=negative)), **shared)
+        return (chunk or self._generate_chunk)(s, params, seed, strength, return_latents, cache_threshold, stats, **({} if negative is None else dict(negative=negative)),
+                                               **shared)
 
     def load_redux(self, path, image_encoder=None):
         """Load FLUX.1 Redux: a SigLIP vision tower and the Redux embedder.  `path` is a FLUX.1-Redux-dev directory (image_encoder/,
@@ -1053,10 +1064,21 @@ class Pipeline:
 
     def _generate_chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
                         control: Optional[_Control] = None, controlnet: Optional[_ControlNetInput] = None, ip_adapter: Optional[_IpAdapterInput] = None):
+        """One denoise call of a request without a solver: _chunk, see there."""
+        return self._chunk(s, params, seed, strength, return_latents, cache_threshold, stats, negative, control, controlnet, ip_adapter)
+
+    def _generate_chunk_solver(self, solver: str, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, **shared):
+        """One denoise call of a request with solver= "heun" / "dpmpp_2m" (DESIGN.md 4.21): the same chunk, integrated by that solver."""
+        return self._chunk(s, params, seed, strength, return_latents, cache_threshold, stats, solver=solver, **shared)
+
+    def _chunk(self, s: _Samples, params, seed, strength, return_latents, cache_threshold, stats, negative: Optional[_Negative] = None,
+               control: Optional[_Control] = None, controlnet: Optional[_ControlNetInput] = None, ip_adapter: Optional[_IpAdapterInput] = None,
+               solver: Optional[str] = None):
         """One denoise call: at most MAX_BATCH samples (one under sequence parallelism; MAX_BATCH // 2 with a negative) of a normalised request.  Returns what
         generate_tensor does.  The request's shared options, each passed only by a request that has it — negative: its true-CFG negative (DESIGN.md 4.12);
         control: the control of a request to a channel-conditioned model; controlnet: the conditioning of one with controlnet_image=
-        (DESIGN.md 4.15); ip_adapter: the image prompt of one with ip_adapter_image_embeds=."""
+        (DESIGN.md 4.15); ip_adapter: the image prompt of one with ip_adapter_image_embeds=; solver: "heun" / "dpmpp_2m" of one with solver=
+        (DESIGN.md 4.21)."""
         cfg = self.flux.cfg
         dev = self.device
         sp = getattr(self, "_sp", None)
@@ -1099,6 +1121,8 @@ class Pipeline:
                              ip_adapter_step_scales=F.controlnet_step_scales(len(timesteps) - 1, ip_adapter.start, ip_adapter.end))
                 if ip_adapter.negative_embeds is not None:
                     cn_kw.update(negative_ip_adapter_image_embeds=ip_adapter.negative_embeds.expand(B, -1).contiguous())
+            if solver is not None:
+                cn_kw.update(solver=solver)
             if getattr(self, "_int8_pending", False):
                 self._int8_calibrate_and_quantize(img[:1], img_ids[:1], t5_emb[:1], txt_ids[:1], clip_emb[:1], None if guidance is None else guidance[:1], timesteps,
                                                   {k: v[:1] for k, v in context.items()})
@@ -1194,8 +1218,8 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, negative_prompt: Optional[str] = None,
-                negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
+                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None,
+                negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
                 ip_adapter_image=None, negative_ip_adapter_image=None, redux_image=None, redux_image_embeds=None, redux_scale: float = 1.0, **kw):
@@ -1214,7 +1238,8 @@ class Pipeline:
         negative_ip_adapter_image=: the same prompt as a picture, encoded by the image encoder of load_image_encoder (every rank loads the same one and encodes
         the picture itself).
         redux_image= / redux_image_embeds= / redux_scale=: FLUX.1 Redux image variation (load_redux), see generate_tensor — one picture per request, likewise
-        (every rank loads the same Redux and encodes the picture itself)."""
+        (every rank loads the same Redux and encodes the picture itself).
+        solver=: None | "euler" | "heun" | "dpmpp_2m", the integrator of the denoise loop, see generate_tensor."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -1224,7 +1249,7 @@ class Pipeline:
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
                        ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image,
-                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale)
+                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

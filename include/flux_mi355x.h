@@ -56,6 +56,8 @@ extern "C" {
  *   Then, still 6: the CLIP vision encoder (an image prompt from a picture) — fmi_resize_bicubic_u8, fmi_clip_preprocess_u8, fmi_clip_vision_*.
  *   Then, still 6: FLUX.1 Redux (image variation: a SigLIP vision tower and the Redux embedder) — fmi_siglip_vision_*, fmi_redux_*.
  *   Then, still 6: single-file fp8 checkpoints (OCP e4m3fn / e5m2 weights resident as codes) — fmi_f8_dequantize, fmi_flux_set_linear_f8.
+ *   Then, still 6: second-order solvers in the denoise loop (Heun, DPM-Solver++ 2M) — fmi_flux_solver, fmi_flux_denoise_solver, fmi_flux_solver_bytes,
+ *                  fmi_heun_predict, fmi_heun_correct, fmi_dpmpp_2m_step, fmi_dpmpp_2m_coefficients.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -667,6 +669,31 @@ int fmi_flux_denoise_controlnet(fmi_flux*, const fmi_flux_inputs* in, const fmi_
  * runs once per call, never per step.  fmi_flux_denoise_controlnet IS this call with ip == NULL: the same launches, bits, errors and allocations. */
 int fmi_flux_denoise_ip(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */, const fmi_flux_controlnet* cn,
                         const fmi_flux_ip* ip, float* img_inout, const double* timesteps_host, int n_steps, void* stream);
+/* The same loop with a second-order integrator.  Flow matching: sigma = t, alpha = 1 - t; g is the model's prediction, or under a negative
+ * prompt neg + scale * (pos - neg).  The solver is an argument of its own and fmi_flux_denoise_ip IS this call with solver == NULL; FMI_SOLVER_EULER is the
+ * same: the launches, bits, errors and allocations of a call that never heard of a solver.
+ *   FMI_SOLVER_HEUN, step i with dt = t_{i+1} - t_i:  g1 = g(x, t_i);  xp = x + g1 * dt;  if t_{i+1} == 0: x = xp (the Euler step) — else g2 = g(xp, t_{i+1}) and
+ *     x = x + ((g1 + g2) * 0.5) * dt.  2 n_steps - 1 evaluations when the schedule ends at 0, else 2 n_steps.  The per-image hoisted rows cover all n_steps + 1
+ *     times; both evaluations of step i run at step i's ControlNet / IP-Adapter scale.  With x0 / noise / mask both xp and the corrected x are states at t_{i+1}
+ *     and both are blended there.
+ *   FMI_SOLVER_DPMPP_2M (data prediction, two-step, midpoint), with l(t) = ln((1 - t) / t):  D_i = x - t_i * g;  a = t_{i+1} / t_i, c = 1 - a,
+ *     w = (l_{i+1} - l_i) / (2 (l_i - l_{i-1})), and w = 0 at i == 0, after t_{i-1} == 1 and into t_{i+1} == 0;  D' = D_i + w * (D_i - D_{i-1});
+ *     x = a * x + c * D';  the history becomes D_i;  then the blend at t_{i+1}, if any.  One evaluation per step; a, c, w are computed in double and rounded once
+ *     (fmi_dpmpp_2m_coefficients).
+ * A solver's schedule is strictly decreasing with 1 >= timesteps_host[0] and timesteps_host[n_steps] >= 0: FMI_ERR_INVALID otherwise, and for an unknown kind.
+ * Not in the table above, in the solver's own check: FMI_SOLVER_HEUN with the step cache, and either solver under sequence parallelism, answer
+ * FMI_ERR_UNSUPPORTED.  Everything else combines: the blend, a context, a control, a negative prompt, a ControlNet, an IP-Adapter, LoRA, the 8-bit modes, and
+ * FMI_SOLVER_DPMPP_2M with the step cache (a reused step's prediction enters the update like any other).  Like every refusal these come before any launch or
+ * allocation.  The first solver call allocates state-sized f32 buffers — two for Heun (xp, g1), one for 2M (the history); regrown when a larger state comes,
+ * counted by fmi_flux_size_in_bytes and fmi_flux_solver_bytes, released with the model; a loop without a solver never allocates them. */
+enum { FMI_SOLVER_EULER = 0, FMI_SOLVER_HEUN = 1, FMI_SOLVER_DPMPP_2M = 2 };
+typedef struct fmi_flux_solver {
+  int kind; /* FMI_SOLVER_* */
+} fmi_flux_solver;
+int fmi_flux_denoise_solver(fmi_flux*, const fmi_flux_inputs* in, const fmi_flux_denoise_options* opts /* NULL == all NULL */, const fmi_flux_controlnet* cn,
+                            const fmi_flux_ip* ip, const fmi_flux_solver* solver /* NULL == FMI_SOLVER_EULER */, float* img_inout, const double* timesteps_host,
+                            int n_steps, void* stream);
+size_t fmi_flux_solver_bytes(fmi_flux*); /* device bytes the solvers' buffers hold (0 until the first Heun / 2M call) */
 
 /* The entries from before fmi_flux_denoise_with.  Each IS fmi_flux_denoise_with with the fields it names set from its arguments and every other field NULL —
  * the same launches, bits, errors and allocations. */
@@ -950,6 +977,26 @@ int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, fl
  * FMI_ERR_INVALID: a null img / pos / neg, n < 0, a scale that is negative, NaN or infinite, x0 / noise / mask given in part. */
 int fmi_cfg_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n,
                        const float* x0, const float* noise, const float* mask, float s, void* stream);
+/* The updates of fmi_flux_denoise_solver on their own (op-level glue; device pointers, no allocation), over n f32 elements, one pass each.
+ * g(pos, neg) = pos when neg is NULL (scale is then ignored), else neg + scale * (pos - neg).  blend(e) = e without x0 / noise / mask (all three or none), else
+ * mask * e + (1 - mask) * ((1 - s) * x0 + s * noise).  Every product that feeds a sum is one fused multiply-add.  16-byte accesses when n % 4 == 0 and every
+ * pointer is 16-byte aligned, else scalar ones: the same bits either way.
+ *   fmi_heun_predict:   g1 = g(pos, neg);  x_pred = blend(img + g1 * dt).  img is only read; img, x_pred and g1 are three buffers.
+ *   fmi_heun_correct:   img = blend(img + ((g1 + g(pos, neg)) * 0.5) * dt), in place; pos / neg are the evaluation on x_pred at the target time.
+ *   fmi_dpmpp_2m_step:  D = img - t * g(pos, neg);  D' = D + w * (D - history), or D when w == 0 (history is then not read);  img = blend(a * img + c * D');
+ *                       history = D.  img and history are updated in place.  a, c, w: fmi_dpmpp_2m_coefficients; t: the step's time, rounded to f32.
+ * FMI_ERR_INVALID: a null required pointer, n < 0, buffers that must differ given as one, with neg a scale that is negative, NaN or infinite, x0 / noise / mask
+ * given in part. */
+int fmi_heun_predict(const float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, float* x_pred, float* g1,
+                     const float* x0, const float* noise, const float* mask, float s, void* stream);
+int fmi_heun_correct(float* img, const float* g1, const float* pos, const float* neg, float scale, float dt, int64_t n,
+                     const float* x0, const float* noise, const float* mask, float s, void* stream);
+int fmi_dpmpp_2m_step(float* img, const float* pos, const float* neg, float scale, float t, float a, float c, float w, int64_t n, float* history,
+                      const float* x0, const float* noise, const float* mask, float s, void* stream);
+/* Step i (0 <= i < n_steps) of the schedule's 2M scalars, computed in double and rounded once to f32: a = t_{i+1} / t_i, c = 1 - a, and
+ * w = (l_{i+1} - l_i) / (2 (l_i - l_{i-1})) with l(t) = ln((1 - t) / t) — 0 when i == 0, when t_{i-1} == 1 and when t_{i+1} == 0.  Host only, no device.
+ * FMI_ERR_INVALID: a null pointer, i out of range, a schedule that is not strictly decreasing inside [0, 1]. */
+int fmi_dpmpp_2m_coefficients(const double* timesteps_host, int n_steps, int i, float* a, float* c, float* w);
 /* ---- channel-concatenated conditioning glue (FLUX.1 Fill / Canny / Depth; device pointers, no allocation) ----
  * A column window of a wider bf16 matrix: row r of src, shaped (rows_src, cols) F32 | BF16 contiguous and read at r % rows_src, goes to
  * dst[r * dst_ld + col0 .. + cols) as bf16 (round to nearest even; a bf16 source is copied), for r in [0, rows); columns outside the window are not touched.
