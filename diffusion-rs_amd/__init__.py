@@ -10,4 +10,4 @@ from .text import (CLIP_L, CLIP_VISION_L, SIGLIP_SO400M, T5_XXL, ClipTextTransfo
                    load_bpe_tokenizer, tokenize_and_pad)
 from . import synth  # noqa: F401
 from . import lora  # noqa: F401
-from .lora import read_lora  # noqa: F401
+from .lora import AdapterTerm, read_adapter, read_lora  # noqa: F401

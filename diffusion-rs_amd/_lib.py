@@ -81,6 +81,15 @@ class FluxSolver(C.Structure):
     _fields_ = [("kind", C.c_int)]
 
 
+ADAPTER_LORA, ADAPTER_LOHA, ADAPTER_LOKR, ADAPTER_DORA = 0, 1, 2, 3  # fmi_adapter_kind
+
+
+class AdapterTermC(C.Structure):
+    """fmi_adapter_term: one LoRA / LoHa / LoKr / DoRA term of one Linear (which fields a kind reads: include/flux_mi355x.h)."""
+    _fields_ = [("kind", C.c_int), ("dtype", C.c_int), ("scale", C.c_float), ("row_offset", C.c_int), ("factor", C.c_void_p * 4),
+                ("factor_rows", C.c_int * 4), ("factor_cols", C.c_int * 4), ("magnitude", C.c_void_p)]
+
+
 class FluxDenoiseOptions(C.Structure):
     """fmi_flux_denoise_options: what fmi_flux_denoise_with's loop is conditioned on, every field NULL for none."""
     _fields_ = [("ctx", C.POINTER(FluxContext)), ("ctl", C.POINTER(FluxControl)), ("cfg", C.POINTER(FluxTrueCfg)), ("cache", C.POINTER(FluxStepCache)),
@@ -227,6 +236,8 @@ def _declare(lib):
     lib.fmi_flux_lora_count.argtypes = [C.c_void_p]
     lib.fmi_flux_lora_name.argtypes = [C.c_void_p, C.c_int]
     lib.fmi_flux_lora_name.restype = C.c_char_p
+    lib.fmi_flux_lora_add_term.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(AdapterTermC)]
+    lib.fmi_adapter_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(AdapterTermC), C.POINTER(C.c_float), C.c_int, C.c_void_p]
     lib.fmi_flux_state_export.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.fmi_flux_state_adopt.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.fmi_flux_state_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
@@ -406,7 +417,7 @@ def check(rc, lib=None):
 # every symbol include/flux_mi355x.h declares (tests/test_host_logic.py::test_library_exports_every_header_symbol checks they are all exported)
 EXPORTED = [
     "fmi_last_error", "fmi_abi_version", "fmi_init", "fmi_device_info", "fmi_build_id", "fmi_has_alt_kernels", "fmi_flux_default_config", "fmi_flux_create", "fmi_flux_destroy",
-    "fmi_flux_set_tensor", "fmi_flux_set_linear_bnb4", "fmi_flux_set_linear_int8", "fmi_flux_set_linear_gguf", "fmi_gguf_block_info", "fmi_gguf_dequantize", "fmi_flux_set_linear_f8", "fmi_f8_dequantize", "fmi_flux_get_tensor", "fmi_flux_lora_add", "fmi_flux_lora_set_weight", "fmi_flux_lora_remove", "fmi_flux_lora_count", "fmi_flux_lora_name", "fmi_flux_set_quant_dense_cache", "fmi_flux_set_sequence_parallel", "fmi_flux_set_split_k", "fmi_set_bnb4_onewave_min_rows", "fmi_flux_set_attention_rescale_threshold", "fmi_flux_set_attention_kernel", "fmi_flux_state_buffer_count", "fmi_flux_state_export", "fmi_flux_state_adopt", "fmi_flux_state_buffer", "fmi_flux_set_modulation_gemm", "fmi_flux_quantize_fp8", "fmi_flux_quantize_int8", "fmi_flux_calibrate_int8", "fmi_flux_set_fp8_attention", "fmi_flux_missing_count", "fmi_flux_missing_name", "fmi_flux_size_in_bytes",
+    "fmi_flux_set_tensor", "fmi_flux_set_linear_bnb4", "fmi_flux_set_linear_int8", "fmi_flux_set_linear_gguf", "fmi_gguf_block_info", "fmi_gguf_dequantize", "fmi_flux_set_linear_f8", "fmi_f8_dequantize", "fmi_flux_get_tensor", "fmi_flux_lora_add", "fmi_flux_lora_set_weight", "fmi_flux_lora_remove", "fmi_flux_lora_count", "fmi_flux_lora_name", "fmi_flux_lora_add_term", "fmi_adapter_merge", "fmi_flux_set_quant_dense_cache", "fmi_flux_set_sequence_parallel", "fmi_flux_set_split_k", "fmi_set_bnb4_onewave_min_rows", "fmi_flux_set_attention_rescale_threshold", "fmi_flux_set_attention_kernel", "fmi_flux_state_buffer_count", "fmi_flux_state_export", "fmi_flux_state_adopt", "fmi_flux_state_buffer", "fmi_flux_set_modulation_gemm", "fmi_flux_quantize_fp8", "fmi_flux_quantize_int8", "fmi_flux_calibrate_int8", "fmi_flux_set_fp8_attention", "fmi_flux_missing_count", "fmi_flux_missing_name", "fmi_flux_size_in_bytes",
     "fmi_flux_forward", "fmi_flux_denoise", "fmi_flux_denoise_inpaint", "fmi_flux_forward_context", "fmi_flux_denoise_context", "fmi_flux_denoise_cached", "fmi_flux_step_cache_bytes", "fmi_flux_denoise_cfg", "fmi_flux_create_cond", "fmi_flux_cond_channels", "fmi_flux_forward_control", "fmi_flux_denoise_control", "fmi_flux_denoise_with",
     "fmi_flux_create_controlnet", "fmi_flux_is_controlnet", "fmi_flux_forward_controlnet", "fmi_flux_denoise_controlnet", "fmi_flux_controlnet_eval", "fmi_flux_controlnet_sample", "fmi_add_scaled_rows_bf16",
     "fmi_ip_adapter_create", "fmi_ip_adapter_destroy", "fmi_ip_adapter_set_tensor", "fmi_ip_adapter_missing_count", "fmi_ip_adapter_missing_name", "fmi_ip_adapter_size_in_bytes",

@@ -476,6 +476,35 @@ int launch_gemv(const float* x, const bf16_t* W, const bf16_t* bias, float* y, i
 constexpr int LORA_TILE_ROWS = 64, LORA_RANK_CHUNK = 16;
 int launch_lora_pack(const float* A, const float* B, int rows, int K, int r, double coef, float* Acat, double* Bt, int rows_pad, int off, hipStream_t stream);
 int launch_lora_merge(const bf16_t* w0, bf16_t* w, int rows, int K, const float* A, const double* Bt, int rows_pad, int Rpad, hipStream_t stream);
+// LyCORIS / DoRA merge (adapter.hip): w rows = bf16_rne(w0 rows + sum over the terms, in order, of weight * Delta), every Delta evaluated in f64, one rounding.
+// AdapterTerm is one validated term resident on the device (f32 factors; f64 for what a pre-pass computed: a decomposed LoKr factor expanded, DoRA's
+// per-row m / n and n); AdapterDesc is what the merge kernel reads of it, together with the weight.
+struct AdapterTerm {
+  int kind = 0;       // fmi_adapter_kind
+  int r = 0;          // rank of the rank sums (LORA, LOHA, DORA)
+  float scale = 1.f;
+  DeviceBuffer f[4];  // f32.  LORA / DORA: f[0] = A (r, K), f[1] = B (rows, r).  LOHA: f[0] = w1_b (r, K), f[1] = w1_a (rows, r), f[2] = w2_b, f[3] = w2_a.
+                      // LOKR: f[0] = w1 (a, b) when given full, f[2] = w2 (c, d) when given full
+  DeviceBuffer x;     // f64.  DORA: g = m / n (rows), then n (rows).  LOKR: the expanded w1 (a * b, when decomposed), then the expanded w2 (c * d, when decomposed)
+  int a = 0, b = 0, c = 0, d = 0, row_offset = 0;  // LOKR
+  bool w1_f64 = false, w2_f64 = false;
+  size_t bytes() const { return f[0].bytes() + f[1].bytes() + f[2].bytes() + f[3].bytes() + x.bytes(); }
+};
+struct AdapterDesc {
+  int kind, r, w_f64, pad;  // w_f64: bit 0 = w1 is f64, bit 1 = w2 is f64
+  const float* fa[2];            // the (r, K) factor of rank sum 0 / 1
+  const float* fb[2];            // the (rows, r) factor of rank sum 0 / 1
+  const double* g;               // DORA
+  const void *w1, *w2;           // LOKR
+  int b, c, d, row_offset;
+  double coef;                   // weight * scale (DORA: the weight alone)
+  double scale;                  // DORA
+};
+// Validates `t` against a (rows, K) Linear, uploads its factors as f32 and runs its pre-passes on the null stream (w0: the pristine rows, read by DoRA's norm;
+// the device is synchronised where a result is checked on the host).  `what` prefixes the error messages.  Changes nothing but *out.
+int adapter_term_build(const fmi_adapter_term* t, const bf16_t* w0, int rows, int K, const std::string& what, AdapterTerm* out);
+AdapterDesc adapter_term_desc(const AdapterTerm& t, double weight);
+int launch_adapter_merge(const bf16_t* w0, bf16_t* w, int rows, int K, const AdapterDesc* descs, int n_terms, hipStream_t stream);
 int launch_timestep_embedding(const float* t, int B, int dim, float* out, hipStream_t stream);
 int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, hipStream_t stream);
 int launch_cast_to_f32(const void* src, fmi_dtype dt, float* dst, int64_t n, hipStream_t stream);

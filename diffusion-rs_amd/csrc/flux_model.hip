@@ -207,19 +207,15 @@ struct fmi_flux {
   // LoRA adapters (fmi_flux_lora_*; lora.hip): merged into the resident bf16 rows.  A Linear with at least one active adapter (weight != 0) has a pristine
   // copy of its rows in lora_backup, and its effective rows are ALWAYS recomputed from that copy and every active adapter in name order (lora_remerge) —
   // never patched incrementally — so the result does not depend on the order of the calls and removing the adapters restores the loaded bits.
-  struct LoraPair {
-    DeviceBuffer A;  // (r, in) f32
-    DeviceBuffer B;  // (out, r) f32
-    int r = 0;
-    float scale = 1.f;  // alpha / r
-  };
+  // One term per (adapter, Linear): a plain pair (kind LORA: f[0] = A (r, in), f[1] = B (out, r), scale = alpha / r) or a LoHa / LoKr / DoRA term (adapter.hip).
   struct LoraAdapter {
     float weight = 1.f;
-    std::map<std::string, LoraPair> pairs;  // by weight name ("<prefix>.weight")
+    std::map<std::string, AdapterTerm> pairs;  // by weight name ("<prefix>.weight")
   };
   std::map<std::string, LoraAdapter> loras;       // by adapter name: iteration order == lexicographic order == summation order
   std::map<std::string, DeviceBuffer> lora_backup;  // by weight name: private allocations, not part of the flat state (fmi_flux_state_*)
   DeviceBuffer lora_scratch;                        // the concatenated factors of the merge in flight (grow-only; released with the last adapter)
+  DeviceBuffer lora_descs;                          // the term descriptors of a LoHa / LoKr / DoRA merge in flight (adapter.hip; grow-only, released with the scratch)
   std::vector<DeviceBuffer> lora_dead;              // blocks a LoRA call has retired (MOVED here, not freed): freed behind its one final synchronisation (lora_leave)
   // ControlNet (fmi_flux_create_controlnet): a truncated FLUX without a final layer, whose every block's image rows go through a zero-initialised
   // Linear(D, D) into a bf16 sample the main model's evaluation adds to its own f32 stream.  bf16 only: the 8-bit modes, LoRA and the quantised setters refuse it.
@@ -1758,11 +1754,10 @@ extern "C" size_t fmi_flux_size_in_bytes(const fmi_flux* m) {
   for (const Dense* d : m->fused) b += resident_code_bytes(*d);
   for (const auto& ad : m->loras)
     for (const auto& pr : ad.second.pairs) {
-      const Dest& dst = m->names.at(pr.first);
-      if (pr.second.A) b += (size_t)pr.second.r * (dst.rows + dst.cols) * 4;
+      b += pr.second.bytes();  // (f32 factors, expanded LoKr factors and DoRA's per-row vectors; 0 once the 8-bit modes have frozen the adapters)
     }
   for (const auto& bk : m->lora_backup) b += (size_t)m->names.at(bk.first).numel * 2;
-  return b + m->lora_scratch.bytes();
+  return b + m->lora_scratch.bytes() + m->lora_descs.bytes();
 }
 
 // ---- weight state as a handful of flat device buffers: the unit of the multi-GPU weight broadcast.
@@ -2431,21 +2426,33 @@ extern "C" int fmi_flux_set_attention_rescale_threshold(fmi_flux* m, int thr_x16
 namespace {
 
 // Everything a later re-merge of the Linear `wname` can need, taken BEFORE any adapter state changes (so that a failed allocation leaves the model as it
-// was): the factor scratch for the total rank of every pair on it plus `extra_r`, and the pristine copy of its rows (while there is none, the rows ARE
+// was): the factor scratch for the total rank of every plain pair on it plus the term `extra` about to arrive, the descriptor block if a term of another kind is among them, and the pristine copy of its rows (while there is none, the rows ARE
 // the loaded weights).  A copy made for a Linear that then has no active adapter is released again by lora_remerge.
-int lora_reserve(fmi_flux* m, const std::string& wname, int extra_r) {
+int lora_reserve(fmi_flux* m, const std::string& wname, const AdapterTerm* extra = nullptr) {
   const Dest& dst = m->names.at(wname);
   const int rows = dst.rows, K = dst.cols;
-  int R = extra_r;
+  // R: the plain pairs' total rank (the all-LoRA path); T: every term, `mixed`: one of them is no plain pair (the descriptors of adapter_merge_kernel)
+  int R = extra && extra->kind == FMI_ADAPTER_LORA ? extra->r : 0, T = extra ? 1 : 0;
+  bool mixed = extra && extra->kind != FMI_ADAPTER_LORA;
   for (const auto& ad : m->loras) {
     auto it = ad.second.pairs.find(wname);
-    if (it != ad.second.pairs.end()) R += it->second.r;
+    if (it == ad.second.pairs.end()) continue;
+    if (it->second.kind == FMI_ADAPTER_LORA) R += it->second.r;
+    else mixed = true;
+    ++T;
   }
-  if (R == 0) return FMI_OK;
+  if (T == 0) return FMI_OK;
+  if (mixed && m->lora_descs.bytes() < (size_t)T * sizeof(AdapterDesc)) {  // grow-only; a model of plain pairs never holds the block
+    DeviceBuffer grown;
+    hipError_t e = grown.alloc((size_t)T * sizeof(AdapterDesc));
+    if (e != hipSuccess) return fail(FMI_ERR_NOMEM, std::string("lora: hipMalloc of the term descriptors failed: ") + hipGetErrorString(e));
+    if (m->lora_descs) m->lora_dead.push_back(std::move(m->lora_descs));
+    m->lora_descs = std::move(grown);
+  }
   const int Rpad = (R + LORA_RANK_CHUNK - 1) / LORA_RANK_CHUNK * LORA_RANK_CHUNK;
   const int rows_pad = (rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * LORA_TILE_ROWS;
   const size_t need = align_up((size_t)Rpad * K * 4, 256) + (size_t)Rpad * rows_pad * 8;
-  if (m->lora_scratch.bytes() < need) {  // grow-only
+  if (R > 0 && m->lora_scratch.bytes() < need) {  // grow-only
     DeviceBuffer grown;
     hipError_t e = grown.alloc(need);
     if (e != hipSuccess) return fail(FMI_ERR_NOMEM, std::string("lora: hipMalloc of the factor scratch failed: ") + hipGetErrorString(e));
@@ -2475,17 +2482,20 @@ int lora_remerge(fmi_flux* m, const std::string& wname) {
   bf16_t* w = d->w + (size_t)d->parts[dst.part].r0 * K;
   const size_t bytes = (size_t)rows * K * 2;
   struct Term {
-    const fmi_flux::LoraPair* p;
+    const AdapterTerm* p;
+    double weight;
     double coef;  // weight * scale, exact in f64
   };
   std::vector<Term> terms;
   int R = 0;
+  bool plain = true;  // every active term is a plain pair: today's path, lora_pack_kernel + lora_merge_kernel with the same arguments
   for (const auto& ad : m->loras) {
     if (ad.second.weight == 0.f) continue;
     auto it = ad.second.pairs.find(wname);
     if (it == ad.second.pairs.end()) continue;
-    terms.push_back({&it->second, (double)ad.second.weight * (double)it->second.scale});
+    terms.push_back({&it->second, (double)ad.second.weight, (double)ad.second.weight * (double)it->second.scale});
     R += it->second.r;
+    plain = plain && it->second.kind == FMI_ADAPTER_LORA;
   }
   auto bk = m->lora_backup.find(wname);
   if (terms.empty()) {
@@ -2495,6 +2505,14 @@ int lora_remerge(fmi_flux* m, const std::string& wname) {
       m->lora_backup.erase(bk);
     }
     return FMI_OK;
+  }
+  if (!plain) {  // a LoHa / LoKr / DoRA term among them: one launch of adapter_merge_kernel over the terms in name order (plain pairs included, each as its own term)
+    if (bk == m->lora_backup.end() || m->lora_descs.bytes() < terms.size() * sizeof(AdapterDesc)) return fail(FMI_ERR_STATE, "lora: re-merge without its reserved storage");
+    std::vector<AdapterDesc> descs;
+    for (const Term& t : terms) descs.push_back(adapter_term_desc(*t.p, t.weight));
+    // (a blocking copy on the null stream: ordered behind the merge of the previous Linear, which read the same block)
+    FMI_HIP_TRY(hipMemcpy(m->lora_descs.ptr, descs.data(), descs.size() * sizeof(AdapterDesc), hipMemcpyHostToDevice));
+    return launch_adapter_merge(bk->second.as<bf16_t>(), w, rows, K, m->lora_descs.as<AdapterDesc>(), (int)descs.size(), nullptr);
   }
   const int Rpad = (R + LORA_RANK_CHUNK - 1) / LORA_RANK_CHUNK * LORA_RANK_CHUNK;
   const int rows_pad = (rows + LORA_TILE_ROWS - 1) / LORA_TILE_ROWS * LORA_TILE_ROWS;
@@ -2508,7 +2526,7 @@ int lora_remerge(fmi_flux* m, const std::string& wname) {
   }
   int off = 0;
   for (const Term& t : terms) {
-    FMI_TRY(launch_lora_pack(t.p->A.as<float>(), t.p->B.as<float>(), rows, K, t.p->r, t.coef, Acat, Bt, rows_pad, off, nullptr));
+    FMI_TRY(launch_lora_pack(t.p->f[0].as<float>(), t.p->f[1].as<float>(), rows, K, t.p->r, t.coef, Acat, Bt, rows_pad, off, nullptr));
     off += t.p->r;
   }
   return launch_lora_merge(bk->second.as<bf16_t>(), w, rows, K, Acat, Bt, rows_pad, Rpad, nullptr);
@@ -2519,7 +2537,7 @@ int lora_leave(fmi_flux* m, int rc) {
   hipError_t e = hipDeviceSynchronize();
   if (rc == FMI_OK && e != hipSuccess) rc = fail(FMI_ERR_HIP, std::string("lora: ") + hipGetErrorString(e));
   m->lora_dead.clear();
-  if (m->loras.empty()) m->lora_scratch.reset();
+  if (m->loras.empty()) m->lora_scratch.reset(), m->lora_descs.reset();
   return rc;
 }
 
@@ -2532,22 +2550,13 @@ int lora_enter(fmi_flux* m, const char* what) {
   return finalize(m);
 }
 
-// device f32 copy of a host / device array of F32 / F16 / BF16 (exact conversions)
-int lora_upload_f32(const void* src, fmi_dtype dtype, int64_t n, DeviceBuffer& out) {
-  FMI_HIP_TRY(out.alloc(n * 4));
-  return upload_as_f32(src, dtype, n, out.as<float>());
-}
-
 }  // namespace
 
-extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* prefix, const void* A, const void* B, fmi_dtype dtype, int rank, float scale) {
-  if (!m || !adapter || !prefix || !A || !B) return fail(FMI_ERR_INVALID, "lora_add: null argument");
+extern "C" int fmi_flux_lora_add_term(fmi_flux* m, const char* adapter, const char* prefix, const fmi_adapter_term* term) {
+  if (!m || !adapter || !prefix || !term) return fail(FMI_ERR_INVALID, "lora_add: null argument");
   if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "lora_add: LoRA-patched ControlNets are out of scope");
   if (m->fp8) return fail(FMI_ERR_STATE, "lora_add: the model was quantised to 8 bits; adapters go in before fmi_flux_quantize_fp8 / fmi_flux_quantize_int8");
   if (!*adapter) return fail(FMI_ERR_INVALID, "lora_add: empty adapter name");
-  if (rank < 1) return fail(FMI_ERR_INVALID, "lora_add: rank must be at least 1");
-  if (!std::isfinite(scale)) return fail(FMI_ERR_INVALID, "lora_add: scale must be finite");
-  if (dtype != FMI_F32 && dtype != FMI_F16 && dtype != FMI_BF16) return fail(FMI_ERR_INVALID, "lora_add: dtype must be F32/F16/BF16");
   const std::string wname = std::string(prefix) + ".weight";
   auto it = m->names.find(wname);
   if (it == m->names.end() || !it->second.d || it->second.bias || !it->second.cols)
@@ -2558,15 +2567,28 @@ extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* p
   if (!part_is_plain(*d, dst.part))
     return fail(FMI_ERR_UNSUPPORTED, std::string("lora_add: ") + prefix + " is resident as nf4 / fp4 / LLM.int8 codes; merging into packed codes is not implemented");
   if (dst.cols % 8) return fail(FMI_ERR_UNSUPPORTED, "lora_add: in_features must be a multiple of 8");
-  fmi_flux::LoraPair np;
-  np.r = rank, np.scale = scale;
-  FMI_TRY(lora_upload_f32(A, dtype, (int64_t)rank * dst.cols, np.A));
-  FMI_TRY(lora_upload_f32(B, dtype, (int64_t)dst.rows * rank, np.B));
+  // the pristine rows (DoRA's norm reads them): the copy while the Linear has one, else the resident rows, which then ARE the loaded weights
+  auto bk = m->lora_backup.find(wname);
+  const bf16_t* w0 = bk != m->lora_backup.end() ? bk->second.as<bf16_t>() : d->w + (size_t)d->parts[dst.part].r0 * dst.cols;
+  AdapterTerm nt;
+  FMI_TRY(adapter_term_build(term, w0, dst.rows, dst.cols, std::string("lora_add: ") + prefix, &nt));
   // storage first, state second: until here nothing of the model has changed, and a re-merge allocates nothing
-  if (int rc = lora_reserve(m, wname, rank)) return lora_leave(m, rc);
-  // re-adding a pair replaces it: the move-assignment frees the slot's earlier factors HERE (the device is idle: lora_enter), after lora_reserve
-  m->loras[adapter].pairs[wname] = std::move(np);  // (a new adapter starts at weight 1)
+  if (int rc = lora_reserve(m, wname, &nt)) return lora_leave(m, rc);
+  // re-adding a term replaces it: the move-assignment frees the slot's earlier factors HERE (the device is idle: lora_enter), after lora_reserve
+  m->loras[adapter].pairs[wname] = std::move(nt);  // (a new adapter starts at weight 1)
   return lora_leave(m, lora_remerge(m, wname));
+}
+
+extern "C" int fmi_flux_lora_add(fmi_flux* m, const char* adapter, const char* prefix, const void* A, const void* B, fmi_dtype dtype, int rank, float scale) {
+  if (!m || !adapter || !prefix || !A || !B) return fail(FMI_ERR_INVALID, "lora_add: null argument");
+  if (rank < 1) return fail(FMI_ERR_INVALID, "lora_add: rank must be at least 1");
+  fmi_adapter_term t{};
+  t.kind = FMI_ADAPTER_LORA, t.dtype = dtype, t.scale = scale;
+  t.factor[0] = A, t.factor[1] = B;
+  auto it = m->names.find(std::string(prefix) + ".weight");  // (the factors' shapes follow from the rank and the Linear, as this entry always took them)
+  const int rows = it != m->names.end() ? it->second.rows : 1, K = it != m->names.end() && it->second.cols ? it->second.cols : 1;
+  t.factor_rows[0] = rank, t.factor_cols[0] = K, t.factor_rows[1] = rows, t.factor_cols[1] = rank;
+  return fmi_flux_lora_add_term(m, adapter, prefix, &t);
 }
 
 extern "C" int fmi_flux_lora_set_weight(fmi_flux* m, const char* adapter, float weight) {
@@ -2579,7 +2601,7 @@ extern "C" int fmi_flux_lora_set_weight(fmi_flux* m, const char* adapter, float 
   FMI_TRY(lora_enter(m, "lora_set_weight"));
   int rc = FMI_OK;
   for (const auto& pr : it->second.pairs)
-    if ((rc = lora_reserve(m, pr.first, 0)) != FMI_OK) return lora_leave(m, rc);  // (nothing has changed yet)
+    if ((rc = lora_reserve(m, pr.first)) != FMI_OK) return lora_leave(m, rc);  // (nothing has changed yet)
   it->second.weight = weight;
   for (const auto& pr : it->second.pairs)
     if ((rc = lora_remerge(m, pr.first)) != FMI_OK) break;
@@ -2599,7 +2621,7 @@ extern "C" int fmi_flux_lora_remove(fmi_flux* m, const char* adapter) {
       for (const auto& pr : ad.second.pairs) touched.insert(pr.first);
   int rc = FMI_OK;
   for (const std::string& wname : touched)
-    if ((rc = lora_reserve(m, wname, 0)) != FMI_OK) return lora_leave(m, rc);  // (nothing has changed yet)
+    if ((rc = lora_reserve(m, wname)) != FMI_OK) return lora_leave(m, rc);  // (nothing has changed yet)
   for (auto ad = m->loras.begin(); ad != m->loras.end();) {
     if (adapter && ad->first != adapter) {
       ++ad;
@@ -2616,9 +2638,13 @@ extern "C" int fmi_flux_lora_remove(fmi_flux* m, const char* adapter) {
 static void lora_release_storage(fmi_flux* m) {
   hipDeviceSynchronize();
   for (auto& ad : m->loras)
-    for (auto& pr : ad.second.pairs) pr.second.A.reset(), pr.second.B.reset();
+    for (auto& pr : ad.second.pairs) {
+      for (DeviceBuffer& f : pr.second.f) f.reset();
+      pr.second.x.reset();
+    }
   m->lora_backup.clear();
   m->lora_scratch.reset();
+  m->lora_descs.reset();
 }
 
 extern "C" int fmi_flux_lora_count(const fmi_flux* m) { return m ? (int)m->loras.size() : 0; }

@@ -379,6 +379,38 @@ class FluxModel:
             raise L.FmiError(f"lora_add: {prefix}: B A is {(sb[0], sa[1])}, the Linear is {tuple(want)}", code=L.ERR_INVALID)
         L.check(self.lib.fmi_flux_lora_add(self.h, adapter.encode(), prefix.encode(), pa, pb, dta, int(sa[0]), float(scale)), self.lib)
 
+    def lora_add_term(self, adapter: str, prefix: str, term):
+        """One term (lora.AdapterTerm: a plain pair, LoHa, LoKr or DoRA) of `adapter` for the Linear `prefix`; its tensors are torch tensors (any device)
+        or numpy arrays, F32 / F16 / BF16 (mixed dtypes are widened to F32).  Takes effect before it returns; a term the adapter already holds for that
+        Linear is replaced.  The library validates the shapes against the Linear."""
+        kinds = {"lora": L.ADAPTER_LORA, "loha": L.ADAPTER_LOHA, "lokr": L.ADAPTER_LOKR, "dora": L.ADAPTER_DORA}
+        kind = kinds.get(term.kind, term.kind)
+        if not isinstance(kind, int):
+            raise L.FmiError(f"lora_add_term: {prefix}: unknown adapter kind {term.kind!r}", code=L.ERR_INVALID)
+        tensors = list(term.tensors)
+        args = [None if t is None else _tensor_arg(t) for t in tensors]
+        if len({a[1] for a in args if a is not None}) > 1:
+            args = [None if t is None else _tensor_arg(_as_f32(t)) for t in tensors]
+        factors, mag = args[:4], None
+        if kind in (L.ADAPTER_LORA, L.ADAPTER_DORA):  # (A, B[, m])
+            factors, mag = args[:2], (args[2] if len(args) > 2 else None)
+        ct = L.AdapterTermC(kind=kind, dtype=next((a[1] for a in args if a is not None), L.F32), scale=float(term.scale), row_offset=int(term.row_offset))
+        for i, a in enumerate(factors):
+            if a is None:
+                continue
+            if len(a[2]) != 2:
+                raise L.FmiError(f"lora_add_term: {prefix}: factor {i} has shape {tuple(a[2])}, not a matrix", code=L.ERR_INVALID)
+            ct.factor[i], ct.factor_rows[i], ct.factor_cols[i] = a[0], int(a[2][0]), int(a[2][1])
+        if mag is not None:
+            want = self._shapes().get(prefix + ".weight")
+            n = 1
+            for v in mag[2]:
+                n *= int(v)
+            if want is not None and n != want[0]:
+                raise L.FmiError(f"lora_add_term: {prefix}: the magnitude has {n} values, the Linear has {want[0]} rows", code=L.ERR_INVALID)
+            ct.magnitude = mag[0]
+        L.check(self.lib.fmi_flux_lora_add_term(self.h, adapter.encode(), prefix.encode(), C.byref(ct)), self.lib)
+
     def lora_set_weight(self, adapter: str, weight: float):
         L.check(self.lib.fmi_flux_lora_set_weight(self.h, adapter.encode(), float(weight)), self.lib)
 

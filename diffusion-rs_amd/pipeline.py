@@ -1159,28 +1159,33 @@ class Pipeline:
     # ModelDType.I8 they work until the first request has quantised the model, afterwards the library answers with its state error.  Under
     # torch.distributed every rank makes the same call on its own copy of the weights: there is no collective.
     def load_lora(self, path_or_dict, name: Optional[str] = None, weight: float = 1.0, skip_unsupported: bool = False) -> str:
-        """Merge the adapter of a .safetensors file (diffusers / PEFT or kohya / BFL keys) or of a {key: tensor} dict into the DiT; returns its name
-        (default: the file's base name).  Several adapters stack; the result does not depend on the order they were loaded in."""
+        """Merge the adapter of a .safetensors file (diffusers / PEFT or kohya / BFL keys; LoRA, LoHa, LoKr, full differences, DoRA: lora.read_adapter) or
+        of a {key: tensor} dict into the DiT; returns its name (default: the file's base name).  Several adapters stack; the result does not depend on the order they were loaded in."""
         from . import lora
-        pairs = lora.read_lora(path_or_dict, skip_unsupported=skip_unsupported, hidden_size=self.flux.hidden)
+        terms = lora.read_adapter(path_or_dict, skip_unsupported=skip_unsupported, hidden_size=self.flux.hidden)
         if name is None:
             name = os.path.splitext(os.path.basename(os.fspath(path_or_dict)))[0] if isinstance(path_or_dict, (str, os.PathLike)) else "lora"
-        if not pairs:
+        if not terms:
             raise ValueError(f"LoRA '{name}': no supported keys")
         shapes = self.flux._shapes()
-        for prefix, (A, B, _) in pairs.items():
+        for prefix, term in terms.items():
             want = shapes.get(prefix + ".weight")
             if want is None or len(want) != 2:
                 raise ValueError(f"LoRA '{name}': {prefix} is not a Linear of this model")
-            if (int(B.shape[0]), int(A.shape[1])) != tuple(want):
-                raise ValueError(f"LoRA '{name}': {prefix}: B A is {(int(B.shape[0]), int(A.shape[1]))}, the Linear is {tuple(want)}")
+            if term.kind in ("lora", "dora"):  # (the factor shapes of the other kinds are checked by the library, which refuses before it changes anything)
+                A, B = term.tensors[:2]
+                if (int(B.shape[0]), int(A.shape[1])) != tuple(want):
+                    raise ValueError(f"LoRA '{name}': {prefix}: B A is {(int(B.shape[0]), int(A.shape[1]))}, the Linear is {tuple(want)}")
         with self._lock:
             if name in self.flux.loras():
                 raise ValueError(f"a LoRA named '{name}' is loaded already: unload_lora('{name}') first, or pass another name")
             try:
                 first = True
-                for prefix, (A, B, scale) in pairs.items():
-                    self.flux.lora_add(name, prefix, A, B, scale)
+                for prefix, term in terms.items():
+                    if term.kind == "lora":
+                        self.flux.lora_add(name, prefix, term.tensors[0], term.tensors[1], term.scale)
+                    else:
+                        self.flux.lora_add_term(name, prefix, term)
                     if first and weight != 1.0:  # before the other pairs arrive: each Linear is then merged once, at its final weight
                         self.flux.lora_set_weight(name, weight)
                     first = False

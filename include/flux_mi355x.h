@@ -272,6 +272,48 @@ int fmi_flux_lora_set_weight(fmi_flux*, const char* adapter, float weight);
 int fmi_flux_lora_remove(fmi_flux*, const char* adapter);
 int fmi_flux_lora_count(const fmi_flux*);
 const char* fmi_flux_lora_name(const fmi_flux*, int i);
+
+/* LyCORIS and DoRA adapters: the other parametrisations FLUX adapters are written in, merged like LoRA.  For a Linear with loaded weight W0 (out, in)
+ *     W = bf16_rne( W0 + sum_a weight_a * Delta_a ),   adapters in lexicographic name order, ONE rounding, always from the pristine copy of W0,
+ * and Delta depends on the term's kind (which fields of fmi_adapter_term are read is listed per kind; every tensor has the one `dtype`, F32 / F16 / BF16,
+ * and is row-major; pointers may be host or device memory for fmi_flux_lora_add_term and are device memory for fmi_adapter_merge):
+ *   FMI_ADAPTER_LORA  Delta = scale * B A.                       factor[0] = A (r, in), factor[1] = B (out, r).
+ *   FMI_ADAPTER_LOHA  Delta = scale * (w1_a w1_b) (.) (w2_a w2_b), (.) element-wise.
+ *                     factor[0] = hada_w1_a (out, r), factor[1] = hada_w1_b (r, in), factor[2] = hada_w2_a (out, r), factor[3] = hada_w2_b (r, in).
+ *   FMI_ADAPTER_LOKR  Delta[i, j] = scale * w1[(i + row_offset) / c, j / d] * w2[(i + row_offset) % c, j % d], w1 (a, b), w2 (c, d), b * d == in,
+ *                     row_offset + out <= a * c.  factor[0] = lokr_w1 (a, b) with factor[1] NULL, or factor[0] = lokr_w1_a (a, r1) and
+ *                     factor[1] = lokr_w1_b (r1, b); factor[2] / factor[3] the same for w2.  row_offset is the first row of this Linear inside a
+ *                     fused module the factors describe (0 otherwise).  A full difference (`.diff`) is w1 = [[1]], w2 = the (out, in) tensor.
+ *   FMI_ADAPTER_DORA  with V = W0 + scale * B A and n_i = ||V[i, :]||_2:  Delta = m (.) V / n - W0 (row i scaled by m_i / n_i).
+ *                     factor[0] = A, factor[1] = B as for LORA, magnitude = m (out values).  The norm uses the pristine W0 and this term alone; it is
+ *                     computed once when the term is added.  A row with n_i zero or not finite is FMI_ERR_INVALID.
+ * factor_rows / factor_cols give the shape of each non-NULL factor.  `scale` is alpha / r (the file reader's rule; the library multiplies by it as given).
+ * Numerics: factors resident as f32 (exact conversions), every product, sum, square root and division in f64 (DoRA's row sum of squares by a fixed
+ * reduction tree: the same bits from run to run), W0 plus all terms rounded once (f64 -> f32 to odd -> bf16 to nearest-even).  Only a Linear whose
+ * active terms are all plain LoRA keeps the claim "correctly rounded value of the exact expression" (it runs exactly the LoRA path above); the other
+ * kinds multiply or divide rounded f64 values, so an element is the one rounding of an f64 evaluation of the formula.
+ * The formulas are written down from memory of PEFT, LyCORIS and ComfyUI; no file or output of those libraries was compared.
+ *   fmi_flux_lora_add_term   the contract of fmi_flux_lora_add (which is this call with kind LORA): replaces the adapter's term on that Linear, a new
+ *                            adapter starts at weight 1, validates first and changes nothing on error.  Further FMI_ERR_INVALID cases: an unknown kind,
+ *                            factor shapes that disagree with the Linear or with each other (b * d != in, row_offset + out > a * c, unequal LoHa
+ *                            ranks, a missing factor), a DoRA row norm of zero (the message names the Linear).
+ *   fmi_adapter_merge        the op-level entry the model's re-merge runs through: w (rows, K) bf16 <- W0 (rows, K) bf16 plus the terms in the ORDER GIVEN,
+ *                            term i at weights[i].  Device pointers; K % 8 == 0, 16-byte aligned w0 / w; completes before it returns.
+ * fmi_flux_lora_set_weight / _remove / _count / _name cover every kind, and everything said above about adapted weights (set_tensor, the quantised
+ * setters, state_adopt, the 8-bit freeze, ControlNets, packed Linears) holds for every kind. */
+typedef enum { FMI_ADAPTER_LORA = 0, FMI_ADAPTER_LOHA = 1, FMI_ADAPTER_LOKR = 2, FMI_ADAPTER_DORA = 3 } fmi_adapter_kind;
+typedef struct fmi_adapter_term {
+  int kind;                /* fmi_adapter_kind */
+  int dtype;               /* fmi_dtype of every tensor of the term */
+  float scale;
+  int row_offset;          /* LOKR */
+  const void* factor[4];
+  int factor_rows[4];
+  int factor_cols[4];
+  const void* magnitude;   /* DORA: out values */
+} fmi_adapter_term;
+int fmi_flux_lora_add_term(fmi_flux*, const char* adapter, const char* prefix, const fmi_adapter_term* term);
+int fmi_adapter_merge(const void* w0_bf16, void* w_bf16, int rows, int K, const fmi_adapter_term* terms, const float* weights, int n_terms, void* stream);
 /* Single-image sequence parallelism.  The reference runs one image on one device
  * (pipelines/mod.rs:214-217 "This will need to be updated!"); here the tokens of ONE image are sharded over the
  * world_size ranks of a group: rank r passes ONLY its token shard to fmi_flux_forward / fmi_flux_denoise
