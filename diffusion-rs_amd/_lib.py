@@ -340,6 +340,8 @@ def _declare(lib):
     lib.fmi_gemm_group.argtypes = [C.POINTER(GemmDesc), C.c_int, C.c_void_p]
     lib.fmi_splitk_resid_gate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_set_gemm_kernel.argtypes = [C.c_int, C.c_int]
+    lib.fmi_set_gemm_rows.argtypes = [C.c_int]
+    lib.fmi_gemm_tile_rows.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5
     lib.fmi_linear_fp8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.fmi_quantize_rows_i8.argtypes = lib.fmi_quantize_rows_fp8.argtypes
     lib.fmi_linear_i8.argtypes = lib.fmi_linear_fp8.argtypes
@@ -436,7 +438,7 @@ EXPORTED = [
     "fmi_redux_create", "fmi_redux_destroy", "fmi_redux_set_tensor", "fmi_redux_missing_count", "fmi_redux_missing_name", "fmi_redux_size_in_bytes", "fmi_redux_forward",
     "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
     "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids", "fmi_cfg_euler_step", "fmi_cast_cols_bf16", "fmi_mask_image", "fmi_fill_condition",
-    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
+    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_set_gemm_rows", "fmi_gemm_tile_rows", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_layernorm_mod",
     "fmi_release_scratch", "fmi_timestep_embedding", "fmi_rope_table", "fmi_rmsnorm_rope",
     "fmi_groupnorm_nhwc", "fmi_conv2d_nhwc",
     "fmi_comm_probe", "fmi_comm_unique_id", "fmi_comm_create", "fmi_comm_destroy", "fmi_comm_rank", "fmi_comm_world_size", "fmi_comm_stats", "fmi_comm_all_to_all",

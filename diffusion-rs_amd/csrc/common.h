@@ -354,6 +354,9 @@ void set_gemm_w4(bool on);             // residual-update launches (N > 128, no 
 void set_gemm_pingpong(bool on);       // dense N > 128 launches: the ping-pong kernel (default) or the double-buffered one
 void set_gemm_w4q_min_rows(int rows);  // 4-bit weights: M from which the one-wave-per-SIMD fused dequant-GEMM runs (default 256)
 void set_gemm_w4_qkv_min_n(int n);     // dense fused-relayout launches at least this wide run on the 4-wave kernel (default: never)
+int set_gemm_rows(int rows);           // tile heights of the bf16 ping-pong kernel: 0 = per launch (pick_tile_rows), 256, 192, 448 = mixed at any size
+// the split pick_tile_rows makes of a group (pure; tests): n256 / n192 per problem, returns the modelled makespan in quarter rounds
+int gemm_tile_rows_of(const int* M, const int* N, int nprob, int cus, int q8, int mode, int* n256, int* n192, int* tall_start, int* short_start);
 
 // attention output routing: query rows [0,rows0) -> p0, the rest -> p1 (token-major, head h at
 // column h*128); or head-major (B,H,Lq,128) in p1.

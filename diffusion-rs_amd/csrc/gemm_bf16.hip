@@ -19,6 +19,8 @@
 //   * Operands are swapped (W rows feed the MFMA A operand, x rows feed B) so every lane ends
 //     up with 4 consecutive output columns of one row: 8-byte bf16 / 16-byte f32 stores and
 //     vector loads of bias / gate in the epilogue.
+//   * The dense bf16 ping-pong kernel also has a 192-row tile (96 x 64 per wave) and mixes the two heights inside one launch where a
+//     scheduling model says the last round of tiles is cheaper that way (pick_tile_rows); rows are split, never K: same bits.
 //   * One barrier per K tile; the DMA of tile k+1 is in flight while tile k is multiplied.
 //   * Grouped launch (img + txt streams of a double block in one grid) and an XCD-aware
 //     bijective block remap so tiles sharing a W panel sit on the same XCD's L2.
@@ -52,7 +54,15 @@ struct GemmBatch {
   int tile_start[MAX_PROBLEMS + 1];
   int band[MAX_PROBLEMS];  // tile-rows per band of problem i's tile order (pick_tile_band)
   int nprob;
+  // Mixed tile heights (gemm_pp_kernel<0, .> only, pick_tile_rows): problem i's first n256[i] * 256 rows are cut into 256-row tiles, the rest
+  // into 192-row tiles.  The launch gives out the tall tiles of ALL problems first (tile_start: problem i's tall region, tile_start[nprob] = their
+  // number), then the short ones (short_start: absolute, short_start[nprob] = grid size), so that the in-order dispatch is a longest-first
+  // schedule; band_s = band height of problem i's short region.  A launch without short tiles has n256 = all tile rows and short_start = the total.
+  int short_start[MAX_PROBLEMS + 1];
+  int n256[MAX_PROBLEMS];
+  int band_s[MAX_PROBLEMS];
 };
+constexpr int BM_SHORT = 192;  // the short tile: 96 rows per wave group
 
 }  // namespace fmi
 #include "gemm_frame.h"
@@ -146,12 +156,14 @@ __device__ __forceinline__ void stage_tile_q4(const GemmProblem& P, int n0, int 
 //   Acc32: v_mfma_f32_32x32x16_bf16 / 32x32x64_f8 with swapped operands: acc[i][j] is rows 32 i + (lane & 31), columns
 //          32 j + 8 q + 4 (lane >> 5) + {0..3} in registers 4 q .. 4 q + 3.
 //   Acc16: v_mfma_f32_16x16x32_bf16: acc[tm][tn] is rows 16 tm + (lane & 15), columns 16 tn + 4 (lane >> 4) + {0..3}.
+// kRows = rows of the sub-tile (a "half" is kRows / 2 of them); the epilogues take every row count from it.
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) int i32x4_nt;
 template <int NJ>
 struct Acc32 {
   f32x16 (&a)[4][NJ];
   int lane;
+  static constexpr int kRows = 128;  // rows of the wave's sub-tile
   static constexpr bool kFence = NJ == 4;
   static constexpr int kSlots = 4 * NJ;
   template <class F>
@@ -182,10 +194,12 @@ struct Acc32 {
     }
   }
 };
-template <int NJ>
+// RB = 16-row blocks of the wave's sub-tile: 8 (128 rows, the 256-row tile) or 6 (96 rows, the 192-row tile of gemm_pp_kernel)
+template <int NJ, int RB = 8>
 struct Acc16 {
-  f32x4 (&a)[8][2 * NJ];
+  f32x4 (&a)[RB][2 * NJ];
   int lane;
+  static constexpr int kRows = 16 * RB;
   static constexpr bool kFence = NJ == 4;
   static constexpr int kSlots = 2 * NJ;
   template <class F>
@@ -198,8 +212,8 @@ struct Acc16 {
   __device__ __forceinline__ void each(F&& f) const {
     const int l15 = lane & 15, l4 = lane >> 4;
 #pragma unroll
-    for (int tm = 0; tm < 8; ++tm) {
-      if (HALF >= 0 && (tm >> 2) != HALF) continue;
+    for (int tm = 0; tm < RB; ++tm) {
+      if (HALF >= 0 && tm / (RB / 2) != HALF) continue;
 #pragma unroll
       for (int tn = 0; tn < 2 * NJ; ++tn) {
         float v[4];
@@ -248,7 +262,7 @@ __device__ __forceinline__ void qkv_relayout_stage(const GemmProblem& P, const A
     // index on the way in, so that a row leaves as plain 16-B pieces of consecutive stored positions
     bf16_t* tp = reinterpret_cast<bf16_t*>(smem);
     acc.template each<-1>([&](int r, int c, float (&v)[4], int slot) {
-      const int tl = wm * 128 + r;
+      const int tl = wm * ACC::kRows + r;
       const int tpos = (tl & ~12) | ((tl & 4) << 1) | ((tl & 8) >> 1);
       const int dc = wn * 64 + 4 * c;
       biased(slot, v);
@@ -258,12 +272,14 @@ __device__ __forceinline__ void qkv_relayout_stage(const GemmProblem& P, const A
   }
 }
 
+// ROWS = rows per wave group (ACC::kRows of the stage: 128, or 96 in a 192-row tile): the tile is 2 ROWS tokens
+template <int ROWS>
 __device__ __forceinline__ void qkv_relayout_emit(const GemmProblem& P, char* smem, int m0, int n0, int wave, int lane) {
   const int hl = lane >> 5;
   const int part = n0 / P.qk_D;                     // 0 q, 1 k, 2 v
   const int head0 = (n0 - part * P.qk_D) >> 7;      // first of the tile's two heads
   if (part < 2) {
-    // ---- 512 (row, head) vectors of 128: 16 lanes x 8 elements each; row group `wave` is rows 32*wave .. +31
+    // ---- 4 ROWS (row, head) vectors of 128: 16 lanes x 8 elements each; row group `wave` is rows (ROWS / 4) * wave .. + ROWS / 4 - 1
     const int sub = lane & 15, grp = lane >> 4;
     const bf16_t* wsel = part == 0 ? P.qk_wq : P.qk_wk;
     bf16_t* osel = part == 0 ? P.qk_qh : P.qk_kh;
@@ -282,11 +298,11 @@ __device__ __forceinline__ void qkv_relayout_emit(const GemmProblem& P, char* sm
     };
     constexpr int GRP = 4;
 #pragma unroll 1
-    for (int it0 = 0; it0 < 16; it0 += GRP) {
+    for (int it0 = 0; it0 < ROWS / 8; it0 += GRP) {
       float4 pc01[GRP], pc23[GRP];
 #pragma unroll
       for (int u = 0; u < GRP; ++u) {
-        const int mc = min(m0 + ((wave * 64 + (it0 + u) * 4 + grp) >> 1), P.M - 1);
+        const int mc = min(m0 + ((wave * (ROWS / 2) + (it0 + u) * 4 + grp) >> 1), P.M - 1);
         int b, pos;
         locate(mc, b, pos);
         const float4* pp = reinterpret_cast<const float4*>(P.qk_pe + (int64_t)b * P.qk_pe_bstride + ((int64_t)pos * 64 + 4 * sub) * 2);
@@ -294,12 +310,12 @@ __device__ __forceinline__ void qkv_relayout_emit(const GemmProblem& P, char* sm
       }
 #pragma unroll
       for (int u = 0; u < GRP; ++u) {
-        const int item = wave * 64 + (it0 + u) * 4 + grp;
+        const int item = wave * (ROWS / 2) + (it0 + u) * 4 + grp;
         const int r = item >> 1, hh = item & 1;
         const int m = m0 + r;
-        // source: staging region of wave (r>>7, 2*hh + (sub>>3)), row r&127, 16 B = 8-B slots 2*(sub&7), +1
-        const int rr = r & 127;
-        const char* reg = smem + ((r >> 7) * 4 + 2 * hh + (sub >> 3)) * 16384 + rr * 128;
+        // source: staging region of wave (r / ROWS, 2*hh + (sub>>3)), row r % ROWS, 16 B = 8-B slots 2*(sub&7), +1
+        const int rr = r % ROWS;
+        const char* reg = smem + ((r / ROWS) * 4 + 2 * hh + (sub >> 3)) * 16384 + rr * 128;
         const int sp = ((2 * (sub & 7)) ^ (rr & 15)) & ~1;
         uint4 raw = *reinterpret_cast<const uint4*>(reg + (sp << 3));
         if (rr & 1) raw = make_uint4(raw.z, raw.w, raw.x, raw.y);  // odd rows hold the slot pair swapped
@@ -350,7 +366,7 @@ __device__ __forceinline__ void qkv_relayout_emit(const GemmProblem& P, char* sm
     for (int it = 0; it < 16; ++it) {
       const int dc = wave * 32 + it * 2 + hl;
       const int m16 = m0 + 16 * (g8 >> 1);  // the 16 tokens this piece's group comes from
-      if (m16 < P.M) {
+      if (m16 < P.M && g8 < ROWS / 4) {  // (a 192-row tile fills 24 of the row's 32 pieces)
         const uint4 x = *reinterpret_cast<const uint4*>(tp + dc * 256 + g8 * 8);
         const int b = m16 / P.qk_rows, kv16 = P.qk_row_off + (m16 - b * P.qk_rows);
         bf16_t* dst = P.qk_vt + (((int64_t)b * P.qk_H + head0 + (dc >> 7)) * 128 + (dc & 127)) * P.qk_Lpad + kv16 + (g8 & 1) * 8;
@@ -365,7 +381,7 @@ __device__ __forceinline__ void qkv_relayout_epilogue(const GemmProblem& P, cons
   __syncthreads();  // every wave is done with the operand tiles
   qkv_relayout_stage(P, acc, smem, n0, wave, lane);
   __syncthreads();
-  qkv_relayout_emit(P, smem, m0, n0, wave, lane);
+  qkv_relayout_emit<ACC::kRows>(P, smem, m0, n0, wave, lane);
 }
 
 // WN = waves along N (4: the 8-wave kernels, wave = wm*4 + wn, 128 x 32*NJ per wave; 2: the 4-wave kernel, 128 x 128 per wave)
@@ -477,12 +493,12 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
       constexpr int LPR = RB / 16, RPI = 64 / LPR;  // lanes per row, rows per wave-instruction
       bf16_t* ob = reinterpret_cast<bf16_t*>(P.out);
 #pragma unroll
-      for (int it = 0; it < 128 / RPI; ++it) {
+      for (int it = 0; it < ACC::kRows / RPI; ++it) {
         const int r = it * RPI + lane / LPR, ch = lane % LPR;
         const int sp = ((2 * ch) ^ (r & (NS8 - 1))) & ~1;
         uint4 d = *reinterpret_cast<const uint4*>(cw + r * RB + (sp << 3));
         if (r & 1) d = make_uint4(d.z, d.w, d.x, d.y);  // odd rows hold the slot pair swapped
-        const int m = m0 + wm * 128 + r;
+        const int m = m0 + wm * ACC::kRows + r;
         // non-temporal: the tile's 128 KiB of output would otherwise push operand panels of the patch out of the XCD's L2 (measured: -1.5 %
         // per bf16-out launch stand-alone, -3 % on the one-round ones; -0.3 ms per denoise step with the consumers' reads included)
         if (m < P.M) __builtin_nontemporal_store(*reinterpret_cast<const i32x4_nt*>(&d), reinterpret_cast<i32x4_nt*>(ob + (int64_t)m * P.ldo + ncol0 + ch * 8));
@@ -494,6 +510,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
       constexpr int RBF = 128 * NJ;  // bytes per staged row (32*NJ f32)
       constexpr int NS16 = 8 * NJ;   // 16-byte slots per row
       constexpr int LPR = RBF / 16, RPI = 64 / LPR;
+      constexpr int HR = ACC::kRows / 2;  // rows per pass
       float* of = reinterpret_cast<float*>(P.out);
       // (explicit instantiation instead of a pragma: with 128-wide wave tiles the optimizer refuses to unroll a loop
       // this large, and a dynamically indexed accumulator array lives in scratch)
@@ -502,24 +519,25 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         acc.template each<pass>([&](int rg, int c, float (&v)[4], int slot) {
           finish_s(slot, ncol0 + 4 * c, v);
-          const int r = rg - pass * 64;  // row inside this 64-row pass
+          const int r = rg - pass * HR;  // row inside this pass (half of the sub-tile's rows)
           *reinterpret_cast<float4*>(cw + r * RBF + ((c ^ (r & (NS16 - 1))) << 4)) = make_float4(v[0], v[1], v[2], v[3]);
         });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        constexpr int NIT = 64 / RPI;
+        constexpr int NIT = HR / RPI;
         const int ch = lane % LPR, n = ncol0 + ch * 4;
         if (epi == EPI_RESID_GATE_F32) {
           // residual read-modify-write: the loads of GRP rows are issued back to back, then consumed — one HBM / L2 round
           // trip per GRP rows instead of one per row (the compiler otherwise waits vmcnt(0) in front of every store: measured
           // ~16 us per tile, all of it latency)
-          constexpr int GRP = NIT < 8 ? NIT : 8;
+          constexpr int GRP = NIT < 8 ? NIT : NIT % 8 == 0 ? 8 : 6;  // (96-row sub-tile: 12 row instructions per pass)
+          static_assert(NIT % GRP == 0, "the row groups must tile a pass");
 #pragma unroll
           for (int g0 = 0; g0 < NIT; g0 += GRP) {
             float4 xr[GRP], gg[GRP];
 #pragma unroll
             for (int u = 0; u < GRP; ++u) {
               const int r = (g0 + u) * RPI + lane / LPR;
-              const int m = min(m0 + wm * 128 + pass * 64 + r, P.M - 1);  // clamped, not predicated: no branch between the loads
+              const int m = min(m0 + wm * ACC::kRows + pass * HR + r, P.M - 1);  // clamped, not predicated: no branch between the loads
               const float* gate = P.gate + (P.rows_per_batch > 0 ? (int64_t)(m / P.rows_per_batch) * P.gate_bstride : 0);
               gg[u] = *reinterpret_cast<const float4*>(gate + n);
               xr[u] = *reinterpret_cast<const float4*>(of + (int64_t)m * P.ldo + n);
@@ -527,7 +545,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
 #pragma unroll
             for (int u = 0; u < GRP; ++u) {
               const int r = (g0 + u) * RPI + lane / LPR;
-              const int m = m0 + wm * 128 + pass * 64 + r;
+              const int m = m0 + wm * ACC::kRows + pass * HR + r;
               const float4 v = *reinterpret_cast<const float4*>(cw + r * RBF + ((ch ^ (r & (NS16 - 1))) << 4));
               if (m < P.M) {
                 float4 x = xr[u];
@@ -544,7 +562,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
           for (int it = 0; it < NIT; ++it) {
             const int r = it * RPI + lane / LPR;
             const float4 v = *reinterpret_cast<const float4*>(cw + r * RBF + ((ch ^ (r & (NS16 - 1))) << 4));
-            const int m = m0 + wm * 128 + pass * 64 + r;
+            const int m = m0 + wm * ACC::kRows + pass * HR + r;
             if (m < P.M) *reinterpret_cast<float4*>(of + (int64_t)m * P.ldo + n) = v;
           }
         }
@@ -556,7 +574,7 @@ __device__ __forceinline__ void gemm_epilogue_impl(const GemmProblem& P, const A
   }
   // ---- direct path (ragged N tile, unaligned output, bf16 residual add)
   acc.template each<-1>([&](int r, int c, float (&v)[4], int) {
-    const int m = m0 + wm * 128 + r;
+    const int m = m0 + wm * ACC::kRows + r;
     const int n = n0 + wn * 32 * NJ + 4 * c;
     if (m >= P.M || n >= P.N) return;
     const float* gate = P.gate;
@@ -800,235 +818,29 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(const GemmBa
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(16))) int i32x16_t;
+//
+// Tile height: RB = 16-row MFMA blocks per wave.  8 is the 256-row tile described above.  6 is the 192-row tile (bf16 only): each group owns 96
+// rows, a wave 96 x 64 of C; the A tile is 24 of the 32 chunks of its slot, 3 DMA pieces per wave instead of 4 (the W side is unchanged), 20
+// fragment reads and 24 MFMAs per LOAD / COMPUTE.  It splits rows, never K: an output element is accumulated in the same order by the same
+// instructions and leaves through the same epilogue arithmetic, so a launch may mix the two heights freely (GemmBatch::n256, pick_tile_rows) and
+// give the same bits.  The kernel branches once, on the workgroup's height.  The e4m3 and int8 forms (<1 | 2, .>) have the 256-row tile only.
 template <int Q8, int ACT>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_pp_kernel(const GemmBatch batch) {
-  constexpr bool FP8 = Q8 != 0;  // 8-bit operands: 1 = OCP e4m3, 2 = int8 (GemmProblem::fp8)
-  constexpr bool I8 = Q8 == 2;
-  constexpr int NJ = 2, BN = 256;
-  constexpr int ES = FP8 ? 1 : 2;  // operand element size
-  constexpr int A_RING = 0, W_RING = 2 * A_TILE_BYTES, TILE = A_TILE_BYTES;  // 2 x 32 KiB + 3 x 32 KiB
-  __shared__ __attribute__((aligned(16))) char smem[5 * TILE];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = wave >> 2, wn = wave & 3;  // group = row half (wm)
-
-  const GemmTile tile = gemm_tile<BN>(batch, ES);  // which problem / tile
-  const GemmProblem& P = tile.P;
-  const int m0 = tile.m0, n0 = tile.n0, nk = tile.nk;
-
-  // fp8: v_mfma_f32_32x32x64_f8f6f4, accumulators acc[4][NJ] of 32 x 32 (Acc32).  bf16: v_mfma_f32_16x16x32_bf16, accumulators
-  // acc16[8][2 NJ] of 16 x 16 (Acc16) — on this power-capped part the 16 x 16 x 32 form sustains 14 % more than 32 x 32 x 16
-  // (tools/mfma_peak); same LDS image, the fragment of a 16-row block is rows lane & 15 at k slot 4 s + (lane >> 4).
-  // int8: v_mfma_i32_32x32x32_i8, two per 32-byte fragment pair (each 16-byte fragment is one instruction's 32-k operand), accumulators
-  // acci of the same shape and lane layout as acc; the sums are exact integers, converted once behind the K loop.
-  f32x16 acc[FP8 ? 4 : 1][NJ];
-  i32x16_t acci[I8 ? 4 : 1][NJ];
-  f32x4 acc16[FP8 ? 1 : 8][2 * NJ];
-  if constexpr (I8) zero(acci);
-  else if constexpr (FP8) zero(acc);
-  else {  // (written out: behind zero() hipcc assigned the accumulators of <0, 1..3> other registers and their K loop lost two v_mov_b64, gemm_frame.h)
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 2 * NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc16[i][j][r] = 0.f;
-  }
-
-  // fragment blocks of 32 rows (8-bit: 16-byte k slots 2 s + (lane >> 5), s = 0..3) or 16 (bf16: slots 4 s + (lane >> 4), s = 0..1)
-  const auto frag = frag_slots<FP8 ? 32 : 16>(lane);
-  const auto& koff = frag.koff;
-  const int a_row_off = frag.row_off(g * 128);
-  const int w_row_off = frag.row_off(wn * 64);
-
-  // chunks (8 rows, 1 KiB) this wave stages: A chunks of the other group's rows, W chunks wave*4+i
-  const int a_chunk0 = (wave ^ 4) * 4, w_chunk0 = wave * 4;
-  // per-lane BYTE offsets (32-bit) from the uniform tile base, so the DMA uses the saddr + voffset form: 8 VGPRs instead of 16 for
-  // pointers (the kernel sits at the 256-register limit and a spilled pointer costs a vmcnt(0) reload — a full pipeline drain).
-  // The text of TileDma (gemm_frame.h), kept here: behind the struct this kernel's bf16 form came out with another scratch size.
-  uint32_t a_off[4], w_off[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ra = (a_chunk0 + i) * 8 + (lane >> 3), rw = (w_chunk0 + i) * 8 + (lane >> 3);
-    a_off[i] = (uint32_t)((int64_t)(min(m0 + ra, P.M - 1) - m0) * P.lda * ES + (((lane & 7) ^ ((ra >> 1) & 7)) << 4));
-    w_off[i] = (uint32_t)((int64_t)(min(n0 + rw, P.N - 1) - n0) * P.ldw * ES + (((lane & 7) ^ ((rw >> 1) & 7)) << 4));
-  }
-  const char* const a_base = reinterpret_cast<const char*>(P.A) + (int64_t)m0 * P.lda * ES;
-  const char* const w_base = reinterpret_cast<const char*>(P.W) + (int64_t)n0 * P.ldw * ES;
-  auto dma_a = [&](int kt, int i) {
-    const char* base = a_base + (int64_t)kt * (BK * 2);  // uniform
-    __builtin_amdgcn_global_load_lds((glb_void*)(base + a_off[i]), (lds_void*)(smem + A_RING + (kt & 1) * TILE + (a_chunk0 + i) * 1024), 16, 0, 0);
-  };
-  auto dma_w = [&](int kt, int slot, int i) {
-    const char* base = w_base + (int64_t)kt * (BK * 2);
-    __builtin_amdgcn_global_load_lds((glb_void*)(base + w_off[i]), (lds_void*)(smem + W_RING + slot * TILE + (w_chunk0 + i) * 1024), 16, 0, 0);
-  };
-
-  // ---- prologue: what the steady-state rule would have issued before LOAD(0): A(0) (both
-  // halves), W(0), W(1), and the rows group 0 reads of A(1) (staged by group 1)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dma_a(0, i);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) dma_w(0, 0, i);
-  if (nk > 1) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma_w(1, 1, i);
-    if (g == 1) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma_a(1, i);
+  __shared__ __attribute__((aligned(16))) char smem[5 * A_TILE_BYTES];
+  if constexpr (Q8 == 0) {
+    const GemmTile tile = gemm_tile_rows<256>(batch, 2);  // which problem / tile, and its height (uniform per workgroup)
+    if (tile.rows == BM_SHORT) {
+      constexpr int RB = 6;
+#include "gemm_pp_body.inc"
+      return;
     }
+    constexpr int RB = 8;
+#include "gemm_pp_body.inc"
+  } else {
+    const GemmTile tile = gemm_tile<256>(batch, 1);  // which problem / tile
+    constexpr int RB = 8;
+#include "gemm_pp_body.inc"
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  slot_barrier();
-  if (g == 1) slot_barrier();  // group 1 starts one slot late
-
-  bf16x8_t xf[2][8], wf[2][2 * NJ];  // bf16: fragments of the 2 k-steps of 32: 8 row blocks of A, 2 NJ of W (16 rows each)
-  i32x8_t xq[2][4], wq[2][NJ];    // fp8: fragments of the 2 k-steps (two 16-byte reads each)
-  int wr = 0;  // W slot of tile t = t % 3
-  int wi = 2;  // W slot of tile t + 2
-  auto ktile = [&](int t, auto main_tag) {
-    constexpr bool MAIN = decltype(main_tag)::value;  // steady state: both issues are in range
-    // ---- LOAD(t): fragments -> registers, then this wave's DMA pieces (issuing them first was
-    // measured 8-10 % slower: the ds_reads queue up behind DMA instructions blocked on a full queue)
-    const bool a_ok = MAIN || (t + 1 + g < nk);
-    const bool w_ok = MAIN || (t + 2 < nk);
-    auto issue_dma = [&]() {
-      if (a_ok) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma_a(t + 1 + g, i);
-      }
-      if (w_ok) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma_w(t + 2, wi, i);
-      }
-    };
-    {
-      const char* la = smem + A_RING + (t & 1) * TILE + a_row_off;
-      const char* lw = smem + W_RING + wr * TILE + w_row_off;
-      if constexpr (FP8) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            wq[s][j] = __builtin_shufflevector(*reinterpret_cast<const i32x4_t*>(lw + j * 32 * 128 + koff[2 * s]),
-                                               *reinterpret_cast<const i32x4_t*>(lw + j * 32 * 128 + koff[2 * s + 1]), 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            xq[s][i] = __builtin_shufflevector(*reinterpret_cast<const i32x4_t*>(la + i * 32 * 128 + koff[2 * s]),
-                                               *reinterpret_cast<const i32x4_t*>(la + i * 32 * 128 + koff[2 * s + 1]), 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-          for (int j = 0; j < 2 * NJ; ++j) wf[s][j] = *reinterpret_cast<const bf16x8_t*>(lw + j * 16 * 128 + koff[s]);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) xf[s][i] = *reinterpret_cast<const bf16x8_t*>(la + i * 16 * 128 + koff[s]);
-        }
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    issue_dma();
-    __builtin_amdgcn_sched_barrier(0);
-    if (MAIN) {
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {  // tail: wait for everything but what was issued just now
-      if (a_ok && w_ok)
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if (a_ok || w_ok)
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    slot_barrier();
-    // ---- COMPUTE(t): the matrix pipe only
-    if constexpr (I8) {
-      // two instructions per 32-byte fragment pair, the halves in separate sweeps over the 8 accumulators (no instruction follows one on its own accumulator)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-              acci[i][j] = h == 0 ? __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_shufflevector(wq[s][j], wq[s][j], 0, 1, 2, 3),
-                                                                         __builtin_shufflevector(xq[s][i], xq[s][i], 0, 1, 2, 3), acci[i][j], 0, 0, 0)
-                                  : __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_shufflevector(wq[s][j], wq[s][j], 4, 5, 6, 7),
-                                                                         __builtin_shufflevector(xq[s][i], xq[s][i], 4, 5, 6, 7), acci[i][j], 0, 0, 0);
-    } else if constexpr (FP8) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wq[s][j], xq[s][i], acc[i][j], 0, 0, 0, 0, 0, 0);  // e4m3 x e4m3, unscaled
-    } else {
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < 2 * NJ; ++j) acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][j], xf[s][i], acc16[i][j], 0, 0, 0);
-    }
-    slot_barrier();
-    wr = wr == 2 ? 0 : wr + 1;
-    wi = wi == 2 ? 0 : wi + 1;
-  };
-  const int nmain = nk > 2 ? nk - 2 : 0;  // t + 2 < nk  (and t + 1 + g < nk)
-  for (int t = 0; t < nmain; ++t) ktile(t, std::true_type{});
-  for (int t = nmain; t < nk; ++t) ktile(t, std::false_type{});
-  if (g == 0) slot_barrier();  // group 0 finished one slot early
-
-  if constexpr (I8) {  // the exact integer sums as f32 (v_cvt_f32_i32: round to nearest even beyond 2^24, as the oracle's (float) cast)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = (float)acci[i][j][r];
-  }
-  if constexpr (FP8) {  // dequantise: per-token scale of the row, per-channel scale of the 4 consecutive columns
-    float sa[4], oa[4];
-    const bool off = I8 && P.a_off != nullptr;  // int8, post-GELU form of the row codes: + a_off[m] * w_sum[n] (uniform per problem)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = min(m0 + g * 128 + i * 32 + (lane & 31), P.M - 1);
-      sa[i] = P.a_scale[r];
-      oa[i] = off ? P.a_off[r] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = n0 + wn * 64 + j * 32 + 8 * q + 4 * (lane >> 5);
-        float sn[4], wsn[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          sn[c] = P.w_scale[min(n + c, P.N - 1)];
-          wsn[c] = off ? P.w_sum[min(n + c, P.N - 1)] : 0.f;
-        }
-        if (off) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[i][j][4 * q + c] = acc[i][j][4 * q + c] * (sa[i] * sn[c]) + oa[i] * wsn[c];
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[i][j][4 * q + c] *= sa[i] * sn[c];
-        }
-      }
-  }
-  // the lane id is laundered (as in w4_epilogue): what the epilogue derives from it is then computed here, not hoisted above the
-  // K loop, held across 256 registers of loop state, spilled and reloaded (a scratch reload waits vmcnt(0): the stores serialise)
-  int lane_e = lane;
-  asm volatile("" : "+v"(lane_e));
-  if constexpr (FP8) gemm_epilogue<NJ, 4, ACT>(P, Acc32<NJ>{acc, lane_e}, smem, m0, n0, wave, lane_e);
-  else gemm_epilogue<NJ, 4, ACT>(P, Acc16<NJ>{acc16, lane_e}, smem, m0, n0, wave, lane_e);
 }
 
 
@@ -1089,7 +901,7 @@ __device__ __forceinline__ void w4_epilogue(const GemmProblem& P, V (&acc)[I][J]
     __syncthreads();
 #pragma clang loop unroll(disable)
     for (int r = 0; r < 2; ++r) {
-      qkv_relayout_emit(P, smem, m0, n0, wave * 2 + r, lane_e);
+      qkv_relayout_emit<128>(P, smem, m0, n0, wave * 2 + r, lane_e);
       asm volatile("" : "+v"(lane_e));
     }
     return;
@@ -1287,6 +1099,18 @@ static std::atomic<bool> g_w4{[] {
 static std::atomic<int> g_w4q_min_rows{256};
 // never for dense weights (measured: slower, see gemm_w4_pays); the packed 4-bit kernel always fuses.  FMI_GEMM_W4_QKV_MIN_N = the bound for experiments
 static std::atomic<int> g_w4_qkv_min_n{[]() { const char* e = getenv("FMI_GEMM_W4_QKV_MIN_N"); return e && atoi(e) > 0 ? atoi(e) : 1 << 30; }()};
+// Tile heights of the bf16 ping-pong kernel (pick_tile_rows): 0 = chosen per launch, 256 / 192 = one height, 448 = a mixed split at any size.
+// FMI_GEMM_ROWS in the environment, or set_gemm_rows.
+static std::atomic<int> g_rows{[] {
+  const char* e = getenv("FMI_GEMM_ROWS");
+  const int v = e ? atoi(e) : 0;
+  return v == 256 || v == 192 || v == 448 ? v : 0;
+}()};
+int set_gemm_rows(int rows) {
+  if (rows != 0 && rows != 256 && rows != 192 && rows != 448) return fail(FMI_ERR_INVALID, "set_gemm_rows: 0 (automatic), 256, 192 or 448 (mixed), got " + std::to_string(rows));
+  g_rows = rows;
+  return FMI_OK;
+}
 void set_gemm_w4_qkv_min_n(int n) { g_w4_qkv_min_n = n; }
 void set_gemm_w4q_min_rows(int rows) { g_w4q_min_rows = rows; }
 void set_gemm_w4(bool on) { g_w4 = on; }
@@ -1314,6 +1138,112 @@ static int pick_tile_band(int tiles_m) {
     if (cost < best_cost - 1e-9) best_cost = cost, best = h;
   }
   return best;
+}
+
+// Tile heights of a group (gemm_pp_kernel<0, .>): how many 256-row tiles each problem's rows are cut into before the rest goes to 192-row
+// tiles.  A launch whose tile count is just over a whole number of rounds of the CUs pays a whole round for the few tiles of its last one
+// (M = 4608 x N = 12288: 864 tiles on 256 CUs, 3.375 rounds of work, 4 paid); cutting some rows lower gives the dispatcher smaller items to
+// fill the end with.  Model: one workgroup per CU, tiles handed out in launch order (all tall tiles, then the short ones) to the CU that is
+// free first, a 256-row tile costs 4 quarter rounds, a 192-row tile 3 (model constant 0.75; K is taken as equal across the group, which
+// it is in the model's grouped launches).  Per problem the candidates are every n256 in [0, M / 256] with the rest in short tiles, the
+// group is searched by coordinate descent from all-tall, and ties go to the fewer short tiles (a 96-row wave tile reads 6 + 4 fragments per
+// 24 MFMAs, the 128-row one 8 + 4 per 32).  All-tall unless the modelled makespan drops by at least a quarter round, always all-tall below one
+// round of tiles and for every kernel but the bf16 dense ping-pong one.
+// Measured (profiles/tile_rows_ratio.txt, stand-alone launches): 4608 x 32768 x 3072 as 3072 short tiles (12 whole rounds) takes 1.020 of the time of
+// the same problem as 2304 tall tiles (9 whole rounds): a short tile costs 0.765 of a tall one at equal FLOPs, not 0.75.  With 0.765 MLP-in's cut
+// still gains 0.47 of a round; the q|k|v cut would gain 0.235 and miss the quarter by 0.015 — but that launch, timed in the model against the parent
+// commit, is 8.0 % faster (233.1 -> 214.4 us, profiles/tile_rows_kernel_stats*.txt; MLP-in 303.8 -> 266.4), far outside its spread, so the constant
+// stays at 0.75 and the cut with it.  All-short launches do not pay: 4608 x 12288 0.982, 4608 x 21504 1.022 of all-256.
+// mode (FMI_GEMM_ROWS / fmi_set_gemm_rows): 0 = this model, 256 = all tall, 192 = all short, 448 = tall tiles while at least 256 + 192 rows
+// remain and short ones for the rest (tests: a mixed launch at any size).  Every split gives the same bits.
+struct TileRows {
+  int n256[MAX_PROBLEMS], n192[MAX_PROBLEMS];
+  int quarters;  // modelled makespan in quarter rounds
+};
+// makespan of `tall` 4-unit items followed by `shrt` 3-unit items on `cus` machines, each item to the machine that is free first
+static int rows_makespan(int64_t tall, int64_t shrt, int cus) {
+  const int64_t q = tall / cus, r = tall % cus;
+  // machines by finishing time: lo at 4 q (cus - r of them), hi at 4 q + 4 (r of them); the short items fill the earliest level first
+  int64_t lvl[2] = {4 * q, 4 * q + 4}, cnt[2] = {cus - r, r};
+  while (shrt > 0) {
+    const int e = (cnt[1] == 0 || (cnt[0] > 0 && lvl[0] <= lvl[1])) ? 0 : 1;
+    if (shrt >= cnt[e]) {
+      shrt -= cnt[e], lvl[e] += 3;
+      if (lvl[0] == lvl[1]) cnt[0] += cnt[1], cnt[1] = 0;
+    } else {  // part of a level moves up and nothing follows: the makespan is that level + 3 or the other level
+      return (int)std::max(lvl[e] + 3, cnt[e ^ 1] > 0 ? lvl[e ^ 1] : (int64_t)0);
+    }
+  }
+  int64_t top = 0;
+  for (int e = 0; e < 2; ++e)
+    if (cnt[e] > 0) top = std::max(top, lvl[e]);
+  return (int)top;
+}
+TileRows pick_tile_rows(const int* M, const int* N, int nprob, int cus, bool pp_bf16, int mode) {
+  TileRows t{};
+  int cols[MAX_PROBLEMS];
+  int64_t tiles = 0;
+  for (int i = 0; i < nprob; ++i) {
+    cols[i] = cdiv(N[i], 256);
+    t.n256[i] = cdiv(M[i], BM), t.n192[i] = 0;
+    tiles += (int64_t)t.n256[i] * cols[i];
+  }
+  auto model = [&](const TileRows& s) {
+    int64_t tall = 0, shrt = 0;
+    for (int i = 0; i < nprob; ++i) tall += (int64_t)s.n256[i] * cols[i], shrt += (int64_t)s.n192[i] * cols[i];
+    return rows_makespan(tall, shrt, cus);
+  };
+  auto cut = [&](TileRows& s, int i, int n256) { s.n256[i] = n256, s.n192[i] = cdiv(std::max(M[i] - n256 * BM, 0), BM_SHORT); };
+  t.quarters = model(t);
+  if (!pp_bf16 || mode == 256 || cus <= 0) return t;
+  if (mode == BM_SHORT || mode == BM + BM_SHORT) {
+    for (int i = 0; i < nprob; ++i) cut(t, i, mode == BM_SHORT ? 0 : M[i] >= BM + BM_SHORT ? (M[i] - BM_SHORT) / BM : 0);
+    t.quarters = model(t);
+    return t;
+  }
+  if (tiles <= cus) return t;
+  TileRows best = t;
+  for (int pass = 0; pass < 4; ++pass) {
+    bool moved = false;
+    for (int i = 0; i < nprob; ++i)
+      for (int n = M[i] / BM; n >= 0; --n) {  // downwards: among equal makespans the first (fewest short tiles) is kept
+        TileRows c = best;
+        cut(c, i, n);
+        c.quarters = model(c);
+        if (c.quarters < best.quarters) best = c, moved = true;
+      }
+    if (!moved) break;
+  }
+  return t.quarters - best.quarters >= 1 ? best : t;
+}
+// The launch order of a split: workgroup ids of problem i's tall region from tile_start[i], of its short region from short_start[i]; every tall
+// region lies in front of every short one.  Returns the grid size.
+static int place_tile_rows(const TileRows& rows, const int* N, int nprob, int bn, GemmBatch& b) {
+  int total = 0;
+  for (int i = 0; i < nprob; ++i) {  // the tall tiles of every problem first ...
+    b.tile_start[i] = total;
+    b.n256[i] = rows.n256[i];
+    b.band[i] = pick_tile_band(rows.n256[i]);
+    total += rows.n256[i] * cdiv(N[i], bn);
+  }
+  for (int i = nprob; i <= MAX_PROBLEMS; ++i) b.tile_start[i] = total;
+  for (int i = 0; i < nprob; ++i) {  // ... then the short ones (none unless pick_tile_rows cut a problem)
+    b.short_start[i] = total;
+    b.band_s[i] = pick_tile_band(rows.n192[i]);
+    total += rows.n192[i] * cdiv(N[i], bn);
+  }
+  for (int i = nprob; i <= MAX_PROBLEMS; ++i) b.short_start[i] = total;
+  for (int i = nprob; i < MAX_PROBLEMS; ++i) b.band[i] = b.band_s[i] = TILE_BAND, b.n256[i] = 0;
+  return total;
+}
+// (q8 == 0 stands for a dense bf16 group wider than 128 columns, the ping-pong kernel's launches; tall_start / short_start: nprob + 1 entries)
+int gemm_tile_rows_of(const int* M, const int* N, int nprob, int cus, int q8, int mode, int* n256, int* n192, int* tall_start, int* short_start) {
+  const TileRows t = pick_tile_rows(M, N, nprob, cus, q8 == 0, mode);
+  GemmBatch b;
+  place_tile_rows(t, N, nprob, 256, b);
+  for (int i = 0; i < nprob; ++i) n256[i] = t.n256[i], n192[i] = t.n192[i];
+  for (int i = 0; i <= nprob; ++i) tall_start[i] = b.tile_start[i], short_start[i] = b.short_start[i];
+  return t.quarters;
 }
 
 // ---- what a group of problems reduces to for the kernel choice
@@ -1417,6 +1347,7 @@ struct GemmTraits {
 struct GemmSwitches {  // a snapshot of the process-wide switches above
   bool pingpong, w4;               // what select_gemm_kernel reads
   int w4q_min_rows, w4_qkv_min_n;  // bounds of the reductions gemm_w4q_ok / gemm_w4_pays, which launch_gemm fills GemmTraits with
+  int rows;                        // tile heights: what pick_tile_rows reads as `mode`
 };
 struct GemmChoice {
   GemmKernel kernel;
@@ -1447,27 +1378,33 @@ static int with_act(int act, F&& launch) {
   }
 }
 
+// CUs of the current device (one workgroup of the ping-pong kernel each): what pick_tile_rows schedules on; asked once
+static int gemm_cu_count() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return n;
+  }();
+  return cus;
+}
+
 int launch_gemm(const GemmProblem* probs, int nprob, hipStream_t stream) {
   if (nprob <= 0) return FMI_OK;
   if (nprob > MAX_PROBLEMS) return fail(FMI_ERR_INVALID, "launch_gemm: too many grouped problems");
   const int bn = gemm_tile_width(probs, nprob);
   FMI_TRY(validate_gemm_problems(probs, nprob, bn));
-  const GemmSwitches sw{g_pingpong, g_w4, g_w4q_min_rows, g_w4_qkv_min_n};
+  const GemmSwitches sw{g_pingpong, g_w4, g_w4q_min_rows, g_w4_qkv_min_n, g_rows};
   const GemmTraits t{probs[0].cv_ks != 0 ? GO_CONV : probs[0].q_type != 0 ? GO_Q4 : GO_DENSE, probs[0].fp8, bn,
                      gemm_w4_pays(probs, nprob, sw.w4_qkv_min_n), gemm_w4q_ok(probs, nprob, sw.w4q_min_rows)};
   const GemmChoice c = select_gemm_kernel(t, sw, FMI_ALT_KERNELS != 0);
   if (c.err != FMI_OK) return fail(c.err, c.msg);
+  int Ms[MAX_PROBLEMS], Ns[MAX_PROBLEMS];
+  for (int i = 0; i < nprob; ++i) Ms[i] = probs[i].M, Ns[i] = probs[i].N;
+  const TileRows rows = pick_tile_rows(Ms, Ns, nprob, gemm_cu_count(), c.kernel == GK_PP, sw.rows);
   GemmBatch b;
   b.nprob = nprob;
-  int total = 0;
-  for (int i = 0; i < nprob; ++i) {
-    b.p[i] = probs[i];
-    b.tile_start[i] = total;
-    b.band[i] = pick_tile_band(cdiv(probs[i].M, BM));
-    total += cdiv(probs[i].M, BM) * cdiv(probs[i].N, bn);
-  }
-  for (int i = nprob; i <= MAX_PROBLEMS; ++i) b.tile_start[i] = total;
-  for (int i = nprob; i < MAX_PROBLEMS; ++i) b.band[i] = TILE_BAND;
+  for (int i = 0; i < nprob; ++i) b.p[i] = probs[i];
+  const int total = place_tile_rows(rows, Ns, nprob, bn, b);
   const bool wide = bn == 256;
   return with_act(epilogue_kind(probs, nprob), [&](auto act) -> int {
     constexpr int ACT = decltype(act)::value;

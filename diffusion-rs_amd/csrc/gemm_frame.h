@@ -12,6 +12,8 @@
 //   TileDma in gemm_w4q_kernel: every resource figure held, but in the K loop (443 instructions, 64 MFMAs) 46 instructions sat elsewhere — a
 //     packed-W global_load_dwordx4, the absmax load, the v_xor + ds_write_b128 of the expansion, 20 - 40 slots away — and the AGPR assignment changed;
 //   zero() on the bf16 accumulators of gemm_pp_kernel: <0, 1..3> got another accumulator assignment, their K loop 161 instead of 163 instructions.
+//   the body of gemm_pp_kernel as a function over the LDS array's address (for its two tile heights): every instantiation moved, the 8-bit forms included
+//     (<0, .> scratch 48 -> 0 B, <1, .> 44 -> 24, <2, 1> 524 -> 588, <2, 3> 420 -> 356) — it is included text, gemm_pp_body.inc, inside the kernel that owns the array.
 // So TileDma serves gemm_w4_kernel (test build) only.  With these three left out every K loop of both builds is the parent's, instruction for instruction.
 #pragma once
 
@@ -32,6 +34,7 @@ __device__ __forceinline__ void tile_coords(int t, int tiles_m, int tiles_n, int
 struct GemmTile {
   const GemmProblem& P;
   int pi, m0, n0, nk;  // index of the problem in the batch; first row / column of the BM x BN tile; number of 128-byte K tiles
+  int rows;            // tile height: BM, or BM_SHORT in the short region of a mixed launch (gemm_tile_rows)
 };
 // es = operand element size in bytes (2: bf16, 1: e4m3 / int8)
 template <int BN>
@@ -48,7 +51,32 @@ __device__ __forceinline__ GemmTile gemm_tile(const GemmBatch& batch, int es) {
   const int tiles_n = (P.N + BN - 1) / BN;
   int tm, tn;
   tile_coords(t, tiles_m, tiles_n, batch.band[pi], tm, tn);
-  return {P, pi, tm * BM, tn * BN, P.K * es / (BK * 2)};
+  return {P, pi, tm * BM, tn * BN, P.K * es / (BK * 2), BM};
+}
+// The same for a launch of mixed heights (GemmBatch::n256): workgroups [0, ntall) are the 256-row tiles of all problems, the rest the 192-row
+// tiles.  Each height region has its own bijective XCD remap (one over the whole grid would hand whole XCDs nothing but short tiles) and,
+// per problem, its own band / patch order.  The height is uniform per workgroup.  The short region's remap runs on bid - ntall while the hardware
+// places workgroup bid on XCD bid % 8: when ntall is no multiple of 8 the remap's XCD numbers are a rotation of the real ones — still a bijection, still
+// one contiguous run of tiles per XCD, so results and locality hold (at the headline cuts ntall is 576 and 504, multiples of 8).
+template <int BN>
+__device__ __forceinline__ GemmTile gemm_tile_rows(const GemmBatch& batch, int es) {
+  const int ntall = batch.tile_start[batch.nprob], total = batch.short_start[batch.nprob];
+  const int bid = blockIdx.x;
+  const bool tall = bid < ntall;
+  const int lid = tall ? xcd_remap(bid, ntall) : ntall + xcd_remap(bid - ntall, total - ntall);
+  const int* start = tall ? batch.tile_start : batch.short_start;
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < MAX_PROBLEMS; ++i)
+    if (i < batch.nprob && lid >= start[i]) pi = i;
+  const GemmProblem& P = batch.p[pi];
+  const int t = lid - start[pi];
+  const int rows_tall = batch.n256[pi] * BM;
+  const int tiles_m = tall ? batch.n256[pi] : (P.M - rows_tall + BM_SHORT - 1) / BM_SHORT;
+  const int tiles_n = (P.N + BN - 1) / BN;
+  int tm, tn;
+  tile_coords(t, tiles_m, tiles_n, tall ? batch.band[pi] : batch.band_s[pi], tm, tn);
+  return {P, pi, tall ? tm * BM : rows_tall + tm * BM_SHORT, tn * BN, P.K * es / (BK * 2), tall ? BM : BM_SHORT};
 }
 
 // ---- LDS-DMA sources of the A and W tiles: this wave stages the 1-KiB chunks (8 rows of 128 B) a_chunk0 / w_chunk0 .. + PIECES - 1 of them, lane l

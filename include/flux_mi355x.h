@@ -46,6 +46,7 @@ extern "C" {
  *   Then, still 6: image to image and inpainting — fmi_preprocess_u8, fmi_latent_mask, fmi_encode_latents, fmi_scale_noise, fmi_flux_denoise_inpaint.
  *   Then, still 6: reference-image (FLUX.1 Kontext) conditioning — fmi_flux_context, fmi_flux_forward_context, fmi_flux_denoise_context, fmi_latent_ids.
  *   Then, still 6: the GEMM launcher's test seams — fmi_gemm_desc, fmi_gemm_group, fmi_splitk_resid_gate, fmi_set_gemm_kernel.
+ *   Then, still 6: the GEMM tile heights — fmi_set_gemm_rows, fmi_gemm_tile_rows.
  *   Then, still 6: the first-block step cache of the denoise loop — fmi_flux_step_cache, fmi_flux_denoise_cached, fmi_flux_step_cache_bytes.
  *   Then, still 6: true classifier-free guidance (negative prompts) in the denoise loop — fmi_flux_true_cfg, fmi_flux_denoise_cfg, fmi_cfg_euler_step.
  *   Then, still 6: channel-concatenated conditioning (FLUX.1 Fill / Canny / Depth) — fmi_flux_create_cond, fmi_flux_cond_channels, fmi_flux_control,
@@ -1204,6 +1205,18 @@ int fmi_gemm_group(const fmi_gemm_desc* probs, int nprob, void* stream);
 int fmi_splitk_resid_gate(const float* parts, int S, const void* bias, const float* gate, int rows_per_batch, int gate_bstride, float* out, int ldo,
                           int M, int N, void* stream);
 int fmi_set_gemm_kernel(int pingpong, int w4);
+/* Tile heights of the dense bf16 ping-pong GEMM kernel, PROCESS-WIDE (a test / ablation hook like fmi_set_gemm_kernel; FMI_GEMM_ROWS=<n> in the
+ * environment sets the initial value): 0 (default) = chosen per launch by a scheduling model — 256-row tiles, with the last rows of a problem in
+ * 192-row tiles where that saves at least a quarter round of the CUs; 256 = 256-row tiles only; 192 = 192-row tiles only; 448 = 256-row tiles
+ * while at least 448 rows remain, 192-row tiles for the rest (a mixed launch at any size).  Rows are split, never K: every setting gives the same
+ * bits.  Other kernels have one height and ignore it.  Anything else: FMI_ERR_INVALID.
+ * fmi_gemm_tile_rows is the model alone (pure, no device): for a group of nprob <= 8 problems (M[i], N[i]) on `cus` compute units, operands q8
+ * (0 = bf16: the kernel above; 1 / 2: an 8-bit kernel, one height) and a setting `mode` as above, the numbers of 256-row and 192-row tiles along
+ * M per problem, the first workgroup id of each problem's 256-row and 192-row tiles in the launch order (nprob + 1 entries each, the last = the
+ * end of that region; all 256-row tiles come first) and the modelled makespan in quarters of a 256-row tile's time. */
+int fmi_set_gemm_rows(int rows);
+int fmi_gemm_tile_rows(const int* M, const int* N, int nprob, int cus, int q8, int mode, int* n256, int* n192, int* tall_start, int* short_start,
+                       int* quarters);
 /* softmax(q k^T * scale) v, q,k,v,o (B,H,L,d) bf16, d == 128, non-causal; o is written
  * token-major (B,L,H*d) when `out_token_major`, else (B,H,L,d).
  * == backend::ops::sdpa fallback (ops.rs:247-262) without materialising the scores. */
