@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <set>
 #include <string>
 #include <vector>
@@ -280,6 +282,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the grid of a grid-stride kernel over `items`: 256 threads a block, at most 2048 blocks, the loop takes the rest
+inline dim3 map_grid(int64_t items) { return dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 256 * 8)); }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if (p && !aligned16(p)) return false;  // (a null pointer is an operand the kernel never touches)
+  return true;
+}
 
 // ---------------------------------------------------------------- kernel launchers (host)
 // GEMM problem: y = epi(x W^T + bias).  All leading dims in elements.
@@ -520,15 +530,13 @@ int launch_cast_cols_bf16(const void* src, fmi_dtype dt, int64_t rows, int64_t r
 int launch_add_scaled_rows_bf16(float* x, int64_t x_bs, const bf16_t* src, int B, int64_t rows, int D, float c, hipStream_t stream);
 int launch_add_scaled_rows_f32(float* x, int64_t x_bs, const float* src, int B, int64_t rows, int D, float c, hipStream_t stream);
 int launch_silu_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t stream);
-int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream);
-// the masked (inpainting) step: img = mask * (img + pred * dt) + (1 - mask) * ((1 - s) * x0 + s * noise), one pass (small_ops.hip)
-int launch_euler_blend(float* img, const float* pred, const float* x0, const float* noise, const float* mask, float dt, float s, int64_t n, hipStream_t stream);
-// the true-CFG step: g = neg + scale * (pos - neg), img = img + g * dt — or, with x0 / noise / mask (all three or none), launch_euler_blend's blend of that — one pass
-int launch_euler_cfg(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0 = nullptr,
-                     const float* noise = nullptr, const float* mask = nullptr, float s = 0.f);
-// the second-order solvers' updates (small_ops.hip), one pass each.  neg null: no guidance (g = pos); x0 / noise / mask all three or none, blended at time s.
-//   predictor: g1 = g, xt = blend(img + g * dt) — the state is only read;  corrector: img = blend(img + ((g1 + g) * 0.5) * dt)
+// the denoise loop's updates of the state (denoise_steps.hip), one pass each.  g = pos, or with neg (true CFG) neg + scale * (pos - neg);
+// blend(e) = e, or with x0 / noise / mask (all three or none; inpainting) mask * e + (1 - mask) * ((1 - s) * x0 + s * noise).
+//   Euler: img = blend(img + g * dt)
+//   Heun predictor: g1 = g, xt = blend(img + g * dt) — the state is only read;  corrector: img = blend(img + ((g1 + g) * 0.5) * dt)
 //   2M: D = img - t * g, D' = D + w * (D - hist) (w == 0: hist unread), img = blend(a * img + c * D'), hist = D
+int launch_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0, const float* noise,
+                      const float* mask, float s);
 int launch_heun_predict(const float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, float* xt, float* g1, hipStream_t stream, const float* x0,
                         const float* noise, const float* mask, float s);
 int launch_heun_correct(float* img, const float* g1, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0,

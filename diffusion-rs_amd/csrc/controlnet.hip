@@ -42,22 +42,18 @@ __global__ __launch_bounds__(256) void add_scaled_rows_kernel(float* __restrict_
     }
   }
 }
-inline bool on16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// the glue kernels' grid: 256 threads, at most 2048 blocks (small_ops.hip's map_grid), the loop takes the rest
-inline dim3 capped_grid(int64_t items) { return dim3((unsigned)std::min<int64_t>(cdiv64(items, 256), 256 * 8)); }
-
 template <typename T>
 int launch_add_scaled_rows_t(float* x, int64_t x_bs, const T* src, int B, int64_t rows, int D, float c, hipStream_t stream) {
   if (!x || !src || B < 0 || rows < 0 || D <= 0) return fail(FMI_ERR_INVALID, "add_scaled_rows: null pointer or negative size");
   const int64_t per = rows * D;
   if (x_bs < per) return fail(FMI_ERR_INVALID, "add_scaled_rows: the batch stride of x must be at least rows * D (the samples' rows must not overlap)");
   if (B == 0 || per == 0) return FMI_OK;
-  if (per % 8 == 0 && x_bs % 4 == 0 && on16(x) && on16(src)) {
+  if (per % 8 == 0 && x_bs % 4 == 0 && aligned16(x) && aligned16(src)) {
     const int64_t items = (int64_t)B * (per / 8);
-    hipLaunchKernelGGL((add_scaled_rows_kernel<T, true>), capped_grid(items), dim3(256), 0, stream, x, x_bs, src, per, items, c);
+    hipLaunchKernelGGL((add_scaled_rows_kernel<T, true>), map_grid(items), dim3(256), 0, stream, x, x_bs, src, per, items, c);
   } else {
     const int64_t items = (int64_t)B * per;
-    hipLaunchKernelGGL((add_scaled_rows_kernel<T, false>), capped_grid(items), dim3(256), 0, stream, x, x_bs, src, per, items, c);
+    hipLaunchKernelGGL((add_scaled_rows_kernel<T, false>), map_grid(items), dim3(256), 0, stream, x, x_bs, src, per, items, c);
   }
   FMI_LAUNCH_CHECK();
   return FMI_OK;

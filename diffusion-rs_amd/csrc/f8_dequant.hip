@@ -25,7 +25,6 @@ enum F8Format { F8_E4M3 = 1, F8_E5M2 = 2 };
 typedef float f8_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int THREADS = 256;
-constexpr int MAX_GRID = 256 * 8;  // small_ops.hip's map_grid
 
 // the four codes of `w` (byte 0 first)
 template <int FMT>
@@ -99,7 +98,7 @@ int launch_t(const void* codes, int64_t n, float scale, void* out, hipStream_t s
   const uintptr_t a = reinterpret_cast<uintptr_t>(codes);
   const int head = (int)std::min<int64_t>(n, (int64_t)((16 - (a & 15)) & 15));
   const int64_t nvec = (n - head) / 16;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(nvec, THREADS), MAX_GRID));
+  const unsigned grid = std::max(1u, map_grid(nvec).x);  // (workgroup 0 also takes the head and the tail)
   const int out_aligned = ((reinterpret_cast<uintptr_t>(out) + (uintptr_t)head * (BF16 ? 2 : 4)) & 15) == 0;
   hipLaunchKernelGGL((f8_dequant_kernel<FMT, BF16>), dim3(grid), dim3(THREADS), 0, s, (const uint8_t*)codes, n, scale, out, head, nvec, out_aligned);
   FMI_LAUNCH_CHECK();

@@ -2033,12 +2033,8 @@ static int run_steps(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, 
       FMI_TRY(launch_heun_predict(img_inout, pos, neg, scale, dt, n, xt, g1, s, o.x0, o.noise, o.mask, t_next));
       FMI_TRY(eval(xt, i + 1, i));
       FMI_TRY(launch_heun_correct(img_inout, g1, pos, neg, scale, dt, n, s, o.x0, o.noise, o.mask, t_next));
-    } else if (o.cfg) {
-      FMI_TRY(launch_euler_cfg(img_inout, pos, neg, scale, dt, n, s, o.x0, o.noise, o.mask, t_next));
-    } else if (o.mask) {  // the re-noised source at the step's target time, blended in where the mask keeps it
-      FMI_TRY(launch_euler_blend(img_inout, pos, o.x0, o.noise, o.mask, dt, t_next, n, s));
     } else {
-      FMI_TRY(launch_euler_update(img_inout, pos, dt, n, s));
+      FMI_TRY(launch_euler_step(img_inout, pos, neg, scale, dt, n, s, o.x0, o.noise, o.mask, t_next));
     }
   }
   return FMI_OK;

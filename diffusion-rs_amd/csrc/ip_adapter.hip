@@ -150,8 +150,6 @@ __global__ __launch_bounds__(256) void ip_kv_pack_kernel(const float* __restrict
   }
 }
 
-inline bool on16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int ip_ensure(fmi_ip_adapter* a, int Bt, hipStream_t s) {
   const size_t rows = (size_t)Bt * a->N, n2 = (size_t)a->nd * 2;
   if (a->kv.bytes() < n2 * rows * a->D * 2) {
@@ -178,7 +176,7 @@ int launch_ip_attention(const bf16_t* q, int ldq, int64_t q_bs, const bf16_t* wq
   const int64_t D = (int64_t)H * 128;
   if (ldq < D || ldq % 8 || q_bs % 8 || q_bs < (int64_t)S * ldq) return fail(FMI_ERR_INVALID, "ip_attention: q needs a row stride >= H * 128 and a batch stride >= S * ldq, both multiples of 8");
   if (x_bs < (int64_t)S * D || x_bs % 4) return fail(FMI_ERR_INVALID, "ip_attention: the batch stride of x must be at least S * H * 128 and a multiple of 4");
-  if (!on16(q) || !on16(wq) || !on16(K) || !on16(V) || !on16(x)) return fail(FMI_ERR_INVALID, "ip_attention: every pointer must be 16-byte aligned");
+  if (!all_aligned16({q, wq, K, V, x})) return fail(FMI_ERR_INVALID, "ip_attention: every pointer must be 16-byte aligned");
   if (B > 65535) return fail(FMI_ERR_UNSUPPORTED, "ip_attention: B > 65535");
   if (B == 0 || S == 0) return FMI_OK;
   int HT = H % 4 == 0 ? 4 : H % 2 == 0 ? 2 : 1;
@@ -212,7 +210,7 @@ int ip_prepare(fmi_ip_adapter* a, const void* embeds, const void* neg_embeds, fm
   FMI_LAUNCH_CHECK();
   FMI_TRY(launch_gemv(tok, a->kv_w, a->kv_b, a->kv_f32.as<float>(), rows, n2 * a->D, a->J, 0, 0, s));
   const int64_t total = (int64_t)n2 * rows * a->D;
-  hipLaunchKernelGGL(ip_kv_pack_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(total, 256), 2048)), dim3(256), 0, s, a->kv_f32.as<float>(), a->kv.as<bf16_t>(), Bt, a->N,
+  hipLaunchKernelGGL(ip_kv_pack_kernel, map_grid(total), dim3(256), 0, s, a->kv_f32.as<float>(), a->kv.as<bf16_t>(), Bt, a->N,
                      a->D, n2, total);
   FMI_LAUNCH_CHECK();
   return FMI_OK;

@@ -1,11 +1,11 @@
 // small_ops.hip — the non-GEMM odds and ends of Flux::forward / FluxPipeline::forward:
 //   gemv            : M<=8 row Linear (MlpEmbedder, Modulation1/2, LastLayer.ada_ln) — pure weight
 //                     streaming, one wave per output row, 16-B loads  (model.rs:178-183,244-299,695-698)
-//   timestep_embedding (model.rs:104-122), Euler update (pipelines/sampling.rs:43),
+//   timestep_embedding (model.rs:104-122),
 //   pack/unpack latents (pipelines/flux/sampling.rs:26-48,61-68), u8 post-process (flux/mod.rs:332),
 //   Philox N(0,1) latents (seedable replacement of get_noise, flux/sampling.rs:5-14), dtype casts,
 //   image-to-image / inpainting glue (no counterpart in the reference; the flow-matching forms of diffusers' FluxImg2ImgPipeline /
-//   FluxInpaintPipeline): scale_noise, the masked Euler step, u8 -> f32, latent mask, encode_latents.
+//   FluxInpaintPipeline): scale_noise, u8 -> f32, latent mask, encode_latents.
 #include "common.h"
 
 namespace fmi {
@@ -103,7 +103,6 @@ template <typename F>
 __global__ void map_kernel(int64_t n, F f) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) f(i);
 }
-static inline dim3 map_grid(int64_t n) { return dim3((unsigned)std::min<int64_t>(cdiv64(n, 256), 256 * 8)); }
 
 int launch_cast_to_bf16(const void* src, fmi_dtype dt, bf16_t* dst, int64_t n, hipStream_t stream) {
   if (n <= 0) return FMI_OK;
@@ -162,63 +161,13 @@ static int upload_as(const void* src, fmi_dtype dtype, fmi_dtype same, int64_t n
 int upload_as_bf16(const void* src, fmi_dtype dtype, int64_t n, bf16_t* dst) { return upload_as(src, dtype, FMI_BF16, n, dst, launch_cast_to_bf16); }
 int upload_as_f32(const void* src, fmi_dtype dtype, int64_t n, float* dst) { return upload_as(src, dtype, FMI_F32, n, dst, launch_cast_to_f32); }
 
-// img = img + pred * dt   (pipelines/sampling.rs:43; latent kept in f32)
-int launch_euler_update(float* img, const float* pred, float dt, int64_t n, hipStream_t stream) {
-  hipLaunchKernelGGL(map_kernel, map_grid(n), dim3(256), 0, stream, n, [=] __device__(int64_t i) { img[i] = img[i] + pred[i] * dt; });
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-
 namespace {
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // a * x + t * y with a = 1 - t computed ONCE by the caller: t = 1 gives y and t = 0 gives x bit for bit (finite inputs), contracted or not
 __device__ __forceinline__ float lerp_at(float a, float x, float t, float y) { return a * x + t * y; }
 __device__ __forceinline__ float4 lerp_at(float a, float4 x, float t, float4 y) {
   return make_float4(lerp_at(a, x.x, t, y.x), lerp_at(a, x.y, t, y.y), lerp_at(a, x.z, t, y.z), lerp_at(a, x.w, t, y.w));
 }
-// e = img + pred * dt (launch_euler_update's expression), k = a * x0 + s * noise, m * e + (1 - m) * k: m = 1 gives e and m = 0 gives k bit for bit
-__device__ __forceinline__ float euler_blend1(float img, float pred, float x0, float noise, float m, float dt, float a, float s) {
-  const float e = img + pred * dt;
-  const float k = lerp_at(a, x0, s, noise);
-  const float keep = 1.0f - m;
-  return m * e + keep * k;
-}
-__device__ __forceinline__ float4 euler_blend1(float4 img, float4 pred, float4 x0, float4 noise, float4 m, float dt, float a, float s) {
-  return make_float4(euler_blend1(img.x, pred.x, x0.x, noise.x, m.x, dt, a, s), euler_blend1(img.y, pred.y, x0.y, noise.y, m.y, dt, a, s),
-                     euler_blend1(img.z, pred.z, x0.z, noise.z, m.z, dt, a, s), euler_blend1(img.w, pred.w, x0.w, noise.w, m.w, dt, a, s));
-}
-// V = float4 (16-B accesses) or float (any alignment, any n); grid-stride like map_kernel.  img is read and written at the same index only.
-template <typename V>
-__global__ __launch_bounds__(256) void euler_blend_kernel(V* img, const V* __restrict__ pred, const V* __restrict__ x0, const V* __restrict__ noise,
-                                                          const V* __restrict__ mask, float dt, float a, float s, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    img[i] = euler_blend1(img[i], pred[i], x0[i], noise[i], mask[i], dt, a, s);
-}
-// The true-CFG step: g = neg + scale * (pos - neg) — the difference first, diffusers' expression: pos == neg or scale == 0 gives neg bit
-// for bit, contracted or not — then launch_euler_update's e = img + g * dt, or with BLEND euler_blend1 on g: both forms unchanged.
-template <bool BLEND>
-__device__ __forceinline__ float euler_cfg1(float img, float pos, float neg, float x0, float noise, float m, float scale, float dt, float a, float s) {
-  const float d = pos - neg;
-  const float g = neg + scale * d;
-  if constexpr (BLEND) return euler_blend1(img, g, x0, noise, m, dt, a, s);
-  return img + g * dt;
-}
-template <bool BLEND>
-__device__ __forceinline__ float4 euler_cfg1(float4 img, float4 pos, float4 neg, float4 x0, float4 noise, float4 m, float scale, float dt, float a, float s) {
-  return make_float4(euler_cfg1<BLEND>(img.x, pos.x, neg.x, x0.x, noise.x, m.x, scale, dt, a, s), euler_cfg1<BLEND>(img.y, pos.y, neg.y, x0.y, noise.y, m.y, scale, dt, a, s),
-                     euler_cfg1<BLEND>(img.z, pos.z, neg.z, x0.z, noise.z, m.z, scale, dt, a, s), euler_cfg1<BLEND>(img.w, pos.w, neg.w, x0.w, noise.w, m.w, scale, dt, a, s));
-}
-// V as in euler_blend_kernel; BLEND = false never touches x0 / noise / mask (null then).  img is read and written at the same index only.
-template <typename V, bool BLEND>
-__global__ __launch_bounds__(256) void euler_cfg_kernel(V* img, const V* __restrict__ pos, const V* __restrict__ neg, const V* __restrict__ x0,
-                                                        const V* __restrict__ noise, const V* __restrict__ mask, float scale, float dt, float a, float s, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    if constexpr (BLEND)
-      img[i] = euler_cfg1<true>(img[i], pos[i], neg[i], x0[i], noise[i], mask[i], scale, dt, a, s);
-    else
-      img[i] = euler_cfg1<false>(img[i], pos[i], neg[i], V{}, V{}, V{}, scale, dt, a, s);
-  }
-}
+// V = float4 (16-B accesses) or float (any alignment, any n); grid-stride like map_kernel
 template <typename V>
 __global__ __launch_bounds__(256) void scale_noise_kernel(const V* __restrict__ x0, const V* __restrict__ noise, float a, float t, V* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = lerp_at(a, x0[i], t, noise[i]);
@@ -231,216 +180,6 @@ __device__ __forceinline__ void store4(float* p, float a, float b, float c, floa
     p[0] = a, p[1] = b, p[2] = c, p[3] = d;
 }
 }  // namespace
-
-// The masked step of the inpainting loop in one pass (five f32 reads, one write per element):
-//   e = img + pred * dt;  k = (1 - s) * x0 + s * noise;  img = mask * e + (1 - mask) * k        (s = the step's target time, rounded to f32)
-int launch_euler_blend(float* img, const float* pred, const float* x0, const float* noise, const float* mask, float dt, float s, int64_t n,
-                       hipStream_t stream) {
-  if (n <= 0) return FMI_OK;
-  const float a = 1.0f - s;
-  if (n % 4 == 0 && aligned16(img) && aligned16(pred) && aligned16(x0) && aligned16(noise) && aligned16(mask))
-    hipLaunchKernelGGL(euler_blend_kernel<float4>, map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), reinterpret_cast<const float4*>(pred),
-                       reinterpret_cast<const float4*>(x0), reinterpret_cast<const float4*>(noise), reinterpret_cast<const float4*>(mask), dt, a, s, n / 4);
-  else
-    hipLaunchKernelGGL(euler_blend_kernel<float>, map_grid(n), dim3(256), 0, stream, img, pred, x0, noise, mask, dt, a, s, n);
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-// The true-CFG step in one pass (three f32 reads and one write per element, six reads with the blend):
-//   g = neg + scale * (pos - neg);  e = img + g * dt;  img = e, or with x0 / noise / mask (all three or none) launch_euler_blend's mask * e + (1 - mask) * k
-int launch_euler_cfg(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0, const float* noise,
-                     const float* mask, float s) {
-  if (n <= 0) return FMI_OK;
-  const bool blend = x0 && noise && mask;
-  if (!blend && (x0 || noise || mask)) return fail(FMI_ERR_INVALID, "euler_cfg: x0, noise and mask go together (all three or none)");
-  const float a = 1.0f - s;
-  const bool v4 = n % 4 == 0 && aligned16(img) && aligned16(pos) && aligned16(neg) && (!blend || (aligned16(x0) && aligned16(noise) && aligned16(mask)));
-  const float4 *p4 = reinterpret_cast<const float4*>(pos), *n4 = reinterpret_cast<const float4*>(neg), *x4 = reinterpret_cast<const float4*>(x0),
-               *z4 = reinterpret_cast<const float4*>(noise), *m4 = reinterpret_cast<const float4*>(mask);
-  if (v4 && blend)
-    hipLaunchKernelGGL((euler_cfg_kernel<float4, true>), map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), p4, n4, x4, z4, m4, scale, dt, a, s, n / 4);
-  else if (v4)
-    hipLaunchKernelGGL((euler_cfg_kernel<float4, false>), map_grid(n / 4), dim3(256), 0, stream, reinterpret_cast<float4*>(img), p4, n4, x4, z4, m4, scale, dt, a, s, n / 4);
-  else if (blend)
-    hipLaunchKernelGGL((euler_cfg_kernel<float, true>), map_grid(n), dim3(256), 0, stream, img, pos, neg, x0, noise, mask, scale, dt, a, s, n);
-  else
-    hipLaunchKernelGGL((euler_cfg_kernel<float, false>), map_grid(n), dim3(256), 0, stream, img, pos, neg, x0, noise, mask, scale, dt, a, s, n);
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-// ---- the second-order solvers' updates: the Heun predictor and corrector and the DPM-Solver++ 2M step, each one pass in euler_cfg_kernel's
-// shape.  Every product that feeds a sum is an explicit fmaf, so an expression rounds the same in every instantiation and the tests can count its roundings.
-namespace {
-template <int W>
-__device__ __forceinline__ void ld(const float* __restrict__ p, int64_t i, float (&r)[W]) {
-  if constexpr (W == 4) {
-    const float4 t = reinterpret_cast<const float4*>(p)[i];
-    r[0] = t.x, r[1] = t.y, r[2] = t.z, r[3] = t.w;
-  } else {
-    r[0] = p[i];
-  }
-}
-template <int W>
-__device__ __forceinline__ void st(float* p, int64_t i, const float (&r)[W]) {
-  if constexpr (W == 4)
-    reinterpret_cast<float4*>(p)[i] = make_float4(r[0], r[1], r[2], r[3]);
-  else
-    p[i] = r[0];
-}
-// what a step walks along: the prediction, or under CFG euler_cfg1's neg + scale * (pos - neg) — pos == neg gives neg (== pos) bit for bit at any scale
-template <bool CFG>
-__device__ __forceinline__ float guided(float pos, float neg, float scale) {
-  if constexpr (CFG) return fmaf(scale, pos - neg, neg);
-  return pos;
-}
-// euler_blend1's blend of a state e at time s: m = 1 gives e and m = 0 gives k = a * x0 + s * noise bit for bit (finite inputs)
-__device__ __forceinline__ float blend_at(float e, float x0, float noise, float m, float a, float s) {
-  const float k = fmaf(a, x0, s * noise);
-  const float keep = 1.0f - m;
-  return fmaf(m, e, keep * k);
-}
-struct BlendArgs {
-  const float *x0, *noise, *mask;  // all three or none
-  float a, s;                      // s: the target time, a = 1 - s
-};
-// W = 4 (16-B accesses; n counts float4s) or 1 (any alignment, any n); grid-stride like map_kernel.  The predictor reads the state and writes only xt and g1.
-template <int W, bool CFG, bool BLEND>
-__global__ __launch_bounds__(256) void heun_predict_kernel(const float* __restrict__ img, const float* __restrict__ pos, const float* __restrict__ neg, float scale, float dt,
-                                                           BlendArgs b, float* __restrict__ xt, float* __restrict__ g1, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float x[W], p[W], q[W], x0[W], z[W], m[W], g[W], o[W];
-    ld<W>(img, i, x), ld<W>(pos, i, p);
-    if constexpr (CFG) ld<W>(neg, i, q);
-    if constexpr (BLEND) ld<W>(b.x0, i, x0), ld<W>(b.noise, i, z), ld<W>(b.mask, i, m);
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      g[j] = guided<CFG>(p[j], q[j], scale);
-      o[j] = fmaf(g[j], dt, x[j]);
-      if constexpr (BLEND) o[j] = blend_at(o[j], x0[j], z[j], m[j], b.a, b.s);
-    }
-    st<W>(xt, i, o), st<W>(g1, i, g);
-  }
-}
-// img = img + ((g1 + g2) * 0.5) * dt, blended; g1 == g2 gives the Euler step along g1 bit for bit.  img is read and written at the same index only.
-template <int W, bool CFG, bool BLEND>
-__global__ __launch_bounds__(256) void heun_correct_kernel(float* img, const float* __restrict__ g1, const float* __restrict__ pos, const float* __restrict__ neg, float scale,
-                                                           float dt, BlendArgs b, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float x[W], p[W], q[W], x0[W], z[W], m[W], g[W], o[W];
-    ld<W>(img, i, x), ld<W>(pos, i, p), ld<W>(g1, i, g);
-    if constexpr (CFG) ld<W>(neg, i, q);
-    if constexpr (BLEND) ld<W>(b.x0, i, x0), ld<W>(b.noise, i, z), ld<W>(b.mask, i, m);
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      const float h = (g[j] + guided<CFG>(p[j], q[j], scale)) * 0.5f;
-      o[j] = fmaf(h, dt, x[j]);
-      if constexpr (BLEND) o[j] = blend_at(o[j], x0[j], z[j], m[j], b.a, b.s);
-    }
-    st<W>(img, i, o);
-  }
-}
-// D = img - t * g;  D' = D + w * (D - hist) (w == 0: D' = D and hist is not read);  img = a * img + c * D', blended;  hist = D.  img and hist are each read and
-// written at the same index only.
-template <int W, bool CFG, bool BLEND>
-__global__ __launch_bounds__(256) void dpmpp_2m_kernel(float* img, const float* __restrict__ pos, const float* __restrict__ neg, float scale, float t, float a, float c,
-                                                       float w, float* hist, BlendArgs b, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float x[W], p[W], q[W], x0[W], z[W], m[W], d[W], h[W], o[W];
-    ld<W>(img, i, x), ld<W>(pos, i, p);
-    if constexpr (CFG) ld<W>(neg, i, q);
-    if constexpr (BLEND) ld<W>(b.x0, i, x0), ld<W>(b.noise, i, z), ld<W>(b.mask, i, m);
-    if (w != 0.f) ld<W>(hist, i, h);  // (uniform over the grid)
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      d[j] = fmaf(-t, guided<CFG>(p[j], q[j], scale), x[j]);
-      const float dp = w != 0.f ? fmaf(w, d[j] - h[j], d[j]) : d[j];
-      o[j] = fmaf(a, x[j], c * dp);
-      if constexpr (BLEND) o[j] = blend_at(o[j], x0[j], z[j], m[j], b.a, b.s);
-    }
-    st<W>(img, i, o), st<W>(hist, i, d);
-  }
-}
-// One of the eight instantiations of a solver kernel: 16-byte accesses when n % 4 == 0 and every pointer in `ptrs` that is used is 16-byte aligned, else scalar.
-#define FMI_SOLVER_LAUNCH(KERNEL, v4, cfg, blend, n, stream, ...)                                                                                 \
-  do {                                                                                                                                            \
-    const int64_t items = (v4) ? (n) / 4 : (n);                                                                                                   \
-    const int sel = ((v4) ? 4 : 0) | ((cfg) ? 2 : 0) | ((blend) ? 1 : 0);                                                                         \
-    switch (sel) {                                                                                                                                \
-      case 0: hipLaunchKernelGGL((KERNEL<1, false, false>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                   \
-      case 1: hipLaunchKernelGGL((KERNEL<1, false, true>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                    \
-      case 2: hipLaunchKernelGGL((KERNEL<1, true, false>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                    \
-      case 3: hipLaunchKernelGGL((KERNEL<1, true, true>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                     \
-      case 4: hipLaunchKernelGGL((KERNEL<4, false, false>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                   \
-      case 5: hipLaunchKernelGGL((KERNEL<4, false, true>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                    \
-      case 6: hipLaunchKernelGGL((KERNEL<4, true, false>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                    \
-      default: hipLaunchKernelGGL((KERNEL<4, true, true>), map_grid(items), dim3(256), 0, stream, __VA_ARGS__, items); break;                    \
-    }                                                                                                                                             \
-  } while (0)
-inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
-  for (const void* p : ptrs)
-    if (p && !aligned16(p)) return false;  // (a null pointer is an operand the instantiation never touches)
-  return true;
-}
-}  // namespace
-
-// The Heun predictor in one pass: g1 = pos, or with neg the guided neg + scale * (pos - neg);  xt = img + g1 * dt, or with x0 / noise / mask (all three or none)
-// its blend at the target time s.  The state is only read.
-int launch_heun_predict(const float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, float* xt, float* g1, hipStream_t stream, const float* x0,
-                        const float* noise, const float* mask, float s) {
-  if (n <= 0) return FMI_OK;
-  const bool blend = x0 && noise && mask;
-  if (!blend && (x0 || noise || mask)) return fail(FMI_ERR_INVALID, "heun_predict: x0, noise and mask go together (all three or none)");
-  const bool v4 = n % 4 == 0 && all_aligned16({img, pos, neg, xt, g1, x0, noise, mask});
-  const BlendArgs b{x0, noise, mask, 1.0f - s, s};
-  FMI_SOLVER_LAUNCH(heun_predict_kernel, v4, neg != nullptr, blend, n, stream, img, pos, neg, scale, dt, b, xt, g1);
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-// The Heun corrector in one pass: g2 = pos or the guided combination;  img = img + ((g1 + g2) * 0.5) * dt, blended like the predictor's.
-int launch_heun_correct(float* img, const float* g1, const float* pos, const float* neg, float scale, float dt, int64_t n, hipStream_t stream, const float* x0,
-                        const float* noise, const float* mask, float s) {
-  if (n <= 0) return FMI_OK;
-  const bool blend = x0 && noise && mask;
-  if (!blend && (x0 || noise || mask)) return fail(FMI_ERR_INVALID, "heun_correct: x0, noise and mask go together (all three or none)");
-  const bool v4 = n % 4 == 0 && all_aligned16({img, g1, pos, neg, x0, noise, mask});
-  const BlendArgs b{x0, noise, mask, 1.0f - s, s};
-  FMI_SOLVER_LAUNCH(heun_correct_kernel, v4, neg != nullptr, blend, n, stream, img, g1, pos, neg, scale, dt, b);
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-// The DPM-Solver++ 2M step in one pass (a, c, w: dpmpp_2m_coefficients; t: the step's time): the state and the history are both updated in place.
-int launch_dpmpp_2m(float* img, const float* pos, const float* neg, float scale, float t, float a, float c, float w, int64_t n, float* hist, hipStream_t stream,
-                    const float* x0, const float* noise, const float* mask, float s) {
-  if (n <= 0) return FMI_OK;
-  const bool blend = x0 && noise && mask;
-  if (!blend && (x0 || noise || mask)) return fail(FMI_ERR_INVALID, "dpmpp_2m_step: x0, noise and mask go together (all three or none)");
-  const bool v4 = n % 4 == 0 && all_aligned16({img, pos, neg, hist, x0, noise, mask});
-  const BlendArgs b{x0, noise, mask, 1.0f - s, s};
-  FMI_SOLVER_LAUNCH(dpmpp_2m_kernel, v4, neg != nullptr, blend, n, stream, img, pos, neg, scale, t, a, c, w, hist, b);
-  FMI_LAUNCH_CHECK();
-  return FMI_OK;
-}
-#undef FMI_SOLVER_LAUNCH
-
-// A solver's schedule: ts[0..n_steps] strictly decreasing inside [0, 1] (NaN fails every comparison).
-int check_solver_schedule(const double* ts, int n_steps, const char* who) {
-  if (!ts || n_steps < 0) return fail(FMI_ERR_INVALID, std::string(who) + ": null schedule or negative n_steps");
-  if (!(ts[0] <= 1.0) || !(ts[n_steps] >= 0.0)) return fail(FMI_ERR_INVALID, std::string(who) + ": a solver's schedule lies in [0, 1] (1 >= ts[0], ts[n_steps] >= 0)");
-  for (int i = 0; i < n_steps; ++i)
-    if (!(ts[i + 1] < ts[i])) return fail(FMI_ERR_INVALID, std::string(who) + ": a solver's schedule is strictly decreasing");
-  return FMI_OK;
-}
-// Step i's scalars of DPM-Solver++ 2M under flow matching (sigma = t, alpha = 1 - t, lambda = ln((1 - t) / t)), in f64 and rounded once:
-//   a = t_{i+1} / t_i, c = 1 - a, w = (l_{i+1} - l_i) / (2 (l_i - l_{i-1})) — and w = 0 without history, after t_{i-1} == 1 and into t_{i+1} == 0.
-void dpmpp_2m_coefficients(const double* ts, int i, float* a, float* c, float* w) {
-  const double t0 = ts[i], t1 = ts[i + 1], ad = t1 / t0;
-  double wd = 0.0;
-  if (i > 0 && ts[i - 1] != 1.0 && t1 != 0.0) {
-    const auto lam = [](double t) { return std::log((1.0 - t) / t); };
-    wd = (lam(t1) - lam(t0)) / (2.0 * (lam(t0) - lam(ts[i - 1])));
-  }
-  *a = (float)ad, *c = (float)(1.0 - ad), *w = (float)wd;
-}
 
 // out = (1 - t) * x0 + t * noise  (FlowMatchEulerDiscreteScheduler.scale_noise)
 int launch_scale_noise(const float* x0, const float* noise, float t, int64_t n, float* out, hipStream_t stream) {
@@ -611,7 +350,7 @@ int launch_splitk_resid_gate(const float* parts, int S, const bf16_t* bias, cons
   if (N % 4 || ldo % 4) return fail(FMI_ERR_INVALID, "splitk reduce: N and ldo must be multiples of 4");
   if (!gate) return fail(FMI_ERR_INVALID, "splitk reduce: needs a gate vector");
   const int64_t total = (int64_t)M * (N / 4);
-  splitk_resid_gate_kernel<<<(int)std::min<int64_t>((total + 255) / 256, 2048), 256, 0, stream>>>(reinterpret_cast<const float4*>(parts), S, bias, gate, rows_per_batch,
+  splitk_resid_gate_kernel<<<map_grid(total), 256, 0, stream>>>(reinterpret_cast<const float4*>(parts), S, bias, gate, rows_per_batch,
                                                                                                  gate_bstride, out, ldo, M, N / 4);
   FMI_LAUNCH_CHECK();
   return FMI_OK;
@@ -891,48 +630,6 @@ extern "C" int fmi_fill_condition(const float* masked_latents, const float* mask
   return FMI_OK;
 }
 
-extern "C" int fmi_cfg_euler_step(float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, const float* x0, const float* noise,
-                                  const float* mask, float s, void* stream) {
-  if (!img || !pos || !neg || n < 0) return fail(FMI_ERR_INVALID, "cfg_euler_step: bad arguments");
-  if (!(scale >= 0.f) || std::isinf(scale)) return fail(FMI_ERR_INVALID, "cfg_euler_step: scale must be finite and >= 0");
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, "cfg_euler_step: x0, noise and mask go together (all three or none)");
-  return launch_euler_cfg(img, pos, neg, scale, dt, n, (hipStream_t)stream, x0, noise, mask, s);
-}
-// The solvers' updates on their own.  neg NULL: no guidance, scale is not looked at.
-static int check_solver_step(const char* who, const void* neg, float scale, int64_t n, const float* x0, const float* noise, const float* mask) {
-  if (n < 0) return fail(FMI_ERR_INVALID, std::string(who) + ": n must not be negative");
-  if (neg && (!(scale >= 0.f) || std::isinf(scale))) return fail(FMI_ERR_INVALID, std::string(who) + ": scale must be finite and >= 0");
-  if ((x0 || noise || mask) && !(x0 && noise && mask)) return fail(FMI_ERR_INVALID, std::string(who) + ": x0, noise and mask go together (all three or none)");
-  return FMI_OK;
-}
-extern "C" int fmi_heun_predict(const float* img, const float* pos, const float* neg, float scale, float dt, int64_t n, float* x_pred, float* g1, const float* x0,
-                                const float* noise, const float* mask, float s, void* stream) {
-  if (!img || !pos || !x_pred || !g1) return fail(FMI_ERR_INVALID, "heun_predict: null img / pos / x_pred / g1");
-  if (x_pred == img || g1 == img || x_pred == g1) return fail(FMI_ERR_INVALID, "heun_predict: img, x_pred and g1 are three buffers");
-  FMI_TRY(check_solver_step("heun_predict", neg, scale, n, x0, noise, mask));
-  return launch_heun_predict(img, pos, neg, scale, dt, n, x_pred, g1, (hipStream_t)stream, x0, noise, mask, s);
-}
-extern "C" int fmi_heun_correct(float* img, const float* g1, const float* pos, const float* neg, float scale, float dt, int64_t n, const float* x0, const float* noise,
-                                const float* mask, float s, void* stream) {
-  if (!img || !g1 || !pos) return fail(FMI_ERR_INVALID, "heun_correct: null img / g1 / pos");
-  if (g1 == img) return fail(FMI_ERR_INVALID, "heun_correct: img and g1 are two buffers");
-  FMI_TRY(check_solver_step("heun_correct", neg, scale, n, x0, noise, mask));
-  return launch_heun_correct(img, g1, pos, neg, scale, dt, n, (hipStream_t)stream, x0, noise, mask, s);
-}
-extern "C" int fmi_dpmpp_2m_step(float* img, const float* pos, const float* neg, float scale, float t, float a, float c, float w, int64_t n, float* history,
-                                 const float* x0, const float* noise, const float* mask, float s, void* stream) {
-  if (!img || !pos || !history) return fail(FMI_ERR_INVALID, "dpmpp_2m_step: null img / pos / history");
-  if (history == img) return fail(FMI_ERR_INVALID, "dpmpp_2m_step: img and history are two buffers");
-  FMI_TRY(check_solver_step("dpmpp_2m_step", neg, scale, n, x0, noise, mask));
-  return launch_dpmpp_2m(img, pos, neg, scale, t, a, c, w, n, history, (hipStream_t)stream, x0, noise, mask, s);
-}
-extern "C" int fmi_dpmpp_2m_coefficients(const double* timesteps_host, int n_steps, int i, float* a, float* c, float* w) {
-  if (!a || !c || !w) return fail(FMI_ERR_INVALID, "dpmpp_2m_coefficients: null output");
-  FMI_TRY(check_solver_schedule(timesteps_host, n_steps, "dpmpp_2m_coefficients"));
-  if (i < 0 || i >= n_steps) return fail(FMI_ERR_INVALID, "dpmpp_2m_coefficients: step i outside [0, n_steps)");
-  dpmpp_2m_coefficients(timesteps_host, i, a, c, w);
-  return FMI_OK;
-}
 extern "C" int fmi_scale_noise(const float* x0, const float* noise, double t, int64_t n, float* out, void* stream) {
   if (!x0 || !noise || !out || n < 0) return fail(FMI_ERR_INVALID, "scale_noise: bad arguments");
   return launch_scale_noise(x0, noise, (float)t, n, out, (hipStream_t)stream);

@@ -14,8 +14,6 @@ namespace {
 constexpr int SC_THREADS = 256, SC_ITERS = 8;
 constexpr int64_t SC_CHUNK = (int64_t)SC_THREADS * 4 * SC_ITERS;  // elements of one sample per workgroup
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <bool V4>
 __device__ __forceinline__ void load4(const float* p, int64_t left, float (&v)[4]) {
   if constexpr (V4) {

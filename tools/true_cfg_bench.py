@@ -10,7 +10,7 @@ process after a warm-up of both (then the B = 1 loop, whose workspace has anothe
 
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/true_cfg_bench.py 1 4
 
-gives the kernel time of euler_cfg_kernel (4096 x 64 elements per step, whatever the step count).
+gives the kernel time of the guided update, step_kernel<4, true, false, EulerOp> (4096 x 64 elements per step, whatever the step count).
 
 Part (b) of the profile is bench.py itself, run alternately from this commit's tree and from its parent's."""
 import os
