@@ -32,6 +32,9 @@ build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -Ibuild -c $< -o $@
 
+# attention_d64 scales its f32x4 accumulators by a scalar: keep that on plain v_mul_f32 (no packed-f32 VALU forms in this object)
+build/attention_d64.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 build/alt/%.o: $(CSRC)/%.hip $(HDRS) build/build_id.h
 	@mkdir -p build/alt
 	$(HIPCC) $(HIPFLAGS) -DFMI_ALT_KERNELS=1 -Ibuild -c $< -o $@

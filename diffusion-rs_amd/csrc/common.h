@@ -442,6 +442,14 @@ int launch_sp_unpack_o(const void* recv, const AttnOut& out, int H, int Ll, int 
 // key-split attention: parts (S, L, W) bf16 normalised partial outputs, lse (S, W/128 heads, L) f32 (log2 domain) ->
 // out (L, W) = sum_s 2^(lse_s - max) parts_s / sum_s 2^(lse_s - max)
 int launch_sp_merge_splits(const bf16_t* parts, const float* lse, int S, bf16_t* out, int heads, int L, hipStream_t s);
+// flash attention, d = 64, with an additive bias and a causal mask (attention_d64.hip): q, k, v, out bf16 token-major (B, T, H, 64), each with
+// its own element strides {batch, token, head}; bias f32 (H, Tq, Tk) or null; causal: key j > query i is masked.  Any Tq, Tk >= 1; 16-byte aligned operands
+// take the LDS-DMA form of the kernel, others its 2-byte-load form.
+int launch_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int H, int Tq, int Tk, const int64_t* sq, const int64_t* sk,
+                         const int64_t* sv, const int64_t* so, float scale, const float* bias, int causal, hipStream_t stream);
+// the attention of the T5 / CLIP text / CLIP vision layers (fmi_set_encoder_attention): 0 = encoder_common.h's lane-per-key kernel (default), 1 = attention_d64
+int encoder_attention_kind();
+void set_encoder_attention_kind(int kind);
 // q/k RMSNorm (eps 1e-6, weight (128)) + RoPE, token-major in (row stride ld, head h at col h*128)
 // -> head-major (B,H,Ltot,128) at row offset row_off.  pe: (B or 1, Ltot, 64, 2) f32 {cos,sin}
 int launch_qk_norm_rope(const bf16_t* q, const bf16_t* k, int ld, int64_t in_bstride, const bf16_t* wq,

@@ -264,7 +264,13 @@ GemmProblem lin(const bf16_t* A, int lda, const bf16_t* W, const bf16_t* bias, v
   return p;
 }
 
+// The attention step of a d = 64 layer on the fused (B T, 3 H 64) projection.  fmi_set_encoder_attention(1): the MFMA kernel of attention_d64.hip reads q, k
+// and v where they lie (three strided views of qkv) — any T; 0: the lane-per-key kernel above, T <= 64 * ENC_MAXKB.
 int enc_attention(const bf16_t* qkv, const float* bias, int B, int T, int H, float scale, int causal, bf16_t* out, hipStream_t s) {
+  if (encoder_attention_kind() == 1) {
+    const int64_t I = (int64_t)H * 64, in[3] = {T * 3 * I, 3 * I, 64}, ot[3] = {T * I, I, 64};
+    return launch_attention_d64(qkv, qkv + I, qkv + 2 * I, out, B, H, T, T, in, in, in, ot, scale, bias, causal, s);
+  }
   if (T > 64 * ENC_MAXKB) return fail(FMI_ERR_UNSUPPORTED, "text encoder attention: sequence longer than " + std::to_string(64 * ENC_MAXKB));
   const size_t sm = 4 * (64 + (size_t)T) * sizeof(float);
   hipLaunchKernelGGL(enc_attention_kernel, dim3((T + 3) / 4, H, B), dim3(256), sm, s, qkv, bias, B, T, H, scale, causal, out);

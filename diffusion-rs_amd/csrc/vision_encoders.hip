@@ -274,7 +274,7 @@ extern "C" int fmi_clip_vision_create(const fmi_clip_vision_config* cfg, fmi_cli
   if (cfg->patch_size <= 0 || cfg->image_size <= 0 || cfg->image_size % cfg->patch_size || cfg->image_size > 16384)
     return fail(FMI_ERR_INVALID, "clip_vision_create: image_size must be a positive multiple of patch_size");
   const int64_t G = cfg->image_size / cfg->patch_size, T = 1 + G * G;
-  if (T > 64 * ENC_MAXKB)
+  if (T > 64 * ENC_MAXKB && encoder_attention_kind() == 0)  // (under fmi_set_encoder_attention(1) any token count; a later switch back to 0 is refused at encode time)
     return fail(FMI_ERR_UNSUPPORTED, "clip_vision_create: " + std::to_string(T) + " tokens (1 + (image_size / patch_size)^2) are more than the encoder attention's " +
                                          std::to_string(64 * ENC_MAXKB));
   if (cfg->patch_size > 256) return fail(FMI_ERR_INVALID, "clip_vision_create: patch_size must be at most 256");

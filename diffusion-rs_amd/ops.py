@@ -1,0 +1,49 @@
+"""Op-level seams that are not part of a model handle: the d = 64 attention of the encoders and the switch that sends the encoders to it."""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from .flux import _ptr, _stream
+
+ENCODER_ATTENTION = {"default": 0, "mfma": 1}
+
+
+def encoder_attention_kind(name) -> int:
+    """"default" | "mfma" -> fmi_set_encoder_attention's number; anything else raises by name."""
+    if name not in ENCODER_ATTENTION:
+        raise ValueError(f"encoder_attention must be one of {sorted(ENCODER_ATTENTION)}, got {name!r}")
+    return ENCODER_ATTENTION[name]
+
+
+def set_encoder_attention(name) -> None:
+    """The process-wide attention kernel of the T5, CLIP text and CLIP vision layers (fmi_set_encoder_attention): "default" = the lane-per-key kernel (at
+    most 1024 tokens), "mfma" = the kernel of sdpa_d64 (any length).  Needs no GPU."""
+    L.check(L.load().fmi_set_encoder_attention(encoder_attention_kind(name)))
+
+
+def get_encoder_attention() -> str:
+    kind = L.load().fmi_get_encoder_attention()
+    return next(k for k, v in ENCODER_ATTENTION.items() if v == kind)
+
+
+def sdpa_d64(q, k, v, bias=None, causal=False, scale=None):
+    """fmi_sdpa_d64_bf16: softmax(q k^T * scale + bias [+ causal]) v at head dim 64.  q (B,Tq,H,64), k and v (B,Tk,H,64) bfloat16 with unit stride inside a
+    head, any other strides (views of a fused projection are read where they lie); bias (H,Tq,Tk) float32 or None; causal: key j > query i is masked; scale:
+    1 / sqrt(64) by default (T5 passes 1).  Returns (B,Tq,H,64) bfloat16."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[3] != 64 or t.stride(3) != 1 or not t.is_cuda:
+            raise TypeError(f"sdpa_d64: {name} must be a bfloat16 device tensor (B,T,H,64) with contiguous heads, got {t.dtype} {tuple(t.shape)}")
+    B, Tq, H, _ = (int(x) for x in q.shape)
+    Tk = int(k.shape[1])
+    if tuple(k.shape) != (B, Tk, H, 64) or tuple(v.shape) != tuple(k.shape) or Tq < 1 or Tk < 1:
+        raise ValueError(f"sdpa_d64: shapes q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit")
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (H, Tq, Tk) or not bias.is_cuda:
+            raise TypeError(f"sdpa_d64: bias must be a float32 device tensor ({H},{Tq},{Tk}), got {bias.dtype} {tuple(bias.shape)}")
+        bias = bias.contiguous()
+    out = torch.empty((B, Tq, H, 64), dtype=torch.bfloat16, device=q.device)
+    strides = (C.c_int64 * 12)(*(int(t.stride(i)) for t in (q, k, v, out) for i in (0, 1, 2)))
+    L.check(L.load().fmi_sdpa_d64_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Tq, Tk, strides, float(64 ** -0.5 if scale is None else scale), _ptr(bias),
+                                       1 if causal else 0, _stream()))
+    return out

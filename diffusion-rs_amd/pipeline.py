@@ -419,12 +419,18 @@ class Pipeline:
     """== diffusion_rs_core::Pipeline (pipelines/mod.rs:110-270) for FluxPipeline."""
 
     def __init__(self, source: ModelSource, silent: bool = False, token: Optional[str] = None, revision: Optional[str] = None,
-                 offloading: Optional[Offloading] = None, dtype: ModelDType = ModelDType.Auto, *, device: int = 0):
+                 offloading: Optional[Offloading] = None, dtype: ModelDType = ModelDType.Auto, *, device: int = 0, encoder_attention: str = "default"):
+        # encoder_attention: "default" | "mfma" — the attention kernel of the T5 / CLIP text / CLIP vision layers (DESIGN.md 4.22), a PROCESS-WIDE switch that
+        # is set here, before any encoder exists
+        from . import ops
+        ops.encoder_attention_kind(encoder_attention)  # (a bad name raises before anything is loaded)
         if dtype in (ModelDType.F16, ModelDType.F32):
             raise ValueError("this build computes in bf16 on MFMA (f32 accumulate); use ModelDType.Auto or BF16")
         self.silent = silent
         self.offloading = offloading
         self.device_index = device
+        self.encoder_attention = encoder_attention
+        ops.set_encoder_attention(encoder_attention)
         self.device = torch.device("cuda", device)
         self._lock = threading.Lock()  # Arc<Mutex<dyn ModelPipeline>>, pipelines/mod.rs:110-113
         self.last_cache_stats = []  # the step-cache stats of the last request (generate_tensor's cache_threshold=), one entry per denoise call
@@ -833,7 +839,7 @@ class Pipeline:
             cfg = dict(loader.clip_vision_config(cfg), **{k: cfg[k] for k in ("image_mean", "image_std") if k in cfg})
             sd = loader.clip_vision_from_tensors(cfg, sd)
         with self._lock:
-            enc = text.ClipVisionModel(cfg, self.device.index or 0, cfg.get("image_mean"), cfg.get("image_std"))
+            enc = text.ClipVisionModel(cfg, self.device.index or 0, cfg.get("image_mean"), cfg.get("image_std"), encoder_attention=self.encoder_attention)
             enc.load_state_dict(sd)
             old, self.image_encoder = getattr(self, "image_encoder", None), enc
             if old is not None:

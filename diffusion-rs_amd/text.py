@@ -42,9 +42,13 @@ def _as_tensor(x):
 class _Encoder:
     _kind = ""
 
-    def _open(self, device, create_fn, *args):
-        """The constructor steps every handle shares: the library, the device, and the handle that the library's `create_fn(*args, &handle)` makes."""
+    def _open(self, device, create_fn, *args, encoder_attention=None):
+        """The constructor steps every handle shares: the library, the device, and the handle that the library's `create_fn(*args, &handle)` makes.
+        encoder_attention ("default" | "mfma"; the d = 64 encoders): sets the PROCESS-WIDE attention kernel of those encoders first (ops.set_encoder_attention)."""
         self.lib = L.load()
+        if encoder_attention is not None:
+            from . import ops
+            ops.set_encoder_attention(encoder_attention)
         L.check(self.lib.fmi_init(device), self.lib)
         self.device = torch.device("cuda", device)
         h = C.c_void_p()
@@ -98,14 +102,14 @@ class _Encoder:
 class T5EncoderModel(_Encoder):
     _kind = "t5"
 
-    def __init__(self, cfg: dict = None, device: int = 0):
+    def __init__(self, cfg: dict = None, device: int = 0, encoder_attention=None):
         cfg = dict(T5_XXL if cfg is None else cfg)
         # `quantization_config` (bitsandbytes nf4 / fp4 / LLM.int8, t5/mod.rs:85-90): the quantised Linears arrive through
         # set_linear_bnb4 / set_linear_int8 (loader.load_text_encoder); nothing to configure up front
         self.cfg = cfg
         c = L.T5Config(cfg["vocab_size"], cfg["d_model"], cfg["d_kv"], cfg["d_ff"], cfg["num_layers"], cfg["num_heads"], cfg["relative_attention_num_buckets"],
                        cfg.get("relative_attention_max_distance", 128), cfg["layer_norm_epsilon"], _T5_ACT[cfg.get("feed_forward_proj", "relu")])
-        self._open(device, "fmi_t5_create", C.byref(c))
+        self._open(device, "fmi_t5_create", C.byref(c), encoder_attention=encoder_attention)
 
     def tensor_names(self):
         from . import synth
@@ -138,12 +142,12 @@ class T5EncoderModel(_Encoder):
 class ClipTextTransformer(_Encoder):
     _kind = "clip"
 
-    def __init__(self, cfg: dict = None, device: int = 0):
+    def __init__(self, cfg: dict = None, device: int = 0, encoder_attention=None):
         cfg = dict(CLIP_L if cfg is None else cfg)
         self.cfg = cfg
         c = L.ClipConfig(cfg["vocab_size"], cfg["projection_dim"], cfg["intermediate_size"], cfg["max_position_embeddings"], cfg["num_hidden_layers"],
                          cfg["num_attention_heads"])
-        self._open(device, "fmi_clip_create", C.byref(c))
+        self._open(device, "fmi_clip_create", C.byref(c), encoder_attention=encoder_attention)
 
     def tensor_names(self):
         from . import synth
@@ -181,13 +185,13 @@ class _VisionTower(_Encoder):
     """What the vision towers share: the image processor on the GPU (a bicubic resize to the tower's own shape, the centre crop to image_size, (v / 255 - mean) /
     std) and the checks of what goes into forward.  A tower adds its resize rule (`_resized`), its forward and its properties."""
 
-    def _open_tower(self, device, cfg, image_mean, image_std, default_mean, default_std, create_fn, config):
+    def _open_tower(self, device, cfg, image_mean, image_std, default_mean, default_std, create_fn, config, encoder_attention=None):
         self.cfg = cfg
         self.image_mean = tuple(float(v) for v in (default_mean if image_mean is None else image_mean))
         self.image_std = tuple(float(v) for v in (default_std if image_std is None else image_std))
         if len(self.image_mean) != 3 or len(self.image_std) != 3:
             raise ValueError("image_mean and image_std hold one value per RGB channel")
-        self._open(device, create_fn, C.byref(config))
+        self._open(device, create_fn, C.byref(config), encoder_attention=encoder_attention)
 
     def _pixel_values(self, pixel_values):
         """forward's input, checked, as f32 (B,3,S,S) on the device."""
@@ -234,10 +238,10 @@ class ClipVisionModel(_VisionTower):
     ip_adapter_image_embeds= takes.  cfg: HuggingFace's CLIPVisionConfig keys (CLIP_VISION_L by default); image_mean / image_std: the processor's constants."""
     _kind = "clip_vision"
 
-    def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None):
+    def __init__(self, cfg: dict = None, device: int = 0, image_mean=None, image_std=None, encoder_attention=None):
         cfg = {k: int((CLIP_VISION_L if cfg is None else cfg)[k]) for k in CLIP_VISION_L}
         self._open_tower(device, cfg, image_mean, image_std, CLIP_IMAGE_MEAN, CLIP_IMAGE_STD, "fmi_clip_vision_create",
-                         L.ClipVisionConfig(*(cfg[k] for k in CLIP_VISION_L)))
+                         L.ClipVisionConfig(*(cfg[k] for k in CLIP_VISION_L)), encoder_attention=encoder_attention)
 
     @property
     def projection_dim(self) -> int:

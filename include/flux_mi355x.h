@@ -1247,6 +1247,20 @@ int fmi_sdpa_bf16_ws(const void* q, const void* k, const void* v, void* o, int B
  *   three are bit-identical to each other, and equal to 3 / 4 to rounding (3 / 4 round q * scale * log2(e) to bf16 once and
  *   normalise by the sum of the bf16-rounded probabilities: rel-L2 ~3e-3 between the families, both within the oracle tolerance). */
 int fmi_set_attention_kernel(int kind);
+/* softmax(q k^T * scale + bias [+ causal]) v at head dim 64 (attention_d64.hip): the attention of T5 (d_kv 64, additive relative-position bias,
+ * scale 1), CLIP text (causal) and CLIP vision as one op — ops::sdpa with a head dim of 64 and a bias or a mask.  q, k, v, o: bf16, token-major (B, T, H, 64)
+ * with 64 contiguous channels; `strides` holds 12 element strides, {batch, token, head} of q, k, v, o in that order (so the operands may be the thirds of a
+ * fused (B, T, 3 H 64) projection), or NULL for four contiguous (B, T, H, 64) tensors.  bias: f32 (H, Tq, Tk) contiguous, shared by the batch, or NULL.
+ * causal != 0: key j > query i is masked.  Any Tq, Tk >= 1.  Asynchronous on `stream`; allocates nothing, never synchronises.  Operands that are 16-byte
+ * aligned (pointers, and strides that are multiples of 8) take the LDS-DMA form of the kernel, others a slower form with 2-byte loads. */
+int fmi_sdpa_d64_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Tq, int Tk, const int64_t* strides, float scale,
+                      const float* bias_or_null, int causal, void* stream);
+/* PROCESS-WIDE: the attention kernel of the T5, CLIP text and CLIP vision layers.  0 (default): the lane-per-key kernel of encoder_common.h (sequences of at
+ * most 1024 tokens); 1: the MFMA kernel of fmi_sdpa_d64_bf16 (any length; the 1024-token refusals of fmi_t5_forward and fmi_clip_vision_create do not apply).
+ * The environment variable FMI_ENCODER_ATTENTION (0 | 1, read once at load) sets the initial value.  The two agree to rounding, not bit for bit.  The SigLIP
+ * tower keeps its d = 128 attention.  Set it before creating encoders and before starting work on other threads. */
+int fmi_set_encoder_attention(int kind);
+int fmi_get_encoder_attention(void);
 /* Same with q and k as OCP e4m3 bytes (B,H,L,128): QK^T on the fp8 MFMA, softmax / P / V in f32 / bf16 as above.
  * `scale` must include 1 / (q scale * k scale).  The fp8-mode attention of fmi_flux_* (fmi_flux_set_fp8_attention). */
 int fmi_sdpa_fp8qk(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
