@@ -30,7 +30,8 @@ def get_encoder_attention() -> str:
 def sdpa_d64(q, k, v, bias=None, causal=False, scale=None):
     """fmi_sdpa_d64_bf16: softmax(q k^T * scale + bias [+ causal]) v at head dim 64.  q (B,Tq,H,64), k and v (B,Tk,H,64) bfloat16 with unit stride inside a
     head, any other strides (views of a fused projection are read where they lie); bias (H,Tq,Tk) float32 or None; causal: key j > query i is masked; scale:
-    1 / sqrt(64) by default (T5 passes 1).  Returns (B,Tq,H,64) bfloat16."""
+    1 / sqrt(64) by default (T5 passes 1).  Returns (B,Tq,H,64) bfloat16.  A bias of -inf masks a key, on any part of a row (whole 64-key tiles included);
+    a row whose visible keys are all masked that way is unsupported: its output is undefined (the kernel divides by a row sum of 0)."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[3] != 64 or t.stride(3) != 1 or not t.is_cuda:
             raise TypeError(f"sdpa_d64: {name} must be a bfloat16 device tensor (B,T,H,64) with contiguous heads, got {t.dtype} {tuple(t.shape)}")

@@ -1252,7 +1252,9 @@ int fmi_set_attention_kernel(int kind);
  * with 64 contiguous channels; `strides` holds 12 element strides, {batch, token, head} of q, k, v, o in that order (so the operands may be the thirds of a
  * fused (B, T, 3 H 64) projection), or NULL for four contiguous (B, T, H, 64) tensors.  bias: f32 (H, Tq, Tk) contiguous, shared by the batch, or NULL.
  * causal != 0: key j > query i is masked.  Any Tq, Tk >= 1.  Asynchronous on `stream`; allocates nothing, never synchronises.  Operands that are 16-byte
- * aligned (pointers, and strides that are multiples of 8) take the LDS-DMA form of the kernel, others a slower form with 2-byte loads. */
+ * aligned (pointers, and strides that are multiples of 8) take the LDS-DMA form of the kernel, others a slower form with 2-byte loads.
+ * A bias of -inf masks a key: supported on any part of a row, whole 64-key tiles included (such keys contribute exactly nothing).  A row whose visible keys
+ * are ALL masked by a -inf bias is unsupported: the kernel has no branch for it (it divides by a row sum of 0) and that row's output is undefined. */
 int fmi_sdpa_d64_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Tq, int Tk, const int64_t* strides, float scale,
                       const float* bias_or_null, int causal, void* stream);
 /* PROCESS-WIDE: the attention kernel of the T5, CLIP text and CLIP vision layers.  0 (default): the lane-per-key kernel of encoder_common.h (sequences of at

@@ -55,11 +55,17 @@ def _reference(q, k, v, bias, causal, scale):
     return (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3).cpu().numpy()
 
 
-def _check(got, want, Tk, what, old_inputs=False):
+def _check(got, want, Tk, what, old_inputs=False, any_tk=False):
+    """any_tk: a key count the old kernel was not measured at is held to the largest rel-L2 figure of OLD_KERNEL (the table is flat in Tk, 1.653e-3 ..
+    1.667e-3: the bf16 rounding of the output dominates), and to the max-abs rule of inputs the old kernel was not measured on."""
     import torch
     got = host(got.float()).astype(np.float64)
     err, mx = rel_l2(got, want), float(np.abs(got - want).max())
-    old_err, old_mx = OLD_KERNEL[Tk]
+    if any_tk and Tk not in OLD_KERNEL:
+        assert not old_inputs
+        old_err, old_mx = max(e for e, _ in OLD_KERNEL.values()), float("nan")
+    else:
+        old_err, old_mx = OLD_KERNEL[Tk]
     best = float(np.abs(torch.from_numpy(want).to(torch.bfloat16).double().numpy() - want).max())  # the float64 result rounded to bf16
     mx_bound = 1.5 * (old_mx if old_inputs else best)
     print(f"sdpa_d64 {what}: rel-L2 {err:.3e} (bound {1.5 * old_err:.3e}), max-abs {mx:.3e} (bound {mx_bound:.3e}; the old kernel {old_mx:.3e}, the best bf16 answer {best:.3e})")
