@@ -447,6 +447,14 @@ int launch_sp_merge_splits(const bf16_t* parts, const float* lse, int S, bf16_t*
 // take the LDS-DMA form of the kernel, others its 2-byte-load form.
 int launch_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int H, int Tq, int Tk, const int64_t* sq, const int64_t* sk,
                          const int64_t* sv, const int64_t* so, float scale, const float* bias, int causal, hipStream_t stream);
+// flash attention, d = 128, with token group masks (attention_groups.hip): operands and output as launch_attention_ex's bf16 form; query i sees
+// key j iff (q_groups[i] & k_groups[j]) != 0.  Words uint32 (groups_batch, L), groups_batch 1 (shared by the batch) or B; ksum = launch_key_tile_summary of
+// k_groups (attention_groups_summary_bytes).  The caller guarantees that every query sees at least one key (else that row's output is undefined).  q, k, vt
+// 16-byte aligned.  Asynchronous, no workspace.
+size_t attention_groups_summary_bytes(int groups_batch, int Lk);
+int launch_key_tile_summary(const uint32_t* k_groups, int groups_batch, int Lk, uint32_t* ksum, hipStream_t stream);
+int launch_attention_groups(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const AttnOut& out, int B, int H, int Lq, int Lk, int Lkpad, float scale,
+                            const uint32_t* q_groups, const uint32_t* k_groups, const uint32_t* ksum, int groups_batch, hipStream_t stream);
 // the attention of the T5 / CLIP text / CLIP vision layers (fmi_set_encoder_attention): 0 = encoder_common.h's lane-per-key kernel (default), 1 = attention_d64
 int encoder_attention_kind();
 void set_encoder_attention_kind(int kind);

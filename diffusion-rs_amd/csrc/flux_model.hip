@@ -143,6 +143,11 @@ struct fmi_flux {
   float phase_ms[PH_COUNT] = {0};
   int attn_thr = 96;
   int attn_kind = -1;  // fmi_flux_set_attention_kernel: 0..5 = this handle's attention kernel, -1 = follow the process-wide switch
+  // token group masks (fmi_flux_set_attention_groups): the words of the joint sequence, uint32 (grp_B, grp_T + grp_S), and behind them the
+  // key tiles' summaries.  Empty = no set: every attention launch is the one it always was.
+  DeviceBuffer grp_words;
+  uint32_t* grp_sum = nullptr;
+  int grp_T = 0, grp_S = 0, grp_B = 0;
   // 4-bit weights, large-M regime: per-layer streaming dequant into a reusable bf16 scratch
   // all denoise steps' modulation vectors (n_steps*B, n_mod) and vec (n_steps*B, D), see fmi_flux_denoise
   DeviceBuffer mod_steps, vec_steps, temb_steps, h1_steps;  // f32
@@ -1084,6 +1089,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
   // afterwards: 4 n_double + 2 n_single small synchronous device-to-host copies, once — not legal under stream capture, like set_tensor itself)
   if (m->fp8_attn == 2 && !sp && !m->attn_scales_valid) FMI_TRY(compute_attention_scales(m));
   const bool qk8_any = m->fp8_attn == 2 && !sp;  // opt-in: e4m3 q, k in front of QK^T whatever the block linears run on
+  const uint32_t* const grp = m->grp_words.as<uint32_t>();  // the installed token group words (validate() has refused what they do not combine with), else null
   const int BT = B * T;  // a8 / a8s rows: [txt (B*T) | img (B*S)]
   // The two ControlNet hooks, after double block i (single = false) or single block i: `rows` = where the block left the image rows, sample b at rows + b * bs.
   //   capture (a ControlNet handle)   sample = bf16(zero_linear(bf16(rows))): the rows cast into the free LayerNorm output buffer, then the existing GEMM launcher
@@ -1208,6 +1214,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       o.p1 = w.attn_img, o.ld1 = D, o.bstride1 = (int64_t)S * D;
       const float sc = qk8 ? att_scale / (m->q8_dbl[i] * m->k8_dbl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
+      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->grp_B, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_dbl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     if (m->two_streams && !fp8 && !sp && !m->profiling && !m->calib && !bw.proj[0].q_type && !bw.proj[1].q_type && !bw.mlp1[0].q_type && !bw.mlp1[1].q_type &&
@@ -1350,6 +1357,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       o.p1 = w.big + 2 * D, o.ld1 = ldbig, o.bstride1 = (int64_t)L * ldbig;
       const float sc = qk8 ? att_scale / (m->q8_sgl[i] * m->k8_sgl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
+      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->grp_B, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_sgl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     {
@@ -1386,6 +1394,15 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
   return FMI_OK;
 }
 
+// the modes of a handle that have no masked attention, refused by fmi_flux_set_attention_groups and again by every evaluation while a set is installed
+int groups_mode_check(const fmi_flux* m, const std::string& who) {
+  if (m->fp8) return fail(FMI_ERR_UNSUPPORTED, who + "not supported in the " + (m->q8_kind == 2 ? "int8" : "fp8") + " mode");
+  if (m->fp8_attn == 2) return fail(FMI_ERR_UNSUPPORTED, who + "not supported with fp8 attention operands (fmi_flux_set_fp8_attention(m, 2))");
+  if (m->sp_world > 1 && m->sp_a2a) return fail(FMI_ERR_UNSUPPORTED, who + "not supported under sequence parallelism");
+  if (m->split_k) return fail(FMI_ERR_UNSUPPORTED, who + "not supported in the split-K latency mode (fmi_flux_set_split_k)");
+  return FMI_OK;
+}
+
 int check_inputs(fmi_flux* m, const fmi_flux_inputs* in) {
   if (!m || !in) return fail(FMI_ERR_INVALID, "flux: null handle or inputs");
   if (in->B <= 0 || in->S <= 0 || in->T <= 0) return fail(FMI_ERR_INVALID, "flux: B, S, T must be positive");
@@ -1413,6 +1430,15 @@ int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_opti
     if (!f32_or_bf16(ctx->ctx_dtype)) return fail(FMI_ERR_INVALID, "flux: ctx_dtype must be F32 or BF16");
     if (sp) return fail(FMI_ERR_UNSUPPORTED, "flux: a context is not supported under sequence parallelism");
     p->R = ctx->R;
+  }
+  if (m->grp_words) {  // token group masks: the set was built for one joint sequence, and only the bf16 single-device attention has a masked form
+    FMI_TRY(groups_mode_check(m, "flux: attention groups are installed (fmi_flux_set_attention_groups): "));
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: attention groups are not combined with a context (reference rows)");
+    if (o.cfg) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: attention groups are not combined with true CFG");
+    if (in->T != m->grp_T || in->S != m->grp_S)
+      return fail(FMI_ERR_INVALID, "flux: the installed attention groups are for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ", this evaluation has T = " +
+                                       std::to_string(in->T) + ", S = " + std::to_string(in->S));
+    if (m->grp_B != 1 && m->grp_B != in->B) return fail(FMI_ERR_INVALID, "flux: the installed attention groups are for a batch of " + std::to_string(m->grp_B));
   }
   if (!m->cond && o.ctl) return fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)");
   if (m->cond) {  // a channel-conditioned model needs a control at every evaluation
@@ -2167,6 +2193,42 @@ extern "C" int fmi_flux_set_attention_kernel(fmi_flux* m, int kind) {
   if (!alt_kernels_built() && kind != -1 && kind != 5 && kind != 1)
     return fail(FMI_ERR_UNSUPPORTED, "flux_set_attention_kernel: this build carries kernels 5 and 1; 0, 2, 3, 4 live in the test build (libflux_mi355x_alt.so: make alt)");
   m->attn_kind = kind;
+  return FMI_OK;
+}
+// Token group masks of the joint attention: the words [txt | img] of every sample and the key tiles' summaries, on the device, once per set.
+// A host-blocking call, like set_tensor: the device is drained before the old set goes and after the new one is complete, so any stream may read it.
+extern "C" int fmi_flux_set_attention_groups(fmi_flux* m, const uint32_t* txt_groups, int T, const uint32_t* img_groups, int S, int groups_batch) {
+  if (!m) return fail(FMI_ERR_INVALID, "flux_set_attention_groups: null handle");
+  FMI_TRY(use_device(m));
+  if (!txt_groups && !img_groups && T == 0 && S == 0 && groups_batch == 0) {  // clear
+    if (m->grp_words) FMI_HIP_TRY(hipDeviceSynchronize());
+    m->grp_words.reset();
+    m->grp_sum = nullptr, m->grp_T = m->grp_S = m->grp_B = 0;
+    return FMI_OK;
+  }
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "flux_set_attention_groups: a ControlNet handle keeps its unmasked attention");
+  if (!txt_groups || !img_groups || T < 1 || S < 1 || groups_batch < 1 || groups_batch > 8)
+    return fail(FMI_ERR_INVALID, "flux_set_attention_groups: txt_groups (groups_batch, T) and img_groups (groups_batch, S) with T, S >= 1 and groups_batch 1 .. 8 (or all zero to clear)");
+  FMI_TRY(groups_mode_check(m, "flux_set_attention_groups: "));
+  const int L = T + S;
+  std::vector<uint32_t> words((size_t)groups_batch * L);
+  for (int b = 0; b < groups_batch; ++b)
+    for (int i = 0; i < L; ++i) {
+      const uint32_t w = i < T ? txt_groups[(size_t)b * T + i] : img_groups[(size_t)b * S + (i - T)];
+      if (!w)  // the same word serves the token as query and as key: a word of 0 is a row without a visible key
+        return fail(FMI_ERR_INVALID, std::string("flux_set_attention_groups: ") + (i < T ? "text" : "image") + " token " + std::to_string(i < T ? i : i - T) + " of sample " +
+                                         std::to_string(b) + " has the group word 0: it would not see itself");
+      words[(size_t)b * L + i] = w;
+    }
+  const size_t wbytes = (words.size() * 4 + 15) / 16 * 16;
+  DeviceBuffer buf;
+  if (buf.alloc(wbytes + attention_groups_summary_bytes(groups_batch, L)) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_set_attention_groups: hipMalloc failed");
+  uint32_t* sum = reinterpret_cast<uint32_t*>(buf.as<char>() + wbytes);
+  FMI_HIP_TRY(hipMemcpy(buf.ptr, words.data(), words.size() * 4, hipMemcpyHostToDevice));
+  FMI_TRY(launch_key_tile_summary(buf.as<uint32_t>(), groups_batch, L, sum, nullptr));
+  FMI_HIP_TRY(hipDeviceSynchronize());  // the summaries are complete, and nothing in flight reads the set this one replaces
+  m->grp_words = std::move(buf);
+  m->grp_sum = sum, m->grp_T = T, m->grp_S = S, m->grp_B = groups_batch;
   return FMI_OK;
 }
 // fmi_flux_denoise's modulation precompute: 1 (default) one MFMA GEMM over all steps (when they are more than 4 rows), 0 f32 GEMV passes of 4 rows,

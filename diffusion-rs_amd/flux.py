@@ -499,6 +499,18 @@ class FluxModel:
         at every row count they are expanded once (1, 3, and -1 with the room) or per call (0, and 2 — which has no fused kernel to select there)."""
         L.check(self.lib.fmi_flux_set_quant_dense_cache(self.h, int(mode)), self.lib)
 
+    def set_attention_groups(self, txt_groups, img_groups):
+        """Token group masks for the joint attention of every block (fmi_flux_set_attention_groups): txt_groups (T,) or (Bg, T) and img_groups
+        (S,) or (Bg, S), integers that fit 32 bits, Bg 1 or the batch of the evaluations to come.  Token i sees token j iff their words share a bit; a word of 0
+        is refused.  Holds for every forward / denoise of this (T, S) until clear_attention_groups()."""
+        t, i = (np.ascontiguousarray(np.atleast_2d(np.asarray(g.cpu() if isinstance(g, torch.Tensor) else g)).astype(np.uint32)) for g in (txt_groups, img_groups))
+        if t.ndim != 2 or i.ndim != 2 or t.shape[0] != i.shape[0]:
+            raise ValueError(f"set_attention_groups: txt_groups {t.shape} and img_groups {i.shape} must be (T,) and (S,), or (Bg, T) and (Bg, S)")
+        L.check(self.lib.fmi_flux_set_attention_groups(self.h, C.c_void_p(t.ctypes.data), t.shape[1], C.c_void_p(i.ctypes.data), i.shape[1], t.shape[0]), self.lib)
+
+    def clear_attention_groups(self):
+        L.check(self.lib.fmi_flux_set_attention_groups(self.h, None, 0, None, 0, 0), self.lib)
+
     def set_split_k(self, on: bool):
         """Latency mode for launches of few rows (sequence-parallel shards): residual projections with fewer than 128 tiles are
         split along K and reduced in a fixed order, and the sequence-parallel attention of few heads walks key ranges in parallel

@@ -48,3 +48,31 @@ def sdpa_d64(q, k, v, bias=None, causal=False, scale=None):
     L.check(L.load().fmi_sdpa_d64_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Tq, Tk, strides, float(64 ** -0.5 if scale is None else scale), _ptr(bias),
                                        1 if causal else 0, _stream()))
     return out
+
+
+def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False):
+    """fmi_sdpa_groups_bf16: softmax(q k^T * scale + M) v at head dim 128 with token group masks — query i sees key j iff
+    (q_groups[i] & k_groups[j]) != 0.  q (B,H,Lq,128), k and v (B,H,Lk,128) bfloat16 device tensors; q_groups (Bg,Lq) and k_groups (Bg,Lk) integers that fit
+    32 bits (any device; (L,) is Bg = 1), Bg 1 — one set for the batch — or B.  scale: 1 / sqrt(128) by default.  Returns (B,H,Lq,128), or (B,Lq,H*128) with
+    out_token_major.  Where Lq == Lk the words are checked for self-visibility (q_groups[i] & k_groups[i]); otherwise the caller guarantees a visible key for
+    every query — a row without one is undefined."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[3] != 128 or not t.is_cuda:
+            raise TypeError(f"sdpa_groups: {name} must be a bfloat16 device tensor (B,H,L,128), got {t.dtype} {tuple(t.shape)}")
+    B, H, Lq, _ = (int(x) for x in q.shape)
+    Lk = int(k.shape[2])
+    if tuple(k.shape) != (B, H, Lk, 128) or tuple(v.shape) != tuple(k.shape) or Lq < 1 or Lk < 1:
+        raise ValueError(f"sdpa_groups: shapes q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit")
+    qg, kg = (torch.atleast_2d(torch.as_tensor(g)).to(torch.int64).bitwise_and(0xFFFFFFFF) for g in (q_groups, k_groups))
+    Bg = int(qg.shape[0])
+    if tuple(qg.shape) != (Bg, Lq) or tuple(kg.shape) != (Bg, Lk) or Bg not in (1, B):
+        raise ValueError(f"sdpa_groups: q_groups {tuple(qg.shape)} and k_groups {tuple(kg.shape)} must be (Bg,{Lq}) and (Bg,{Lk}) with Bg 1 or {B}")
+    if Lq == Lk and not bool((qg.cpu() & kg.cpu()).ne(0).all()):
+        raise ValueError("sdpa_groups: a token does not see itself ((q_groups[i] & k_groups[i]) == 0): a row without a visible key is not supported")
+    # uint32 words as int32 bit patterns on the device (torch has no uint32 arithmetic everywhere)
+    qg, kg = (g.where(g < 2 ** 31, g - 2 ** 32).to(torch.int32).to(q.device).contiguous() for g in (qg, kg))
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    out = torch.empty((B, Lq, H * 128) if out_token_major else (B, H, Lq, 128), dtype=torch.bfloat16, device=q.device)
+    L.check(L.load().fmi_sdpa_groups_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
+                                          1 if out_token_major else 0, _ptr(qg), _ptr(kg), Bg, _stream()))
+    return out

@@ -198,6 +198,42 @@ REQUEST_NAMES = dict(context="reference= (a context)", control="a control (a cha
                      fp8="supported on a transformer in the fp8 mode", int8="supported on a transformer in the int8 mode")
 
 
+REQUEST_NAMES["regions"] = "regions= (regional prompts)"
+REGIONS_MAX = 31                  # bit 0 of a group word is the base prompt's, bits 1 .. 31 the regions'
+REGIONS_MAX_TEXT_ROWS = 32 * 512  # the concatenated text rows the model is given at most: 32 prompts of T5's 512 rows
+
+
+def region_groups(masks, T: int, H: int, W: int):
+    """The group words of a request with regional prompts, a pure host function: (txt_words ((N + 1) * T,), img_words (H / 16 * W / 16,)) uint32 for
+    the text rows [base | region 1 | ... | region N], T rows each, and the image tokens in row-major order.  Base text rows carry bit 0, region r's bit r; an
+    image token (16 x 16 pixels) carries bit 0, plus bit r where the mean of mask r over its pixels is >= 0.5.  So image sees image, base text and image see each
+    other, region text r and the image tokens of region r see each other, and region texts see neither the base text nor one another."""
+    txt = np.repeat(np.uint32(1) << np.arange(len(masks) + 1, dtype=np.uint32), T)
+    img = np.ones((H // 16) * (W // 16), np.uint32)
+    for r, m in enumerate(masks, 1):
+        m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64).reshape(H // 16, 16, W // 16, 16)
+        img |= np.where(m.mean((1, 3)).reshape(-1) >= 0.5, np.uint32(1 << r), np.uint32(0))
+    return txt, img
+
+
+def check_regions_request(n_regions: int, mask_shapes, height: int, width: int, present=(), text_rows: Optional[int] = None):
+    """The regions= argument of a request, checked without a device.  ValueError by name: no region or more than 31; a height or width that is no multiple of 16;
+    a mask that is not (height, width); anything in `present` — the names of what the request also carries, none of which regions combine with: embeddings= /
+    token_ids=, a negative prompt, reference=, cache_threshold=, a control, a ControlNet, an IP-Adapter, Redux, sequence parallelism, the fp8 / int8 modes;
+    text_rows (the concatenated T, once known) beyond REGIONS_MAX_TEXT_ROWS."""
+    if not 1 <= n_regions <= REGIONS_MAX:
+        raise ValueError(f"regions= takes 1 .. {REGIONS_MAX} (prompt, mask) pairs, got {n_regions}")
+    if height % 16 or width % 16:
+        raise ValueError(f"regions= needs height and width that are multiples of 16, got {height} x {width}")
+    for r, shape in enumerate(mask_shapes, 1):
+        if tuple(shape) != (height, width):
+            raise ValueError(f"the mask of region {r} must be ({height},{width}) as params say, got {tuple(shape)}")
+    for name in present:
+        raise ValueError(f"regions= is not combined with {name}")
+    if text_rows is not None and text_rows > REGIONS_MAX_TEXT_ROWS:
+        raise ValueError(f"regions= concatenates {text_rows} text rows, the model takes at most {REGIONS_MAX_TEXT_ROWS}")
+
+
 def _rows(x, idx):
     """Rows `idx` (a slice or a list of ints) of one per-sample input: a tensor, a numpy array, a list, or a pair (tuple) of those; None stays None."""
     if x is None:
@@ -639,7 +675,7 @@ class Pipeline:
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        solver: Optional[str] = None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
+                        solver: Optional[str] = None, regions=None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                         negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -717,7 +753,16 @@ class Pipeline:
         "dpmpp_2m" (DPMSolverMultistepScheduler with use_flow_sigmas, ComfyUI's dpmpp_2m) over the request's own schedule — after a strength= cut the schedule
         starts below 1 and "dpmpp_2m" uses its history from step 1 on.  "heun" evaluates the model twice per step but the last, "dpmpp_2m" once.  Both combine
         with everything above except "heun" with cache_threshold= and either under sequence parallelism.  A capability, not a recommendation: no step count is
-        suggested for either, there are no real weights here to judge one."""
+        suggested for either, there are no real weights here to judge one.
+
+        Regional prompts (`regions=[(prompt, mask), ...]`): ONE region set per request, shared by its prompts, at most 31 regions; each mask is
+        (height, width), numpy or torch, 1 inside the region.  The T5 rows of the request's prompt and of every region prompt are concatenated, [base | r1 | ... | rN]
+        (the pooled CLIP vector is the base prompt's), before the request is chunked — its chunks are embeddings= chunks, as Redux's are — and region_groups' words
+        are installed on the transformer (FluxModel.set_attention_groups) before the first chunk and cleared when the last has run or one has raised: region text r
+        and the image tokens under mask r see each other, the base text and the image see each other, region texts see nothing else.  Combines with image= /
+        strength= / mask=, solver=, LoRA and the quantised (4-bit, GGUF, single-file) models; raises with embeddings= / token_ids=, a negative prompt, reference=,
+        cache_threshold=, a control, a ControlNet, an IP-Adapter, Redux, under sequence parallelism and on an 8-bit transformer.  No base / region weighting is
+        recommended: there are no real weights here to judge one."""
         rdx = self._redux_input(redux_image, redux_image_embeds, redux_scale)
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
                                      negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
@@ -734,6 +779,13 @@ class Pipeline:
                  "int8" if getattr(self, "_int8_pending", False) else getattr(getattr(self, "flux", None), "_eight_bit", None)}
         present = dict(context=reference, cache=cache_threshold, true_cfg=neg, control=ctl, controlnet=cn, ip_adapter=ipa)  # (a negative at a scale <= 1: neg is None)
         F.check_combination({k for k, v in present.items() if v is not None} | modes, REQUEST_NAMES)
+        words = None  # the group words of a request with regions=: installed before the first chunk, cleared behind the last
+        if regions is not None:
+            carried = dict(embeddings=embeddings, token_ids=token_ids, negative_prompt=negative_prompt, negative_embeddings=negative_embeddings,
+                           negative_token_ids=negative_token_ids, reference=reference, cache_threshold=cache_threshold)
+            embeddings, words = self._region_inputs(prompts, list(regions), params, [k + "=" for k, v in carried.items() if v is not None] +
+                                                    [REQUEST_NAMES[k] for k, v in (("control", ctl), ("controlnet", cn), ("ip_adapter", ipa), ("redux", rdx)) if v is not None] +
+                                                    [REQUEST_NAMES[m] for m in modes if m is not None])
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
         if not s.prompts:
@@ -744,11 +796,36 @@ class Pipeline:
         # a request with a solver takes the chunk body through _generate_chunk_solver; any other makes exactly the call it always made
         base = self._generate_chunk if kind is None else (lambda *a, **kw: self._generate_chunk_solver(solver, *a, **kw))
         chunk = base if rdx is None else (lambda *a, **kw: self._generate_chunk_redux(rdx, *a, **({} if kind is None else dict(chunk=base)), **kw))
-        outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
-                for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
+        try:
+            if words is not None:
+                self.flux.set_attention_groups(*words)
+            outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
+                    for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
+        finally:
+            if words is not None:
+                self.flux.clear_attention_groups()
         if len(outs) == 1:
             return outs[0]
         return (torch.cat([o[0] for o in outs], 0), torch.cat([o[1] for o in outs], 0)) if return_latents else torch.cat(outs, 0)
+
+    def _region_inputs(self, prompts, regions, params, present):
+        """((t5 (B, (N + 1) T, J), clip (B, P)), (txt_words, img_words)) of a request with regions=, checked first: the T5 rows of the prompts and of
+        the region prompts, encoded through the request's own text source, concatenated [base | r1 | ... | rN]; the pooled vector is the base prompt's."""
+        masks = [torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m for _, m in regions]
+        if not all(isinstance(m, torch.Tensor) and m.dim() == 2 for m in masks):
+            raise ValueError("every region is a (prompt, mask) pair with a 2-d numpy or torch mask")
+        check_regions_request(len(regions), [m.shape for m in masks], params.height, params.width, present)
+        if not prompts:
+            return None, None
+        with self._lock:
+            t5, clip, _ = self._chunk_embeddings(_Samples(list(prompts), list(range(len(prompts)))), None)
+            rt5 = self._chunk_embeddings(_Samples([p for p, _ in regions], list(range(len(regions)))), None)[0]
+        B, T = int(t5.shape[0]), int(t5.shape[1])
+        if int(rt5.shape[1]) != T:
+            raise ValueError(f"the region prompts encode to {int(rt5.shape[1])} text rows, the request's prompts to {T}")
+        check_regions_request(len(regions), [], params.height, params.width, text_rows=(len(regions) + 1) * T)
+        t5 = torch.cat([t5] + [rt5[r:r + 1].to(t5.dtype).expand(B, -1, -1) for r in range(len(regions))], 1)
+        return (t5, clip), region_groups(masks, T, params.height, params.width)
 
     def _control(self, control_image, control_mask, params, *_) -> Optional[_Control]:
         """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share.  (Callers from before
@@ -1229,7 +1306,7 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None,
+                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None, regions=None,
                 negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -1250,7 +1327,8 @@ class Pipeline:
         the picture itself).
         redux_image= / redux_image_embeds= / redux_scale=: FLUX.1 Redux image variation (load_redux), see generate_tensor — one picture per request, likewise
         (every rank loads the same Redux and encodes the picture itself).
-        solver=: None | "euler" | "heun" | "dpmpp_2m", the integrator of the denoise loop, see generate_tensor."""
+        solver=: None | "euler" | "heun" | "dpmpp_2m", the integrator of the denoise loop, see generate_tensor.
+        regions=: [(prompt, mask), ...], regional prompts, see generate_tensor — one region set per request, handed to every rank of a sharded batch unchanged."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -1260,7 +1338,7 @@ class Pipeline:
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
                        ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image,
-                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver)
+                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver, regions=regions)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

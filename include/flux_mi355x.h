@@ -59,6 +59,7 @@ extern "C" {
  *   Then, still 6: single-file fp8 checkpoints (OCP e4m3fn / e5m2 weights resident as codes) — fmi_f8_dequantize, fmi_flux_set_linear_f8.
  *   Then, still 6: second-order solvers in the denoise loop (Heun, DPM-Solver++ 2M) — fmi_flux_solver, fmi_flux_denoise_solver, fmi_flux_solver_bytes,
  *                  fmi_heun_predict, fmi_heun_correct, fmi_dpmpp_2m_step, fmi_dpmpp_2m_coefficients.
+ *   Then, still 6: joint attention with token group masks at d = 128 (regional prompts) — fmi_sdpa_groups_bf16, fmi_flux_set_attention_groups.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -378,6 +379,17 @@ int fmi_flux_set_attention_rescale_threshold(fmi_flux*, int thr_x16);
  * the process-wide switch.  Two handles of one process can run different kernels; the op-level fmi_sdpa_* entry points have no handle and
  * keep following the process-wide switch. */
 int fmi_flux_set_attention_kernel(fmi_flux*, int kind);
+/* PER HANDLE: token group masks for the joint attention of every double and single block (attention_groups.hip) — regional prompts.  Every
+ * token of the joint sequence [txt (T) | img (S)] carries one 32-bit group word, the same as query and as key; token i sees token j iff their words share a
+ * bit.  txt_groups (groups_batch, T) and img_groups (groups_batch, S) are HOST arrays, groups_batch 1 (one set for every sample) or the B of the evaluations
+ * to come; they are copied to the device and the key tiles' summaries are built here, once (the call waits for the device).  NULL, 0, NULL, 0, 0 clears.
+ * FMI_ERR_INVALID: a word of 0 (a token that would not see itself), T or S < 1, a groups_batch outside 1 .. 8 (the per-device batch limit of an evaluation).  While a set is installed, forward_core sends both block
+ * kinds' attention to the masked kernel, and an evaluation is refused if its (T, S) differs from the set's or its B fits no groups_batch (FMI_ERR_INVALID),
+ * and — by this call and by the evaluation, FMI_ERR_UNSUPPORTED — in the fp8 / int8 modes and with fp8 attention operands (fmi_flux_set_fp8_attention(m, 2)),
+ * under sequence parallelism, in the split-K latency mode (fmi_flux_set_split_k), with a context (reference rows) and under true CFG; a ControlNet handle
+ * refuses the call and keeps its own unmasked attention when the main model carries a set.  With no set installed every entry issues exactly the launches
+ * it always did. */
+int fmi_flux_set_attention_groups(fmi_flux*, const uint32_t* txt_groups, int T, const uint32_t* img_groups, int S, int groups_batch);
 /* The weights as flat device buffers — the unit of the multi-GPU broadcast (north star: "RCCL broadcast of
  * weights").  Rank 0 loads a checkpoint, fmi_flux_state_export() fills a small host blob saying which
  * arenas exist and how every fused matrix is stored (pass blob_host = NULL to query *len); the other ranks
@@ -1222,6 +1234,14 @@ int fmi_gemm_tile_rows(const int* M, const int* N, int nprob, int cus, int q8, i
  * == backend::ops::sdpa fallback (ops.rs:247-262) without materialising the scores. */
 int fmi_sdpa_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
                   int Lk, int d, float scale, int out_token_major, void* stream);
+/* fmi_sdpa_bf16 with token group masks (attention_groups.hip): query i sees key j iff (q_groups[i] & k_groups[j]) != 0.  The words are DEVICE
+ * arrays uint32 (groups_batch, Lq) and (groups_batch, Lk), per sample and shared by all heads, groups_batch 1 (broadcast over the batch) or B.  d != 128 is
+ * FMI_ERR_UNSUPPORTED.  The caller guarantees that every query sees at least one key: the kernel has no branch for an empty row (it divides by a row sum of 0)
+ * and such a row's output is undefined; the words live on the device, so the entry cannot check it without waiting.  Keys no query sees are never read as
+ * scores: they contribute exactly nothing, whatever finite values they hold.  The V^T image and the per-tile summaries of k_groups live in the library's
+ * per-stream block, as fmi_sdpa_bf16's image does; asynchronous on `stream`, never synchronises.  q, k 16-byte aligned. */
+int fmi_sdpa_groups_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int d, float scale, int out_token_major,
+                         const uint32_t* q_groups, const uint32_t* k_groups, int groups_batch, void* stream);
 /* The attention kernels read V transposed (B,H,128,Lk rounded up to 64) with the kv index permuted inside groups of 16; the op-level
  * entry points build that image first.  fmi_sdpa_bf16 / fmi_sdpa_fp8qk keep it in a grow-only block the library holds per (device, stream)
  * — calls on one stream run in order and share it; a call allocates only when it needs more than any earlier call on that stream (once,
