@@ -451,10 +451,13 @@ int launch_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16
 // key j iff (q_groups[i] & k_groups[j]) != 0.  Words uint32 (groups_batch, L), groups_batch 1 (shared by the batch) or B; ksum = launch_key_tile_summary of
 // k_groups (attention_groups_summary_bytes).  The caller guarantees that every query sees at least one key (else that row's output is undefined).  q, k, vt
 // 16-byte aligned.  Asynchronous, no workspace.
+// Key weights: k_lw = launch_key_weight_log2 of the positive finite f32 weights (groups_batch, Lk), given to the summaries and to the launch
+// alike; key j then counts w_j-fold in every softmax that sees it.  k_lw null: the unweighted kernel, as before.
 size_t attention_groups_summary_bytes(int groups_batch, int Lk);
-int launch_key_tile_summary(const uint32_t* k_groups, int groups_batch, int Lk, uint32_t* ksum, hipStream_t stream);
+int launch_key_weight_log2(const float* w, int64_t n, float* lw, hipStream_t stream);  // in place (lw == w) is fine
+int launch_key_tile_summary(const uint32_t* k_groups, const float* k_lw, int groups_batch, int Lk, uint32_t* ksum, hipStream_t stream);
 int launch_attention_groups(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const AttnOut& out, int B, int H, int Lq, int Lk, int Lkpad, float scale,
-                            const uint32_t* q_groups, const uint32_t* k_groups, const uint32_t* ksum, int groups_batch, hipStream_t stream);
+                            const uint32_t* q_groups, const uint32_t* k_groups, const uint32_t* ksum, const float* k_lw, int groups_batch, hipStream_t stream);
 // the attention of the T5 / CLIP text / CLIP vision layers (fmi_set_encoder_attention): 0 = encoder_common.h's lane-per-key kernel (default), 1 = attention_d64
 int encoder_attention_kind();
 void set_encoder_attention_kind(int kind);

@@ -148,6 +148,13 @@ struct fmi_flux {
   DeviceBuffer grp_words;
   uint32_t* grp_sum = nullptr;
   int grp_T = 0, grp_S = 0, grp_B = 0;
+  // key weights (fmi_flux_set_attention_key_weights) ride in the same device set: grp_words then also holds log2 of the weights (grp_B, L) at
+  // kw_lw, and the all-ones word stands where no group words are installed.  The two setters are independent: each keeps what it was given on the host
+  // (grp_host (grp_hB, L), kw_host (kw_hB, L)) and the device set is rebuilt from both, for grp_B = the larger batch.
+  float* kw_lw = nullptr;
+  std::vector<uint32_t> grp_host;
+  std::vector<float> kw_host;
+  int grp_hB = 0, kw_hB = 0;
   // 4-bit weights, large-M regime: per-layer streaming dequant into a reusable bf16 scratch
   // all denoise steps' modulation vectors (n_steps*B, n_mod) and vec (n_steps*B, D), see fmi_flux_denoise
   DeviceBuffer mod_steps, vec_steps, temb_steps, h1_steps;  // f32
@@ -1214,7 +1221,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       o.p1 = w.attn_img, o.ld1 = D, o.bstride1 = (int64_t)S * D;
       const float sc = qk8 ? att_scale / (m->q8_dbl[i] * m->k8_dbl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
-      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->grp_B, s));
+      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->kw_lw, m->grp_B, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_dbl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     if (m->two_streams && !fp8 && !sp && !m->profiling && !m->calib && !bw.proj[0].q_type && !bw.proj[1].q_type && !bw.mlp1[0].q_type && !bw.mlp1[1].q_type &&
@@ -1357,7 +1364,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       o.p1 = w.big + 2 * D, o.ld1 = ldbig, o.bstride1 = (int64_t)L * ldbig;
       const float sc = qk8 ? att_scale / (m->q8_sgl[i] * m->k8_sgl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
-      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->grp_B, s));
+      else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->kw_lw, m->grp_B, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_sgl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     {
@@ -1432,13 +1439,15 @@ int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_opti
     p->R = ctx->R;
   }
   if (m->grp_words) {  // token group masks: the set was built for one joint sequence, and only the bf16 single-device attention has a masked form
-    FMI_TRY(groups_mode_check(m, "flux: attention groups are installed (fmi_flux_set_attention_groups): "));
-    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: attention groups are not combined with a context (reference rows)");
-    if (o.cfg) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: attention groups are not combined with true CFG");
+    if (m->grp_host.empty()) FMI_TRY(groups_mode_check(m, "flux: attention key weights are installed (fmi_flux_set_attention_key_weights): "));
+    else FMI_TRY(groups_mode_check(m, "flux: attention groups are installed (fmi_flux_set_attention_groups): "));
+    const std::string what = m->grp_host.empty() ? "attention key weights" : m->kw_host.empty() ? "attention groups" : "attention groups and key weights";
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: " + what + " are not combined with a context (reference rows)");
+    if (o.cfg) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: " + what + " are not combined with true CFG");
     if (in->T != m->grp_T || in->S != m->grp_S)
-      return fail(FMI_ERR_INVALID, "flux: the installed attention groups are for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ", this evaluation has T = " +
+      return fail(FMI_ERR_INVALID, "flux: the installed " + what + " are for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ", this evaluation has T = " +
                                        std::to_string(in->T) + ", S = " + std::to_string(in->S));
-    if (m->grp_B != 1 && m->grp_B != in->B) return fail(FMI_ERR_INVALID, "flux: the installed attention groups are for a batch of " + std::to_string(m->grp_B));
+    if (m->grp_B != 1 && m->grp_B != in->B) return fail(FMI_ERR_INVALID, "flux: the installed " + what + " are for a batch of " + std::to_string(m->grp_B));
   }
   if (!m->cond && o.ctl) return fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)");
   if (m->cond) {  // a channel-conditioned model needs a control at every evaluation
@@ -2195,21 +2204,56 @@ extern "C" int fmi_flux_set_attention_kernel(fmi_flux* m, int kind) {
   m->attn_kind = kind;
   return FMI_OK;
 }
-// Token group masks of the joint attention: the words [txt | img] of every sample and the key tiles' summaries, on the device, once per set.
-// A host-blocking call, like set_tensor: the device is drained before the old set goes and after the new one is complete, so any stream may read it.
+// Token group masks and key weights of the joint attention.  The device set — words (nb, L), with weights their log2 (nb, L), the key
+// tiles' summaries — is built here from what the two setters hold on the host, once per change; nb is the larger of the two batches and a set of 1 is repeated.
+// Without words the all-ones word stands in; without either the set goes.  Host-blocking, like set_tensor: the device is drained before the old set goes and
+// after the new one is complete, so any stream may read it.  Nothing of the handle changes unless all of it succeeded.
+static int rebuild_attention_set(fmi_flux* m, std::vector<uint32_t> words, int gB, std::vector<float> wts, int wB, int T, int S, const std::string& who) {
+  if (words.empty() && wts.empty()) {
+    if (m->grp_words) FMI_HIP_TRY(hipDeviceSynchronize());
+    m->grp_words.reset();
+    m->grp_sum = nullptr, m->kw_lw = nullptr, m->grp_T = m->grp_S = m->grp_B = m->grp_hB = m->kw_hB = 0;
+    m->grp_host.clear(), m->kw_host.clear();
+    return FMI_OK;
+  }
+  const int L = T + S, nb = std::max(gB, wB);
+  if (gB > 1 && wB > 1 && gB != wB)
+    return fail(FMI_ERR_INVALID, who + "the installed attention groups and key weights are for batches of " + std::to_string(gB) + " and " + std::to_string(wB));
+  std::vector<uint32_t> dw((size_t)nb * L, 1u);
+  std::vector<float> dl(wts.empty() ? 0 : (size_t)nb * L);
+  for (int b = 0; b < nb; ++b) {
+    if (!words.empty()) std::copy_n(words.begin() + (size_t)(gB == 1 ? 0 : b) * L, L, dw.begin() + (size_t)b * L);
+    if (!wts.empty()) std::copy_n(wts.begin() + (size_t)(wB == 1 ? 0 : b) * L, L, dl.begin() + (size_t)b * L);
+  }
+  const size_t wbytes = (dw.size() * 4 + 15) / 16 * 16, lbytes = (dl.size() * 4 + 15) / 16 * 16;
+  DeviceBuffer buf;
+  if (buf.alloc(wbytes + lbytes + attention_groups_summary_bytes(nb, L)) != hipSuccess) return fail(FMI_ERR_NOMEM, who + "hipMalloc failed");
+  float* lw = dl.empty() ? nullptr : reinterpret_cast<float*>(buf.as<char>() + wbytes);
+  uint32_t* sum = reinterpret_cast<uint32_t*>(buf.as<char>() + wbytes + lbytes);
+  FMI_HIP_TRY(hipMemcpy(buf.ptr, dw.data(), dw.size() * 4, hipMemcpyHostToDevice));
+  if (lw) {
+    FMI_HIP_TRY(hipMemcpy(lw, dl.data(), dl.size() * 4, hipMemcpyHostToDevice));
+    FMI_TRY(launch_key_weight_log2(lw, (int64_t)dl.size(), lw, nullptr));
+  }
+  FMI_TRY(launch_key_tile_summary(buf.as<uint32_t>(), lw, nb, L, sum, nullptr));
+  FMI_HIP_TRY(hipDeviceSynchronize());  // the summaries are complete, and nothing in flight reads the set this one replaces
+  m->grp_words = std::move(buf);
+  m->grp_sum = sum, m->kw_lw = lw, m->grp_T = T, m->grp_S = S, m->grp_B = nb;
+  m->grp_host = std::move(words), m->grp_hB = gB, m->kw_host = std::move(wts), m->kw_hB = wB;
+  return FMI_OK;
+}
 extern "C" int fmi_flux_set_attention_groups(fmi_flux* m, const uint32_t* txt_groups, int T, const uint32_t* img_groups, int S, int groups_batch) {
   if (!m) return fail(FMI_ERR_INVALID, "flux_set_attention_groups: null handle");
   FMI_TRY(use_device(m));
-  if (!txt_groups && !img_groups && T == 0 && S == 0 && groups_batch == 0) {  // clear
-    if (m->grp_words) FMI_HIP_TRY(hipDeviceSynchronize());
-    m->grp_words.reset();
-    m->grp_sum = nullptr, m->grp_T = m->grp_S = m->grp_B = 0;
-    return FMI_OK;
-  }
+  const std::string who = "flux_set_attention_groups: ";
+  if (!txt_groups && !img_groups && T == 0 && S == 0 && groups_batch == 0)  // clear: installed key weights stay, over the all-ones word
+    return rebuild_attention_set(m, {}, 0, m->kw_host, m->kw_hB, m->grp_T, m->grp_S, who);
   if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, "flux_set_attention_groups: a ControlNet handle keeps its unmasked attention");
   if (!txt_groups || !img_groups || T < 1 || S < 1 || groups_batch < 1 || groups_batch > 8)
     return fail(FMI_ERR_INVALID, "flux_set_attention_groups: txt_groups (groups_batch, T) and img_groups (groups_batch, S) with T, S >= 1 and groups_batch 1 .. 8 (or all zero to clear)");
-  FMI_TRY(groups_mode_check(m, "flux_set_attention_groups: "));
+  FMI_TRY(groups_mode_check(m, who));
+  if (!m->kw_host.empty() && (T != m->grp_T || S != m->grp_S))
+    return fail(FMI_ERR_INVALID, who + "key weights are installed for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ": clear them first");
   const int L = T + S;
   std::vector<uint32_t> words((size_t)groups_batch * L);
   for (int b = 0; b < groups_batch; ++b)
@@ -2220,16 +2264,33 @@ extern "C" int fmi_flux_set_attention_groups(fmi_flux* m, const uint32_t* txt_gr
                                          std::to_string(b) + " has the group word 0: it would not see itself");
       words[(size_t)b * L + i] = w;
     }
-  const size_t wbytes = (words.size() * 4 + 15) / 16 * 16;
-  DeviceBuffer buf;
-  if (buf.alloc(wbytes + attention_groups_summary_bytes(groups_batch, L)) != hipSuccess) return fail(FMI_ERR_NOMEM, "flux_set_attention_groups: hipMalloc failed");
-  uint32_t* sum = reinterpret_cast<uint32_t*>(buf.as<char>() + wbytes);
-  FMI_HIP_TRY(hipMemcpy(buf.ptr, words.data(), words.size() * 4, hipMemcpyHostToDevice));
-  FMI_TRY(launch_key_tile_summary(buf.as<uint32_t>(), groups_batch, L, sum, nullptr));
-  FMI_HIP_TRY(hipDeviceSynchronize());  // the summaries are complete, and nothing in flight reads the set this one replaces
-  m->grp_words = std::move(buf);
-  m->grp_sum = sum, m->grp_T = T, m->grp_S = S, m->grp_B = groups_batch;
-  return FMI_OK;
+  return rebuild_attention_set(m, std::move(words), groups_batch, m->kw_host, m->kw_hB, T, S, who);
+}
+// Key weights of the joint attention: host f32 [txt | img] of every sample, each finite and > 0; key j counts w_j-fold in every softmax that
+// sees it.  Independent of the group words: either setter leaves what the other installed.
+extern "C" int fmi_flux_set_attention_key_weights(fmi_flux* m, const float* txt_weights, const float* img_weights, int T, int S, int batch) {
+  if (!m) return fail(FMI_ERR_INVALID, "flux_set_attention_key_weights: null handle");
+  FMI_TRY(use_device(m));
+  const std::string who = "flux_set_attention_key_weights: ";
+  if (!txt_weights && !img_weights && T == 0 && S == 0 && batch == 0)  // clear: installed group words stay
+    return rebuild_attention_set(m, m->grp_host, m->grp_hB, {}, 0, m->grp_T, m->grp_S, who);
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, who + "a ControlNet handle keeps its unweighted attention");
+  if (!txt_weights || !img_weights || T < 1 || S < 1 || batch < 1 || batch > 8)
+    return fail(FMI_ERR_INVALID, who + "txt_weights (batch, T) and img_weights (batch, S) with T, S >= 1 and batch 1 .. 8 (or all zero to clear)");
+  FMI_TRY(groups_mode_check(m, who));
+  if (!m->grp_host.empty() && (T != m->grp_T || S != m->grp_S))
+    return fail(FMI_ERR_INVALID, who + "attention groups are installed for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ": clear them first");
+  const int L = T + S;
+  std::vector<float> wts((size_t)batch * L);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < L; ++i) {
+      const float w = i < T ? txt_weights[(size_t)b * T + i] : img_weights[(size_t)b * S + (i - T)];
+      if (!std::isfinite(w) || !(w > 0.f))  // a weight of 0 is not a way to hide a key: that is the group words' job
+        return fail(FMI_ERR_INVALID, who + "the weight of " + (i < T ? "text" : "image") + " token " + std::to_string(i < T ? i : i - T) + " of sample " + std::to_string(b) +
+                                         " is " + std::to_string(w) + ": weights are finite and > 0");
+      wts[(size_t)b * L + i] = w;
+    }
+  return rebuild_attention_set(m, m->grp_host, m->grp_hB, std::move(wts), batch, T, S, who);
 }
 // fmi_flux_denoise's modulation precompute: 1 (default) one MFMA GEMM over all steps (when they are more than 4 rows), 0 f32 GEMV passes of 4 rows,
 // 2 the GEMM at any row count (how a 2-step full-size run is compared with the oracle THROUGH the 6.5 GB one-GEMM path)

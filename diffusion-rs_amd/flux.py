@@ -511,6 +511,20 @@ class FluxModel:
     def clear_attention_groups(self):
         L.check(self.lib.fmi_flux_set_attention_groups(self.h, None, 0, None, 0, 0), self.lib)
 
+    def set_attention_key_weights(self, txt_weights, img_weights):
+        """Key weights for the joint attention of every block (fmi_flux_set_attention_key_weights): txt_weights (T,) or (Bw, T) and img_weights
+        (S,) or (Bw, S), floats that are finite and > 0, Bw 1 or the batch of the evaluations to come.  Key j counts w_j-fold in every softmax that sees it
+        (softmax(s + ln w)); 1 is the plain attention.  Independent of set_attention_groups — with both, the weights act inside what the words let a query
+        see.  Holds for every forward / denoise of this (T, S) until clear_attention_key_weights()."""
+        t, i = (np.ascontiguousarray(np.atleast_2d(np.asarray(w.detach().cpu().float() if isinstance(w, torch.Tensor) else w)).astype(np.float32))
+                for w in (txt_weights, img_weights))
+        if t.ndim != 2 or i.ndim != 2 or t.shape[0] != i.shape[0]:
+            raise ValueError(f"set_attention_key_weights: txt_weights {t.shape} and img_weights {i.shape} must be (T,) and (S,), or (Bw, T) and (Bw, S)")
+        L.check(self.lib.fmi_flux_set_attention_key_weights(self.h, C.c_void_p(t.ctypes.data), C.c_void_p(i.ctypes.data), t.shape[1], i.shape[1], t.shape[0]), self.lib)
+
+    def clear_attention_key_weights(self):
+        L.check(self.lib.fmi_flux_set_attention_key_weights(self.h, None, None, 0, 0, 0), self.lib)
+
     def set_split_k(self, on: bool):
         """Latency mode for launches of few rows (sequence-parallel shards): residual projections with fewer than 128 tiles are
         split along K and reduced in a fixed order, and the sequence-parallel attention of few heads walks key ranges in parallel

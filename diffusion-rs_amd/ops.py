@@ -50,12 +50,14 @@ def sdpa_d64(q, k, v, bias=None, causal=False, scale=None):
     return out
 
 
-def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False):
+def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False, k_weights=None):
     """fmi_sdpa_groups_bf16: softmax(q k^T * scale + M) v at head dim 128 with token group masks — query i sees key j iff
     (q_groups[i] & k_groups[j]) != 0.  q (B,H,Lq,128), k and v (B,H,Lk,128) bfloat16 device tensors; q_groups (Bg,Lq) and k_groups (Bg,Lk) integers that fit
     32 bits (any device; (L,) is Bg = 1), Bg 1 — one set for the batch — or B.  scale: 1 / sqrt(128) by default.  Returns (B,H,Lq,128), or (B,Lq,H*128) with
     out_token_major.  Where Lq == Lk the words are checked for self-visibility (q_groups[i] & k_groups[i]); otherwise the caller guarantees a visible key for
-    every query — a row without one is undefined."""
+    every query — a row without one is undefined.
+    k_weights (fmi_sdpa_groups_weighted_bf16): None — the call above —, or one float weight per key, (Bg,Lk) or (Lk,) for Bg = 1, finite and
+    > 0: key j counts w_j-fold in every softmax that sees it, softmax(s + ln w).  Host data is checked here; a device tensor is taken as it is (no wait)."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[3] != 128 or not t.is_cuda:
             raise TypeError(f"sdpa_groups: {name} must be a bfloat16 device tensor (B,H,L,128), got {t.dtype} {tuple(t.shape)}")
@@ -73,6 +75,16 @@ def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False):
     qg, kg = (g.where(g < 2 ** 31, g - 2 ** 32).to(torch.int32).to(q.device).contiguous() for g in (qg, kg))
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     out = torch.empty((B, Lq, H * 128) if out_token_major else (B, H, Lq, 128), dtype=torch.bfloat16, device=q.device)
-    L.check(L.load().fmi_sdpa_groups_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
-                                          1 if out_token_major else 0, _ptr(qg), _ptr(kg), Bg, _stream()))
+    if k_weights is None:
+        L.check(L.load().fmi_sdpa_groups_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
+                                              1 if out_token_major else 0, _ptr(qg), _ptr(kg), Bg, _stream()))
+        return out
+    kw = torch.atleast_2d(torch.as_tensor(k_weights)).to(torch.float32)
+    if tuple(kw.shape) != (Bg, Lk):
+        raise ValueError(f"sdpa_groups: k_weights {tuple(kw.shape)} must be ({Bg},{Lk}), one weight per key and per sample of the groups")
+    if not kw.is_cuda and not bool((torch.isfinite(kw) & (kw > 0)).all()):
+        raise ValueError("sdpa_groups: k_weights must be finite and > 0 (a weight of 0 is not a way to hide a key: that is the group words' job)")
+    kw = kw.to(q.device).contiguous()
+    L.check(L.load().fmi_sdpa_groups_weighted_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
+                                                   1 if out_token_major else 0, _ptr(qg), _ptr(kg), _ptr(kw), Bg, _stream()))
     return out

@@ -234,6 +234,53 @@ def check_regions_request(n_regions: int, mask_shapes, height: int, width: int, 
         raise ValueError(f"regions= concatenates {text_rows} text rows, the model takes at most {REGIONS_MAX_TEXT_ROWS}")
 
 
+REQUEST_NAMES["key_weights"] = "key_weights= (attention key weights)"
+KEY_WEIGHT_NAMES = ("prompt", "redux", "image")
+
+
+def check_key_weights_request(key_weights, height: int, width: int, present=(), text_rows: Optional[int] = None, prompt_rows: Optional[int] = None, redux_rows: int = 0):
+    """The key_weights= argument of a request, checked without a device.  ValueError by name: not a dict, or an entry other than prompt / redux /
+    image; a height or width that is no multiple of 16; a weight that is not finite or not > 0 (0 is not a way to hide a key: that is regions=' job); an image
+    entry that is not (height / 16, width / 16); a redux entry on a request without Redux rows, or neither a scalar nor (redux_rows,); anything in `present` — what
+    the request also carries and weights do not combine with: reference=, true CFG, sequence parallelism, the fp8 / int8 modes ("option" names an option,
+    "mode" a mode of the transformer); and once the text rows are known, a prompt entry that is neither (prompt_rows,) — one prompt's T5 rows — nor
+    (text_rows,) — all of them, the region prompts' included."""
+    name = REQUEST_NAMES["key_weights"]
+    if not isinstance(key_weights, dict) or set(key_weights) - set(KEY_WEIGHT_NAMES):
+        raise ValueError(f"{name} takes a dict with the entries {', '.join(KEY_WEIGHT_NAMES)} (each optional), got {sorted(key_weights) if isinstance(key_weights, dict) else type(key_weights).__name__}")
+    if height % 16 or width % 16:
+        raise ValueError(f"{name} needs height and width that are multiples of 16, got {height} x {width}")
+    rows = {k: np.asarray(v.detach().cpu().float() if isinstance(v, torch.Tensor) else v, dtype=np.float64) for k, v in key_weights.items() if v is not None}
+    for k, w in rows.items():
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError(f"{name}: the {k} weights must be finite and > 0 (a weight of 0 is not a way to hide a key: that is what regions= is for)")
+    if "image" in rows and rows["image"].shape != (height // 16, width // 16):
+        raise ValueError(f"{name}: the image weights must be ({height // 16},{width // 16}), one per packed image token, got {rows['image'].shape}")
+    if "redux" in rows and (redux_rows == 0 or rows["redux"].shape not in ((), (redux_rows,))):
+        raise ValueError(f"{name}: the redux weights need a request with Redux and are a scalar or ({redux_rows},), got {rows['redux'].shape}" if redux_rows else
+                         f"{name}: redux weights on a request without {REQUEST_NAMES['redux']}")
+    for kind, what in present:
+        raise ValueError(f"{name} is not {'combined with ' if kind == 'option' else ''}{what}")
+    if text_rows is not None and "prompt" in rows and rows["prompt"].shape not in ((prompt_rows,), (text_rows,)):
+        raise ValueError(f"{name}: the prompt weights must be ({prompt_rows},)" + (f" or ({text_rows},), the region prompts' rows included" if text_rows != prompt_rows else "") +
+                         f", got {rows['prompt'].shape}")
+
+
+def key_weight_rows(key_weights, text_rows: int, height: int, width: int, redux_rows: int = 0):
+    """The weights of a checked key_weights= request as the model takes them, a pure host function: (txt (text_rows + redux_rows,), img (height / 16 * width / 16,))
+    float32 for the text rows [T5 rows | Redux rows] and the image tokens in row-major order.  Whatever the dict does not name has the weight 1: the T5 rows
+    behind a prompt entry that covers one prompt only (the region prompts'), the Redux rows without a redux entry, the image."""
+    txt, img = np.ones(text_rows + redux_rows, np.float32), np.ones((height // 16) * (width // 16), np.float32)
+    get = lambda k: None if key_weights.get(k) is None else np.asarray(key_weights[k].detach().cpu().float() if isinstance(key_weights[k], torch.Tensor) else key_weights[k], np.float32)
+    if get("prompt") is not None:
+        txt[:get("prompt").shape[0]] = get("prompt")
+    if get("redux") is not None:
+        txt[text_rows:] = get("redux")
+    if get("image") is not None:
+        img[:] = get("image").reshape(-1)
+    return txt, img
+
+
 def _rows(x, idx):
     """Rows `idx` (a slice or a list of ints) of one per-sample input: a tensor, a numpy array, a list, or a pair (tuple) of those; None stays None."""
     if x is None:
@@ -675,7 +722,7 @@ class Pipeline:
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        solver: Optional[str] = None, regions=None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
+                        solver: Optional[str] = None, regions=None, key_weights=None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                         negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -762,7 +809,17 @@ class Pipeline:
         and the image tokens under mask r see each other, the base text and the image see each other, region texts see nothing else.  Combines with image= /
         strength= / mask=, solver=, LoRA and the quantised (4-bit, GGUF, single-file) models; raises with embeddings= / token_ids=, a negative prompt, reference=,
         cache_threshold=, a control, a ControlNet, an IP-Adapter, Redux, under sequence parallelism and on an 8-bit transformer.  No base / region weighting is
-        recommended: there are no real weights here to judge one."""
+        recommended: there are no real weights here to judge one.
+
+        Key weights (`key_weights=dict(prompt=, redux=, image=)`): how much the keys of the joint attention count, in every block — key j enters
+        every softmax that sees it w_j-fold (softmax(s + ln w)); every entry is optional, every weight finite and > 0, what is not named has 1.  `prompt` is (T,)
+        over the T5 rows (prompt emphasis; with regions= also ((N + 1) T,), the region prompts' rows included), `redux` a scalar or (729,) over the Redux rows of a
+        request with Redux (its strength as attention received, where redux_scale changes what the tokens say), `image` (height / 16, width / 16) over the packed
+        image tokens.  ONE set per request, shared by its prompts: the prompts are encoded before the request is chunked, so that every chunk has one T, the
+        weights are installed on the transformer (FluxModel.set_attention_key_weights) before the first chunk and cleared when the last has run or one has raised.
+        Combines with regions= (the weights act inside what the regions let a token see), Redux, image= / strength= / mask=, solver=, the step cache, a control, a
+        ControlNet, an IP-Adapter (whose own attention is not weighted) and the quantised models; raises with reference=, true CFG, under sequence parallelism and
+        on an 8-bit transformer.  No weight is recommended: there are no real weights here to judge one."""
         rdx = self._redux_input(redux_image, redux_image_embeds, redux_scale)
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
                                      negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
@@ -786,6 +843,12 @@ class Pipeline:
             embeddings, words = self._region_inputs(prompts, list(regions), params, [k + "=" for k, v in carried.items() if v is not None] +
                                                     [REQUEST_NAMES[k] for k, v in (("control", ctl), ("controlnet", cn), ("ip_adapter", ipa), ("redux", rdx)) if v is not None] +
                                                     [REQUEST_NAMES[m] for m in modes if m is not None])
+        weights = None  # the key weights of a request with key_weights=, threaded as the words are
+        if key_weights is not None:
+            embeddings, token_ids, weights = self._key_weight_inputs(prompts, key_weights, params, embeddings, token_ids, 0 if rdx is None else int(rdx.tokens.shape[1]),
+                                                                     0 if regions is None else len(regions),
+                                                                     [("option", REQUEST_NAMES[k]) for k, v in (("context", reference), ("true_cfg", neg)) if v is not None] +
+                                                                     [("mode", REQUEST_NAMES[m]) for m in modes if m is not None])
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
         if not s.prompts:
@@ -799,9 +862,13 @@ class Pipeline:
         try:
             if words is not None:
                 self.flux.set_attention_groups(*words)
+            if weights is not None:
+                self.flux.set_attention_key_weights(*weights)
             outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
                     for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         finally:
+            if weights is not None:
+                self.flux.clear_attention_key_weights()
             if words is not None:
                 self.flux.clear_attention_groups()
         if len(outs) == 1:
@@ -826,6 +893,20 @@ class Pipeline:
         check_regions_request(len(regions), [], params.height, params.width, text_rows=(len(regions) + 1) * T)
         t5 = torch.cat([t5] + [rt5[r:r + 1].to(t5.dtype).expand(B, -1, -1) for r in range(len(regions))], 1)
         return (t5, clip), region_groups(masks, T, params.height, params.width)
+
+    def _key_weight_inputs(self, prompts, key_weights, params, embeddings, token_ids, redux_rows, n_regions, present):
+        """(embeddings, token_ids, (txt_weights, img_weights)) of a request with key_weights=, checked first.  The weights are for ONE count of text
+        rows, so a request that came as text or token ids is encoded here, once, through its own text source, and goes on as the embeddings= request it now is
+        (one with regions= already is one)."""
+        check_key_weights_request(key_weights, params.height, params.width, present, redux_rows=redux_rows)
+        if not prompts:
+            return embeddings, token_ids, None
+        if embeddings is None:
+            with self._lock:
+                embeddings = self._chunk_embeddings(_Samples(list(prompts), list(range(len(prompts))), token_ids=token_ids), None)[:2]
+        T = int(embeddings[0].shape[-2])
+        check_key_weights_request(key_weights, params.height, params.width, text_rows=T, prompt_rows=T // (n_regions + 1), redux_rows=redux_rows)
+        return embeddings, None, key_weight_rows(key_weights, T, params.height, params.width, redux_rows)
 
     def _control(self, control_image, control_mask, params, *_) -> Optional[_Control]:
         """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share.  (Callers from before
@@ -1306,7 +1387,7 @@ class Pipeline:
             self._sp = None
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
-                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None, regions=None,
+                reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None, regions=None, key_weights=None,
                 negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -1328,7 +1409,8 @@ class Pipeline:
         redux_image= / redux_image_embeds= / redux_scale=: FLUX.1 Redux image variation (load_redux), see generate_tensor — one picture per request, likewise
         (every rank loads the same Redux and encodes the picture itself).
         solver=: None | "euler" | "heun" | "dpmpp_2m", the integrator of the denoise loop, see generate_tensor.
-        regions=: [(prompt, mask), ...], regional prompts, see generate_tensor — one region set per request, handed to every rank of a sharded batch unchanged."""
+        regions=: [(prompt, mask), ...], regional prompts, see generate_tensor — one region set per request, handed to every rank of a sharded batch unchanged.
+        key_weights=: dict(prompt=, redux=, image=), attention key weights, see generate_tensor — one set per request, handed to every rank likewise."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -1338,7 +1420,7 @@ class Pipeline:
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
                        ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image,
-                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver, regions=regions)
+                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver, regions=regions, key_weights=key_weights)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

@@ -60,6 +60,7 @@ extern "C" {
  *   Then, still 6: second-order solvers in the denoise loop (Heun, DPM-Solver++ 2M) — fmi_flux_solver, fmi_flux_denoise_solver, fmi_flux_solver_bytes,
  *                  fmi_heun_predict, fmi_heun_correct, fmi_dpmpp_2m_step, fmi_dpmpp_2m_coefficients.
  *   Then, still 6: joint attention with token group masks at d = 128 (regional prompts) — fmi_sdpa_groups_bf16, fmi_flux_set_attention_groups.
+ *   Then, still 6: per-key weights in that attention (weighted prompts, Redux strength) — fmi_sdpa_groups_weighted_bf16, fmi_flux_set_attention_key_weights.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -390,6 +391,17 @@ int fmi_flux_set_attention_kernel(fmi_flux*, int kind);
  * refuses the call and keeps its own unmasked attention when the main model carries a set.  With no set installed every entry issues exactly the launches
  * it always did. */
 int fmi_flux_set_attention_groups(fmi_flux*, const uint32_t* txt_groups, int T, const uint32_t* img_groups, int S, int groups_batch);
+/* PER HANDLE: key weights for the joint attention of every double and single block — prompt emphasis, Redux strength, soft regions.  Every
+ * token of the joint sequence [txt (T) | img (S)] carries one f32 weight w > 0 as a KEY: O_i = sum_j w_j e^(s_ij) v_j / sum_j w_j e^(s_ij) over the keys query i
+ * sees, which is softmax(s + ln w); 1 is the plain attention.  txt_weights (batch, T) and img_weights (batch, S) are HOST arrays, batch 1 (one set for every
+ * sample) or the B of the evaluations to come; log2 of them and the key tiles' summaries are built on the device here, once (the call waits for the device).
+ * NULL, NULL, 0, 0, 0 clears.  Independent of fmi_flux_set_attention_groups: either call leaves what the other installed; with no group words every token sees
+ * every token, with both the weights act inside what the words let a query see, and the two must agree in (T, S) and, where both are above 1, in batch
+ * (FMI_ERR_INVALID).  FMI_ERR_INVALID, and nothing is installed or removed: a weight that is not finite or not > 0 (0 is not a way to hide a key: that is the
+ * group words' job), T or S < 1, a batch outside 1 .. 8.  Refused like the group words (FMI_ERR_UNSUPPORTED, by this call and by an evaluation while weights
+ * are installed): a ControlNet handle, the fp8 / int8 modes, fp8 attention operands, sequence parallelism, the split-K latency mode, a context, true CFG; an
+ * evaluation of another (T, S) is FMI_ERR_INVALID.  With nothing installed every entry issues exactly the launches it always did. */
+int fmi_flux_set_attention_key_weights(fmi_flux*, const float* txt_weights, const float* img_weights, int T, int S, int batch);
 /* The weights as flat device buffers — the unit of the multi-GPU broadcast (north star: "RCCL broadcast of
  * weights").  Rank 0 loads a checkpoint, fmi_flux_state_export() fills a small host blob saying which
  * arenas exist and how every fused matrix is stored (pass blob_host = NULL to query *len); the other ranks
@@ -1242,6 +1254,13 @@ int fmi_sdpa_bf16(const void* q, const void* k, const void* v, void* o, int B, i
  * per-stream block, as fmi_sdpa_bf16's image does; asynchronous on `stream`, never synchronises.  q, k 16-byte aligned. */
 int fmi_sdpa_groups_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int d, float scale, int out_token_major,
                          const uint32_t* q_groups, const uint32_t* k_groups, int groups_batch, void* stream);
+/* fmi_sdpa_groups_bf16 with per-key weights: O_i = sum_j w_j e^(s_ij) v_j / sum_j w_j e^(s_ij) over the keys j query i sees, s = scale q.k.
+ * k_weights is a DEVICE array f32 (groups_batch, Lk), shared by all heads and queries; every entry must be finite and > 0 (not checked: the entry never
+ * waits for the device; a 0, a negative or a NaN makes the rows that see that key undefined).  k_weights == NULL is exactly fmi_sdpa_groups_bf16, the
+ * unweighted call.  Weights that are all 1 give its output bit for bit; scaling every weight by one power of two changes no output bit.  log2 of the weights
+ * is built per call behind the summaries in the per-stream block; asynchronous on `stream`. */
+int fmi_sdpa_groups_weighted_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int d, float scale, int out_token_major,
+                                  const uint32_t* q_groups, const uint32_t* k_groups, const float* k_weights, int groups_batch, void* stream);
 /* The attention kernels read V transposed (B,H,128,Lk rounded up to 64) with the kv index permuted inside groups of 16; the op-level
  * entry points build that image first.  fmi_sdpa_bf16 / fmi_sdpa_fp8qk keep it in a grow-only block the library holds per (device, stream)
  * — calls on one stream run in order and share it; a call allocates only when it needs more than any earlier call on that stream (once,
