@@ -10,6 +10,6 @@ from .text import (CLIP_L, CLIP_VISION_L, SIGLIP_SO400M, T5_XXL, ClipTextTransfo
                    load_bpe_tokenizer, tokenize_and_pad)
 from . import synth  # noqa: F401
 from . import ops  # noqa: F401
-from .ops import sdpa_d64, sdpa_groups, set_encoder_attention, get_encoder_attention  # noqa: F401
+from .ops import sdpa_d64, sdpa_d512, sdpa_groups, set_encoder_attention, get_encoder_attention  # noqa: F401
 from . import lora  # noqa: F401
 from .lora import AdapterTerm, read_adapter, read_lora  # noqa: F401

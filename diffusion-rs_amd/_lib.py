@@ -373,6 +373,9 @@ def _declare(lib):
     lib.fmi_flux_set_attention_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
     lib.fmi_sdpa_groups_weighted_bf16.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.fmi_flux_set_attention_key_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.fmi_sdpa_d512_bf16.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.POINTER(C.c_int64), C.c_float, C.c_void_p]
+    lib.fmi_vae_set_mid_attention.argtypes = [C.c_void_p, C.c_int]
+    lib.fmi_vae_get_mid_attention.argtypes = [C.c_void_p]
     lib.fmi_set_encoder_attention.argtypes = [C.c_int]
     lib.fmi_get_encoder_attention.argtypes = []
     lib.fmi_linear_q8_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -434,7 +437,7 @@ EXPORTED = [
     "fmi_flux_denoise_solver", "fmi_flux_solver_bytes", "fmi_heun_predict", "fmi_heun_correct", "fmi_dpmpp_2m_step", "fmi_dpmpp_2m_coefficients",
     "fmi_flux_set_profiling", "fmi_flux_set_fused_qkv_relayout", "fmi_flux_phase_count", "fmi_flux_phase_name", "fmi_flux_phase_ms",
     "fmi_vae_default_config", "fmi_vae_create", "fmi_vae_destroy", "fmi_vae_set_tensor", "fmi_vae_missing_count", "fmi_vae_missing_name",
-    "fmi_vae_scale_factor", "fmi_vae_shift_factor", "fmi_vae_decode", "fmi_vae_encode", "fmi_vae_mid_attention",
+    "fmi_vae_scale_factor", "fmi_vae_shift_factor", "fmi_vae_decode", "fmi_vae_encode", "fmi_vae_mid_attention", "fmi_vae_set_mid_attention", "fmi_vae_get_mid_attention", "fmi_sdpa_d512_bf16",
     "fmi_t5_default_config", "fmi_t5_create", "fmi_t5_destroy", "fmi_t5_set_tensor", "fmi_t5_set_linear_bnb4", "fmi_t5_set_linear_int8", "fmi_t5_missing_count", "fmi_t5_missing_name",
     "fmi_t5_size_in_bytes", "fmi_t5_forward", "fmi_clip_default_config", "fmi_clip_create", "fmi_clip_destroy", "fmi_clip_set_tensor",
     "fmi_clip_missing_count", "fmi_clip_missing_name", "fmi_clip_size_in_bytes", "fmi_clip_forward",

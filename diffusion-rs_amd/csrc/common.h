@@ -447,6 +447,11 @@ int launch_sp_merge_splits(const bf16_t* parts, const float* lse, int S, bf16_t*
 // take the LDS-DMA form of the kernel, others its 2-byte-load form.
 int launch_attention_d64(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int H, int Tq, int Tk, const int64_t* sq, const int64_t* sk,
                          const int64_t* sv, const int64_t* so, float scale, const float* bias, int causal, hipStream_t stream);
+// flash attention, one head of width 512 (attention_d512.hip): q (B, Lq, 512), k, v (B, Lk, 512), out (B, Lq, 512) bf16 token-major; st = the
+// element strides {row, batch} of q, k, v, out (rows multiples of 8 and >= 512).  Any Lq, Lk >= 1; B == 0 or Lq == 0: nothing to do.  16-byte aligned operands.
+// No workspace, asynchronous, deterministic.
+int launch_attention_d512(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* out, int B, int Lq, int Lk, const int64_t* st, float scale,
+                          hipStream_t stream);
 // flash attention, d = 128, with token group masks (attention_groups.hip): operands and output as launch_attention_ex's bf16 form; query i sees
 // key j iff (q_groups[i] & k_groups[j]) != 0.  Words uint32 (groups_batch, L), groups_batch 1 (shared by the batch) or B; ksum = launch_key_tile_summary of
 // k_groups (attention_groups_summary_bytes).  The caller guarantees that every query sees at least one key (else that row's output is undefined).  q, k, vt

@@ -340,6 +340,7 @@ struct fmi_vae {
   bf16_t* zero = nullptr;
   std::map<std::string, Dest> names;
   MissingSet missing;
+  int mid_attention = 0;  // fmi_vae_set_mid_attention: 0 = the GEMM path with its (L, L) score matrix, 1 = attention_d512's flash kernel
   // workspace
   int wB = 0, wh = 0, ww = 0;
   DeviceBuffer ws;
@@ -412,9 +413,10 @@ int vae_workspace(fmi_vae* v, int B, int h, int w) {
     }
   }
   const size_t hw = (size_t)h * w, hwp = (hw + 63) / 64 * 64;  // run_attn pads the key dimension to the GEMM's K tile
-  if (c.mid_block_add_attention) max_act = std::max(max_act, (2 * hw + hwp) * (size_t)c.block_out_channels[c.n_blocks - 1]);  // q, k and V^T of one sample
+  const bool flash = v->mid_attention == 1;                    // q, k, v of ALL samples, unpadded, and no score matrix
+  if (c.mid_block_add_attention) max_act = std::max(max_act, (flash ? 3 * B * hw : 2 * hw + hwp) * (size_t)c.block_out_channels[c.n_blocks - 1]);  // q, k and V^T of one sample
   const size_t act_bytes = (max_act * 2 + 255) / 256 * 256;
-  const size_t score_bytes = c.mid_block_add_attention ? (hw * hwp * 2 + 255) / 256 * 256 : 256;
+  const size_t score_bytes = c.mid_block_add_attention && !flash ? (hw * hwp * 2 + 255) / 256 * 256 : 256;
   const int G = c.norm_num_groups;
   const size_t part_bytes = ((size_t)B * gn_max_chunks((int)((size_t)H * W)) * G * sizeof(float2) + 255) / 256 * 256;
   const size_t stat_bytes = ((size_t)B * G * sizeof(float2) + 255) / 256 * 256;
@@ -486,6 +488,20 @@ int run_attn(fmi_vae* v, const AttnW& a, int B, int H, int W, hipStream_t s) {
   const int C = a.q.cout, HW = H * W, HWp = (HW + 63) / 64 * 64;
   FMI_TRY(run_gn_trunk(v, a.gn, v->fx, v->bt1, nullptr, B, HW, 0, s));
   const float scale = (float)(1.0 / sqrt((double)C));
+  if (v->mid_attention == 1) {
+    // four launches for all B samples: GroupNorm (above), q | k | v (each with its own bias) as one grouped launch, the flash kernel, to_out + residual
+    const size_t n = (size_t)B * HW * C;
+    bf16_t *q = v->bt2, *k = v->bt2 + n, *vv = v->bt2 + 2 * n, *o = v->bsc;  // (B HW, C) each
+    GemmProblem p[3];
+    p[0] = conv_problem(v->bt1, a.q.w, a.q.b, nullptr, q, B, H, W, C, C, 1, 0, v->zero);
+    p[1] = conv_problem(v->bt1, a.k.w, a.k.b, nullptr, k, B, H, W, C, C, 1, 0, v->zero);
+    p[2] = conv_problem(v->bt1, a.v.w, a.v.b, nullptr, vv, B, H, W, C, C, 1, 0, v->zero);
+    FMI_TRY(launch_gemm(p, 3, s));
+    const int64_t st[8] = {C, (int64_t)HW * C, C, (int64_t)HW * C, C, (int64_t)HW * C, C, (int64_t)HW * C};
+    FMI_TRY(launch_attention_d512(q, k, vv, o, B, HW, HW, st, scale, s));
+    GemmProblem pf = conv_problem_f32(o, a.o.w, a.o.b, v->fx, true, v->ones, B, H, W, C, C, 1, 0, v->zero);
+    return launch_gemm(&pf, 1, s);
+  }
   for (int b = 0; b < B; ++b) {
     const bf16_t* xn = v->bt1 + (size_t)b * HW * C;
     bf16_t* q = v->bt2;                       // (HW, C)
@@ -788,6 +804,23 @@ extern "C" int fmi_vae_mid_attention(fmi_vae* v, const void* x_bf16_nhwc, int B,
   FMI_TRY(run_attn(v, AttnW{v->attn_gn, v->aq, v->ak, v->av, v->ao}, B, H, W, s));
   return trunk_to_bf16(v, (bf16_t*)out_bf16_nhwc, n, s);
 }
+
+extern "C" int fmi_vae_set_mid_attention(fmi_vae* v, int kind) {
+  if (!v) return fail(FMI_ERR_INVALID, "vae_set_mid_attention: null handle");
+  if (kind != 0 && kind != 1) return fail(FMI_ERR_INVALID, "vae_set_mid_attention: kind must be 0 or 1");
+  if (kind == 1 && v->cfg.block_out_channels[v->cfg.n_blocks - 1] != 512)
+    return fail(FMI_ERR_UNSUPPORTED, "vae_set_mid_attention: the flash kernel serves block_out_channels.last == 512, this VAE has " +
+                                         std::to_string(v->cfg.block_out_channels[v->cfg.n_blocks - 1]));
+  if (kind == v->mid_attention) return FMI_OK;
+  FMI_TRY(use_device_ordinal(v->device));
+  if (v->ws) {  // the other kind sizes the workspace differently: the next call allocates it again
+    FMI_HIP_TRY(hipDeviceSynchronize());
+    v->ws.reset();
+  }
+  v->mid_attention = kind;
+  return FMI_OK;
+}
+extern "C" int fmi_vae_get_mid_attention(const fmi_vae* v) { return v ? v->mid_attention : 0; }
 
 extern "C" int fmi_groupnorm_nhwc(const void* x_bf16, const float* weight, const float* bias, void* out_bf16, int B, int HW, int C, int groups, float eps,
                                   int fuse_silu, void* stream) {

@@ -956,6 +956,24 @@ class AutoEncoderKl:
     def shift_factor(self) -> float:
         return self.lib.fmi_vae_shift_factor(self.h)
 
+    MID_ATTENTION = {"default": 0, "flash": 1}
+
+    @classmethod
+    def mid_attention_kind(cls, name) -> int:
+        """"default" | "flash" -> fmi_vae_set_mid_attention's number; anything else raises by name."""
+        if name not in cls.MID_ATTENTION:
+            raise ValueError(f"vae_attention must be one of {sorted(cls.MID_ATTENTION)}, got {name!r}")
+        return cls.MID_ATTENTION[name]
+
+    def set_mid_attention(self, name) -> None:
+        """How this handle's mid-block AttnBlock runs (fmi_vae_set_mid_attention): "default" = GEMMs around a bf16 (L, L) score matrix, per
+        sample; "flash" = the d = 512 flash kernel of ops.sdpa_d512 over the whole batch, f32 scores, no score matrix (needs block_out_channels[-1] == 512)."""
+        L.check(self.lib.fmi_vae_set_mid_attention(self.h, self.mid_attention_kind(name)), self.lib)
+
+    def get_mid_attention(self) -> str:
+        kind = self.lib.fmi_vae_get_mid_attention(self.h)
+        return next(k for k, v in self.MID_ATTENTION.items() if v == kind)
+
     def mid_attention(self, x_nhwc):
         """AttnBlock::forward (vae.rs:95-111) of the decoder's mid block alone: (B,H,W,C) bf16 NHWC -> same shape."""
         x = x_nhwc.contiguous()

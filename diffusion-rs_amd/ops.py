@@ -50,6 +50,24 @@ def sdpa_d64(q, k, v, bias=None, causal=False, scale=None):
     return out
 
 
+def sdpa_d512(q, k, v, scale=None, out=None):
+    """fmi_sdpa_d512_bf16: softmax(q k^T * scale) v for one head of width 512.  q (B,Lq,512), k and v (B,Lk,512) bfloat16 device tensors with
+    unit stride along the channels, 16-byte aligned, row strides multiples of 8 (column windows of a fused projection are read where they lie); scale:
+    1 / sqrt(512) by default.  Returns (B,Lq,512) bfloat16 — a new tensor, or `out` (a view with the same rules) written in place."""
+    for name, t in (("q", q), ("k", k), ("v", v)) + ((("out", out),) if out is not None else ()):
+        if t.dtype != torch.bfloat16 or t.dim() != 3 or t.shape[2] != 512 or t.stride(2) != 1 or not t.is_cuda:
+            raise TypeError(f"sdpa_d512: {name} must be a bfloat16 device tensor (B,L,512) with contiguous channels, got {t.dtype} {tuple(t.shape)}")
+    B, Lq, _ = (int(x) for x in q.shape)
+    Lk = int(k.shape[1])
+    if tuple(k.shape) != (B, Lk, 512) or tuple(v.shape) != tuple(k.shape) or Lq < 1 or Lk < 1 or (out is not None and tuple(out.shape) != tuple(q.shape)):
+        raise ValueError(f"sdpa_d512: shapes q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit")
+    if out is None:
+        out = torch.empty((B, Lq, 512), dtype=torch.bfloat16, device=q.device)
+    strides = (C.c_int64 * 8)(*(int(t.stride(i)) for t in (q, k, v, out) for i in (1, 0)))
+    L.check(L.load().fmi_sdpa_d512_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Lq, Lk, strides, float(512 ** -0.5 if scale is None else scale), _stream()))
+    return out
+
+
 def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False, k_weights=None):
     """fmi_sdpa_groups_bf16: softmax(q k^T * scale + M) v at head dim 128 with token group masks — query i sees key j iff
     (q_groups[i] & k_groups[j]) != 0.  q (B,H,Lq,128), k and v (B,H,Lk,128) bfloat16 device tensors; q_groups (Bg,Lq) and k_groups (Bg,Lk) integers that fit

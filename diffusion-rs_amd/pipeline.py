@@ -502,17 +502,21 @@ class Pipeline:
     """== diffusion_rs_core::Pipeline (pipelines/mod.rs:110-270) for FluxPipeline."""
 
     def __init__(self, source: ModelSource, silent: bool = False, token: Optional[str] = None, revision: Optional[str] = None,
-                 offloading: Optional[Offloading] = None, dtype: ModelDType = ModelDType.Auto, *, device: int = 0, encoder_attention: str = "default"):
+                 offloading: Optional[Offloading] = None, dtype: ModelDType = ModelDType.Auto, *, device: int = 0, encoder_attention: str = "default",
+                 vae_attention: str = "default"):
         # encoder_attention: "default" | "mfma" — the attention kernel of the T5 / CLIP text / CLIP vision layers (DESIGN.md 4.22), a PROCESS-WIDE switch that
         # is set here, before any encoder exists
+        # vae_attention: "default" | "flash" — how the VAE's mid-block attention runs (DESIGN.md 4.25), set on this pipeline's VAE handle when it is created
         from . import ops
         ops.encoder_attention_kind(encoder_attention)  # (a bad name raises before anything is loaded)
+        F.AutoEncoderKl.mid_attention_kind(vae_attention)
         if dtype in (ModelDType.F16, ModelDType.F32):
             raise ValueError("this build computes in bf16 on MFMA (f32 accumulate); use ModelDType.Auto or BF16")
         self.silent = silent
         self.offloading = offloading
         self.device_index = device
         self.encoder_attention = encoder_attention
+        self.vae_attention = vae_attention
         ops.set_encoder_attention(encoder_attention)
         self.device = torch.device("cuda", device)
         self._lock = threading.Lock()  # Arc<Mutex<dyn ModelPipeline>>, pipelines/mod.rs:110-113
@@ -536,6 +540,7 @@ class Pipeline:
                 if rank == 0:
                     self._dit_loader()
                 self.vae = F.AutoEncoderKl(vcfg, device)
+                self.vae.set_mid_attention(vae_attention)
                 # (a channel-conditioned model encodes its control image at every request: the encoder's weights too — the decoder's keep their values)
                 synth.fill_vae_random_device(self.vae, seed=source.seed + 1, device=self.device, encoder=bool(self.flux.cond_channels))
                 if source.variant != "dev":
@@ -610,6 +615,7 @@ class Pipeline:
         vc = fl.read_json("vae/config.json")
         vcfg = dict(F.VAE_FLUX, **{k: vc[k] for k in F.VAE_FLUX if k in vc})
         self.vae = F.AutoEncoderKl(vcfg, self.device_index)
+        self.vae.set_mid_attention(self.vae_attention)
         loader.load_vae(self.vae, fl.tensors("vae"))
         # text_encoder (CLIP) / text_encoder_2 (T5) + their tokenizers (flux/mod.rs:74-127), when the checkpoint ships them
         if fl.has("text_encoder/config.json") and fl.has("text_encoder_2/config.json"):

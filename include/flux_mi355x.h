@@ -849,6 +849,13 @@ int fmi_vae_encode(fmi_vae*, const float* image, int B, int H, int W, const floa
  * buffers, C = block_out_channels.last; out = x + to_out(sdpa(q,k,v)(group_norm(x))).  Needs the
  * `decoder.*` tensors.  Used by the parity tests to check the block alone at production size. */
 int fmi_vae_mid_attention(fmi_vae*, const void* x_bf16_nhwc, int B, int H, int W, void* out_bf16_nhwc, void* stream);
+/* PER HANDLE: how the mid-block AttnBlock of decode / encode / fmi_vae_mid_attention runs.  0 (default): per sample, q | k GEMMs, a V^T GEMM, a bf16
+ * (L, L) score matrix in the workspace, a row softmax, P V, to_out.  1: the three projections of all samples in one grouped launch, the flash kernel of
+ * fmi_sdpa_d512_bf16 (f32 scores, no score matrix: the workspace holds nothing proportional to L^2), to_out over all samples — four launches a call.  The two
+ * agree to rounding, not bit for bit.  Kind 1 needs block_out_channels.last == 512 (FMI_ERR_UNSUPPORTED otherwise); any other kind is FMI_ERR_INVALID.  A
+ * change of kind releases the workspace (after a device synchronisation); the next call sizes it again. */
+int fmi_vae_set_mid_attention(fmi_vae*, int kind);
+int fmi_vae_get_mid_attention(const fmi_vae*);
 
 /* ------------------------------------------------------------------------------------
  * Text encoders — they run once per image in front of the denoise loop and
@@ -1302,6 +1309,13 @@ int fmi_sdpa_d64_bf16(const void* q, const void* k, const void* v, void* o, int 
  * tower keeps its d = 128 attention.  Set it before creating encoders and before starting work on other threads. */
 int fmi_set_encoder_attention(int kind);
 int fmi_get_encoder_attention(void);
+/* softmax(q k^T * scale) v for ONE head of width 512 (attention_d512.hip): the attention of the VAE's mid block without an (Lq, Lk) score
+ * matrix.  q (B, Lq, 512), k and v (B, Lk, 512), o (B, Lq, 512): bf16, token-major, 512 contiguous channels.  `strides` holds 8 element strides, {row, batch}
+ * of q, k, v, o in that order (so the operands may be column windows of one fused projection), or NULL for four contiguous tensors.  Pointers 16-byte
+ * aligned; row strides multiples of 8 and at least 512; batch strides non-negative multiples of 8 (0 shares an input across the batch), o's at least one
+ * sample; B <= 65535; any Lq, Lk >= 1; B == 0 or Lq == 0 does nothing.  Scores and the softmax are f32, P is rounded to bf16 once for P V, O is accumulated in
+ * f32 and rounded once.  Asynchronous on `stream`; allocates nothing, never synchronises; no atomics. */
+int fmi_sdpa_d512_bf16(const void* q, const void* k, const void* v, void* o, int B, int Lq, int Lk, const int64_t* strides, float scale, void* stream);
 /* Same with q and k as OCP e4m3 bytes (B,H,L,128): QK^T on the fp8 MFMA, softmax / P / V in f32 / bf16 as above.
  * `scale` must include 1 / (q scale * k scale).  The fp8-mode attention of fmi_flux_* (fmi_flux_set_fp8_attention). */
 int fmi_sdpa_fp8qk(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
