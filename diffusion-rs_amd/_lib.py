@@ -373,6 +373,8 @@ def _declare(lib):
     lib.fmi_flux_set_attention_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
     lib.fmi_sdpa_groups_weighted_bf16.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.fmi_flux_set_attention_key_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.fmi_sdpa_blocks_bf16.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.fmi_flux_set_attention_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.fmi_sdpa_d512_bf16.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.POINTER(C.c_int64), C.c_float, C.c_void_p]
     lib.fmi_vae_set_mid_attention.argtypes = [C.c_void_p, C.c_int]
     lib.fmi_vae_get_mid_attention.argtypes = [C.c_void_p]
@@ -448,7 +450,7 @@ EXPORTED = [
     "fmi_redux_create", "fmi_redux_destroy", "fmi_redux_set_tensor", "fmi_redux_missing_count", "fmi_redux_missing_name", "fmi_redux_size_in_bytes", "fmi_redux_forward",
     "fmi_pack_latents", "fmi_unpack_latents", "fmi_postprocess_u8",
     "fmi_preprocess_u8", "fmi_latent_mask", "fmi_encode_latents", "fmi_scale_noise", "fmi_latent_ids", "fmi_cfg_euler_step", "fmi_cast_cols_bf16", "fmi_mask_image", "fmi_fill_condition",
-    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_set_gemm_rows", "fmi_gemm_tile_rows", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_sdpa_d64_bf16", "fmi_sdpa_groups_bf16", "fmi_flux_set_attention_groups", "fmi_sdpa_groups_weighted_bf16", "fmi_flux_set_attention_key_weights", "fmi_set_encoder_attention", "fmi_get_encoder_attention", "fmi_layernorm_mod",
+    "fmi_randn", "fmi_philox_u32", "fmi_calculate_shift", "fmi_get_timesteps", "fmi_linear_bf16", "fmi_linear_bnb4_bf16", "fmi_linear_int8_bf16", "fmi_quantize_rows_fp8", "fmi_linear_fp8", "fmi_quantize_rows_i8", "fmi_linear_i8", "fmi_gemm_q8", "fmi_quantize_rows_i8_asym", "fmi_rowsum_i8", "fmi_quantize_rows_i8_scaled", "fmi_col_absmax", "fmi_gemm_i8_asym", "fmi_gemm_group", "fmi_splitk_resid_gate", "fmi_set_gemm_kernel", "fmi_set_gemm_rows", "fmi_gemm_tile_rows", "fmi_linear_q8_workspace_bytes", "fmi_linear_fp8_ws", "fmi_linear_i8_ws", "fmi_sdpa_bf16", "fmi_sdpa_fp8qk", "fmi_sdpa_workspace_bytes", "fmi_sdpa_bf16_ws", "fmi_sdpa_fp8qk_ws", "fmi_sdpa_fp8", "fmi_sdpa_fp8_ws", "fmi_set_attention_kernel", "fmi_sdpa_d64_bf16", "fmi_sdpa_groups_bf16", "fmi_flux_set_attention_groups", "fmi_sdpa_groups_weighted_bf16", "fmi_flux_set_attention_key_weights", "fmi_sdpa_blocks_bf16", "fmi_flux_set_attention_blocks", "fmi_set_encoder_attention", "fmi_get_encoder_attention", "fmi_layernorm_mod",
     "fmi_release_scratch", "fmi_timestep_embedding", "fmi_rope_table", "fmi_rmsnorm_rope",
     "fmi_groupnorm_nhwc", "fmi_conv2d_nhwc",
     "fmi_comm_probe", "fmi_comm_unique_id", "fmi_comm_create", "fmi_comm_destroy", "fmi_comm_rank", "fmi_comm_world_size", "fmi_comm_stats", "fmi_comm_all_to_all",

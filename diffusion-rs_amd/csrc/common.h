@@ -463,6 +463,15 @@ int launch_key_weight_log2(const float* w, int64_t n, float* lw, hipStream_t str
 int launch_key_tile_summary(const uint32_t* k_groups, const float* k_lw, int groups_batch, int Lk, uint32_t* ksum, hipStream_t stream);
 int launch_attention_groups(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const AttnOut& out, int B, int H, int Lq, int Lk, int Lkpad, float scale,
                             const uint32_t* q_groups, const uint32_t* k_groups, const uint32_t* ksum, const float* k_lw, int groups_batch, hipStream_t stream);
+// flash attention, d = 128, with a block-sparse mask (attention_blocks.hip): operands and output as launch_attention_groups'; the queries of
+// block i / 128 see the keys of the 64-key tiles cols[row_ptr[i / 128] .. row_ptr[i / 128 + 1]) and no others.  row_ptr (n_query_blocks + 1), cols (n_cols)
+// and order (n_query_blocks: the query blocks in launch order, attention_blocks_order) are DEVICE int32 arrays, one set for all samples and heads, taken as
+// they are.  n_query_blocks must be ceil(Lq / 128).  Asynchronous, no workspace.
+// attention_blocks_check_lists: the host-side contract of a list (row_ptr from 0, no empty row, tiles strictly ascending in [0, n_tiles)), `who` leads the message.
+int attention_blocks_check_lists(const int* row_ptr, const int* cols, int n_query_blocks, int n_tiles, const std::string& who);
+std::vector<int> attention_blocks_order(const int* row_ptr, int n_query_blocks);  // by descending list length, ties by ascending index
+int launch_attention_blocks(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const AttnOut& out, int B, int H, int Lq, int Lk, int Lkpad, float scale,
+                            const int* row_ptr, const int* cols, const int* order, int n_query_blocks, int n_cols, hipStream_t stream);
 // the attention of the T5 / CLIP text / CLIP vision layers (fmi_set_encoder_attention): 0 = encoder_common.h's lane-per-key kernel (default), 1 = attention_d64
 int encoder_attention_kind();
 void set_encoder_attention_kind(int kind);

@@ -155,6 +155,11 @@ struct fmi_flux {
   std::vector<uint32_t> grp_host;
   std::vector<float> kw_host;
   int grp_hB = 0, kw_hB = 0;
+  // block-sparse mask (fmi_flux_set_attention_blocks): row_ptr (blk_nqb + 1) | cols | order (blk_nqb) int32 in one device buffer, and the same
+  // arrays on the host.  Empty = no lists.  One mask per handle: never installed together with grp_words.
+  DeviceBuffer blk_lists;
+  std::vector<int> blk_host;
+  int blk_nqb = 0, blk_ncols = 0, blk_max_tile = 0;
   // 4-bit weights, large-M regime: per-layer streaming dequant into a reusable bf16 scratch
   // all denoise steps' modulation vectors (n_steps*B, n_mod) and vec (n_steps*B, D), see fmi_flux_denoise
   DeviceBuffer mod_steps, vec_steps, temb_steps, h1_steps;  // f32
@@ -1097,6 +1102,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
   if (m->fp8_attn == 2 && !sp && !m->attn_scales_valid) FMI_TRY(compute_attention_scales(m));
   const bool qk8_any = m->fp8_attn == 2 && !sp;  // opt-in: e4m3 q, k in front of QK^T whatever the block linears run on
   const uint32_t* const grp = m->grp_words.as<uint32_t>();  // the installed token group words (validate() has refused what they do not combine with), else null
+  const int* const blk = m->blk_lists.as<int>();            // the installed key-tile lists (never together with grp), else null
   const int BT = B * T;  // a8 / a8s rows: [txt (B*T) | img (B*S)]
   // The two ControlNet hooks, after double block i (single = false) or single block i: `rows` = where the block left the image rows, sample b at rows + b * bs.
   //   capture (a ControlNet handle)   sample = bf16(zero_linear(bf16(rows))): the rows cast into the free LayerNorm output buffer, then the existing GEMM launcher
@@ -1222,6 +1228,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       const float sc = qk8 ? att_scale / (m->q8_dbl[i] * m->k8_dbl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
       else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->kw_lw, m->grp_B, s));
+      else if (blk) FMI_TRY(launch_attention_blocks(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, blk, blk + m->blk_nqb + 1, blk + m->blk_nqb + 1 + m->blk_ncols, m->blk_nqb, m->blk_ncols, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_dbl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     if (m->two_streams && !fp8 && !sp && !m->profiling && !m->calib && !bw.proj[0].q_type && !bw.proj[1].q_type && !bw.mlp1[0].q_type && !bw.mlp1[1].q_type &&
@@ -1365,6 +1372,7 @@ int forward_core(fmi_flux* m, const fmi_flux_inputs* in, const EvalPlan& p, cons
       const float sc = qk8 ? att_scale / (m->q8_sgl[i] * m->k8_sgl[i]) : att_scale;
       if (sp) FMI_TRY(attention_sp(m, o, T, S, sc, s));
       else if (grp) FMI_TRY(launch_attention_groups(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, grp, grp, m->grp_sum, m->kw_lw, m->grp_B, s));
+      else if (blk) FMI_TRY(launch_attention_blocks(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, blk, blk + m->blk_nqb + 1, blk + m->blk_nqb + 1 + m->blk_ncols, m->blk_nqb, m->blk_ncols, s));
       else FMI_TRY(launch_attention_ex(w.Qh, w.Kh, w.Vt, o, B, H, L, L, w.Lpad, sc, m->attn_thr, s, qk8 ? 1 : 0, nullptr, 0, qk8 ? -m->n8_sgl[i] : ATT_NO_EXP2, m->attn_kind));
     }
     {
@@ -1448,6 +1456,16 @@ int validate(fmi_flux* m, const fmi_flux_inputs* in, const fmi_flux_denoise_opti
       return fail(FMI_ERR_INVALID, "flux: the installed " + what + " are for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ", this evaluation has T = " +
                                        std::to_string(in->T) + ", S = " + std::to_string(in->S));
     if (m->grp_B != 1 && m->grp_B != in->B) return fail(FMI_ERR_INVALID, "flux: the installed " + what + " are for a batch of " + std::to_string(m->grp_B));
+  }
+  if (m->blk_lists) {  // block-sparse mask: the lists were built for one joint length, and only the bf16 single-device attention has this form
+    FMI_TRY(groups_mode_check(m, "flux: attention blocks are installed (fmi_flux_set_attention_blocks): "));
+    if (p->R) return fail(FMI_ERR_UNSUPPORTED, "flux: attention blocks are not combined with a context (reference rows)");
+    if (o.cfg) return fail(FMI_ERR_UNSUPPORTED, "flux_denoise: attention blocks are not combined with true CFG");
+    const int L = in->T + in->S;
+    if ((L + 127) / 128 != m->blk_nqb || m->blk_max_tile >= (L + 63) / 64)
+      return fail(FMI_ERR_INVALID, "flux: the installed attention blocks are for " + std::to_string(m->blk_nqb) + " query blocks and key tiles up to " + std::to_string(m->blk_max_tile) +
+                                       ", this evaluation has T + S = " + std::to_string(L) + ": " + std::to_string((L + 127) / 128) + " query blocks, " + std::to_string((L + 63) / 64) +
+                                       " key tiles");
   }
   if (!m->cond && o.ctl) return fail(FMI_ERR_INVALID, "flux: a control was given to a model without conditioning channels (fmi_flux_create_cond)");
   if (m->cond) {  // a channel-conditioned model needs a control at every evaluation
@@ -2252,6 +2270,7 @@ extern "C" int fmi_flux_set_attention_groups(fmi_flux* m, const uint32_t* txt_gr
   if (!txt_groups || !img_groups || T < 1 || S < 1 || groups_batch < 1 || groups_batch > 8)
     return fail(FMI_ERR_INVALID, "flux_set_attention_groups: txt_groups (groups_batch, T) and img_groups (groups_batch, S) with T, S >= 1 and groups_batch 1 .. 8 (or all zero to clear)");
   FMI_TRY(groups_mode_check(m, who));
+  if (m->blk_lists) return fail(FMI_ERR_UNSUPPORTED, who + "attention blocks are installed (fmi_flux_set_attention_blocks): one mask per handle, clear them first");
   if (!m->kw_host.empty() && (T != m->grp_T || S != m->grp_S))
     return fail(FMI_ERR_INVALID, who + "key weights are installed for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ": clear them first");
   const int L = T + S;
@@ -2278,6 +2297,7 @@ extern "C" int fmi_flux_set_attention_key_weights(fmi_flux* m, const float* txt_
   if (!txt_weights || !img_weights || T < 1 || S < 1 || batch < 1 || batch > 8)
     return fail(FMI_ERR_INVALID, who + "txt_weights (batch, T) and img_weights (batch, S) with T, S >= 1 and batch 1 .. 8 (or all zero to clear)");
   FMI_TRY(groups_mode_check(m, who));
+  if (m->blk_lists) return fail(FMI_ERR_UNSUPPORTED, who + "attention blocks are installed (fmi_flux_set_attention_blocks): one mask per handle, clear them first");
   if (!m->grp_host.empty() && (T != m->grp_T || S != m->grp_S))
     return fail(FMI_ERR_INVALID, who + "attention groups are installed for T = " + std::to_string(m->grp_T) + ", S = " + std::to_string(m->grp_S) + ": clear them first");
   const int L = T + S;
@@ -2291,6 +2311,51 @@ extern "C" int fmi_flux_set_attention_key_weights(fmi_flux* m, const float* txt_
       wts[(size_t)b * L + i] = w;
     }
   return rebuild_attention_set(m, m->grp_host, m->grp_hB, std::move(wts), batch, T, S, who);
+}
+// Block-sparse mask of the joint attention: host CSR lists of key tiles per query block, validated in full, uploaded with their launch order
+// and kept.  The joint length is not known here: tiles are held to [0, 2 n_query_blocks), and validate() holds the largest one to the evaluation's tile count.
+// Host-blocking like the group words; nothing of the handle changes unless all of it succeeded.
+extern "C" int fmi_flux_set_attention_blocks(fmi_flux* m, const int32_t* row_ptr, const int32_t* cols, int n_query_blocks, const int32_t* order) {
+  if (!m) return fail(FMI_ERR_INVALID, "flux_set_attention_blocks: null handle");
+  FMI_TRY(use_device(m));
+  const std::string who = "flux_set_attention_blocks: ";
+  if ((!row_ptr && !cols && !order) || n_query_blocks == 0) {  // clear
+    if (m->blk_lists) FMI_HIP_TRY(hipDeviceSynchronize());
+    m->blk_lists.reset();
+    m->blk_host.clear();
+    m->blk_nqb = m->blk_ncols = m->blk_max_tile = 0;
+    return FMI_OK;
+  }
+  if (m->is_cn) return fail(FMI_ERR_UNSUPPORTED, who + "a ControlNet handle keeps its unmasked attention");
+  FMI_TRY(groups_mode_check(m, who));
+  if (m->grp_words)
+    return fail(FMI_ERR_UNSUPPORTED, who + (m->grp_host.empty() ? "attention key weights" : "attention groups") + " are installed: one mask per handle, clear them first");
+  const int nqb = n_query_blocks;
+  if (nqb < 0 || nqb > (1 << 20)) return fail(FMI_ERR_INVALID, who + "n_query_blocks must be 1 .. 2^20 (or 0 to clear)");
+  FMI_TRY(attention_blocks_check_lists(row_ptr, cols, nqb, 2 * nqb, who));
+  const int ncols = row_ptr[nqb];
+  std::vector<int> host(row_ptr, row_ptr + nqb + 1);
+  host.insert(host.end(), cols, cols + ncols);
+  if (order) {
+    std::vector<char> seen(nqb, 0);
+    for (int r = 0; r < nqb; ++r) {
+      if (order[r] < 0 || order[r] >= nqb || seen[order[r]]) return fail(FMI_ERR_INVALID, who + "order is not a permutation of the query blocks");
+      seen[order[r]] = 1;
+    }
+    host.insert(host.end(), order, order + nqb);
+  } else {
+    const std::vector<int> ord = attention_blocks_order(row_ptr, nqb);
+    host.insert(host.end(), ord.begin(), ord.end());
+  }
+  DeviceBuffer buf;
+  if (buf.alloc(host.size() * sizeof(int)) != hipSuccess) return fail(FMI_ERR_NOMEM, who + "hipMalloc failed");
+  FMI_HIP_TRY(hipMemcpy(buf.ptr, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+  FMI_HIP_TRY(hipDeviceSynchronize());  // the lists are complete, and nothing in flight reads the set this one replaces
+  m->blk_lists = std::move(buf);
+  m->blk_max_tile = *std::max_element(host.begin() + nqb + 1, host.begin() + nqb + 1 + ncols);
+  m->blk_host = std::move(host);
+  m->blk_nqb = nqb, m->blk_ncols = ncols;
+  return FMI_OK;
 }
 // fmi_flux_denoise's modulation precompute: 1 (default) one MFMA GEMM over all steps (when they are more than 4 rows), 0 f32 GEMV passes of 4 rows,
 // 2 the GEMM at any row count (how a 2-step full-size run is compared with the oracle THROUGH the 6.5 GB one-GEMM path)

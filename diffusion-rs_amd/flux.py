@@ -302,6 +302,62 @@ def check_ip_adapter_args(cfg: dict, adapter=None, img_shape=None, embeds_shape=
     return check_step_scales(step_scales, n_steps, "ip_adapter_step_scales")
 
 
+def local_attention_tiles(text_rows: int, h: int, w: int, radius: int):
+    """Key-tile lists of a local attention window for FluxModel.set_attention_blocks / ops.sdpa_blocks, pure numpy.  Tokens are [txt | img]:
+    text_rows text tokens, then the h x w packed-latent grid row-major.  A text token sees everything; the image token at (y, x) sees the text and every image
+    token with max(|dy|, |dx|) <= radius.  A query block (128 tokens) lists every key tile (64 tokens) that holds at least one token one of its tokens sees —
+    a superset of the window, and the list is what the kernel computes.  radius >= max(h, w) lists every tile.  Returns (row_ptr (nqb + 1,), cols) int32."""
+    T, h, w, r = int(text_rows), int(h), int(w), int(radius)
+    if T < 0 or h < 1 or w < 1 or r < 0:
+        raise ValueError(f"local_attention_tiles: text_rows >= 0, h, w >= 1 and radius >= 0, got {text_rows!r}, {h!r}, {w!r}, {radius!r}")
+    n_tokens = T + h * w
+    nqb, nt = -(-n_tokens // 128), -(-n_tokens // 64)
+    ys, xs = np.arange(h), np.arange(w)
+    y0, y1, x0, x1 = np.maximum(ys - r, 0), np.minimum(ys + r + 1, h), np.maximum(xs - r, 0), np.minimum(xs + r + 1, w)
+    row_ptr, cols = np.zeros(nqb + 1, np.int32), []
+    for b in range(nqb):
+        lo, hi = 128 * b, min(128 * b + 128, n_tokens)
+        if lo < T:  # a text token: everything
+            tiles = np.arange(nt, dtype=np.int32)
+        else:
+            # the block's queries on the grid, their count in every key's window off a summed-area table: a key is seen iff it is > 0
+            sat = np.zeros((h + 1, w + 1), np.int64)
+            qm = np.zeros(h * w, np.int64)
+            qm[lo - T:hi - T] = 1
+            sat[1:, 1:] = qm.reshape(h, w).cumsum(0).cumsum(1)
+            seen = (sat[y1][:, x1] - sat[y0][:, x1] - sat[y1][:, x0] + sat[y0][:, x0]) > 0
+            vis = np.zeros(nt * 64, bool)
+            vis[:T] = True
+            vis[T:n_tokens] = seen.ravel()
+            tiles = np.flatnonzero(vis.reshape(nt, 64).any(1)).astype(np.int32)
+        cols.append(tiles)
+        row_ptr[b + 1] = row_ptr[b] + tiles.size
+    return row_ptr, np.concatenate(cols)
+
+
+def attention_blocks_order(row_ptr):
+    """The launch order of the query blocks for ops.sdpa_blocks: by descending list length, ties by ascending index (what fmi_flux_set_attention_blocks
+    computes for a NULL order)."""
+    return np.argsort(-np.diff(np.asarray(row_ptr, np.int64)), kind="stable").astype(np.int32)
+
+
+def check_attention_blocks(row_ptr, cols, n_query_blocks: int, n_tiles: int):
+    """The contract of host key-tile lists, as fmi_flux_set_attention_blocks holds it: ValueError by name for a row_ptr that is not (n_query_blocks + 1,) from 0
+    to len(cols), an empty row, tiles outside [0, n_tiles) or not strictly ascending inside a row.  Returns (row_ptr, cols) as int32 arrays."""
+    rp, cl = np.asarray(row_ptr), np.asarray(cols)
+    if rp.shape != (n_query_blocks + 1,) or cl.ndim != 1 or int(rp[0]) != 0 or int(rp[-1]) != cl.size:
+        raise ValueError(f"attention blocks: row_ptr {rp.shape} must be ({n_query_blocks + 1},), start at 0 and end at len(cols) = {cl.size}")
+    if (np.diff(rp) <= 0).any():
+        raise ValueError(f"attention blocks: query block {int(np.flatnonzero(np.diff(rp) <= 0)[0])} lists no key tile")
+    if (cl < 0).any() or (cl >= n_tiles).any():
+        raise ValueError(f"attention blocks: a key tile outside [0, {n_tiles})")
+    inner = np.ones(cl.size, bool)
+    inner[rp[:-1]] = False  # the first entry of a row has no predecessor
+    if (np.diff(cl, prepend=cl[:1])[inner] <= 0).any():
+        raise ValueError("attention blocks: the key tiles of a query block must be strictly ascending")
+    return rp.astype(np.int32), cl.astype(np.int32)
+
+
 class FluxModel:
     def __init__(self, cfg: dict, device: int = 0):
         self.lib = L.load()
@@ -524,6 +580,19 @@ class FluxModel:
 
     def clear_attention_key_weights(self):
         L.check(self.lib.fmi_flux_set_attention_key_weights(self.h, None, None, 0, 0, 0), self.lib)
+
+    def set_attention_blocks(self, row_ptr, cols):
+        """A block-sparse mask for the joint attention of every block (fmi_flux_set_attention_blocks): the queries of block b (128 tokens of
+        [txt | img]) see the keys of the 64-key tiles cols[row_ptr[b] : row_ptr[b + 1]] and no others — local_attention_tiles builds such lists.  Rows strictly
+        ascending and non-empty; one set for every sample and head.  Not combined with group words or key weights.  Holds for every forward / denoise of this
+        joint length until clear_attention_blocks()."""
+        rp, cl = (np.ascontiguousarray(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a).astype(np.int32)) for a in (row_ptr, cols))
+        if rp.ndim != 1 or cl.ndim != 1 or rp.size < 2 or int(rp[-1]) != cl.size:
+            raise ValueError(f"set_attention_blocks: row_ptr {rp.shape} must be (n_query_blocks + 1,) and end at len(cols) = {cl.size}")
+        L.check(self.lib.fmi_flux_set_attention_blocks(self.h, C.c_void_p(rp.ctypes.data), C.c_void_p(cl.ctypes.data), rp.size - 1, None), self.lib)
+
+    def clear_attention_blocks(self):
+        L.check(self.lib.fmi_flux_set_attention_blocks(self.h, None, None, 0, None), self.lib)
 
     def set_split_k(self, on: bool):
         """Latency mode for launches of few rows (sequence-parallel shards): residual projections with fewer than 128 tiles are

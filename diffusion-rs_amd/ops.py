@@ -106,3 +106,40 @@ def sdpa_groups(q, k, v, q_groups, k_groups, scale=None, out_token_major=False, 
     L.check(L.load().fmi_sdpa_groups_weighted_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
                                                    1 if out_token_major else 0, _ptr(qg), _ptr(kg), _ptr(kw), Bg, _stream()))
     return out
+
+
+def sdpa_blocks(q, k, v, row_ptr, cols, scale=None, order=None, out_token_major=False):
+    """fmi_sdpa_blocks_bf16: softmax(q k^T * scale + M) v at head dim 128 with a block-sparse mask (DESIGN.md 4.26) — the queries of block i // 128 see the keys
+    of the 64-key tiles cols[row_ptr[i // 128] : row_ptr[i // 128 + 1]] and no others.  q (B,H,Lq,128), k and v (B,H,Lk,128) bfloat16 device tensors; row_ptr
+    (ceil(Lq / 128) + 1,) and cols integers, one set for all samples and heads: rows non-empty, tiles strictly ascending in [0, ceil(Lk / 64)).  order: the
+    launch order of the query blocks, a permutation (None: long lists first); it changes no bit of the result.  Host lists are checked and uploaded here;
+    device tensors (all of row_ptr, cols and order, int32) are taken as they are (no wait).  Returns (B,H,Lq,128), or (B,Lq,H*128) with out_token_major."""
+    import numpy as np
+
+    from .flux import attention_blocks_order, check_attention_blocks
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.bfloat16 or t.dim() != 4 or t.shape[3] != 128 or not t.is_cuda:
+            raise TypeError(f"sdpa_blocks: {name} must be a bfloat16 device tensor (B,H,L,128), got {t.dtype} {tuple(t.shape)}")
+    B, H, Lq, _ = (int(x) for x in q.shape)
+    Lk = int(k.shape[2])
+    if tuple(k.shape) != (B, H, Lk, 128) or tuple(v.shape) != tuple(k.shape) or Lq < 1 or Lk < 1:
+        raise ValueError(f"sdpa_blocks: shapes q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit")
+    nqb, nt = -(-Lq // 128), -(-Lk // 64)
+    lists = (row_ptr, cols) if order is None else (row_ptr, cols, order)
+    if all(isinstance(a, torch.Tensor) and a.is_cuda for a in lists):
+        if order is None:
+            raise ValueError("sdpa_blocks: device lists need a device order (the entry does not wait for the device to sort them)")
+        if any(a.dtype != torch.int32 or a.dim() != 1 for a in lists) or row_ptr.numel() != nqb + 1 or order.numel() != nqb:
+            raise ValueError(f"sdpa_blocks: device row_ptr ({nqb + 1},), cols and order ({nqb},) must be int32 vectors")
+        rp, cl, od = (a.contiguous() for a in lists)
+    else:
+        rp, cl = check_attention_blocks(*(a.cpu().numpy() if isinstance(a, torch.Tensor) else a for a in (row_ptr, cols)), nqb, nt)
+        od = attention_blocks_order(rp) if order is None else np.asarray(order.cpu() if isinstance(order, torch.Tensor) else order).astype(np.int32)
+        if od.shape != (nqb,) or not np.array_equal(np.sort(od), np.arange(nqb)):
+            raise ValueError(f"sdpa_blocks: order must be a permutation of the {nqb} query blocks")
+        rp, cl, od = (torch.from_numpy(np.ascontiguousarray(a)).to(q.device) for a in (rp, cl, od))
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    out = torch.empty((B, Lq, H * 128) if out_token_major else (B, H, Lq, 128), dtype=torch.bfloat16, device=q.device)
+    L.check(L.load().fmi_sdpa_blocks_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, Lq, Lk, 128, float(128 ** -0.5 if scale is None else scale),
+                                          1 if out_token_major else 0, _ptr(rp), _ptr(cl), _ptr(od), nqb, int(cl.numel()), _stream()))
+    return out

@@ -266,6 +266,22 @@ def check_key_weights_request(key_weights, height: int, width: int, present=(), 
                          f", got {rows['prompt'].shape}")
 
 
+REQUEST_NAMES["attention_window"] = "attention_window= (local attention)"
+
+
+def check_attention_window_request(radius, height: int, width: int, present=()):
+    """The attention_window= argument of a request, checked without a device.  ValueError by name: a radius that is no integer >= 0; a height or
+    width that is no multiple of 16; anything in `present` — what the request also carries and the window does not combine with: regions=, key_weights=,
+    reference=, true CFG, sequence parallelism, the fp8 / int8 modes ("option" names an option, "mode" a mode of the transformer)."""
+    name = REQUEST_NAMES["attention_window"]
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or radius < 0:
+        raise ValueError(f"{name} takes a radius in packed-latent tokens, an integer >= 0, got {radius!r}")
+    if height % 16 or width % 16:
+        raise ValueError(f"{name} needs height and width that are multiples of 16, got {height} x {width}")
+    for kind, what in present:
+        raise ValueError(f"{name} is not {'combined with ' if kind == 'option' else ''}{what}")
+
+
 def key_weight_rows(key_weights, text_rows: int, height: int, width: int, redux_rows: int = 0):
     """The weights of a checked key_weights= request as the model takes them, a pure host function: (txt (text_rows + redux_rows,), img (height / 16 * width / 16,))
     float32 for the text rows [T5 rows | Redux rows] and the image tokens in row-major order.  Whatever the dict does not name has the weight 1: the T5 rows
@@ -728,7 +744,7 @@ class Pipeline:
     def generate_tensor(self, prompts: List[str], params: DiffusionGenerationParams, *, embeddings=None, latents=None,
                         seed: Optional[int] = None, first_sample: int = 0, token_ids=None, sample_ids: Optional[Sequence[int]] = None,
                         image=None, strength: float = 1.0, mask=None, reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None,
-                        solver: Optional[str] = None, regions=None, key_weights=None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
+                        solver: Optional[str] = None, regions=None, key_weights=None, attention_window: Optional[int] = None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0,
                         control_image=None, control_mask=None, controlnet_image=None, controlnet_conditioning_scale: float = 1.0,
                         control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                         negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
@@ -825,7 +841,15 @@ class Pipeline:
         weights are installed on the transformer (FluxModel.set_attention_key_weights) before the first chunk and cleared when the last has run or one has raised.
         Combines with regions= (the weights act inside what the regions let a token see), Redux, image= / strength= / mask=, solver=, the step cache, a control, a
         ControlNet, an IP-Adapter (whose own attention is not weighted) and the quantised models; raises with reference=, true CFG, under sequence parallelism and
-        on an 8-bit transformer.  No weight is recommended: there are no real weights here to judge one."""
+        on an 8-bit transformer.  No weight is recommended: there are no real weights here to judge one.
+
+        Local attention (`attention_window=radius`): in every block an image token at (y, x) of the packed-latent grid attends to the text and to the
+        image tokens with max(|dy|, |dx|) <= radius, at tile granularity — flux.local_attention_tiles' lists (a superset of the window: whole 64-key tiles), which
+        the block-sparse attention kernel computes exactly; a text token sees everything.  ONE list set per request: the prompts are encoded before the request is
+        chunked, the lists are installed on the transformer (FluxModel.set_attention_blocks) before the first chunk and cleared when the last has run or one has
+        raised.  Combines with what key_weights= combines with, except key_weights= and regions= themselves (one mask per transformer); raises with reference=,
+        true CFG, under sequence parallelism and on an 8-bit transformer.  A capability, not a recommendation: no radius is suggested, there are no real weights
+        here to judge one."""
         rdx = self._redux_input(redux_image, redux_image_embeds, redux_scale)
         ipa = self._ip_adapter_input(ip_adapter_image_embeds, negative_ip_adapter_image_embeds, ip_adapter_scale, ip_adapter_start, ip_adapter_end,
                                      negative_prompt is not None or negative_embeddings is not None or negative_token_ids is not None,
@@ -855,6 +879,11 @@ class Pipeline:
                                                                      0 if regions is None else len(regions),
                                                                      [("option", REQUEST_NAMES[k]) for k, v in (("context", reference), ("true_cfg", neg)) if v is not None] +
                                                                      [("mode", REQUEST_NAMES[m]) for m in modes if m is not None])
+        lists = None  # the key-tile lists of a request with attention_window=, threaded as the words are
+        if attention_window is not None:
+            embeddings, token_ids, lists = self._attention_window_inputs(prompts, attention_window, params, embeddings, token_ids, 0 if rdx is None else int(rdx.tokens.shape[1]),
+                                                                         [("option", REQUEST_NAMES[k]) for k, v in (("regions", regions), ("key_weights", key_weights), ("context", reference), ("true_cfg", neg)) if v is not None] +
+                                                                         [("mode", REQUEST_NAMES[m]) for m in modes if m is not None])
         s = self._samples(prompts, params, strength, first_sample, sample_ids, embeddings=embeddings, token_ids=token_ids, latents=latents, image=image,
                           mask=mask, reference=reference)
         if not s.prompts:
@@ -870,9 +899,13 @@ class Pipeline:
                 self.flux.set_attention_groups(*words)
             if weights is not None:
                 self.flux.set_attention_key_weights(*weights)
+            if lists is not None:
+                self.flux.set_attention_blocks(*lists)
             outs = [chunk(s.take(idx), params, seed, strength, return_latents, cache_threshold, stats, **shared)
                     for idx in _index_sets(len(s.prompts), self.MAX_BATCH // 2 if neg is not None else self.MAX_BATCH, getattr(self, "_sp", None) is not None)]
         finally:
+            if lists is not None:
+                self.flux.clear_attention_blocks()
             if weights is not None:
                 self.flux.clear_attention_key_weights()
             if words is not None:
@@ -913,6 +946,18 @@ class Pipeline:
         T = int(embeddings[0].shape[-2])
         check_key_weights_request(key_weights, params.height, params.width, text_rows=T, prompt_rows=T // (n_regions + 1), redux_rows=redux_rows)
         return embeddings, None, key_weight_rows(key_weights, T, params.height, params.width, redux_rows)
+
+    def _attention_window_inputs(self, prompts, radius, params, embeddings, token_ids, redux_rows, present):
+        """(embeddings, token_ids, (row_ptr, cols)) of a request with attention_window=, checked first.  The lists are for ONE count of text rows, so
+        a request that came as text or token ids is encoded here, once, and goes on as the embeddings= request it now is (as one with key_weights= does)."""
+        check_attention_window_request(radius, params.height, params.width, present)
+        if not prompts:
+            return embeddings, token_ids, None
+        if embeddings is None:
+            with self._lock:
+                embeddings = self._chunk_embeddings(_Samples(list(prompts), list(range(len(prompts))), token_ids=token_ids), None)[:2]
+        T = int(embeddings[0].shape[-2]) + redux_rows
+        return embeddings, None, F.local_attention_tiles(T, params.height // 16, params.width // 16, int(radius))
 
     def _control(self, control_image, control_mask, params, *_) -> Optional[_Control]:
         """The control of a request, checked once and brought to its device form: None on a plain model, else the object its chunks share.  (Callers from before
@@ -1394,7 +1439,7 @@ class Pipeline:
 
     def forward(self, prompts: List[str], params: DiffusionGenerationParams, *, output: str = "png", image=None, strength: float = 1.0, mask=None,
                 reference=None, return_latents: bool = False, cache_threshold: Optional[float] = None, solver: Optional[str] = None, regions=None, key_weights=None,
-                negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
+                attention_window: Optional[int] = None, negative_prompt: Optional[str] = None, negative_embeddings=None, negative_token_ids=None, true_cfg_scale: float = 1.0, control_image=None, control_mask=None, controlnet_image=None,
                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0, ip_adapter_image_embeds=None,
                 negative_ip_adapter_image_embeds=None, ip_adapter_scale: float = 1.0, ip_adapter_start: float = 0.0, ip_adapter_end: float = 1.0,
                 ip_adapter_image=None, negative_ip_adapter_image=None, redux_image=None, redux_image_embeds=None, redux_scale: float = 1.0, **kw):
@@ -1416,7 +1461,8 @@ class Pipeline:
         (every rank loads the same Redux and encodes the picture itself).
         solver=: None | "euler" | "heun" | "dpmpp_2m", the integrator of the denoise loop, see generate_tensor.
         regions=: [(prompt, mask), ...], regional prompts, see generate_tensor — one region set per request, handed to every rank of a sharded batch unchanged.
-        key_weights=: dict(prompt=, redux=, image=), attention key weights, see generate_tensor — one set per request, handed to every rank likewise."""
+        key_weights=: dict(prompt=, redux=, image=), attention key weights, see generate_tensor — one set per request, handed to every rank likewise.
+        attention_window=: a radius in packed-latent tokens, local attention at tile granularity, see generate_tensor — one per request, handed to every rank likewise."""
         from . import dist as D
         rank, world = D.world()
         shared = dict(seed=kw.pop("seed", None), strength=strength, return_latents=return_latents, cache_threshold=cache_threshold)
@@ -1426,7 +1472,8 @@ class Pipeline:
                        control_guidance_end=control_guidance_end, ip_adapter_image_embeds=ip_adapter_image_embeds,
                        negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds, ip_adapter_scale=ip_adapter_scale, ip_adapter_start=ip_adapter_start,
                        ip_adapter_end=ip_adapter_end, ip_adapter_image=ip_adapter_image, negative_ip_adapter_image=negative_ip_adapter_image,
-                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver, regions=regions, key_weights=key_weights)
+                       redux_image=redux_image, redux_image_embeds=redux_image_embeds, redux_scale=redux_scale, solver=solver, regions=regions, key_weights=key_weights,
+                       attention_window=attention_window)
         defaults = inspect.signature(Pipeline.generate_tensor).parameters
         for name, value in options.items():  # only what differs from generate_tensor's own default: any other request makes exactly the call it always made
             default = defaults[name].default

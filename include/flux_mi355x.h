@@ -61,6 +61,7 @@ extern "C" {
  *                  fmi_heun_predict, fmi_heun_correct, fmi_dpmpp_2m_step, fmi_dpmpp_2m_coefficients.
  *   Then, still 6: joint attention with token group masks at d = 128 (regional prompts) — fmi_sdpa_groups_bf16, fmi_flux_set_attention_groups.
  *   Then, still 6: per-key weights in that attention (weighted prompts, Redux strength) — fmi_sdpa_groups_weighted_bf16, fmi_flux_set_attention_key_weights.
+ *   Then, still 6: block-sparse joint attention at d = 128 (key-tile lists, local windows) — fmi_sdpa_blocks_bf16, fmi_flux_set_attention_blocks.
  * Additions only: a host bound against version 3 keeps working. */
 #define FMI_ABI_VERSION 6
 
@@ -402,6 +403,18 @@ int fmi_flux_set_attention_groups(fmi_flux*, const uint32_t* txt_groups, int T, 
  * are installed): a ControlNet handle, the fp8 / int8 modes, fp8 attention operands, sequence parallelism, the split-K latency mode, a context, true CFG; an
  * evaluation of another (T, S) is FMI_ERR_INVALID.  With nothing installed every entry issues exactly the launches it always did. */
 int fmi_flux_set_attention_key_weights(fmi_flux*, const float* txt_weights, const float* img_weights, int T, int S, int batch);
+/* PER HANDLE: a block-sparse mask for the joint attention of every double and single block (attention_blocks.hip) — local windows, sliding
+ * tiles.  The joint sequence [txt | img] of L tokens is cut into query blocks of 128 and key tiles of 64; row_ptr (n_query_blocks + 1) and cols
+ * (row_ptr[n_query_blocks]) are HOST int32 arrays in CSR form: the queries of block b see the keys of the tiles cols[row_ptr[b] .. row_ptr[b + 1]) and no
+ * others.  One set serves every sample and head.  order (n_query_blocks) is the launch order of the query blocks, a permutation; NULL computes it (descending
+ * list length, ties by ascending index).  The arrays are validated, copied to the device and kept (the call waits for the device); NULL, NULL, 0, NULL clears.
+ * FMI_ERR_INVALID, and nothing is installed or removed: row_ptr[0] != 0, an empty row, tiles of a row not strictly ascending, a tile outside
+ * [0, 2 n_query_blocks), an order that is no permutation.  An evaluation is FMI_ERR_INVALID before any launch unless ceil((T + S) / 128) == n_query_blocks
+ * and every listed tile lies below ceil((T + S) / 64).  Refused like the group words (FMI_ERR_UNSUPPORTED, by this call and by an evaluation while lists are
+ * installed): a ControlNet handle, the fp8 / int8 modes, fp8 attention operands, sequence parallelism, the split-K latency mode, a context, true CFG.  One
+ * mask per handle: refused while group words or key weights are installed, and those two setters are refused while lists are.  With nothing installed every
+ * entry issues exactly the launches it always did. */
+int fmi_flux_set_attention_blocks(fmi_flux*, const int32_t* row_ptr, const int32_t* cols, int n_query_blocks, const int32_t* order);
 /* The weights as flat device buffers — the unit of the multi-GPU broadcast (north star: "RCCL broadcast of
  * weights").  Rank 0 loads a checkpoint, fmi_flux_state_export() fills a small host blob saying which
  * arenas exist and how every fused matrix is stored (pass blob_host = NULL to query *len); the other ranks
@@ -1268,6 +1281,15 @@ int fmi_sdpa_groups_bf16(const void* q, const void* k, const void* v, void* o, i
  * is built per call behind the summaries in the per-stream block; asynchronous on `stream`. */
 int fmi_sdpa_groups_weighted_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int d, float scale, int out_token_major,
                                   const uint32_t* q_groups, const uint32_t* k_groups, const float* k_weights, int groups_batch, void* stream);
+/* fmi_sdpa_bf16 with a block-sparse mask (attention_blocks.hip): the queries of block i / 128 see the keys of the 64-key tiles
+ * cols[row_ptr[i / 128] .. row_ptr[i / 128 + 1]) and no others; keys past Lk in the last tile are hidden by index.  row_ptr (n_query_blocks + 1), cols (n_cols)
+ * and order (n_query_blocks: the query blocks in launch order, long lists first) are DEVICE int32 arrays, one set for all samples and heads.  Checked here:
+ * n_query_blocks == ceil(Lq / 128), n_cols in n_query_blocks .. n_query_blocks * ceil(Lk / 64), alignment, d == 128 (else FMI_ERR_UNSUPPORTED), Lk <= 131072.
+ * The list CONTENTS are taken as they are (the entry never waits for the device): tiles strictly ascending in [0, ceil(Lk / 64)), no empty row, order a
+ * permutation; anything else computes an undefined output (indices are clamped into the problem, nothing is read outside the operands).  Every listed tile
+ * is processed as fmi_sdpa_groups_bf16 processes a fully visible one: for a list that group words can express the two outputs are equal bit for bit. */
+int fmi_sdpa_blocks_bf16(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int d, float scale, int out_token_major,
+                         const int32_t* row_ptr, const int32_t* cols, const int32_t* order, int n_query_blocks, int n_cols, void* stream);
 /* The attention kernels read V transposed (B,H,128,Lk rounded up to 64) with the kv index permuted inside groups of 16; the op-level
  * entry points build that image first.  fmi_sdpa_bf16 / fmi_sdpa_fp8qk keep it in a grow-only block the library holds per (device, stream)
  * — calls on one stream run in order and share it; a call allocates only when it needs more than any earlier call on that stream (once,
